@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- candidate-net evals/hour of the population-fitness hot path on MI355X.
 
-One "step" = one pass of the hot path over one generation:
-``compute_objectives_and_constraints(population)`` for pop=40 candidates
-(BASELINE.json configs[1]: "pop=40 gen=1 fitness eval on 1xMI355X: HIP MFCC +
+The workload is the hot path over generations of pop=40 candidates,
+``compute_objectives_and_constraints(population)``; one timed "step" = one
+candidate evaluation of it, the metric's own unit (BASELINE.json configs[1]: "pop=40 gen=1 fitness eval on 1xMI355X: HIP MFCC +
 tiny-CNN train, GSC 10-keyword"; reference call site nsga_penalty.py:613/670,
 the loop itself :418-442).  Inputs are synthetic 1 s @ 16 kHz clips (SURVEY.md
 §8d), turned into standardised [N,101,40] log-mel features by the HIP front end
@@ -18,18 +18,32 @@ the hard synthetic set and reports the epochs distribution next to evals/hour.
   python bench.py --gpus N --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Wall-clock budget.  One generation of the headline workload (pop 40, N=30 000,
-101x40, fp32, E=10) takes about five minutes on one MI355X, so K and W are UPPER BOUNDS
-under ``--budget-s`` (seconds from process start by which the JSON line must be
-out; default 450 for the driver's 600 s limit):
-* warm-up = up to W light untimed passes: the whole population for one epoch on
-  a few hundred clips -- loads every kernel family and fills the buffer cache;
-* the timed region holds as many WHOLE generations as fit (>= 1, <= K): the
-  first one is timed, then ``plan_steps`` decides how many more fit.  The line
-  reports ``steps`` = generations actually timed and ``steps_requested`` = K;
-* the CPU-baseline leg runs before the timed region on a bounded sample
-  (``--cpu-baseline-s``) and the isolated-kernel leg is a few launches, so
-  ``roofline`` and ``cpu_baseline`` are always in the line.
+Steps.  The steps form one stream: the seeded population in ``stream_order``
+(every prefix carries about its share of a generation's closed-form work; the
+candidates' work spans ~100x), repeated.  K steps are the stream's first K
+candidates, as one call per whole generation and one call on the first K mod pop,
+so K = pop (the default) is one whole generation; ``ms_per_step`` = wall time of
+the timed calls / K.  Warm-up: one light pass (the whole population for one epoch
+on a few hundred clips -- loads every kernel family and fills the buffer cache),
+then W untimed steps, the stream's first W candidates on an evaluator of their
+own (W = 0: none of it).
+
+Plain run vs ``--full``.  A plain run sets up, warms up, times exactly K steps
+and prints the line; ``roofline`` and ``cpu_baseline`` are not measured
+(``roofline`` is null).  ``--full`` adds the legs that take runs of
+their own: the CPU baseline before the timed region on a bounded sample
+(``--cpu-baseline-s``), and after it the lone-heaviest-candidate leg and the
+isolated-kernel launches behind ``roofline``.  ``--dump-outputs DIR`` writes what
+the timed calls returned (``objs.npy``, ``cv.npy``; float64, one row per step, the
+last step last); the inputs are seeded, so the same arguments give the same inputs.
+
+Wall-clock budget (opt-in).  One generation of the headline workload (pop 40,
+N=30 000, 101x40, fp32, E=10) takes about five minutes on one MI355X.  With
+``--budget-s S`` (seconds from process start by which the JSON line must be out)
+K is an UPPER BOUND: the first call is timed, then ``plan_steps`` decides how
+many more whole calls fit, and the ``--full`` legs are skipped when they would
+not fit.  The line reports ``steps`` = candidate evaluations actually timed and
+``steps_requested`` = K.
 
 N > 1: ``--gpus N`` without a torchrun environment starts the N ranks itself
 (child ``python -m torch.distributed.run``, before any GPU call in the parent)
@@ -39,9 +53,9 @@ dynamic``) or LPT buckets (``static``) and the objective vectors are exchanged
 with one RCCL all_gather per step.  The population is fixed at --pop (strong
 scaling: the reference shards ONE generation); --weak multiplies it by N.
 
-Rank 0 prints ONE JSON line (contract in the task statement), including
-``roofline`` and, at N=1, ``cpu_baseline`` (the torch-CPU oracle timed on this
-box's host cores on a bounded sample).  ``roofline.achieved`` is a WORK RATE: the
+Rank 0 prints ONE JSON line (contract in the task statement); with ``--full`` it
+includes ``roofline`` and, at N=1, ``cpu_baseline`` (the torch-CPU oracle timed on
+this box's host cores on a bounded sample).  ``roofline.achieved`` is a WORK RATE: the
 dominant MFMA kernel's algorithmic FLOPs / its HIP-event duration with the
 heaviest candidate of the population training ALONE (one launching thread, no CU
 sharing) inside this run, right after the timed region; the same kernel's in-job
@@ -190,7 +204,7 @@ def cpu_baseline_rate(pop, variant, classes, T, F, X_sample, y_sample, budget_s=
 
 
 def plan_steps(first_step_s, now_s, deadline_s, steps_requested, safety=1.05):
-    """How many whole generations the timed region holds in total (>= 1, <= steps_requested), given that the first
+    """How many whole calls (generations) the timed region holds in total (>= 1, <= steps_requested), given that the first
     took ``first_step_s`` and ended at ``now_s``; later ones are assumed to take ``safety`` x as long and must
     finish by ``deadline_s`` (all on one clock)."""
     if steps_requested <= 1:
@@ -198,6 +212,35 @@ def plan_steps(first_step_s, now_s, deadline_s, steps_requested, safety=1.05):
     per = max(first_step_s * safety, 1e-9)
     more = int(max(0.0, deadline_s - now_s) // per)
     return 1 + max(0, min(steps_requested - 1, more))
+
+
+def stream_order(work):
+    """Population order of the step stream: greedily, the candidate that keeps the running sum of the closed-form work
+    closest to k x the mean after k steps (ties: lowest index).  Candidates' work spans ~100x, so without this the first
+    K steps (and the W warm-up steps) could carry a third or three times their share of a generation; with it every
+    prefix carries about its share, and a step costs about the same for any K."""
+    left, order, acc = list(range(len(work))), [], 0.0
+    mean = sum(work) / max(len(work), 1)
+    for k in range(1, len(work) + 1):
+        i = min(left, key=lambda j: (abs(acc + work[j] - k * mean), j))
+        order.append(i)
+        left.remove(i)
+        acc += work[i]
+    return order
+
+
+def call_sizes(steps, n_pop):
+    """K steps (candidate evaluations) as calls of compute_objectives_and_constraints on the first candidates of the
+    step stream: whole generations, then one partial generation for the remainder."""
+    return [n_pop] * (steps // n_pop) + ([steps % n_pop] if steps % n_pop else [])
+
+
+def dump_outputs(out_dir, res):
+    """What ``compute_objectives_and_constraints`` returned for the K timed steps, in step order (the last one last):
+    ``objs.npy`` [K, n_objs] float64 (nsga_penalty: -accuracy, model size MB, FPR) and ``cv.npy`` [K] float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "objs.npy"), np.asarray([r["objs"] for r in res], dtype=np.float64))
+    np.save(os.path.join(out_dir, "cv.npy"), np.asarray([r["CV"] for r in res], dtype=np.float64))
 
 
 def _free_port():
@@ -312,11 +355,20 @@ def main(argv=None, t_origin=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2, help="upper bound on timed generations (whole generations that fit --budget-s)")
-    ap.add_argument("--warmup", type=int, default=1, help="upper bound on light untimed warm-up passes (each: the population, 1 epoch, a few hundred clips)")
-    ap.add_argument("--budget-s", type=float, default=450.0,
-                    help="seconds from process start by which the JSON line must be printed (driver limit 600 s)")
-    ap.add_argument("--cpu-baseline-s", type=float, default=15.0, help="wall-clock cap of the CPU-baseline leg")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps = candidate evaluations: the first K candidates of the population, repeated (exactly K; under "
+                         "--budget-s an upper bound in whole calls). Default: one generation (--pop candidates)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed warm-up steps, the same kind as the timed ones (after one light pass "
+                                                          "that loads every kernel family; 0: no warm-up)")
+    ap.add_argument("--budget-s", type=float, default=None,
+                    help="opt-in: seconds from process start by which the JSON line must be printed; --steps becomes an upper bound "
+                         "(the whole calls that fit) and the --full legs are skipped when they would not fit (default: no budget)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (N=1), the lone-heaviest-candidate "
+                         "and isolated-kernel legs behind `roofline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed: DIR/objs.npy [K, 3], DIR/cv.npy [K] (float64)")
+    ap.add_argument("--cpu-baseline-s", type=float, default=15.0, help="wall-clock cap of the CPU-baseline leg (--full)")
     ap.add_argument("--pop", type=int, default=40)
     ap.add_argument("--clips", type=int, default=30000, help="synthetic clips (80/10/10 split)")
     ap.add_argument("--epochs", type=int, default=10, help="fixed epoch budget per candidate (SURVEY section 8d: E_fixed = 10, early stopping off)")
@@ -346,6 +398,12 @@ def main(argv=None, t_origin=None):
     ap.add_argument("--stub", action="store_true", help="harness rehearsal without a GPU (tests only): StubEvaluator, gloo; never a measurement")
     ap.add_argument("--stub-ms-per-gflop", type=float, default=2.0)
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    if args.lone_only and args.dump_outputs:
+        ap.error("--dump-outputs needs the timed generations; --lone-only runs none")
     if args.stub:
         args.backend = "gloo"
 
@@ -359,6 +417,10 @@ def main(argv=None, t_origin=None):
 
     def since_start():
         return time.perf_counter() - t_origin
+
+    def over_budget(margin_s):
+        """past --budget-s less margin_s (never without a budget)"""
+        return args.budget_s is not None and since_start() > args.budget_s - margin_s
 
     # under rocprofv3 the tool library crashes on hipExtLaunchKernelGGL (ROCm 7.2): fall back to plain
     # hipEventRecord pairs around the sampled launches there (slightly inflated when streams overlap)
@@ -438,10 +500,12 @@ def main(argv=None, t_origin=None):
     rng = random.Random(args.seed)          # initialize_population: random.choice per gene (nsga_penalty.py:402-415)
     pop = [G.random_hparams(rng) for _ in range(n_pop)]
     genes = [G.normalize_hparams(hp) for hp in pop]
+    order = stream_order([G.eval_flops(g, variant, args.classes, T, F, n_tr, n_va, args.epochs, 0) for g in genes])
+    stream_pop, stream_genes = [pop[i] for i in order], [genes[i] for i in order]
 
     # ---- CPU baseline FIRST (rank 0, N=1): bounded, and no timeout later in the run can lose it
     cpu_rate = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub and not args.lone_only:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub and not args.lone_only:
         phase["name"] = "cpu baseline"
         xs, ys = Xtr[:64].cpu().numpy(), ytr[:64].cpu().numpy()
         cpu_rate = cpu_baseline_rate(genes, variant, args.classes, T, F, xs, ys, budget_s=args.cpu_baseline_s)
@@ -457,9 +521,12 @@ def main(argv=None, t_origin=None):
                                 schedule=args.schedule)
     if args.stub:
         ev = StubEvaluator(cfg, variant, args.classes, T, F, args.stub_ms_per_gflop)
-        ev_warm = ev
+        ev_warm = ev_steps_warm = ev
     else:
         ev = PopulationEvaluator(Xtr, ytr, Xva, yva, cfg)
+        # warm-up steps: the same steps as the timed ones, on an evaluator of their own (the timed steps' seeds do not
+        # depend on W)
+        ev_steps_warm = PopulationEvaluator(Xtr, ytr, Xva, yva, cfg)
         # warm-up evaluator: same population, one epoch on the first few hundred clips (every kernel family of every
         # candidate gets loaded and its buffers enter the cache; buffer sizes depend on the batch, not on N)
         from dataclasses import replace
@@ -518,7 +585,7 @@ def main(argv=None, t_origin=None):
             for i in range(n_steps):
                 net.train_step(Xtr, ytr, None, row0=((i + 3) * cfg.batch) % max(rows, 1), B=cfg.batch)
                 done += 1
-                if since_start() > args.budget_s - 6.0 and not args.lone_only:
+                if over_budget(6.0) and not args.lone_only:
                     break
             t_l = time.perf_counter() - t_l
         ent = read_profile()
@@ -531,36 +598,47 @@ def main(argv=None, t_origin=None):
 
     warm_done = 0
     first = elapsed = 0.0
-    steps, res, n_ranks_seen = 0, [], world
-    epochs_run = []
+    steps, res, evaluated, epochs_run, n_ranks_seen = 0, [], [], [], world
     if not args.lone_only:
         phase["name"] = "warm-up"
-        for _ in range(min(args.warmup, 2)):
-            ev_warm.compute_objectives_and_constraints(pop)
-            warm_done += 1
+        if args.warmup > 0:
+            ev_warm.compute_objectives_and_constraints(pop)         # light pass: loads every kernel family of the population
+            for n in call_sizes(args.warmup, n_pop):
+                ev_steps_warm.compute_objectives_and_constraints(stream_pop[:n])
+                warm_done += n
         if not args.stub:
             _lib.check(_lib.lib().cmoop_profile_reset())
 
-        # ---- timed region: barrier + sync on both sides, whole generations, MAX over ranks
-        reserve_s = min(30.0, 0.1 * args.budget_s)         # roofline legs + JSON after the timed region
-        deadline = args.budget_s - reserve_s
-        phase["name"] = "timed generation 1"
+        # ---- timed region: barrier + sync on both sides, MAX over ranks.  One step = one candidate evaluation; the K steps
+        # are the first K candidates of the population repeated, one call per (partial) generation
+        calls = call_sizes(n_pop if args.steps is None else args.steps, n_pop)
+
+        def timed_call(n):
+            res.extend(ev.compute_objectives_and_constraints(stream_pop[:n]))
+            evaluated.extend(stream_genes[:n])
+            epochs_run.extend(list(getattr(ev, "last_epochs_run", []) or []))
+
+        phase["name"] = f"timed call 1 of {len(calls)}"
         barrier()
         t0 = time.perf_counter()
-        res = ev.compute_objectives_and_constraints(pop)
+        timed_call(calls[0])
         if not args.stub:
             torch.cuda.synchronize()
         first = agree(time.perf_counter() - t0, dist.ReduceOp.MAX if world > 1 else None)
-        # the reference protocol's epochs are data-dependent: its line is ONE generation
-        want = 1 if reference_protocol else max(1, args.steps)
-        steps = int(agree(plan_steps(first, since_start(), deadline, want), dist.ReduceOp.MIN if world > 1 else None))
-        for k in range(1, steps):
-            phase["name"] = f"timed generation {k + 1} of {steps}"
-            res = ev.compute_objectives_and_constraints(pop)
+        n_calls = len(calls)
+        if args.budget_s is not None:
+            reserve_s = min(30.0, 0.1 * args.budget_s)     # roofline legs + JSON after the timed region
+            deadline = args.budget_s - reserve_s
+            n_calls = int(agree(plan_steps(first, since_start(), deadline, n_calls), dist.ReduceOp.MIN if world > 1 else None))
+        for k in range(1, n_calls):
+            phase["name"] = f"timed call {k + 1} of {n_calls}"
+            timed_call(calls[k])
         barrier()
         elapsed = agree(time.perf_counter() - t0, dist.ReduceOp.MAX if world > 1 else None)
+        steps = len(res)
         n_ranks_seen = int(agree(1.0, dist.ReduceOp.SUM)) if world > 1 else 1
-        epochs_run = list(getattr(ev, "last_epochs_run", []) or [])
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, res)
     phase["name"] = "roofline legs"
 
     # ---- multi-GPU diagnostics of the last generation (outside the timed region): one small all_gather
@@ -586,10 +664,10 @@ def main(argv=None, t_origin=None):
     # ---- roofline
     roofline = None
     lone = None
-    if not args.stub:
+    if not args.stub and (args.full or args.lone_only):
         L = _lib.lib()
         entries = read_profile() if not args.lone_only else []
-        if rank == 0 and args.lone_steps > 0 and since_start() < args.budget_s - 15.0 or args.lone_only:
+        if rank == 0 and args.lone_steps > 0 and not over_budget(15.0) or args.lone_only:
             lone, lone_entries = lone_candidate_leg(args.lone_steps)
         else:
             lone_entries = []
@@ -634,7 +712,7 @@ def main(argv=None, t_origin=None):
         if rank == 0 and roofline is not None and not args.lone_only:
             iso = []
             for (B, H, W, Cin, Cout, KS) in ((64, 101, 40, 64, 64, 5), (64, 51, 20, 128, 128, 5), (64, 26, 10, 256, 256, 5)):
-                if since_start() > args.budget_s - 8.0:
+                if over_budget(8.0):
                     break
                 x = torch.randn((B, H, W, Cin), device=dev)
                 w = torch.randn((Cout, KS, KS, Cin), device=dev) * 0.05
@@ -664,18 +742,17 @@ def main(argv=None, t_origin=None):
             print(json.dumps(line), flush=True)
             stop_hb.set()
             return 0
-        evals = n_pop * steps
-        value = evals / (elapsed / 3600.0)
+        value = steps / (elapsed / 3600.0)                 # one step = one candidate evaluation
         # FLOPs actually executed: the read-out pass reuses the last epoch's validation pass (same weights, deterministic
         # inference), so P = 0 extra inference passes here (the reference runs predict() again: P = 1)
-        ep_of = epochs_run if (reference_protocol and len(epochs_run) == len(genes)) else [args.epochs] * len(genes)
-        work = sum(G.eval_flops(g, variant, args.classes, T, F, n_tr, n_va, int(e), 0) for g, e in zip(genes, ep_of)) * steps
+        ep_of = epochs_run if (reference_protocol and len(epochs_run) == len(evaluated)) else [args.epochs] * len(evaluated)
+        work = sum(G.eval_flops(g, variant, args.classes, T, F, n_tr, n_va, int(e), 0) for g, e in zip(evaluated, ep_of))
         if roofline is not None:   # chip-level view: all algorithmic conv/dense FLOPs of the step / wall time
             roofline["aggregate_timed_region"] = {"achieved": round(work / elapsed / 1e12 / world, 2),
                                                   "frac": round(work / elapsed / 1e12 / world / peak, 4),
                                                   "note": "all algorithmic conv+dense FLOPs of the timed region / wall time / GPUs"}
         if cpu_rate is not None:
-            cpu_line = cpu_baseline_line(genes, variant, args.classes, T, F, n_tr, n_va,
+            cpu_line = cpu_baseline_line(evaluated, variant, args.classes, T, F, n_tr, n_va,
                                          [int(e) for e in ep_of] if reference_protocol else args.epochs, *cpu_rate)
         per_rank = [0] * world
         for r_ in getattr(ev, "last_rank_of", []) or []:
@@ -688,15 +765,16 @@ def main(argv=None, t_origin=None):
             proto_txt = f"tiny-CNN train E={args.epochs} fixed epochs (SURVEY 8d throughput protocol, early stopping off)"
         line = {
             "metric": "candidate-net evals/hour (pop=40, GSC-v2)", "value": round(value, 2), "unit": "candidate-evals/hour",
-            "n_gpus": world, "n_ranks_seen": n_ranks_seen, "steps": steps, "steps_requested": args.steps, "warmup": warm_done,
+            "n_gpus": world, "n_ranks_seen": n_ranks_seen, "steps": steps, "steps_requested": sum(calls), "warmup": warm_done,
             "warmup_requested": args.warmup,
-            "warmup_kind": "light pass: whole population, 1 epoch on the first 512 train / 512 val clips (loads every kernel, fills the buffer cache)",
+            "warmup_kind": "one light pass (whole population, 1 epoch on the first 512 train / 512 val clips: loads every kernel, fills the "
+                           "buffer cache), then W untimed steps: the step stream's first W candidates on an evaluator of their own",
             "ms_per_step": round(elapsed * 1e3 / steps, 2),
             "higher_is_better": True, "scaling": "weak" if args.weak else "strong", "vs_baseline": None,
             "dtype": {"fp32": "f32", "bf16x3": "f32 operands as 3 x bf16 (opt-in bf16x3 mode, fp32-accurate)",
                       "bf16": "bf16 operands, f32 accumulate (opt-in bf16-train mode)"}[args.gemm_mode],
             "data": "stub (harness rehearsal, NOT a measurement)" if args.stub else "synthetic",
-            "config": {"workload": f"pop={n_pop} gen=1 fitness eval (topology {args.variant}, {args.classes} classes): "
+            "config": {"workload": f"pop={n_pop} fitness eval, one step = one candidate evaluation (topology {args.variant}, {args.classes} classes): "
                                    f"HIP log-mel front end (untimed) + {proto_txt}, "
                                    f"batch 64, N_train={n_tr}, N_val={n_va}, features {T}x{F}",
                        "protocol": args.protocol,

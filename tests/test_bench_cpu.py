@@ -62,31 +62,78 @@ def test_plan_steps_fits_whole_generations_into_the_budget():
 
 
 def test_driver_argv_resolves_to_a_bounded_run_with_a_stub_evaluator():
-    """The driver's exact flags (--gpus 1 --steps 20 --warmup 5) under a small budget: main()'s budgeting logic with the
-    stub evaluator (no GPU, no kernels) times >= 1 whole generation, fewer than requested, and prints ONE JSON line in
-    time.  A stub line is marked as such: it is a harness rehearsal, never a measurement."""
+    """20 generations' worth of steps (one step = one candidate evaluation: --steps 800 at pop 40) with --warmup 5 under a
+    small budget: main()'s budgeting logic with the stub evaluator (no GPU, no kernels) times >= 1 whole generation, fewer
+    than requested, and prints ONE JSON line in time.  A stub line is marked as such: it is a harness rehearsal, never a
+    measurement."""
     buf = io.StringIO()
     t0 = time.perf_counter()
     with redirect_stdout(buf):
-        rc = bench.main(["--gpus", "1", "--steps", "20", "--warmup", "5", "--stub", "--stub-ms-per-gflop", "100",
+        rc = bench.main(["--gpus", "1", "--steps", "800", "--warmup", "5", "--stub", "--stub-ms-per-gflop", "100",
                          "--budget-s", "6"], t_origin=time.perf_counter())
     wall = time.perf_counter() - t0
     assert rc == 0 and wall < 7.5, wall            # budget 6 s; the slack absorbs sleep jitter of the stub on a loaded host
     lines = [ln for ln in buf.getvalue().splitlines() if ln.strip()]
     assert len(lines) == 1
     d = json.loads(lines[0])
-    assert d["steps_requested"] == 20 and 1 <= d["steps"] < 20 and d["warmup"] <= 2 and d["warmup_requested"] == 5
+    assert d["steps_requested"] == 800 and 40 <= d["steps"] < 800 and d["steps"] % 40 == 0
+    assert d["warmup"] == d["warmup_requested"] == 5                    # warm-up steps are whole steps, never cut
     assert d["n_gpus"] == 1 and d["n_ranks_seen"] == 1 and "stub" in d["data"]
-    assert abs(d["value"] - 40 * d["steps"] / (d["ms_per_step"] * d["steps"] / 3.6e6)) < 1e-3 * d["value"]
+    assert abs(d["value"] - d["steps"] / (d["ms_per_step"] * d["steps"] / 3.6e6)) < 1e-3 * d["value"]
     assert d["ms_per_step"] * d["steps"] / 1e3 <= wall
     assert d["budget"]["seconds_since_start_at_print"] <= 7.5
+
+
+def test_plain_run_times_exactly_the_requested_steps_and_dumps_the_last_outputs(tmp_path):
+    """Without --budget-s, --steps is the number of timed candidate evaluations: 47 at pop 40 = the whole population, then
+    its first 7 candidates.  A plain run measures no CPU-baseline or roofline legs (those are --full); --dump-outputs writes
+    what the timed steps returned, one row per step, and the same arguments give the same population, so two runs dump the
+    same arrays (the stub's objectives are closed forms of the gene).  The steps follow the balanced stream order."""
+    import random
+    dumps = []
+    for name in ("a", "b"):
+        buf = io.StringIO()
+        with redirect_stdout(buf):
+            rc = bench.main(["--gpus", "1", "--steps", "47", "--warmup", "1", "--stub", "--stub-ms-per-gflop", "20",
+                             "--dump-outputs", str(tmp_path / name)], t_origin=time.perf_counter())
+        assert rc == 0
+        lines = [ln for ln in buf.getvalue().splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == d["steps_requested"] == 47 and d["warmup"] == 1 and d["budget"]["budget_s"] is None
+        assert d["roofline"] is None and "cpu_baseline" not in d
+        assert abs(d["value"] - 3.6e6 / d["ms_per_step"]) < (1e-3 + 0.005 / d["ms_per_step"]) * d["value"]   # ms_per_step: 2 decimals
+        objs, cv = np.load(tmp_path / name / "objs.npy"), np.load(tmp_path / name / "cv.npy")
+        assert objs.shape == (47, 3) and objs.dtype == np.float64 and cv.shape == (47,) and cv.dtype == np.float64
+        dumps.append((objs, cv))
+    rng = random.Random(0)
+    genes = [G.normalize_hparams(G.random_hparams(rng)) for _ in range(40)]
+    order = bench.stream_order([G.eval_flops(g, G.VARIANT_A, 10, 101, 40, 24000, 3000, 10, 0) for g in genes])
+    stream = [genes[i] for i in order]
+    assert dumps[0][0][:, 1].tolist() == [G.model_size_mb(g, G.VARIANT_A, 10) for g in stream + stream[:7]]   # step order
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_step_stream_prefixes_carry_their_share_of_the_work():
+    """The headline population's candidates differ ~100x in work; in stream order every prefix of k >= 1 steps carries
+    k x the mean within 10 %, so K timed steps and W warm-up steps each cost about K and W average steps."""
+    import random
+    rng = random.Random(0)
+    genes = [G.normalize_hparams(G.random_hparams(rng)) for _ in range(40)]
+    work = np.array([G.eval_flops(g, G.VARIANT_A, 10, 101, 40, 24000, 3000, 10, 0) for g in genes])
+    assert work.max() / work.min() > 50
+    order = bench.stream_order(list(work))
+    assert sorted(order) == list(range(40))
+    prefix = np.cumsum(work[order]) / (np.arange(1, 41) * work.mean())
+    assert np.all(np.abs(prefix - 1.0) < 0.1), prefix.round(3)
+    assert bench.call_sizes(47, 40) == [40, 7] and bench.call_sizes(80, 40) == [40, 40] and bench.call_sizes(3, 40) == [3]
 
 
 def test_gpus_2_starts_two_ranks_itself_and_reports_them():
     """`python bench.py --gpus 2` WITHOUT torchrun must start the two ranks itself (VERDICT r1: it silently ran one);
     rehearsed with the stub evaluator over gloo.  Both ranks must have evaluated candidates (shared queue)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--steps", "120", "--warmup", "1",
                         "--budget-s", "30", "--stub-ms-per-gflop", "6"], capture_output=True, text=True, timeout=240, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -109,7 +156,7 @@ def test_gpus_8_rehearsal_deals_five_candidates_to_every_rank():
     every rank runs min(8, ceil(40 / 8)) = 5 workers and gets exactly the 5 candidates of the deterministic deal
     (evaluator.queue_plan) -- no burst of fetch-adds decides who trains the large ones."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--stub", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--stub", "--steps", "80", "--warmup", "1",
                         "--budget-s", "60", "--stub-ms-per-gflop", "6"], capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

@@ -7,7 +7,7 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$ROOT/gpurun_out/${1:-prof_headline}"; shift
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$OUT/raw" -o trace --output-format csv -- python3 "$ROOT/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --budget-s 1100 "$@" > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+rocprofv3 --kernel-trace --stats -d "$OUT/raw" -o trace --output-format csv -- python3 "$ROOT/bench.py" --full --warmup 1 --no-cpu-baseline --budget-s 1100 "$@" > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 rc=$?
 echo "rocprofv3 rc=$rc" | tee -a "$OUT/bench.err"
 TRACE=$(find "$OUT/raw" -name '*kernel_trace.csv' | head -1)

@@ -6,7 +6,7 @@ OUT=gpurun_out/$1; shift
 mkdir -p "$OUT"
 for q in default 2 8 1; do
     if [ "$q" = default ]; then unset GPU_MAX_HW_QUEUES; else export GPU_MAX_HW_QUEUES=$q; fi
-    python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@" > "$OUT/queues_$q.json" 2> "$OUT/queues_$q.err"
+    python3 bench.py --full --warmup 1 --no-cpu-baseline "$@" > "$OUT/queues_$q.json" 2> "$OUT/queues_$q.err"
     python3 - "$OUT/queues_$q.json" "$q" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
