@@ -311,6 +311,57 @@ def test_every_launch_variant_of_every_gene_has_a_gpu_parity_case():
     assert {"halo_fwd_kernel<5, 128, 64, 2, false>+stats", "halo_fwd_kernel<3, 256, 32, 4, false>", "halo_fwd_kernel<5, 128, 64, 2, true>+bal", "halo_wgrad_kernel<5, 10>+slabs", "halo_wgrad_kernel<3, 5>+slabs"} <= covered
 
 
+def test_geometry_sweep_covers_every_variant_and_edge_of_the_domain():
+    """The launch choice moves with the batch (a partial last batch is any of 1..63, inference launches have their own) and
+    with the feature size the caller hands over.  Re-enumerate that domain with the host-only plan function -- every conv
+    layer of every gene, both topologies, at SWEEP_FEATURE_SIZES; forward (with / without the statistics epilogue) at batch
+    1..64 and {100, 255, 256}, dgrad and wgrad at 1..64 -- and name for every launch its variant and its edge flags
+    (tools/launch_variants.py::edge_flags).  tests/test_gpu_geometry_sweep.py compares every case of SWEEP_CONVS bit for
+    bit with float64, so the list must
+    (1) witness every (variant, flag) pair of the domain at two different (H, W), or at one where the domain has only one
+        (PRODUCTION_CONVS count for the `any` flag);
+    (2) stay inside the bounds that make the integer regime exact, checked from the shape alone;
+    (3) hold no case larger than the largest production shape.
+    A new tile choice or a widened halo eligibility fails here, on the CPU, until a sweep case is added."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import launch_variants as LV
+    from _production_shapes import PRODUCTION_CONVS
+    from _sweep_shapes import SWEEP_BWD_BATCHES, SWEEP_CONVS, SWEEP_FEATURE_SIZES, SWEEP_FWD_BATCHES, integer_regime_is_exact
+    assert SWEEP_FEATURE_SIZES == [(101, 40), (101, 13), (128, 128), (41, 20), (21, 12), (11, 40), (26, 40)]
+    assert SWEEP_FWD_BATCHES == tuple(range(1, 65)) + (100, 255, 256) and SWEEP_BWD_BATCHES == tuple(range(1, 65))
+    dom = LV.sweep_domain(SWEEP_FEATURE_SIZES, SWEEP_FWD_BATCHES, SWEEP_BWD_BATCHES)
+    variants = {v for v, _ in dom}
+    assert len(variants) >= 60 and len(dom) >= 250, (len(variants), len(dom))      # a plan change that collapses the domain is noticed
+    assert {f for _, f in dom} == set(LV.FLAGS)
+
+    def macs(c):
+        B, H, W, Ci, Co, KS, st = c
+        return B * (-(-H // st)) * (-(-W // st)) * Ci * Co * KS * KS
+    assert len(set(SWEEP_CONVS)) == len(SWEEP_CONVS)
+    cap = max(macs(c) for c in PRODUCTION_CONVS)
+    assert not [c for c in SWEEP_CONVS if macs(c) > cap]                                                    # (3)
+    assert not [c for c in list(SWEEP_CONVS) + list(PRODUCTION_CONVS) if not integer_regime_is_exact(*c)]   # (2)
+    seen = {}
+    for c in SWEEP_CONVS:
+        for pr in LV.pairs_of(*c, backward=c[0] in SWEEP_BWD_BATCHES):      # as the domain: an inference batch witnesses forward launches
+            seen.setdefault(pr, set()).add(c[1:3])
+    for c in PRODUCTION_CONVS:
+        seen.setdefault((LV.plan(0, *c, 1), "any"), set()).add(c[1:3])
+        seen.setdefault((LV.plan(0, *c, 0), "any"), set()).add(c[1:3])
+        seen.setdefault((LV.plan(1, *c), "any"), set()).add(c[1:3])
+        seen.setdefault((LV.plan(2, *c), "any"), set()).add(c[1:3])
+    missing = {}
+    for pr, by_hw in sorted(dom.items()):                                                                   # (1)
+        need, have = min(2, len(by_hw)), seen.get(pr, set())
+        if len(have) < need:
+            missing[pr] = f"{len(have)} of {need} (H, W); the domain has e.g. {sorted(min(v) for hw, v in by_hw.items() if hw not in have)[:3]}"
+    assert not missing, "(variant, flag) pairs of the domain without enough sweep cases:\n" + "\n".join(f"{k}: {v}" for k, v in missing.items())
+    # the variants the benchmark's three batches never reach are in the domain (and therefore in the sweep)
+    assert {"igemm_fwd_kernel<128, 128, 32, 2, 0>+bal+tab", "igemm_fwd_kernel<128, 16, 16, 4, 0>+sk+tab", "igemm_wgrad_kernel<128, 128, 32>+tab",
+            "igemm_wgrad_kernel<128, 64, 32>+tab", "halo_wgrad_kernel<3, 5>", "halo_wgrad_kernel<5, 10>"} <= variants
+
+
 def test_halo_tile_bound_covers_every_tile_of_every_geometry():
     """The halo-tiled direct convolution sizes its LDS image and its per-thread staging slots from a closed-form bound on the
     rows a flat 128- / 256-pixel tile can span (image boundaries add gap rows).  cmoop_halo_tile_check walks every tile of
