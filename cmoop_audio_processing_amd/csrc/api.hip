@@ -3,6 +3,7 @@
 #include "net.h"
 
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -47,6 +48,39 @@ static const FrontendTables* frontend_tables_for_current_device() {
     std::lock_guard<std::mutex> l(mu);
     if (!tables[dev]) tables[dev] = frontend_tables_create(FrontendCfg());
     return tables[dev];
+}
+
+// tables of the configurable front end: a bounded map keyed by (device, config), oldest entry dropped first.  A caller
+// keeps its shared_ptr for the length of its launch, so dropping an entry never frees tables another thread is using.
+static std::shared_ptr<const FrontendTables> frontend_tables_for(const FrontendCfg& c) {
+    struct Entry { int dev; FrontendCfg cfg; std::shared_ptr<const FrontendTables> t; };
+    constexpr size_t CAP = 16;
+    static std::mutex mu;
+    static std::vector<Entry>& cache = *new std::vector<Entry>;   // never destroyed: no hipFree after the runtime has shut down
+    int dev = 0;
+    CMOOP_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> l(mu);
+    for (const Entry& e : cache)
+        if (e.dev == dev && frontend_cfg_equal(e.cfg, c)) return e.t;
+    std::shared_ptr<const FrontendTables> t(frontend_tables_create(c), [dev](const FrontendTables* p) {
+        int cur = 0;
+        if (hipGetDevice(&cur) == hipSuccess && cur != dev) hipSetDevice(dev);
+        frontend_tables_destroy(const_cast<FrontendTables*>(p));
+        if (cur != dev) hipSetDevice(cur);
+    });
+    if (cache.size() >= CAP) cache.erase(cache.begin());
+    cache.push_back(Entry{dev, c, t});
+    return t;
+}
+
+static FrontendCfg to_frontend_cfg(const cmoop_frontend_config* c) {
+    CMOOP_REQUIRE(c != nullptr, "front end config is NULL");
+    FrontendCfg f;
+    f.sr = c->sr; f.n_fft = c->n_fft; f.win = c->win; f.hop = c->hop; f.n_mels = c->n_mels; f.scale = c->scale;
+    f.db_ref_max = c->db_ref_max != 0; f.fmin = c->fmin; f.fmax = c->fmax; f.log_eps = c->log_eps; f.db_amin = c->db_amin;
+    f.top_db = c->top_db;
+    frontend_check(f);
+    return f;
 }
 
 static NetConfig to_cfg(const cmoop_config* c) {
@@ -231,6 +265,72 @@ int cmoop_logmel(const float* wav_dev, int64_t n_clips, int32_t n_samples, float
         hipStream_t s = lib_stream();
         launch_logmel(wav_dev, n_clips, n_samples, out_dev, tables, s);
         CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_frontend_config_default(cmoop_frontend_config* c) {
+    return guard([&] {
+        CMOOP_REQUIRE(c != nullptr, "front end config is NULL");
+        const FrontendCfg f;
+        c->sr = f.sr; c->n_fft = f.n_fft; c->win = f.win; c->hop = f.hop; c->n_mels = f.n_mels; c->scale = f.scale;
+        c->db_ref_max = f.db_ref_max; c->fmin = f.fmin; c->fmax = f.fmax; c->log_eps = f.log_eps; c->db_amin = f.db_amin;
+        c->top_db = f.top_db;
+    });
+}
+
+int cmoop_frontend_check(const cmoop_frontend_config* c) {
+    return guard([&] { to_frontend_cfg(c); });
+}
+
+int cmoop_frontend_frames(const cmoop_frontend_config* c, int32_t n_samples, int32_t* T) {
+    return guard([&] {
+        CMOOP_REQUIRE(T != nullptr, "frontend_frames: NULL output");
+        *T = frontend_frames(to_frontend_cfg(c), n_samples);
+    });
+}
+
+int cmoop_frontend_mel_basis(const cmoop_frontend_config* c, float* out_host) {
+    return guard([&] {
+        CMOOP_REQUIRE(out_host != nullptr, "frontend_mel_basis: NULL output");
+        const FrontendCfg f = to_frontend_cfg(c);
+        const FrontendHostTables h = frontend_host_tables(f);
+        const int nb = f.n_fft / 2 + 1;
+        std::memset(out_host, 0, (size_t)f.n_mels * nb * sizeof(float));
+        for (int i = 0; i < f.n_mels; ++i)
+            for (int k = 0; k < h.count[i]; ++k) out_host[(size_t)i * nb + h.first_bin[i] + k] = h.melw[h.start[i] + k];
+    });
+}
+
+int cmoop_logmel_ex(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_clips, int32_t n_samples, float* out_dev) {
+    return guard([&] {
+        const FrontendCfg f = to_frontend_cfg(c);
+        CMOOP_REQUIRE(n_samples >= 1 && n_clips >= 0, "logmel_ex: n_samples >= 1, n_clips >= 0");
+        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+        hipStream_t s = lib_stream();
+        launch_logmel(wav_dev, n_clips, n_samples, out_dev, tables.get(), s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_logmel_ex_time(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_clips, int32_t n_samples, float* out_dev,
+                         int32_t iters, double* avg_ms) {
+    return guard([&] {
+        const FrontendCfg f = to_frontend_cfg(c);
+        CMOOP_REQUIRE(n_samples >= 1 && n_clips >= 1 && iters >= 1 && avg_ms, "logmel_ex_time: n_samples, n_clips, iters >= 1");
+        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+        hipStream_t s = lib_stream();
+        for (int i = 0; i < 3; ++i) launch_logmel(wav_dev, n_clips, n_samples, out_dev, tables.get(), s);
+        hipEvent_t a, b;
+        CMOOP_HIP(hipEventCreate(&a));
+        CMOOP_HIP(hipEventCreate(&b));
+        CMOOP_HIP(hipEventRecord(a, s));
+        for (int i = 0; i < iters; ++i) launch_logmel(wav_dev, n_clips, n_samples, out_dev, tables.get(), s);
+        CMOOP_HIP(hipEventRecord(b, s));
+        CMOOP_HIP(hipEventSynchronize(b));
+        float ms = 0.f;
+        CMOOP_HIP(hipEventElapsedTime(&ms, a, b));
+        hipEventDestroy(a); hipEventDestroy(b);
+        *avg_ms = (double)ms / iters;
     });
 }
 

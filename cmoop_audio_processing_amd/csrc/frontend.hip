@@ -1,4 +1,6 @@
-// Audio front end: framing -> Hann -> 512-pt real FFT -> |.|^2 -> sparse Slaney mel -> log.
+// Audio front end: framing -> Hann -> real FFT -> |.|^2 -> sparse Slaney mel -> log (or dB).
+// logmel_kernel is the 512-point kernel of the build-defined configuration; logmel_ex_kernel (further down) serves
+// n_fft 256-2048, up to 128 bands and the dB scale.
 // North-star addition beneath the reference's data loader (the reference ships
 // pre-extracted features only: nsga_penalty.py:64-71); the
 // algorithm restates librosa.feature.melspectrogram (requirements.txt:80) and is
@@ -21,16 +23,20 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 namespace cmoop {
 
 struct FrontendTables {
     FrontendCfg cfg;
-    float* tw = nullptr;       // [n_fft/2][2] cos, -sin
+    bool general = false;      // tables of logmel_ex_kernel (below) instead of logmel_kernel's
+    float* tw = nullptr;       // logmel_kernel: [n_fft/2][2] cos, -sin ; general: the whole circle, [n_fft][2]
     float* win = nullptr;      // [n_fft] padded periodic Hann
     float* melw = nullptr;     // sparse weights, band after band
-    int* meltask = nullptr;    // [64][3] first bin, count, weight offset of each lane's task ; then [64] second task of a band or -1
+    int* meltask = nullptr;    // logmel_kernel: [64][3] first bin, count, weight offset of each lane's task ; then [64] second task of a band or -1
+                               // general: [n_mels][3] first bin, count, weight offset of each band
     int nnz = 0;
 };
 
@@ -43,30 +49,54 @@ static double mel_to_hz(double m) {
     return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
 }
 
-FrontendTables* frontend_tables_create(const FrontendCfg& c) {
-    CMOOP_REQUIRE(c.n_fft == 512, "front end: n_fft must be 512");
-    CMOOP_REQUIRE(c.n_mels >= 1 && c.n_mels <= 64 && c.win <= c.n_fft, "front end: n_mels <= 64, win <= n_fft");
-    auto* t = new FrontendTables;
-    t->cfg = c;
+bool frontend_cfg_equal(const FrontendCfg& a, const FrontendCfg& b) {
+    return a.sr == b.sr && a.n_fft == b.n_fft && a.win == b.win && a.hop == b.hop && a.n_mels == b.n_mels && a.fmin == b.fmin &&
+           a.fmax == b.fmax && a.log_eps == b.log_eps && a.scale == b.scale && a.db_ref_max == b.db_ref_max &&
+           a.db_amin == b.db_amin && a.top_db == b.top_db;
+}
+
+bool frontend_uses_fixed_kernel(const FrontendCfg& c) { return c.n_fft == 512 && c.n_mels <= 64 && c.scale == 0; }
+
+void frontend_check(const FrontendCfg& c) {
+    auto fail = [](const char* field, const std::string& rule) { throw std::runtime_error(std::string("front end config: ") + field + " " + rule); };
+    if (c.sr <= 0) fail("sr", "must be positive (got " + std::to_string(c.sr) + ")");
+    if (c.n_fft != 256 && c.n_fft != 512 && c.n_fft != 1024 && c.n_fft != 2048)
+        fail("n_fft", "must be 256, 512, 1024 or 2048 (got " + std::to_string(c.n_fft) + ")");
+    if (c.win < 1 || c.win > c.n_fft) fail("win", "must lie in 1..n_fft (got " + std::to_string(c.win) + ")");
+    if (c.hop < 1) fail("hop", "must be at least 1 (got " + std::to_string(c.hop) + ")");
+    if (c.n_mels < 1 || c.n_mels > FRONTEND_MAX_MELS) fail("n_mels", "must lie in 1..128 (got " + std::to_string(c.n_mels) + ")");
+    if (!(c.fmax <= 0.5f * (float)c.sr)) fail("fmax", "must not exceed sr/2 (got " + std::to_string(c.fmax) + ")");
+    if (!(c.fmin >= 0.f && c.fmin < c.fmax)) fail("fmin", "must satisfy 0 <= fmin < fmax (got " + std::to_string(c.fmin) + ")");
+    if (c.scale != 0 && c.scale != 1) fail("scale", "must be 0 (log) or 1 (dB)");
+    if (c.scale == 0 && !(c.log_eps > 0.f)) fail("log_eps", "must be positive");
+    if (c.scale == 1 && !(c.db_amin > 0.f)) fail("db_amin", "must be positive");
+    if (c.scale == 1 && !(c.top_db == c.top_db)) fail("top_db", "must be a number (negative: no clip)");
+}
+
+// Host-side tables in double, stored as float: twiddles exp(-2 pi i k / n_fft) for the whole circle, the periodic Hann
+// of win points centred in n_fft, and the Slaney mel basis (librosa.filters.mel, norm='slaney') as one run of
+// consecutive non-zero weights per band.  Nothing here touches the GPU.
+FrontendHostTables frontend_host_tables(const FrontendCfg& c) {
+    frontend_check(c);
+    FrontendHostTables h;
     const int half = c.n_fft / 2, nb = half + 1;
-    std::vector<float> tw(2 * half), win(c.n_fft, 0.f);
-    for (int k = 0; k < half; ++k) {
+    h.tw.resize(2 * c.n_fft);
+    h.win.assign(c.n_fft, 0.f);
+    for (int k = 0; k < c.n_fft; ++k) {
         const double a = -2.0 * M_PI * k / c.n_fft;
-        tw[2 * k] = (float)std::cos(a);
-        tw[2 * k + 1] = (float)std::sin(a);
+        h.tw[2 * k] = (float)std::cos(a);
+        h.tw[2 * k + 1] = (float)std::sin(a);
     }
     const int lpad = (c.n_fft - c.win) / 2;
-    for (int n = 0; n < c.win; ++n) win[lpad + n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / c.win));
-    // Slaney mel basis, norm='slaney' (librosa.filters.mel)
+    for (int n = 0; n < c.win; ++n) h.win[lpad + n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / c.win));
     std::vector<double> mel_f(c.n_mels + 2);
     const double m_lo = hz_to_mel(c.fmin), m_hi = hz_to_mel(c.fmax);
     for (int i = 0; i < c.n_mels + 2; ++i) mel_f[i] = mel_to_hz(m_lo + (m_hi - m_lo) * i / (c.n_mels + 1));
-    std::vector<float> w;
-    std::vector<int> first_bin(c.n_mels), count(c.n_mels), start(c.n_mels);
+    h.first_bin.resize(c.n_mels); h.count.resize(c.n_mels); h.start.resize(c.n_mels);
     for (int i = 0; i < c.n_mels; ++i) {
         const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
         int first = -1, cnt = 0;
-        start[i] = (int)w.size();
+        h.start[i] = (int)h.melw.size();
         for (int b = 0; b < nb; ++b) {
             const double f = (double)b * (c.sr / 2.0) / half;
             const double lower = (f - mel_f[i]) / (mel_f[i + 1] - mel_f[i]);
@@ -74,41 +104,67 @@ FrontendTables* frontend_tables_create(const FrontendCfg& c) {
             const double v = std::max(0.0, std::min(lower, upper)) * enorm;
             if (v > 0.0) {
                 if (first < 0) first = b;
-                w.push_back((float)v);     // bins of one triangle are contiguous
+                CMOOP_REQUIRE(b == first + cnt, "front end: a mel band's bins are not contiguous");
+                h.melw.push_back((float)v);     // bins of one triangle are contiguous
                 ++cnt;
             }
         }
-        first_bin[i] = first < 0 ? 0 : first;
-        count[i] = cnt;
+        h.first_bin[i] = first < 0 ? 0 : first;
+        h.count[i] = cnt;
     }
-    // lane tasks: task i < n_mels = band i; the spare lanes take the second half of the widest bands
-    std::vector<int> task(64 * 3 + 64, 0);
-    for (int i = 0; i < 64; ++i) task[192 + i] = -1;
-    for (int i = 0; i < c.n_mels; ++i) { task[3 * i] = first_bin[i]; task[3 * i + 1] = count[i]; task[3 * i + 2] = start[i]; }
-    std::vector<int> order(c.n_mels);
-    for (int i = 0; i < c.n_mels; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return count[a] > count[b]; });
-    int next = c.n_mels;
-    for (int oi = 0; oi < c.n_mels && next < 64; ++oi) {
-        const int b = order[oi];
-        if (count[b] < 8) break;
-        const int h = count[b] / 2;                  // first task keeps bins [0, h), second [h, count)
-        task[3 * b + 1] = h;
-        task[3 * next] = first_bin[b] + h; task[3 * next + 1] = count[b] - h; task[3 * next + 2] = start[b] + h;
-        task[192 + b] = next;
-        ++next;
+    // a bin lies strictly inside at most two triangles
+    CMOOP_REQUIRE((int)h.melw.size() <= 2 * nb, "front end: mel table too large");
+    return h;
+}
+
+FrontendTables* frontend_tables_create(const FrontendCfg& c) {
+    const FrontendHostTables h = frontend_host_tables(c);
+    auto* t = new FrontendTables;
+    t->cfg = c;
+    t->general = !frontend_uses_fixed_kernel(c);
+    const int half = c.n_fft / 2;
+    std::vector<float> tw(h.tw.begin(), h.tw.begin() + 2 * (t->general ? c.n_fft : half));
+    std::vector<float> w = h.melw;
+    std::vector<int> task;
+    if (t->general) {
+        task.resize(3 * c.n_mels);
+        for (int i = 0; i < c.n_mels; ++i) { task[3 * i] = h.first_bin[i]; task[3 * i + 1] = h.count[i]; task[3 * i + 2] = h.start[i]; }
+    } else {
+        // lane tasks: task i < n_mels = band i; the spare lanes take the second half of the widest bands
+        const std::vector<int>&first_bin = h.first_bin, &count = h.count, &start = h.start;
+        task.assign(64 * 3 + 64, 0);
+        for (int i = 0; i < 64; ++i) task[192 + i] = -1;
+        for (int i = 0; i < c.n_mels; ++i) { task[3 * i] = first_bin[i]; task[3 * i + 1] = count[i]; task[3 * i + 2] = start[i]; }
+        std::vector<int> order(c.n_mels);
+        for (int i = 0; i < c.n_mels; ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return count[a] > count[b]; });
+        int next = c.n_mels;
+        for (int oi = 0; oi < c.n_mels && next < 64; ++oi) {
+            const int b = order[oi];
+            if (count[b] < 8) break;
+            const int hh = count[b] / 2;                 // first task keeps bins [0, hh), second [hh, count)
+            task[3 * b + 1] = hh;
+            task[3 * next] = first_bin[b] + hh; task[3 * next + 1] = count[b] - hh; task[3 * next + 2] = start[b] + hh;
+            task[192 + b] = next;
+            ++next;
+        }
+        CMOOP_REQUIRE(w.size() <= 1024, "front end: mel table too large");
     }
     t->nnz = (int)w.size();
     if (w.empty()) w.push_back(0.f);
-    CMOOP_HIP(hipMalloc(&t->tw, tw.size() * 4));
-    CMOOP_HIP(hipMalloc(&t->win, win.size() * 4));
-    CMOOP_HIP(hipMalloc(&t->melw, w.size() * 4));
-    CMOOP_HIP(hipMalloc(&t->meltask, task.size() * 4));
-    CMOOP_HIP(hipMemcpy(t->tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
-    CMOOP_HIP(hipMemcpy(t->win, win.data(), win.size() * 4, hipMemcpyHostToDevice));
-    CMOOP_HIP(hipMemcpy(t->melw, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-    CMOOP_HIP(hipMemcpy(t->meltask, task.data(), task.size() * 4, hipMemcpyHostToDevice));
-    CMOOP_REQUIRE(t->nnz <= 1024, "front end: mel table too large");
+    try {
+        CMOOP_HIP(hipMalloc(&t->tw, tw.size() * 4));
+        CMOOP_HIP(hipMalloc(&t->win, h.win.size() * 4));
+        CMOOP_HIP(hipMalloc(&t->melw, w.size() * 4));
+        CMOOP_HIP(hipMalloc(&t->meltask, task.size() * 4));
+        CMOOP_HIP(hipMemcpy(t->tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
+        CMOOP_HIP(hipMemcpy(t->win, h.win.data(), h.win.size() * 4, hipMemcpyHostToDevice));
+        CMOOP_HIP(hipMemcpy(t->melw, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+        CMOOP_HIP(hipMemcpy(t->meltask, task.data(), task.size() * 4, hipMemcpyHostToDevice));
+    } catch (...) {
+        frontend_tables_destroy(t);
+        throw;
+    }
     return t;
 }
 
@@ -272,12 +328,233 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
     }
 }
 
-void launch_logmel(const float* wav, int64_t n_clips, int n_samples, float* out, const FrontendTables* t, hipStream_t s) {
-    if (n_clips == 0) return;
+// ---- general geometry: n_fft 256 / 512 / 1024 / 2048, up to 128 mel bands, log or dB scale ---------------------------
+// Same shape as logmel_kernel (one workgroup per clip, a wave owns a frame at a time, wave-level synchronisation only),
+// but the packed NC = n_fft/2 complex points live in the wave's own LDS buffer instead of registers: a lane would hold up
+// to 16 points.  The transform is a Stockham radix-4 decimation-in-time FFT with a radix-2 tail where log2 NC is odd
+// (NC 128, 512): stage Ns (1, 4, 16, ...) reads points j + r NC/4, multiplies by W_(4Ns)^(r (j mod Ns)), and stores
+// the butterfly at (j / Ns) 4 Ns + (j mod Ns) + r Ns, so input and output are both in natural order.  Every lane reads
+// all its points of a stage into registers before any lane stores, which makes the exchange in place (8 KiB per wave at
+// n_fft 2048).  Loads of a stage are consecutive complex points across lanes; the stores of the first two stages are not
+// (pitch 4 and 16), so slot i is kept at ex_slot(i), a rotation inside each aligned run of 16 points by 5 (i / 16):
+// loads stay conflict-free (an aligned run of 32 points still fills 32 distinct 8-byte slots), the pitch-4 stores become
+// conflict-free and the pitch-16 stores two-way; later stages store runs of >= 16 consecutive points.
+// Twiddles, window and the real-split factors are per-lane registers, read once from the host-built double tables.
+// The mel bands are lane i & 63, bands 0-63 first and then 64-127, each a serial loop in bin order (deterministic).
+// dB scale: the workgroup stores 10 log10(max(amin, S)), reduces the clip's maximum over its waves, barriers, then
+// subtracts the reference and applies the top_db floor to its own rows -- no second launch, no atomics.
+__device__ __forceinline__ int ex_slot(const int i) { return (i & ~15) | ((i + 5 * (i >> 4)) & 15); }
+
+template <int NC>
+__global__ __launch_bounds__(256) void logmel_ex_kernel(const float* __restrict__ wav, int n_samples, float* __restrict__ out,
+                                                        int T, int hop, int n_mels, int scale, int db_ref_max, float log_eps,
+                                                        float amin, float top_db, const float* __restrict__ g_tw,
+                                                        const float* __restrict__ g_win, const float* __restrict__ g_melw,
+                                                        const int* __restrict__ g_band, int nnz) {
+    constexpr int LG = NC == 128 ? 7 : NC == 256 ? 8 : NC == 512 ? 9 : 10;
+    constexpr int S4 = LG / 2;                                   // radix-4 stages
+    constexpr bool TAIL2 = (LG & 1) != 0;
+    constexpr int B4 = NC >= 256 ? NC / 256 : 1;                 // radix-4 butterflies per lane (NC 128: lanes 0-31 only)
+    constexpr int B2 = NC / 128;                                 // radix-2 butterflies per lane in the tail
+    constexpr int U = NC / 64;                                   // spectrum bins per lane in the real split
+    __shared__ float s_melw[2 * (NC + 1)];
+    __shared__ __attribute__((aligned(16))) f32x2 s_x[4][NC];
+    __shared__ float s_p[4][NC + 4];
+    __shared__ float s_red[4];
+
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const float* clip = wav + (size_t)blockIdx.x * n_samples;
+    for (int i = t; i < nnz; i += 256) s_melw[i] = g_melw[i];
+    __syncthreads();
+
+    // ---- per-lane constants, fixed over the frames -------------------------------------------------
+    const f32x2* tw = reinterpret_cast<const f32x2*>(g_tw);      // tw[k] = exp(-2 pi i k / n_fft), k < n_fft = 2 NC
+    f32x2 w4[S4 > 1 ? S4 - 1 : 1][B4][3], w2[TAIL2 ? B2 : 1], wp[U];
+    float win[B4][4][2];
+#pragma unroll
+    for (int b = 0; b < B4; ++b) {
+        const int j = lane + 64 * b;
+        const bool on = j < NC / 4;
+#pragma unroll
+        for (int st = 1; st < S4; ++st) {
+            const int k = j & ((1 << (2 * st)) - 1);             // j mod Ns, Ns = 4^st
+#pragma unroll
+            for (int r = 1; r < 4; ++r) w4[st - 1][b][r - 1] = tw[on ? (k * r) << (LG - 1 - 2 * st) : 0];   // W_(4Ns)^(k r)
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = on ? j + r * (NC / 4) : 0;
+            win[b][r][0] = g_win[2 * m];
+            win[b][r][1] = g_win[2 * m + 1];
+        }
+    }
+    if (TAIL2) {
+#pragma unroll
+        for (int b = 0; b < B2; ++b) w2[b] = tw[2 * (lane + 64 * b)];     // W_NC^j, j < NC/2
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) wp[u] = tw[lane + 64 * u];               // W_nfft^k
+    int band_first[2], band_cnt[2], band_w[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int band = lane + 64 * h;
+        const bool on = band < n_mels;
+        band_first[h] = on ? g_band[3 * band] : 0;
+        band_cnt[h] = on ? g_band[3 * band + 1] : 0;
+        band_w[h] = on ? g_band[3 * band + 2] : 0;
+    }
+
+    f32x2* xb = s_x[wave];
+    float* pw = s_p[wave];
+    float vmax = -INFINITY;                                      // dB scale: this lane's largest stored value
+    const int iters = (T + 3) >> 2;
+    for (int it = 0; it < iters; ++it) {
+        const int frame = it * 4 + wave;
+        if (frame >= T) break;                                   // wave-uniform; no workgroup barrier inside the loop
+        const int base = frame * hop - NC;                       // centre padding: n_fft / 2 zeros on either side
+        f32x2 a[B4][4], v[4];
+        // stage 0 (Ns = 1, no twiddles) straight from the windowed frame: z[m] = x[2m] + i x[2m+1]
+#pragma unroll
+        for (int b = 0; b < B4; ++b) {
+            const int j = lane + 64 * b;
+            if (j < NC / 4) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int i0 = base + 2 * (j + r * (NC / 4));
+                    const float x0 = (i0 >= 0 && i0 < n_samples) ? clip[i0] : 0.f;
+                    const float x1 = (i0 + 1 >= 0 && i0 + 1 < n_samples) ? clip[i0 + 1] : 0.f;
+                    a[b][r] = f32x2{x0 * win[b][r][0], x1 * win[b][r][1]};
+                }
+                bfly4(a[b][0], a[b][1], a[b][2], a[b][3], v[0], v[1], v[2], v[3]);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) xb[ex_slot(4 * j + r)] = v[r];
+            }
+        }
+        wave_sync();
+#pragma unroll
+        for (int st = 1; st < S4; ++st) {
+            const int ns = 1 << (2 * st);
+#pragma unroll
+            for (int b = 0; b < B4; ++b) {
+                const int j = lane + 64 * b;
+                if (j < NC / 4) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) a[b][r] = xb[ex_slot(j + r * (NC / 4))];
+                }
+            }
+            wave_sync();
+#pragma unroll
+            for (int b = 0; b < B4; ++b) {
+                const int j = lane + 64 * b;
+                if (j < NC / 4) {
+                    bfly4(a[b][0], cmul(a[b][1], w4[st - 1][b][0]), cmul(a[b][2], w4[st - 1][b][1]), cmul(a[b][3], w4[st - 1][b][2]),
+                          v[0], v[1], v[2], v[3]);
+                    const int d = ((j >> (2 * st)) << (2 * st + 2)) + (j & (ns - 1));
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) xb[ex_slot(d + r * ns)] = v[r];
+                }
+            }
+            wave_sync();
+        }
+        if (TAIL2) {
+            f32x2 p0[B2], p1[B2];
+#pragma unroll
+            for (int b = 0; b < B2; ++b) {
+                const int j = lane + 64 * b;
+                p0[b] = xb[ex_slot(j)];
+                p1[b] = xb[ex_slot(j + NC / 2)];
+            }
+            wave_sync();
+#pragma unroll
+            for (int b = 0; b < B2; ++b) {
+                const int j = lane + 64 * b;
+                const f32x2 q = cmul(p1[b], w2[b]);
+                xb[ex_slot(j)] = p0[b] + q;
+                xb[ex_slot(j + NC / 2)] = p0[b] - q;
+            }
+            wave_sync();
+        }
+        // real-FFT split and power spectrum: X[k] = E[k] + W_nfft^k O[k], E = (Z[k] + conj Z[NC-k]) / 2, O = (Z[k] - conj Z[NC-k]) / 2i
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int k = lane + 64 * u, kc = (NC - k) & (NC - 1);
+            const f32x2 z = xb[ex_slot(k)], zc = xb[ex_slot(kc)];
+            const f32x2 e = f32x2{0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y)};
+            const f32x2 o = f32x2{0.5f * (z.y + zc.y), -0.5f * (z.x - zc.x)};
+            const f32x2 x = e + cmul(o, wp[u]);
+            pw[k] = x.x * x.x + x.y * x.y;
+            if (k == 0) {                                        // bin NC: E[0] - O[0]
+                const float xn = e.x - o.x;
+                pw[NC] = xn * xn;
+            }
+        }
+        wave_sync();
+        // sparse mel: band lane + 64 h, bins in ascending order; a band without a bin stores log(eps) / the amin floor
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int band = lane + 64 * h;
+            float acc = 0.f;
+            for (int i = 0; i < band_cnt[h]; ++i) acc = fmaf(s_melw[band_w[h] + i], pw[band_first[h] + i], acc);
+            if (band < n_mels) {
+                float y;
+                if (scale == 0) {
+                    y = logf(acc + log_eps);
+                } else {
+                    y = 10.f * log10f(fmaxf(amin, acc));
+                    vmax = fmaxf(vmax, y);
+                }
+                out[((size_t)blockIdx.x * T + frame) * n_mels + band] = y;
+            }
+        }
+        wave_sync();
+    }
+    if (scale == 0) return;                                      // kernel argument: uniform over the grid
+    // dB scale: reference and top_db floor from the clip's own maximum, applied to the rows this workgroup stored
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
+    if (lane == 0) s_red[wave] = vmax;
+    __syncthreads();                                             // also orders the waves' stores to out before the reads below
+    const float cmax = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    const float ref = db_ref_max ? cmax : 10.f * log10f(fmaxf(amin, 1.f));
+    const float floor_db = top_db >= 0.f ? (cmax - ref) - top_db : -INFINITY;
+    float* rows = out + (size_t)blockIdx.x * T * n_mels;
+    const int total = T * n_mels;
+    for (int i = t; i < total; i += 256) rows[i] = fmaxf(rows[i] - ref, floor_db);
+}
+
+template <int NC>
+static void launch_logmel_ex(const float* wav, int64_t n_clips, int n_samples, float* out, int T, const FrontendTables* t, hipStream_t s) {
     const FrontendCfg& c = t->cfg;
-    const int T = 1 + n_samples / c.hop;
-    hipLaunchKernelGGL(logmel_kernel, dim3((unsigned)n_clips), dim3(256), 0, s, wav, n_samples, out, T, c.hop, c.n_mels,
-                       c.log_eps, t->tw, t->win, t->melw, t->meltask, t->nnz);
+    hipLaunchKernelGGL(logmel_ex_kernel<NC>, dim3((unsigned)n_clips), dim3(256), 0, s, wav, n_samples, out, T, c.hop, c.n_mels,
+                       c.scale, c.db_ref_max, c.log_eps, c.db_amin, c.top_db, t->tw, t->win, t->melw, t->meltask, t->nnz);
+}
+
+int frontend_frames(const FrontendCfg& c, int n_samples) {
+    CMOOP_REQUIRE(n_samples >= 1, "front end: n_samples must be at least 1");
+    CMOOP_REQUIRE(c.hop >= 1, "front end config: hop must be at least 1");
+    const int64_t T = 1 + (int64_t)n_samples / c.hop;
+    CMOOP_REQUIRE(T <= 0x7fffffff, "front end: too many frames");
+    return (int)T;
+}
+
+void launch_logmel(const float* wav, int64_t n_clips, int n_samples, float* out, const FrontendTables* t, hipStream_t s) {
+    const FrontendCfg& c = t->cfg;
+    const int T = frontend_frames(c, n_samples);
+    CMOOP_REQUIRE(n_clips >= 0 && n_clips <= 0x7fffffff && (int64_t)T * c.n_mels <= 0x7fffffff, "front end: clip count / clip length out of range");
+    if (n_clips == 0) return;
+    CMOOP_REQUIRE(wav && out, "front end: NULL buffer");
+    if (!t->general) {
+        hipLaunchKernelGGL(logmel_kernel, dim3((unsigned)n_clips), dim3(256), 0, s, wav, n_samples, out, T, c.hop, c.n_mels,
+                           c.log_eps, t->tw, t->win, t->melw, t->meltask, t->nnz);
+    } else if (c.n_fft == 256) {
+        launch_logmel_ex<128>(wav, n_clips, n_samples, out, T, t, s);
+    } else if (c.n_fft == 512) {
+        launch_logmel_ex<256>(wav, n_clips, n_samples, out, T, t, s);
+    } else if (c.n_fft == 1024) {
+        launch_logmel_ex<512>(wav, n_clips, n_samples, out, T, t, s);
+    } else {
+        launch_logmel_ex<1024>(wav, n_clips, n_samples, out, T, t, s);
+    }
     CMOOP_HIP(hipGetLastError());
 }
 

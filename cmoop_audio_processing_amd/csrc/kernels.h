@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include <string>
+#include <vector>
 
 namespace cmoop {
 
@@ -238,10 +239,26 @@ void launch_confusion(const int32_t* y_true, const int32_t* y_pred, int64_t n, i
 // ---------------------------------------------------------------------------
 // Audio front end (north-star addition; no reference counterpart)
 // ---------------------------------------------------------------------------
+constexpr int FRONTEND_MAX_MELS = 128;
 struct FrontendCfg {
     int sr = 16000, n_fft = 512, win = 400, hop = 160, n_mels = 40;
     float fmin = 20.f, fmax = 7600.f, log_eps = 1e-6f;
+    int scale = 0;             // 0: log(mel + log_eps) ; 1: dB, 10 log10(max(db_amin, mel)) - 10 log10(max(db_amin, ref))
+    int db_ref_max = 0;        // dB reference: 0 -> 1.0, 1 -> the clip's own largest mel power
+    float db_amin = 1e-10f, top_db = 80.f;   // top_db >= 0: values below (clip maximum - top_db) are raised to it
 };
+// host-only: throws with a message naming the offending field when the config is outside the kernels' domain
+void frontend_check(const FrontendCfg& c);
+bool frontend_cfg_equal(const FrontendCfg& a, const FrontendCfg& b);
+// n_fft 512, n_mels <= 64, log scale: served by logmel_kernel; everything else by logmel_ex_kernel
+bool frontend_uses_fixed_kernel(const FrontendCfg& c);
+int frontend_frames(const FrontendCfg& c, int n_samples);   // 1 + n_samples / hop
+// host-only tables (built in double, stored as float); the sparse mel basis is band i = melw[start[i] .. + count[i]) on bins first_bin[i] ..
+struct FrontendHostTables {
+    std::vector<float> tw, win, melw;        // [n_fft][2] cos, -sin ; [n_fft] ; non-zero weights band after band
+    std::vector<int> first_bin, count, start;
+};
+FrontendHostTables frontend_host_tables(const FrontendCfg& c);
 struct FrontendTables;   // device-resident twiddles / window / sparse mel weights
 FrontendTables* frontend_tables_create(const FrontendCfg& c);
 void frontend_tables_destroy(FrontendTables* t);

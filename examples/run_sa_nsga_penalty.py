@@ -9,6 +9,7 @@ offspring, only max(1, int(pop * infill)) of them per generation get a TRUE eval
     python examples/run_sa_nsga_penalty.py --pop 8 --gen 2 --clips 1200 --epochs 6                       # smoke-sized
     python examples/run_sa_nsga_penalty.py --pop 40 --gen 20 --classes 35                                 # BASELINE configs[2]
     python examples/run_sa_nsga_penalty.py --pop 64 --gen 20 --infill 0.334 --memetic --compute bf16      # BASELINE configs[4]
+    python examples/run_sa_nsga_penalty.py --audio birdclef --pop 8 --gen 2 --clips 264 --epochs 6       # 128 x 128 dB-mel patches
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_sa_nsga_penalty.py --pop 40 --gen 20
 """
 import argparse
@@ -35,6 +36,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--memetic", action="store_true", help="LHS initial population + Lamarckian LCB local search (sa_nsga_local.py:351-433)")
     ap.add_argument("--compute", default="fp32", choices=["fp32", "bf16x3", "bf16"])
+    ap.add_argument("--audio", default="gsc", choices=["gsc", "birdclef"],
+                    help="gsc: 1 s clips at 16 kHz -> [101, 40] log-mel; birdclef: 65 280-sample clips at 32 kHz -> [128, 128] dB-mel "
+                         "patches through FrontendConfig.preset('birdclef_128') (a build-defined recipe, see its docstring)")
     ap.add_argument("--out", default="sa_nsga_generations.csv")
     ap.add_argument("--trace", default="", help="write a JSON trace: per evaluate call wall-clock, epochs run, hypervolume")
     a = ap.parse_args()
@@ -44,8 +48,15 @@ def main():
     if world > 1:
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local))
     dev = torch.device("cuda", local)
-    wav, y = synth_waveforms(a.clips, a.classes, 1234, dev)
-    feats = frontend.log_mel(wav).cpu().numpy()                 # [N, 101, 40]; no StandardScaler in this script (Q2)
+    if a.audio == "birdclef":
+        # the synthesiser's time axis is in 1/16000 s steps: read at 32 kHz its partials sit at 400-8000 Hz
+        cfg = frontend.FrontendConfig.preset("birdclef_128")
+        wav, y = synth_waveforms(a.clips, a.classes, 1234, dev, n_samples=65280)
+        feats = frontend.log_mel(wav, cfg).cpu().numpy()        # [N, 128, 128] dB-mel, unscaled (Q2)
+    else:
+        wav, y = synth_waveforms(a.clips, a.classes, 1234, dev)
+        feats = frontend.log_mel(wav).cpu().numpy()             # [N, 101, 40]; no StandardScaler in this script (Q2)
+    del wav
     Xtr, ytr, Xva, yva, _, _ = datasets.stratified_50_25_25(feats, y.cpu().numpy(), random_state=42)
     preset = "sa_nsga_local" if a.memetic else "sa_nsga_penalty"
     ev = PopulationEvaluator(Xtr, ytr, Xva, yva, EvalConfig.preset(preset, classes=a.classes, epochs=a.epochs, seed=a.seed,

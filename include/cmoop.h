@@ -136,6 +136,30 @@ int cmoop_calculate_fpr(const int32_t* y_true, const int32_t* y_pred, int64_t n,
  *      nsga_penalty.py:64-71) and prepare_dataset's StandardScaler (nsga_penalty.py:103-141) */
 int cmoop_logmel(const float* wav_dev /* [n_clips][n_samples] */, int64_t n_clips, int32_t n_samples,
                  float* out_dev /* [n_clips][1+n_samples/160][40] */);
+/* Configurable front end.  Domain: n_fft in {256, 512, 1024, 2048}; 1 <= win <= n_fft (periodic Hann of win points centred
+ * in n_fft); hop >= 1; 1 <= n_mels <= 128; 0 <= fmin < fmax <= sr/2; n_samples >= 1; T = 1 + n_samples / hop frames,
+ * centre-padded with zeros.  scale 0: log(mel + log_eps).  scale 1: 10 log10(max(db_amin, mel)) - 10 log10(max(db_amin, ref))
+ * with ref = 1.0 (db_ref_max 0) or the clip's own largest mel power (db_ref_max 1), then, when top_db >= 0, every value below
+ * (the clip's maximum - top_db) is raised to it.  The default is the geometry of the fixed-geometry call above. */
+typedef struct cmoop_frontend_config {
+    int32_t sr, n_fft, win, hop, n_mels;
+    int32_t scale;       /* 0 log, 1 dB */
+    int32_t db_ref_max;
+    float fmin, fmax, log_eps, db_amin, top_db;
+} cmoop_frontend_config;
+int cmoop_frontend_config_default(cmoop_frontend_config* c);
+/* host-only: non-zero + a message naming the offending field when the config is outside the domain */
+int cmoop_frontend_check(const cmoop_frontend_config* c);
+/* host-only: T = 1 + n_samples / hop */
+int cmoop_frontend_frames(const cmoop_frontend_config* c, int32_t n_samples, int32_t* T);
+/* host-only: the dense form [n_mels][1 + n_fft/2] of the sparse mel table the kernel reads (Slaney scale, slaney norm) */
+int cmoop_frontend_mel_basis(const cmoop_frontend_config* c, float* out_host);
+/* Configs with n_fft 512, n_mels <= 64 and the log scale run on the fixed-geometry call's kernel, every other on the general one. */
+int cmoop_logmel_ex(const cmoop_frontend_config* c, const float* wav_dev /* [n_clips][n_samples] */, int64_t n_clips,
+                    int32_t n_samples, float* out_dev /* [n_clips][T][n_mels] */);
+/* average milliseconds of `iters` launches of the call above between two HIP events on the library's stream, after 3 warm-up launches */
+int cmoop_logmel_ex_time(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_clips, int32_t n_samples, float* out_dev,
+                         int32_t iters, double* avg_ms);
 /* optional MFCC features: DCT-II, ortho-normalised, along the mel axis of log-mel rows; first n_mfcc coefficients.
  * The reference ships no front end; its comment at ablation_study/sa_nsga_init.py:68 calls the stored features MFCCs. */
 int cmoop_mfcc(const float* logmel_dev /* [rows][n_mels] */, int64_t rows, int32_t n_mels, int32_t n_mfcc,
