@@ -44,6 +44,16 @@ class DatasetStruct(C.Structure):
 NEXT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
 
+#: prototypes of the scoring entry points (include/cmoop.h); pointers travel as void*, None is NULL
+STREAM_PROTOTYPES = {
+    "cmoop_net_predict": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "cmoop_logmel_stream": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "cmoop_logmel_stream_time": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p],
+    "cmoop_stream_windows": [C.c_int64, C.c_int32, C.c_int32, C.c_void_p],
+    "cmoop_net_predict_stream": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
 def build(verbose: bool = False) -> str:
     """Compile libcmoop_hip.so for gfx950 in-tree (make; hipcc cross-compiles on CPU-only hosts)."""
     jobs = str(min(8, os.cpu_count() or 1))
@@ -82,6 +92,8 @@ def lib():
             if name not in ("cmoop_last_error", "cmoop_config_default"):
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
+        for name, argtypes in STREAM_PROTOTYPES.items():
+            getattr(L, name).argtypes = argtypes
         _lib = L
         return L
 

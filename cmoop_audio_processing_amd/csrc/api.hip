@@ -334,6 +334,53 @@ int cmoop_logmel_ex_time(const cmoop_frontend_config* c, const float* wav_dev, i
     });
 }
 
+static int compute_units_of_current_device() {
+    int dev = 0, cu = 0;
+    CMOOP_HIP(hipGetDevice(&dev));
+    CMOOP_HIP(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
+    return cu > 0 ? cu : 256;
+}
+
+int cmoop_logmel_stream(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_samples, float* out_dev) {
+    return guard([&] {
+        const FrontendCfg f = to_frontend_cfg(c);
+        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+        hipStream_t s = lib_stream();
+        launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), compute_units_of_current_device(), s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_logmel_stream_time(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_samples, float* out_dev, int32_t iters,
+                             double* avg_ms) {
+    return guard([&] {
+        const FrontendCfg f = to_frontend_cfg(c);
+        CMOOP_REQUIRE(iters >= 1 && avg_ms, "logmel_stream_time: iters >= 1");
+        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+        const int cu = compute_units_of_current_device();
+        hipStream_t s = lib_stream();
+        for (int i = 0; i < 3; ++i) launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s);
+        hipEvent_t a, b;
+        CMOOP_HIP(hipEventCreate(&a));
+        CMOOP_HIP(hipEventCreate(&b));
+        CMOOP_HIP(hipEventRecord(a, s));
+        for (int i = 0; i < iters; ++i) launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s);
+        CMOOP_HIP(hipEventRecord(b, s));
+        CMOOP_HIP(hipEventSynchronize(b));
+        float ms = 0.f;
+        CMOOP_HIP(hipEventElapsedTime(&ms, a, b));
+        hipEventDestroy(a); hipEventDestroy(b);
+        *avg_ms = (double)ms / iters;
+    });
+}
+
+int cmoop_stream_windows(int64_t n_frames, int32_t T, int32_t hop_frames, int64_t* n_windows) {
+    return guard([&] {
+        CMOOP_REQUIRE(n_windows != nullptr, "stream_windows: NULL output");
+        *n_windows = stream_windows(n_frames, T, hop_frames);
+    });
+}
+
 int cmoop_mfcc(const float* logmel_dev, int64_t rows, int32_t n_mels, int32_t n_mfcc, float* out_dev) {
     return guard([&] {
         CMOOP_REQUIRE(rows >= 0 && (rows == 0 || (logmel_dev && out_dev && logmel_dev != out_dev)), "mfcc: out of place, rows >= 0");
@@ -511,6 +558,26 @@ int cmoop_net_evaluate(cmoop_net* h, const float* x, const int32_t* y, int64_t n
         long long c = 0;
         h->net->evaluate(x, y, n, loss_sum, &c, preds_dev);
         *correct = c;
+    });
+}
+int cmoop_net_predict(cmoop_net* h, const float* x, int64_t n, float* probs) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "predict: NULL net");
+        h->net->predict(x, n, probs);
+    });
+}
+int cmoop_net_predict_stream(cmoop_net* h, const float* feat, int64_t n_frames, int32_t hop_frames, const cmoop_frontend_config* db,
+                             const double* mean_host, const double* scale_host, float* probs) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "predict_stream: NULL net");
+        FrontendCfg f;
+        const bool db_scale = db != nullptr && db->scale == 1;
+        if (db_scale) {
+            f = to_frontend_cfg(db);
+            CMOOP_REQUIRE(f.n_mels == h->net->feature_F(), "predict_stream: the front end config has " + std::to_string(f.n_mels) +
+                          " mel bands, the net reads " + std::to_string(h->net->feature_F()) + " features per frame");
+        }
+        h->net->predict_stream(feat, n_frames, hop_frames, db_scale, f.db_ref_max != 0, f.db_amin, f.top_db, mean_host, scale_host, probs);
     });
 }
 int cmoop_net_train_metrics(cmoop_net* h, double* loss_sum, int64_t* correct, int32_t reset) {

@@ -1183,6 +1183,75 @@ void launch_softmax_ce(const float* Z, const int32_t* labels, const int32_t* idx
     CMOOP_HIP(hipGetLastError());
 }
 
+// Model.predict: the probabilities softmax_ce_kernel forms and discards.  One thread per row; the same serial loops in
+// the same order (maximum, sum over ascending j, expf(z_j - max) / sum), so p is bit-equal to the p behind the loss and
+// the row's arg max is the prediction evaluate returns.  C <= a few dozen floats per row: the pass is launch-bound.
+__global__ __launch_bounds__(256) void softmax_probs_kernel(const float* __restrict__ Z, float* __restrict__ P, int B, int C) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= B) return;
+    const float* z = Z + (size_t)r * C;
+    float* p = P + (size_t)r * C;
+    float mx = z[0];
+    for (int j = 1; j < C; ++j)
+        if (z[j] > mx) mx = z[j];
+    float se = 0.f;
+    for (int j = 0; j < C; ++j) se += expf(z[j] - mx);
+    for (int j = 0; j < C; ++j) p[j] = expf(z[j] - mx) / se;
+}
+
+void launch_softmax_probs(const float* Z, float* P, int B, int C, hipStream_t s) {
+    if (B == 0) return;
+    hipLaunchKernelGGL(softmax_probs_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, Z, P, B, C);
+    CMOOP_HIP(hipGetLastError());
+}
+
+// Sliding-window scoring: window w = rows [w hop, w hop + T) of a feature stream [n_frames][F] -- T F CONTIGUOUS floats
+// at element offset w hop F.  One workgroup copies one window into the [B][T][F] chunk the forward pass reads, applying
+// on the way (a) the dB reference / top_db floor of THIS window (the tail of logmel_ex_kernel with "window" for "clip":
+// workgroup maximum, then max(v - ref, floor)) and (b) the StandardScaler, (float)(((double)v - mean[c]) / scale[c]) as
+// standardize_kernel.  64-bit base per window, 32-bit index inside it; the column of element i = t + 256 k is carried
+// along (c += 256 mod F) instead of a modulo per element.  The stream itself is only read.
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ feat, float* __restrict__ chunk, int64_t w0,
+                                                            int hop, int TF, int F, int db, int db_ref_max, float amin,
+                                                            float top_db, const double* __restrict__ mean,
+                                                            const double* __restrict__ scale) {
+    __shared__ float s_red[4];
+    const int t = threadIdx.x;
+    const float* src = feat + (w0 + blockIdx.x) * (int64_t)hop * F;
+    float* dst = chunk + (size_t)blockIdx.x * TF;
+    float ref = 0.f, floor_db = -INFINITY;
+    if (db) {                                                     // kernel argument: uniform over the grid
+        float vmax = -INFINITY;
+        for (int i = t; i < TF; i += 256) vmax = fmaxf(vmax, src[i]);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
+        if ((t & 63) == 0) s_red[t >> 6] = vmax;
+        __syncthreads();
+        const float cmax = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+        ref = db_ref_max ? cmax : 10.f * log10f(fmaxf(amin, 1.f));
+        floor_db = top_db >= 0.f ? (cmax - ref) - top_db : -INFINITY;
+    }
+    const int step = 256 % F;
+    int c = t % F;
+    for (int i = t; i < TF; i += 256) {
+        float v = src[i];
+        if (db) v = fmaxf(v - ref, floor_db);
+        if (mean) v = (float)(((double)v - mean[c]) / scale[c]);
+        dst[i] = v;
+        c += step;
+        if (c >= F) c -= F;
+    }
+}
+
+void launch_window_gather(const float* feat, float* chunk, int64_t w0, int B, int hop, int T, int F, int db, int db_ref_max,
+                          float amin, float top_db, const double* mean, const double* scale, hipStream_t s) {
+    if (B == 0) return;
+    CMOOP_REQUIRE((int64_t)T * F <= 0x7fffffff - 256, "window gather: T * F out of range");
+    hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)B), dim3(256), 0, s, feat, chunk, w0, hop, T * F, F, db, db_ref_max, amin,
+                       top_db, mean, scale);
+    CMOOP_HIP(hipGetLastError());
+}
+
 // Every operation of the update is a separately rounded IEEE single operation, in the order the reference's CPU path and
 // the oracle apply them (oracle/net.py train_step): no fused multiply-add.  Left to the compiler, the contraction of
 // m + (g - m) * c1 differed BETWEEN TWO KERNELS of this file (fused in one, mul + add in the other), an ulp apart --

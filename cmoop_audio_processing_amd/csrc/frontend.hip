@@ -1,6 +1,8 @@
 // Audio front end: framing -> Hann -> real FFT -> |.|^2 -> sparse Slaney mel -> log (or dB).
 // logmel_kernel is the 512-point kernel of the build-defined configuration; logmel_ex_kernel (further down) serves
-// n_fft 256-2048, up to 128 bands and the dB scale.
+// n_fft 256-2048, up to 128 bands and the dB scale.  Both have a stream form (logmel_stream_kernel,
+// logmel_ex_stream_kernel) for ONE long recording: the grid runs over runs of its frames instead of over clips, the frame
+// arithmetic is the same __device__ function.
 // North-star addition beneath the reference's data loader (the reference ships
 // pre-extracted features only: nsga_penalty.py:64-71); the
 // algorithm restates librosa.feature.melspectrogram (requirements.txt:80) and is
@@ -200,11 +202,13 @@ __device__ __forceinline__ void bfly4(const f32x2 a0, const f32x2 a1, const f32x
     b3 = d02 - nid;
 }
 
-__global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ wav, int n_samples, float* __restrict__ out,
-                                                     int T, int hop, int n_mels, float log_eps,
-                                                     const float* __restrict__ g_tw, const float* __restrict__ g_win,
-                                                     const float* __restrict__ g_melw, const int* __restrict__ g_task,
-                                                     int nnz) {
+// Frames [f0, f1) of one waveform `clip`, written to rows f0.. of `rows` ([.][n_mels]): the whole per-frame arithmetic
+// of the 512-point kernel.  logmel_kernel runs it over a clip's frames, logmel_stream_kernel over one run of a recording's.
+__device__ __forceinline__ void logmel_frames(const float* __restrict__ clip, int n_samples, float* __restrict__ rows,
+                                              int f0, int f1, int hop, int n_mels, float log_eps,
+                                              const float* __restrict__ g_tw, const float* __restrict__ g_win,
+                                              const float* __restrict__ g_melw, const int* __restrict__ g_task,
+                                              int nnz) {
     constexpr int XB = 320;    // complex slots of the exchange buffer (pitch-20 / pitch-5 layouts, skewed spectrum)
     constexpr int PB = 264;    // power spectrum bins 0..256
     __shared__ float s_melw[1024];
@@ -214,7 +218,6 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
     __shared__ float s_part[4][64];
 
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const float* clip = wav + (size_t)blockIdx.x * n_samples;
     for (int i = t; i < nnz; i += 256) s_melw[i] = g_melw[i];
     s_task[t] = g_task[t];
     __syncthreads();
@@ -248,10 +251,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
     f32x2* xb = s_x[wave];
     float* pw = s_p[wave];
     float* part = s_part[wave];
-    const int iters = (T + 3) >> 2;
-    for (int it = 0; it < iters; ++it) {
-        const int frame = it * 4 + wave;
-        if (frame >= T) break;                                // wave-uniform; no workgroup barrier below
+    for (int frame = f0 + wave; frame < f1; frame += 4) {     // wave-uniform; no workgroup barrier below
         // windowed frame, centre-padded with zeros (pad_mode='constant'); z[m] = x[2m] + i x[2m+1]
         const int base = frame * hop - NFFT / 2;
         f32x2 a[4], b[4];
@@ -322,10 +322,30 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
         if (lane < n_mels) {
             float acc = part[lane];
             if (task2 >= 0) acc += part[task2];
-            out[((size_t)blockIdx.x * T + frame) * n_mels + lane] = logf(acc + log_eps);
+            rows[(size_t)frame * n_mels + lane] = logf(acc + log_eps);
         }
         wave_sync();
     }
+}
+
+__global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ wav, int n_samples, float* __restrict__ out,
+                                                     int T, int hop, int n_mels, float log_eps,
+                                                     const float* __restrict__ g_tw, const float* __restrict__ g_win,
+                                                     const float* __restrict__ g_melw, const int* __restrict__ g_task,
+                                                     int nnz) {
+    logmel_frames(wav + (size_t)blockIdx.x * n_samples, n_samples, out + (size_t)blockIdx.x * T * n_mels, 0, T, hop, n_mels,
+                  log_eps, g_tw, g_win, g_melw, g_task, nnz);
+}
+
+// Stream form: ONE recording, workgroup b owns frames [b run, min((b + 1) run, T)) -- a wave still owns a frame at a time,
+// so frame f carries the bits logmel_kernel gives it.  Every workgroup re-loads the tables (the prologue of logmel_frames).
+__global__ __launch_bounds__(256) void logmel_stream_kernel(const float* __restrict__ wav, int n_samples, float* __restrict__ out,
+                                                            int T, int run, int hop, int n_mels, float log_eps,
+                                                            const float* __restrict__ g_tw, const float* __restrict__ g_win,
+                                                            const float* __restrict__ g_melw, const int* __restrict__ g_task,
+                                                            int nnz) {
+    const int f0 = blockIdx.x * run;                          // < T: the grid is ceil(T / run)
+    logmel_frames(wav, n_samples, out, f0, f0 + min(run, T - f0), hop, n_mels, log_eps, g_tw, g_win, g_melw, g_task, nnz);
 }
 
 // ---- general geometry: n_fft 256 / 512 / 1024 / 2048, up to 128 mel bands, log or dB scale ---------------------------
@@ -345,12 +365,14 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
 // subtracts the reference and applies the top_db floor to its own rows -- no second launch, no atomics.
 __device__ __forceinline__ int ex_slot(const int i) { return (i & ~15) | ((i + 5 * (i >> 4)) & 15); }
 
+// Frames [f0, f1) of one waveform `clip`, written to rows f0.. of `rows` ([.][n_mels]) as log(mel + eps) or as the
+// un-referenced 10 log10(max(amin, mel)); returns this lane's largest stored value (dB scale).  Shared by
+// logmel_ex_kernel (a clip's frames, then the dB tail) and logmel_ex_stream_kernel (one run of a recording's frames).
 template <int NC>
-__global__ __launch_bounds__(256) void logmel_ex_kernel(const float* __restrict__ wav, int n_samples, float* __restrict__ out,
-                                                        int T, int hop, int n_mels, int scale, int db_ref_max, float log_eps,
-                                                        float amin, float top_db, const float* __restrict__ g_tw,
-                                                        const float* __restrict__ g_win, const float* __restrict__ g_melw,
-                                                        const int* __restrict__ g_band, int nnz) {
+__device__ __forceinline__ float logmel_ex_frames(const float* __restrict__ clip, int n_samples, float* __restrict__ rows,
+                                                  int f0, int f1, int hop, int n_mels, int scale, float log_eps, float amin,
+                                                  const float* __restrict__ g_tw, const float* __restrict__ g_win,
+                                                  const float* __restrict__ g_melw, const int* __restrict__ g_band, int nnz) {
     constexpr int LG = NC == 128 ? 7 : NC == 256 ? 8 : NC == 512 ? 9 : 10;
     constexpr int S4 = LG / 2;                                   // radix-4 stages
     constexpr bool TAIL2 = (LG & 1) != 0;
@@ -360,10 +382,8 @@ __global__ __launch_bounds__(256) void logmel_ex_kernel(const float* __restrict_
     __shared__ float s_melw[2 * (NC + 1)];
     __shared__ __attribute__((aligned(16))) f32x2 s_x[4][NC];
     __shared__ float s_p[4][NC + 4];
-    __shared__ float s_red[4];
 
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const float* clip = wav + (size_t)blockIdx.x * n_samples;
     for (int i = t; i < nnz; i += 256) s_melw[i] = g_melw[i];
     __syncthreads();
 
@@ -407,10 +427,7 @@ __global__ __launch_bounds__(256) void logmel_ex_kernel(const float* __restrict_
     f32x2* xb = s_x[wave];
     float* pw = s_p[wave];
     float vmax = -INFINITY;                                      // dB scale: this lane's largest stored value
-    const int iters = (T + 3) >> 2;
-    for (int it = 0; it < iters; ++it) {
-        const int frame = it * 4 + wave;
-        if (frame >= T) break;                                   // wave-uniform; no workgroup barrier inside the loop
+    for (int frame = f0 + wave; frame < f1; frame += 4) {        // wave-uniform; no workgroup barrier inside the loop
         const int base = frame * hop - NC;                       // centre padding: n_fft / 2 zeros on either side
         f32x2 a[B4][4], v[4];
         // stage 0 (Ns = 1, no twiddles) straight from the windowed frame: z[m] = x[2m] + i x[2m+1]
@@ -503,11 +520,25 @@ __global__ __launch_bounds__(256) void logmel_ex_kernel(const float* __restrict_
                     y = 10.f * log10f(fmaxf(amin, acc));
                     vmax = fmaxf(vmax, y);
                 }
-                out[((size_t)blockIdx.x * T + frame) * n_mels + band] = y;
+                rows[(size_t)frame * n_mels + band] = y;
             }
         }
         wave_sync();
     }
+    return vmax;
+}
+
+template <int NC>
+__global__ __launch_bounds__(256) void logmel_ex_kernel(const float* __restrict__ wav, int n_samples, float* __restrict__ out,
+                                                        int T, int hop, int n_mels, int scale, int db_ref_max, float log_eps,
+                                                        float amin, float top_db, const float* __restrict__ g_tw,
+                                                        const float* __restrict__ g_win, const float* __restrict__ g_melw,
+                                                        const int* __restrict__ g_band, int nnz) {
+    __shared__ float s_red[4];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    float* rows = out + (size_t)blockIdx.x * T * n_mels;
+    float vmax = logmel_ex_frames<NC>(wav + (size_t)blockIdx.x * n_samples, n_samples, rows, 0, T, hop, n_mels, scale, log_eps,
+                                      amin, g_tw, g_win, g_melw, g_band, nnz);
     if (scale == 0) return;                                      // kernel argument: uniform over the grid
     // dB scale: reference and top_db floor from the clip's own maximum, applied to the rows this workgroup stored
 #pragma unroll
@@ -517,9 +548,22 @@ __global__ __launch_bounds__(256) void logmel_ex_kernel(const float* __restrict_
     const float cmax = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
     const float ref = db_ref_max ? cmax : 10.f * log10f(fmaxf(amin, 1.f));
     const float floor_db = top_db >= 0.f ? (cmax - ref) - top_db : -INFINITY;
-    float* rows = out + (size_t)blockIdx.x * T * n_mels;
     const int total = T * n_mels;
     for (int i = t; i < total; i += 256) rows[i] = fmaxf(rows[i] - ref, floor_db);
+}
+
+// Stream form of the general kernel: ONE recording, workgroup b owns frames [b run, min((b + 1) run, T)).  No dB tail:
+// a recording has no clip maximum; the reference and the top_db floor belong to the windows cut from the stream later
+// (window_gather_kernel, elem.hip), so the dB scale leaves the un-referenced 10 log10(max(amin, mel)) here.
+template <int NC>
+__global__ __launch_bounds__(256) void logmel_ex_stream_kernel(const float* __restrict__ wav, int n_samples, float* __restrict__ out,
+                                                               int T, int run, int hop, int n_mels, int scale, float log_eps,
+                                                               float amin, const float* __restrict__ g_tw,
+                                                               const float* __restrict__ g_win, const float* __restrict__ g_melw,
+                                                               const int* __restrict__ g_band, int nnz) {
+    const int f0 = blockIdx.x * run;                             // < T: the grid is ceil(T / run)
+    logmel_ex_frames<NC>(wav, n_samples, out, f0, f0 + min(run, T - f0), hop, n_mels, scale, log_eps, amin, g_tw, g_win, g_melw,
+                         g_band, nnz);
 }
 
 template <int NC>
@@ -554,6 +598,45 @@ void launch_logmel(const float* wav, int64_t n_clips, int n_samples, float* out,
         launch_logmel_ex<512>(wav, n_clips, n_samples, out, T, t, s);
     } else {
         launch_logmel_ex<1024>(wav, n_clips, n_samples, out, T, t, s);
+    }
+    CMOOP_HIP(hipGetLastError());
+}
+
+// Frames per workgroup of the stream kernels.  A workgroup's prologue (mel table into LDS, ~30 twiddle / window loads
+// per lane) costs about as much as one frame of a wave, so a run should give every wave several frames; the grid should
+// still hold at least two workgroups per compute unit so a 60 s recording (6 001 frames at hop 160) covers the chip.
+// run = ceil(T / (2 CUs)) rounded up to the four waves, kept inside [8, 64].
+int frontend_stream_run(int T, int compute_units) {
+    const int64_t want = cdiv64((int64_t)T, 2 * (int64_t)std::max(1, compute_units));
+    return (int)std::min<int64_t>(64, std::max<int64_t>(8, (want + 3) & ~(int64_t)3));
+}
+
+template <int NC>
+static void launch_logmel_ex_stream(const float* wav, int n_samples, float* out, int T, int run, const FrontendTables* t, hipStream_t s) {
+    const FrontendCfg& c = t->cfg;
+    hipLaunchKernelGGL(logmel_ex_stream_kernel<NC>, dim3((unsigned)cdiv(T, run)), dim3(256), 0, s, wav, n_samples, out, T, run, c.hop,
+                       c.n_mels, c.scale, c.log_eps, c.db_amin, t->tw, t->win, t->melw, t->meltask, t->nnz);
+}
+
+void launch_logmel_stream(const float* wav, int64_t n_samples, float* out, const FrontendTables* t, int compute_units, hipStream_t s) {
+    const FrontendCfg& c = t->cfg;
+    // frame * hop + n_fft stays inside int32 in the kernels' sample index
+    CMOOP_REQUIRE(n_samples >= 1 && n_samples <= 0x7fffffffll - 2 * c.n_fft, "stream front end: 1 <= n_samples < 2^31 - 2 n_fft");
+    const int T = frontend_frames(c, (int)n_samples);
+    CMOOP_REQUIRE((int64_t)T * c.n_mels <= 0x7fffffff && T <= 0x7fffffff - 64, "stream front end: T * n_mels must stay below 2^31");
+    CMOOP_REQUIRE(wav && out, "stream front end: NULL buffer");
+    const int run = frontend_stream_run(T, compute_units);
+    if (!t->general) {
+        hipLaunchKernelGGL(logmel_stream_kernel, dim3((unsigned)cdiv(T, run)), dim3(256), 0, s, wav, (int)n_samples, out, T, run, c.hop,
+                           c.n_mels, c.log_eps, t->tw, t->win, t->melw, t->meltask, t->nnz);
+    } else if (c.n_fft == 256) {
+        launch_logmel_ex_stream<128>(wav, (int)n_samples, out, T, run, t, s);
+    } else if (c.n_fft == 512) {
+        launch_logmel_ex_stream<256>(wav, (int)n_samples, out, T, run, t, s);
+    } else if (c.n_fft == 1024) {
+        launch_logmel_ex_stream<512>(wav, (int)n_samples, out, T, run, t, s);
+    } else {
+        launch_logmel_ex_stream<1024>(wav, (int)n_samples, out, T, run, t, s);
     }
     CMOOP_HIP(hipGetLastError());
 }

@@ -208,6 +208,12 @@ void launch_gap_bwd(const float* dY, const float* X, float* dX, int B, int HW, i
 // acc[0] (double: sum of per-sample losses) and acc[1] (as int64: correct); writes preds when non-null.
 void launch_softmax_ce(const float* Z, const int32_t* labels, const int32_t* idx, int64_t row0, int B, int C,
                        float* dZ, double* acc, int32_t* preds, hipStream_t s, const StepState* st = nullptr, int64_t n_rows = 0);
+// P[r][j] = the p softmax_ce_kernel forms for row r (same loops, same order): Model.predict
+void launch_softmax_probs(const float* Z, float* P, int B, int C, hipStream_t s);
+// windows w0 .. w0 + B of a feature stream [n_frames][F] (window w = rows [w hop, w hop + T)) into chunk [B][T][F]; db: the
+// per-window dB reference / top_db floor first; mean / scale (device doubles [F], both or neither): the StandardScaler next
+void launch_window_gather(const float* feat, float* chunk, int64_t w0, int B, int hop, int T, int F, int db, int db_ref_max,
+                          float amin, float top_db, const double* mean, const double* scale, hipStream_t s);
 // st != null: alpha = alpha_table[st->iter] (host-precomputed per iteration: the Keras step size in double, rounded once)
 void launch_adam(float* w, const float* g, float* m, float* v, int64_t n, float alpha, float c1, float c2,
                  float eps, hipStream_t s, const StepState* st = nullptr, const float* alpha_table = nullptr);
@@ -263,6 +269,11 @@ struct FrontendTables;   // device-resident twiddles / window / sparse mel weigh
 FrontendTables* frontend_tables_create(const FrontendCfg& c);
 void frontend_tables_destroy(FrontendTables* t);
 void launch_logmel(const float* wav, int64_t n_clips, int n_samples, float* out, const FrontendTables* t, hipStream_t s);
+// ONE recording [n_samples] -> out [T][n_mels], its frames spread over the chip in runs of frontend_stream_run frames per
+// workgroup; frame f carries the bits launch_logmel gives it for the recording passed as one clip, the dB scale WITHOUT
+// the clip reference / top_db floor (un-referenced 10 log10(max(db_amin, mel)))
+int frontend_stream_run(int T, int compute_units);
+void launch_logmel_stream(const float* wav, int64_t n_samples, float* out, const FrontendTables* t, int compute_units, hipStream_t s);
 void launch_mfcc(const float* X, float* Y, int64_t rows, int n_mels, int n_mfcc, hipStream_t s);   // DCT-II ortho along the mel axis
 void launch_standardize(float* X, const double* mean, const double* scale, int64_t rows, int C, hipStream_t s);
 void colstats_finalize_f64(const float* P, int blocks, int64_t M, int C, double* mean, double* scale, hipStream_t s);

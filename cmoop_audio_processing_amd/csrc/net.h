@@ -147,6 +147,12 @@ class Net : public GemmHook {
     void train_step_stateful(const float* X, const int32_t* y, const int32_t* idx, int B);
     // inference over n rows of (X, y); returns sum of per-sample losses and #correct, fills preds (device, may be null)
     void evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum, long long* correct, int32_t* preds);
+    // Model.predict: probs [n][classes] (device) of n rows of X, inference mode, eval_batch rows per launch
+    void predict(const float* X, int64_t n, float* probs);
+    // the same over the windows [i hop, i hop + T) of a feature stream [n_frames][F]: eval_batch windows at a time are
+    // gathered (per-window dB tail when db_scale, StandardScaler when mean / scale: host doubles [F]) into one chunk buffer
+    void predict_stream(const float* feat, int64_t n_frames, int hop, bool db_scale, bool db_ref_max, float db_amin, float top_db,
+                        const double* mean, const double* scale, float* probs);
     void read_train_metrics(double* loss_sum, long long* correct, bool reset);
     void drain_profile();
     hipStream_t stream() const { return stream_; }
@@ -225,6 +231,8 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
                      EvalResult* out, const std::function<int()>& pull = {});
 
+// host-only: windows of T frames at hop frames in a stream of n_frames, 1 + (n_frames - T) / hop; throws when n_frames < T or hop < 1
+int64_t stream_windows(int64_t n_frames, int T, int hop);
 double fpr_from_confusion(const int64_t* cm, int C, int variant);
 void epoch_permutation(uint32_t seed, uint32_t epoch, int64_t n, int32_t* out);
 

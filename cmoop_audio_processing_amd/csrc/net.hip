@@ -959,6 +959,50 @@ void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum
     std::memcpy(correct, &host[1], 8);
 }
 
+void Net::predict(const float* X, int64_t n, float* probs) {
+    CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && probs)), "predict: NULL buffer");
+    for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
+        const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
+        forward(X, nullptr, s, B, false);
+        launch_softmax_probs(acts_[logits_].data, probs + s * cfg_.classes, B, cfg_.classes, stream_);
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+}
+
+int64_t stream_windows(int64_t n_frames, int T, int hop) {
+    CMOOP_REQUIRE(hop >= 1, "stream windows: hop_frames must be at least 1");
+    CMOOP_REQUIRE(T >= 1 && n_frames >= T, "stream windows: the stream has " + std::to_string(n_frames) + " frames, a window needs " + std::to_string(T));
+    return 1 + (n_frames - T) / hop;
+}
+
+void Net::predict_stream(const float* feat, int64_t n_frames, int hop, bool db_scale, bool db_ref_max, float db_amin, float top_db,
+                         const double* mean, const double* scale, float* probs) {
+    const int64_t n = stream_windows(n_frames, T_, hop);
+    CMOOP_REQUIRE(feat && probs, "predict_stream: NULL buffer");
+    CMOOP_REQUIRE((mean == nullptr) == (scale == nullptr), "predict_stream: mean and scale come together (both or neither)");
+    const int B0 = (int)std::min<int64_t>(cfg_.eval_batch, n);
+    float* chunk = static_cast<float*>(pool_alloc((size_t)B0 * T_ * F_ * 4));
+    double* ms = mean ? static_cast<double*>(pool_alloc((size_t)2 * F_ * 8)) : nullptr;
+    auto cleanup = [&]() { hipStreamSynchronize(stream_); pool_free(chunk); if (ms) pool_free(ms); };
+    try {
+        if (ms) {
+            CMOOP_HIP(hipMemcpyAsync(ms, mean, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
+            CMOOP_HIP(hipMemcpyAsync(ms + F_, scale, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
+        }
+        for (int64_t w = 0; w < n; w += cfg_.eval_batch) {       // window i sits at position i % eval_batch of chunk i / eval_batch
+            const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - w);
+            launch_window_gather(feat, chunk, w, B, hop, T_, F_, db_scale ? 1 : 0, db_ref_max ? 1 : 0, db_amin, top_db, ms,
+                                 ms ? ms + F_ : nullptr, stream_);
+            forward(chunk, nullptr, 0, B, false);
+            launch_softmax_probs(acts_[logits_].data, probs + w * cfg_.classes, B, cfg_.classes, stream_);
+        }
+    } catch (...) {
+        cleanup();
+        throw;
+    }
+    cleanup();
+}
+
 void Net::read_train_metrics(double* loss_sum, long long* correct, bool reset) {
     double host[2];
     CMOOP_HIP(hipMemcpyAsync(host, acc_train_, 16, hipMemcpyDeviceToHost, stream_));

@@ -1,0 +1,189 @@
+"""From a search result to a model that scores recordings.
+
+The search ranks candidates by (accuracy, size, FPR) and keeps no weights.  ``PopulationEvaluator.train_model`` trains
+one candidate again on its own seed and returns a ``TrainedModel``: the gene, the parameters in canonical order
+(BatchNorm moving statistics included) and, optionally, the front end and the StandardScaler the features were made
+with.  ``StreamScorer`` runs such a model over ONE recording: ``log_mel_stream`` (the front end's frames spread over the
+chip) followed by ``NetSession.predict_stream`` (overlapping windows of T frames every ``hop_frames``, each one forward
+pass; the frames two windows share are convolved again -- there is no streaming convolution cache).
+
+Train / serve difference to know about: a training clip is centre-padded, so its first and last ``n_fft / (2 hop)``
+frames see zeros where a window inside a recording sees real audio.
+
+``smooth_posteriors`` and ``detect_events`` are the usual host-side read-out of the window posteriors (float64 numpy).
+"""
+from __future__ import annotations
+
+import dataclasses
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import genes as G
+from .evaluator import EvalConfig
+from .frontend import FrontendConfig, log_mel_stream
+
+_OBJECTIVE_KEYS = ("acc", "size_mb", "fpr", "epochs_run")
+_FE_INT = ("sr", "n_fft", "win", "hop", "n_mels")
+_FE_FLOAT = ("fmin", "fmax", "log_eps", "db_amin", "top_db")
+
+
+@dataclasses.dataclass
+class TrainedModel:
+    """One trained candidate: everything ``session()`` needs to rebuild the net, in plain numpy."""
+    gene: Tuple[int, ...]
+    variant: str                       # "A" / "B"
+    classes: int
+    T: int
+    F: int
+    seed: int
+    params: np.ndarray                 # float32, canonical order (genes.param_tensors), moving statistics included
+    objectives: Dict[str, float]       # acc, size_mb, fpr, epochs_run
+    frontend: Optional[FrontendConfig] = None
+    mean: Optional[np.ndarray] = None  # StandardScaler of the training features, float64 [F]
+    scale: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        self.gene = tuple(int(v) for v in self.gene)
+        G.validate_gene(self.gene)
+        if self.variant not in ("A", "B"):
+            raise ValueError(f"variant must be 'A' or 'B', got {self.variant!r}")
+        self.params = np.ascontiguousarray(self.params, np.float32).reshape(-1)
+        want = G.param_count(self.gene, G.VARIANT_NAMES[self.variant], int(self.classes))
+        if self.params.size != want:
+            raise ValueError(f"params holds {self.params.size} values, gene {self.gene} has {want}")
+        if (self.mean is None) != (self.scale is None):
+            raise ValueError("mean and scale come together (both or neither)")
+        if self.mean is not None:
+            self.mean = np.ascontiguousarray(self.mean, np.float64).reshape(-1)
+            self.scale = np.ascontiguousarray(self.scale, np.float64).reshape(-1)
+            if self.mean.size != self.F or self.scale.size != self.F:
+                raise ValueError(f"mean and scale must hold F = {self.F} values each")
+        self.objectives = {k: (int(self.objectives[k]) if k == "epochs_run" else float(self.objectives[k]))
+                           for k in _OBJECTIVE_KEYS if k in self.objectives}
+
+    def tensors(self) -> Dict[str, np.ndarray]:
+        """{name: array} in the shapes of ``genes.param_tensors`` (views of ``params``)."""
+        out, off = {}, 0
+        for name, shape, _role in G.param_tensors(self.gene, G.VARIANT_NAMES[self.variant], self.classes):
+            n = int(np.prod(shape))
+            out[name] = self.params[off:off + n].reshape(shape)
+            off += n
+        return out
+
+    def save(self, path) -> None:
+        """One ``.npz`` (numeric arrays only, no pickle), written to exactly ``path``."""
+        d = {"gene": np.asarray(self.gene, np.int32),
+             "meta": np.asarray([G.VARIANT_NAMES[self.variant], self.classes, self.T, self.F, self.seed], np.int64),
+             "params": self.params,
+             "objectives": np.asarray([float(self.objectives.get(k, np.nan)) for k in _OBJECTIVE_KEYS], np.float64)}
+        if self.frontend is not None:
+            fe = self.frontend
+            d["frontend_int"] = np.asarray([getattr(fe, k) for k in _FE_INT] + [int(fe.scale == "db"), int(bool(fe.db_ref_max))],
+                                           np.int64)
+            d["frontend_float"] = np.asarray([getattr(fe, k) for k in _FE_FLOAT], np.float64)
+        if self.mean is not None:
+            d["mean"], d["scale"] = self.mean, self.scale
+        with open(path, "wb") as f:
+            np.savez(f, **d)
+
+    @classmethod
+    def load(cls, path) -> "TrainedModel":
+        with np.load(path, allow_pickle=False) as z:
+            variant, classes, T, F, seed = (int(v) for v in z["meta"])
+            obj = {k: float(v) for k, v in zip(_OBJECTIVE_KEYS, z["objectives"]) if not np.isnan(v)}
+            fe = None
+            if "frontend_int" in z.files:
+                fi, ff = [int(v) for v in z["frontend_int"]], [float(v) for v in z["frontend_float"]]
+                fe = FrontendConfig(**dict(zip(_FE_INT, fi[:5])), scale="db" if fi[5] else "log", db_ref_max=bool(fi[6]),
+                                    **dict(zip(_FE_FLOAT, ff)))
+            mean = z["mean"].copy() if "mean" in z.files else None
+            scale = z["scale"].copy() if "scale" in z.files else None
+            return cls(gene=tuple(int(v) for v in z["gene"]), variant="AB"[variant], classes=classes, T=T, F=F, seed=seed,
+                       params=z["params"].copy(), objectives=obj, frontend=fe, mean=mean, scale=scale)
+
+    def session(self, config: Optional[EvalConfig] = None):
+        """A ``NetSession`` holding these parameters (needs the GPU).  ``config`` supplies ``eval_batch`` and the like;
+        its variant and class count must be the model's."""
+        from .session import NetSession
+        if config is None:
+            config = EvalConfig(variant=self.variant, classes=self.classes)
+        if config.variant != self.variant or int(config.classes) != self.classes:
+            raise ValueError(f"config is variant {config.variant} / {config.classes} classes, the model is "
+                             f"{self.variant} / {self.classes}")
+        net = NetSession(self.gene, config, self.T, self.F, self.seed)
+        try:
+            net.set_params(self.params)
+        except Exception:
+            net.close()
+            raise
+        return net
+
+
+class StreamScorer:
+    """``score(recording)`` = ``log_mel_stream`` with the model's front end, then ``predict_stream`` every ``hop_frames``."""
+
+    def __init__(self, model: TrainedModel, hop_frames: int, config: Optional[EvalConfig] = None):
+        if int(hop_frames) < 1:
+            raise ValueError("hop_frames must be at least 1")
+        self.model, self.hop_frames = model, int(hop_frames)
+        self.frontend = model.frontend if model.frontend is not None else FrontendConfig()
+        if int(self.frontend.n_mels) != model.F:
+            raise ValueError(f"the front end gives {self.frontend.n_mels} mel bands, the model reads F = {model.F}")
+        self.net = model.session(config)
+
+    def close(self):
+        self.net.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def score(self, wav):
+        """wav: CUDA float32 [n_samples] -> (t_start seconds float64 [n_windows], CUDA float32 probs [n_windows, classes]);
+        window i starts at frame i * hop_frames, i.e. at ``i * hop_frames * hop / sr`` seconds."""
+        fe = self.frontend
+        feat = log_mel_stream(wav, fe)
+        probs = self.net.predict_stream(feat, self.hop_frames, frontend_config=fe if fe.scale == "db" else None,
+                                        mean=self.model.mean, scale=self.model.scale)
+        t = np.arange(int(probs.shape[0]), dtype=np.float64) * (self.hop_frames * int(fe.hop)) / float(fe.sr)
+        return t, probs
+
+
+def smooth_posteriors(p, w: int) -> np.ndarray:
+    """Causal moving average over windows: ``out[i] = mean(p[max(0, i - w + 1) : i + 1])`` (float64 [n, classes])."""
+    p = np.asarray(p, np.float64)
+    if p.ndim != 2:
+        raise ValueError("smooth_posteriors expects [n_windows, classes]")
+    if int(w) < 1:
+        raise ValueError("w must be at least 1")
+    out = np.empty_like(p)
+    for i in range(len(p)):
+        out[i] = p[max(0, i - int(w) + 1):i + 1].mean(axis=0)
+    return out
+
+
+def detect_events(t, p, threshold: float, keyword_classes: Sequence[int], refractory_windows: int) -> List[Tuple[float, int, float]]:
+    """[(t[i], class, score)]: scan the windows in order; outside a refractory span, when the largest posterior among
+    ``keyword_classes`` reaches ``threshold`` emit that class (ties: the lowest class id) and skip the next
+    ``refractory_windows`` windows."""
+    t, p = np.asarray(t, np.float64).reshape(-1), np.asarray(p, np.float64)
+    if p.ndim != 2 or len(t) != len(p):
+        raise ValueError("detect_events expects t [n] and p [n, classes]")
+    kw = sorted(set(int(c) for c in keyword_classes))
+    if not kw or kw[0] < 0 or kw[-1] >= p.shape[1]:
+        raise ValueError("keyword_classes must name classes of p")
+    if int(refractory_windows) < 0:
+        raise ValueError("refractory_windows must not be negative")
+    events, i = [], 0
+    while i < len(p):
+        scores = p[i, kw]
+        j = int(np.argmax(scores))          # first maximum = lowest class id
+        if scores[j] >= threshold:
+            events.append((float(t[i]), kw[j], float(scores[j])))
+            i += 1 + int(refractory_windows)
+        else:
+            i += 1
+    return events

@@ -337,6 +337,7 @@ class PopulationEvaluator:
         self._queue_prefix, self._generation = f"cmoop/queue/{_queue_serial[0]}", 0
         self.last_rank_of: List[int] = []   # which rank trained each candidate of the last generation
         self.last_epochs_run: List[int] = []
+        self.last_seeds: List[int] = []     # seed of each candidate of the last evaluate_individual / population call (train_model)
         self.last_seconds: List[float] = []
         self.last_queue_stats: Dict = {}     # multi-GPU diagnostics of the last generation on THIS rank (queued_map's stats)
         torch.cuda.synchronize()
@@ -404,7 +405,8 @@ class PopulationEvaluator:
     def evaluate_individual(self, hparams: Dict):
         """(accuracy, size_mb, fpr) of one candidate -- nsga_penalty.py:368-395."""
         g = G.normalize_hparams(hparams)
-        r = self.evaluate_genes([g], [self.config.seed + self.evals_done])[0]
+        self.last_seeds = [self.config.seed + self.evals_done]
+        r = self.evaluate_genes([g], self.last_seeds)[0]
         self.evals_done += 1
         self.last_epochs_run, self.last_seconds = [int(r[3])], [float(r[4])]
         self._print(r)
@@ -438,6 +440,7 @@ class PopulationEvaluator:
                              costs, 6, f"{self._queue_prefix}/{self._generation}", device="cuda", slots=self.config.n_slots,
                              stats=self.last_queue_stats)
         self.last_rank_of = [int(r) for r in res[:, 5]]
+        self.last_seeds = [int(sd) for sd in seeds]
         self.evals_done += n
         self.last_epochs_run = [int(e) for e in res[:, 3]]
         self.last_seconds = [float(s) for s in res[:, 4]]
@@ -448,6 +451,26 @@ class PopulationEvaluator:
             self._print(r)
             results.append(pack_result(ind, acc, size_mb, fpr, c))
         return results
+
+    def train_model(self, hparams, seed: int, frontend=None, mean=None, scale=None):
+        """Train ONE candidate on the resident splits and keep its weights -> ``deploy.TrainedModel``.
+
+        The body of the population call's per-candidate work (``NetSession.fit``) on the given seed: with
+        ``seed = last_seeds[i]`` it reproduces candidate i of the last generation, accuracy and FPR included.
+        ``hparams`` is the reference's dict or a gene tuple; ``frontend`` / ``mean`` / ``scale`` (the front end and the
+        StandardScaler the features were made with) ride along for ``StreamScorer``."""
+        from .deploy import TrainedModel
+        from .session import NetSession
+        g = G.normalize_hparams(hparams) if isinstance(hparams, dict) else tuple(int(v) for v in hparams)
+        G.validate_gene(g)
+        with NetSession(g, self.config, self.T, self.F, int(seed)) as net:
+            r = net.fit(self.X_train, self.y_train, self.X_val, self.y_val)
+            params = net.get_params()
+        v = G.VARIANT_NAMES[self.config.variant]
+        objectives = {"acc": float(r["acc"]), "size_mb": float(G.model_size_mb(g, v, self.config.classes)), "fpr": float(r["fpr"]),
+                      "epochs_run": int(r["epochs_run"])}
+        return TrainedModel(gene=g, variant=self.config.variant, classes=int(self.config.classes), T=self.T, F=self.F,
+                            seed=int(seed), params=params, objectives=objectives, frontend=frontend, mean=mean, scale=scale)
 
     def _print(self, r):
         if self.config.verbose:

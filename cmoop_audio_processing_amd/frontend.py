@@ -140,6 +140,28 @@ def log_mel(wav, config: FrontendConfig | None = None):
     return out
 
 
+def log_mel_stream(wav, config: FrontendConfig | None = None):
+    """ONE recording, CUDA float32 [L] -> CUDA float32 [1 + L//hop, n_mels], its frames spread over the whole chip.
+
+    Log scale: frame for frame the bits of ``log_mel(wav[None], config)[0]``.  dB scale: the UN-REFERENCED
+    ``10 log10(max(db_amin, mel))`` -- the reference and the ``top_db`` floor are quantities of a window, applied by
+    ``NetSession.predict_stream`` to each window it cuts from the stream.  ``config=None`` is ``FrontendConfig()``."""
+    import torch
+    if config is None:
+        config = FrontendConfig()
+    if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 1):
+        raise ValueError("log_mel_stream expects a CUDA float32 tensor [n_samples]")
+    wav = wav.contiguous()
+    L = int(wav.shape[0])
+    if L < 1:
+        raise ValueError("log_mel_stream: the recording is empty")
+    out = torch.empty((config.frames(L), config.n_mels), dtype=torch.float32, device=wav.device)
+    st = config._struct()
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_logmel_stream(C.byref(st), _lib.ptr(wav), C.c_int64(L), _lib.ptr(out)))
+    return out
+
+
 def mfcc(wav, n_mfcc: int | None = None, config: FrontendConfig | None = None):
     """wav: CUDA float32 [N, L] -> CUDA float32 [N, T, n_mfcc]: DCT-II (ortho) of the log-mel frames.
 

@@ -23,6 +23,7 @@ class NetSession:
         n = C.c_int64()
         _lib.check(_lib.lib().cmoop_net_total_params(self._h, C.byref(n)))
         self.n_params = int(n.value)
+        self.T, self.F = int(T), int(F)
 
     def close(self):
         if self._h:
@@ -73,6 +74,51 @@ class NetSession:
         ls, corr = C.c_double(), C.c_int64()
         _lib.check(_lib.lib().cmoop_net_evaluate(self._h, _lib.ptr(X), _lib.ptr(y), C.c_int64(n), C.byref(ls), C.byref(corr), _lib.ptr(preds)))
         return ls.value / max(n, 1), corr.value / max(n, 1), preds
+
+    # -- Model.predict: probabilities of rows, and of the overlapping windows of a feature stream ------------------
+    def predict_proba(self, X):
+        """X: CUDA float32 [n, T, F] -> CUDA float32 [n, classes], inference mode, ``eval_batch`` rows per launch.
+        Row r's arg max is the prediction ``evaluate`` returns for it (the same softmax arithmetic)."""
+        import torch
+        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 3):
+            raise ValueError("predict_proba expects a CUDA float32 tensor [n, T, F]")
+        if (int(X.shape[1]), int(X.shape[2])) != (self.T, self.F):
+            raise ValueError(f"predict_proba: rows are {int(X.shape[1])} x {int(X.shape[2])}, the net reads {self.T} x {self.F}")
+        X = X.contiguous()
+        n = int(X.shape[0])
+        probs = torch.empty((n, int(self.config.classes)), dtype=torch.float32, device=X.device)
+        torch.cuda.synchronize()
+        _lib.check(_lib.lib().cmoop_net_predict(self._h, _lib.ptr(X), C.c_int64(n), _lib.ptr(probs)))
+        return probs
+
+    def predict_stream(self, feat, hop_frames: int, frontend_config=None, mean=None, scale=None):
+        """feat: CUDA float32 [n_frames, F] (``log_mel_stream``) -> CUDA float32 [n_windows, classes].
+
+        Window i is rows [i * hop_frames, i * hop_frames + T).  Per window: with a dB-scale ``frontend_config`` its own
+        reference / top_db floor first (``feat`` then holds the un-referenced dB values ``log_mel_stream`` gives), then
+        ``(v - mean) / scale`` when the StandardScaler's float64 ``mean`` and ``scale`` [F] are given, then forward and
+        softmax.  ``feat`` is only read; memory is one ``eval_batch`` chunk of windows however long the stream is."""
+        import torch
+        if not (isinstance(feat, torch.Tensor) and feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 2):
+            raise ValueError("predict_stream expects a CUDA float32 tensor [n_frames, F]")
+        if int(feat.shape[1]) != self.F:
+            raise ValueError(f"predict_stream: the stream has {int(feat.shape[1])} features per frame, the net reads {self.F}")
+        if (mean is None) != (scale is None):
+            raise ValueError("predict_stream: mean and scale come together (both or neither)")
+        if mean is not None:
+            mean, scale = np.ascontiguousarray(mean, np.float64).reshape(-1), np.ascontiguousarray(scale, np.float64).reshape(-1)
+            if mean.size != self.F or scale.size != self.F:
+                raise ValueError(f"predict_stream: mean and scale must hold {self.F} values each")
+        feat = feat.contiguous()
+        n_frames, nw = int(feat.shape[0]), C.c_int64()
+        _lib.check(_lib.lib().cmoop_stream_windows(C.c_int64(n_frames), C.c_int32(self.T), C.c_int32(int(hop_frames)), C.byref(nw)))
+        st = frontend_config._struct() if frontend_config is not None else None
+        probs = torch.empty((int(nw.value), int(self.config.classes)), dtype=torch.float32, device=feat.device)
+        torch.cuda.synchronize()
+        _lib.check(_lib.lib().cmoop_net_predict_stream(self._h, _lib.ptr(feat), C.c_int64(n_frames), C.c_int32(int(hop_frames)),
+                                                       C.byref(st) if st is not None else None, _lib.ptr(mean), _lib.ptr(scale),
+                                                       _lib.ptr(probs)))
+        return probs
 
     # -- full training state / epoch-granular driving (re-synchronised parity tests) -----------------------------
     def get_state(self):

@@ -160,6 +160,18 @@ int cmoop_logmel_ex(const cmoop_frontend_config* c, const float* wav_dev /* [n_c
 /* average milliseconds of `iters` launches of the call above between two HIP events on the library's stream, after 3 warm-up launches */
 int cmoop_logmel_ex_time(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_clips, int32_t n_samples, float* out_dev,
                          int32_t iters, double* avg_ms);
+/* Stream front end: ONE recording, its frames spread over the whole chip.  out_dev [T][n_mels], T = cmoop_frontend_frames.
+ * scale 0: the values cmoop_logmel_ex gives for the recording passed as one clip, bit for bit (the same kernel arithmetic,
+ *          the 512-point kernel included; only the grid differs).
+ * scale 1: the UN-REFERENCED dB value 10 log10(max(db_amin, mel)); db_ref_max / top_db are per-window quantities and are
+ *          applied by cmoop_net_predict_stream, not here.
+ * Domain: cmoop_frontend_check's, 1 <= n_samples < 2^31 - 2 n_fft (the kernels index samples in 32 bits), T * n_mels < 2^31. */
+int cmoop_logmel_stream(const cmoop_frontend_config* c, const float* wav_dev /* [n_samples] */, int64_t n_samples, float* out_dev);
+/* as cmoop_logmel_ex_time: average milliseconds of `iters` launches between two HIP events after 3 warm-up launches */
+int cmoop_logmel_stream_time(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_samples, float* out_dev,
+                             int32_t iters, double* avg_ms);
+/* host-only: n_windows = 1 + (n_frames - T) / hop_frames; error when n_frames < T or hop_frames < 1 */
+int cmoop_stream_windows(int64_t n_frames, int32_t T, int32_t hop_frames, int64_t* n_windows);
 /* optional MFCC features: DCT-II, ortho-normalised, along the mel axis of log-mel rows; first n_mfcc coefficients.
  * The reference ships no front end; its comment at ablation_study/sa_nsga_init.py:68 calls the stored features MFCCs. */
 int cmoop_mfcc(const float* logmel_dev /* [rows][n_mels] */, int64_t rows, int32_t n_mels, int32_t n_mfcc,
@@ -190,6 +202,23 @@ int cmoop_net_train_step(cmoop_net* net, const float* x_dev, const int32_t* y_de
 int cmoop_net_evaluate(cmoop_net* net, const float* x_dev, const int32_t* y_dev, int64_t n, double* loss_sum,
                        int64_t* correct, int32_t* preds_dev);
 int cmoop_net_train_metrics(cmoop_net* net, double* loss_sum, int64_t* correct, int32_t reset);
+/* Model.predict: class probabilities of n rows, inference mode (moving statistics, no dropout), eval_batch rows per launch;
+ * p_j = exp(z_j - max) / sum, the p behind cmoop_net_evaluate's loss, so argmax p is the prediction that call returns */
+int cmoop_net_predict(cmoop_net* net, const float* x_dev /* [n][T][F] */, int64_t n, float* probs_dev /* [n][classes] */);
+/* Sliding-window scoring: window i = rows [i*hop_frames, i*hop_frames + T) of feat_dev [n_frames][F] (T, F: the net's).
+ * Per window, in this order:
+ *   (a) when db != NULL and db->scale == 1: cmax = the window's largest value,
+ *       ref = db_ref_max ? cmax : 10 log10(max(db_amin, 1)),
+ *       floor = top_db >= 0 ? (cmax - ref) - top_db : -inf, value = max(value - ref, floor)
+ *       -- the dB tail of cmoop_logmel_ex with "window" for "clip", on the un-referenced values of cmoop_logmel_stream;
+ *   (b) when mean_host != NULL (then scale_host too, both [F]): (float)(((double)v - mean[c]) / scale[c]),
+ *       as cmoop_standardize_apply;
+ *   (c) forward + softmax, eval_batch windows per launch.
+ * feat_dev is not modified and the window tensor is never materialised (one eval_batch * T * F chunk, whatever n_frames).
+ * probs_dev [n_windows][classes], n_windows = cmoop_stream_windows(n_frames, T, hop_frames). */
+int cmoop_net_predict_stream(cmoop_net* net, const float* feat_dev, int64_t n_frames, int32_t hop_frames,
+                             const cmoop_frontend_config* db, const double* mean_host, const double* scale_host,
+                             float* probs_dev);
 /* Full training state of the net (host arrays of cmoop_net_total_params floats; any pointer may be NULL): parameters in
  * canonical order INCLUDING the BatchNorm moving statistics, Adam's m and v in the same layout (zero in the
  * non-trainable slots), optimizer.iterations and the global train-step count that keys the dropout masks.  With these a
