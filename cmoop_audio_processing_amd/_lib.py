@@ -116,6 +116,24 @@ def last_kernels():
     return [k for k in buf.value.decode().split(";") if k]
 
 
+def plan_convs(gene, variant, T, F):
+    """[(H, W, Cin, Cout, KS, stride, feeds_bn)] of the MFMA conv layers of a candidate, forward order (host-only)."""
+    g, n, cap = (C.c_int32 * 6)(*gene), C.c_int32(), 16
+    rows = (C.c_int32 * (7 * cap))()
+    check(lib().cmoop_plan_convs(g, C.c_int32(variant), C.c_int32(T), C.c_int32(F), rows, C.c_int32(cap), C.byref(n)))
+    assert n.value <= cap
+    return [tuple(rows[7 * i:7 * i + 7]) for i in range(n.value)]
+
+
+def net_launch_plan(gene, config, T, F, B, train):
+    """Launch-path variants of the MFMA conv launches of one train step (train) or inference pass of a net at batch B,
+    in launch order, under the net's shared split-K workspace (host-only); config: a Config struct."""
+    g, buf = (C.c_int32 * 6)(*gene), C.create_string_buffer(8192)
+    check(lib().cmoop_net_launch_plan(g, C.byref(config), C.c_int32(T), C.c_int32(F), C.c_int32(B), C.c_int32(int(train)), buf,
+                                      C.c_int32(8192)))
+    return [k for k in buf.value.decode().split(";") if k]
+
+
 def profile_entries():
     """[(kernel name, launches, total ms, total flops)] of the HIP-event-sampled MFMA GEMM launches."""
     L, cnt, out = lib(), C.c_int32(), []

@@ -101,14 +101,48 @@ static NetConfig to_cfg(const cmoop_config* c) {
     return n;
 }
 
-static ConvGeom make_geom(int B, int H, int W, int Cin, int Cout, int KS, int stride) {
-    ConvGeom g;
-    g.B = B; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.KH = g.KW = KS; g.stride = stride;
-    g.OH = (H + stride - 1) / stride; g.OW = (W + stride - 1) / stride;
-    g.pad_t = std::max((g.OH - 1) * stride + KS - H, 0) / 2;
-    g.pad_l = std::max((g.OW - 1) * stride + KS - W, 0) / 2;
-    return g;
+static Dataset to_dataset(const cmoop_dataset* ds) {
+    Dataset d;
+    d.x_train = ds->x_train; d.y_train = ds->y_train; d.n_train = ds->n_train;
+    d.x_val = ds->x_val; d.y_val = ds->y_val; d.n_val = ds->n_val; d.T = ds->T; d.F = ds->F;
+    return d;
 }
+
+// average ms of `iters` back-to-back runs of once() on stream s, after three warm-up runs (HIP events)
+template <class F>
+static double time_launches(hipStream_t s, int iters, F&& once) {
+    for (int i = 0; i < 3; ++i) once();
+    hipEvent_t a, b;
+    CMOOP_HIP(hipEventCreate(&a));
+    CMOOP_HIP(hipEventCreate(&b));
+    CMOOP_HIP(hipEventRecord(a, s));
+    for (int i = 0; i < iters; ++i) once();
+    CMOOP_HIP(hipEventRecord(b, s));
+    CMOOP_HIP(hipEventSynchronize(b));
+    float ms = 0.f;
+    CMOOP_HIP(hipEventElapsedTime(&ms, a, b));
+    hipEventDestroy(a); hipEventDestroy(b);
+    return (double)ms / std::max(1, iters);
+}
+
+// device scratch of one call: released when the call ends, after its stream has drained
+struct Scratch {
+    hipStream_t s;
+    std::vector<void*> ptrs;
+    explicit Scratch(hipStream_t stream) : s(stream) {}
+    Scratch(const Scratch&) = delete;
+    ~Scratch() { hipStreamSynchronize(s); for (void* p : ptrs) hipFree(p); }
+    float* floats(size_t n) {   // null for n == 0
+        void* p = nullptr;
+        if (n) { CMOOP_HIP(hipMalloc(&p, n * 4)); ptrs.push_back(p); }
+        return static_cast<float*>(p);
+    }
+    void* rowtab(const ConvGeom& g, int rows) {   // a lone layer's row table of geometry g (rows == 0: it has none)
+        void* t = floats((size_t)rows * 2);
+        if (t) launch_build_rowtab(g, t, s);
+        return t;
+    }
+};
 
 // records the launch-path variant names of the GEMM launches a kernel-level call makes (cmoop_last_kernels)
 struct RecordingHook : GemmHook {
@@ -144,54 +178,42 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
     return guard([&] { *out = fwd_flops_per_sample(gene, variant, classes, T, F); });
 }
 
+// both population calls; next == NULL: candidates are taken longest-first from a process-local counter
+static void eval_population_abi(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n,
+                                cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
+                                double* val_loss, double* seconds, int32_t* evaluated) {
+    CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
+    CMOOP_REQUIRE(n >= 0, "negative population size");
+    NetConfig c = to_cfg(cfg);
+    const Dataset d = to_dataset(ds);
+    CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
+    for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
+    std::vector<EvalResult> r(n);
+    if (next) eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); });
+    else eval_population(c, d, genes, seeds, n, r.data());
+    for (int i = 0; i < n; ++i) {
+        if (evaluated) evaluated[i] = r[i].evaluated;
+        if (acc) acc[i] = r[i].acc;
+        if (size_mb) size_mb[i] = r[i].size_mb;
+        if (fpr) fpr[i] = r[i].fpr;
+        if (epochs_run) epochs_run[i] = r[i].epochs_run;
+        if (val_loss) val_loss[i] = r[i].val_loss;
+        if (seconds) seconds[i] = r[i].seconds;
+    }
+}
+
 int cmoop_eval_population(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds,
                           int32_t n, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
                           double* seconds) {
-    return guard([&] {
-        CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
-        CMOOP_REQUIRE(n >= 0, "negative population size");
-        NetConfig c = to_cfg(cfg);
-        Dataset d;
-        d.x_train = ds->x_train; d.y_train = ds->y_train; d.n_train = ds->n_train;
-        d.x_val = ds->x_val; d.y_val = ds->y_val; d.n_val = ds->n_val; d.T = ds->T; d.F = ds->F;
-        CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
-        for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
-        std::vector<EvalResult> r(n);
-        eval_population(c, d, genes, seeds, n, r.data());
-        for (int i = 0; i < n; ++i) {
-            if (acc) acc[i] = r[i].acc;
-            if (size_mb) size_mb[i] = r[i].size_mb;
-            if (fpr) fpr[i] = r[i].fpr;
-            if (epochs_run) epochs_run[i] = r[i].epochs_run;
-            if (val_loss) val_loss[i] = r[i].val_loss;
-            if (seconds) seconds[i] = r[i].seconds;
-        }
-    });
+    return guard([&] { eval_population_abi(cfg, ds, genes, seeds, n, nullptr, nullptr, acc, size_mb, fpr, epochs_run, val_loss, seconds, nullptr); });
 }
 
 int cmoop_eval_population_pull(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds,
                                int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr,
                                int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
     return guard([&] {
-        CMOOP_REQUIRE(ds && genes && seeds && next && evaluated, "NULL argument");
-        CMOOP_REQUIRE(n >= 0, "negative population size");
-        NetConfig c = to_cfg(cfg);
-        Dataset d;
-        d.x_train = ds->x_train; d.y_train = ds->y_train; d.n_train = ds->n_train;
-        d.x_val = ds->x_val; d.y_val = ds->y_val; d.n_val = ds->n_val; d.T = ds->T; d.F = ds->F;
-        CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
-        for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
-        std::vector<EvalResult> r(n);
-        eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); });
-        for (int i = 0; i < n; ++i) {
-            evaluated[i] = r[i].evaluated;
-            if (acc) acc[i] = r[i].acc;
-            if (size_mb) size_mb[i] = r[i].size_mb;
-            if (fpr) fpr[i] = r[i].fpr;
-            if (epochs_run) epochs_run[i] = r[i].epochs_run;
-            if (val_loss) val_loss[i] = r[i].val_loss;
-            if (seconds) seconds[i] = r[i].seconds;
-        }
+        CMOOP_REQUIRE(next && evaluated, "NULL argument");
+        eval_population_abi(cfg, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds, evaluated);
     });
 }
 
@@ -207,22 +229,41 @@ int cmoop_conv_launch_plan(int32_t op, int32_t B, int32_t H, int32_t W, int32_t 
     return guard([&] {
         CMOOP_REQUIRE(name && name_cap > 0 && op >= 0 && op <= 2, "launch_plan: bad arguments");
         CMOOP_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cin >= 16 && Cout >= 1 && KS >= 1 && stride >= 1, "bad conv shape");
-        const ConvGeom g = make_geom(B, H, W, Cin, Cout, KS, stride);
-        const bool tab = KS * KS <= 32;              // Net::build_plan builds the layer's row tables under this condition
-        int flags = 0, code = 0, cls = 0;
-        GemmEpilogue e;
-        if (op == 0) {
-            code = igemm_fwd_plan(g, e, igemm_splitk_workspace(g), want_stats != 0, tab, &flags);
-        } else if (op == 1) {
-            CMOOP_REQUIRE(ilog2_exact(Cout) >= 4, "launch_plan: the dgrad of this layer does not run on the MFMA kernel");
-            const ConvGeom gd = dgrad_geometry(g);
-            if (stride != 1) { e.out_stride = stride; e.OHf = H; e.OWf = W; e.accumulate = 1; }
-            code = igemm_fwd_plan(gd, e, igemm_splitk_workspace(gd), false, tab, &flags);
-        } else {
-            cls = 1;
-            code = igemm_wgrad_plan(g, wgrad_slices(g), GEMM_DEFAULT, tab, &flags);
+        // a lone layer: the split-K workspace is the launch's own geometry's (cmoop_conv_*_trainer allocate the same)
+        const ConvLayer L{H, W, Cin, Cout, KS, stride};
+        const std::string v = op == 0   ? L.plan_forward(B, want_stats != 0, igemm_splitk_workspace(L.geometry(B)), GEMM_DEFAULT)
+                              : op == 1 ? L.plan_dgrad(B, igemm_splitk_workspace(L.dgrad_geom(B)), GEMM_DEFAULT)
+                                        : L.plan_wgrad(B, GEMM_DEFAULT);
+        std::snprintf(name, name_cap, "%s", v.c_str());
+    });
+}
+
+int cmoop_plan_convs(const int32_t gene[6], int32_t variant, int32_t T, int32_t F, int32_t* layers, int32_t cap, int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(gene && count && (variant == 0 || variant == 1) && T >= 1 && F >= 1 && cap >= 0 && (layers || cap == 0), "plan_convs: bad arguments");
+        NetConfig cfg;
+        cfg.variant = variant;
+        int n = 0;
+        for (const Op& op : plan_net(gene, cfg, T, F).ops) {
+            if (op.kind != OP_CONV) continue;
+            if (n < cap) {
+                const int32_t row[7] = {op.H, op.W, op.Cin, op.Cout, op.KS, op.stride, op.feeds_bn};
+                std::memcpy(layers + 7 * n, row, sizeof(row));
+            }
+            ++n;
         }
-        std::snprintf(name, name_cap, "%s", gemm_variant_name(cls, code, flags).c_str());
+        *count = n;
+    });
+}
+
+int cmoop_net_launch_plan(const int32_t gene[6], const cmoop_config* cfg, int32_t T, int32_t F, int32_t B, int32_t train, char* buf,
+                          int32_t cap) {
+    return guard([&] {
+        CMOOP_REQUIRE(gene && buf && cap > 0 && T >= 1 && F >= 1, "net_launch_plan: bad arguments");
+        const NetConfig c = to_cfg(cfg);
+        const std::string v = plan_net(gene, c, T, F).launch_plan(c.batch, std::max(c.batch, c.eval_batch), B, train != 0);
+        CMOOP_REQUIRE((int)v.size() < cap, "net_launch_plan: buffer too small");
+        std::memcpy(buf, v.c_str(), v.size() + 1);
     });
 }
 
@@ -231,7 +272,7 @@ int cmoop_halo_tile_check(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t 
     return guard([&] {
         CMOOP_REQUIRE(rows_bound && rows_needed && rows_stageable && B >= 1 && H >= 1 && W >= 1 && Cin >= 16 && Cout >= 1 && KS >= 1, "bad conv shape");
         int b = 0, n = 0, c = 0;
-        halo_rows_bound_and_need(make_geom(B, H, W, Cin, Cout, KS, 1), &b, &n, &c);
+        halo_rows_bound_and_need(conv_geometry(B, H, W, Cin, Cout, KS, 1), &b, &n, &c);
         *rows_bound = b; *rows_needed = n; *rows_stageable = c;
     });
 }
@@ -239,7 +280,7 @@ int cmoop_halo_tile_check(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t 
 int cmoop_wgrad_slices(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t* out) {
     return guard([&] {
         CMOOP_REQUIRE(out && B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && KS >= 1 && stride >= 1, "bad conv shape");
-        *out = wgrad_slices(make_geom(B, H, W, Cin, Cout, KS, stride));
+        *out = wgrad_slices(conv_geometry(B, H, W, Cin, Cout, KS, stride));
     });
 }
 
@@ -319,18 +360,7 @@ int cmoop_logmel_ex_time(const cmoop_frontend_config* c, const float* wav_dev, i
         CMOOP_REQUIRE(n_samples >= 1 && n_clips >= 1 && iters >= 1 && avg_ms, "logmel_ex_time: n_samples, n_clips, iters >= 1");
         const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
         hipStream_t s = lib_stream();
-        for (int i = 0; i < 3; ++i) launch_logmel(wav_dev, n_clips, n_samples, out_dev, tables.get(), s);
-        hipEvent_t a, b;
-        CMOOP_HIP(hipEventCreate(&a));
-        CMOOP_HIP(hipEventCreate(&b));
-        CMOOP_HIP(hipEventRecord(a, s));
-        for (int i = 0; i < iters; ++i) launch_logmel(wav_dev, n_clips, n_samples, out_dev, tables.get(), s);
-        CMOOP_HIP(hipEventRecord(b, s));
-        CMOOP_HIP(hipEventSynchronize(b));
-        float ms = 0.f;
-        CMOOP_HIP(hipEventElapsedTime(&ms, a, b));
-        hipEventDestroy(a); hipEventDestroy(b);
-        *avg_ms = (double)ms / iters;
+        *avg_ms = time_launches(s, iters, [&] { launch_logmel(wav_dev, n_clips, n_samples, out_dev, tables.get(), s); });
     });
 }
 
@@ -359,18 +389,7 @@ int cmoop_logmel_stream_time(const cmoop_frontend_config* c, const float* wav_de
         const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
         const int cu = compute_units_of_current_device();
         hipStream_t s = lib_stream();
-        for (int i = 0; i < 3; ++i) launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s);
-        hipEvent_t a, b;
-        CMOOP_HIP(hipEventCreate(&a));
-        CMOOP_HIP(hipEventCreate(&b));
-        CMOOP_HIP(hipEventRecord(a, s));
-        for (int i = 0; i < iters; ++i) launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s);
-        CMOOP_HIP(hipEventRecord(b, s));
-        CMOOP_HIP(hipEventSynchronize(b));
-        float ms = 0.f;
-        CMOOP_HIP(hipEventElapsedTime(&ms, a, b));
-        hipEventDestroy(a); hipEventDestroy(b);
-        *avg_ms = (double)ms / iters;
+        *avg_ms = time_launches(s, iters, [&] { launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s); });
     });
 }
 
@@ -395,29 +414,26 @@ int cmoop_standardize_fit(const float* x_dev, int64_t rows, int32_t cols, double
         CMOOP_REQUIRE(rows >= 1 && cols >= 4 && cols % 4 == 0, "standardize: cols must be a multiple of 4");
         hipStream_t s = lib_stream();
         const int nb = colreduce_blocks(rows, cols);
-        float* P = nullptr;
-        double* ms = nullptr;
-        CMOOP_HIP(hipMalloc(&P, (size_t)nb * 2 * cols * 4));
-        CMOOP_HIP(hipMalloc(&ms, (size_t)2 * cols * 8));
+        Scratch m(s);
+        float* P = m.floats((size_t)nb * 2 * cols);
+        double* ms = reinterpret_cast<double*>(m.floats((size_t)4 * cols));
         launch_colstats(x_dev, P, rows, cols, nb, s);
         colstats_finalize_f64(P, nb, rows, cols, ms, ms + cols, s);
         CMOOP_HIP(hipMemcpyAsync(mean_host, ms, cols * 8, hipMemcpyDeviceToHost, s));
         CMOOP_HIP(hipMemcpyAsync(scale_host, ms + cols, cols * 8, hipMemcpyDeviceToHost, s));
         CMOOP_HIP(hipStreamSynchronize(s));
-        hipFree(P); hipFree(ms);
     });
 }
 
 int cmoop_standardize_apply(float* x_dev, int64_t rows, int32_t cols, const double* mean_host, const double* scale_host) {
     return guard([&] {
         hipStream_t s = lib_stream();
-        double* ms = nullptr;
-        CMOOP_HIP(hipMalloc(&ms, (size_t)2 * cols * 8));
+        Scratch m(s);
+        double* ms = reinterpret_cast<double*>(m.floats((size_t)4 * cols));
         CMOOP_HIP(hipMemcpyAsync(ms, mean_host, cols * 8, hipMemcpyHostToDevice, s));
         CMOOP_HIP(hipMemcpyAsync(ms + cols, scale_host, cols * 8, hipMemcpyHostToDevice, s));
         launch_standardize(x_dev, ms, ms + cols, rows, cols, s);
         CMOOP_HIP(hipStreamSynchronize(s));
-        hipFree(ms);
     });
 }
 
@@ -535,9 +551,7 @@ int cmoop_net_fit(cmoop_net* h, const cmoop_dataset* ds, int32_t hist_cap, doubl
                   int32_t* epochs_run, int32_t* best_epoch, double* acc, double* fpr, double* val_loss) {
     return guard([&] {
         CMOOP_REQUIRE(ds && ds->x_train && ds->y_train && ds->x_val && ds->y_val, "fit: dataset pointers are NULL");
-        Dataset d;
-        d.x_train = ds->x_train; d.y_train = ds->y_train; d.n_train = ds->n_train;
-        d.x_val = ds->x_val; d.y_val = ds->y_val; d.n_val = ds->n_val; d.T = ds->T; d.F = ds->F;
+        const Dataset d = to_dataset(ds);
         CMOOP_REQUIRE(d.T == h->net->feature_T() && d.F == h->net->feature_F(), "fit: dataset feature shape differs from the net's");
         FitHistory hist;
         const EvalResult r = fit_and_read_out(*h->net, h->net->config(), d, h->net->seed(), &hist);
@@ -606,21 +620,18 @@ int cmoop_conv_fwd(const float* x, const float* w, const float* bias, float* y, 
     return guard([&] {
         g_last_kernels.clear();
         hipStream_t s = lib_stream();
+        Scratch m(s);
         if (Cin == 1) {
             CMOOP_REQUIRE(stride == 1 && bias, "first-layer conv: stride 1 with bias");
             launch_conv1_fwd(x, nullptr, 0, w, bias, y, B, H, W, Cout, KS, relu, s);
         } else {
             GemmEpilogue e;
             e.bias = bias; e.relu = relu;
-            const ConvGeom g = make_geom(B, H, W, Cin, Cout, KS, stride);
+            const ConvGeom g = conv_geometry(B, H, W, Cin, Cout, KS, stride);
             const size_t skf = igemm_splitk_workspace(g);
-            float* sk = nullptr;
-            if (skf) CMOOP_HIP(hipMalloc(&sk, skf * 4));
             int flags = 0;
-            const int code = launch_igemm_fwd(x, w, y, g, e, s, nullptr, sk, skf, nullptr, nullptr, 0, &flags);
+            const int code = launch_igemm_fwd(x, w, y, g, e, s, nullptr, m.floats(skf), skf, nullptr, nullptr, 0, &flags);
             g_last_kernels = gemm_variant_name(0, code, flags);
-            CMOOP_HIP(hipStreamSynchronize(s));
-            if (sk) hipFree(sk);
         }
         CMOOP_HIP(hipStreamSynchronize(s));
     });
@@ -630,111 +641,80 @@ int cmoop_conv_bwd(const float* x, const float* w, const float* dy, float* dx, f
                    int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t mask_relu) {
     return guard([&] {
         hipStream_t s = lib_stream();
+        Scratch m(s);
         if (Cin == 1) {
             const int nb = conv1_wgrad_blocks(B, H, W);
             const int64_t per = (int64_t)Cout * (KS * KS + 1);
-            float *P = nullptr, *tmp = nullptr;
-            CMOOP_HIP(hipMalloc(&P, (size_t)nb * per * 4));
-            CMOOP_HIP(hipMalloc(&tmp, (size_t)per * 4));
+            float *P = m.floats((size_t)nb * per), *tmp = m.floats((size_t)per);
             launch_conv1_wgrad(x, nullptr, 0, dy, P, B, H, W, Cout, KS, s);
             launch_reduce_slices(P, tmp, nb, per, s);
             CMOOP_HIP(hipMemcpyAsync(dw, tmp, (size_t)Cout * KS * KS * 4, hipMemcpyDeviceToDevice, s));
             CMOOP_HIP(hipMemcpyAsync(db, tmp + (size_t)Cout * KS * KS, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
             CMOOP_HIP(hipStreamSynchronize(s));
-            hipFree(P); hipFree(tmp);
             return;
         }
-        const ConvGeom g = make_geom(B, H, W, Cin, Cout, KS, stride);
-        float *wg = nullptr, *red = nullptr, *wd = nullptr, *sk = nullptr;
-        const size_t wg_floats = (size_t)wgrad_slices(g) * g.Cout * (g.K() + 1);
-        CMOOP_HIP(hipMalloc(&wg, wg_floats * 4));
-        CMOOP_HIP(hipMalloc(&red, ((size_t)1024 * 2 * Cout + 2 * Cout + 64) * 4));
-        CMOOP_HIP(hipMalloc(&wd, (size_t)g.Cout * g.K() * 4));
-        void* tab = nullptr;
-        const int tab_rows = (KS * KS <= 32) ? rowtab_rows(g) : 0;
-        if (tab_rows) {
-            CMOOP_HIP(hipMalloc(&tab, (size_t)tab_rows * 8));
-            launch_build_rowtab(g, tab, s);
-        }
+        // the launchers with defaults: this batch's slabs, separate dw / db reduction, no dgrad row table, dgrad split-K
+        // slabs for stride-1 layers only
+        const ConvLayer L{H, W, Cin, Cout, KS, stride};
+        ConvBuffers buf;
+        buf.slab_floats = L.slab_floats_at(B);
+        buf.slabs = m.floats(buf.slab_floats);
+        buf.wd = m.floats(L.flip_floats());
+        buf.tab_rows = L.table_rows(B);
+        buf.tab = m.rowtab(L.geometry(B), buf.tab_rows);
         g_last_kernels.clear();
         RecordingHook hook(&g_last_kernels);
-        conv_backward_weights(x, dy, dw, db, g, wg, wg_floats, s, &hook, GEMM_DEFAULT, tab, tab_rows);
+        L.wgrad(x, dy, dw, db, B, buf, GEMM_DEFAULT, s, &hook);
         if (dx) {
             int accumulate = 0;
             if (stride != 1) {
                 CMOOP_HIP(hipMemsetAsync(dx, 0, (size_t)B * H * W * Cin * 4, s));
                 accumulate = 1;
             }
-            ConvGeom gd = g;
-            gd.H = g.OH; gd.W = g.OW; gd.Cin = g.Cout; gd.Cout = g.Cin; gd.OH = g.H; gd.OW = g.W;
-            const size_t skf = (stride == 1 && Cout >= 16 && (Cout & (Cout - 1)) == 0) ? igemm_splitk_workspace(gd) : 0;
-            if (skf) CMOOP_HIP(hipMalloc(&sk, skf * 4));
-            conv_backward_data(dy, w, dx, g, wd, mask_relu ? x : nullptr, 1.f, accumulate, s, &hook, sk, skf);
+            buf.splitk_floats = (stride == 1 && L.mfma_dgrad()) ? igemm_splitk_workspace(L.dgrad_geom(B)) : 0;
+            buf.splitk = m.floats(buf.splitk_floats);
+            L.dgrad(dy, w, dx, B, mask_relu ? x : nullptr, 1.f, accumulate, false, buf, GEMM_DEFAULT, s, &hook);
         }
         CMOOP_HIP(hipStreamSynchronize(s));
-        hipFree(wg); hipFree(red); hipFree(wd);
-        if (sk) hipFree(sk);
-        if (tab) hipFree(tab);
     });
 }
 
-// ---- the same two operations launched as the trainer launches them -------------------
-// ---- the same two operations launched as the trainer launches them -------------------
+// ---- the same two operations launched as the trainer launches them: ConvLayer's launches, with a lone layer's buffers
+//      (tables and split-K workspace of the batch at hand; Net's are shared and planned for its batch / eval_batch) ------
 int cmoop_conv_fwd_trainer(const float* x, const float* w, const float* bias, float* y, int32_t B, int32_t H, int32_t W,
                            int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t relu, double* col_sum,
                            double* col_sumsq, int32_t* stats_fused) {
     return guard([&] {
         g_last_kernels.clear();
         hipStream_t s = lib_stream();
-        const ConvGeom g = make_geom(B, H, W, Cin, Cout, KS, stride);
-        const int64_t M = g.M();
+        Scratch m(s);
+        const ConvLayer L{H, W, Cin, Cout, KS, stride};
         GemmEpilogue e;
         e.bias = bias; e.relu = relu;
-        float *sk = nullptr, *red = nullptr;
-        void* tab = nullptr;
-        const size_t skf = igemm_splitk_workspace(g);
         const bool want_stats = col_sum != nullptr && col_sumsq != nullptr;
         CMOOP_REQUIRE(!want_stats || Cout % 4 == 0, "statistics need Cout % 4 == 0");
-        auto cleanup = [&] { hipStreamSynchronize(s); if (sk) hipFree(sk); if (red) hipFree(red); if (tab) hipFree(tab); };
-        try {
-            if (skf) CMOOP_HIP(hipMalloc(&sk, skf * 4));
-            const int tab_rows = (KS * KS <= 32) ? rowtab_rows(g) : 0;     // Net::build_plan's condition
-            if (tab_rows) {
-                CMOOP_HIP(hipMalloc(&tab, (size_t)tab_rows * 8));
-                launch_build_rowtab(g, tab, s);
-            }
-            size_t red_floats = 0;
-            if (want_stats) {   // Net::build_plan's sizing of the statistics partials
-                const size_t blocks = std::max<size_t>((size_t)colreduce_blocks(M, Cout), (size_t)cdiv64(M, 64));
-                red_floats = blocks * 2 * Cout + 2 * Cout;
-                CMOOP_HIP(hipMalloc(&red, red_floats * 4));
-                e.stats = red;
-            }
-            int nb = 0, flags = 0;
-            const int code = launch_igemm_fwd(x, w, y, g, e, s, nullptr, sk, skf, want_stats ? &nb : nullptr, tab, tab_rows, &flags);
-            g_last_kernels = gemm_variant_name(0, code, flags);
-            if (want_stats) {
-                if (stats_fused) *stats_fused = nb > 0 ? 1 : 0;
-                if (nb == 0) {          // split-K launch: the trainer falls back to the stand-alone reduction
-                    nb = colreduce_blocks(M, Cout);
-                    launch_colstats(y, red, M, Cout, nb, s);
-                }
-                std::vector<float> hp((size_t)nb * 2 * Cout);
-                CMOOP_HIP(hipMemcpyAsync(hp.data(), red, hp.size() * 4, hipMemcpyDeviceToHost, s));
-                CMOOP_HIP(hipStreamSynchronize(s));
-                for (int c = 0; c < Cout; ++c) { col_sum[c] = 0.0; col_sumsq[c] = 0.0; }
-                for (int b = 0; b < nb; ++b)
-                    for (int c = 0; c < Cout; ++c) {
-                        col_sum[c] += (double)hp[((size_t)b * 2) * Cout + c];
-                        col_sumsq[c] += (double)hp[((size_t)b * 2 + 1) * Cout + c];
-                    }
-            }
+        ConvBuffers buf;
+        buf.splitk_floats = igemm_splitk_workspace(L.geometry(B));
+        buf.splitk = m.floats(buf.splitk_floats);
+        buf.tab_rows = L.table_rows(B);
+        buf.tab = m.rowtab(L.geometry(B), buf.tab_rows);
+        if (want_stats) buf.stats = m.floats(L.stats_floats(B));
+        RecordingHook hook(&g_last_kernels);
+        bool fused = false;
+        const int nb = L.forward(x, w, y, B, e, want_stats, buf, s, &hook, &fused);
+        if (want_stats) {
+            if (stats_fused) *stats_fused = fused ? 1 : 0;
+            std::vector<float> hp((size_t)nb * 2 * Cout);
+            CMOOP_HIP(hipMemcpyAsync(hp.data(), buf.stats, hp.size() * 4, hipMemcpyDeviceToHost, s));
             CMOOP_HIP(hipStreamSynchronize(s));
-        } catch (...) {
-            cleanup();
-            throw;
+            for (int c = 0; c < Cout; ++c) { col_sum[c] = 0.0; col_sumsq[c] = 0.0; }
+            for (int b = 0; b < nb; ++b)
+                for (int c = 0; c < Cout; ++c) {
+                    col_sum[c] += (double)hp[((size_t)b * 2) * Cout + c];
+                    col_sumsq[c] += (double)hp[((size_t)b * 2 + 1) * Cout + c];
+                }
         }
-        cleanup();
+        CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
 
@@ -743,57 +723,36 @@ int cmoop_conv_bwd_trainer(const float* x, const float* w, const float* dy, floa
     return guard([&] {
         g_last_kernels.clear();
         hipStream_t s = lib_stream();
-        const ConvGeom g = make_geom(B, H, W, Cin, Cout, KS, stride);
-        float *wg = nullptr, *wd = nullptr, *sk = nullptr, *dwb = nullptr;
-        void *tab = nullptr, *tab_d = nullptr;
-        auto cleanup = [&] {
-            hipStreamSynchronize(s);
-            if (wg) hipFree(wg); if (wd) hipFree(wd); if (sk) hipFree(sk); if (dwb) hipFree(dwb); if (tab) hipFree(tab); if (tab_d) hipFree(tab_d);
-        };
-        try {
-            RecordingHook hook(&g_last_kernels);
-            const size_t NK = (size_t)g.Cout * g.K();
-            const size_t wg_floats = (size_t)wgrad_slices(g) * g.Cout * (g.K() + 1);
-            CMOOP_HIP(hipMalloc(&wg, wg_floats * 4));
-            CMOOP_HIP(hipMalloc(&dwb, (NK + g.Cout) * 4));          // the trainer's arena layout: bias gradient directly after the kernel gradient
-            const int tab_rows = (KS * KS <= 32) ? rowtab_rows(g) : 0;
-            if (tab_rows) {
-                CMOOP_HIP(hipMalloc(&tab, (size_t)tab_rows * 8));
-                launch_build_rowtab(g, tab, s);
+        Scratch m(s);
+        const ConvLayer L{H, W, Cin, Cout, KS, stride};
+        RecordingHook hook(&g_last_kernels);
+        const size_t NK = L.flip_floats();
+        ConvBuffers buf;
+        buf.slab_floats = L.slab_floats_at(B);       // (the trainer: the worst batch's)
+        buf.slabs = m.floats(buf.slab_floats);
+        float* dwb = m.floats(NK + Cout);            // the trainer's arena layout: bias gradient directly after the kernel gradient
+        buf.tab_rows = L.table_rows(B);
+        buf.tab = m.rowtab(L.geometry(B), buf.tab_rows);
+        L.wgrad(x, dy, dwb, dwb + NK, B, buf, GEMM_DEFAULT, s, &hook);
+        CMOOP_HIP(hipMemcpyAsync(dw, dwb, NK * 4, hipMemcpyDeviceToDevice, s));
+        CMOOP_HIP(hipMemcpyAsync(db, dwb + NK, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
+        if (dx) {
+            int accumulate = 0;
+            if (stride != 1) {
+                CMOOP_HIP(hipMemsetAsync(dx, 0, (size_t)B * H * W * Cin * 4, s));
+                accumulate = 1;
             }
-            conv_backward_weights(x, dy, dwb, dwb + NK, g, wg, wg_floats, s, &hook, GEMM_DEFAULT, tab, tab_rows);
-            CMOOP_HIP(hipMemcpyAsync(dw, dwb, NK * 4, hipMemcpyDeviceToDevice, s));
-            CMOOP_HIP(hipMemcpyAsync(db, dwb + NK, (size_t)g.Cout * 4, hipMemcpyDeviceToDevice, s));
-            if (dx) {
-                int accumulate = 0;
-                if (stride != 1) {
-                    CMOOP_HIP(hipMemsetAsync(dx, 0, (size_t)B * H * W * Cin * 4, s));
-                    accumulate = 1;
-                }
-                const bool mfma_dgrad = ilog2_exact(Cout) >= 4;
-                const ConvGeom gd = dgrad_geometry(g);
-                int tab_d_rows = 0;
-                size_t skf = 0;
-                if (mfma_dgrad) {
-                    CMOOP_HIP(hipMalloc(&wd, NK * 4));
-                    launch_flip_transpose(w, wd, Cout, KS, KS, Cin, s);       // the trainer's one-launch-per-step refresh, for one layer
-                    if (KS * KS <= 32) {
-                        tab_d_rows = rowtab_rows(gd);
-                        CMOOP_HIP(hipMalloc(&tab_d, (size_t)tab_d_rows * 8));
-                        launch_build_rowtab(gd, tab_d, s);
-                    }
-                    skf = igemm_splitk_workspace(gd);      // the trainer passes its workspace to every dgrad, the skip projection's too
-                    if (skf) CMOOP_HIP(hipMalloc(&sk, skf * 4));
-                }
-                conv_backward_data(dy, w, dx, g, wd, mask_relu ? x : nullptr, 1.f, accumulate, s, &hook, sk, skf, GEMM_DEFAULT, mfma_dgrad,
-                                   tab_d, tab_d_rows);
+            if (L.mfma_dgrad()) {
+                buf.wd = m.floats(NK);
+                launch_flip_transpose(w, buf.wd, Cout, KS, KS, Cin, s);       // the trainer's one-launch-per-step refresh, for one layer
+                buf.tab_d_rows = L.dgrad_table_rows(B);
+                buf.tab_d = m.rowtab(L.dgrad_geom(B), buf.tab_d_rows);
+                buf.splitk_floats = igemm_splitk_workspace(L.dgrad_geom(B));      // the trainer passes its workspace to every dgrad, the skip projection's too
+                buf.splitk = m.floats(buf.splitk_floats);
             }
-            CMOOP_HIP(hipStreamSynchronize(s));
-        } catch (...) {
-            cleanup();
-            throw;
+            L.dgrad(dy, w, dx, B, mask_relu ? x : nullptr, 1.f, accumulate, L.mfma_dgrad(), buf, GEMM_DEFAULT, s, &hook);
         }
-        cleanup();
+        CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
 
@@ -810,48 +769,28 @@ int cmoop_conv_time(int32_t mode, const float* x, const float* w, const float* b
     // mode 2: wgrad MFMA kernel only (y = dY in, partials into a scratch buffer)
     return guard([&] {
         hipStream_t s = lib_stream();
-        const ConvGeom g = make_geom(B, H, W, Cin, Cout, KS, 1);
-        float *wd = nullptr, *wg = nullptr, *sk = nullptr;
-        ConvGeom gd = g;
+        Scratch m(s);
+        const ConvLayer L{H, W, Cin, Cout, KS, 1};
+        const ConvGeom g = L.geometry(B), gd = L.dgrad_geom(B);
+        float *wd = nullptr, *wg = nullptr;
         GemmEpilogue e;
         const int S = wgrad_slices(g);
         if (mode == 0) e.bias = bias;
         if (mode == 1) {
-            CMOOP_HIP(hipMalloc(&wd, (size_t)g.Cout * g.K() * 4));
+            wd = m.floats(L.flip_floats());
             launch_flip_transpose(w, wd, Cout, KS, KS, Cin, s);
-            gd.H = g.OH; gd.W = g.OW; gd.Cin = Cout; gd.Cout = Cin; gd.OH = g.H; gd.OW = g.W;
-            gd.pad_t = KS - 1 - g.pad_t; gd.pad_l = KS - 1 - g.pad_l;
         }
-        void* tab = nullptr;   // the layer's row table, as the trainer passes it (forward / wgrad: forward geometry; dgrad: its own)
-        const int tab_rows = (KS * KS <= 32 && Cin >= 16) ? rowtab_rows(mode == 1 ? gd : g) : 0;
-        if (mode == 2) CMOOP_HIP(hipMalloc(&wg, (size_t)S * g.Cout * g.K() * 4));
-        if (tab_rows) {
-            CMOOP_HIP(hipMalloc(&tab, (size_t)tab_rows * 8));
-            launch_build_rowtab(mode == 1 ? gd : g, tab, s);
-        }
+        if (mode == 2) wg = m.floats((size_t)S * g.Cout * g.K());      // kernel partials only: no bias slabs
+        // the layer's row table, as the trainer passes it (forward / wgrad: forward geometry; dgrad: its own)
+        const int tab_rows = (L.has_tables() && Cin >= 16) ? rowtab_rows(mode == 1 ? gd : g) : 0;
+        void* tab = m.rowtab(mode == 1 ? gd : g, tab_rows);
         const size_t skf = mode == 0 ? igemm_splitk_workspace(g) : (mode == 1 ? igemm_splitk_workspace(gd) : 0);
-        if (skf) CMOOP_HIP(hipMalloc(&sk, skf * 4));
-        auto once = [&]() {
+        float* sk = m.floats(skf);
+        *avg_ms = time_launches(s, iters, [&] {
             if (mode == 0) launch_igemm_fwd(x, w, y, g, e, s, nullptr, sk, skf, nullptr, tab, tab_rows);
             else if (mode == 1) launch_igemm_fwd(y, wd, const_cast<float*>(x), gd, e, s, nullptr, sk, skf, nullptr, tab, tab_rows);
             else launch_igemm_wgrad(x, y, wg, g, S, s, nullptr, nullptr, 0, GEMM_DEFAULT, tab, tab_rows);
-        };
-        for (int i = 0; i < 3; ++i) once();
-        hipEvent_t a, b;
-        CMOOP_HIP(hipEventCreate(&a));
-        CMOOP_HIP(hipEventCreate(&b));
-        CMOOP_HIP(hipEventRecord(a, s));
-        for (int i = 0; i < iters; ++i) once();
-        CMOOP_HIP(hipEventRecord(b, s));
-        CMOOP_HIP(hipEventSynchronize(b));
-        float ms = 0.f;
-        CMOOP_HIP(hipEventElapsedTime(&ms, a, b));
-        hipEventDestroy(a); hipEventDestroy(b);
-        if (wd) hipFree(wd);
-        if (wg) hipFree(wg);
-        if (sk) hipFree(sk);
-        if (tab) hipFree(tab);
-        *avg_ms = (double)ms / std::max(1, iters);
+        });
     });
 }
 

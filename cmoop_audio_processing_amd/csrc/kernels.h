@@ -21,6 +21,15 @@ struct ConvGeom {
     int M() const { return B * OH * OW; }
     int K() const { return KH * KW * Cin; }
 };
+// geometry of a square-window SAME convolution (output ceil(H / stride) x ceil(W / stride))
+inline ConvGeom conv_geometry(int B, int H, int W, int Cin, int Cout, int KS, int stride) {
+    ConvGeom g;
+    g.B = B; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.KH = g.KW = KS; g.stride = stride;
+    g.OH = (H + stride - 1) / stride; g.OW = (W + stride - 1) / stride;
+    const int th = (g.OH - 1) * stride + KS - H, tw = (g.OW - 1) * stride + KS - W;
+    g.pad_t = (th > 0 ? th : 0) / 2; g.pad_l = (tw > 0 ? tw : 0) / 2;
+    return g;
+}
 
 // Arithmetic of the MFMA GEMM kernels.  GEMM_FP32 (exact v_mfma_f32_16x16x4_f32) is the product default;
 // the bf16 matrix-core modes are opt-in (cmoop_config.gemm_mode or CMOOP_GEMM_MODE=bf16x3|bf16), see gemm.hip.

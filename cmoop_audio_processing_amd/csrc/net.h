@@ -51,21 +51,70 @@ struct GemmHook {   // brackets every MFMA GEMM launch (HIP-event sampling)
     virtual void end(int code, int flags) = 0;   // code: instantiation (gemm_kernel_name), flags: GemmFlags of the path taken
     virtual ~GemmHook() {}
 };
-// wgrad_ws holds wgrad_ws_floats floats; the slice count is clamped to what fits (never written past)
-void conv_backward_weights(const float* X, const float* dY, float* dW, float* dB, const ConvGeom& g, float* wgrad_ws,
-                           size_t wgrad_ws_floats, hipStream_t s, GemmHook* hook, int mode = GEMM_DEFAULT,
-                           const void* rowtab = nullptr, int tab_rows = 0, AdamSeg* defer = nullptr);
-// defer != null (requires dB == dW + Cout*K): the slice sum is left to the optimiser launch -- *defer receives the slab
-// pointer / stride / slice count (slab stays null when one slice wrote dW, dB in place)
-// wd_ready: wd_ws already holds the flip-transposed weights (the trainer refreshes all layers in one launch per step)
-// rowtab_d: row table of the DGRAD geometry (see dgrad_geometry), optional
-void conv_backward_data(const float* dY, const float* W, float* dX, const ConvGeom& g, float* wd_ws, const float* mask,
-                        float mask_scale, int accumulate, hipStream_t s, GemmHook* hook, float* sk_ws = nullptr,
-                        size_t sk_floats = 0, int mode = GEMM_DEFAULT, bool wd_ready = false, const void* rowtab_d = nullptr,
-                        int rowtab_d_rows = 0);
 // geometry of the implicit GEMM that computes dX from dY for forward geometry g (stride 1: flipped SAME padding;
 // the strided 1x1 skip projection: a 1x1 GEMM over the output pixels, scattered by the epilogue)
 ConvGeom dgrad_geometry(const ConvGeom& g);
+// floats of BatchNorm statistics partials for an [M][C] tensor: the stand-alone reduction's blocks, or one partial per
+// 64-row tile of the producing conv (fused statistics), plus the finalised pair
+size_t stats_partials_floats(int64_t M, int C);
+
+// Device memory the launches of one conv layer use.  The caller owns all of it: the trainer hands out slices of its
+// arenas, the lone-layer entry points (api.hip) allocate per call.
+struct ConvBuffers {
+    const void* tab = nullptr;      // row table of geometry(B') for a B' >= the launch batch (forward and weight gradient)
+    int tab_rows = 0;
+    const void* tab_d = nullptr;    // row table of dgrad_geom(B') (data gradient)
+    int tab_d_rows = 0;
+    float* splitk = nullptr;        // split-K / balanced-partition slabs of the forward-type launches
+    size_t splitk_floats = 0;
+    float* slabs = nullptr;         // weight-gradient row-slice slabs
+    size_t slab_floats = 0;
+    float* wd = nullptr;            // flip-transposed weights (dgrad operand), flip_floats()
+    float* stats = nullptr;         // BatchNorm statistics partials, stats_floats(B)
+};
+
+// One implicit-GEMM conv layer as the trainer launches it: THE place of every per-layer launch decision.  Net's plan,
+// forward and backward, the lone-layer entry points of api.hip (cmoop_conv_*_trainer, cmoop_conv_time) and the host-only
+// launch plans (cmoop_conv_launch_plan, cmoop_net_launch_plan) all go through it.  A host-side value: owns no memory.
+struct ConvLayer {
+    int H, W, Cin, Cout, KS, stride;
+
+    ConvGeom geometry(int B) const { return conv_geometry(B, H, W, Cin, Cout, KS, stride); }
+    ConvGeom dgrad_geom(int B) const { return dgrad_geometry(geometry(B)); }
+    // row tables (geometry only: a table built for a batch serves every smaller one); the dgrad's when it is an MFMA launch
+    bool has_tables() const { return KS * KS <= 32; }
+    bool mfma_dgrad() const { return ilog2_exact(Cout) >= 4; }   // else: the classifier's tiny VALU kernel (dense layers only)
+    int table_rows(int B) const { return has_tables() ? rowtab_rows(geometry(B)) : 0; }
+    int dgrad_table_rows(int B) const { return has_tables() && mfma_dgrad() ? rowtab_rows(dgrad_geom(B)) : 0; }
+    // workspace sizes in floats.  The weight gradient's slice count is NOT monotone in the batch rows (a smaller M can
+    // flip the K-tile width and the co-resident workgroup count): slabs are sized for the worst train batch 1..b
+    size_t slab_floats_at(int B) const;   // this batch's slices
+    size_t slab_floats(int b) const;
+    size_t stats_floats(int B) const { return stats_partials_floats(geometry(B).M(), Cout); }
+    size_t flip_floats() const { return (size_t)Cout * KS * KS * Cin; }
+    // split-K floats this layer asks of a net planned for train batch `batch` and Bmax = max(batch, eval_batch): forward
+    // at both, dgrad (stride-1 layers) at the train batch.  NOT every partial batch: an under-filled one may want more,
+    // and then takes another tile or partition than a lone launch of the same batch ("Launch plan")
+    size_t splitk_need(int batch, int Bmax) const;
+
+    // Y = conv(X, Wt) + epilogue e (bias / ReLU / mode; e.stats is set here).  want_stats: BatchNorm column partials into
+    // buf.stats, by the conv's epilogue when the launch allows (*fused), else by the stand-alone reduction right after
+    // it; returns the number of partials (0 without want_stats)
+    int forward(const float* X, const float* Wt, float* Y, int B, GemmEpilogue e, bool want_stats, const ConvBuffers& buf,
+                hipStream_t s, GemmHook* hook, bool* fused = nullptr) const;
+    // dW [Cout][K] and dB [Cout] through buf.slabs; the slice count is clamped to the slab_floats that fit (never written
+    // past).  defer != null (requires dB == dW + Cout*K): the slice sum is left to the optimiser launch -- *defer receives
+    // the slab pointer / stride / slice count (slab stays null when one slice wrote dW, dB in place)
+    void wgrad(const float* X, const float* dY, float* dW, float* dB, int B, const ConvBuffers& buf, int mode, hipStream_t s,
+               GemmHook* hook, AdamSeg* defer = nullptr) const;
+    // dX; wd_ready: buf.wd already holds the flip-transposed weights (the trainer refreshes all layers in one launch per step)
+    void dgrad(const float* dY, const float* W, float* dX, int B, const float* mask, float mask_scale, int accumulate,
+               bool wd_ready, const ConvBuffers& buf, int mode, hipStream_t s, GemmHook* hook) const;
+    // host-only twins: the gemm_variant_name the launch above takes when handed splitk_floats of split-K workspace
+    std::string plan_forward(int B, bool want_stats, size_t splitk_floats, int mode) const;
+    std::string plan_wgrad(int B, int mode) const;
+    std::string plan_dgrad(int B, size_t splitk_floats, int mode) const;
+};
 
 // cached device allocations (net.hip): get may return stale contents, free never blocks on other streams
 void* pool_alloc(size_t bytes);
@@ -89,7 +138,9 @@ struct Op {
     int in = -1, in2 = -1, out = -1;
     // conv / dense
     int KS = 1, stride = 1, Cin = 0, Cout = 0;
-    int relu = 0, need_dgrad = 1, in_is_relu = 0, dgrad_accumulate = 0, dropout_layer = -1;
+    int H = 0, W = 0;          // spatial size of the input
+    ConvLayer conv() const { return ConvLayer{H, W, Cin, Cout, KS, stride}; }   // OP_CONV: the layer's launch context
+    int relu = 0, in_is_relu = 0, dgrad_accumulate = 0, dropout_layer = -1;
     float in_mask_scale = 1.f;
     int gemm_mode = GEMM_FP32;   // arithmetic of this layer's three GEMMs
     void* rowtab = nullptr;    // conv: row table of the layer (forward tile prologue and weight-gradient gather), max(batch, eval_batch) samples
@@ -111,6 +162,22 @@ struct Op {
     int mask_y_pos = 0;
     int fused_into_bn = 0;     // pool: executed inside the preceding BatchNorm's fused kernels
 };
+
+// The op list and activation shapes of a candidate, from the six genes: host arithmetic only.  Net::build_plan allocates
+// for it; check_plan_ranges, cmoop_plan_convs and cmoop_net_launch_plan walk it without a device.
+struct NetPlan {
+    std::vector<Act> acts;
+    std::vector<Op> ops;
+    int logits = -1;
+    int64_t n_params = 0;
+    // the net's shared split-K workspace for train batch `batch` and Bmax = max(batch, eval_batch)
+    size_t splitk_floats(int batch, int Bmax) const;
+    // ';'-joined launch-path variants (gemm_variant_name) of the MFMA conv launches of one train step (forward with the
+    // statistics epilogue where a layer feeds a BatchNorm, then weight and data gradients in backward order) or of one
+    // inference pass at batch B, in launch order, under that workspace
+    std::string launch_plan(int batch, int Bmax, int B, bool train) const;
+};
+NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F);
 
 class Net : public GemmHook {
   public:
@@ -168,9 +235,7 @@ class Net : public GemmHook {
     void forward(const float* X, const int32_t* idx, int64_t row0, int B, bool train, const StepState* st = nullptr);
     void backward(const float* X, const int32_t* idx, int64_t row0, int B, const StepState* st = nullptr);
     void step_body(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B, const StepState* st);
-    ConvGeom geom_of(const Op& op, int B) const;
-    void run_gemm(int cls, const float* X, const float* Wt, float* Y, const ConvGeom& g, const GemmEpilogue& e, int* stats_blocks = nullptr,
-                  const void* rowtab = nullptr, int tab_rows = 0);
+    ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
 
     int32_t gene_[6];
@@ -220,7 +285,7 @@ struct FitHistory {
 EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, uint32_t seed, FitHistory* hist = nullptr);
 // train-to-early-stop + readouts for one candidate (evaluate_individual, nsga_penalty.py:368-395)
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream);
-// host-only: every implicit-GEMM conv geometry of a candidate at batch B (plan walk without device memory); throws
+// host-only: every implicit-GEMM conv geometry of a candidate at batch B (a walk of plan_net's ops); throws
 // through igemm_check_range when a layer is beyond the kernels' 32-bit byte offsets
 void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
 // the population loop (compute_objectives_and_constraints, nsga_penalty.py:418-442): n_slots

@@ -191,38 +191,42 @@ Net::~Net() {
     for (void* p : allocs_) pool_free(p);
 }
 
-void Net::build_plan() {
-    const int f = gene_[0], k = gene_[1], bn = gene_[2], R = gene_[3], fc = gene_[4], dr = gene_[5];
-    const bool A = cfg_.variant == 0;
+NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F) {
+    validate_gene(gene);
+    const int f = gene[0], k = gene[1], bn = gene[2], R = gene[3], fc = gene[4], dr = gene[5];
+    const bool A = cfg.variant == 0;
+    NetPlan plan;
+    std::vector<Act>& acts = plan.acts;
+    std::vector<Op>& ops = plan.ops;
     int64_t off = 0;
     int tindex = 0;
 
     auto new_act = [&](int H, int W, int C) {
         Act a; a.H = H; a.W = W; a.C = C;
-        acts_.push_back(a);
-        return (int)acts_.size() - 1;
+        acts.push_back(a);
+        return (int)acts.size() - 1;
     };
-    new_act(T_, F_, 1);   // 0: the input features (never materialised: conv1 reads the resident tensor)
+    new_act(T, F, 1);   // 0: the input features (never materialised: conv1 reads the resident tensor)
 
     auto add_conv = [&](OpKind kind, int in, int Cout, int KS, int stride, int relu, int in_is_relu, float mask_scale,
                         int accumulate) {
         Op op; op.kind = kind; op.in = in;
-        const Act& ia = acts_[in];
-        op.KS = KS; op.stride = stride; op.Cin = ia.C; op.Cout = Cout; op.relu = relu;
+        const Act& ia = acts[in];
+        op.KS = KS; op.stride = stride; op.Cin = ia.C; op.Cout = Cout; op.H = ia.H; op.W = ia.W; op.relu = relu;
         op.in_is_relu = in_is_relu; op.in_mask_scale = mask_scale; op.dgrad_accumulate = accumulate;
         op.w_off = off; op.tensor_index = tindex;
-        op.gemm_mode = cfg_.gemm_mode;
+        op.gemm_mode = cfg.gemm_mode;
         off += (int64_t)Cout * KS * KS * ia.C;
         op.b_off = off; off += Cout;
         tindex += 2;
         op.out = new_act((ia.H + stride - 1) / stride, (ia.W + stride - 1) / stride, Cout);
-        ops_.push_back(op);
+        ops.push_back(op);
         return op.out;
     };
     auto add_bn = [&](int in, int relu_after, int mask_in_pos) {
-        if (!ops_.empty() && (ops_.back().kind == OP_CONV || ops_.back().kind == OP_CONV1) && ops_.back().out == in) ops_.back().feeds_bn = 1;
+        if (!ops.empty() && (ops.back().kind == OP_CONV || ops.back().kind == OP_CONV1) && ops.back().out == in) ops.back().feeds_bn = 1;
         Op op; op.kind = OP_BN; op.in = in; op.relu_after = relu_after; op.mask_in_pos = mask_in_pos;
-        const Act ia = acts_[in];
+        const Act ia = acts[in];
         op.Cout = ia.C;
         op.gamma_off = off; off += ia.C;
         op.beta_off = off; off += ia.C;
@@ -230,7 +234,7 @@ void Net::build_plan() {
         op.mv_off = off; off += ia.C;
         tindex += 4;
         op.out = new_act(ia.H, ia.W, ia.C);
-        ops_.push_back(op);
+        ops.push_back(op);
         return op.out;
     };
     auto add_pool = [&](int in, int mask_y_pos) {
@@ -238,14 +242,14 @@ void Net::build_plan() {
         // CMOOP_BN_POOL_UNFUSED=1 (read per net: tests A/B the fused kernels against scale_shift + maxpool, bit for bit)
         const char* unf = std::getenv("CMOOP_BN_POOL_UNFUSED");
         const bool fuse_ok = !(unf && unf[0] == '1');
-        if (fuse_ok && !ops_.empty() && ops_.back().kind == OP_BN && ops_.back().out == in && !mask_y_pos) {
-            ops_.back().fuse_pool = 1;      // BN-apply (+ReLU) + pool in one pass; the BN output is never written
+        if (fuse_ok && !ops.empty() && ops.back().kind == OP_BN && ops.back().out == in && !mask_y_pos) {
+            ops.back().fuse_pool = 1;      // BN-apply (+ReLU) + pool in one pass; the BN output is never written
             op.fused_into_bn = 1;
-            acts_[in].virt = true;
+            acts[in].virt = true;
         }
-        const Act ia = acts_[in];
+        const Act ia = acts[in];
         op.out = new_act((ia.H + 1) / 2, (ia.W + 1) / 2, ia.C);
-        ops_.push_back(op);
+        ops.push_back(op);
         return op.out;
     };
 
@@ -280,29 +284,62 @@ void Net::build_plan() {
             y = add_pool(y, !bn);
         }
         Op op; op.kind = OP_ADDRELU; op.in = y; op.in2 = skip;
-        op.out = new_act(acts_[y].H, acts_[y].W, acts_[y].C);
-        ops_.push_back(op);
+        op.out = new_act(acts[y].H, acts[y].W, acts[y].C);
+        ops.push_back(op);
         x = op.out;
         c *= 2;
     }
     {
         Op op; op.kind = OP_GAP; op.in = x;
-        op.out = new_act(1, 1, acts_[x].C);
-        ops_.push_back(op);
+        op.out = new_act(1, 1, acts[x].C);
+        ops.push_back(op);
         x = op.out;
     }
-    const float keep_scale = (float)(1.0 / (1.0 - cfg_.dropout));
+    const float keep_scale = (float)(1.0 / (1.0 - cfg.dropout));
     for (int i = 0; i < fc; ++i) {
         const int in_relu = i > 0;
         const float ms = (in_relu && dr) ? keep_scale : 1.f;
         x = add_conv(OP_DENSE, x, FC_LADDER[fc][i], 1, 1, 1, in_relu, ms, 0);
-        if (dr) ops_.back().dropout_layer = i;
+        if (dr) ops.back().dropout_layer = i;
     }
-    x = add_conv(OP_DENSE, x, cfg_.classes, 1, 1, 0, 1, dr ? keep_scale : 1.f, 0);
-    ops_.back().gemm_mode = GEMM_FP32;   // the classifier layer stays fp32 in every mode (as does the C_in = 1 first conv)
-    logits_ = x;
-    n_params_ = off;
-    CMOOP_REQUIRE(n_params_ == param_count(gene_, cfg_.variant, cfg_.classes), "plan / closed-form parameter count mismatch");
+    x = add_conv(OP_DENSE, x, cfg.classes, 1, 1, 0, 1, dr ? keep_scale : 1.f, 0);
+    ops.back().gemm_mode = GEMM_FP32;   // the classifier layer stays fp32 in every mode (as does the C_in = 1 first conv)
+    plan.logits = x;
+    plan.n_params = off;
+    CMOOP_REQUIRE(plan.n_params == param_count(gene, cfg.variant, cfg.classes), "plan / closed-form parameter count mismatch");
+    return plan;
+}
+
+size_t NetPlan::splitk_floats(int batch, int Bmax) const {
+    size_t need = 0;
+    for (const Op& op : ops)
+        if (op.kind == OP_CONV) need = std::max(need, op.conv().splitk_need(batch, Bmax));
+    return need;
+}
+
+std::string NetPlan::launch_plan(int batch, int Bmax, int B, bool train) const {
+    CMOOP_REQUIRE(B >= 1 && B <= (train ? batch : Bmax), "launch plan: batch larger than the net is planned for");
+    const size_t sk = splitk_floats(batch, Bmax);
+    std::string out;
+    auto add = [&](const std::string& v) { out += (out.empty() ? "" : ";") + v; };
+    for (const Op& op : ops)
+        if (op.kind == OP_CONV) add(op.conv().plan_forward(B, train && op.feeds_bn, sk, op.gemm_mode));
+    if (train)
+        for (auto op = ops.rbegin(); op != ops.rend(); ++op)
+            if (op->kind == OP_CONV) {
+                add(op->conv().plan_wgrad(B, op->gemm_mode));
+                add(op->conv().plan_dgrad(B, sk, op->gemm_mode));
+            }
+    return out;
+}
+
+void Net::build_plan() {
+    NetPlan plan = plan_net(gene_, cfg_, T_, F_);
+    splitk_ws_floats_ = plan.splitk_floats(cfg_.batch, Bmax_);
+    acts_ = std::move(plan.acts);
+    ops_ = std::move(plan.ops);
+    logits_ = plan.logits;
+    n_params_ = plan.n_params;
 
     // ---- activations ------------------------------------------------------
     for (size_t i = 1; i < acts_.size(); ++i)
@@ -351,39 +388,24 @@ void Net::build_plan() {
             op.arg = static_cast<uint8_t*>(p);
         }
         if (op.kind == OP_CONV) {   // (dense layers need no workspace: dense.hip)
-            const ConvGeom g = geom_of(op, cfg_.batch);
-            if (op.KS * op.KS <= 32) {   // row tables of the layer (geometry only): built once, serve every smaller batch
-                const ConvGeom gmax = geom_of(op, Bmax_);
-                op.rowtab_rows = rowtab_rows(gmax);
+            const ConvLayer L = op.conv();
+            // row tables: the layer's for the largest batch, its dgrad's for the train batch; built once
+            if ((op.rowtab_rows = L.table_rows(Bmax_)) > 0) {
                 op.rowtab = dalloc((size_t)op.rowtab_rows * 2);
-                launch_build_rowtab(gmax, op.rowtab, stream_);
-                if (op.need_dgrad && ilog2_exact(op.Cout) >= 4) {
-                    const ConvGeom gd = dgrad_geometry(g);
-                    op.rowtab_d_rows = rowtab_rows(gd);
-                    op.rowtab_d = dalloc((size_t)op.rowtab_d_rows * 2);
-                    launch_build_rowtab(gd, op.rowtab_d, stream_);
-                }
+                launch_build_rowtab(L.geometry(Bmax_), op.rowtab, stream_);
             }
-            // the slice count is NOT monotone in the batch rows (a smaller M can flip the K-tile width and the
-            // co-resident workgroup count, so a partial last batch may ask for MORE slices than the full one):
-            // size the slab workspace for the worst train batch 1..cfg.batch
+            if ((op.rowtab_d_rows = L.dgrad_table_rows(cfg_.batch)) > 0) {
+                op.rowtab_d = dalloc((size_t)op.rowtab_d_rows * 2);
+                launch_build_rowtab(L.dgrad_geom(cfg_.batch), op.rowtab_d, stream_);
+            }
             // Each layer owns its slabs: they live until the optimiser launch at the end of the step sums them.
-            for (int b = 1; b <= cfg_.batch; ++b) {
-                const ConvGeom gb = geom_of(op, b);
-                op.slab_floats = std::max(op.slab_floats, (size_t)wgrad_slices(gb) * gb.Cout * (gb.K() + 1));
-            }
+            op.slab_floats = L.slab_floats(cfg_.batch);
             op.slab_off = (int64_t)wgrad_ws_floats_;
             wgrad_ws_floats_ += (op.slab_floats + 3) / 4 * 4;
-            if (op.need_dgrad) { op.wd_off = (int64_t)wd_ws_floats_; wd_ws_floats_ += (size_t)g.Cout * g.K(); }
-            // split-K slabs: forward (train and inference batch) and dgrad (input-shaped output)
-            splitk_ws_floats_ = std::max(splitk_ws_floats_, igemm_splitk_workspace(g));
-            splitk_ws_floats_ = std::max(splitk_ws_floats_, igemm_splitk_workspace(geom_of(op, Bmax_)));
-            if (op.stride == 1 && ilog2_exact(op.Cout) >= 4) {
-                ConvGeom gd = g;
-                gd.H = g.OH; gd.W = g.OW; gd.Cin = g.Cout; gd.Cout = g.Cin; gd.OH = g.H; gd.OW = g.W;
-                splitk_ws_floats_ = std::max(splitk_ws_floats_, igemm_splitk_workspace(gd));
-            }
-            const int64_t M = g.M();
+            op.wd_off = (int64_t)wd_ws_floats_;
+            wd_ws_floats_ += L.flip_floats();
+            // (the shared split-K workspace is sized by NetPlan::splitk_floats)
+            const int64_t M = L.geometry(cfg_.batch).M();
             if (op.Cout % 4 == 0)
                 red_ws_floats_ = std::max(red_ws_floats_, (size_t)colreduce_blocks(M, op.Cout) * 2 * op.Cout + 2 * op.Cout);
         }
@@ -395,10 +417,7 @@ void Net::build_plan() {
             red_ws_floats_ = std::max(red_ws_floats_, (size_t)colreduce_blocks((int64_t)Bmax_ * T_ * F_, op.Cout) * 2 * op.Cout + 2 * op.Cout);
         }
         if (op.kind == OP_BN) {
-            const int64_t M = (int64_t)Bmax_ * acts_[op.in].H * acts_[op.in].W;
-            // stand-alone reduction partials, or one partial per 64-row tile of the producing conv (fused statistics)
-            const size_t blocks = std::max<size_t>((size_t)colreduce_blocks(M, op.Cout), (size_t)cdiv64(M, 64));
-            red_ws_floats_ = std::max(red_ws_floats_, blocks * 2 * op.Cout + 2 * op.Cout);
+            red_ws_floats_ = std::max(red_ws_floats_, stats_partials_floats((int64_t)Bmax_ * acts_[op.in].H * acts_[op.in].W, op.Cout));
         }
     }
     wgrad_ws_ = dalloc(wgrad_ws_floats_);
@@ -437,16 +456,12 @@ void Net::build_plan() {
     }
 }
 
-ConvGeom Net::geom_of(const Op& op, int B) const {
-    const Act& ia = acts_[op.in];
-    ConvGeom g;
-    g.B = B; g.H = ia.H; g.W = ia.W; g.Cin = op.Cin;
-    g.OH = (ia.H + op.stride - 1) / op.stride; g.OW = (ia.W + op.stride - 1) / op.stride; g.Cout = op.Cout;
-    g.KH = g.KW = op.KS; g.stride = op.stride;
-    const int th = std::max((g.OH - 1) * op.stride + op.KS - ia.H, 0);
-    const int tw = std::max((g.OW - 1) * op.stride + op.KS - ia.W, 0);
-    g.pad_t = th / 2; g.pad_l = tw / 2;
-    return g;
+ConvBuffers Net::buffers_of(const Op& op) const {
+    ConvBuffers b;
+    b.tab = op.rowtab; b.tab_rows = op.rowtab_rows; b.tab_d = op.rowtab_d; b.tab_d_rows = op.rowtab_d_rows;
+    b.slabs = wgrad_ws_ + op.slab_off; b.slab_floats = op.slab_floats; b.wd = wd_ws_ + op.wd_off;
+    b.splitk = splitk_ws_; b.splitk_floats = splitk_ws_floats_; b.stats = red_ws_;
+    return b;
 }
 
 void Net::get_params(float* host) {
@@ -494,58 +509,48 @@ std::string gemm_variant_name(int cls, int code, int flags) {
     return v;
 }
 
-// dW[N][K] and db[N] of a conv / dense layer: MFMA split over row slices, then a fixed-order slice sum
-void conv_backward_weights(const float* X, const float* dY, float* dW, float* dB, const ConvGeom& g, float* wgrad_ws,
-                           size_t wgrad_ws_floats, hipStream_t s, GemmHook* hook, int mode, const void* rowtab, int tab_rows,
-                           AdamSeg* defer) {
+// ---------------------------------------------------------------------------
+// ConvLayer: sizes, launches and host-only launch plans of one implicit-GEMM conv layer
+// dW[N][K] and db[N]: MFMA split over row slices, then a fixed-order slice sum
+void ConvLayer::wgrad(const float* X, const float* dY, float* dW, float* dB, int B, const ConvBuffers& buf, int mode, hipStream_t s,
+                      GemmHook* hook, AdamSeg* defer) const {
+    const ConvGeom g = geometry(B);
     const int M = g.M(), N = g.Cout, K = g.K();
     int S = wgrad_slices(g);
     // never write past the slab workspace: fewer slices is always correct (each slice is a row range)
     const size_t per_slice = (size_t)N * (K + 1);
-    if (S > 1 && (size_t)S * per_slice > wgrad_ws_floats) S = (int)std::max<size_t>(1, wgrad_ws_floats / per_slice);
-    CMOOP_REQUIRE(S == 1 || (size_t)S * per_slice <= wgrad_ws_floats, "wgrad slab workspace too small");
+    if (S > 1 && (size_t)S * per_slice > buf.slab_floats) S = (int)std::max<size_t>(1, buf.slab_floats / per_slice);
+    CMOOP_REQUIRE(S == 1 || (size_t)S * per_slice <= buf.slab_floats, "wgrad slab workspace too small");
     // slices are laid out [S][N*K + N] (kernel partials then bias partials): when dB directly follows dW
     // (the trainer's arena) a single fixed-order reduction produces both; one slice writes in place.
     const size_t NK = (size_t)N * K, stride = NK + N;
     const bool in_place = S == 1;
-    float* Pk = in_place ? dW : wgrad_ws;
-    float* Pbias = in_place ? dB : wgrad_ws + NK;
+    float* Pk = in_place ? dW : buf.slabs;
+    float* Pbias = in_place ? dB : buf.slabs + NK;
     const GemmTiming* tm = hook ? hook->begin(1, 2.0 * M * (double)N * K) : nullptr;
     int flags = 0;
-    const int code = launch_igemm_wgrad(X, dY, Pk, g, S, s, tm, Pbias, in_place ? NK : stride, mode, rowtab, tab_rows, &flags);
+    const int code = launch_igemm_wgrad(X, dY, Pk, g, S, s, tm, Pbias, in_place ? NK : stride, mode, buf.tab, buf.tab_rows, &flags);
     if (hook) hook->end(code, flags);
     if (defer) {
         CMOOP_REQUIRE(dB == dW + NK, "deferred slice sum needs the bias gradient directly after the kernel gradient");
         defer->n = (int64_t)stride;
-        defer->slab = in_place ? nullptr : wgrad_ws;
+        defer->slab = in_place ? nullptr : buf.slabs;
         defer->stride = (int64_t)stride;
         defer->S = S;
         return;
     }
     if (!in_place) {
         if (dB == dW + NK) {
-            launch_reduce_slices(wgrad_ws, dW, S, (int64_t)stride, s, (int64_t)stride);
+            launch_reduce_slices(buf.slabs, dW, S, (int64_t)stride, s, (int64_t)stride);
         } else {
-            launch_reduce_slices(wgrad_ws, dW, S, (int64_t)NK, s, (int64_t)stride);
-            launch_reduce_slices(wgrad_ws + NK, dB, S, N, s, (int64_t)stride);
+            launch_reduce_slices(buf.slabs, dW, S, (int64_t)NK, s, (int64_t)stride);
+            launch_reduce_slices(buf.slabs + NK, dB, S, N, s, (int64_t)stride);
         }
     }
 }
 
-// dX of a conv / dense layer: the same implicit-GEMM kernel on dY with flip-transposed weights.
-// `g` is the FORWARD geometry.  mask != null applies the ReLU (and dropout scale) backward of the
-// layer's input in the epilogue; accumulate adds into dX (second consumer of a tensor).
-void conv_backward_data(const float* dY, const float* W, float* dX, const ConvGeom& g, float* wd_ws, const float* mask,
-                        float mask_scale, int accumulate, hipStream_t s, GemmHook* hook, float* sk_ws, size_t sk_floats, int mode,
-                        bool wd_ready, const void* rowtab_d, int rowtab_d_rows) {
-    const int N = g.Cout;
-    if (ilog2_exact(N) < 4) {   // output layer: K_dgrad = classes (10/11/35) -- tiny VALU kernel
-        CMOOP_REQUIRE(g.KH == 1 && g.H == 1 && g.W == 1 && !accumulate, "non power-of-two C_out only supported for dense layers");
-        launch_dense_dgrad_small(dY, W, dX, g.M(), N, g.K(), mask, mask_scale, s);
-        return;
-    }
-    if (!wd_ready) launch_flip_transpose(W, wd_ws, N, g.KH, g.KW, g.Cin, s);
-    const ConvGeom gd = dgrad_geometry(g);
+// the part of the dgrad launch's epilogue its tile / path choice depends on (`g` is the FORWARD geometry)
+static GemmEpilogue dgrad_epilogue(const ConvGeom& g, int mode, int accumulate) {
     GemmEpilogue e;
     if (g.stride != 1) {
         CMOOP_REQUIRE(g.KH == 1 && g.KW == 1 && accumulate, "strided conv dgrad: only the 1x1 skip projection (accumulating)");
@@ -553,11 +558,28 @@ void conv_backward_data(const float* dY, const float* W, float* dX, const ConvGe
     }
     e.mode = mode;
     e.accumulate = accumulate;
+    return e;
+}
+
+// dX: the same implicit-GEMM kernel on dY with flip-transposed weights.  mask != null applies the ReLU (and dropout
+// scale) backward of the layer's input in the epilogue; accumulate adds into dX (second consumer of a tensor).
+void ConvLayer::dgrad(const float* dY, const float* W, float* dX, int B, const float* mask, float mask_scale, int accumulate,
+                      bool wd_ready, const ConvBuffers& buf, int mode, hipStream_t s, GemmHook* hook) const {
+    const ConvGeom g = geometry(B);
+    const int N = g.Cout;
+    if (!mfma_dgrad()) {   // a classifier-shaped layer: K_dgrad = classes (10/11/35) -- tiny VALU kernel
+        CMOOP_REQUIRE(g.KH == 1 && g.H == 1 && g.W == 1 && !accumulate, "non power-of-two C_out only supported for dense layers");
+        launch_dense_dgrad_small(dY, W, dX, g.M(), N, g.K(), mask, mask_scale, s);
+        return;
+    }
+    if (!wd_ready) launch_flip_transpose(W, buf.wd, N, g.KH, g.KW, g.Cin, s);
+    const ConvGeom gd = dgrad_geometry(g);
+    GemmEpilogue e = dgrad_epilogue(g, mode, accumulate);
     e.mask = mask;
     e.mask_scale = mask_scale;
     const GemmTiming* tm = hook ? hook->begin(0, 2.0 * gd.M() * (double)gd.Cout * gd.K()) : nullptr;
     int flags = 0;
-    const int code = launch_igemm_fwd(dY, wd_ws, dX, gd, e, s, tm, sk_ws, sk_floats, nullptr, rowtab_d, rowtab_d_rows, &flags);
+    const int code = launch_igemm_fwd(dY, buf.wd, dX, gd, e, s, tm, buf.splitk, buf.splitk_floats, nullptr, buf.tab_d, buf.tab_d_rows, &flags);
     if (hook) hook->end(code, flags);
 }
 
@@ -573,12 +595,66 @@ ConvGeom dgrad_geometry(const ConvGeom& g) {
     return gd;
 }
 
-void Net::run_gemm(int cls, const float* X, const float* Wt, float* Y, const ConvGeom& g, const GemmEpilogue& e, int* stats_blocks,
-                   const void* rowtab, int tab_rows) {
-    const GemmTiming* tm = begin(cls, 2.0 * g.M() * (double)g.Cout * g.K());
+size_t stats_partials_floats(int64_t M, int C) {
+    const size_t blocks = std::max<size_t>((size_t)colreduce_blocks(M, C), (size_t)cdiv64(M, 64));
+    return blocks * 2 * C + 2 * C;
+}
+
+size_t ConvLayer::slab_floats_at(int B) const {   // [slices][Cout * K kernel partials + Cout bias partials]
+    const ConvGeom g = geometry(B);
+    return (size_t)wgrad_slices(g) * g.Cout * (g.K() + 1);
+}
+
+size_t ConvLayer::slab_floats(int b) const {
+    size_t worst = 0;
+    for (int i = 1; i <= b; ++i) worst = std::max(worst, slab_floats_at(i));
+    return worst;
+}
+
+size_t ConvLayer::splitk_need(int batch, int Bmax) const {
+    size_t need = std::max(igemm_splitk_workspace(geometry(batch)), igemm_splitk_workspace(geometry(Bmax)));
+    if (stride == 1 && mfma_dgrad()) need = std::max(need, igemm_splitk_workspace(dgrad_geom(batch)));
+    return need;
+}
+
+int ConvLayer::forward(const float* X, const float* Wt, float* Y, int B, GemmEpilogue e, bool want_stats, const ConvBuffers& buf,
+                       hipStream_t s, GemmHook* hook, bool* fused) const {
+    const ConvGeom g = geometry(B);
+    e.stats = want_stats ? buf.stats : nullptr;
+    const GemmTiming* tm = hook ? hook->begin(0, 2.0 * g.M() * (double)g.Cout * g.K()) : nullptr;
+    int nb = 0, flags = 0;
+    const int code = launch_igemm_fwd(X, Wt, Y, g, e, s, tm, buf.splitk, buf.splitk_floats, want_stats ? &nb : nullptr, buf.tab,
+                                      buf.tab_rows, &flags);
+    if (hook) hook->end(code, flags);
+    if (fused) *fused = nb > 0;
+    if (want_stats && nb == 0) {   // split launch (raw partial sums, no fused statistics): the stand-alone reduction
+        nb = colreduce_blocks(g.M(), Cout);
+        launch_colstats(Y, buf.stats, g.M(), Cout, nb, s);
+    }
+    return nb;
+}
+
+std::string ConvLayer::plan_forward(int B, bool want_stats, size_t splitk_floats, int mode) const {
+    GemmEpilogue e;
+    e.mode = mode;
     int flags = 0;
-    const int code = launch_igemm_fwd(X, Wt, Y, g, e, stream_, tm, splitk_ws_, splitk_ws_floats_, stats_blocks, rowtab, tab_rows, &flags);
-    end(code, flags);
+    const int code = igemm_fwd_plan(geometry(B), e, splitk_floats, want_stats, has_tables(), &flags);
+    return gemm_variant_name(0, code, flags);
+}
+
+std::string ConvLayer::plan_wgrad(int B, int mode) const {   // (slabs sized by slab_floats never clamp the slice count)
+    const ConvGeom g = geometry(B);
+    int flags = 0;
+    const int code = igemm_wgrad_plan(g, wgrad_slices(g), mode, has_tables(), &flags);
+    return gemm_variant_name(1, code, flags);
+}
+
+std::string ConvLayer::plan_dgrad(int B, size_t splitk_floats, int mode) const {
+    CMOOP_REQUIRE(mfma_dgrad(), "launch plan: the dgrad of this layer does not run on the MFMA kernel");
+    const ConvGeom g = geometry(B);
+    int flags = 0;
+    const int code = igemm_fwd_plan(dgrad_geometry(g), dgrad_epilogue(g, mode, stride != 1), splitk_floats, false, has_tables(), &flags);
+    return gemm_variant_name(0, code, flags);
 }
 
 void Net::drain_profile() {
@@ -617,10 +693,9 @@ void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool 
             e.mode = op.gemm_mode;
             e.bias = params_ + op.b_off;
             e.relu = op.relu;
-            fused_stats_blocks_ = 0;
-            if (train && op.feeds_bn) e.stats = red_ws_;    // BatchNorm batch statistics in the conv epilogue
-            run_gemm(0, acts_[op.in].data, params_ + op.w_off, acts_[op.out].data, geom_of(op, B), e,
-                     e.stats ? &fused_stats_blocks_ : nullptr, op.rowtab, op.rowtab_rows);
+            // train && feeds_bn: the BatchNorm batch statistics come with the conv (its epilogue, or the reduction after it)
+            fused_stats_blocks_ = op.conv().forward(acts_[op.in].data, params_ + op.w_off, acts_[op.out].data, B, e,
+                                                    train && op.feeds_bn, buffers_of(op), stream_, this);
             break;
         }
         case OP_DENSE: {
@@ -638,9 +713,9 @@ void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool 
             const int C = op.Cout;
             float *mean = op.bn_buf, *invstd = mean + C, *scale = invstd + C, *shift = scale + C;
             if (train) {
-                int nb = fused_stats_blocks_;              // partials left by the producing conv's epilogue, if any
+                int nb = fused_stats_blocks_;              // partials the producing conv left, if any
                 fused_stats_blocks_ = 0;
-                if (nb == 0) {
+                if (nb == 0) {                             // first conv on the VALU kernel
                     nb = colreduce_blocks(M, C);
                     launch_colstats(ia.data, red_ws_, M, C, nb, stream_);
                 }
@@ -691,19 +766,19 @@ void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, cons
             // CMOOP_DENSE_UNFUSED=1 (read per step, like CMOOP_ADAM_UNFUSED): the two launches of round 2 instead of the merged one
             const char* du = std::getenv("CMOOP_DENSE_UNFUSED");
             const bool unfused = du && du[0] == '1';
-            if (op.need_dgrad && !unfused) {
+            if (!unfused) {
                 launch_dense_bwd(ia.data, dY, params_ + op.w_off, grads_ + op.w_off, grads_ + op.b_off, ia.grad, B, op.Cout, op.Cin,
                                  op.in_is_relu ? ia.data : nullptr, op.in_mask_scale, op.gemm_mode, stream_);
                 break;
             }
             launch_dense_wgrad(ia.data, dY, grads_ + op.w_off, grads_ + op.b_off, B, op.Cout, op.Cin, op.gemm_mode, stream_);
-            if (op.need_dgrad)
-                launch_dense_dgrad(dY, params_ + op.w_off, ia.grad, B, op.Cout, op.Cin, op.in_is_relu ? ia.data : nullptr,
-                                   op.in_mask_scale, op.gemm_mode, stream_);
+            launch_dense_dgrad(dY, params_ + op.w_off, ia.grad, B, op.Cout, op.Cin, op.in_is_relu ? ia.data : nullptr,
+                               op.in_mask_scale, op.gemm_mode, stream_);
             break;
         }
         case OP_CONV: {
-            const ConvGeom g = geom_of(op, B);
+            const ConvLayer L = op.conv();
+            const ConvBuffers buf = buffers_of(op);
             const float* dY = acts_[op.out].grad;
             Act& ia = acts_[op.in];
             // (measured, not adopted: wgrad on a low-priority side stream forked per layer and joined before Adam -- off the
@@ -711,13 +786,10 @@ void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, cons
             // than the overlap wins)
             AdamSeg sg;
             sg.off = op.w_off;
-            conv_backward_weights(ia.data, dY, grads_ + op.w_off, grads_ + op.b_off, g, wgrad_ws_ + op.slab_off, op.slab_floats, stream_,
-                                  this, op.gemm_mode, op.rowtab, op.rowtab_rows, &sg);
+            L.wgrad(ia.data, dY, grads_ + op.w_off, grads_ + op.b_off, B, buf, op.gemm_mode, stream_, this, &sg);
             if (sg.slab) slab_segs_.push_back(sg);
-            if (op.need_dgrad)
-                conv_backward_data(dY, params_ + op.w_off, ia.grad, g, wd_ws_ + op.wd_off, op.in_is_relu ? ia.data : nullptr,
-                                   op.in_mask_scale, op.dgrad_accumulate, stream_, this, splitk_ws_, splitk_ws_floats_, op.gemm_mode,
-                                   true, op.rowtab_d, op.rowtab_d_rows);
+            L.dgrad(dY, params_ + op.w_off, ia.grad, B, op.in_is_relu ? ia.data : nullptr, op.in_mask_scale, op.dgrad_accumulate,
+                    true, buf, op.gemm_mode, stream_, this);
             break;
         }
         case OP_BN: {
@@ -1139,28 +1211,15 @@ EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Data
     return res;
 }
 
-// plan walk without device memory (the conv stack of Net::build_plan): conv geometries of a candidate at batch B
+// conv geometries of a candidate at batch B, from the host-only plan
 void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B) {
-    validate_gene(gene);
-    const int f = gene[0], k = gene[1], R = gene[3];
-    auto geom = [&](int H, int W, int Cin, int Cout, int KS, int stride) {
-        ConvGeom g;
-        g.B = B; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.KH = g.KW = KS; g.stride = stride;
-        g.OH = (H + stride - 1) / stride; g.OW = (W + stride - 1) / stride;
-        g.pad_t = std::max((g.OH - 1) * stride + KS - H, 0) / 2;
-        g.pad_l = std::max((g.OW - 1) * stride + KS - W, 0) / 2;
-        return g;
-    };
+    NetConfig cfg;
+    cfg.variant = variant;
+    const NetPlan plan = plan_net(gene, cfg, T, F);
     // first conv (C_in = 1, direct kernel): its output feeds the GEMM layers, so the same element bound applies to it
-    CMOOP_REQUIRE((int64_t)B * T * F * f < (1ll << 29), "first-layer output exceeds 2^29 elements (32-bit byte offsets): lower the batch / eval_batch");
-    if (variant == 0) igemm_check_range(geom(T, F, f, f, k, 1));
-    int h = (T + 1) / 2, w = (F + 1) / 2, c = f;
-    for (int r = 0; r < R; ++r) {
-        igemm_check_range(geom(h, w, c, 2 * c, 1, 2));
-        igemm_check_range(geom(h, w, c, 2 * c, k, 1));
-        if (variant == 0) igemm_check_range(geom(h, w, 2 * c, 2 * c, k, 1));
-        h = (h + 1) / 2; w = (w + 1) / 2; c *= 2;
-    }
+    CMOOP_REQUIRE((int64_t)B * T * F * gene[0] < (1ll << 29), "first-layer output exceeds 2^29 elements (32-bit byte offsets): lower the batch / eval_batch");
+    for (const Op& op : plan.ops)
+        if (op.kind == OP_CONV) igemm_check_range(op.conv().geometry(B));
 }
 
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,

@@ -113,9 +113,25 @@ int cmoop_plan_check(const int32_t gene[6], int32_t variant, int32_t T, int32_t 
 /* host-only: the launch-path variant (kernel instantiation as rocprofv3 names it + "+sk" / "+stats" / "+tab" / "+slabs",
  * see cmoop_profile_variant) the TRAINER uses for one conv layer at this batch: op 0 forward (want_stats: the layer
  * feeds a BatchNorm), 1 dgrad, 2 wgrad.  Pure arithmetic on the shape -- tests enumerate every layer of every gene with
- * it and require a GPU parity case for each variant. */
+ * it and require a GPU parity case for each variant.  The layer is planned ALONE, as cmoop_conv_fwd_trainer /
+ * cmoop_conv_bwd_trainer launch it: with the split-K workspace of its own geometry at this batch. */
 int cmoop_conv_launch_plan(int32_t op, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride,
                            int32_t want_stats, char* name, int32_t name_cap);
+
+/* host-only: the MFMA (implicit-GEMM) conv layers of a candidate in forward order, from the same plan walk the trainer
+ * allocates for: layers[7 * i ..] = H, W, Cin, Cout, KS, stride, feeds_bn (the layer's output goes straight into a
+ * BatchNorm).  At most `cap` layers are written; *count receives how many there are. */
+int cmoop_plan_convs(const int32_t gene[6], int32_t variant, int32_t T, int32_t F, int32_t* layers /* [cap][7] */, int32_t cap,
+                     int32_t* count);
+
+/* host-only: the launch-path variants, ';'-separated as in cmoop_last_kernels and in launch order, of the MFMA conv launches
+ * a net created with (gene, cfg, T, F) makes in ONE train step at batch B (train != 0: forward with the statistics
+ * epilogue where a layer feeds a BatchNorm, then weight and data gradients) or in one inference pass at batch B
+ * (train == 0).  Unlike cmoop_conv_launch_plan this is computed with the net's SHARED split-K workspace, which is sized
+ * from cfg.batch and max(cfg.batch, cfg.eval_batch) only: on an under-filled partial batch a layer may take another
+ * tile or partition than the lone-layer plan of the same batch names. */
+int cmoop_net_launch_plan(const int32_t gene[6], const cmoop_config* cfg, int32_t T, int32_t F, int32_t B, int32_t train,
+                          char* buf, int32_t cap);
 
 /* host-only: the halo-tiled direct convolution (stride-1 KS x KS layers) stages the input rows of a 128- / 256-pixel tile in LDS;
  * rows_bound = rows its LDS image is sized for (closed form), rows_needed = the most rows any tile of this geometry really

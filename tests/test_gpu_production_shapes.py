@@ -313,6 +313,47 @@ def test_a_corrupt_shuffle_index_cannot_address_outside_the_resident_tensor():
 
 
 @fp32_only
+def test_a_net_launches_what_its_launch_plan_names_at_full_and_partial_batches():
+    """The only test that ties a launch plan to what a Net really launched at a partial batch.  cmoop_net_launch_plan names
+    the MFMA conv launches of a train step / inference pass under the net's SHARED split-K workspace (sized from batch 64 and
+    eval batch 256 only); at batch 37 that is not what the lone-layer plan (cmoop_conv_launch_plan) names: the gene is picked
+    on the CPU so that the two differ for one of its layers (a 16-filter k5 gene: 32->32 k5 at 51x20 runs "+sk" in the net,
+    "+bal" alone).  One BatchNorm net of topology A at 101x40 with every train step sampled (profile_every = 1): a train step
+    at 64, one at 37, then evaluate over 256 + 37 rows.  The sampled launch-path variants must EQUAL the planned ones of the
+    two train steps.  profile_every samples train steps only (include/cmoop.h), so the inference passes at 256 and 37 -- planned
+    here too, and held to the sweep domain by the host test -- must leave the sampled set as it was."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import launch_variants as LV
+    from test_host_cpu import _lone_step_plan
+    T, F, classes = 101, 40, 10
+    cfg = EvalConfig(variant="A", classes=classes, batch=64, eval_batch=256, profile_every=1)
+    st = cfg.to_struct()
+
+    def planned(gene, B, train):
+        return _lib.net_launch_plan(gene, st, T, F, B, train)
+    gene = next(g for g in LV.ALL_CONV_GENES
+                if g[2] == 1 and planned(g, 37, 1) != _lone_step_plan(LV.plan, LV.conv_layers(g, 0, T, F), 37, 1))
+    train_plan = set(planned(gene, 64, 1)) | set(planned(gene, 37, 1))
+    infer_plan = set(planned(gene, 256, 0)) | set(planned(gene, 37, 0))
+    assert train_plan and infer_plan
+    rs = np.random.RandomState(5)
+    Xd = torch.from_numpy(rs.randn(256 + 37, T, F).astype(np.float32)).cuda()
+    yd = torch.from_numpy(rs.randint(0, classes, 256 + 37).astype(np.int32)).cuda()
+    _lib.check(_lib.lib().cmoop_profile_reset())
+    with NetSession(gene, cfg, T, F, 3) as net:
+        net.train_step(Xd, yd, None, row0=0, B=64)
+        net.train_step(Xd, yd, None, row0=64, B=37)
+        sampled = set(_lib.profile_variants())
+        loss, _, _ = net.evaluate(Xd, yd)
+        after_inference = set(_lib.profile_variants())
+    print(f"gene {gene}: sampled {sorted(sampled)}; planned for the train steps {sorted(train_plan)}; for inference {sorted(infer_plan)}")
+    assert np.isfinite(loss)
+    assert sampled == train_plan, (sorted(sampled - train_plan), sorted(train_plan - sampled))
+    assert after_inference == sampled
+
+
+@fp32_only
 def test_every_launch_variant_of_the_pop40_job_is_covered_by_a_parity_case():
     """Coverage assertion: run the bench's population (40 genes of random.Random(0), topology A,
     101x40, batch 64, eval_batch 256) with EVERY MFMA launch sampled, collect the launch-path variants it used --

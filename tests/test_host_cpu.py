@@ -413,3 +413,57 @@ def test_32bit_byte_offset_guard_refuses_oversized_plans():
     buf = C.create_string_buffer(200)
     assert L.cmoop_conv_launch_plan(0, 2 ** 13, 256, 256, 16, 16, 3, 1, 0, buf, 200) != 0      # 2^13 * 2^16 * 16 = 2^33
     assert L.cmoop_conv_launch_plan(0, 64, 101, 40, 16, 16, 3, 1, 0, buf, 200) == 0
+
+
+def _lone_step_plan(plan, layers, B, train):
+    """What cmoop_net_launch_plan lists, named layer by layer with the lone-layer plan (plan = launch_variants.plan)."""
+    out = [plan(0, B, H, W, Ci, Co, KS, st, bn if train else 0) for (H, W, Ci, Co, KS, st, bn) in layers]
+    if train:
+        for (H, W, Ci, Co, KS, st, bn) in reversed(layers):
+            out += [plan(2, B, H, W, Ci, Co, KS, st), plan(1, B, H, W, Ci, Co, KS, st)]
+    return out
+
+
+def test_every_launch_a_net_plans_is_a_variant_of_the_geometry_sweep():
+    """cmoop_net_launch_plan names what a Net launches: the same per-layer context as the trainer, under the net's SHARED
+    split-K workspace, which is sized from cfg.batch and max(batch, eval_batch) only.  An under-filled partial batch can want
+    more than that, so there the net takes another tile / partition than the lone-layer plan (cmoop_conv_launch_plan, what
+    cmoop_conv_*_trainer launch) names for the same layer and batch.  Over SWEEP_FEATURE_SIZES x both topologies x every conv
+    gene, a net planned for batch 64 / eval batch 256: one train step at every batch of SWEEP_BWD_BATCHES and one inference
+    pass at every batch of SWEEP_FWD_BATCHES --
+    (1) every name is a variant of the sweep domain, i.e. its kernel instantiation and path are compared bit for bit by
+        tests/test_gpu_geometry_sweep.py (on some shape; not necessarily on the shape the net pairs it with);
+    (2) the two plans do disagree, e.g. at batch 37 on 101x40: whoever changes the workspace sizing so that they no longer do
+        has to change DESIGN.md ("Launch plan") and INTEGRATION.md with it.
+    The number of disagreeing launches over the domain is printed (DESIGN.md quotes it)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import functools
+    import launch_variants as LV
+    from _sweep_shapes import SWEEP_BWD_BATCHES, SWEEP_FEATURE_SIZES, SWEEP_FWD_BATCHES
+    swept = {v for v, _ in LV.sweep_domain(SWEEP_FEATURE_SIZES, SWEEP_FWD_BATCHES, SWEEP_BWD_BATCHES)}
+    lone = functools.lru_cache(maxsize=None)(LV.plan)
+    names, launches, differ, differ_37 = set(), 0, 0, 0
+    for (T, F) in SWEEP_FEATURE_SIZES:
+        for variant in ("A", "B"):
+            cfg = EvalConfig(variant=variant, batch=64, eval_batch=256).to_struct()
+            for gene in LV.ALL_CONV_GENES:
+                layers = LV.conv_layers(gene, G.VARIANT_NAMES[variant], T, F)
+                for train, batches in ((1, SWEEP_BWD_BATCHES), (0, SWEEP_FWD_BATCHES)):
+                    for B in batches:
+                        net = _lib.net_launch_plan(gene, cfg, T, F, B, train)
+                        alone = _lone_step_plan(lone, layers, B, train)
+                        assert len(net) == len(alone) == len(layers) * (3 if train else 1)
+                        d = sum(a != b for a, b in zip(net, alone))
+                        names.update(net)
+                        launches += len(net)
+                        differ += d
+                        if (T, F) == (101, 40) and B == 37:
+                            differ_37 += d
+    print(f"{differ} of {launches} planned launches take another variant in a net (batch 64, eval batch 256) than alone; "
+          f"{differ_37} of them at batch 37 on 101x40; {len(names)} variant names in nets, {len(swept)} in the sweep domain")
+    assert names <= swept, f"launch-path variants a net launches that the geometry sweep does not compare: {sorted(names - swept)}"
+    assert differ_37 >= 1
+    # a batch the net was not planned for is refused, not planned
+    with pytest.raises(_lib.CmoopError):
+        _lib.net_launch_plan((16, 3, 1, 1, 1, 0), EvalConfig(batch=64, eval_batch=256).to_struct(), 101, 40, 65, 1)

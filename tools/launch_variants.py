@@ -22,19 +22,8 @@ def plan(op, B, H, W, Ci, Co, KS, st, stats=0):
 
 
 def conv_layers(gene, variant, T, F):
-    """(H, W, Cin, Cout, KS, stride, feeds_bn) of every implicit-GEMM conv of a candidate (Net::build_plan's walk)."""
-    f, k, bn, R, fc, dr = gene
-    out = []
-    if variant == 0:
-        out.append((T, F, f, f, k, 1, bn))
-    h, w, c = (T + 1) // 2, (F + 1) // 2, f
-    for _ in range(R):
-        out.append((h, w, c, 2 * c, 1, 2, 0))
-        out.append((h, w, c, 2 * c, k, 1, bn))
-        if variant == 0:
-            out.append((h, w, 2 * c, 2 * c, k, 1, bn))
-        h, w, c = (h + 1) // 2, (w + 1) // 2, 2 * c
-    return out
+    """(H, W, Cin, Cout, KS, stride, feeds_bn) of every implicit-GEMM conv of a candidate (the library's own plan walk)."""
+    return _lib.plan_convs(gene, variant, T, F)
 
 
 def variants_of(genes, variant, T, F, batch=64, eval_batch=256, partial=(37,)):

@@ -7,7 +7,7 @@ per-shape kernel table (tools/kernel_bench.py output, e.g. profiles/r02_kernel_b
 import argparse, ast, collections, os, random, re, sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cmoop_audio_processing_amd import genes as G
+from cmoop_audio_processing_amd import _lib, genes as G
 
 
 def read_table(path):
@@ -21,16 +21,9 @@ def read_table(path):
 
 
 def conv_shapes(g, T=101, F=40):
-    """(H, W, Cin, Cout, KS, stride, needs_dgrad) of every MFMA conv of a variant-A candidate, forward order."""
-    f, k, bn, R, fc, _ = g
-    out = [(T, F, f, f, k, 1, True)]           # conv2; conv1 (C_in = 1) is a VALU kernel
-    h, w, c = (T + 1) // 2, (F + 1) // 2, f    # max-pool
-    for r in range(R):                          # nsga_penalty.py:276-301: skip 1x1/2, conv c->2c, conv 2c->2c, pool
-        out.append((h, w, c, 2 * c, 1, 2, True))
-        out.append((h, w, c, 2 * c, k, 1, True))
-        out.append((h, w, 2 * c, 2 * c, k, 1, True))
-        h, w, c = (h + 1) // 2, (w + 1) // 2, 2 * c
-    return out
+    """(H, W, Cin, Cout, KS, stride, needs_dgrad) of every MFMA conv of a variant-A candidate, forward order (the library's
+    own plan walk; conv1, C_in = 1, is a VALU kernel and not listed)."""
+    return [l[:6] + (True,) for l in _lib.plan_convs(g, G.VARIANT_A, T, F)]
 
 
 def main():
