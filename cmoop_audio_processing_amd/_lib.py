@@ -40,6 +40,12 @@ class DatasetStruct(C.Structure):
                 ("T", C.c_int32), ("F", C.c_int32)]
 
 
+class Augment(C.Structure):
+    """cmoop_augment (include/cmoop.h), 48 bytes."""
+    _fields_ = [(n, C.c_int32) for n in ("time_shift", "time_masks", "time_mask_max", "freq_masks", "freq_mask_max", "reserved")] + \
+        [(n, C.c_double) for n in ("p", "noise_std", "fill")]
+
+
 #: cmoop_next_fn (include/cmoop.h): int32_t (*)(void* ctx)
 NEXT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
@@ -51,6 +57,19 @@ STREAM_PROTOTYPES = {
     "cmoop_logmel_stream_time": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p],
     "cmoop_stream_windows": [C.c_int64, C.c_int32, C.c_int32, C.c_void_p],
     "cmoop_net_predict_stream": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
+#: prototypes of the train-time augmentation entry points (include/cmoop.h); structs travel as void* (C.byref), None is NULL
+AUGMENT_PROTOTYPES = {
+    "cmoop_augment_default": [C.c_void_p],
+    "cmoop_augment_check": [C.c_void_p, C.c_int32, C.c_int32],
+    "cmoop_augment_draws": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
+    "cmoop_augment_batch": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
+                            C.c_void_p],
+    "cmoop_net_set_augment": [C.c_void_p, C.c_void_p],
+    "cmoop_eval_population_aug": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] +
+                                 [C.c_void_p] * 7,
 }
 
 
@@ -92,7 +111,7 @@ def lib():
             if name not in ("cmoop_last_error", "cmoop_config_default"):
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
-        for name, argtypes in STREAM_PROTOTYPES.items():
+        for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         _lib = L
         return L

@@ -101,6 +101,16 @@ static NetConfig to_cfg(const cmoop_config* c) {
     return n;
 }
 
+static_assert(sizeof(cmoop_augment) == 48, "cmoop_augment is part of the ABI");
+static AugmentCfg to_augment(const cmoop_augment* a) {
+    CMOOP_REQUIRE(a != nullptr, "augment config is NULL");
+    AugmentCfg c;
+    c.time_shift = a->time_shift; c.time_masks = a->time_masks; c.time_mask_max = a->time_mask_max;
+    c.freq_masks = a->freq_masks; c.freq_mask_max = a->freq_mask_max;
+    c.p = a->p; c.noise_std = a->noise_std; c.fill = a->fill;
+    return c;
+}
+
 static Dataset to_dataset(const cmoop_dataset* ds) {
     Dataset d;
     d.x_train = ds->x_train; d.y_train = ds->y_train; d.n_train = ds->n_train;
@@ -178,19 +188,25 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
     return guard([&] { *out = fwd_flops_per_sample(gene, variant, classes, T, F); });
 }
 
-// both population calls; next == NULL: candidates are taken longest-first from a process-local counter
-static void eval_population_abi(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n,
-                                cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
-                                double* val_loss, double* seconds, int32_t* evaluated) {
+// every population call; next == NULL: candidates are taken longest-first from a process-local counter; aug == NULL: no augmentation
+static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_dataset* ds, const int32_t* genes,
+                                const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
+                                double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
     CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
     CMOOP_REQUIRE(n >= 0, "negative population size");
+    CMOOP_REQUIRE(!next || evaluated, "NULL argument");
     NetConfig c = to_cfg(cfg);
     const Dataset d = to_dataset(ds);
+    AugmentCfg a;
+    if (aug) {
+        a = to_augment(aug);
+        augment_check(a, d.T, d.F);
+    }
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
-    if (next) eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); });
-    else eval_population(c, d, genes, seeds, n, r.data());
+    if (next) eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); }, aug ? &a : nullptr);
+    else eval_population(c, d, genes, seeds, n, r.data(), {}, aug ? &a : nullptr);
     for (int i = 0; i < n; ++i) {
         if (evaluated) evaluated[i] = r[i].evaluated;
         if (acc) acc[i] = r[i].acc;
@@ -205,15 +221,60 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_dataset* ds
 int cmoop_eval_population(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds,
                           int32_t n, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
                           double* seconds) {
-    return guard([&] { eval_population_abi(cfg, ds, genes, seeds, n, nullptr, nullptr, acc, size_mb, fpr, epochs_run, val_loss, seconds, nullptr); });
+    return cmoop_eval_population_aug(cfg, nullptr, ds, genes, seeds, n, nullptr, nullptr, acc, size_mb, fpr, epochs_run, val_loss, seconds,
+                                     nullptr);
 }
 
 int cmoop_eval_population_pull(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds,
                                int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr,
                                int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
+    if (!next || !evaluated) return guard([] { CMOOP_REQUIRE(false, "NULL argument"); });
+    return cmoop_eval_population_aug(cfg, nullptr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds,
+                                     evaluated);
+}
+
+int cmoop_eval_population_aug(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_dataset* ds, const int32_t* genes,
+                              const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
+                              double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
     return guard([&] {
-        CMOOP_REQUIRE(next && evaluated, "NULL argument");
-        eval_population_abi(cfg, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds, evaluated);
+        eval_population_abi(cfg, aug, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds, evaluated);
+    });
+}
+
+// ---- train-time augmentation ----------------------------------------------------
+int cmoop_augment_default(cmoop_augment* aug) {
+    return guard([&] {
+        CMOOP_REQUIRE(aug != nullptr, "augment config is NULL");
+        const AugmentCfg c;
+        std::memset(aug, 0, sizeof(*aug));
+        aug->time_shift = c.time_shift; aug->time_masks = c.time_masks; aug->time_mask_max = c.time_mask_max;
+        aug->freq_masks = c.freq_masks; aug->freq_mask_max = c.freq_mask_max;
+        aug->p = c.p; aug->noise_std = c.noise_std; aug->fill = c.fill;
+    });
+}
+
+int cmoop_augment_check(const cmoop_augment* aug, int32_t T, int32_t F) {
+    return guard([&] { augment_check(to_augment(aug), T, F); });
+}
+
+int cmoop_augment_draws(const cmoop_augment* aug, uint32_t seed, uint32_t step, int32_t b, int32_t T, int32_t F, int32_t out[18]) {
+    return guard([&] {
+        const AugmentCfg c = to_augment(aug);
+        augment_check(c, T, F);
+        CMOOP_REQUIRE(out != nullptr && b >= 0 && b < (1 << 27), "augment_draws: b must be in [0, 2^27)");
+        augment_row_draws(augment_params(c), seed, step, (uint32_t)b, T, F, out);
+    });
+}
+
+int cmoop_augment_batch(const cmoop_augment* aug, const float* x_dev, const int32_t* idx_dev, int64_t row0, int32_t B, int32_t T,
+                        int32_t F, uint32_t seed, uint32_t step, float* out_dev) {
+    return guard([&] {
+        const AugmentCfg c = to_augment(aug);
+        augment_check(c, T, F);
+        CMOOP_REQUIRE(B >= 0 && row0 >= 0 && (B == 0 || (x_dev && out_dev)), "augment_batch: bad arguments");
+        hipStream_t s = lib_stream();
+        launch_augment_gather(x_dev, idx_dev, row0, out_dev, B, T, F, augment_params(c), seed, step, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
 
@@ -524,6 +585,14 @@ int cmoop_net_get_state(cmoop_net* h, float* params, float* adam_m, float* adam_
 int cmoop_net_set_state(cmoop_net* h, const float* params, const float* adam_m, const float* adam_v, int64_t iterations,
                         int64_t steps) {
     return guard([&] { h->net->set_state(params, adam_m, adam_v, iterations, steps); });
+}
+int cmoop_net_set_augment(cmoop_net* h, const cmoop_augment* aug) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "set_augment: NULL net");
+        if (!aug) { h->net->set_augment(nullptr); return; }
+        const AugmentCfg c = to_augment(aug);
+        h->net->set_augment(&c);
+    });
 }
 int cmoop_net_set_gather_rows(cmoop_net* h, int64_t n_rows) {
     return guard([&] {

@@ -164,6 +164,66 @@ void launch_conv1_wgrad(const float* X, const int32_t* idx, int64_t row0, const 
                         int B, int H, int W, int Cout, int KS, hipStream_t s, const StepState* st = nullptr, int64_t n_rows = 0);
 
 // ---------------------------------------------------------------------------
+// Train-time augmentation of the [T][F] feature patches (opt-in; no reference counterpart): random time shift,
+// SpecAugment time / frequency masks and additive feature noise, keyed by (net seed, global train step, position in the
+// batch) on the counter RNG -- the same bits on the device, in augment_row_draws on the host and in augment.py.
+//   u(k)    = rng_u32(seed, STREAM_AUGMENT, step, 32 b + k),   R(u, n) = ((uint64)u n) >> 32
+//   gate    : (u(0) >> 8) < floor(p 2^24), else the row is a plain copy of its source row
+//   shift   : s = R(u(1), 2 S + 1) - S
+//   t-mask j: w = R(u(2+2j), time_mask_max + 1), t0 = R(u(3+2j), T - w + 1)     (j < time_masks <= 4)
+//   f-mask j: w = R(u(10+2j), freq_mask_max + 1), f0 = R(u(11+2j), F - w + 1)   (j < freq_masks <= 4)
+//   out[b][t][f] = fill when t - s is outside [0, T) or t / f lies in a mask (output coordinates), else x[row][t - s][f],
+//   plus, with noise_std > 0, (float)n * k: n = the four 16-bit halves of rng_u32(seed, STREAM_AUGMENT + 1 | + 2, step, e)
+//   summed minus 131070 (Irwin-Hall, exact integer), e = (b T + t) F + f, k = (float)(noise_std sqrt(3) / 65536)
+// ---------------------------------------------------------------------------
+struct AugmentCfg {
+    int time_shift = 0, time_masks = 0, time_mask_max = 0, freq_masks = 0, freq_mask_max = 0;
+    double p = 1.0, noise_std = 0.0, fill = 0.0;
+};
+constexpr int AUGMENT_MAX_MASKS = 4;
+constexpr int AUGMENT_DRAWS = 18;   // gate, shift, 4 x (w, t0), 4 x (w, f0)
+// host-only: throws with a message naming the offending field when the config is outside the domain for [T][F] patches
+void augment_check(const AugmentCfg& c, int T, int F);
+// p > 0 and at least one of: a shift, a mask with a non-zero largest width, noise.  A disabled config is no config
+bool augment_enabled(const AugmentCfg& c);
+// the config as the kernel reads it: the doubles reduced once on the host
+struct AugmentParams {
+    int S = 0, time_masks = 0, time_mask_max = 0, freq_masks = 0, freq_mask_max = 0;
+    uint32_t gate_thr = 0;   // floor(p 2^24)
+    int noise = 0;           // noise_std > 0
+    float noise_k = 0.f, fill = 0.f;
+};
+AugmentParams augment_params(const AugmentCfg& c);
+// draws of batch position b: d[0] gate, d[1] shift, d[2 + 2j] / d[3 + 2j] width / first frame of time mask j,
+// d[10 + 2j] / d[11 + 2j] width / first band of frequency mask j.  Unused masks are zero; so is everything after the
+// gate of a gated-off row (it is a plain copy)
+__host__ __device__ __forceinline__ uint32_t augment_range(uint32_t u, uint32_t n) { return (uint32_t)(((uint64_t)u * n) >> 32); }
+__host__ __device__ __forceinline__ void augment_row_draws(const AugmentParams& a, uint32_t seed, uint32_t step, uint32_t b, int T,
+                                                           int F, int32_t* d) {
+    const uint32_t prefix = rng_prefix(seed, STREAM_AUGMENT, step), base = 32u * b;
+    for (int k = 1; k < AUGMENT_DRAWS; ++k) d[k] = 0;
+    d[0] = (fmix32(prefix ^ base) >> 8) < a.gate_thr ? 1 : 0;
+    if (!d[0]) return;
+    d[1] = (int32_t)augment_range(fmix32(prefix ^ (base + 1u)), 2u * (uint32_t)a.S + 1u) - a.S;
+    for (int j = 0; j < a.time_masks; ++j) {
+        const uint32_t w = augment_range(fmix32(prefix ^ (base + 2u + 2u * j)), (uint32_t)a.time_mask_max + 1u);
+        d[2 + 2 * j] = (int32_t)w;
+        d[3 + 2 * j] = (int32_t)augment_range(fmix32(prefix ^ (base + 3u + 2u * j)), (uint32_t)T - w + 1u);
+    }
+    for (int j = 0; j < a.freq_masks; ++j) {
+        const uint32_t w = augment_range(fmix32(prefix ^ (base + 10u + 2u * j)), (uint32_t)a.freq_mask_max + 1u);
+        d[10 + 2 * j] = (int32_t)w;
+        d[11 + 2 * j] = (int32_t)augment_range(fmix32(prefix ^ (base + 11u + 2u * j)), (uint32_t)F - w + 1u);
+    }
+}
+// out[B][T][F] = the augmented rows idx[row0 + b] (idx null: row0 + b) of the resident tensor X, b = 0 .. B-1.  A streaming
+// kernel: 16-byte loads / stores along F when F % 4 == 0 and both buffers are 16-byte aligned (a whole-frame shift keeps the
+// alignment), else element by element.  st != null: row0 and step are read from the device state (graph replay).
+// n_rows as launch_conv1_fwd's.  Needs B T F < 2^32 (the noise counter) and T F < 2^30.
+void launch_augment_gather(const float* X, const int32_t* idx, int64_t row0, float* out, int B, int T, int F, const AugmentParams& a,
+                           uint32_t seed, uint32_t step, hipStream_t s, const StepState* st = nullptr, int64_t n_rows = 0);
+
+// ---------------------------------------------------------------------------
 // Per-channel reductions over the M rows of an [M][C] tensor (C % 4 == 0).
 // Two-stage and order-fixed: `blocks` partials then a double-precision finalize.
 // ---------------------------------------------------------------------------

@@ -198,6 +198,12 @@ class Net : public GemmHook {
     // global step that keys the dropout masks -- what a checker needs to re-synchronise with this net at an epoch boundary
     void get_state(float* params, float* m, float* v, long long* iterations, long long* steps);
     void set_state(const float* params, const float* m, const float* v, long long iterations, long long steps);
+    // Train-time augmentation (kernels.h) of every following train step, both step paths; null or a disabled config: off,
+    // and a step's launches and allocations are those of a net that never had one.  Enabled: each step first writes its
+    // augmented batch (keyed by seed, the global step and the position in the batch) to a buffer of cfg.batch rows,
+    // allocated on first use, which the first-layer kernels then read in place of the resident tensor.  Labels, loss,
+    // dropout and Adam are untouched; evaluate / predict / predict_stream never augment.  Drops a captured step graph
+    void set_augment(const AugmentCfg* aug);
     // rows of the resident tensor the next train steps gather from (0: unknown, no clamp)
     void set_gather_rows(int64_t n) { gather_rows_ = n; }
     // ONE epoch of Model.fit on the production path (device permutation of (seed, epoch) when cfg.shuffle, device
@@ -249,6 +255,9 @@ class Net : public GemmHook {
     int64_t n_params_ = 0;
     float *params_ = nullptr, *grads_ = nullptr, *adam_m_ = nullptr, *adam_v_ = nullptr, *snap_ = nullptr;
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;
+    bool aug_on_ = false;               // train steps read aug_buf_ (set_augment)
+    AugmentParams aug_;
+    float* aug_buf_ = nullptr;          // [cfg.batch][T][F], allocated by the first enabled set_augment
     StepState* st_dev_ = nullptr;       // device step state (train_step_stateful)
     float* alpha_tab_ = nullptr;        // Adam step size per iteration
     int64_t alpha_tab_n_ = 0, host_row0_ = 0, gather_rows_ = 0;
@@ -284,7 +293,9 @@ struct FitHistory {
 // Model.fit + EarlyStopping + the read-outs on an EXISTING net (the body of run_candidate); seed keys the epoch shuffle
 EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, uint32_t seed, FitHistory* hist = nullptr);
 // train-to-early-stop + readouts for one candidate (evaluate_individual, nsga_penalty.py:368-395)
-EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream);
+// aug (optional): train-time augmentation of the candidate's fit (Net::set_augment)
+EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
+                         const AugmentCfg* aug = nullptr);
 // host-only: every implicit-GEMM conv geometry of a candidate at batch B (a walk of plan_net's ops); throws
 // through igemm_check_range when a layer is beyond the kernels' 32-bit byte offsets
 void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
@@ -294,7 +305,7 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
 // lets several ranks drain ONE longest-first queue (cross-rank dynamic scheduling, evaluator.py); without it the
 // n candidates are taken longest-first from a process-local counter.
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
-                     EvalResult* out, const std::function<int()>& pull = {});
+                     EvalResult* out, const std::function<int()>& pull = {}, const AugmentCfg* aug = nullptr);
 
 // host-only: windows of T frames at hop frames in a stream of n_frames, 1 + (n_frames - T) / hop; throws when n_frames < T or hop < 1
 int64_t stream_windows(int64_t n_frames, int T, int hop);

@@ -682,12 +682,15 @@ void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool 
     for (size_t oi = 0; oi < ops_.size(); ++oi) {
         const Op& op = ops_[oi];
         switch (op.kind) {
-        case OP_CONV1:
+        case OP_CONV1: {
             fused_stats_blocks_ = 0;
-            launch_conv1_fwd(X, idx, row0, params_ + op.w_off, params_ + op.b_off, acts_[op.out].data, B, T_, F_, op.Cout,
-                             op.KS, op.relu, stream_, st, train ? gather_rows_ : 0, (train && op.feeds_bn) ? red_ws_ : nullptr,
+            const bool aug = train && aug_on_;   // the batch is rows 0 .. B of the buffer step_body's augment launch wrote
+            launch_conv1_fwd(aug ? aug_buf_ : X, aug ? nullptr : idx, aug ? 0 : row0, params_ + op.w_off, params_ + op.b_off,
+                             acts_[op.out].data, B, T_, F_, op.Cout, op.KS, op.relu, stream_, aug ? nullptr : st,
+                             (train && !aug) ? gather_rows_ : 0, (train && op.feeds_bn) ? red_ws_ : nullptr,
                              (train && op.feeds_bn) ? &fused_stats_blocks_ : nullptr);
             break;
+        }
         case OP_CONV: {
             GemmEpilogue e;
             e.mode = op.gemm_mode;
@@ -825,8 +828,12 @@ void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, cons
             break;
         }
         case OP_CONV1: {
-            launch_conv1_wgrad(X, idx, row0, acts_[op.out].grad, wgrad_ws_ + op.slab_off, B, T_, F_, op.Cout, op.KS, stream_, st,
-                               gather_rows_);
+            if (aug_on_)
+                launch_conv1_wgrad(aug_buf_, nullptr, 0, acts_[op.out].grad, wgrad_ws_ + op.slab_off, B, T_, F_, op.Cout, op.KS, stream_,
+                                   nullptr, 0);
+            else
+                launch_conv1_wgrad(X, idx, row0, acts_[op.out].grad, wgrad_ws_ + op.slab_off, B, T_, F_, op.Cout, op.KS, stream_, st,
+                                   gather_rows_);
             AdamSeg sg;
             sg.off = op.w_off;
             sg.n = sg.stride = (int64_t)op.Cout * (op.KS * op.KS + 1);
@@ -844,6 +851,9 @@ void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, cons
 // one optimiser step: forward -> loss -> backward -> Adam.  st == null: explicit host arguments (session API);
 // st != null: batch position / dropout counter / Adam iteration come from the device state, which the step advances
 void Net::step_body(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B, const StepState* st) {
+    // augmentation on: the batch's rows are gathered and augmented into aug_buf_ first (st != null: the kernel reads the
+    // batch position and the step from the device state, so a replayed graph draws for the step it replays)
+    if (aug_on_) launch_augment_gather(X, idx, row0, aug_buf_, B, T_, F_, aug_, seed_, (uint32_t)step_, stream_, st, gather_rows_);
     forward(X, idx, row0, B, true, st);
     launch_softmax_ce(acts_[logits_].data, y, idx, row0, B, cfg_.classes, acts_[logits_].grad, acc_train_, nullptr, stream_, st,
                       gather_rows_);
@@ -984,6 +994,19 @@ void Net::set_state(const float* params, const float* m, const float* v, long lo
     }
     CMOOP_HIP(hipStreamSynchronize(stream_));
     if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
+}
+
+void Net::set_augment(const AugmentCfg* aug) {
+    const bool on = aug != nullptr && augment_enabled(*aug);
+    if (aug) augment_check(*aug, T_, F_);
+    if (on) {
+        CMOOP_REQUIRE((int64_t)cfg_.batch * T_ * F_ < (1ll << 32), "augment: batch * T * F must stay below 2^32");
+        aug_ = augment_params(*aug);
+        if (!aug_buf_) aug_buf_ = dalloc((size_t)cfg_.batch * T_ * F_);
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+    aug_on_ = on;
+    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }   // the captured step has the old launch sequence
 }
 
 void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch, int32_t* idx_scratch) {
@@ -1202,10 +1225,12 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
     return res;
 }
 
-EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream) {
+EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
+                         const AugmentCfg* aug) {
     const auto t0 = std::chrono::steady_clock::now();
     CMOOP_REQUIRE(ds.n_train >= 1 && ds.n_val >= 1, "empty train or validation split");
     Net net(gene, cfg, ds.T, ds.F, seed, stream);
+    if (aug) net.set_augment(aug);
     EvalResult res = fit_and_read_out(net, cfg, ds, seed, nullptr);
     res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return res;
@@ -1223,8 +1248,9 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B) 
 }
 
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
-                     EvalResult* out, const std::function<int()>& pull) {
+                     EvalResult* out, const std::function<int()>& pull, const AugmentCfg* aug) {
     if (n <= 0) return;
+    if (aug && !augment_enabled(*aug)) aug = nullptr;   // a disabled config is no config: today's path, call for call
     for (int i = 0; i < n; ++i) validate_gene(genes + 6 * i);
     for (int i = 0; i < n; ++i) out[i].evaluated = 0;
     // longest first (closed-form FLOPs) so the tail of the generation is made of cheap candidates
@@ -1256,7 +1282,7 @@ void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* gen
                     if (j >= n) break;
                     i = order[j];
                 }
-                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream);
+                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream, aug);
                 out[i].evaluated = 1;
             }
         } catch (const std::exception& e) {

@@ -33,6 +33,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, genes as G
+from .augment import AugmentConfig
 
 FPR_CODES = {"v1": 0, "v1_quirk": 1, "v3": 2}
 ACC_CODES = {"last": 0, "evaluate": 1}
@@ -74,6 +75,9 @@ class EvalConfig:
     # "acc_fpr" (acc_fpr_nsga_1.py:283-310, 'size_metric'), "acc_size" (acc_size_nsga_1.py:283-311, 'fpr_metric'),
     # "size_fpr" (size_fpr_nsga_1.py:283-310, 'acc_metric')
     objectives: str = "all"
+    # train-time augmentation of every candidate's fit (augment.py): None or a config that does nothing = off, every number
+    # as without the field.  Not part of cmoop_config: it travels beside it (cmoop_net_set_augment, cmoop_eval_population_aug)
+    augment: Optional[AugmentConfig] = None
 
     @staticmethod
     def preset(script: str, **over) -> "EvalConfig":
@@ -120,6 +124,12 @@ class EvalConfig:
         c.lr, c.dropout = self.lr, self.dropout
         c.gemm_mode = GEMM_CODES[self.compute]
         return c
+
+    def augment_struct(self, T: int, F: int) -> Optional["_lib.Augment"]:
+        """The enabled augmentation as a ``cmoop_augment``, checked for [T, F] patches; None when it is off."""
+        if self.augment is None or not self.augment.enabled:
+            return None
+        return self.augment.check(T, F)._struct()
 
 
 def _as_device_features(x):
@@ -363,9 +373,15 @@ class PopulationEvaluator:
         acc, size, fpr, secs = (np.zeros(n, np.float64) for _ in range(4))
         ep = np.zeros(n, np.int32)
         cfg, ds = self.config.to_struct(), self._dataset()
-        _lib.check(_lib.lib().cmoop_eval_population(
-            C.byref(cfg), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), _lib.ptr(acc), _lib.ptr(size),
-            _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs)))
+        aug = self.config.augment_struct(self.T, self.F)
+        if aug is not None:
+            _lib.check(_lib.lib().cmoop_eval_population_aug(
+                C.byref(cfg), C.byref(aug), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), None, None, _lib.ptr(acc),
+                _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), None))
+        else:
+            _lib.check(_lib.lib().cmoop_eval_population(
+                C.byref(cfg), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), _lib.ptr(acc), _lib.ptr(size),
+                _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs)))
         out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4] = acc, size, fpr, ep, secs
         return out
 
@@ -394,9 +410,15 @@ class PopulationEvaluator:
                 errors.append(e)
                 return -1
         cb = _lib.NEXT_FN(_next)
-        _lib.check(_lib.lib().cmoop_eval_population_pull(
-            C.byref(cfg), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), cb, None, _lib.ptr(acc), _lib.ptr(size),
-            _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
+        aug = self.config.augment_struct(self.T, self.F)
+        if aug is not None:
+            _lib.check(_lib.lib().cmoop_eval_population_aug(
+                C.byref(cfg), C.byref(aug), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), C.cast(cb, C.c_void_p), None,
+                _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
+        else:
+            _lib.check(_lib.lib().cmoop_eval_population_pull(
+                C.byref(cfg), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), cb, None, _lib.ptr(acc), _lib.ptr(size),
+                _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
         if errors:
             raise errors[0]
         return {int(i): np.array([acc[i], size[i], fpr[i], ep[i], secs[i]], dtype=np.float64) for i in np.nonzero(done)[0]}

@@ -24,6 +24,24 @@ class NetSession:
         _lib.check(_lib.lib().cmoop_net_total_params(self._h, C.byref(n)))
         self.n_params = int(n.value)
         self.T, self.F = int(T), int(F)
+        self.augment = None
+        if getattr(config, "augment", None) is not None:
+            try:
+                self.set_augment(config.augment)
+            except Exception:
+                self.close()
+                raise
+
+    def set_augment(self, augment) -> None:
+        """Train-time augmentation (``AugmentConfig``) of every following train step of this net -- ``train_step``,
+        ``run_epoch`` and ``fit`` alike; None or a config that does nothing turns it off.  ``evaluate``, ``predict_proba``
+        and ``predict_stream`` never augment; ``train_metrics`` then reports the loss and accuracy of the augmented batches."""
+        if augment is None:
+            _lib.check(_lib.lib().cmoop_net_set_augment(self._h, None))
+        else:
+            st = augment.check(self.T, self.F)._struct()
+            _lib.check(_lib.lib().cmoop_net_set_augment(self._h, C.byref(st)))
+        self.augment = augment
 
     def close(self):
         if self._h:

@@ -19,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import synth_waveforms  # noqa: E402
-from cmoop_audio_processing_amd import EvalConfig, PopulationEvaluator, frontend, nsga  # noqa: E402
+from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, PopulationEvaluator, frontend, nsga  # noqa: E402
 
 
 def main():
@@ -38,6 +38,9 @@ def main():
     ap.add_argument("--snr-db", type=float, default=-17.0, help="SNR of the --hard set")
     ap.add_argument("--fpr", default="v1_quirk", choices=["v1_quirk", "v1", "v3"],
                     help="v1_quirk = nsga_penalty.py:387 (y_true all zeros: FPR <= 1/C, constraint g3 inactive); v1 = every other script")
+    ap.add_argument("--augment", default="", choices=["", "kws"],
+                    help="train-time augmentation of every candidate's fit (AugmentConfig.preset; the reference has none): "
+                         "kws = time shift <= 10 frames, 2 time masks <= 10, 2 frequency masks <= 5")
     a = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -52,7 +55,8 @@ def main():
     frontend.prepare_dataset(Xtr, Xva, None, mode="refit")
     ev = PopulationEvaluator(Xtr, y[:n_tr], Xva, y[n_tr:n_tr + n_va],
                              EvalConfig.preset("nsga_penalty", epochs=a.epochs, seed=a.seed, verbose=(rank == 0),
-                                               compute=a.compute, fpr_variant=a.fpr))
+                                               compute=a.compute, fpr_variant=a.fpr,
+                                               augment=AugmentConfig.preset(a.augment) if a.augment else None))
     calls = []
     t_start = time.perf_counter()
     if rank == 0:      # a generation at full size takes minutes: keep stderr alive (job runners kill silent commands)

@@ -22,7 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import synth_waveforms  # noqa: E402
-from cmoop_audio_processing_amd import EvalConfig, PopulationEvaluator, datasets, frontend, nsga, surrogate  # noqa: E402
+from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, PopulationEvaluator, datasets, frontend, nsga, surrogate  # noqa: E402
 
 
 def main():
@@ -41,6 +41,9 @@ def main():
                          "patches through FrontendConfig.preset('birdclef_128') (a build-defined recipe, see its docstring)")
     ap.add_argument("--out", default="sa_nsga_generations.csv")
     ap.add_argument("--trace", default="", help="write a JSON trace: per evaluate call wall-clock, epochs run, hypervolume")
+    ap.add_argument("--augment", default="", choices=["", "kws"],
+                    help="train-time augmentation of every candidate's fit (AugmentConfig.preset; the reference has none): "
+                         "kws = time shift <= 10 frames, 2 time masks <= 10, 2 frequency masks <= 5")
     a = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -59,8 +62,10 @@ def main():
     del wav
     Xtr, ytr, Xva, yva, _, _ = datasets.stratified_50_25_25(feats, y.cpu().numpy(), random_state=42)
     preset = "sa_nsga_local" if a.memetic else "sa_nsga_penalty"
+    # this script's features are not standardised (Q2): masked cells take the training mean, not 0.0
+    augment = AugmentConfig.preset(a.augment, fill=float(Xtr.mean())) if a.augment else None
     ev = PopulationEvaluator(Xtr, ytr, Xva, yva, EvalConfig.preset(preset, classes=a.classes, epochs=a.epochs, seed=a.seed,
-                                                                   verbose=(rank == 0), compute=a.compute))
+                                                                   verbose=(rank == 0), compute=a.compute, augment=augment))
     calls = []
     t_start = time.perf_counter()
 

@@ -105,6 +105,47 @@ int cmoop_eval_population_pull(const cmoop_config* cfg, const cmoop_dataset* ds,
                                double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds,
                                int32_t* evaluated /* [n], required */);
 
+/* ---- train-time augmentation of the [T][F] feature patches (opt-in, off by default; the reference has none).
+ * Keyed by (seed of the net, global train step -- the `steps` of cmoop_net_get_state, the counter that keys dropout --,
+ * position b of the row inside its batch), so the same bits come out of the device, of cmoop_augment_draws and of the
+ * numpy restatement in augment.py:
+ *   u(k) = rng_u32(seed, 0x4000, step, 32 b + k),  R(u, n) = ((uint64)u * n) >> 32
+ *   gate         the row is augmented iff (u(0) >> 8) < floor(p * 2^24), else it is a plain copy of its source row
+ *   time shift   s = R(u(1), 2 time_shift + 1) - time_shift
+ *   time mask j  w = R(u(2+2j), time_mask_max + 1), t0 = R(u(3+2j), T - w + 1): frames [t0, t0 + w)    (j < time_masks)
+ *   freq mask j  w = R(u(10+2j), freq_mask_max + 1), f0 = R(u(11+2j), F - w + 1): bands [f0, f0 + w)   (j < freq_masks)
+ *   out[b][t][f] = fill when t - s is outside [0, T) or t is in a time mask or f in a frequency mask (masks are in output
+ *                  coordinates: applied after the shift), else x[row(b)][t - s][f]
+ *   noise (noise_std > 0, un-filled positions of gated-on rows): + (float)n * k, two separately rounded fp32 operations;
+ *                  e = (b T + t) F + f, a = rng_u32(seed, 0x4001, step, e), c = rng_u32(seed, 0x4002, step, e),
+ *                  n = lo16(a) + hi16(a) + lo16(c) + hi16(c) - 131070, k = (float)(noise_std * sqrt(3) / 65536):
+ *                  a 4-term Irwin-Hall variate, mean 0, standard deviation noise_std, |.| <= 3.47 noise_std
+ * Domain: 0 <= p <= 1, 0 <= time_shift < T, 0 <= time_masks, freq_masks <= 4, 0 <= time_mask_max <= T,
+ * 0 <= freq_mask_max <= F, noise_std >= 0 and finite, fill finite (0.0 is the feature mean after the StandardScaler).
+ * A config is ENABLED iff p > 0 and it has a shift, a mask with a non-zero largest width, or noise; a disabled config
+ * is the same as no config. */
+typedef struct cmoop_augment {
+    int32_t time_shift, time_masks, time_mask_max, freq_masks, freq_mask_max, reserved;
+    double p, noise_std, fill;
+} cmoop_augment;
+int cmoop_augment_default(cmoop_augment* aug); /* everything off: p 1, no shift, no masks, no noise, fill 0 */
+/* host-only: non-zero + a message naming the offending field when the config is outside the domain for [T][F] patches */
+int cmoop_augment_check(const cmoop_augment* aug, int32_t T, int32_t F);
+/* host-only: the draws of batch position b at `step`: out = gate, s, (w, t0) of the four time masks, (w, f0) of the four
+ * frequency masks.  Unused masks are zero, and so is everything after the gate of a gated-off row. */
+int cmoop_augment_draws(const cmoop_augment* aug, uint32_t seed, uint32_t step, int32_t b, int32_t T, int32_t F, int32_t out[18]);
+/* the kernel alone, on the library stream: out_dev [B][T][F] = the augmented rows idx_dev[row0 + b] (idx_dev NULL:
+ * row0 + b) of x_dev [.][T][F].  Any config of the domain, enabled or not (p = 0 is a plain gather).  B * T * F < 2^32. */
+int cmoop_augment_batch(const cmoop_augment* aug, const float* x_dev, const int32_t* idx_dev /* may be NULL */, int64_t row0,
+                        int32_t B, int32_t T, int32_t F, uint32_t seed, uint32_t step, float* out_dev);
+/* compute_objectives_and_constraints' inner loop with train-time augmentation: cmoop_eval_population (next == NULL: the
+ * library's own longest-first queue; evaluated may then be NULL) or cmoop_eval_population_pull (next != NULL) with every
+ * candidate's fit augmented by aug.  aug NULL or disabled: exactly those two calls. */
+int cmoop_eval_population_aug(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_dataset* ds,
+                              const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next,
+                              void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
+                              double* seconds, int32_t* evaluated);
+
 /* host-only: does every conv layer of this candidate at `batch` rows per launch (pass max(batch, eval_batch)) stay inside
  * the kernels' 32-bit byte offsets (each activation / kernel tensor below 2^29 elements)?  Non-zero + message if not;
  * cmoop_net_create and the population calls make the same check before they allocate anything. */
@@ -243,6 +284,11 @@ int cmoop_net_predict_stream(cmoop_net* net, const float* feat_dev, int64_t n_fr
 int cmoop_net_get_state(cmoop_net* net, float* params, float* adam_m, float* adam_v, int64_t* iterations, int64_t* steps);
 int cmoop_net_set_state(cmoop_net* net, const float* params, const float* adam_m, const float* adam_v, int64_t iterations,
                         int64_t steps);
+/* Train-time augmentation of every following cmoop_net_train_step / _run_epoch / _fit step of this net (aug NULL or a
+ * disabled config: off, and the net steps bit for bit as one that never had one).  cmoop_net_evaluate / _predict /
+ * _predict_stream never augment.  The loss and accuracy cmoop_net_train_metrics reports are those of the augmented batches.
+ * The draws are keyed by the position in the batch and the step: another cfg.batch gives other draws. */
+int cmoop_net_set_augment(cmoop_net* net, const cmoop_augment* aug /* NULL = off */);
 /* rows the resident training tensor holds: gathered row indices are clamped into [0, n_rows) (0 = unknown, no clamp) */
 int cmoop_net_set_gather_rows(cmoop_net* net, int64_t n_rows);
 /* ONE epoch of Model.fit on the trainer's own path: epoch permutation of (seed, epoch) computed on the device when

@@ -4,7 +4,10 @@ its slowest-converging candidate does, and that is often a small net).  Syntheti
 stream, fixed epochs; prints train steps/s and the evaluation's wall time.  Run it under
 `rocprofv3 --kernel-trace --stats` to get the sum of kernel durations and the launch count of the same command.
 
-  python tools/lone_candidate.py 16,3,0,1,1,0 [--variant A] [--clips 6000] [--epochs 2]
+  python tools/lone_candidate.py 16,3,0,1,1,0 [--variant A] [--clips 6000] [--epochs 2] [--augment kws [--noise-std 0.1]]
+
+--augment NAME trains with AugmentConfig.preset(NAME): one more launch (the augment kernel) and 2 * 4 * batch * T * F bytes
+per step; compare the ms per step with and without it.
 """
 import argparse
 import json
@@ -16,7 +19,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cmoop_audio_processing_amd import EvalConfig, PopulationEvaluator, genes as G  # noqa: E402
+from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, PopulationEvaluator, genes as G  # noqa: E402
 
 
 def main():
@@ -26,6 +29,8 @@ def main():
     ap.add_argument("--clips", type=int, default=6000)
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--repeat", type=int, default=2)
+    ap.add_argument("--augment", default="", help="AugmentConfig.preset name (kws); empty: no augmentation")
+    ap.add_argument("--noise-std", type=float, default=0.0, help="feature noise on top of the --augment preset")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     g = torch.Generator(device="cuda")
@@ -33,7 +38,9 @@ def main():
     n_tr, n_va = int(args.clips * 0.8), int(args.clips * 0.1)
     X = torch.randn((n_tr + n_va, 101, 40), device="cuda", generator=g)
     y = (torch.arange(n_tr + n_va, device="cuda") % 10).to(torch.int32)
-    cfg = EvalConfig.preset("nsga_penalty", variant=args.variant, epochs=args.epochs, early_stop=False, n_slots=1, seed=0)
+    augment = AugmentConfig.preset(args.augment, noise_std=args.noise_std) if args.augment else None
+    cfg = EvalConfig.preset("nsga_penalty", variant=args.variant, epochs=args.epochs, early_stop=False, n_slots=1, seed=0,
+                            augment=augment)
     ev = PopulationEvaluator(X[:n_tr], y[:n_tr], X[n_tr:], y[n_tr:], cfg)
     steps = args.epochs * ((n_tr + cfg.batch - 1) // cfg.batch)
     for gs in args.genes:
@@ -46,7 +53,8 @@ def main():
             ev.evaluate_individual(hp)
             best = min(best, time.perf_counter() - t0)
         fl = G.eval_flops(gene, G.VARIANT_NAMES[args.variant], 10, 101, 40, n_tr, n_va, args.epochs, 1)
-        print(json.dumps({"gene": gene, "variant": args.variant, "train_steps": steps, "wall_s": round(best, 4),
+        print(json.dumps({"gene": gene, "variant": args.variant, "augment": args.augment or None, "noise_std": args.noise_std,
+                          "train_steps": steps, "wall_s": round(best, 4),
                           "steps_per_s": round(steps / best, 1), "ms_per_step_incl_val": round(best / steps * 1e3, 4),
                           "tflops": round(fl / best / 1e12, 2)}), flush=True)
 
