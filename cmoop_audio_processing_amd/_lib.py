@@ -73,6 +73,20 @@ AUGMENT_PROTOTYPES = {
 }
 
 
+#: prototypes of the PCEN entry points (include/cmoop.h); structs travel as void* (C.byref)
+PCEN_PROTOTYPES = {
+    "cmoop_pcen_default": [C.c_void_p],
+    "cmoop_pcen_check": [C.c_void_p],
+    "cmoop_pcen_smoothing": [C.c_double, C.c_int32, C.c_int32, C.c_void_p],
+    "cmoop_pcen_apply": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32],
+    "cmoop_logmel_pcen": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
+    "cmoop_pcen_stream_plan": [C.c_int64, C.c_void_p, C.c_void_p],
+    "cmoop_pcen_stream": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32],
+    "cmoop_logmel_pcen_stream": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "cmoop_logmel_pcen_stream_time": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p],
+}
+
+
 def build(verbose: bool = False) -> str:
     """Compile libcmoop_hip.so for gfx950 in-tree (make; hipcc cross-compiles on CPU-only hosts)."""
     jobs = str(min(8, os.cpu_count() or 1))
@@ -111,7 +125,7 @@ def lib():
             if name not in ("cmoop_last_error", "cmoop_config_default"):
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
-        for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()):
+        for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(PCEN_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         _lib = L
         return L

@@ -83,6 +83,22 @@ static FrontendCfg to_frontend_cfg(const cmoop_frontend_config* c) {
     return f;
 }
 
+static_assert(sizeof(cmoop_pcen) == 48, "cmoop_pcen is part of the ABI");
+static PcenParams to_pcen(const cmoop_pcen* p) {
+    CMOOP_REQUIRE(p != nullptr, "pcen config is NULL");
+    PcenCfg c;
+    c.s = p->s; c.alpha = p->alpha; c.delta = p->delta; c.r = p->r; c.eps = p->eps; c.input_scale = p->input_scale;
+    pcen_check(c);
+    return pcen_params(c);
+}
+// the front end config of a PCEN call: any scale but 2 (power) is the caller's mistake, not something to override
+static FrontendCfg to_pcen_frontend_cfg(const cmoop_frontend_config* c, const char* who) {
+    const FrontendCfg f = to_frontend_cfg(c);
+    CMOOP_REQUIRE(f.scale == 2, std::string(who) + ": PCEN normalises mel power, the front end config must have scale 2 (got scale " +
+                                    std::to_string(f.scale) + ")");
+    return f;
+}
+
 static NetConfig to_cfg(const cmoop_config* c) {
     CMOOP_REQUIRE(c != nullptr, "config is NULL");
     NetConfig n;
@@ -133,6 +149,21 @@ static double time_launches(hipStream_t s, int iters, F&& once) {
     CMOOP_HIP(hipEventElapsedTime(&ms, a, b));
     hipEventDestroy(a); hipEventDestroy(b);
     return (double)ms / std::max(1, iters);
+}
+
+// the three PCEN launches on s with their pooled workspace; the workspace goes back once the stream has drained
+template <class F>
+static void with_pcen_workspace(int T, int n_bands, hipStream_t s, F&& body) {
+    float* ws = static_cast<float*>(pool_alloc(std::max<size_t>(pcen_stream_workspace_floats(T, n_bands), 4) * sizeof(float)));
+    try {
+        body(ws);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    } catch (...) {
+        hipStreamSynchronize(s);
+        pool_free(ws);
+        throw;
+    }
+    pool_free(ws);
 }
 
 // device scratch of one call: released when the call ends, after its stream has drained
@@ -451,6 +482,105 @@ int cmoop_logmel_stream_time(const cmoop_frontend_config* c, const float* wav_de
         const int cu = compute_units_of_current_device();
         hipStream_t s = lib_stream();
         *avg_ms = time_launches(s, iters, [&] { launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s); });
+    });
+}
+
+// ---- PCEN ----------------------------------------------------------------------
+int cmoop_pcen_default(cmoop_pcen* p) {
+    return guard([&] {
+        CMOOP_REQUIRE(p != nullptr, "pcen config is NULL");
+        const PcenCfg c;
+        p->s = c.s; p->alpha = c.alpha; p->delta = c.delta; p->r = c.r; p->eps = c.eps; p->input_scale = c.input_scale;
+    });
+}
+
+int cmoop_pcen_check(const cmoop_pcen* p) {
+    return guard([&] { to_pcen(p); });
+}
+
+int cmoop_pcen_smoothing(double time_constant_s, int32_t sr, int32_t hop, double* s) {
+    return guard([&] {
+        CMOOP_REQUIRE(s != nullptr, "pcen_smoothing: NULL output");
+        *s = pcen_smoothing(time_constant_s, sr, hop);
+    });
+}
+
+int cmoop_pcen_stream_plan(int64_t n_frames, int32_t* chunk, int32_t* n_chunks) {
+    return guard([&] {
+        int ch = 0, nc = 0;
+        pcen_stream_plan(n_frames, &ch, &nc);
+        if (chunk) *chunk = ch;
+        if (n_chunks) *n_chunks = nc;
+    });
+}
+
+int cmoop_pcen_apply(const cmoop_pcen* p, float* e_dev, int64_t n, int32_t T, int32_t F) {
+    return guard([&] {
+        const PcenParams pp = to_pcen(p);
+        hipStream_t s = lib_stream();
+        launch_pcen_apply(pp, e_dev, n, T, F, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_logmel_pcen(const cmoop_frontend_config* c, const cmoop_pcen* p, const float* wav_dev, int64_t n_clips, int32_t n_samples,
+                      float* out_dev) {
+    return guard([&] {
+        const FrontendCfg f = to_pcen_frontend_cfg(c, "logmel_pcen");
+        const PcenParams pp = to_pcen(p);
+        CMOOP_REQUIRE(n_samples >= 1 && n_clips >= 0, "logmel_pcen: n_samples >= 1, n_clips >= 0");
+        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+        hipStream_t s = lib_stream();
+        launch_logmel_pcen(wav_dev, n_clips, n_samples, out_dev, tables.get(), pp, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_pcen_stream(const cmoop_pcen* p, float* e_dev, int64_t n_frames, int32_t F) {
+    return guard([&] {
+        const PcenParams pp = to_pcen(p);
+        CMOOP_REQUIRE(F >= 1 && F <= FRONTEND_MAX_MELS, "pcen_stream: F must lie in 1..128 (got " + std::to_string(F) + ")");
+        CMOOP_REQUIRE(n_frames >= 1 && n_frames * F <= 0x7fffffffll - 256, "pcen_stream: n_frames >= 1, n_frames * F must stay below 2^31");
+        CMOOP_REQUIRE(e_dev != nullptr, "pcen_stream: NULL buffer");
+        hipStream_t s = lib_stream();
+        with_pcen_workspace((int)n_frames, F, s, [&](float* ws) { launch_pcen_stream(pp, e_dev, (int)n_frames, F, ws, s); });
+    });
+}
+
+int cmoop_logmel_pcen_stream(const cmoop_frontend_config* c, const cmoop_pcen* p, const float* wav_dev, int64_t n_samples,
+                             float* out_dev) {
+    return guard([&] {
+        const FrontendCfg f = to_pcen_frontend_cfg(c, "logmel_pcen_stream");
+        const PcenParams pp = to_pcen(p);
+        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+        const int cu = compute_units_of_current_device();
+        hipStream_t s = lib_stream();
+        CMOOP_REQUIRE(n_samples >= 1 && n_samples <= 0x7fffffffll - 2 * f.n_fft, "stream front end: 1 <= n_samples < 2^31 - 2 n_fft");
+        const int T = frontend_frames(f, (int)n_samples);
+        with_pcen_workspace(T, f.n_mels, s, [&](float* ws) {
+            launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s);
+            launch_pcen_stream(pp, out_dev, T, f.n_mels, ws, s);
+        });
+    });
+}
+
+int cmoop_logmel_pcen_stream_time(const cmoop_frontend_config* c, const cmoop_pcen* p, const float* wav_dev, int64_t n_samples,
+                                  float* out_dev, int32_t iters, double* avg_ms) {
+    return guard([&] {
+        const FrontendCfg f = to_pcen_frontend_cfg(c, "logmel_pcen_stream_time");
+        const PcenParams pp = to_pcen(p);
+        CMOOP_REQUIRE(iters >= 1 && avg_ms, "logmel_pcen_stream_time: iters >= 1");
+        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+        const int cu = compute_units_of_current_device();
+        hipStream_t s = lib_stream();
+        CMOOP_REQUIRE(n_samples >= 1 && n_samples <= 0x7fffffffll - 2 * f.n_fft, "stream front end: 1 <= n_samples < 2^31 - 2 n_fft");
+        const int T = frontend_frames(f, (int)n_samples);
+        with_pcen_workspace(T, f.n_mels, s, [&](float* ws) {
+            *avg_ms = time_launches(s, iters, [&] {
+                launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s);
+                launch_pcen_stream(pp, out_dev, T, f.n_mels, ws, s);
+            });
+        });
     });
 }
 

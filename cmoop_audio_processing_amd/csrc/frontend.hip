@@ -1,6 +1,6 @@
-// Audio front end: framing -> Hann -> real FFT -> |.|^2 -> sparse Slaney mel -> log (or dB).
+// Audio front end: framing -> Hann -> real FFT -> |.|^2 -> sparse Slaney mel -> log (or dB, or power -> PCEN).
 // logmel_kernel is the 512-point kernel of the build-defined configuration; logmel_ex_kernel (further down) serves
-// n_fft 256-2048, up to 128 bands and the dB scale.  Both have a stream form (logmel_stream_kernel,
+// n_fft 256-2048, up to 128 bands and the dB and power scales.  Both have a stream form (logmel_stream_kernel,
 // logmel_ex_stream_kernel) for ONE long recording: the grid runs over runs of its frames instead of over clips, the frame
 // arithmetic is the same __device__ function.
 // North-star addition beneath the reference's data loader (the reference ships
@@ -69,7 +69,7 @@ void frontend_check(const FrontendCfg& c) {
     if (c.n_mels < 1 || c.n_mels > FRONTEND_MAX_MELS) fail("n_mels", "must lie in 1..128 (got " + std::to_string(c.n_mels) + ")");
     if (!(c.fmax <= 0.5f * (float)c.sr)) fail("fmax", "must not exceed sr/2 (got " + std::to_string(c.fmax) + ")");
     if (!(c.fmin >= 0.f && c.fmin < c.fmax)) fail("fmin", "must satisfy 0 <= fmin < fmax (got " + std::to_string(c.fmin) + ")");
-    if (c.scale != 0 && c.scale != 1) fail("scale", "must be 0 (log) or 1 (dB)");
+    if (c.scale != 0 && c.scale != 1 && c.scale != 2) fail("scale", "must be 0 (log), 1 (dB) or 2 (power)");
     if (c.scale == 0 && !(c.log_eps > 0.f)) fail("log_eps", "must be positive");
     if (c.scale == 1 && !(c.db_amin > 0.f)) fail("db_amin", "must be positive");
     if (c.scale == 1 && !(c.top_db == c.top_db)) fail("top_db", "must be a number (negative: no clip)");
@@ -365,9 +365,10 @@ __global__ __launch_bounds__(256) void logmel_stream_kernel(const float* __restr
 // subtracts the reference and applies the top_db floor to its own rows -- no second launch, no atomics.
 __device__ __forceinline__ int ex_slot(const int i) { return (i & ~15) | ((i + 5 * (i >> 4)) & 15); }
 
-// Frames [f0, f1) of one waveform `clip`, written to rows f0.. of `rows` ([.][n_mels]) as log(mel + eps) or as the
-// un-referenced 10 log10(max(amin, mel)); returns this lane's largest stored value (dB scale).  Shared by
-// logmel_ex_kernel (a clip's frames, then the dB tail) and logmel_ex_stream_kernel (one run of a recording's frames).
+// Frames [f0, f1) of one waveform `clip`, written to rows f0.. of `rows` ([.][n_mels]) as log(mel + eps), as the
+// un-referenced 10 log10(max(amin, mel)) or as the mel power itself (scale 2); returns this lane's largest stored value
+// (dB scale).  Shared by logmel_ex_kernel (a clip's frames, then the dB tail), logmel_pcen_kernel (a clip's frames, then
+// the PCEN recurrence) and logmel_ex_stream_kernel (one run of a recording's frames).
 template <int NC>
 __device__ __forceinline__ float logmel_ex_frames(const float* __restrict__ clip, int n_samples, float* __restrict__ rows,
                                                   int f0, int f1, int hop, int n_mels, int scale, float log_eps, float amin,
@@ -516,9 +517,11 @@ __device__ __forceinline__ float logmel_ex_frames(const float* __restrict__ clip
                 float y;
                 if (scale == 0) {
                     y = logf(acc + log_eps);
-                } else {
+                } else if (scale == 1) {
                     y = 10.f * log10f(fmaxf(amin, acc));
                     vmax = fmaxf(vmax, y);
+                } else {
+                    y = acc;                                     // linear mel power; a band without a bin stores 0
                 }
                 rows[(size_t)frame * n_mels + band] = y;
             }
@@ -539,7 +542,7 @@ __global__ __launch_bounds__(256) void logmel_ex_kernel(const float* __restrict_
     float* rows = out + (size_t)blockIdx.x * T * n_mels;
     float vmax = logmel_ex_frames<NC>(wav + (size_t)blockIdx.x * n_samples, n_samples, rows, 0, T, hop, n_mels, scale, log_eps,
                                       amin, g_tw, g_win, g_melw, g_band, nnz);
-    if (scale == 0) return;                                      // kernel argument: uniform over the grid
+    if (scale != 1) return;                                      // kernel argument: uniform over the grid
     // dB scale: reference and top_db floor from the clip's own maximum, applied to the rows this workgroup stored
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
@@ -638,6 +641,239 @@ void launch_logmel_stream(const float* wav, int64_t n_samples, float* out, const
     } else {
         launch_logmel_ex_stream<1024>(wav, (int)n_samples, out, T, run, t, s);
     }
+    CMOOP_HIP(hipGetLastError());
+}
+
+// ---- PCEN: per-channel energy normalisation of mel power (Wang et al. 2017; no reference counterpart) ---------------
+// Per band, E[t] = input_scale P[t]:  M[t] = M[t-1] + s (E[t] - M[t-1]), M[-1] = E[0];
+//                                     out[t] = (E[t] / (eps + M[t])^alpha + delta)^r - delta^r.
+// The recurrence is serial in t and independent over bands, so every kernel gives a band (of a clip or of a chunk) to one
+// thread with lanes on consecutive bands: a frame row is one coalesced access.
+//   pcen_apply_kernel     clip form on a power tensor [n][T][F], one thread per (clip, band)
+//   logmel_pcen_kernel    one launch from audio: the clip's workgroup stores power (logmel_ex_frames), barriers, then its
+//                         first n_mels threads walk their own rows -- where the dB tail sits in logmel_ex_kernel
+//   stream form, ONE recording [T][F] cut into chunks of `chunk` frames (pcen_stream_plan), three launches on one stream:
+//     pcen_local_kernel   per (chunk, band): the smoother's state at the chunk's end from a zero start
+//     pcen_carry_kernel   one workgroup, a thread per band, serial over chunks: carry[0] = E[0],
+//                         carry[c+1] = a^chunk carry[c] + local[c]   (the update is linear in M: exact in real arithmetic)
+//     pcen_apply_stream_kernel  per (chunk, band): the recurrence from carry[c], in place
+//   The launches order themselves on the stream: no flags, no spinning, no atomics between workgroups.
+// pcen_scale / pcen_step are the only arithmetic; contraction is off inside them so every kernel rounds alike.
+__device__ __forceinline__ float pcen_scale(const PcenParams& p, const float P) {
+#pragma clang fp contract(off)
+    return p.input_scale * P;
+}
+// one frame: advances M and returns the output; dr = pcen_floor(p)
+__device__ __forceinline__ float pcen_step(const PcenParams& p, const float dr, const float P, float& M) {
+#pragma clang fp contract(off)
+    const float E = pcen_scale(p, P);
+    M = fmaf(p.s, E - M, M);
+    return powf(E / powf(p.eps + M, p.alpha) + p.delta, p.r) - dr;
+}
+// delta^r by the call that raises the first term: E = 0 gives powf(0 + delta, r) - powf(delta, r) = 0.0f exactly
+__device__ __forceinline__ float pcen_floor(const PcenParams& p) { return powf(p.delta, p.r); }
+
+// `len` frames of one band column (rows [.][F]) from the state M, in place when WRITE (else only M advances: the output,
+// and with it both powf, is dead code).  The chain is serial but its loads are not: eight frames are read ahead of it,
+// which the compiler cannot do by itself past the stores.  The order of the arithmetic is the plain loop's.
+constexpr int PCEN_AHEAD = 8;
+template <bool WRITE, class Ptr>
+__device__ __forceinline__ void pcen_run(const PcenParams& p, const float dr, Ptr col, const int len, const int F, float& M) {
+    int t = 0;
+    for (; t + PCEN_AHEAD <= len; t += PCEN_AHEAD) {
+        float v[PCEN_AHEAD];
+#pragma unroll
+        for (int u = 0; u < PCEN_AHEAD; ++u) v[u] = col[(size_t)(t + u) * F];
+#pragma unroll
+        for (int u = 0; u < PCEN_AHEAD; ++u) {
+            const float o = pcen_step(p, dr, v[u], M);
+            if constexpr (WRITE) col[(size_t)(t + u) * F] = o;
+        }
+    }
+    for (; t < len; ++t) {
+        const float o = pcen_step(p, dr, col[(size_t)t * F], M);
+        if constexpr (WRITE) col[(size_t)t * F] = o;
+    }
+}
+
+// rows [.][F] of one band column: frames [0, T) from the state M[-1] = E[0]
+__device__ __forceinline__ void pcen_walk(const PcenParams& p, float* col, int T, int F) {
+    float M = pcen_scale(p, col[0]);
+    pcen_run<true>(p, pcen_floor(p), col, T, F, M);
+}
+
+__global__ __launch_bounds__(256) void pcen_apply_kernel(PcenParams p, float* __restrict__ e, int cols, int T, int F) {
+    const int g = blockIdx.x * 256 + threadIdx.x;                // (clip, band) = (g / F, g % F); cols = n F
+    if (g >= cols) return;
+    const int clip = g / F, band = g - clip * F;
+    pcen_walk(p, e + (size_t)clip * T * F + band, T, F);
+}
+
+template <int NC>
+__global__ __launch_bounds__(256) void logmel_pcen_kernel(const float* __restrict__ wav, int n_samples, float* __restrict__ out,
+                                                          int T, int hop, int n_mels, PcenParams p,
+                                                          const float* __restrict__ g_tw, const float* __restrict__ g_win,
+                                                          const float* __restrict__ g_melw, const int* __restrict__ g_band,
+                                                          int nnz) {
+    float* rows = out + (size_t)blockIdx.x * T * n_mels;
+    logmel_ex_frames<NC>(wav + (size_t)blockIdx.x * n_samples, n_samples, rows, 0, T, hop, n_mels, 2, 0.f, 0.f, g_tw, g_win, g_melw,
+                         g_band, nnz);
+    __syncthreads();                                             // orders the waves' stores of the power rows before the reads below
+    if ((int)threadIdx.x < n_mels) pcen_walk(p, rows + threadIdx.x, T, n_mels);
+}
+
+__global__ __launch_bounds__(256) void pcen_local_kernel(PcenParams p, const float* __restrict__ e, float* __restrict__ local,
+                                                         int T, int F, int chunk, int n_chunks) {
+    const int g = blockIdx.x * 256 + threadIdx.x;                // (chunk, band) = (g / F, g % F)
+    if (g >= (n_chunks - 1) * F) return;                         // the last chunk's end state is never read
+    const int c = g / F, band = g - c * F;
+    const float* col = e + (size_t)c * chunk * F + band;         // a full chunk: (c + 1) chunk < T
+    float M = 0.f;
+    pcen_run<false>(p, 0.f, col, chunk, F, M);
+    local[g] = M;
+}
+
+__global__ __launch_bounds__(FRONTEND_MAX_MELS) void pcen_carry_kernel(PcenParams p, const float* __restrict__ e,
+                                                                       const float* __restrict__ local, float* __restrict__ carry,
+                                                                       int F, int n_chunks, float a_chunk) {
+    const int band = threadIdx.x;
+    if (band >= F) return;
+    float M = pcen_scale(p, e[band]);
+    carry[band] = M;
+    int c = 0;
+    constexpr int AHEAD = 32;                                    // the loads do not depend on the chain: 32 in flight at a time
+    for (; c + AHEAD < n_chunks; c += AHEAD) {
+        float l[AHEAD];
+#pragma unroll
+        for (int u = 0; u < AHEAD; ++u) l[u] = local[(size_t)(c + u) * F + band];
+#pragma unroll
+        for (int u = 0; u < AHEAD; ++u) {
+            M = fmaf(a_chunk, M, l[u]);
+            carry[(size_t)(c + u + 1) * F + band] = M;
+        }
+    }
+    for (; c + 1 < n_chunks; ++c) {
+        M = fmaf(a_chunk, M, local[(size_t)c * F + band]);
+        carry[(size_t)(c + 1) * F + band] = M;
+    }
+}
+
+__global__ __launch_bounds__(256) void pcen_apply_stream_kernel(PcenParams p, float* __restrict__ e, const float* __restrict__ carry,
+                                                                int T, int F, int chunk, int n_chunks) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_chunks * F) return;
+    const int c = g / F, band = g - c * F;
+    const int f0 = c * chunk, len = min(chunk, T - f0);
+    float* col = e + (size_t)f0 * F + band;
+    float M = carry[g];                                          // chunk 0: E[0], the clip form's start
+    pcen_run<true>(p, pcen_floor(p), col, len, F, M);
+}
+
+void pcen_check(const PcenCfg& c) {
+    auto fail = [](const char* field, const char* rule, double got) {
+        throw std::runtime_error(std::string("pcen config: ") + field + " " + rule + " (got " + std::to_string(got) + ")");
+    };
+    if (!(c.s > 0.0 && c.s <= 1.0)) fail("s", "must satisfy 0 < s <= 1", c.s);
+    if (!(c.alpha >= 0.0 && c.alpha <= 1.0)) fail("alpha", "must lie in [0, 1]", c.alpha);
+    if (!(c.delta >= 0.0 && std::isfinite(c.delta))) fail("delta", "must be finite and not negative", c.delta);
+    if (!(c.r > 0.0 && c.r <= 1.0)) fail("r", "must satisfy 0 < r <= 1", c.r);
+    if (!(c.eps > 0.0 && std::isfinite(c.eps))) fail("eps", "must be finite and positive", c.eps);
+    if (!(c.input_scale > 0.0 && std::isfinite(c.input_scale))) fail("input_scale", "must be finite and positive", c.input_scale);
+    // the kernels compute in fp32: the rounded values must stay inside the domain too
+    const PcenParams p = pcen_params(c);
+    if (!(p.s > 0.f)) fail("s", "underflows fp32", c.s);
+    if (!(p.r > 0.f)) fail("r", "underflows fp32", c.r);
+    if (!(p.eps > 0.f)) fail("eps", "underflows fp32", c.eps);
+    if (!(p.input_scale > 0.f && std::isfinite(p.input_scale))) fail("input_scale", "leaves the fp32 range", c.input_scale);
+    if (!std::isfinite(p.delta)) fail("delta", "leaves the fp32 range", c.delta);
+}
+
+PcenParams pcen_params(const PcenCfg& c) {
+    return PcenParams{(float)c.s, (float)c.alpha, (float)c.delta, (float)c.r, (float)c.eps, (float)c.input_scale};
+}
+
+double pcen_smoothing(double time_constant_s, int sr, int hop) {
+    if (!(time_constant_s > 0.0 && std::isfinite(time_constant_s))) throw std::runtime_error("pcen smoothing: time_constant_s must be finite and positive");
+    if (sr <= 0) throw std::runtime_error("pcen smoothing: sr must be positive");
+    if (hop < 1) throw std::runtime_error("pcen smoothing: hop must be at least 1");
+    const double tf = time_constant_s * (double)sr / (double)hop, tf2 = tf * tf;
+    return (std::sqrt(1.0 + 4.0 * tf2) - 1.0) / (2.0 * tf2);
+}
+
+// chunk = ceil(sqrt(T)) / 4 rounded up to 64 frames, at least 64.  A frame of the apply pass is two powf (some hundreds
+// of cycles), a chunk of the carry pass one dependent fma and a store (tens): the quarter keeps the two serial chains,
+// `chunk` frames per thread and ceil(T / chunk) <= 4 sqrt(T) chunks in the carry pass's one workgroup, of comparable
+// length, and short chunks put more threads on the chip (600 s at hop 160: 938 chunks of 64 frames; 64 up to 65 536 frames).
+// A function of T alone: the chunking, and with it the bits, is the same on every device.
+void pcen_stream_plan(int64_t n_frames, int* chunk, int* n_chunks) {
+    CMOOP_REQUIRE(n_frames >= 1 && n_frames <= 0x7fffffff, "pcen stream plan: 1 <= n_frames < 2^31");
+    int64_t root = (int64_t)std::sqrt((double)n_frames);
+    while (root * root < n_frames) ++root;
+    while (root > 1 && (root - 1) * (root - 1) >= n_frames) --root;
+    const int64_t ch = std::max<int64_t>(PCEN_MIN_CHUNK, cdiv64(root, 4 * PCEN_MIN_CHUNK) * PCEN_MIN_CHUNK);
+    if (chunk) *chunk = (int)ch;
+    if (n_chunks) *n_chunks = (int)cdiv64(n_frames, ch);
+}
+
+static void pcen_shape_check(const char* who, int64_t n, int T, int F) {
+    const std::string w(who);
+    CMOOP_REQUIRE(F >= 1 && F <= FRONTEND_MAX_MELS, w + ": F must lie in 1..128 (got " + std::to_string(F) + ")");
+    CMOOP_REQUIRE(T >= 1, w + ": T must be at least 1 (got " + std::to_string(T) + ")");
+    CMOOP_REQUIRE(n >= 0 && n * (int64_t)T * F <= 0x7fffffffll - 256, w + ": n * T * F must stay below 2^31");
+}
+
+void launch_pcen_apply(const PcenParams& p, float* e, int64_t n, int T, int F, hipStream_t s) {
+    pcen_shape_check("pcen_apply", n, T, F);
+    if (n == 0) return;
+    CMOOP_REQUIRE(e != nullptr, "pcen_apply: NULL buffer");
+    const int cols = (int)(n * F);
+    hipLaunchKernelGGL(pcen_apply_kernel, dim3((unsigned)cdiv(cols, 256)), dim3(256), 0, s, p, e, cols, T, F);
+    CMOOP_HIP(hipGetLastError());
+}
+
+template <int NC>
+static void launch_logmel_pcen_nc(const float* wav, int64_t n_clips, int n_samples, float* out, int T, const FrontendTables* t,
+                                  const PcenParams& p, hipStream_t s) {
+    const FrontendCfg& c = t->cfg;
+    hipLaunchKernelGGL(logmel_pcen_kernel<NC>, dim3((unsigned)n_clips), dim3(256), 0, s, wav, n_samples, out, T, c.hop, c.n_mels, p,
+                       t->tw, t->win, t->melw, t->meltask, t->nnz);
+}
+
+void launch_logmel_pcen(const float* wav, int64_t n_clips, int n_samples, float* out, const FrontendTables* t, const PcenParams& p,
+                        hipStream_t s) {
+    const FrontendCfg& c = t->cfg;
+    CMOOP_REQUIRE(c.scale == 2 && t->general, "logmel_pcen: the front end config must have scale 2 (power)");
+    const int T = frontend_frames(c, n_samples);
+    CMOOP_REQUIRE(n_clips >= 0 && n_clips <= 0x7fffffff && (int64_t)T * c.n_mels <= 0x7fffffff, "front end: clip count / clip length out of range");
+    if (n_clips == 0) return;
+    CMOOP_REQUIRE(wav && out, "front end: NULL buffer");
+    if (c.n_fft == 256) launch_logmel_pcen_nc<128>(wav, n_clips, n_samples, out, T, t, p, s);
+    else if (c.n_fft == 512) launch_logmel_pcen_nc<256>(wav, n_clips, n_samples, out, T, t, p, s);
+    else if (c.n_fft == 1024) launch_logmel_pcen_nc<512>(wav, n_clips, n_samples, out, T, t, p, s);
+    else launch_logmel_pcen_nc<1024>(wav, n_clips, n_samples, out, T, t, p, s);
+    CMOOP_HIP(hipGetLastError());
+}
+
+size_t pcen_stream_workspace_floats(int T, int F) {
+    int chunk = 0, n_chunks = 0;
+    pcen_stream_plan(T, &chunk, &n_chunks);
+    return (size_t)2 * n_chunks * F;                             // local | carry, each [n_chunks][F]
+}
+
+void launch_pcen_stream(const PcenParams& p, float* e, int T, int F, float* ws, hipStream_t s) {
+    pcen_shape_check("pcen_stream", 1, T, F);
+    CMOOP_REQUIRE(e && ws, "pcen_stream: NULL buffer");
+    int chunk = 0, n_chunks = 0;
+    pcen_stream_plan(T, &chunk, &n_chunks);
+    float* local = ws;
+    float* carry = ws + (size_t)n_chunks * F;
+    const float a_chunk = (float)std::pow(1.0 - (double)p.s, (double)chunk);
+    if (n_chunks > 1)
+        hipLaunchKernelGGL(pcen_local_kernel, dim3((unsigned)cdiv((n_chunks - 1) * F, 256)), dim3(256), 0, s, p, e, local, T, F, chunk,
+                           n_chunks);
+    hipLaunchKernelGGL(pcen_carry_kernel, dim3(1), dim3(FRONTEND_MAX_MELS), 0, s, p, e, local, carry, F, n_chunks, a_chunk);
+    hipLaunchKernelGGL(pcen_apply_stream_kernel, dim3((unsigned)cdiv(n_chunks * F, 256)), dim3(256), 0, s, p, e, carry, T, F, chunk,
+                       n_chunks);
     CMOOP_HIP(hipGetLastError());
 }
 

@@ -318,7 +318,7 @@ constexpr int FRONTEND_MAX_MELS = 128;
 struct FrontendCfg {
     int sr = 16000, n_fft = 512, win = 400, hop = 160, n_mels = 40;
     float fmin = 20.f, fmax = 7600.f, log_eps = 1e-6f;
-    int scale = 0;             // 0: log(mel + log_eps) ; 1: dB, 10 log10(max(db_amin, mel)) - 10 log10(max(db_amin, ref))
+    int scale = 0;             // 0: log(mel + log_eps) ; 1: dB, 10 log10(max(db_amin, mel)) - 10 log10(max(db_amin, ref)) ; 2: mel power
     int db_ref_max = 0;        // dB reference: 0 -> 1.0, 1 -> the clip's own largest mel power
     float db_amin = 1e-10f, top_db = 80.f;   // top_db >= 0: values below (clip maximum - top_db) are raised to it
 };
@@ -343,6 +343,32 @@ void launch_logmel(const float* wav, int64_t n_clips, int n_samples, float* out,
 // the clip reference / top_db floor (un-referenced 10 log10(max(db_amin, mel)))
 int frontend_stream_run(int T, int compute_units);
 void launch_logmel_stream(const float* wav, int64_t n_samples, float* out, const FrontendTables* t, int compute_units, hipStream_t s);
+// Per-channel energy normalisation of mel power, per band over time (E = input_scale P):
+//   M[t] = M[t-1] + s (E[t] - M[t-1]), M[-1] = E[0];  out[t] = (E[t] / (eps + M[t])^alpha + delta)^r - delta^r
+struct PcenCfg {
+    double s = 0.025, alpha = 0.98, delta = 2.0, r = 0.5, eps = 1e-6, input_scale = 1.0;
+};
+struct PcenParams {            // the fp32 values the kernels compute with
+    float s, alpha, delta, r, eps, input_scale;
+};
+// host-only: throws with a message naming the offending field (0 < s <= 1, 0 <= alpha <= 1, delta >= 0, 0 < r <= 1, eps > 0,
+// input_scale > 0, everything finite)
+void pcen_check(const PcenCfg& c);
+PcenParams pcen_params(const PcenCfg& c);
+// host-only: the smoothing coefficient of a time constant, s = (sqrt(1 + 4 Tf^2) - 1) / (2 Tf^2), Tf = time_constant_s sr / hop
+double pcen_smoothing(double time_constant_s, int sr, int hop);
+// host-only: frames per chunk (a function of n_frames alone, at least PCEN_MIN_CHUNK) and chunks of the stream form
+constexpr int PCEN_MIN_CHUNK = 64;
+void pcen_stream_plan(int64_t n_frames, int* chunk, int* n_chunks);
+// clip form, in place on e [n][T][F]: one thread per (clip, band) walks the frames
+void launch_pcen_apply(const PcenParams& p, float* e, int64_t n, int T, int F, hipStream_t s);
+// mel power of every clip (tables of a scale-2 config) and its PCEN in ONE launch; the bits of launch_logmel + launch_pcen_apply
+void launch_logmel_pcen(const float* wav, int64_t n_clips, int n_samples, float* out, const FrontendTables* t, const PcenParams& p,
+                        hipStream_t s);
+// stream form, in place on e [T][F] of ONE recording: local pass, carry pass, apply pass (three launches).
+// ws: pcen_stream_workspace_floats(T, F) floats; a_chunk = (1 - s)^chunk in double with the fp32 s.
+size_t pcen_stream_workspace_floats(int T, int F);
+void launch_pcen_stream(const PcenParams& p, float* e, int T, int F, float* ws, hipStream_t s);
 void launch_mfcc(const float* X, float* Y, int64_t rows, int n_mels, int n_mfcc, hipStream_t s);   // DCT-II ortho along the mel axis
 void launch_standardize(float* X, const double* mean, const double* scale, int64_t rows, int C, hipStream_t s);
 void colstats_finalize_f64(const float* P, int blocks, int64_t M, int C, double* mean, double* scale, hipStream_t s);

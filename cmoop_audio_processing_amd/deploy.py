@@ -8,7 +8,12 @@ chip) followed by ``NetSession.predict_stream`` (overlapping windows of T frames
 pass; the frames two windows share are convolved again -- there is no streaming convolution cache).
 
 Train / serve difference to know about: a training clip is centre-padded, so its first and last ``n_fft / (2 hop)``
-frames see zeros where a window inside a recording sees real audio.
+frames see zeros where a window inside a recording sees real audio.  With a PCEN front end there is a second one: a
+training clip starts its smoother at its own first frame (``M[-1] = E[0]``), a window inside a recording inherits the
+state the recording has built up since ITS first frame.  The smoother forgets with a time constant of ``1 / s`` frames
+(40 at the default s = 0.025), which is not short beside a 101-frame clip: the first frames of a training patch are
+normalised by a younger smoother than the same audio gets inside a stream.  There is no per-window reset in
+``predict_stream``; train on clips cut with some lead-in, or use a larger ``s``, when that matters.
 
 ``smooth_posteriors`` and ``detect_events`` are the usual host-side read-out of the window posteriors (float64 numpy).
 """
@@ -21,11 +26,13 @@ import numpy as np
 
 from . import genes as G
 from .evaluator import EvalConfig
-from .frontend import FrontendConfig, log_mel_stream
+from .frontend import FrontendConfig, PcenConfig, log_mel_stream
 
 _OBJECTIVE_KEYS = ("acc", "size_mb", "fpr", "epochs_run")
 _FE_INT = ("sr", "n_fft", "win", "hop", "n_mels")
 _FE_FLOAT = ("fmin", "fmax", "log_eps", "db_amin", "top_db")
+_FE_SCALES = ("log", "db", "power", "pcen")                 # "frontend_scale" holds the index; written for the last two only
+_PCEN_FIELDS = ("s", "alpha", "delta", "r", "eps", "input_scale")
 
 
 @dataclasses.dataclass
@@ -72,7 +79,13 @@ class TrainedModel:
         return out
 
     def save(self, path) -> None:
-        """One ``.npz`` (numeric arrays only, no pickle), written to exactly ``path``."""
+        """One ``.npz`` (numeric arrays only, no pickle), written to exactly ``path``.
+
+        Front end keys: ``frontend_int`` (sr, n_fft, win, hop, n_mels, 1 for the dB scale else 0, db_ref_max) and
+        ``frontend_float`` as ever; ``frontend_scale`` (index into log / db / power / pcen) only for a power or PCEN
+        front end, whose ``frontend_int[5]`` is 0; ``frontend_pcen`` (s, alpha, delta, r, eps, input_scale) only when
+        the front end carries a ``PcenConfig``.  A model without a front end, or with a log or dB one, writes the keys
+        it always wrote."""
         d = {"gene": np.asarray(self.gene, np.int32),
              "meta": np.asarray([G.VARIANT_NAMES[self.variant], self.classes, self.T, self.F, self.seed], np.int64),
              "params": self.params,
@@ -82,6 +95,12 @@ class TrainedModel:
             d["frontend_int"] = np.asarray([getattr(fe, k) for k in _FE_INT] + [int(fe.scale == "db"), int(bool(fe.db_ref_max))],
                                            np.int64)
             d["frontend_float"] = np.asarray([getattr(fe, k) for k in _FE_FLOAT], np.float64)
+            if fe.scale not in _FE_SCALES:
+                raise ValueError(f"front end scale {fe.scale!r} cannot be saved")
+            if fe.scale in ("power", "pcen"):
+                d["frontend_scale"] = np.asarray([_FE_SCALES.index(fe.scale)], np.int64)
+            if fe.pcen is not None:
+                d["frontend_pcen"] = np.asarray([getattr(fe.pcen, k) for k in _PCEN_FIELDS], np.float64)
         if self.mean is not None:
             d["mean"], d["scale"] = self.mean, self.scale
         with open(path, "wb") as f:
@@ -95,8 +114,14 @@ class TrainedModel:
             fe = None
             if "frontend_int" in z.files:
                 fi, ff = [int(v) for v in z["frontend_int"]], [float(v) for v in z["frontend_float"]]
-                fe = FrontendConfig(**dict(zip(_FE_INT, fi[:5])), scale="db" if fi[5] else "log", db_ref_max=bool(fi[6]),
-                                    **dict(zip(_FE_FLOAT, ff)))
+                scale = "db" if fi[5] else "log"
+                if "frontend_scale" in z.files:
+                    scale = _FE_SCALES[int(z["frontend_scale"][0])]
+                pcen = None
+                if "frontend_pcen" in z.files:
+                    pcen = PcenConfig(**dict(zip(_PCEN_FIELDS, (float(v) for v in z["frontend_pcen"]))))
+                fe = FrontendConfig(**dict(zip(_FE_INT, fi[:5])), scale=scale, db_ref_max=bool(fi[6]),
+                                    **dict(zip(_FE_FLOAT, ff)), pcen=pcen)
             mean = z["mean"].copy() if "mean" in z.files else None
             scale = z["scale"].copy() if "scale" in z.files else None
             return cls(gene=tuple(int(v) for v in z["gene"]), variant="AB"[variant], classes=classes, T=T, F=F, seed=seed,
@@ -121,7 +146,10 @@ class TrainedModel:
 
 
 class StreamScorer:
-    """``score(recording)`` = ``log_mel_stream`` with the model's front end, then ``predict_stream`` every ``hop_frames``."""
+    """``score(recording)`` = ``log_mel_stream`` with the model's front end, then ``predict_stream`` every ``hop_frames``.
+
+    A dB front end hands its config to ``predict_stream`` for the per-window reference and floor.  A PCEN front end
+    does not: ``log_mel_stream`` has normalised the recording once, windows are plain cuts of it."""
 
     def __init__(self, model: TrainedModel, hop_frames: int, config: Optional[EvalConfig] = None):
         if int(hop_frames) < 1:

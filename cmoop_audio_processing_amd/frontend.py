@@ -8,13 +8,21 @@ sa_nsga_penalty.py:58); the north-star adds the extraction beneath that loader:
 over the N*T rows) including the per-script quirks Q1/Q2 of SURVEY §8a.
 
 ``FrontendConfig`` names any other geometry the library serves (n_fft 256-2048,
-up to 128 mel bands, log or dB scale); ``log_mel`` / ``mfcc`` without a config
-are the fixed geometry above, unchanged.
+up to 128 mel bands; log, dB, linear power or PCEN scale); ``log_mel`` / ``mfcc``
+without a config are the fixed geometry above, unchanged.
+
+PCEN (per-channel energy normalisation, ``PcenConfig``) divides every band's mel power by a
+causal first-order smoothing of itself: the recording level and the stationary background
+leave the features.  ``log_mel`` normalises each clip from its own first frame in the launch
+that makes the power, ``log_mel_stream`` normalises ONE recording once (three more launches),
+``pcen`` does either on a power tensor; ``pcen_reference`` / ``pcen_scan_reference`` are the
+host restatements the tests hold the kernels to.
 """
 from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+from typing import Optional
 
 import numpy as np
 
@@ -23,7 +31,8 @@ from . import _lib
 HOP, N_MELS = 160, 40
 MFCC_MAX_MELS = 64      # cmoop_mfcc's DCT kernel holds at most a 64 x 64 basis
 
-SCALE_LOG, SCALE_DB = 0, 1
+SCALE_LOG, SCALE_DB, SCALE_POWER = 0, 1, 2
+_SCALE_CODES = {"log": SCALE_LOG, "db": SCALE_DB, "power": SCALE_POWER, "pcen": SCALE_POWER}   # PCEN runs on the power scale
 
 
 class FrontendConfigStruct(C.Structure):
@@ -32,15 +41,98 @@ class FrontendConfigStruct(C.Structure):
         [(n, C.c_float) for n in ("fmin", "fmax", "log_eps", "db_amin", "top_db")]
 
 
+class PcenStruct(C.Structure):
+    """cmoop_pcen (include/cmoop.h), 48 bytes."""
+    _fields_ = [(n, C.c_double) for n in ("s", "alpha", "delta", "r", "eps", "input_scale")]
+
+
+@dataclasses.dataclass(frozen=True)
+class PcenConfig:
+    """Per-channel energy normalisation of mel power; mirrors ``cmoop_pcen``.
+
+    For one band with mel power ``P[t]`` and ``E[t] = input_scale * P[t]``::
+
+        M[-1] = E[0];   M[t] = M[t-1] + s * (E[t] - M[t-1])
+        out[t] = (E[t] / (eps + M[t]) ** alpha + delta) ** r - delta ** r
+
+    Domain, all finite: 0 < s <= 1, 0 <= alpha <= 1, delta >= 0, 0 < r <= 1, eps > 0, input_scale > 0.  The default is
+    ``cmoop_pcen_default``: s 0.025, alpha 0.98, delta 2, r 0.5, eps 1e-6, input_scale 1 (the values of Wang et al. 2017,
+    "Trainable frontend for robust and far-field keyword spotting"; s 0.025 is a 0.4 s time constant at a 10 ms hop).
+
+    Presets are BUILD-DEFINED, as ``FrontendConfig.preset("birdclef_128")`` is: the reference ships pre-extracted
+    features and no PCEN recipe, so these are common published settings, not the reference's.
+
+    "speech"      -- the default above.
+    "bioacoustic" -- a 60 ms time constant at the ``birdclef_128`` frame rate (32 kHz, hop 512: s = 0.2335), alpha 0.8,
+                     delta 10, r 0.25, eps 1e-6, input_scale 1: the short smoother, weaker gain control and stronger
+                     compression that Lostanlen et al. 2019 ("Per-channel energy normalization: why and how")
+                     recommend for bird calls over far-field background.
+    """
+    s: float = 0.025
+    alpha: float = 0.98
+    delta: float = 2.0
+    r: float = 0.5
+    eps: float = 1e-6
+    input_scale: float = 1.0
+
+    @classmethod
+    def preset(cls, name: str = "speech") -> "PcenConfig":
+        if name == "speech":
+            return cls()
+        if name == "bioacoustic":
+            return cls.from_time_constant(0.06, 32000, 512, alpha=0.8, delta=10.0, r=0.25)
+        raise ValueError(f"unknown PCEN preset {name!r} (known: 'speech', 'bioacoustic')")
+
+    @classmethod
+    def from_time_constant(cls, time_constant_s: float, sr: int, hop: int, **kw) -> "PcenConfig":
+        """``s`` from the smoother's time constant: ``Tf = time_constant_s * sr / hop`` frames,
+        ``s = (sqrt(1 + 4 Tf^2) - 1) / (2 Tf^2)`` (host only); the other fields from ``kw``."""
+        if "s" in kw:
+            raise ValueError("from_time_constant computes s; do not pass it")
+        s = C.c_double()
+        L = _lib.lib()
+        if L.cmoop_pcen_smoothing(C.c_double(float(time_constant_s)), C.c_int32(int(sr)), C.c_int32(int(hop)), C.byref(s)) != 0:
+            raise ValueError(L.cmoop_last_error().decode("utf-8", "replace"))
+        return cls(s=float(s.value), **kw)
+
+    def _struct(self) -> PcenStruct:
+        return PcenStruct(*(float(getattr(self, f.name)) for f in dataclasses.fields(self)))
+
+    def check(self) -> "PcenConfig":
+        """Raise ValueError naming the offending field when a value is outside the domain (host only)."""
+        st = self._struct()
+        L = _lib.lib()
+        if L.cmoop_pcen_check(C.byref(st)) != 0:
+            raise ValueError(L.cmoop_last_error().decode("utf-8", "replace"))
+        return self
+
+
+def default_pcen_config() -> PcenConfig:
+    """cmoop_pcen_default as a PcenConfig (equals PcenConfig())."""
+    st = PcenStruct()
+    _lib.check(_lib.lib().cmoop_pcen_default(C.byref(st)))
+    return PcenConfig(s=st.s, alpha=st.alpha, delta=st.delta, r=st.r, eps=st.eps, input_scale=st.input_scale)
+
+
+def pcen_stream_plan(n_frames: int):
+    """(chunk, n_chunks) of the stream form for a recording of n_frames frames (host only): chunk depends on n_frames
+    alone, is a multiple of 64 and at least 64; n_chunks = ceil(n_frames / chunk)."""
+    chunk, n_chunks = C.c_int32(), C.c_int32()
+    _lib.check(_lib.lib().cmoop_pcen_stream_plan(C.c_int64(int(n_frames)), C.byref(chunk), C.byref(n_chunks)))
+    return int(chunk.value), int(n_chunks.value)
+
+
 @dataclasses.dataclass(frozen=True)
 class FrontendConfig:
     """Geometry and output scale of the front end; mirrors ``cmoop_frontend_config``.
 
     Domain: n_fft in {256, 512, 1024, 2048}, 1 <= win <= n_fft, hop >= 1, 1 <= n_mels <= 128,
-    0 <= fmin < fmax <= sr/2.  ``scale`` is "log" (``log(mel + log_eps)``) or "db"
+    0 <= fmin < fmax <= sr/2.  ``scale`` is "log" (``log(mel + log_eps)``), "db"
     (``10 log10(max(db_amin, mel)) - 10 log10(max(db_amin, ref))`` with ref = 1.0, or the clip's own largest mel
     power when ``db_ref_max``; then values more than ``top_db`` below the clip's maximum are raised to that floor,
-    ``top_db < 0`` turns the floor off).  The default is the build-defined GSC geometry of ``log_mel(wav)``.
+    ``top_db < 0`` turns the floor off), "power" (the linear mel power) or "pcen" (the mel power normalised per band
+    by ``pcen``, see ``PcenConfig``; ``pcen=None`` means ``PcenConfig()``; the field is ignored on the other scales).
+    The default is the build-defined GSC geometry of ``log_mel(wav)``.
     """
     sr: int = 16000
     n_fft: int = 512
@@ -54,6 +146,7 @@ class FrontendConfig:
     db_ref_max: bool = False
     db_amin: float = 1e-10
     top_db: float = 80.0
+    pcen: Optional[PcenConfig] = None
 
     @classmethod
     def preset(cls, name: str = "gsc") -> "FrontendConfig":
@@ -74,10 +167,12 @@ class FrontendConfig:
         raise ValueError(f"unknown front end preset {name!r} (known: 'gsc', 'birdclef_128')")
 
     def _struct(self) -> FrontendConfigStruct:
-        if self.scale not in ("log", "db"):
-            raise ValueError("front end config: scale must be 'log' or 'db'")
+        if self.scale not in _SCALE_CODES:
+            raise ValueError("front end config: scale must be 'log', 'db', 'power' or 'pcen'")
+        if self.pcen is not None and not isinstance(self.pcen, PcenConfig):
+            raise ValueError("front end config: pcen must be a PcenConfig or None")
         return FrontendConfigStruct(int(self.sr), int(self.n_fft), int(self.win), int(self.hop), int(self.n_mels),
-                                    SCALE_DB if self.scale == "db" else SCALE_LOG, int(bool(self.db_ref_max)),
+                                    _SCALE_CODES[self.scale], int(bool(self.db_ref_max)),
                                     float(self.fmin), float(self.fmax), float(self.log_eps), float(self.db_amin),
                                     float(self.top_db))
 
@@ -87,7 +182,13 @@ class FrontendConfig:
         L = _lib.lib()
         if L.cmoop_frontend_check(C.byref(st)) != 0:
             raise ValueError(L.cmoop_last_error().decode("utf-8", "replace"))
+        if self.scale == "pcen":
+            self.pcen_config().check()
         return self
+
+    def pcen_config(self) -> PcenConfig:
+        """The PCEN parameters the "pcen" scale runs with: the ``pcen`` field, or ``PcenConfig()`` when it is None."""
+        return self.pcen if self.pcen is not None else PcenConfig()
 
     def frames(self, n_samples: int) -> int:
         """T = 1 + n_samples // hop (host only)."""
@@ -108,7 +209,8 @@ def default_frontend_config() -> FrontendConfig:
     st = FrontendConfigStruct()
     _lib.check(_lib.lib().cmoop_frontend_config_default(C.byref(st)))
     return FrontendConfig(sr=st.sr, n_fft=st.n_fft, win=st.win, hop=st.hop, n_mels=st.n_mels, fmin=st.fmin, fmax=st.fmax,
-                          log_eps=st.log_eps, scale="db" if st.scale == SCALE_DB else "log", db_ref_max=bool(st.db_ref_max),
+                          log_eps=st.log_eps, scale={SCALE_DB: "db", SCALE_POWER: "power"}.get(st.scale, "log"),
+                          db_ref_max=bool(st.db_ref_max),
                           db_amin=st.db_amin, top_db=st.top_db)
 
 
@@ -121,7 +223,11 @@ def _log_mel_config(wav, config: FrontendConfig):
     out = torch.empty((n, config.frames(L), config.n_mels), dtype=torch.float32, device=wav.device)
     st = config._struct()
     torch.cuda.synchronize()
-    _lib.check(_lib.lib().cmoop_logmel_ex(C.byref(st), _lib.ptr(wav), C.c_int64(n), C.c_int32(L), _lib.ptr(out)))
+    if config.scale == "pcen":                                    # power and the per-clip recurrence in one launch
+        pc = config.pcen_config()._struct()
+        _lib.check(_lib.lib().cmoop_logmel_pcen(C.byref(st), C.byref(pc), _lib.ptr(wav), C.c_int64(n), C.c_int32(L), _lib.ptr(out)))
+    else:
+        _lib.check(_lib.lib().cmoop_logmel_ex(C.byref(st), _lib.ptr(wav), C.c_int64(n), C.c_int32(L), _lib.ptr(out)))
     return out
 
 
@@ -145,7 +251,11 @@ def log_mel_stream(wav, config: FrontendConfig | None = None):
 
     Log scale: frame for frame the bits of ``log_mel(wav[None], config)[0]``.  dB scale: the UN-REFERENCED
     ``10 log10(max(db_amin, mel))`` -- the reference and the ``top_db`` floor are quantities of a window, applied by
-    ``NetSession.predict_stream`` to each window it cuts from the stream.  ``config=None`` is ``FrontendConfig()``."""
+    ``NetSession.predict_stream`` to each window it cuts from the stream.  Power scale: the clip call's bits.  PCEN scale:
+    the recording is normalised ONCE, from its first frame, by the chunked three-launch scan (``pcen`` on the power
+    stream, bit for bit); windows cut from it need no per-window step, and a recording of at most
+    ``pcen_stream_plan(T)[0]`` frames carries the bits of ``log_mel(wav[None], config)[0]``.
+    ``config=None`` is ``FrontendConfig()``."""
     import torch
     if config is None:
         config = FrontendConfig()
@@ -158,7 +268,96 @@ def log_mel_stream(wav, config: FrontendConfig | None = None):
     out = torch.empty((config.frames(L), config.n_mels), dtype=torch.float32, device=wav.device)
     st = config._struct()
     torch.cuda.synchronize()
-    _lib.check(_lib.lib().cmoop_logmel_stream(C.byref(st), _lib.ptr(wav), C.c_int64(L), _lib.ptr(out)))
+    if config.scale == "pcen":
+        pc = config.pcen_config()._struct()
+        _lib.check(_lib.lib().cmoop_logmel_pcen_stream(C.byref(st), C.byref(pc), _lib.ptr(wav), C.c_int64(L), _lib.ptr(out)))
+    else:
+        _lib.check(_lib.lib().cmoop_logmel_stream(C.byref(st), _lib.ptr(wav), C.c_int64(L), _lib.ptr(out)))
+    return out
+
+
+def _as_pcen_config(config) -> PcenConfig:
+    if config is None:
+        return PcenConfig()
+    if isinstance(config, FrontendConfig):
+        return config.pcen_config()
+    if isinstance(config, PcenConfig):
+        return config
+    raise ValueError("pcen expects a PcenConfig, a FrontendConfig or None")
+
+
+def pcen(power, config=None):
+    """PCEN of a mel-power tensor, returned as a new tensor (the input is only read).
+
+    CUDA float32 ``[n, T, F]``: every clip from its own first frame (``cmoop_pcen_apply``).  CUDA float32 ``[T, F]``: ONE
+    recording, its frames spread over the chip by the chunked scan (``cmoop_pcen_stream``).  ``config`` is a
+    ``PcenConfig``, a ``FrontendConfig`` (its ``pcen_config()``) or None (``PcenConfig()``).  1 <= F <= 128."""
+    import torch
+    pc = _as_pcen_config(config)
+    if not (isinstance(power, torch.Tensor) and power.is_cuda and power.dtype == torch.float32 and power.dim() in (2, 3)):
+        raise ValueError("pcen expects a CUDA float32 tensor [n, T, F] or [T, F]")
+    out = power.contiguous().clone()
+    st = pc._struct()
+    T, F = int(out.shape[-2]), int(out.shape[-1])
+    torch.cuda.synchronize()
+    if out.dim() == 3:
+        _lib.check(_lib.lib().cmoop_pcen_apply(C.byref(st), _lib.ptr(out), C.c_int64(int(out.shape[0])), C.c_int32(T), C.c_int32(F)))
+    else:
+        _lib.check(_lib.lib().cmoop_pcen_stream(C.byref(st), _lib.ptr(out), C.c_int64(T), C.c_int32(F)))
+    return out
+
+
+def pcen_reference(P, config=None, dtype=np.float64) -> np.ndarray:
+    """Host numpy: the serial definition of ``PcenConfig`` along axis -2 of ``P [..., T, F]``, every operation (the six
+    parameters included) in ``dtype``; float32 is the plain restatement of the device arithmetic without its fused update."""
+    pc = _as_pcen_config(config)
+    dt = np.dtype(dtype).type
+    s, alpha, delta, r, eps, gain = (dt(getattr(pc, k)) for k in ("s", "alpha", "delta", "r", "eps", "input_scale"))
+    E = np.asarray(P, dtype=dt) * gain
+    if E.ndim < 2:
+        raise ValueError("pcen_reference expects [..., T, F]")
+    out = np.empty_like(E)
+    M = E[..., 0, :].copy()
+    floor = np.power(np.zeros_like(M) + delta, r)
+    for t in range(E.shape[-2]):
+        e = E[..., t, :]
+        M = M + s * (e - M)
+        out[..., t, :] = np.power(e / np.power(eps + M, alpha) + delta, r) - floor
+    assert out.dtype == np.dtype(dtype)
+    return out
+
+
+def pcen_scan_reference(P, config=None, chunk: int = 64) -> np.ndarray:
+    """Host numpy, float64: the three-pass composition of the stream form on ``P [T, F]`` -- (1) every full chunk's end
+    state from a zero start, (2) ``carry[0] = E[0]``, ``carry[c+1] = (1 - s)^chunk carry[c] + local[c]``, (3) the serial
+    recurrence of each chunk from ``carry[c]``.  Equals ``pcen_reference`` up to rounding for any ``chunk >= 1``."""
+    pc = _as_pcen_config(config)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    E = np.asarray(P, np.float64) * float(pc.input_scale)
+    if E.ndim != 2:
+        raise ValueError("pcen_scan_reference expects [T, F]")
+    T, F = E.shape
+    s, n_chunks = float(pc.s), -(-T // chunk)
+    local = np.zeros((n_chunks, F))
+    for c in range(n_chunks - 1):
+        M = np.zeros(F)
+        for t in range(c * chunk, (c + 1) * chunk):
+            M = M + s * (E[t] - M)
+        local[c] = M
+    carry = np.zeros((n_chunks, F))
+    carry[0] = E[0]
+    a_chunk = (1.0 - s) ** chunk
+    for c in range(n_chunks - 1):
+        carry[c + 1] = a_chunk * carry[c] + local[c]
+    out = np.empty_like(E)
+    floor = np.power(np.zeros(F) + float(pc.delta), float(pc.r))
+    for c in range(n_chunks):
+        M = carry[c]
+        for t in range(c * chunk, min(T, (c + 1) * chunk)):
+            M = M + s * (E[t] - M)
+            out[t] = np.power(E[t] / np.power(float(pc.eps) + M, float(pc.alpha)) + float(pc.delta), float(pc.r)) - floor
     return out
 
 
@@ -168,6 +367,8 @@ def mfcc(wav, n_mfcc: int | None = None, config: FrontendConfig | None = None):
     Without a config: T = 1 + L//160 and n_mfcc defaults to 40.  With one: the config's frames, n_mfcc defaults to its
     n_mels, which the DCT kernel limits to 64."""
     import torch
+    if config is not None and config.scale in ("power", "pcen"):
+        raise ValueError(f"mfcc: the DCT is taken of log-mel (or dB) frames, not of scale {config.scale!r}")
     if config is None:
         n_mels, bound = N_MELS, "1 <= n_mfcc <= 40"
     else:

@@ -10,9 +10,11 @@ offspring, only max(1, int(pop * infill)) of them per generation get a TRUE eval
     python examples/run_sa_nsga_penalty.py --pop 40 --gen 20 --classes 35                                 # BASELINE configs[2]
     python examples/run_sa_nsga_penalty.py --pop 64 --gen 20 --infill 0.334 --memetic --compute bf16      # BASELINE configs[4]
     python examples/run_sa_nsga_penalty.py --audio birdclef --pop 8 --gen 2 --clips 264 --epochs 6       # 128 x 128 dB-mel patches
+    python examples/run_sa_nsga_penalty.py --audio birdclef --scale pcen --pop 8 --gen 2 --clips 264 --epochs 6   # ... PCEN patches
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_sa_nsga_penalty.py --pop 40 --gen 20
 """
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -39,6 +41,10 @@ def main():
     ap.add_argument("--audio", default="gsc", choices=["gsc", "birdclef"],
                     help="gsc: 1 s clips at 16 kHz -> [101, 40] log-mel; birdclef: 65 280-sample clips at 32 kHz -> [128, 128] dB-mel "
                          "patches through FrontendConfig.preset('birdclef_128') (a build-defined recipe, see its docstring)")
+    ap.add_argument("--scale", default="db", choices=["db", "pcen"],
+                    help="--audio birdclef only: db = the preset's dB scale relative to each clip's loudest bin; pcen = the same "
+                         "geometry with per-channel energy normalisation (PcenConfig.preset('bioacoustic')), which takes the "
+                         "recording level and the stationary background out of the patch")
     ap.add_argument("--out", default="sa_nsga_generations.csv")
     ap.add_argument("--trace", default="", help="write a JSON trace: per evaluate call wall-clock, epochs run, hypervolume")
     ap.add_argument("--augment", default="", choices=["", "kws"],
@@ -54,9 +60,13 @@ def main():
     if a.audio == "birdclef":
         # the synthesiser's time axis is in 1/16000 s steps: read at 32 kHz its partials sit at 400-8000 Hz
         cfg = frontend.FrontendConfig.preset("birdclef_128")
+        if a.scale == "pcen":
+            cfg = dataclasses.replace(cfg, scale="pcen", pcen=frontend.PcenConfig.preset("bioacoustic"))
         wav, y = synth_waveforms(a.clips, a.classes, 1234, dev, n_samples=65280)
-        feats = frontend.log_mel(wav, cfg).cpu().numpy()        # [N, 128, 128] dB-mel, unscaled (Q2)
+        feats = frontend.log_mel(wav, cfg).cpu().numpy()        # [N, 128, 128] dB-mel (or PCEN), unscaled (Q2)
     else:
+        if a.scale != "db":
+            ap.error("--scale applies to --audio birdclef")
         wav, y = synth_waveforms(a.clips, a.classes, 1234, dev)
         feats = frontend.log_mel(wav).cpu().numpy()             # [N, 101, 40]; no StandardScaler in this script (Q2)
     del wav

@@ -197,10 +197,11 @@ int cmoop_logmel(const float* wav_dev /* [n_clips][n_samples] */, int64_t n_clip
  * in n_fft); hop >= 1; 1 <= n_mels <= 128; 0 <= fmin < fmax <= sr/2; n_samples >= 1; T = 1 + n_samples / hop frames,
  * centre-padded with zeros.  scale 0: log(mel + log_eps).  scale 1: 10 log10(max(db_amin, mel)) - 10 log10(max(db_amin, ref))
  * with ref = 1.0 (db_ref_max 0) or the clip's own largest mel power (db_ref_max 1), then, when top_db >= 0, every value below
- * (the clip's maximum - top_db) is raised to it.  The default is the geometry of the fixed-geometry call above. */
+ * (the clip's maximum - top_db) is raised to it.  scale 2: the linear mel power itself (a band that holds no FFT bin gives 0);
+ * it is what the PCEN calls below normalise.  The default is the geometry of the fixed-geometry call above. */
 typedef struct cmoop_frontend_config {
     int32_t sr, n_fft, win, hop, n_mels;
-    int32_t scale;       /* 0 log, 1 dB */
+    int32_t scale;       /* 0 log, 1 dB, 2 power */
     int32_t db_ref_max;
     float fmin, fmax, log_eps, db_amin, top_db;
 } cmoop_frontend_config;
@@ -211,7 +212,8 @@ int cmoop_frontend_check(const cmoop_frontend_config* c);
 int cmoop_frontend_frames(const cmoop_frontend_config* c, int32_t n_samples, int32_t* T);
 /* host-only: the dense form [n_mels][1 + n_fft/2] of the sparse mel table the kernel reads (Slaney scale, slaney norm) */
 int cmoop_frontend_mel_basis(const cmoop_frontend_config* c, float* out_host);
-/* Configs with n_fft 512, n_mels <= 64 and the log scale run on the fixed-geometry call's kernel, every other on the general one. */
+/* Configs with n_fft 512, n_mels <= 64 and the log scale run on the fixed-geometry call's kernel, every other (the dB and
+ * power scales always) on the general one. */
 int cmoop_logmel_ex(const cmoop_frontend_config* c, const float* wav_dev /* [n_clips][n_samples] */, int64_t n_clips,
                     int32_t n_samples, float* out_dev /* [n_clips][T][n_mels] */);
 /* average milliseconds of `iters` launches of the call above between two HIP events on the library's stream, after 3 warm-up launches */
@@ -222,6 +224,7 @@ int cmoop_logmel_ex_time(const cmoop_frontend_config* c, const float* wav_dev, i
  *          the 512-point kernel included; only the grid differs).
  * scale 1: the UN-REFERENCED dB value 10 log10(max(db_amin, mel)); db_ref_max / top_db are per-window quantities and are
  *          applied by cmoop_net_predict_stream, not here.
+ * scale 2: the mel power, bit for bit the clip call's.
  * Domain: cmoop_frontend_check's, 1 <= n_samples < 2^31 - 2 n_fft (the kernels index samples in 32 bits), T * n_mels < 2^31. */
 int cmoop_logmel_stream(const cmoop_frontend_config* c, const float* wav_dev /* [n_samples] */, int64_t n_samples, float* out_dev);
 /* as cmoop_logmel_ex_time: average milliseconds of `iters` launches between two HIP events after 3 warm-up launches */
@@ -229,6 +232,45 @@ int cmoop_logmel_stream_time(const cmoop_frontend_config* c, const float* wav_de
                              int32_t iters, double* avg_ms);
 /* host-only: n_windows = 1 + (n_frames - T) / hop_frames; error when n_frames < T or hop_frames < 1 */
 int cmoop_stream_windows(int64_t n_frames, int32_t T, int32_t hop_frames, int64_t* n_windows);
+/* ---- PCEN: per-channel energy normalisation of mel power (north-star addition; the reference has no front end).
+ * For one band of one clip or recording with mel power P[t], t = 0..T-1, and E[t] = input_scale * P[t]:
+ *     M[-1] = E[0];   M[t] = M[t-1] + s * (E[t] - M[t-1])        (so M[0] = E[0])
+ *     out[t] = (E[t] / (eps + M[t])^alpha + delta)^r - delta^r
+ * Domain, all values finite: 0 < s <= 1, 0 <= alpha <= 1, delta >= 0, 0 < r <= 1, eps > 0, input_scale > 0.
+ * The device computes in fp32 with the six values rounded to fp32: the update is fmaf(s, E - M, M), delta^r comes from the
+ * same powf that raises the first term, so an all-zero band gives exactly 0.0f.  One device function holds this arithmetic
+ * for every call below: the clip, stand-alone and stream forms agree bit for bit wherever their carry-in is the same. */
+typedef struct cmoop_pcen {
+    double s, alpha, delta, r, eps, input_scale;
+} cmoop_pcen;
+int cmoop_pcen_default(cmoop_pcen* p); /* s 0.025, alpha 0.98, delta 2, r 0.5, eps 1e-6, input_scale 1 */
+/* host-only: non-zero + a message naming the offending field when a value is outside the domain */
+int cmoop_pcen_check(const cmoop_pcen* p);
+/* host-only: the s of a smoother with time constant time_constant_s: Tf = time_constant_s * sr / hop frames,
+ * s = (sqrt(1 + 4 Tf^2) - 1) / (2 Tf^2) */
+int cmoop_pcen_smoothing(double time_constant_s, int32_t sr, int32_t hop, double* s);
+/* Clip form on a power tensor, in place: every (clip, band) column of e_dev [n][T][F] is normalised from its own first
+ * frame.  1 <= F <= 128, T >= 1, n * T * F < 2^31. */
+int cmoop_pcen_apply(const cmoop_pcen* p, float* e_dev /* [n][T][F], in place */, int64_t n, int32_t T, int32_t F);
+/* Mel power of every clip and its PCEN in ONE launch; c->scale must be 2.  Bit-equal to cmoop_logmel_ex followed by
+ * cmoop_pcen_apply. */
+int cmoop_logmel_pcen(const cmoop_frontend_config* c, const cmoop_pcen* p, const float* wav_dev /* [n_clips][n_samples] */,
+                      int64_t n_clips, int32_t n_samples, float* out_dev /* [n_clips][T][n_mels] */);
+/* host-only: the stream form cuts a recording of n_frames frames into n_chunks = ceil(n_frames / chunk) chunks; chunk is a
+ * function of n_frames alone (never of the device): ceil(sqrt(n_frames)) / 4 rounded up to a multiple of 64, at least 64 */
+int cmoop_pcen_stream_plan(int64_t n_frames, int32_t* chunk, int32_t* n_chunks);
+/* The same recurrence for ONE recording, in place on e_dev [n_frames][F], spread over the chip as three launches on the
+ * library stream: (1) per (chunk, band) the chunk's end state from a zero start, (2) one workgroup, serial over the chunks,
+ * carry[0] = E[0], carry[c+1] = (1-s)^chunk * carry[c] + local[c] with (1-s)^chunk computed in double on the host,
+ * (3) per (chunk, band) the serial recurrence from carry[c].  Chunk 0 starts from E[0]: a recording of at most `chunk` frames
+ * carries the bits of cmoop_pcen_apply (and then needs no launch 1).  1 <= F <= 128, n_frames * F < 2^31. */
+int cmoop_pcen_stream(const cmoop_pcen* p, float* e_dev /* [n_frames][F], in place */, int64_t n_frames, int32_t F);
+/* cmoop_logmel_stream at scale 2 (c->scale must be 2) followed by cmoop_pcen_stream on its output */
+int cmoop_logmel_pcen_stream(const cmoop_frontend_config* c, const cmoop_pcen* p, const float* wav_dev /* [n_samples] */,
+                             int64_t n_samples, float* out_dev /* [T][n_mels] */);
+/* as cmoop_logmel_stream_time, for the four launches of the call above */
+int cmoop_logmel_pcen_stream_time(const cmoop_frontend_config* c, const cmoop_pcen* p, const float* wav_dev, int64_t n_samples,
+                                  float* out_dev, int32_t iters, double* avg_ms);
 /* optional MFCC features: DCT-II, ortho-normalised, along the mel axis of log-mel rows; first n_mfcc coefficients.
  * The reference ships no front end; its comment at ablation_study/sa_nsga_init.py:68 calls the stored features MFCCs. */
 int cmoop_mfcc(const float* logmel_dev /* [rows][n_mels] */, int64_t rows, int32_t n_mels, int32_t n_mfcc,
