@@ -87,6 +87,27 @@ PCEN_PROTOTYPES = {
 }
 
 
+#: prototypes of the per-kernel entry points of the BatchNorm / pooling / loss / optimiser kernels (include/cmoop.h)
+_V, _I32, _I64, _F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+ELEM_PROTOTYPES = {
+    "cmoop_bn_train_fwd": [_V] * 10 + [_I64, _I32, _F64, _F64, _I32, _I32],
+    "cmoop_bn_eval_fwd": [_V] * 8 + [_I64, _I32, _F64, _I32],
+    "cmoop_bn_bwd": [_V] * 9 + [_I64, _I32, _I32, _I32],
+    "cmoop_bn_pool_fwd": [_V] * 5 + [_I32] * 5,
+    "cmoop_bn_pool_bwd": [_V] * 10 + [_I32] * 6,
+    "cmoop_add_relu": [_V, _V, _V, _I64],
+    "cmoop_gap_fwd": [_V, _V, _I32, _I32, _I32],
+    "cmoop_gap_bwd": [_V, _V, _V, _I32, _I32, _I32],
+    "cmoop_softmax_ce": [_V, _V, _V, _I64, _I64, _I32, _I32, _V, _V, _V],
+    "cmoop_softmax_probs": [_V, _V, _I32, _I32],
+    "cmoop_adam": [_V, _V, _V, _V, _I64, _F64, _F64, _F64, _F64],
+    "cmoop_adam_segments": [_V] * 5 + [_I32] + [_V] * 5 + [_F64] * 4,
+    "cmoop_confusion": [_V, _V, _I64, _I32, _I32, _V],
+    "cmoop_colsum_small": [_V, _V, _I32, _I32],
+    "cmoop_dense_dgrad_small": [_V, _V, _V, _I32, _I32, _I32, _V, _F64],
+}
+
+
 def build(verbose: bool = False) -> str:
     """Compile libcmoop_hip.so for gfx950 in-tree (make; hipcc cross-compiles on CPU-only hosts)."""
     jobs = str(min(8, os.cpu_count() or 1))
@@ -125,7 +146,8 @@ def lib():
             if name not in ("cmoop_last_error", "cmoop_config_default"):
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
-        for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(PCEN_PROTOTYPES.items()):
+        for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(PCEN_PROTOTYPES.items()) + \
+                list(ELEM_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         _lib = L
         return L

@@ -1024,6 +1024,170 @@ int cmoop_maxpool_bwd(const float* dy, const uint8_t* arg, const float* y, float
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
+// ---- kernel-level entry points of elem.hip (per-kernel parity tests): each launches what Net::forward / Net::backward /
+//      Net::step_body launch for the operation, in their order and with their argument casts; reduction workspaces live
+//      for the length of the call
+static int reduce_blocks_arg(int32_t blocks, int64_t M, int32_t C) {
+    CMOOP_REQUIRE(M >= 1 && C >= 4 && C % 4 == 0, "M >= 1 and C a multiple of 4 (>= 4)");
+    CMOOP_REQUIRE(blocks >= 0 && blocks <= 4096, "blocks must be 0 (the trainer's count) or 1..4096");
+    return blocks ? blocks : colreduce_blocks(M, C);
+}
+
+int cmoop_bn_train_fwd(const float* x, const float* gamma, const float* beta, float* moving_mean, float* moving_var, float* y,
+                       float* mean, float* invstd, float* scale, float* shift, int64_t M, int32_t C, double eps, double momentum,
+                       int32_t relu, int32_t blocks) {
+    return guard([&] {
+        const int nb = reduce_blocks_arg(blocks, M, C);
+        hipStream_t s = lib_stream();
+        Scratch ws(s);
+        float* P = ws.floats((size_t)nb * 2 * C);
+        launch_colstats(x, P, M, C, nb, s);
+        launch_bn_finalize(P, nb, M, C, gamma, beta, moving_mean, moving_var, mean, invstd, scale, shift, (float)eps,
+                           (float)momentum, (float)(1.0 - momentum), s);
+        launch_scale_shift(x, y, scale, shift, M, C, relu, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_bn_eval_fwd(const float* x, const float* gamma, const float* beta, const float* moving_mean, const float* moving_var,
+                      float* y, float* scale, float* shift, int64_t M, int32_t C, double eps, int32_t relu) {
+    return guard([&] {
+        CMOOP_REQUIRE(M >= 0 && C >= 4 && C % 4 == 0, "bn_eval_fwd: C must be a multiple of 4");
+        hipStream_t s = lib_stream();
+        launch_bn_eval_prepare(gamma, beta, moving_mean, moving_var, scale, shift, C, (float)eps, s);
+        launch_scale_shift(x, y, scale, shift, M, C, relu, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_bn_bwd(const float* dy, const float* x, const float* mean, const float* invstd, const float* gamma, float* dx,
+                 float* dgamma, float* dbeta, float* sums, int64_t M, int32_t C, int32_t mask_x_pos, int32_t blocks) {
+    return guard([&] {
+        const int nb = reduce_blocks_arg(blocks, M, C);
+        hipStream_t s = lib_stream();
+        Scratch ws(s);
+        float* P = ws.floats((size_t)nb * 2 * C + 2 * C);       // the finalised sums sit right after the partials
+        launch_bn_bwd_reduce(dy, x, mean, invstd, P, M, C, nb, s);
+        launch_bn_bwd_apply(dy, x, mean, invstd, gamma, P, nb, dx, dgamma, dbeta, M, C, mask_x_pos, s);
+        if (sums) CMOOP_HIP(hipMemcpyAsync(sums, P + (size_t)nb * 2 * C, (size_t)2 * C * 4, hipMemcpyDeviceToDevice, s));
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_bn_pool_fwd(const float* x, const float* scale, const float* shift, float* y, uint8_t* arg, int32_t B, int32_t H,
+                      int32_t W, int32_t C, int32_t relu) {
+    return guard([&] {
+        hipStream_t s = lib_stream();
+        launch_bn_pool_fwd(x, y, arg, scale, shift, B, H, W, C, relu, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_bn_pool_bwd(const float* g_pooled, const uint8_t* arg, const float* x, const float* mean, const float* invstd,
+                      const float* gamma, float* dx, float* dgamma, float* dbeta, float* sums, int32_t B, int32_t H, int32_t W,
+                      int32_t C, int32_t mask_x_pos, int32_t blocks) {
+    return guard([&] {
+        CMOOP_REQUIRE(B >= 1 && H >= 1 && W >= 1, "bn_pool_bwd: empty tensor");
+        const int nb = reduce_blocks_arg(blocks, (int64_t)B * H * W, C);
+        hipStream_t s = lib_stream();
+        Scratch ws(s);
+        float* P = ws.floats((size_t)nb * 2 * C + 2 * C);
+        launch_bn_pool_bwd_reduce(g_pooled, arg, x, mean, invstd, P, B, H, W, C, nb, s);
+        launch_bn_pool_bwd_apply(g_pooled, arg, x, mean, invstd, gamma, P, nb, dx, dgamma, dbeta, B, H, W, C, mask_x_pos, s);
+        if (sums) CMOOP_HIP(hipMemcpyAsync(sums, P + (size_t)nb * 2 * C, (size_t)2 * C * 4, hipMemcpyDeviceToDevice, s));
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_add_relu(const float* a, const float* b, float* y, int64_t n) {
+    return guard([&] {
+        hipStream_t s = lib_stream();
+        launch_add_relu(a, b, y, n, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_gap_fwd(const float* x, float* y, int32_t B, int32_t HW, int32_t C) {
+    return guard([&] {
+        CMOOP_REQUIRE(B >= 0 && HW >= 1 && C >= 4, "gap_fwd: HW >= 1, C >= 4");
+        hipStream_t s = lib_stream();
+        launch_gap_fwd(x, y, B, HW, C, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_gap_bwd(const float* dy, const float* x, float* dx, int32_t B, int32_t HW, int32_t C) {
+    return guard([&] {
+        CMOOP_REQUIRE(B >= 0 && HW >= 1 && C >= 4 && C % 4 == 0, "gap_bwd: HW >= 1, C a multiple of 4");
+        hipStream_t s = lib_stream();
+        launch_gap_bwd(dy, x, dx, B, HW, C, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_softmax_ce(const float* z, const int32_t* labels, const int32_t* idx, int64_t row0, int64_t n_rows, int32_t B, int32_t C,
+                     float* dz, double* acc, int32_t* preds) {
+    return guard([&] {
+        CMOOP_REQUIRE(B >= 0 && C >= 1 && row0 >= 0, "softmax_ce: B >= 0, C >= 1, row0 >= 0");
+        hipStream_t s = lib_stream();
+        launch_softmax_ce(z, labels, idx, row0, B, C, dz, acc, preds, s, nullptr, n_rows);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_softmax_probs(const float* z, float* p, int32_t B, int32_t C) {
+    return guard([&] {
+        CMOOP_REQUIRE(B >= 0 && C >= 1, "softmax_probs: B >= 0, C >= 1");
+        hipStream_t s = lib_stream();
+        launch_softmax_probs(z, p, B, C, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_adam(float* w, const float* g, float* m, float* v, int64_t n, double alpha, double beta1, double beta2, double eps) {
+    return guard([&] {
+        CMOOP_REQUIRE(n >= 0, "adam: n >= 0");
+        hipStream_t s = lib_stream();
+        launch_adam(w, g, m, v, n, (float)alpha, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_adam_segments(float* w, float* g, float* m, float* v, const float* slab, int32_t count, const int64_t* off,
+                        const int64_t* n, const int32_t* S, const int64_t* stride, const int64_t* slab_off, double alpha,
+                        double beta1, double beta2, double eps) {
+    return guard([&] {
+        CMOOP_REQUIRE(count >= 0 && count <= ADAM_MAX_SEGS, "adam_segments: at most 64 segments");
+        CMOOP_REQUIRE(count == 0 || (off && n && S && stride && slab_off), "adam_segments: NULL segment array");
+        AdamSegTable tab;
+        for (int i = 0; i < count; ++i) {
+            AdamSeg sg;
+            sg.off = off[i]; sg.n = n[i];
+            CMOOP_REQUIRE(S[i] >= 0 && (S[i] == 0 || (slab && stride[i] >= n[i] && slab_off[i] >= 0)),
+                          "adam_segments: a slab segment needs the slab buffer, stride >= n and slab_off >= 0");
+            if (S[i] > 0) { sg.slab = slab + slab_off[i]; sg.stride = stride[i]; sg.S = S[i]; }
+            tab.seg[tab.count++] = sg;
+        }
+        adam_segments_finalize(tab);
+        hipStream_t s = lib_stream();
+        launch_adam_segments(w, g, m, v, tab, (float)alpha, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_confusion(const int32_t* y_true, const int32_t* y_pred, int64_t n, int32_t C, int32_t force_true_zero, int64_t* cm) {
+    return guard([&] {
+        CMOOP_REQUIRE(n >= 0 && C >= 1 && cm, "confusion: n >= 0, C >= 1");
+        hipStream_t s = lib_stream();
+        launch_confusion(y_true, y_pred, n, C, force_true_zero, cm, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_colsum_small(const float* x, float* out, int32_t M, int32_t C) {
+    return guard([&] {
+        CMOOP_REQUIRE(M >= 0 && C >= 1, "colsum_small: M >= 0, C >= 1");
+        hipStream_t s = lib_stream();
+        launch_colsum_small(x, out, M, C, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_dense_dgrad_small(const float* dy, const float* w, float* dx, int32_t M, int32_t N, int32_t K, const float* mask,
+                            double scale) {
+    return guard([&] {
+        CMOOP_REQUIRE(M >= 0 && N >= 0 && K >= 0, "dense_dgrad_small: negative size");
+        hipStream_t s = lib_stream();
+        launch_dense_dgrad_small(dy, w, dx, M, N, K, mask, (float)scale, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
 int cmoop_device_synchronize(void) { return guard([] { CMOOP_HIP(hipDeviceSynchronize()); }); }
 
 }  // extern "C"

@@ -379,6 +379,53 @@ int cmoop_dense_bwd(const float* x_dev, const float* w_dev, const float* dy_dev,
 int cmoop_maxpool_fwd(const float* x_dev, float* y_dev, uint8_t* arg_dev, int32_t B, int32_t H, int32_t W, int32_t C);
 int cmoop_maxpool_bwd(const float* dy_dev, const uint8_t* arg_dev, const float* y_dev, float* dx_dev, int32_t B, int32_t H,
                       int32_t W, int32_t C, int32_t mask_y_pos);
+/* ---- per-kernel entry points of the BatchNorm / pooling / loss / optimiser kernels (parity tests).  Each call launches
+ *      what the trainer launches for the operation, in the trainer's order, on device pointers; reduction workspaces are
+ *      allocated and freed inside the call; hyper-parameters travel as double and are cast to float where the trainer casts.
+ *      blocks: 0 = the trainer's partial count for (M, C); 1..4096 forces that many reduction workgroups.
+ *      BatchNorm over x[M][C] (C % 4 == 0, C <= 1024): batch statistics -> mean / invstd / scale / shift [C] each, moving
+ *      statistics updated in place, y = x scale + shift (optional ReLU) */
+int cmoop_bn_train_fwd(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* moving_mean_dev,
+                       float* moving_var_dev, float* y_dev, float* mean_dev, float* invstd_dev, float* scale_dev, float* shift_dev,
+                       int64_t M, int32_t C, double eps, double momentum, int32_t relu, int32_t blocks);
+int cmoop_bn_eval_fwd(const float* x_dev, const float* gamma_dev, const float* beta_dev, const float* moving_mean_dev,
+                      const float* moving_var_dev, float* y_dev, float* scale_dev, float* shift_dev, int64_t M, int32_t C,
+                      double eps, int32_t relu);
+/* dx (optionally masked by x > 0), dgamma, dbeta; sums_dev (may be NULL): the finalised (sum dy, sum dy xhat) [2][C] */
+int cmoop_bn_bwd(const float* dy_dev, const float* x_dev, const float* mean_dev, const float* invstd_dev, const float* gamma_dev,
+                 float* dx_dev, float* dgamma_dev, float* dbeta_dev, float* sums_dev, int64_t M, int32_t C, int32_t mask_x_pos,
+                 int32_t blocks);
+/* BatchNorm-apply (+ReLU) + MaxPool 2x2 SAME in one pass over x[B,H,W,C], and its backward from the pooled gradient */
+int cmoop_bn_pool_fwd(const float* x_dev, const float* scale_dev, const float* shift_dev, float* y_dev, uint8_t* arg_dev, int32_t B,
+                      int32_t H, int32_t W, int32_t C, int32_t relu);
+int cmoop_bn_pool_bwd(const float* g_pooled_dev, const uint8_t* arg_dev, const float* x_dev, const float* mean_dev,
+                      const float* invstd_dev, const float* gamma_dev, float* dx_dev, float* dgamma_dev, float* dbeta_dev,
+                      float* sums_dev, int32_t B, int32_t H, int32_t W, int32_t C, int32_t mask_x_pos, int32_t blocks);
+/* y = max(a + b, 0) over n floats (n % 4 == 0); global average pooling of x[B][HW][C] and its backward (masked by x > 0) */
+int cmoop_add_relu(const float* a_dev, const float* b_dev, float* y_dev, int64_t n);
+int cmoop_gap_fwd(const float* x_dev, float* y_dev, int32_t B, int32_t HW, int32_t C);
+int cmoop_gap_bwd(const float* dy_dev, const float* x_dev, float* dx_dev, int32_t B, int32_t HW, int32_t C);
+/* softmax + clipped sparse cross-entropy of z[B][C]; row r's label is labels[idx ? idx[row0 + r] : row0 + r], the row index
+ * clamped into [0, n_rows) when n_rows > 0.  dz (may be NULL): d(mean loss)/dz; acc (two 8-byte words: double loss sum,
+ * int64 correct) is ADDED into; preds (may be NULL): the row arg max */
+int cmoop_softmax_ce(const float* z_dev, const int32_t* labels_dev, const int32_t* idx_dev, int64_t row0, int64_t n_rows, int32_t B,
+                     int32_t C, float* dz_dev, double* acc_dev, int32_t* preds_dev);
+int cmoop_softmax_probs(const float* z_dev, float* p_dev, int32_t B, int32_t C);
+/* one Keras-form Adam update of n floats with the step size alpha (the caller's bias-corrected lr) */
+int cmoop_adam(float* w_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t n, double alpha, double beta1, double beta2,
+               double eps);
+/* the fused optimiser launch: `count` (<= 64) segments tiling the arena in order, host arrays; S[i] == 0: plain segment
+ * (gradient read from g); S[i] > 0: g = fixed-order sum of the S[i] slices at slab_dev + slab_off[i] + s stride[i] */
+int cmoop_adam_segments(float* w_dev, float* g_dev, float* m_dev, float* v_dev, const float* slab_dev, int32_t count,
+                        const int64_t* off, const int64_t* n, const int32_t* S, const int64_t* stride, const int64_t* slab_off,
+                        double alpha, double beta1, double beta2, double eps);
+/* cm[C][C] (int64) = confusion matrix of n label pairs (out-of-range labels ignored; force_true_zero: every true label 0) */
+int cmoop_confusion(const int32_t* y_true_dev, const int32_t* y_pred_dev, int64_t n, int32_t C, int32_t force_true_zero,
+                    int64_t* cm_dev);
+/* output-layer helpers: out[C] = column sums of x[M][C]; dx[M][K] = dy[M][N] w[N][K], mask (may be NULL): dx = mask > 0 ? dx scale : 0 */
+int cmoop_colsum_small(const float* x_dev, float* out_dev, int32_t M, int32_t C);
+int cmoop_dense_dgrad_small(const float* dy_dev, const float* w_dev, float* dx_dev, int32_t M, int32_t N, int32_t K,
+                            const float* mask_dev, double scale);
 int cmoop_device_synchronize(void);
 
 #ifdef __cplusplus

@@ -136,7 +136,8 @@ def test_production_conv_shapes_under_the_fp32_accurate_bf16x3_mode():
 
 
 @fp32_only
-@pytest.mark.parametrize("M,N,K,relu", [(64, 512, 512, 1), (64, 256, 512, 1), (37, 64, 128, 1), (64, 10, 64, 0), (64, 35, 64, 0), (256, 512, 512, 1)])
+@pytest.mark.parametrize("M,N,K,relu", [(64, 512, 512, 1), (64, 256, 512, 1), (37, 64, 128, 1), (64, 10, 64, 0), (64, 35, 64, 0), (256, 512, 512, 1),
+                                           (1, 10, 64, 0), (5, 11, 16, 1), (17, 35, 128, 1)])
 def test_dense_head_kernels(M, N, K, relu):
     """dense.hip (MLP head, nsga_penalty.py:306-330): forward, dgrad with the ReLU mask, wgrad, bias gradient; K = 512 walks
     the second trip of the kernels' 16-deep reduction loop per wave (never gradient-checked before)."""
