@@ -46,6 +46,12 @@ class Augment(C.Structure):
         [(n, C.c_double) for n in ("p", "noise_std", "fill")]
 
 
+class Loss(C.Structure):
+    """cmoop_loss (include/cmoop.h), 40 bytes."""
+    _fields_ = [("label_smoothing", C.c_double), ("mixup_alpha", C.c_double), ("mixup_p", C.c_double),
+                ("class_weight", C.c_void_p), ("n_class_weight", C.c_int32), ("reserved", C.c_int32)]
+
+
 #: cmoop_next_fn (include/cmoop.h): int32_t (*)(void* ctx)
 NEXT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
@@ -70,6 +76,25 @@ AUGMENT_PROTOTYPES = {
     "cmoop_net_set_augment": [C.c_void_p, C.c_void_p],
     "cmoop_eval_population_aug": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] +
                                  [C.c_void_p] * 7,
+}
+
+
+#: prototypes of the soft-target training loss entry points (include/cmoop.h); structs travel as void* (C.byref), None is NULL
+LOSS_PROTOTYPES = {
+    "cmoop_loss_default": [C.c_void_p],
+    "cmoop_loss_check": [C.c_void_p, C.c_int32],
+    "cmoop_mixup_table": [C.c_double, C.c_void_p],
+    "cmoop_mixup_draws": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_mixup_batch": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
+                          C.c_void_p],
+    "cmoop_soft_targets": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
+                           C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_softmax_ce_soft": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_net_set_loss": [C.c_void_p, C.c_void_p],
+    "cmoop_net_train_step_targets": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32],
+    "cmoop_net_loss_buffers": [C.c_void_p, C.c_void_p],
+    "cmoop_eval_population_ex": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] +
+                                [C.c_void_p] * 7,
 }
 
 
@@ -147,7 +172,7 @@ def lib():
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
         for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(PCEN_PROTOTYPES.items()) + \
-                list(ELEM_PROTOTYPES.items()):
+                list(ELEM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         _lib = L
         return L

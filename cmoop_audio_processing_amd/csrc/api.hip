@@ -127,6 +127,28 @@ static AugmentCfg to_augment(const cmoop_augment* a) {
     return c;
 }
 
+static_assert(sizeof(cmoop_loss) == 40, "cmoop_loss is part of the ABI");
+static LossCfg to_loss(const cmoop_loss* l) {   // class_weight stays the caller's array
+    CMOOP_REQUIRE(l != nullptr, "loss config is NULL");
+    LossCfg c;
+    c.label_smoothing = l->label_smoothing; c.mixup_alpha = l->mixup_alpha; c.mixup_p = l->mixup_p;
+    c.class_weight = l->class_weight; c.n_class_weight = l->n_class_weight;
+    return c;
+}
+// the lam table of an enabled mixup on the device for one kernel-alone call (null with mixup off)
+static MixupParams scratch_mixup(const LossCfg& c, float* tab_dev, hipStream_t s) {
+    MixupParams m;
+    if (!loss_mixup_on(c)) return m;
+    std::vector<float> tab(MIXUP_TABLE);
+    mixup_table(c.mixup_alpha, tab.data());
+    CMOOP_HIP(hipMemcpyAsync(tab_dev, tab.data(), MIXUP_TABLE * 4, hipMemcpyHostToDevice, s));
+    CMOOP_HIP(hipStreamSynchronize(s));
+    m.on = 1;
+    m.gate_thr = (uint32_t)std::floor(c.mixup_p * 16777216.0);
+    m.tab = tab_dev;
+    return m;
+}
+
 static Dataset to_dataset(const cmoop_dataset* ds) {
     Dataset d;
     d.x_train = ds->x_train; d.y_train = ds->y_train; d.n_train = ds->n_train;
@@ -220,7 +242,8 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 }
 
 // every population call; next == NULL: candidates are taken longest-first from a process-local counter; aug == NULL: no augmentation
-static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_dataset* ds, const int32_t* genes,
+static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_dataset* ds,
+                                const int32_t* genes,
                                 const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
                                 double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
     CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
@@ -233,11 +256,16 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* au
         a = to_augment(aug);
         augment_check(a, d.T, d.F);
     }
+    LossCfg lc;
+    if (loss) {
+        lc = to_loss(loss);
+        loss_check(lc, c.classes);
+    }
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
-    if (next) eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); }, aug ? &a : nullptr);
-    else eval_population(c, d, genes, seeds, n, r.data(), {}, aug ? &a : nullptr);
+    if (next) eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); }, aug ? &a : nullptr, loss ? &lc : nullptr);
+    else eval_population(c, d, genes, seeds, n, r.data(), {}, aug ? &a : nullptr, loss ? &lc : nullptr);
     for (int i = 0; i < n; ++i) {
         if (evaluated) evaluated[i] = r[i].evaluated;
         if (acc) acc[i] = r[i].acc;
@@ -267,8 +295,105 @@ int cmoop_eval_population_pull(const cmoop_config* cfg, const cmoop_dataset* ds,
 int cmoop_eval_population_aug(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_dataset* ds, const int32_t* genes,
                               const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
                               double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
+    return cmoop_eval_population_ex(cfg, aug, nullptr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds,
+                                    evaluated);
+}
+
+int cmoop_eval_population_ex(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_dataset* ds,
+                             const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc,
+                             double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
     return guard([&] {
-        eval_population_abi(cfg, aug, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds, evaluated);
+        eval_population_abi(cfg, aug, loss, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds, evaluated);
+    });
+}
+
+// ---- soft-target training loss ---------------------------------------------------
+int cmoop_loss_default(cmoop_loss* loss) {
+    return guard([&] {
+        CMOOP_REQUIRE(loss != nullptr, "loss config is NULL");
+        const LossCfg c;
+        std::memset(loss, 0, sizeof(*loss));
+        loss->label_smoothing = c.label_smoothing; loss->mixup_alpha = c.mixup_alpha; loss->mixup_p = c.mixup_p;
+    });
+}
+
+int cmoop_loss_check(const cmoop_loss* loss, int32_t classes) {
+    return guard([&] { loss_check(to_loss(loss), classes); });
+}
+
+int cmoop_mixup_table(double alpha, float out[1024]) {
+    return guard([&] {
+        CMOOP_REQUIRE(out != nullptr, "mixup_table: NULL output");
+        mixup_table(alpha, out);
+    });
+}
+
+int cmoop_mixup_draws(const cmoop_loss* loss, uint32_t seed, uint32_t step, int32_t B, int32_t* gate, int32_t* partner, float* lam) {
+    return guard([&] {
+        LossCfg c = to_loss(loss);
+        c.class_weight = nullptr;               // not read here
+        loss_check(c, 1);
+        CMOOP_REQUIRE(B >= 0 && B < (1 << 27) && (B == 0 || (gate && partner && lam)), "mixup_draws: B must be in [0, 2^27), outputs non-NULL");
+        std::vector<float> tab;
+        MixupParams m;
+        if (loss_mixup_on(c)) {
+            tab.resize(MIXUP_TABLE);
+            mixup_table(c.mixup_alpha, tab.data());
+            m.on = 1;
+            m.gate_thr = (uint32_t)std::floor(c.mixup_p * 16777216.0);
+            m.tab = tab.data();
+        }
+        for (int32_t b = 0; b < B; ++b) mixup_row_draws(m, seed, step, (uint32_t)b, (uint32_t)B, gate + b, partner + b, lam + b);
+    });
+}
+
+int cmoop_mixup_batch(const cmoop_loss* loss, const float* x_dev, const int32_t* idx_dev, int64_t row0, int32_t B, int32_t T, int32_t F,
+                      uint32_t seed, uint32_t step, float* out_dev) {
+    return guard([&] {
+        LossCfg c = to_loss(loss);
+        c.class_weight = nullptr;
+        loss_check(c, 1);
+        CMOOP_REQUIRE(B >= 0 && row0 >= 0 && T >= 1 && F >= 1 && (B == 0 || (x_dev && out_dev)), "mixup_batch: bad arguments");
+        hipStream_t s = lib_stream();
+        Scratch m(s);
+        const MixupParams mp = scratch_mixup(c, m.floats(MIXUP_TABLE), s);
+        launch_mixup_gather(x_dev, idx_dev, row0, 0, out_dev, B, T, F, mp, seed, step, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_soft_targets(const cmoop_loss* loss, const int32_t* labels_dev, const int32_t* idx_dev, int64_t row0, int64_t n_rows,
+                       int32_t B, int32_t C, uint32_t seed, uint32_t step, float* t_dev, float* w_dev, int32_t* primary_dev) {
+    return guard([&] {
+        CMOOP_REQUIRE(B >= 0 && C >= 1 && row0 >= 0 && n_rows >= 0, "soft_targets: B >= 0, C >= 1, row0 >= 0, n_rows >= 0");
+        const LossCfg c = to_loss(loss);
+        loss_check(c, C);
+        CMOOP_REQUIRE(B == 0 || (labels_dev && t_dev && w_dev && primary_dev), "soft_targets: NULL buffer");
+        hipStream_t s = lib_stream();
+        Scratch m(s);
+        const MixupParams mp = scratch_mixup(c, m.floats(MIXUP_TABLE), s);
+        float* cw_dev = nullptr;
+        std::vector<float> cw;
+        if (c.class_weight) {
+            cw.resize(C);
+            for (int j = 0; j < C; ++j) cw[j] = (float)c.class_weight[j];
+            cw_dev = m.floats(C);
+            CMOOP_HIP(hipMemcpyAsync(cw_dev, cw.data(), (size_t)C * 4, hipMemcpyHostToDevice, s));
+        }
+        launch_soft_targets(labels_dev, idx_dev, row0, B, C, mp, target_params(c, C, cw_dev), seed, step, t_dev, w_dev, primary_dev, s,
+                            nullptr, n_rows);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_softmax_ce_soft(const float* z, const float* t, const float* w, const int32_t* primary, int32_t B, int32_t C, float* dz,
+                          double* acc, int32_t* preds) {
+    return guard([&] {
+        CMOOP_REQUIRE(B >= 0 && C >= 1, "softmax_ce_soft: B >= 0, C >= 1");
+        CMOOP_REQUIRE(B == 0 || (z && t), "softmax_ce_soft: NULL logits or targets");
+        hipStream_t s = lib_stream();
+        launch_softmax_ce_soft(z, t, w, primary, B, C, dz, acc, preds, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
 
@@ -722,6 +847,28 @@ int cmoop_net_set_augment(cmoop_net* h, const cmoop_augment* aug) {
         if (!aug) { h->net->set_augment(nullptr); return; }
         const AugmentCfg c = to_augment(aug);
         h->net->set_augment(&c);
+    });
+}
+int cmoop_net_set_loss(cmoop_net* h, const cmoop_loss* loss) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "set_loss: NULL net");
+        if (!loss) { h->net->set_loss(nullptr); return; }
+        const LossCfg c = to_loss(loss);
+        h->net->set_loss(&c);
+    });
+}
+int cmoop_net_train_step_targets(cmoop_net* h, const float* x_rows, const float* t, const float* w, const int32_t* primary, int32_t B) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "train_step_targets: NULL net");
+        h->net->train_step_targets(x_rows, t, w, primary, B);
+        CMOOP_HIP(hipStreamSynchronize(h->net->stream()));
+        h->net->drain_profile();
+    });
+}
+int cmoop_net_loss_buffers(cmoop_net* h, int64_t out[4]) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net && out, "loss_buffers: NULL argument");
+        h->net->loss_buffers(out);
     });
 }
 int cmoop_net_set_gather_rows(cmoop_net* h, int64_t n_rows) {

@@ -28,9 +28,10 @@ struct Error : std::runtime_error {
 // ---------------------------------------------------------------------------
 // Counter-based RNG, bit-exact twin of oracle/rng.py (murmur3 fmix32 chain).
 // Streams: 0x1000+tensor (init), 0x2000+fc layer (dropout), 0x3000 (shuffle),
-// 0x4000 (train-time augmentation: row draws; 0x4001 / 0x4002 the two noise words).
+// 0x4000 (train-time augmentation: row draws; 0x4001 / 0x4002 the two noise words), 0x5000 (mixup: gate / partner / lam).
 // ---------------------------------------------------------------------------
-constexpr uint32_t STREAM_INIT = 0x1000u, STREAM_DROPOUT = 0x2000u, STREAM_SHUFFLE = 0x3000u, STREAM_AUGMENT = 0x4000u;
+constexpr uint32_t STREAM_INIT = 0x1000u, STREAM_DROPOUT = 0x2000u, STREAM_SHUFFLE = 0x3000u, STREAM_AUGMENT = 0x4000u,
+                   STREAM_MIXUP = 0x5000u;
 
 __host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
     h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cmath>
+#include <mutex>
 
 namespace cmoop {
 
@@ -1372,6 +1373,296 @@ void launch_augment_gather(const float* X, const int32_t* idx, int64_t row0, flo
     else
         hipLaunchKernelGGL(augment_gather_kernel<1>, dim3(grid), dim3(256), 0, s, X, idx, row0, out, B, T, F, a, seed, step, cpr, st, n_rows);
     CMOOP_HIP(hipGetLastError());
+}
+
+// ===========================================================================
+// Soft-target training loss (kernels.h: semantics): the mixup blend of two batch rows, the dense targets / row weights,
+// and cross-entropy against them.
+// ===========================================================================
+// lam x + mu xq as two products and one add, each rounded separately (the numpy twin multiplies, multiplies, adds): no
+// fused multiply-add, for augment_add_noise's reason
+__device__ __forceinline__ float mixup_blend(float x, float xq, float lam, float mu) {
+#pragma clang fp contract(off)
+    const float a = lam * x;
+    const float c = mu * xq;
+    return a + c;
+}
+
+// Work items as augment_gather_kernel: 256-thread slice `chunk` of `cpr` of batch row b; thread 0 makes the row's draw
+// once per item into LDS.  An un-mixed row is a plain copy
+template <int VEC>
+__global__ __launch_bounds__(256) void mixup_gather_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx,
+                                                           int64_t row0, int from_batch, float* __restrict__ out, int B, int TF,
+                                                           MixupParams m, uint32_t seed, uint32_t step, int cpr,
+                                                           const StepState* __restrict__ st, int64_t n_rows) {
+    __shared__ int32_t dq[2];
+    __shared__ float dlam;
+    if (st) {
+        step = st->step;
+        if (!from_batch) row0 = st->row0;      // the batch buffer always starts at its row 0
+    }
+    const int TFV = TF / VEC;
+    const int items = B * cpr;
+    for (int w = blockIdx.x; w < items; w += gridDim.x) {
+        const int b = w / cpr, chunk = w - b * cpr;
+        __syncthreads();                       // the previous item's readers are done with the draw
+        if (threadIdx.x == 0) mixup_row_draws(m, seed, step, (uint32_t)b, (uint32_t)B, &dq[0], &dq[1], &dlam);
+        __syncthreads();
+        const int q = dq[1];
+        const float lam = dlam, mu = 1.0f - lam;
+        const float* xb = src + (from_batch ? (int64_t)b : gather_row(idx, row0 + b, n_rows)) * (int64_t)TF;
+        const float* xq = src + (from_batch ? (int64_t)q : gather_row(idx, row0 + q, n_rows)) * (int64_t)TF;
+        float* dst = out + (int64_t)b * TF;
+        const bool mixed = q != b;
+        for (int i = chunk * 256 + threadIdx.x; i < TFV; i += cpr * 256) {
+            if constexpr (VEC == 4) {
+                f32x4 v = *reinterpret_cast<const f32x4*>(xb + 4 * i);
+                if (mixed) {
+                    const f32x4 u = *reinterpret_cast<const f32x4*>(xq + 4 * i);
+                    v.x = mixup_blend(v.x, u.x, lam, mu); v.y = mixup_blend(v.y, u.y, lam, mu);
+                    v.z = mixup_blend(v.z, u.z, lam, mu); v.w = mixup_blend(v.w, u.w, lam, mu);
+                }
+                *reinterpret_cast<f32x4*>(dst + 4 * i) = v;
+            } else {
+                float v = xb[i];
+                if (mixed) v = mixup_blend(v, xq[i], lam, mu);
+                dst[i] = v;
+            }
+        }
+    }
+}
+
+void launch_mixup_gather(const float* src, const int32_t* idx, int64_t row0, int from_batch, float* out, int B, int T, int F,
+                         const MixupParams& m, uint32_t seed, uint32_t step, hipStream_t s, const StepState* st, int64_t n_rows) {
+    if (B == 0) return;
+    CMOOP_REQUIRE(B >= 1 && T >= 1 && F >= 1 && src && out && src != out, "mixup gather: bad arguments");
+    CMOOP_REQUIRE((int64_t)T * F < (1ll << 30), "mixup gather: T * F must stay below 2^30");
+    CMOOP_REQUIRE(!m.on || m.tab != nullptr, "mixup gather: the lam table is missing");
+    const bool vec = F % 4 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const int TF = T * F, TFV = vec ? TF / 4 : TF;
+    const int cpr = std::max(1, std::min(cdiv(TFV, 256), std::max(1, 2048 / B)));
+    const unsigned grid = (unsigned)std::min<int64_t>((int64_t)B * cpr, 2048);
+    if (vec)
+        hipLaunchKernelGGL(mixup_gather_kernel<4>, dim3(grid), dim3(256), 0, s, src, idx, row0, from_batch, out, B, TF, m, seed, step,
+                           cpr, st, n_rows);
+    else
+        hipLaunchKernelGGL(mixup_gather_kernel<1>, dim3(grid), dim3(256), 0, s, src, idx, row0, from_batch, out, B, TF, m, seed, step,
+                           cpr, st, n_rows);
+    CMOOP_HIP(hipGetLastError());
+}
+
+// One thread per batch row: the row's draw, its two labels, then C targets.  A label outside [0, C) matches no class (its
+// share of the target is dropped, as the sparse kernel's comparison drops it) and reads the weight of the nearest class
+__global__ __launch_bounds__(256) void soft_targets_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ idx,
+                                                           int64_t row0, int B, int C, MixupParams m, TargetParams tp, uint32_t seed,
+                                                           uint32_t step, float* __restrict__ T, float* __restrict__ W,
+                                                           int32_t* __restrict__ primary, const StepState* __restrict__ st,
+                                                           int64_t n_rows) {
+#pragma clang fp contract(off)
+    if (st) { row0 = st->row0; step = st->step; }
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    int32_t gate, q;
+    float lam;
+    mixup_row_draws(m, seed, step, (uint32_t)b, (uint32_t)B, &gate, &q, &lam);
+    const float mu = 1.0f - lam;
+    const int a = labels[gather_row(idx, row0 + b, n_rows)];
+    const int c = q == b ? a : labels[gather_row(idx, row0 + q, n_rows)];
+    float* t = T + (size_t)b * C;
+    for (int j = 0; j < C; ++j) {
+        const float mj = (j == a ? lam : 0.f) + (j == c ? mu : 0.f);
+        const float sc = mj * tp.one_minus_eps;
+        t[j] = sc + tp.eps_over_c;
+    }
+    float w = 1.0f;
+    if (tp.cw) {
+        const float wa = lam * tp.cw[min(max(a, 0), C - 1)];
+        const float wc = mu * tp.cw[min(max(c, 0), C - 1)];
+        w = wa + wc;
+    }
+    W[b] = w;
+    primary[b] = a;
+}
+
+void launch_soft_targets(const int32_t* labels, const int32_t* idx, int64_t row0, int B, int C, const MixupParams& m,
+                         const TargetParams& tp, uint32_t seed, uint32_t step, float* t, float* w, int32_t* primary, hipStream_t s,
+                         const StepState* st, int64_t n_rows) {
+    if (B == 0) return;
+    CMOOP_REQUIRE(B >= 1 && C >= 1 && labels && t && w && primary, "soft targets: bad arguments");
+    CMOOP_REQUIRE(!m.on || m.tab != nullptr, "soft targets: the lam table is missing");
+    hipLaunchKernelGGL(soft_targets_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, labels, idx, row0, B, C, m, tp, seed, step, t, w,
+                       primary, st, n_rows);
+    CMOOP_HIP(hipGetLastError());
+}
+
+// softmax_ce_kernel with a dense target row in place of the label: the same loops in the same order for the maximum, the
+// sum, p, pc and S, the same fixed-order reduction.  On a one-hot row with unit weight the only extra operations are
+// 1.0f * x and x + 0.0f, so the loss, dz, the predictions and the correct count carry the sparse kernel's bits
+__global__ __launch_bounds__(256) void softmax_ce_soft_kernel(const float* __restrict__ Z, const float* __restrict__ Tg,
+                                                              const float* __restrict__ Wr, const int32_t* __restrict__ primary,
+                                                              int B, int C, float* __restrict__ dZ, double* __restrict__ acc,
+                                                              int32_t* __restrict__ preds) {
+    __shared__ double lsum[4];
+    __shared__ int csum[4];
+    const int t = threadIdx.x;
+    const float lo = 1e-7f, hi = 1.0f - 1e-7f;
+    double myloss = 0.0;
+    int mycorrect = 0;
+    for (int r = t; r < B; r += 256) {
+        const float* z = Z + (size_t)r * C;
+        const float* tg = Tg + (size_t)r * C;
+        const float w = Wr ? Wr[r] : 1.0f;
+        int y;
+        if (primary) {
+            y = primary[r];
+        } else {                               // the first maximum of the target row
+            y = 0;
+            float tm = tg[0];
+            for (int j = 1; j < C; ++j)
+                if (tg[j] > tm) { tm = tg[j]; y = j; }
+        }
+        float mx = z[0];
+        int am = 0;
+        for (int j = 1; j < C; ++j)
+            if (z[j] > mx) { mx = z[j]; am = j; }
+        float se = 0.f;
+        for (int j = 0; j < C; ++j) se += expf(z[j] - mx);
+        float S = 0.f, Tsum = 0.f;
+        for (int j = 0; j < C; ++j) {
+            const float p = expf(z[j] - mx) / se;
+            const float pc = fminf(fmaxf(p, lo), hi);
+            S += pc;
+            Tsum += tg[j];
+        }
+        const float logS = logf(S);
+        float l = 0.f;
+        for (int j = 0; j < C; ++j) {
+            const float tj = tg[j];
+            if (tj > 0.f) {
+                const float p = expf(z[j] - mx) / se;
+                const float pc = fminf(fmaxf(p, lo), hi);
+                l += tj * (logf(pc) - logS);
+            }
+        }
+        myloss += (double)(w * -l);
+        mycorrect += (am == y);
+        if (preds) preds[r] = am;
+        if (dZ) {
+            // q_j = gate_j * (Tsum/S - t_j/pc_j); dz_i = w * p_i * (q_i - sum_j p_j q_j), then / B
+            float dot = 0.f;
+            for (int j = 0; j < C; ++j) {
+                const float p = expf(z[j] - mx) / se;
+                const float pc = fminf(fmaxf(p, lo), hi);
+                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
+                const float qj = gate * (Tsum / S - tg[j] / pc);
+                dot += p * qj;
+            }
+            const float invB = 1.f / (float)B;
+            for (int j = 0; j < C; ++j) {
+                const float p = expf(z[j] - mx) / se;
+                const float pc = fminf(fmaxf(p, lo), hi);
+                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
+                const float qj = gate * (Tsum / S - tg[j] / pc);
+                dZ[(size_t)r * C + j] = w * (p * (qj - dot) * invB);
+            }
+        }
+    }
+    // wavefront reduction (fixed butterfly order: deterministic), then the four wave sums in wave order
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        myloss += __shfl_xor(myloss, off, 64);
+        mycorrect += __shfl_xor(mycorrect, off, 64);
+    }
+    if ((t & 63) == 0) { lsum[t >> 6] = myloss; csum[t >> 6] = mycorrect; }
+    __syncthreads();
+    if (t == 0 && acc) {
+        acc[0] += ((lsum[0] + lsum[1]) + lsum[2]) + lsum[3];
+        reinterpret_cast<long long*>(acc)[1] += (csum[0] + csum[1]) + (csum[2] + csum[3]);
+    }
+}
+
+void launch_softmax_ce_soft(const float* Z, const float* t, const float* w, const int32_t* primary, int B, int C, float* dZ,
+                            double* acc, int32_t* preds, hipStream_t s) {
+    if (B == 0) return;
+    CMOOP_REQUIRE(B >= 1 && C >= 1 && Z && t, "softmax_ce_soft: bad arguments");
+    hipLaunchKernelGGL(softmax_ce_soft_kernel, dim3(1), dim3(256), 0, s, Z, t, w, primary, B, C, dZ, acc, preds);
+    CMOOP_HIP(hipGetLastError());
+}
+
+void loss_check(const LossCfg& c, int classes) {
+    CMOOP_REQUIRE(classes >= 1, "loss: classes must be >= 1");
+    CMOOP_REQUIRE(c.label_smoothing >= 0.0 && c.label_smoothing < 1.0, "loss: label_smoothing must be in [0, 1)");   // (a NaN fails)
+    CMOOP_REQUIRE(std::isfinite(c.mixup_alpha) && c.mixup_alpha >= 0.0 && c.mixup_alpha <= 64.0,
+                  "loss: mixup_alpha must be finite and in [0, 64]");
+    CMOOP_REQUIRE(c.mixup_p >= 0.0 && c.mixup_p <= 1.0, "loss: mixup_p must be in [0, 1]");
+    if (c.class_weight) {
+        CMOOP_REQUIRE(c.n_class_weight == classes, "loss: n_class_weight must equal classes = " + std::to_string(classes) + " (got " +
+                                                       std::to_string(c.n_class_weight) + ")");
+        for (int j = 0; j < classes; ++j)
+            CMOOP_REQUIRE(std::isfinite(c.class_weight[j]) && c.class_weight[j] > 0.0,
+                          "loss: class_weight[" + std::to_string(j) + "] must be finite and > 0");
+    }
+}
+
+bool loss_enabled(const LossCfg& c) { return c.label_smoothing > 0.0 || loss_mixup_on(c) || c.class_weight != nullptr; }
+
+TargetParams target_params(const LossCfg& c, int classes, const float* cw_dev) {
+    TargetParams tp;
+    tp.one_minus_eps = (float)(1.0 - c.label_smoothing);
+    tp.eps_over_c = (float)(c.label_smoothing / (double)classes);
+    tp.cw = c.class_weight ? cw_dev : nullptr;
+    return tp;
+}
+
+// I_y(a, a) for 0 < y <= 1/2 (where the continued fraction of the incomplete beta converges fastest): modified Lentz
+static double inc_beta_sym(double a, double y, double ln_beta) {
+    if (y <= 0.0) return 0.0;
+    const double tiny = 1e-300, b = a, qab = a + b, qap = a + 1.0, qam = a - 1.0;
+    double c = 1.0, d = 1.0 - qab * y / qap;
+    if (std::fabs(d) < tiny) d = tiny;
+    d = 1.0 / d;
+    double h = d;
+    for (int m = 1; m <= 1000; ++m) {
+        const double m2 = 2.0 * m;
+        double aa = m * (b - m) * y / ((qam + m2) * (a + m2));
+        d = 1.0 + aa * d; if (std::fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c; if (std::fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        h *= d * c;
+        aa = -(a + m) * (qab + m) * y / ((a + m2) * (qap + m2));
+        d = 1.0 + aa * d; if (std::fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c; if (std::fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        const double del = d * c;
+        h *= del;
+        if (std::fabs(del - 1.0) < 3e-16) break;
+    }
+    return std::exp(a * std::log(y) + b * std::log1p(-y) - ln_beta) * h / a;
+}
+
+void mixup_table(double alpha, float out[MIXUP_TABLE]) {
+    CMOOP_REQUIRE(std::isfinite(alpha) && alpha > 0.0 && alpha <= 64.0, "mixup table: alpha must be finite and in (0, 64]");
+    // every candidate of a population asks for the same table: keep the last one
+    static std::mutex mu;
+    static double last_alpha = 0.0;
+    static float last_tab[MIXUP_TABLE];
+    std::lock_guard<std::mutex> lock(mu);
+    if (alpha == last_alpha) { std::copy(last_tab, last_tab + MIXUP_TABLE, out); return; }
+    const double ln_beta = 2.0 * std::lgamma(alpha) - std::lgamma(2.0 * alpha);
+    for (int k = 0; k < MIXUP_TABLE; ++k) {
+        // Q(0.5 + (k + 0.5) / 2048) = 1 - y with I_y(alpha, alpha) = 0.5 - (k + 0.5) / 2048 (symmetry), y in (0, 1/2):
+        // solved on the lower tail, where the small quantiles of a small alpha keep their relative precision
+        const double target = 0.5 - ((double)k + 0.5) / 2048.0;
+        double ylo = 0.0, yhi = 0.5;
+        for (int it = 0; it < 1200; ++it) {
+            const double mid = 0.5 * (ylo + yhi);
+            if (!(mid > ylo && mid < yhi)) break;
+            if (inc_beta_sym(alpha, mid, ln_beta) < target) ylo = mid; else yhi = mid;
+        }
+        out[k] = (float)(1.0 - 0.5 * (ylo + yhi));
+    }
+    std::copy(out, out + MIXUP_TABLE, last_tab);
+    last_alpha = alpha;
 }
 
 // Every operation of the update is a separately rounded IEEE single operation, in the order the reference's CPU path and

@@ -224,6 +224,75 @@ void launch_augment_gather(const float* X, const int32_t* idx, int64_t row0, flo
                            uint32_t seed, uint32_t step, hipStream_t s, const StepState* st = nullptr, int64_t n_rows = 0);
 
 // ---------------------------------------------------------------------------
+// Soft-target training loss (opt-in; no reference counterpart, BUILD-DEFINED -- include/cmoop.h fixes the semantics): mixup
+// of two rows of a batch, label smoothing and class weights, all funnelled into cross-entropy against a dense target
+// distribution t[B][C] with a per-row weight w[B].  Draws on the counter RNG, keyed like dropout and augmentation:
+//   u(k) = rng_u32(seed, STREAM_MIXUP, step, 4 b + k),   R(u, n) = ((uint64)u n) >> 32
+//   gate (u(0) >> 8) < floor(mixup_p 2^24);  partner q = R(u(1), B);  lam = tab[R(u(2), 1024)]
+//   tab[k] = (float)Q(0.5 + (k + 0.5) / 2048), Q the quantile function of Beta(alpha, alpha): the upper half, lam in [0.5, 1]
+//   a row is MIXED iff mixup is on, its gate is on, q != b and lam < 1; otherwise lam := 1, q := b
+// Validation never sees any of this: evaluate / predict / the val_loss EarlyStopping monitors stay the sparse cross-entropy.
+// ---------------------------------------------------------------------------
+struct LossCfg {
+    double label_smoothing = 0.0, mixup_alpha = 0.0, mixup_p = 1.0;
+    const double* class_weight = nullptr;   // null: off; else n_class_weight values
+    int n_class_weight = 0;
+};
+constexpr int MIXUP_TABLE = 1024;
+// host-only: throws with a message naming the offending field when the config is outside the domain for `classes` classes
+void loss_check(const LossCfg& c, int classes);
+// eps > 0, or (alpha > 0 and p > 0), or class weights.  A disabled config is no config
+bool loss_enabled(const LossCfg& c);
+inline bool loss_mixup_on(const LossCfg& c) { return c.mixup_alpha > 0.0 && c.mixup_p > 0.0; }
+// host-only: the lam table of Beta(alpha, alpha), evaluated in double (regularised incomplete beta by continued fraction,
+// then bisection), each entry rounded once
+void mixup_table(double alpha, float out[MIXUP_TABLE]);
+// the config as the kernels read it; tab / cw are device pointers in a launch (host pointers in mixup_row_draws on the host)
+struct MixupParams {
+    int on = 0;                  // mixup on (alpha > 0 and p > 0)
+    uint32_t gate_thr = 0;       // floor(mixup_p 2^24)
+    const float* tab = nullptr;  // [MIXUP_TABLE], required when on
+};
+struct TargetParams {
+    float one_minus_eps = 1.f;   // (float)(1 - eps)
+    float eps_over_c = 0.f;      // (float)(eps / C)
+    const float* cw = nullptr;   // [C] (float)class_weight, null: every weight 1.0f
+};
+TargetParams target_params(const LossCfg& c, int classes, const float* cw_dev);
+// effective draws of batch position b of a batch of B rows: *gate = the gate bit (0 with mixup off), *q / *lam after the MIXED rule
+__host__ __device__ __forceinline__ void mixup_row_draws(const MixupParams& m, uint32_t seed, uint32_t step, uint32_t b, uint32_t B,
+                                                         int32_t* gate, int32_t* q, float* lam) {
+    *gate = 0; *q = (int32_t)b; *lam = 1.0f;
+    if (!m.on) return;
+    const uint32_t prefix = rng_prefix(seed, STREAM_MIXUP, step), base = 4u * b;
+    if (!((fmix32(prefix ^ base) >> 8) < m.gate_thr)) return;
+    *gate = 1;
+    const uint32_t qq = augment_range(fmix32(prefix ^ (base + 1u)), B);
+    const float l = m.tab[augment_range(fmix32(prefix ^ (base + 2u)), (uint32_t)MIXUP_TABLE)];
+    if (qq != b && l < 1.0f) { *q = (int32_t)qq; *lam = l; }
+}
+// out[B][T][F]: row b = lam x[b] + (1 - lam) x[q] (two fp32 products, one fp32 add, separately rounded) for a MIXED row,
+// a plain copy (bits kept, the sign of a zero included) otherwise.  from_batch == 0: x[b] = row idx[row0 + b] (idx null:
+// row0 + b) of the resident tensor src, clamped by n_rows as launch_conv1_fwd; from_batch != 0: x[b] = row b of the
+// already gathered batch buffer src (idx / row0 / n_rows unused).  st != null: step -- and, from_batch == 0 only, row0 --
+// come from the device state (graph replay).  16-byte accesses under launch_augment_gather's rule.  T F < 2^30.
+void launch_mixup_gather(const float* src, const int32_t* idx, int64_t row0, int from_batch, float* out, int B, int T, int F,
+                         const MixupParams& m, uint32_t seed, uint32_t step, hipStream_t s, const StepState* st = nullptr,
+                         int64_t n_rows = 0);
+// t[B][C], w[B], primary[B] from the labels a = y[row(b)], c = y[row(q)] (rows through idx / row0 / n_rows as above), fp32,
+// every operation rounded separately:  m_j = (j == a ? lam : 0) + (j == c ? mu : 0),  mu = 1 - lam (exact);
+// t[b][j] = m_j (float)(1 - eps) + (float)(eps / C);  w[b] = lam cw[a] + mu cw[c] (1.0f without class weights);  primary[b] = a
+void launch_soft_targets(const int32_t* labels, const int32_t* idx, int64_t row0, int B, int C, const MixupParams& m,
+                         const TargetParams& tp, uint32_t seed, uint32_t step, float* t, float* w, int32_t* primary, hipStream_t s,
+                         const StepState* st = nullptr, int64_t n_rows = 0);
+// softmax + clipped cross-entropy against dense targets: p, pc = clip(p, 1e-7, 1 - 1e-7), S = sum pc by softmax_ce_kernel's
+// loops;  l_b = -sum_{t_j > 0} t_j (log pc_j - log S);  acc[0] += w_b l_b;  acc[1] += (argmax z == primary[b]);
+// dz_i = w_b p_i (q_i - sum_j p_j q_j) / B with q_j = gate_j (sum_j t_j / S - t_j / pc_j).  w null: 1; primary null: the
+// first maximum of t[b].  One-hot t and unit w give softmax_ce_kernel's bits (loss, dz, preds, correct)
+void launch_softmax_ce_soft(const float* Z, const float* t, const float* w, const int32_t* primary, int B, int C, float* dZ,
+                            double* acc, int32_t* preds, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Per-channel reductions over the M rows of an [M][C] tensor (C % 4 == 0).
 // Two-stage and order-fixed: `blocks` partials then a double-precision finalize.
 // ---------------------------------------------------------------------------

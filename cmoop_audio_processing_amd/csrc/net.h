@@ -204,6 +204,16 @@ class Net : public GemmHook {
     // allocated on first use, which the first-layer kernels then read in place of the resident tensor.  Labels, loss,
     // dropout and Adam are untouched; evaluate / predict / predict_stream never augment.  Drops a captured step graph
     void set_augment(const AugmentCfg* aug);
+    // Soft-target training loss (kernels.h) of every following train step, both step paths; null or a disabled config: off,
+    // and a step's launches and allocations are those of a net that never had one.  Enabled: the domain is checked against
+    // cfg.classes, the lam table and the class weights are uploaded, the target / weight / primary buffers (and, with mixup,
+    // a second [cfg.batch][T][F] batch buffer) are allocated on first use; each step then blends its batch (mixup only),
+    // builds t / w / primary after the forward pass and takes softmax_ce_soft_kernel in place of softmax_ce_kernel.
+    // evaluate / predict / predict_stream and the validation loss of a fit stay the sparse cross-entropy.  Drops a captured
+    // step graph
+    void set_loss(const LossCfg* loss);
+    // floats (int32 words) allocated for the mixup batch buffer, t, w and primary: 0 where the buffer does not exist
+    void loss_buffers(int64_t out[4]) const;
     // rows of the resident tensor the next train steps gather from (0: unknown, no clamp)
     void set_gather_rows(int64_t n) { gather_rows_ = n; }
     // ONE epoch of Model.fit on the production path (device permutation of (seed, epoch) when cfg.shuffle, device
@@ -212,6 +222,10 @@ class Net : public GemmHook {
 
     // fwd + bwd + Adam on rows idx[row0 .. row0+B) (idx may be null -> rows row0..)
     void train_step(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B);
+    // one optimiser step on caller-built rows and targets: x_rows [B][T][F], t [B][classes], w [B] (null: 1), primary [B]
+    // (null: the first maximum of t), all on the device.  No augmentation, no mixing, no target construction, whatever
+    // set_augment / set_loss say; dropout, Adam and the counters advance as in train_step
+    void train_step_targets(const float* x_rows, const float* t, const float* w, const int32_t* primary, int B);
     // The fit loop's form of the same step: the batch position, dropout counter and Adam iteration live in a device
     // StepState (kernels.h), so a full-batch step has no per-step host arguments; with CMOOP_GRAPH=1 it is captured ONCE
     // as a hipGraph and replayed (opt-in: measured no faster than eager launches, see begin_fit).
@@ -241,6 +255,7 @@ class Net : public GemmHook {
     void forward(const float* X, const int32_t* idx, int64_t row0, int B, bool train, const StepState* st = nullptr);
     void backward(const float* X, const int32_t* idx, int64_t row0, int B, const StepState* st = nullptr);
     void step_body(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B, const StepState* st);
+    void optimiser_step(int B, const StepState* st);   // the tail of a step: weight-gradient slabs summed + Adam (+ state advance)
     ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
 
@@ -258,6 +273,14 @@ class Net : public GemmHook {
     bool aug_on_ = false;               // train steps read aug_buf_ (set_augment)
     AugmentParams aug_;
     float* aug_buf_ = nullptr;          // [cfg.batch][T][F], allocated by the first enabled set_augment
+    bool loss_on_ = false, mix_on_ = false;   // train steps take the soft-target loss / blend their batch first (set_loss)
+    MixupParams mixp_;                  // tab: lam_tab_
+    TargetParams tgtp_;                 // cw: cw_dev_ or null
+    float *lam_tab_ = nullptr, *cw_dev_ = nullptr;
+    float* mix_buf_ = nullptr;          // [cfg.batch][T][F], allocated by the first set_loss with mixup on
+    float *tgt_t_ = nullptr, *tgt_w_ = nullptr;   // [cfg.batch][classes], [cfg.batch]: allocated by the first enabled set_loss
+    int32_t* tgt_primary_ = nullptr;    // [cfg.batch]
+    const float* batch_in_ = nullptr;   // this train step's gathered batch (mix_buf_ / aug_buf_), null: rows come from (X, idx, row0)
     StepState* st_dev_ = nullptr;       // device step state (train_step_stateful)
     float* alpha_tab_ = nullptr;        // Adam step size per iteration
     int64_t alpha_tab_n_ = 0, host_row0_ = 0, gather_rows_ = 0;
@@ -293,9 +316,10 @@ struct FitHistory {
 // Model.fit + EarlyStopping + the read-outs on an EXISTING net (the body of run_candidate); seed keys the epoch shuffle
 EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, uint32_t seed, FitHistory* hist = nullptr);
 // train-to-early-stop + readouts for one candidate (evaluate_individual, nsga_penalty.py:368-395)
-// aug (optional): train-time augmentation of the candidate's fit (Net::set_augment)
+// aug (optional): train-time augmentation of the candidate's fit (Net::set_augment); loss (optional): its soft-target
+// training loss (Net::set_loss)
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
-                         const AugmentCfg* aug = nullptr);
+                         const AugmentCfg* aug = nullptr, const LossCfg* loss = nullptr);
 // host-only: every implicit-GEMM conv geometry of a candidate at batch B (a walk of plan_net's ops); throws
 // through igemm_check_range when a layer is beyond the kernels' 32-bit byte offsets
 void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
@@ -305,7 +329,8 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
 // lets several ranks drain ONE longest-first queue (cross-rank dynamic scheduling, evaluator.py); without it the
 // n candidates are taken longest-first from a process-local counter.
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
-                     EvalResult* out, const std::function<int()>& pull = {}, const AugmentCfg* aug = nullptr);
+                     EvalResult* out, const std::function<int()>& pull = {}, const AugmentCfg* aug = nullptr,
+                     const LossCfg* loss = nullptr);
 
 // host-only: windows of T frames at hop frames in a stream of n_frames, 1 + (n_frames - T) / hop; throws when n_frames < T or hop < 1
 int64_t stream_windows(int64_t n_frames, int T, int hop);

@@ -684,8 +684,9 @@ void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool 
         switch (op.kind) {
         case OP_CONV1: {
             fused_stats_blocks_ = 0;
-            const bool aug = train && aug_on_;   // the batch is rows 0 .. B of the buffer step_body's augment launch wrote
-            launch_conv1_fwd(aug ? aug_buf_ : X, aug ? nullptr : idx, aug ? 0 : row0, params_ + op.w_off, params_ + op.b_off,
+            const float* bin = train ? batch_in_ : nullptr;   // the batch is rows 0 .. B of the buffer step_body's augment / mixup launch wrote
+            const bool aug = bin != nullptr;
+            launch_conv1_fwd(aug ? bin : X, aug ? nullptr : idx, aug ? 0 : row0, params_ + op.w_off, params_ + op.b_off,
                              acts_[op.out].data, B, T_, F_, op.Cout, op.KS, op.relu, stream_, aug ? nullptr : st,
                              (train && !aug) ? gather_rows_ : 0, (train && op.feeds_bn) ? red_ws_ : nullptr,
                              (train && op.feeds_bn) ? &fused_stats_blocks_ : nullptr);
@@ -828,8 +829,8 @@ void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, cons
             break;
         }
         case OP_CONV1: {
-            if (aug_on_)
-                launch_conv1_wgrad(aug_buf_, nullptr, 0, acts_[op.out].grad, wgrad_ws_ + op.slab_off, B, T_, F_, op.Cout, op.KS, stream_,
+            if (batch_in_)
+                launch_conv1_wgrad(batch_in_, nullptr, 0, acts_[op.out].grad, wgrad_ws_ + op.slab_off, B, T_, F_, op.Cout, op.KS, stream_,
                                    nullptr, 0);
             else
                 launch_conv1_wgrad(X, idx, row0, acts_[op.out].grad, wgrad_ws_ + op.slab_off, B, T_, F_, op.Cout, op.KS, stream_, st,
@@ -854,10 +855,27 @@ void Net::step_body(const float* X, const int32_t* y, const int32_t* idx, int64_
     // augmentation on: the batch's rows are gathered and augmented into aug_buf_ first (st != null: the kernel reads the
     // batch position and the step from the device state, so a replayed graph draws for the step it replays)
     if (aug_on_) launch_augment_gather(X, idx, row0, aug_buf_, B, T_, F_, aug_, seed_, (uint32_t)step_, stream_, st, gather_rows_);
+    // mixup on: the (augmented) rows are blended into mix_buf_ next; each row keeps its own batch position's augmentation
+    if (mix_on_) {
+        if (aug_on_) launch_mixup_gather(aug_buf_, nullptr, 0, 1, mix_buf_, B, T_, F_, mixp_, seed_, (uint32_t)step_, stream_, st, 0);
+        else launch_mixup_gather(X, idx, row0, 0, mix_buf_, B, T_, F_, mixp_, seed_, (uint32_t)step_, stream_, st, gather_rows_);
+    }
+    batch_in_ = mix_on_ ? mix_buf_ : (aug_on_ ? aug_buf_ : nullptr);
     forward(X, idx, row0, B, true, st);
-    launch_softmax_ce(acts_[logits_].data, y, idx, row0, B, cfg_.classes, acts_[logits_].grad, acc_train_, nullptr, stream_, st,
-                      gather_rows_);
+    if (loss_on_) {
+        launch_soft_targets(y, idx, row0, B, cfg_.classes, mixp_, tgtp_, seed_, (uint32_t)step_, tgt_t_, tgt_w_, tgt_primary_, stream_,
+                            st, gather_rows_);
+        launch_softmax_ce_soft(acts_[logits_].data, tgt_t_, tgt_w_, tgt_primary_, B, cfg_.classes, acts_[logits_].grad, acc_train_,
+                               nullptr, stream_);
+    } else {
+        launch_softmax_ce(acts_[logits_].data, y, idx, row0, B, cfg_.classes, acts_[logits_].grad, acc_train_, nullptr, stream_, st,
+                          gather_rows_);
+    }
     backward(X, idx, row0, B, st);
+    optimiser_step(B, st);
+}
+
+void Net::optimiser_step(int B, const StepState* st) {
     const double t = (double)(iterations_ + 1);
     const double b1 = cfg_.beta1, b2 = cfg_.beta2;
     const float alpha = (float)(cfg_.lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t)));
@@ -895,6 +913,29 @@ void Net::train_step(const float* X, const int32_t* y, const int32_t* idx, int64
     CMOOP_REQUIRE(B >= 1 && B <= cfg_.batch, "train batch larger than configured");
     profiling_now_ = cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0;
     step_body(X, y, idx, row0, B, nullptr);
+    ++iterations_;
+    ++step_;
+    profiling_now_ = false;
+}
+
+void Net::train_step_targets(const float* x_rows, const float* t, const float* w, const int32_t* primary, int B) {
+    CMOOP_REQUIRE(B >= 1 && B <= cfg_.batch, "train batch larger than configured");
+    CMOOP_REQUIRE(x_rows && t, "train_step_targets: NULL rows or targets");
+    profiling_now_ = cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0;
+    const int64_t rows = gather_rows_;
+    gather_rows_ = 0;          // x_rows holds exactly the B rows of this step: no resident tensor to clamp into
+    batch_in_ = nullptr;
+    try {
+        forward(x_rows, nullptr, 0, B, true, nullptr);
+        launch_softmax_ce_soft(acts_[logits_].data, t, w, primary, B, cfg_.classes, acts_[logits_].grad, acc_train_, nullptr, stream_);
+        backward(x_rows, nullptr, 0, B, nullptr);
+        optimiser_step(B, nullptr);
+    } catch (...) {
+        gather_rows_ = rows;
+        profiling_now_ = false;
+        throw;
+    }
+    gather_rows_ = rows;
     ++iterations_;
     ++step_;
     profiling_now_ = false;
@@ -1007,6 +1048,56 @@ void Net::set_augment(const AugmentCfg* aug) {
     CMOOP_HIP(hipStreamSynchronize(stream_));
     aug_on_ = on;
     if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }   // the captured step has the old launch sequence
+}
+
+void Net::set_loss(const LossCfg* loss) {
+    const bool on = loss != nullptr && loss_enabled(*loss);
+    if (loss) loss_check(*loss, cfg_.classes);
+    const bool mix = on && loss_mixup_on(*loss);
+    MixupParams mp;
+    TargetParams tp;
+    if (on) {
+        const size_t C = (size_t)cfg_.classes;
+        if (!tgt_t_) {
+            tgt_t_ = dalloc((size_t)cfg_.batch * C);
+            tgt_w_ = dalloc((size_t)cfg_.batch);
+            tgt_primary_ = reinterpret_cast<int32_t*>(dalloc((size_t)cfg_.batch));
+        }
+        std::vector<float> tab, cw;
+        if (mix) {
+            CMOOP_REQUIRE((int64_t)T_ * F_ < (1ll << 30), "mixup: T * F must stay below 2^30");
+            tab.resize(MIXUP_TABLE);
+            mixup_table(loss->mixup_alpha, tab.data());
+            if (!lam_tab_) lam_tab_ = dalloc(MIXUP_TABLE);
+            if (!mix_buf_) mix_buf_ = dalloc((size_t)cfg_.batch * T_ * F_);
+            CMOOP_HIP(hipMemcpyAsync(lam_tab_, tab.data(), MIXUP_TABLE * 4, hipMemcpyHostToDevice, stream_));
+            mp.on = 1;
+            mp.gate_thr = (uint32_t)std::floor(loss->mixup_p * 16777216.0);
+            mp.tab = lam_tab_;
+        }
+        if (loss->class_weight) {
+            cw.resize(C);
+            for (size_t j = 0; j < C; ++j) cw[j] = (float)loss->class_weight[j];
+            if (!cw_dev_) cw_dev_ = dalloc(C);
+            CMOOP_HIP(hipMemcpyAsync(cw_dev_, cw.data(), C * 4, hipMemcpyHostToDevice, stream_));
+        }
+        tp = target_params(*loss, cfg_.classes, cw_dev_);
+        CMOOP_HIP(hipStreamSynchronize(stream_));   // tab and cw are locals
+    } else {
+        CMOOP_HIP(hipStreamSynchronize(stream_));
+    }
+    loss_on_ = on;
+    mix_on_ = mix;
+    mixp_ = mp;
+    tgtp_ = tp;
+    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }   // the captured step has the old launch sequence
+}
+
+void Net::loss_buffers(int64_t out[4]) const {
+    out[0] = mix_buf_ ? (int64_t)cfg_.batch * T_ * F_ : 0;
+    out[1] = tgt_t_ ? (int64_t)cfg_.batch * cfg_.classes : 0;
+    out[2] = tgt_w_ ? (int64_t)cfg_.batch : 0;
+    out[3] = tgt_primary_ ? (int64_t)cfg_.batch : 0;
 }
 
 void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch, int32_t* idx_scratch) {
@@ -1226,11 +1317,12 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
 }
 
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
-                         const AugmentCfg* aug) {
+                         const AugmentCfg* aug, const LossCfg* loss) {
     const auto t0 = std::chrono::steady_clock::now();
     CMOOP_REQUIRE(ds.n_train >= 1 && ds.n_val >= 1, "empty train or validation split");
     Net net(gene, cfg, ds.T, ds.F, seed, stream);
     if (aug) net.set_augment(aug);
+    if (loss) net.set_loss(loss);
     EvalResult res = fit_and_read_out(net, cfg, ds, seed, nullptr);
     res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return res;
@@ -1248,9 +1340,10 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B) 
 }
 
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
-                     EvalResult* out, const std::function<int()>& pull, const AugmentCfg* aug) {
+                     EvalResult* out, const std::function<int()>& pull, const AugmentCfg* aug, const LossCfg* loss) {
     if (n <= 0) return;
     if (aug && !augment_enabled(*aug)) aug = nullptr;   // a disabled config is no config: today's path, call for call
+    if (loss && !loss_enabled(*loss)) loss = nullptr;
     for (int i = 0; i < n; ++i) validate_gene(genes + 6 * i);
     for (int i = 0; i < n; ++i) out[i].evaluated = 0;
     // longest first (closed-form FLOPs) so the tail of the generation is made of cheap candidates
@@ -1282,7 +1375,7 @@ void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* gen
                     if (j >= n) break;
                     i = order[j];
                 }
-                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream, aug);
+                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream, aug, loss);
                 out[i].evaluated = 1;
             }
         } catch (const std::exception& e) {

@@ -34,6 +34,7 @@ import numpy as np
 
 from . import _lib, genes as G
 from .augment import AugmentConfig
+from .loss import LossConfig
 
 FPR_CODES = {"v1": 0, "v1_quirk": 1, "v3": 2}
 ACC_CODES = {"last": 0, "evaluate": 1}
@@ -78,6 +79,10 @@ class EvalConfig:
     # train-time augmentation of every candidate's fit (augment.py): None or a config that does nothing = off, every number
     # as without the field.  Not part of cmoop_config: it travels beside it (cmoop_net_set_augment, cmoop_eval_population_aug)
     augment: Optional[AugmentConfig] = None
+    # soft-target training loss of every candidate's fit (loss.py: mixup, label smoothing, class weights): None or a config
+    # that does nothing = off, every number as without the field.  Validation stays the sparse cross-entropy.  Travels
+    # beside cmoop_config like augment (cmoop_net_set_loss, cmoop_eval_population_ex)
+    loss: Optional[LossConfig] = None
 
     @staticmethod
     def preset(script: str, **over) -> "EvalConfig":
@@ -130,6 +135,13 @@ class EvalConfig:
         if self.augment is None or not self.augment.enabled:
             return None
         return self.augment.check(T, F)._struct()
+
+
+    def loss_struct(self) -> Optional["_lib.Loss"]:
+        """The enabled training loss as a ``cmoop_loss``, checked for ``classes``; None when it is off."""
+        if self.loss is None or not self.loss.enabled:
+            return None
+        return self.loss.check(self.classes)._struct()
 
 
 def _as_device_features(x):
@@ -373,8 +385,12 @@ class PopulationEvaluator:
         acc, size, fpr, secs = (np.zeros(n, np.float64) for _ in range(4))
         ep = np.zeros(n, np.int32)
         cfg, ds = self.config.to_struct(), self._dataset()
-        aug = self.config.augment_struct(self.T, self.F)
-        if aug is not None:
+        aug, loss = self.config.augment_struct(self.T, self.F), self.config.loss_struct()
+        if loss is not None:
+            _lib.check(_lib.lib().cmoop_eval_population_ex(
+                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
+                C.c_int32(n), None, None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), None))
+        elif aug is not None:
             _lib.check(_lib.lib().cmoop_eval_population_aug(
                 C.byref(cfg), C.byref(aug), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), None, None, _lib.ptr(acc),
                 _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), None))
@@ -410,8 +426,13 @@ class PopulationEvaluator:
                 errors.append(e)
                 return -1
         cb = _lib.NEXT_FN(_next)
-        aug = self.config.augment_struct(self.T, self.F)
-        if aug is not None:
+        aug, loss = self.config.augment_struct(self.T, self.F), self.config.loss_struct()
+        if loss is not None:
+            _lib.check(_lib.lib().cmoop_eval_population_ex(
+                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
+                C.c_int32(n), C.cast(cb, C.c_void_p), None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None,
+                _lib.ptr(secs), _lib.ptr(done)))
+        elif aug is not None:
             _lib.check(_lib.lib().cmoop_eval_population_aug(
                 C.byref(cfg), C.byref(aug), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), C.cast(cb, C.c_void_p), None,
                 _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
@@ -477,7 +498,8 @@ class PopulationEvaluator:
     def train_model(self, hparams, seed: int, frontend=None, mean=None, scale=None):
         """Train ONE candidate on the resident splits and keep its weights -> ``deploy.TrainedModel``.
 
-        The body of the population call's per-candidate work (``NetSession.fit``) on the given seed: with
+        The body of the population call's per-candidate work (``NetSession.fit``) on the given seed and under the same
+        ``config.augment`` / ``config.loss``: with
         ``seed = last_seeds[i]`` it reproduces candidate i of the last generation, accuracy and FPR included.
         ``hparams`` is the reference's dict or a gene tuple; ``frontend`` / ``mean`` / ``scale`` (the front end and the
         StandardScaler the features were made with) ride along for ``StreamScorer``."""

@@ -31,6 +31,47 @@ class NetSession:
             except Exception:
                 self.close()
                 raise
+        self.loss = None
+        if getattr(config, "loss", None) is not None:
+            try:
+                self.set_loss(config.loss)
+            except Exception:
+                self.close()
+                raise
+
+    def set_loss(self, loss) -> None:
+        """Soft-target training loss (``LossConfig``: mixup, label smoothing, class weights) of every following train step
+        of this net -- ``train_step``, ``run_epoch`` and ``fit`` alike; None or a config that does nothing turns it off.
+        ``evaluate``, ``predict_proba``, ``predict_stream`` and the validation loss of ``fit`` stay the sparse cross-entropy;
+        ``train_metrics`` then reports the weighted soft-target loss sum and the rows whose arg max is their own label."""
+        if loss is None:
+            _lib.check(_lib.lib().cmoop_net_set_loss(self._h, None))
+        else:
+            st = loss.check(int(self.config.classes))._struct()
+            _lib.check(_lib.lib().cmoop_net_set_loss(self._h, C.byref(st)))
+        self.loss = loss
+
+    def loss_buffers(self):
+        """dict(mix, t, w, primary): floats the net has allocated for the training loss (0: that buffer does not exist)."""
+        out = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().cmoop_net_loss_buffers(self._h, out))
+        return dict(zip(("mix", "t", "w", "primary"), (int(v) for v in out)))
+
+    def train_step_targets(self, X_rows, t, w=None, primary=None) -> None:
+        """One optimiser step on caller-built rows and targets: X_rows CUDA float32 [B, T, F], t CUDA float32 [B, classes]
+        (rows of a distribution), w CUDA float32 [B] or None (1), primary CUDA int32 [B] or None (arg max of t: the class a
+        row counts as correct for).  No augmentation, no mixing, no target construction; dropout, Adam and the counters
+        advance as in ``train_step``.  The hook for soft targets from elsewhere, a teacher's probabilities for one."""
+        import torch
+        B = int(X_rows.shape[0])
+        if tuple(X_rows.shape) != (B, self.T, self.F) or tuple(t.shape) != (B, int(self.config.classes)):
+            raise ValueError(f"train_step_targets: rows must be [B, {self.T}, {self.F}] and targets [B, {int(self.config.classes)}]")
+        for name, v, dt in (("X_rows", X_rows, torch.float32), ("t", t, torch.float32), ("w", w, torch.float32), ("primary", primary, torch.int32)):
+            if v is not None and not (v.is_cuda and v.dtype == dt and v.is_contiguous() and int(v.shape[0]) == B):
+                raise ValueError(f"train_step_targets: {name} must be a contiguous CUDA {dt} tensor of {B} rows")
+        torch.cuda.synchronize()
+        _lib.check(_lib.lib().cmoop_net_train_step_targets(self._h, _lib.ptr(X_rows), _lib.ptr(t), _lib.ptr(w), _lib.ptr(primary),
+                                                           C.c_int32(B)))
 
     def set_augment(self, augment) -> None:
         """Train-time augmentation (``AugmentConfig``) of every following train step of this net -- ``train_step``,

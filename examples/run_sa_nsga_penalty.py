@@ -24,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import synth_waveforms  # noqa: E402
-from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, PopulationEvaluator, datasets, frontend, nsga, surrogate  # noqa: E402
+from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, LossConfig, PopulationEvaluator, datasets, frontend, nsga, surrogate  # noqa: E402
 
 
 def main():
@@ -50,6 +50,12 @@ def main():
     ap.add_argument("--augment", default="", choices=["", "kws"],
                     help="train-time augmentation of every candidate's fit (AugmentConfig.preset; the reference has none): "
                          "kws = time shift <= 10 frames, 2 time masks <= 10, 2 frequency masks <= 5")
+    ap.add_argument("--mixup-alpha", type=float, default=0.0,
+                    help="mixup of every candidate's train batches with lam from Beta(alpha, alpha) (LossConfig; the reference has "
+                         "none; 0 = off, 0.2 is the usual keyword-spotting value)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing eps of the training loss (0 = off)")
+    ap.add_argument("--class-weight", default="", choices=["", "balanced"],
+                    help="balanced: weight class c by n / (classes * count_c) of the training split (Keras' class_weight=)")
     a = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -74,8 +80,13 @@ def main():
     preset = "sa_nsga_local" if a.memetic else "sa_nsga_penalty"
     # this script's features are not standardised (Q2): masked cells take the training mean, not 0.0
     augment = AugmentConfig.preset(a.augment, fill=float(Xtr.mean())) if a.augment else None
+    # the training objective only: validation loss, accuracy and FPR stay those of the sparse cross-entropy
+    loss = LossConfig(mixup_alpha=a.mixup_alpha, label_smoothing=a.label_smoothing)
+    if a.class_weight == "balanced":
+        loss = LossConfig.balanced(ytr, a.classes, mixup_alpha=a.mixup_alpha, label_smoothing=a.label_smoothing)
     ev = PopulationEvaluator(Xtr, ytr, Xva, yva, EvalConfig.preset(preset, classes=a.classes, epochs=a.epochs, seed=a.seed,
-                                                                   verbose=(rank == 0), compute=a.compute, augment=augment))
+                                                                   verbose=(rank == 0), compute=a.compute, augment=augment,
+                                                                   loss=loss if loss.enabled else None))
     calls = []
     t_start = time.perf_counter()
 

@@ -146,6 +146,73 @@ int cmoop_eval_population_aug(const cmoop_config* cfg, const cmoop_augment* aug,
                               void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
                               double* seconds, int32_t* evaluated);
 
+/* ---- soft-target training loss: mixup, label smoothing, class weights (opt-in, off by default).  BUILD-DEFINED: the
+ * reference trains on one hard label per row, unweighted, and has no counterpart; with no loss config, or a disabled one,
+ * every launch and every bit is the reference's sparse cross-entropy.
+ * VALIDATION IS NEVER CHANGED: cmoop_net_evaluate / _predict / _predict_stream, the per-epoch val_loss that EarlyStopping
+ * monitors and the final read-outs stay the plain sparse cross-entropy, so val_loss stays comparable between configs.
+ * Draws, for batch position b of a batch of B rows (the batch actually stepped: a last partial batch draws from its own
+ * size) at global train step `step` -- the counter that keys dropout and augmentation:
+ *   u(k) = rng_u32(seed, 0x5000, step, 4 b + k),  R(u, n) = ((uint64)u * n) >> 32
+ *   gate (u(0) >> 8) < floor(mixup_p * 2^24);  partner q = R(u(1), B);  lam = tab[R(u(2), 1024)]
+ *   tab[k] = (float)Q(0.5 + (k + 0.5) / 2048), Q the quantile function of Beta(alpha, alpha), evaluated in double on the
+ *            host (regularised incomplete beta by continued fraction, then bisection) and rounded once; the upper half
+ *            of the symmetric distribution, i.e. lam' = max(lam, 1 - lam): lam is in [0.5, 1], a row's own label dominates
+ *   a row is MIXED iff mixup is on (alpha > 0 and p > 0), its gate is on, q != b and lam < 1; otherwise lam := 1, q := b
+ * Row blend, mu = 1.0f - lam (exact):  x'[b][e] = lam * x[b][e] + mu * x[q][e], two fp32 products and one fp32 add, each
+ *   rounded separately; an un-mixed row is a plain copy (its bits, the sign of a zero included).  With augmentation also on,
+ *   x[b] and x[q] are the already augmented rows, each augmented with its own batch position's draws.
+ * Targets and weights, fp32, every operation rounded separately, a = y[row(b)], c = y[row(q)]:
+ *   m_j = (j == a ? lam : 0) + (j == c ? mu : 0);   t[b][j] = m_j * (float)(1 - eps) + (float)(eps / C)
+ *   w[b] = lam * cw[a] + mu * cw[c], cw = (float)class_weight[.]  (1.0f without class weights);   primary[b] = a
+ * Loss: p, pc = clip(p, 1e-7, 1 - 1e-7), S = sum_j pc_j exactly as cmoop_softmax_ce forms them; then
+ *   l_b = -sum over j with t_j > 0 of t_j (logf(pc_j) - logf(S));  loss sum += w_b * l_b;  correct += (argmax z == primary[b])
+ *   q_j = gate_j (Tsum / S - t_j / pc_j), Tsum = sum_j t_j, gate_j = (lo <= p_j <= hi);  dz_i = w_b p_i (q_i - sum_j p_j q_j) / B
+ *   (Keras' sum-over-batch-size reduction: divided by B, not by the sum of the weights).
+ * With one-hot targets and unit weights the loss sum, dz, the predictions and the correct count are bit-equal to
+ * cmoop_softmax_ce on the same logits.
+ * Domain: 0 <= label_smoothing < 1; mixup_alpha finite, 0 <= alpha <= 64; 0 <= mixup_p <= 1; class_weight NULL or
+ * n_class_weight == classes values, each finite and > 0.  A config is ENABLED iff label_smoothing > 0, or (mixup_alpha > 0
+ * and mixup_p > 0), or class_weight != NULL; a disabled config is the same as no config. */
+typedef struct cmoop_loss {
+    double label_smoothing;      /* eps, 0 <= eps < 1; 0 = off */
+    double mixup_alpha;          /* Beta(alpha, alpha); 0 = off; finite, 0 <= alpha <= 64 */
+    double mixup_p;              /* probability that a row is mixed, in [0, 1] */
+    const double* class_weight;  /* NULL = off, else n_class_weight values, each finite and > 0 */
+    int32_t n_class_weight;      /* must equal cfg.classes when class_weight != NULL */
+    int32_t reserved;
+} cmoop_loss;
+int cmoop_loss_default(cmoop_loss* loss); /* everything off: eps 0, alpha 0, p 1, no class weights */
+/* host-only: non-zero + a message naming the offending field when the config is outside the domain for `classes` classes */
+int cmoop_loss_check(const cmoop_loss* loss, int32_t classes);
+/* host-only: the lam table of Beta(alpha, alpha), 0 < alpha <= 64 */
+int cmoop_mixup_table(double alpha, float out[1024]);
+/* host-only: the draws of a batch of B rows at `step`, AFTER the MIXED rule: gate[b] = the gate bit (0 with mixup off),
+ * partner[b] = q and lam[b] of a MIXED row, else b and 1.0f.  class_weight is not read. */
+int cmoop_mixup_draws(const cmoop_loss* loss, uint32_t seed, uint32_t step, int32_t B, int32_t* gate /* [B] */,
+                      int32_t* partner /* [B] */, float* lam /* [B] */);
+/* the blend kernel alone, on the library stream: out_dev [B][T][F], x[b] = row idx_dev[row0 + b] (idx_dev NULL: row0 + b) of
+ * x_dev [.][T][F].  Any config of the domain, enabled or not (mixup off: a plain gather).  T * F < 2^30. */
+int cmoop_mixup_batch(const cmoop_loss* loss, const float* x_dev, const int32_t* idx_dev /* may be NULL */, int64_t row0, int32_t B,
+                      int32_t T, int32_t F, uint32_t seed, uint32_t step, float* out_dev);
+/* the targets kernel alone: t_dev [B][C], w_dev [B], primary_dev [B] from labels_dev through idx_dev / row0 / n_rows as
+ * cmoop_softmax_ce reads them.  Labels must lie in [0, C). */
+int cmoop_soft_targets(const cmoop_loss* loss, const int32_t* labels_dev, const int32_t* idx_dev /* may be NULL */, int64_t row0,
+                       int64_t n_rows, int32_t B, int32_t C, uint32_t seed, uint32_t step, float* t_dev, float* w_dev,
+                       int32_t* primary_dev);
+/* softmax + clipped cross-entropy of z[B][C] against the dense targets t[B][C]; w (may be NULL): row weights, 1 when NULL;
+ * primary (may be NULL): the class a row counts as correct for, NULL = arg max of its target row, first maximum.  dz, acc
+ * and preds as cmoop_softmax_ce */
+int cmoop_softmax_ce_soft(const float* z_dev, const float* t_dev, const float* w_dev /* may be NULL */,
+                          const int32_t* primary_dev /* may be NULL */, int32_t B, int32_t C, float* dz_dev /* may be NULL */,
+                          double* acc_dev, int32_t* preds_dev /* may be NULL */);
+/* cmoop_eval_population_aug with every candidate's fit trained on the soft-target loss.  loss NULL or disabled: exactly
+ * cmoop_eval_population_aug. */
+int cmoop_eval_population_ex(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_dataset* ds,
+                             const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next,
+                             void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
+                             double* seconds, int32_t* evaluated);
+
 /* host-only: does every conv layer of this candidate at `batch` rows per launch (pass max(batch, eval_batch)) stay inside
  * the kernels' 32-bit byte offsets (each activation / kernel tensor below 2^29 elements)?  Non-zero + message if not;
  * cmoop_net_create and the population calls make the same check before they allocate anything. */
@@ -331,6 +398,19 @@ int cmoop_net_set_state(cmoop_net* net, const float* params, const float* adam_m
  * _predict_stream never augment.  The loss and accuracy cmoop_net_train_metrics reports are those of the augmented batches.
  * The draws are keyed by the position in the batch and the step: another cfg.batch gives other draws. */
 int cmoop_net_set_augment(cmoop_net* net, const cmoop_augment* aug /* NULL = off */);
+/* Soft-target training loss (cmoop_loss above) of every following cmoop_net_train_step / _run_epoch / _fit step of this net
+ * (loss NULL or a disabled config: off, and the net steps bit for bit as one that never had one).  The config is copied.
+ * cmoop_net_evaluate / _predict / _predict_stream and the validation loss of cmoop_net_fit stay the sparse cross-entropy.
+ * cmoop_net_train_metrics then reports the weighted soft-target loss sum and the count of argmax z == primary. */
+int cmoop_net_set_loss(cmoop_net* net, const cmoop_loss* loss /* NULL = off */);
+/* ONE optimiser step on rows and targets given by the caller (device pointers): x_rows_dev [B][T][F], t_dev [B][classes],
+ * w_dev [B] (NULL: 1), primary_dev [B] (NULL: arg max of t).  No augmentation, no mixing and no target construction, whatever
+ * the net's augment / loss settings; dropout, Adam and the counters advance as in any step.  The hook for soft targets
+ * from elsewhere (a teacher's probabilities, for one). */
+int cmoop_net_train_step_targets(cmoop_net* net, const float* x_rows_dev, const float* t_dev, const float* w_dev,
+                                 const int32_t* primary_dev, int32_t B);
+/* floats the net has allocated for the loss: out = mixup batch buffer, t, w, primary (0: that buffer does not exist) */
+int cmoop_net_loss_buffers(cmoop_net* net, int64_t out[4]);
 /* rows the resident training tensor holds: gathered row indices are clamped into [0, n_rows) (0 = unknown, no clamp) */
 int cmoop_net_set_gather_rows(cmoop_net* net, int64_t n_rows);
 /* ONE epoch of Model.fit on the trainer's own path: epoch permutation of (seed, epoch) computed on the device when

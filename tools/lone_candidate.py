@@ -8,6 +8,9 @@ stream, fixed epochs; prints train steps/s and the evaluation's wall time.  Run 
 
 --augment NAME trains with AugmentConfig.preset(NAME): one more launch (the augment kernel) and 2 * 4 * batch * T * F bytes
 per step; compare the ms per step with and without it.
+--mixup-alpha A / --label-smoothing E / --class-weight balanced train on the soft-target loss (LossConfig): two more launches
+per step (targets, soft cross-entropy in place of the sparse one: one net launch more), and with mixup a third, the blend,
+another streaming pass over one batch.
 """
 import argparse
 import json
@@ -19,7 +22,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, PopulationEvaluator, genes as G  # noqa: E402
+from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, LossConfig, PopulationEvaluator, genes as G  # noqa: E402
 
 
 def main():
@@ -31,6 +34,9 @@ def main():
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--augment", default="", help="AugmentConfig.preset name (kws); empty: no augmentation")
     ap.add_argument("--noise-std", type=float, default=0.0, help="feature noise on top of the --augment preset")
+    ap.add_argument("--mixup-alpha", type=float, default=0.0, help="mixup with lam from Beta(alpha, alpha); 0: off")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing eps; 0: off")
+    ap.add_argument("--class-weight", default="", choices=["", "balanced"], help="balanced: n / (classes * count_c) of the train labels")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     g = torch.Generator(device="cuda")
@@ -39,8 +45,11 @@ def main():
     X = torch.randn((n_tr + n_va, 101, 40), device="cuda", generator=g)
     y = (torch.arange(n_tr + n_va, device="cuda") % 10).to(torch.int32)
     augment = AugmentConfig.preset(args.augment, noise_std=args.noise_std) if args.augment else None
+    loss = LossConfig(mixup_alpha=args.mixup_alpha, label_smoothing=args.label_smoothing)
+    if args.class_weight == "balanced":
+        loss = LossConfig.balanced(y[:n_tr], 10, mixup_alpha=args.mixup_alpha, label_smoothing=args.label_smoothing)
     cfg = EvalConfig.preset("nsga_penalty", variant=args.variant, epochs=args.epochs, early_stop=False, n_slots=1, seed=0,
-                            augment=augment)
+                            augment=augment, loss=loss if loss.enabled else None)
     ev = PopulationEvaluator(X[:n_tr], y[:n_tr], X[n_tr:], y[n_tr:], cfg)
     steps = args.epochs * ((n_tr + cfg.batch - 1) // cfg.batch)
     for gs in args.genes:
@@ -54,6 +63,7 @@ def main():
             best = min(best, time.perf_counter() - t0)
         fl = G.eval_flops(gene, G.VARIANT_NAMES[args.variant], 10, 101, 40, n_tr, n_va, args.epochs, 1)
         print(json.dumps({"gene": gene, "variant": args.variant, "augment": args.augment or None, "noise_std": args.noise_std,
+                          "mixup_alpha": args.mixup_alpha, "label_smoothing": args.label_smoothing, "class_weight": args.class_weight or None,
                           "train_steps": steps, "wall_s": round(best, 4),
                           "steps_per_s": round(steps / best, 1), "ms_per_step_incl_val": round(best / steps * 1e3, 4),
                           "tflops": round(fl / best / 1e12, 2)}), flush=True)
