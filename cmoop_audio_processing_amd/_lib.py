@@ -133,6 +133,17 @@ ELEM_PROTOTYPES = {
 }
 
 
+#: prototypes of the dense-head entry points that launch dense.hip as a train step does (include/cmoop.h)
+_U32 = C.c_uint32
+DENSE_PROTOTYPES = {
+    "cmoop_dense_fwd_ex": [_V] * 4 + [_I32] * 5 + [_F64, _U32, _I32, _U32, _V],
+    "cmoop_dense_bwd_ex": [_V] * 6 + [_I32] * 4 + [_F64, _I32, _I32],
+}
+
+#: CMOOP_GEMM_* (include/cmoop.h)
+GEMM_DEFAULT, GEMM_FP32, GEMM_BF16X3, GEMM_BF16 = 0, 1, 2, 3
+
+
 def build(verbose: bool = False) -> str:
     """Compile libcmoop_hip.so for gfx950 in-tree (make; hipcc cross-compiles on CPU-only hosts)."""
     jobs = str(min(8, os.cpu_count() or 1))
@@ -172,7 +183,7 @@ def lib():
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
         for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(PCEN_PROTOTYPES.items()) + \
-                list(ELEM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()):
+                list(ELEM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         _lib = L
         return L

@@ -1156,6 +1156,47 @@ int cmoop_dense_bwd(const float* x, const float* w, const float* dy, float* dx, 
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
+// CMOOP_GEMM_* of a kernel-level dense call -> the GemmMode a Net would hold for it
+static int dense_ex_mode(int32_t gemm_mode) {
+    CMOOP_REQUIRE(gemm_mode == CMOOP_GEMM_DEFAULT || gemm_mode == CMOOP_GEMM_FP32 || gemm_mode == CMOOP_GEMM_BF16X3 ||
+                      gemm_mode == CMOOP_GEMM_BF16, "bad gemm_mode");
+    if (gemm_mode == CMOOP_GEMM_DEFAULT) return gemm_mode_default();
+    return gemm_mode == CMOOP_GEMM_FP32 ? (int)GEMM_FP32 : (int)gemm_mode;
+}
+int cmoop_dense_fwd_ex(const float* x, const float* w, const float* bias, float* y, int32_t M, int32_t N, int32_t K, int32_t relu,
+                       int32_t gemm_mode, double dropout_rate, uint32_t seed, int32_t dropout_layer, uint32_t step,
+                       const void* step_state_dev) {
+    return guard([&] {
+        const int mode = dense_ex_mode(gemm_mode);
+        const DropoutParams dp = dropout_params(dropout_rate);
+        const bool drop = dropout_rate > 0.0;
+        CMOOP_REQUIRE(!drop || dropout_layer >= 0, "dense_fwd_ex: dropout_layer >= 0");
+        static_assert(sizeof(StepState) == 16, "cmoop_dense_fwd_ex documents a 16-byte step state");
+        const StepState* st = drop ? static_cast<const StepState*>(step_state_dev) : nullptr;
+        const uint32_t drop_stream = drop ? DropoutParams::stream(dropout_layer) : 0u;
+        hipStream_t s = lib_stream();
+        // the argument list of Net::forward's OP_DENSE launch (the host prefix is passed in both forms, as there)
+        launch_dense_fwd(x, w, bias, y, M, N, K, relu, drop ? 1 : 0, drop ? rng_prefix(seed, drop_stream, step) : 0u, dp.thr,
+                         dp.keep_scale, mode, s, st, seed, drop_stream);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_dense_bwd_ex(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, int32_t M, int32_t N,
+                       int32_t K, int32_t mask_relu, double mask_scale, int32_t gemm_mode, int32_t merged) {
+    return guard([&] {
+        const int mode = dense_ex_mode(gemm_mode);
+        CMOOP_REQUIRE(dx != nullptr, "dense_bwd_ex: dx is NULL");
+        hipStream_t s = lib_stream();
+        const float* mask = mask_relu ? x : nullptr;
+        if (merged) {
+            launch_dense_bwd(x, dy, w, dw, db, dx, M, N, K, mask, (float)mask_scale, mode, s);
+        } else {
+            launch_dense_wgrad(x, dy, dw, db, M, N, K, mode, s);
+            launch_dense_dgrad(dy, w, dx, M, N, K, mask, (float)mask_scale, mode, s);
+        }
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
 int cmoop_maxpool_fwd(const float* x, float* y, uint8_t* arg, int32_t B, int32_t H, int32_t W, int32_t C) {
     return guard([&] {
         hipStream_t s = lib_stream();

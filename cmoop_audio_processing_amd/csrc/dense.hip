@@ -141,7 +141,7 @@ __device__ __forceinline__ void dense_dgrad_body(const int bid, float* red, cons
     }
 }
 
-// dW[n][k] = sum_m dY[m][n] * X[m][k];  dB[n] = sum_m dY[m][n] (by the k-tile-0 workgroups)
+// the data gradient alone (dense_dgrad_body): one workgroup per 16x16 tile of dX, cdiv(M, 16) * (K / 16) of them
 __global__ __launch_bounds__(256) void dense_dgrad_kernel(const float* __restrict__ dY, const float* __restrict__ W,
                                                           float* __restrict__ dX, int M, int N, int K,
                                                           const float* __restrict__ mask, float scale, int bf16) {

@@ -22,6 +22,17 @@ struct NetConfig {
     double lr = 1e-3, beta1 = 0.9, beta2 = 0.999, adam_eps = 1e-7, bn_eps = 1e-3, bn_momentum = 0.99, dropout = 0.3;
 };
 
+// Inverted dropout of a Dense+ReLU layer as dense_fwd_kernel takes it: element (row, col) of fc layer `layer` is kept iff
+// its 24-bit draw from stream(layer) is >= thr, kept values are multiplied by keep_scale (and so is the layer's input
+// gradient).  THE place of these three values: Net::forward, plan_net's mask scales and the kernel-level entry point
+// cmoop_dense_fwd_ex all take them from here.
+struct DropoutParams {
+    uint32_t thr;
+    float keep_scale;
+    static uint32_t stream(int layer) { return STREAM_DROPOUT + (uint32_t)layer; }
+};
+DropoutParams dropout_params(double rate);
+
 struct Dataset {
     const float* x_train = nullptr; const int32_t* y_train = nullptr; int64_t n_train = 0;
     const float* x_val = nullptr;   const int32_t* y_val = nullptr;   int64_t n_val = 0;

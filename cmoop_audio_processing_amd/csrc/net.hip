@@ -22,6 +22,11 @@ void validate_gene(const int32_t g[6]) {
     CMOOP_REQUIRE(ok, "gene outside the search space (filters{16,32,64}, kernel{3,5}, bn{0,1}, res{1..3}, fc{1..4}, dropout{0,1})");
 }
 
+DropoutParams dropout_params(double rate) {
+    CMOOP_REQUIRE(rate >= 0.0 && rate < 1.0, "dropout must be in [0,1)");
+    return DropoutParams{(uint32_t)(rate * 16777216.0), (float)(1.0 / (1.0 - rate))};
+}
+
 int64_t param_count(const int32_t g[6], int variant, int classes) {
     validate_gene(g);
     const int64_t f = g[0], kk = (int64_t)g[1] * g[1], bn = g[2], R = g[3], fc = g[4];
@@ -295,7 +300,7 @@ NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F) {
         ops.push_back(op);
         x = op.out;
     }
-    const float keep_scale = (float)(1.0 / (1.0 - cfg.dropout));
+    const float keep_scale = dropout_params(cfg.dropout).keep_scale;
     for (int i = 0; i < fc; ++i) {
         const int in_relu = i > 0;
         const float ms = (in_relu && dr) ? keep_scale : 1.f;
@@ -704,11 +709,11 @@ void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool 
         }
         case OP_DENSE: {
             const bool drop = train && op.dropout_layer >= 0;
+            const DropoutParams dp = dropout_params(cfg_.dropout);
+            const uint32_t drop_stream = drop ? DropoutParams::stream(op.dropout_layer) : 0u;
             launch_dense_fwd(acts_[op.in].data, params_ + op.w_off, params_ + op.b_off, acts_[op.out].data, B, op.Cout, op.Cin,
-                             op.relu, drop ? 1 : 0,
-                             drop ? rng_prefix(seed_, STREAM_DROPOUT + (uint32_t)op.dropout_layer, (uint32_t)step_) : 0u,
-                             (uint32_t)(cfg_.dropout * 16777216.0), (float)(1.0 / (1.0 - cfg_.dropout)), op.gemm_mode, stream_,
-                             drop ? st : nullptr, seed_, drop ? STREAM_DROPOUT + (uint32_t)op.dropout_layer : 0u);
+                             op.relu, drop ? 1 : 0, drop ? rng_prefix(seed_, drop_stream, (uint32_t)step_) : 0u, dp.thr,
+                             dp.keep_scale, op.gemm_mode, stream_, drop ? st : nullptr, seed_, drop_stream);
             break;
         }
         case OP_BN: {

@@ -39,6 +39,7 @@ extern "C" {
  * BF16X3 and BF16 are opt-in: BF16X3 = fp32 operands split exactly into 3 bf16, six bf16 MFMA terms
  * (fp32-accurate); BF16 = operands rounded to bf16, fp32 accumulation (BASELINE.json configs[4] "bf16 train"). */
 #define CMOOP_GEMM_DEFAULT 0 /* exact fp32 unless the environment variable CMOOP_GEMM_MODE=bf16x3|bf16 overrides */
+#define CMOOP_GEMM_FP32 1  /* exact fp32 whatever the environment says: the kernel-level cmoop_dense_*_ex calls only */
 #define CMOOP_GEMM_BF16X3 2
 #define CMOOP_GEMM_BF16 3
 
@@ -456,6 +457,19 @@ int cmoop_dense_fwd(const float* x_dev, const float* w_dev, const float* bias_de
                     int32_t relu);
 int cmoop_dense_bwd(const float* x_dev, const float* w_dev, const float* dy_dev, float* dx_dev, float* dw_dev, float* db_dev,
                     int32_t M, int32_t N, int32_t K, int32_t mask_relu);
+/* The same kernels launched as a train step launches them (tests).  gemm_mode: CMOOP_GEMM_* (FP32 and BF16 do not depend
+ * on the environment).  dropout_rate in [0,1), 0: no dropout; else the inverted-dropout epilogue of fc layer dropout_layer:
+ * element (m, n) is kept, and multiplied by (float)(1 / (1 - rate)), iff the 24-bit draw of (seed, 0x2000 + dropout_layer,
+ * step, m N + n) is >= (uint32_t)(rate 2^24).  step_state_dev == NULL: step is the host argument.  Else it points to the
+ * 16-byte device step state {int64 row0; uint32 step; uint32 iter} of a fit, the kernel reads step from there and the host
+ * argument is ignored. */
+int cmoop_dense_fwd_ex(const float* x_dev, const float* w_dev, const float* bias_dev, float* y_dev, int32_t M, int32_t N, int32_t K,
+                       int32_t relu, int32_t gemm_mode, double dropout_rate, uint32_t seed, int32_t dropout_layer, uint32_t step,
+                       const void* step_state_dev);
+/* dx = mask_relu ? (x > 0 ? dx mask_scale : 0) : dx (ReLU / dropout backward of the layer's input); merged != 0: the one
+ * launch of the trainer's default backward, 0: weight gradient and data gradient as two launches */
+int cmoop_dense_bwd_ex(const float* x_dev, const float* w_dev, const float* dy_dev, float* dx_dev, float* dw_dev, float* db_dev,
+                       int32_t M, int32_t N, int32_t K, int32_t mask_relu, double mask_scale, int32_t gemm_mode, int32_t merged);
 int cmoop_maxpool_fwd(const float* x_dev, float* y_dev, uint8_t* arg_dev, int32_t B, int32_t H, int32_t W, int32_t C);
 int cmoop_maxpool_bwd(const float* dy_dev, const uint8_t* arg_dev, const float* y_dev, float* dx_dev, int32_t B, int32_t H,
                       int32_t W, int32_t C, int32_t mask_y_pos);
