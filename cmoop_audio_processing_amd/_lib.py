@@ -140,6 +140,15 @@ DENSE_PROTOTYPES = {
     "cmoop_dense_bwd_ex": [_V] * 6 + [_I32] * 4 + [_F64, _I32, _I32],
 }
 
+#: prototypes of the depthwise-convolution entry points of the separable layers (include/cmoop.h)
+DWCONV_PROTOTYPES = {
+    "cmoop_dwconv_fwd": [_V] * 3 + [_I32] * 5,
+    "cmoop_dwconv_bwd": [_V] * 5 + [_I32] * 6,
+    "cmoop_dwconv_wgrad_slices": [_I32] * 5 + [_V],
+    "cmoop_dwconv_time": [_I32] + [_V] * 4 + [_I32] * 6 + [_V],
+    "cmoop_plan_dwconvs": [_V, _I32, _I32, _I32, _V, _I32, _V],
+}
+
 #: CMOOP_GEMM_* (include/cmoop.h)
 GEMM_DEFAULT, GEMM_FP32, GEMM_BF16X3, GEMM_BF16 = 0, 1, 2, 3
 
@@ -183,7 +192,7 @@ def lib():
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
         for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(PCEN_PROTOTYPES.items()) + \
-                list(ELEM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()):
+                list(ELEM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(DWCONV_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         _lib = L
         return L
@@ -214,6 +223,23 @@ def plan_convs(gene, variant, T, F):
     check(lib().cmoop_plan_convs(g, C.c_int32(variant), C.c_int32(T), C.c_int32(F), rows, C.c_int32(cap), C.byref(n)))
     assert n.value <= cap
     return [tuple(rows[7 * i:7 * i + 7]) for i in range(n.value)]
+
+
+def plan_dwconvs(gene, variant, T, F):
+    """[(H, W, C, KS)] of the depthwise layers of a candidate (variants A_ds / B_ds), forward order (host-only); their
+    pointwise halves are the KS = 1, stride = 1 rows of plan_convs."""
+    g, n, cap = (C.c_int32 * 6)(*gene), C.c_int32(), 16
+    rows = (C.c_int32 * (4 * cap))()
+    check(lib().cmoop_plan_dwconvs(g, C.c_int32(variant), C.c_int32(T), C.c_int32(F), rows, C.c_int32(cap), C.byref(n)))
+    assert n.value <= cap
+    return [tuple(rows[4 * i:4 * i + 4]) for i in range(n.value)]
+
+
+def dwconv_wgrad_slices(B, H, W, Cn, KS):
+    """Row-run slices of the depthwise weight gradient at this shape (host-only)."""
+    out = C.c_int32()
+    check(lib().cmoop_dwconv_wgrad_slices(B, H, W, Cn, KS, C.byref(out)))
+    return int(out.value)
 
 
 def net_launch_plan(gene, config, T, F, B, train):

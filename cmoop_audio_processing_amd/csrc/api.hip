@@ -109,7 +109,7 @@ static NetConfig to_cfg(const cmoop_config* c) {
     n.gemm_mode = c->gemm_mode == CMOOP_GEMM_DEFAULT ? gemm_mode_default() : c->gemm_mode;
     n.lr = c->lr; n.beta1 = c->beta1; n.beta2 = c->beta2; n.adam_eps = c->adam_eps; n.bn_eps = c->bn_eps;
     n.bn_momentum = c->bn_momentum; n.dropout = c->dropout;
-    CMOOP_REQUIRE(n.variant == 0 || n.variant == 1, "variant must be CMOOP_VARIANT_A or _B");
+    CMOOP_REQUIRE(n.variant >= 0 && n.variant <= 3, "variant must be CMOOP_VARIANT_A, _B, _A_DS or _B_DS");
     CMOOP_REQUIRE(n.fpr_variant >= 0 && n.fpr_variant <= 2, "bad fpr_variant");
     CMOOP_REQUIRE(n.epochs >= 0 && n.patience >= 0 && n.batch >= 1 && n.eval_batch >= 1, "bad epochs/patience/batch");
     CMOOP_REQUIRE(n.dropout >= 0.0 && n.dropout < 1.0, "dropout must be in [0,1)");
@@ -436,7 +436,7 @@ int cmoop_augment_batch(const cmoop_augment* aug, const float* x_dev, const int3
 
 int cmoop_plan_check(const int32_t gene[6], int32_t variant, int32_t T, int32_t F, int32_t batch) {
     return guard([&] {
-        CMOOP_REQUIRE(gene && (variant == 0 || variant == 1) && T >= 1 && F >= 1 && batch >= 1, "plan_check: bad arguments");
+        CMOOP_REQUIRE(gene && (variant >= 0 && variant <= 3) && T >= 1 && F >= 1 && batch >= 1, "plan_check: bad arguments");
         check_plan_ranges(gene, variant, T, F, batch);
     });
 }
@@ -457,7 +457,7 @@ int cmoop_conv_launch_plan(int32_t op, int32_t B, int32_t H, int32_t W, int32_t 
 
 int cmoop_plan_convs(const int32_t gene[6], int32_t variant, int32_t T, int32_t F, int32_t* layers, int32_t cap, int32_t* count) {
     return guard([&] {
-        CMOOP_REQUIRE(gene && count && (variant == 0 || variant == 1) && T >= 1 && F >= 1 && cap >= 0 && (layers || cap == 0), "plan_convs: bad arguments");
+        CMOOP_REQUIRE(gene && count && (variant >= 0 && variant <= 3) && T >= 1 && F >= 1 && cap >= 0 && (layers || cap == 0), "plan_convs: bad arguments");
         NetConfig cfg;
         cfg.variant = variant;
         int n = 0;
@@ -470,6 +470,31 @@ int cmoop_plan_convs(const int32_t gene[6], int32_t variant, int32_t T, int32_t 
             ++n;
         }
         *count = n;
+    });
+}
+
+int cmoop_plan_dwconvs(const int32_t gene[6], int32_t variant, int32_t T, int32_t F, int32_t* layers, int32_t cap, int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(gene && count && (variant >= 0 && variant <= 3) && T >= 1 && F >= 1 && cap >= 0 && (layers || cap == 0), "plan_dwconvs: bad arguments");
+        NetConfig cfg;
+        cfg.variant = variant;
+        int n = 0;
+        for (const Op& op : plan_net(gene, cfg, T, F).ops) {
+            if (op.kind != OP_DWCONV) continue;
+            if (n < cap) {
+                const int32_t row[4] = {op.H, op.W, op.Cin, op.KS};
+                std::memcpy(layers + 4 * n, row, sizeof(row));
+            }
+            ++n;
+        }
+        *count = n;
+    });
+}
+
+int cmoop_dwconv_wgrad_slices(int32_t B, int32_t H, int32_t W, int32_t C, int32_t KS, int32_t* out) {
+    return guard([&] {
+        CMOOP_REQUIRE(out, "dwconv_wgrad_slices: NULL output");
+        *out = dwconv_wgrad_slices(B, H, W, C, KS);
     });
 }
 
@@ -1022,6 +1047,50 @@ int cmoop_conv_bwd(const float* x, const float* w, const float* dy, float* dx, f
             L.dgrad(dy, w, dx, B, mask_relu ? x : nullptr, 1.f, accumulate, false, buf, GEMM_DEFAULT, s, &hook);
         }
         CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+// ---- depthwise half of a separable layer, launched as Net::forward / Net::backward launch it ------------------------------
+int cmoop_dwconv_fwd(const float* x, const float* w, float* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t KS) {
+    return guard([&] {
+        CMOOP_REQUIRE(x && w && y, "dwconv_fwd: NULL buffer");
+        hipStream_t s = lib_stream();
+        launch_dwconv_fwd(x, w, y, B, H, W, C, KS, 0, nullptr, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_dwconv_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, int32_t B, int32_t H, int32_t W,
+                     int32_t C, int32_t KS, int32_t mask_relu) {
+    return guard([&] {
+        CMOOP_REQUIRE(x && w && dy && dw, "dwconv_bwd: NULL buffer");
+        hipStream_t s = lib_stream();
+        Scratch m(s);
+        // the trainer's order: weight-gradient slabs, data gradient, then the fixed-order slice sum (the optimiser launch's order)
+        const int S = dwconv_wgrad_slices(B, H, W, C, KS);
+        const int64_t per = (int64_t)KS * KS * C;
+        float* P = m.floats((size_t)S * per);
+        launch_dwconv_wgrad(x, dy, P, B, H, W, C, KS, s);
+        if (dx) launch_dwconv_fwd(dy, w, dx, B, H, W, C, KS, 1, mask_relu ? x : nullptr, s);
+        launch_reduce_slices(P, dw, S, per, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_dwconv_time(int32_t mode, const float* x, const float* w, const float* dy, float* out, int32_t B, int32_t H, int32_t W,
+                      int32_t C, int32_t KS, int32_t iters, double* avg_ms) {
+    // mode 0: forward (out = y); 1: data gradient with the x > 0 mask (out = dx); 2: weight-gradient kernel alone (partials
+    // into a scratch buffer; out unused)
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && mode >= 0 && mode <= 2 && iters >= 1, "dwconv_time: bad arguments");
+        hipStream_t s = lib_stream();
+        Scratch m(s);
+        float* P = mode == 2 ? m.floats((size_t)dwconv_wgrad_slices(B, H, W, C, KS) * KS * KS * C) : nullptr;
+        *avg_ms = time_launches(s, iters, [&] {
+            if (mode == 0) launch_dwconv_fwd(x, w, out, B, H, W, C, KS, 0, nullptr, s);
+            else if (mode == 1) launch_dwconv_fwd(dy, w, out, B, H, W, C, KS, 1, x, s);
+            else launch_dwconv_wgrad(x, dy, P, B, H, W, C, KS, s);
+        });
     });
 }
 

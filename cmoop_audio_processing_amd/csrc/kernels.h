@@ -158,6 +158,15 @@ void launch_dense_bwd(const float* X, const float* dY, const float* W, float* dW
 void launch_conv1_fwd(const float* X, const int32_t* idx, int64_t row0, const float* Wt, const float* bias,
                       float* Y, int B, int H, int W, int Cout, int KS, int relu, hipStream_t s, const StepState* st = nullptr,
                       int64_t n_rows = 0, float* stats = nullptr, int* stats_blocks = nullptr);
+// Depthwise k x k convolution of the separable layers (dwconv.hip): SAME, stride 1, depth multiplier 1, no bias; NHWC fp32
+// in every gemm_mode.  C a power of two in 16..512, KS in {3, 5}, B H W C < 2^29.  Wt [KS][KS][C].
+// flip: the taps reversed -- the data gradient when X = dY; mask (optional, output-shaped): Y = mask > 0 ? Y : 0
+void launch_dwconv_fwd(const float* X, const float* Wt, float* Y, int B, int H, int W, int C, int KS, int flip, const float* mask,
+                       hipStream_t s);
+// row-run slices of the weight gradient: a function of the shape alone, NOT monotone in B
+int dwconv_wgrad_slices(int B, int H, int W, int C, int KS);
+// P[slice][KS][KS][C]: per-slice partial weight gradients (no atomics); their fixed-order sum is the caller's
+void launch_dwconv_wgrad(const float* X, const float* dY, float* P, int B, int H, int W, int C, int KS, hipStream_t s);
 int conv1_wgrad_blocks(int B, int H, int W);
 // P[blk][Cout*(KS*KS) + Cout]: per-block partial kernel grads then bias grads
 void launch_conv1_wgrad(const float* X, const int32_t* idx, int64_t row0, const float* dY, float* P,

@@ -39,6 +39,9 @@ struct Dataset {
     int T = 0, F = 0;
 };
 
+// topologies: 0 = A, 1 = B, 2 = A_ds, 3 = B_ds (A / B with every k x k stride-1 conv of C_in >= 16 made depthwise-separable)
+inline bool variant_is_a(int variant) { return (variant & 1) == 0; }
+inline bool variant_is_ds(int variant) { return variant >= 2; }
 // host-side closed forms (bit-exact twins of genes.py)
 int64_t param_count(const int32_t g[6], int variant, int classes);
 double fwd_flops_per_sample(const int32_t g[6], int variant, int classes, int T, int F);
@@ -142,7 +145,8 @@ struct Act {
     size_t per_sample() const { return (size_t)H * W * C; }
 };
 
-enum OpKind { OP_CONV1, OP_CONV, OP_BN, OP_POOL, OP_ADDRELU, OP_GAP, OP_DENSE };
+// OP_DWCONV: the depthwise half of a separable layer (topologies A_ds / B_ds); its pointwise half is an OP_CONV with KS = 1
+enum OpKind { OP_CONV1, OP_CONV, OP_BN, OP_POOL, OP_ADDRELU, OP_GAP, OP_DENSE, OP_DWCONV };
 
 struct Op {
     OpKind kind;
@@ -159,7 +163,7 @@ struct Op {
     void* rowtab_d = nullptr;  // conv: row table of the layer's dgrad geometry (dY as input, flipped padding), train batch
     int rowtab_d_rows = 0;
     int64_t w_off = 0, b_off = 0, wd_off = -1;   // wd_off: this layer's slice of the flip-transposed copy (dgrad operand)
-    int64_t slab_off = -1;     // conv / first conv: this layer's weight-gradient slabs in the candidate's slab arena
+    int64_t slab_off = -1;     // conv / first conv / depthwise: this layer's weight-gradient slabs in the candidate's slab arena
     size_t slab_floats = 0;    // (kept until the optimiser launch sums them), sized for the worst train batch
     int tensor_index = 0;   // canonical index of the kernel tensor (RNG init stream)
     // bn
@@ -332,7 +336,7 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
                          const AugmentCfg* aug = nullptr, const LossCfg* loss = nullptr);
 // host-only: every implicit-GEMM conv geometry of a candidate at batch B (a walk of plan_net's ops); throws
-// through igemm_check_range when a layer is beyond the kernels' 32-bit byte offsets
+// through igemm_check_range when a layer is beyond the kernels' 32-bit byte offsets (depthwise activations: 2^29 elements)
 void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
 // the population loop (compute_objectives_and_constraints, nsga_penalty.py:418-442): n_slots
 // candidates in flight on their own HIP streams, longest-first

@@ -29,14 +29,18 @@ DropoutParams dropout_params(double rate) {
 
 int64_t param_count(const int32_t g[6], int variant, int classes) {
     validate_gene(g);
+    CMOOP_REQUIRE(variant >= 0 && variant <= 3, "variant must be CMOOP_VARIANT_A, _B, _A_DS or _B_DS");
     const int64_t f = g[0], kk = (int64_t)g[1] * g[1], bn = g[2], R = g[3], fc = g[4];
+    const bool ds = variant_is_ds(variant);
+    // a k x k stride-1 conv with C_in >= 16: full, or depthwise [k][k][cin] + pointwise [cout][cin] + bias
+    auto convp = [&](int64_t cin, int64_t cout) { return ds ? kk * cin + cin * cout + cout : kk * cin * cout + cout; };
     int64_t p, c = f;
-    if (variant == 0) {
-        p = (kk * f + f) + (kk * f * f + f) + (bn ? 8 * f : 0);
+    if (variant_is_a(variant)) {
+        p = (kk * f + f) + convp(f, f) + (bn ? 8 * f : 0);
         for (int r = 0; r < R; ++r) {
             p += c * 2 * c + 2 * c;
-            p += kk * c * 2 * c + 2 * c;
-            p += kk * (2 * c) * (2 * c) + 2 * c;
+            p += convp(c, 2 * c);
+            p += convp(2 * c, 2 * c);
             p += bn ? 16 * c : 0;
             c *= 2;
         }
@@ -44,7 +48,7 @@ int64_t param_count(const int32_t g[6], int variant, int classes) {
         p = (kk * f + f) + (bn ? 4 * f : 0);
         for (int r = 0; r < R; ++r) {
             p += c * 2 * c + 2 * c;
-            p += kk * c * 2 * c + 2 * c;
+            p += convp(c, 2 * c);
             p += bn ? 8 * c : 0;
             c *= 2;
         }
@@ -61,17 +65,20 @@ int64_t param_count(const int32_t g[6], int variant, int classes) {
 
 double fwd_flops_per_sample(const int32_t g[6], int variant, int classes, int T, int F) {
     validate_gene(g);
+    CMOOP_REQUIRE(variant >= 0 && variant <= 3, "variant must be CMOOP_VARIANT_A, _B, _A_DS or _B_DS");
     const double f = g[0], kk = (double)g[1] * g[1];
     const int R = g[3], fc = g[4];
+    const bool A = variant_is_a(variant), ds = variant_is_ds(variant);
+    auto convf = [&](double hw, double cin, double cout) { return ds ? 2.0 * hw * kk * cin + 2.0 * hw * cin * cout : 2.0 * hw * kk * cin * cout; };
     double fl = 2.0 * T * F * kk * f;
-    if (variant == 0) fl += 2.0 * T * F * kk * f * f;
+    if (A) fl += convf((double)T * F, f, f);
     int h = (T + 1) / 2, w = (F + 1) / 2;
     double c = f;
     for (int r = 0; r < R; ++r) {
         const int h2 = (h + 1) / 2, w2 = (w + 1) / 2;
         fl += 2.0 * h2 * w2 * c * 2 * c;
-        fl += 2.0 * h * w * kk * c * 2 * c;
-        if (variant == 0) fl += 2.0 * h * w * kk * 2 * c * 2 * c;
+        fl += convf((double)h * w, c, 2 * c);
+        if (A) fl += convf((double)h * w, 2 * c, 2 * c);
         h = h2; w = w2; c *= 2;
     }
     double prev = c;
@@ -199,7 +206,8 @@ Net::~Net() {
 NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F) {
     validate_gene(gene);
     const int f = gene[0], k = gene[1], bn = gene[2], R = gene[3], fc = gene[4], dr = gene[5];
-    const bool A = cfg.variant == 0;
+    CMOOP_REQUIRE(cfg.variant >= 0 && cfg.variant <= 3, "variant must be CMOOP_VARIANT_A, _B, _A_DS or _B_DS");
+    const bool A = variant_is_a(cfg.variant), ds = variant_is_ds(cfg.variant);
     NetPlan plan;
     std::vector<Act>& acts = plan.acts;
     std::vector<Op>& ops = plan.ops;
@@ -227,6 +235,21 @@ NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F) {
         op.out = new_act((ia.H + stride - 1) / stride, (ia.W + stride - 1) / stride, Cout);
         ops.push_back(op);
         return op.out;
+    };
+    // a k x k stride-1 conv of the block body: full, or (A_ds / B_ds) depthwise k x k (no bias, no activation; its data
+    // gradient carries the x > 0 mask of the conv it replaces and never accumulates) + pointwise 1 x 1 (bias, ReLU, and
+    // the "feeds a BatchNorm" role).  Canonical tensors: depthwise kernel [k][k][C_in], pointwise kernel, bias
+    auto add_sepconv = [&](int in, int Cout, int KS, int relu, int in_is_relu) {
+        if (!ds) return add_conv(OP_CONV, in, Cout, KS, 1, relu, in_is_relu, 1.f, 0);
+        Op op; op.kind = OP_DWCONV; op.in = in;
+        const Act ia = acts[in];
+        op.KS = KS; op.stride = 1; op.Cin = op.Cout = ia.C; op.H = ia.H; op.W = ia.W; op.in_is_relu = in_is_relu;
+        op.w_off = op.b_off = off; op.tensor_index = tindex;
+        off += (int64_t)KS * KS * ia.C;
+        tindex += 1;
+        op.out = new_act(ia.H, ia.W, ia.C);
+        ops.push_back(op);
+        return add_conv(OP_CONV, op.out, Cout, 1, 1, relu, 0, 1.f, 0);
     };
     auto add_bn = [&](int in, int relu_after, int mask_in_pos) {
         if (!ops.empty() && (ops.back().kind == OP_CONV || ops.back().kind == OP_CONV1) && ops.back().out == in) ops.back().feeds_bn = 1;
@@ -262,7 +285,7 @@ NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F) {
     if (A) {   // nsga_penalty.py:255-265
         x = add_conv(OP_CONV1, 0, f, k, 1, !bn, 0, 1.f, 0);
         if (bn) x = add_bn(x, 1, 0);
-        x = add_conv(OP_CONV, x, f, k, 1, !bn, 1, 1.f, 0);
+        x = add_sepconv(x, f, k, !bn, 1);
         if (bn) x = add_bn(x, 1, 0);
         x = add_pool(x, 0);
     } else {   // sa_nsga_penalty.py:151-153 (ReLU fused into the conv, BN after it)
@@ -278,13 +301,13 @@ NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F) {
         const int skip = add_conv(OP_CONV, x, 2 * c, 1, 2, 0, in_relu, 1.f, 1);
         int y;
         if (A) {   // nsga_penalty.py:276-301
-            y = add_conv(OP_CONV, x, 2 * c, k, 1, !bn, in_relu, 1.f, 0);
+            y = add_sepconv(x, 2 * c, k, !bn, in_relu);
             if (bn) y = add_bn(y, 1, 0);
-            y = add_conv(OP_CONV, y, 2 * c, k, 1, 0, 1, 1.f, 0);
+            y = add_sepconv(y, 2 * c, k, 0, 1);
             if (bn) y = add_bn(y, 0, 0);
             y = add_pool(y, 0);
         } else {   // sa_nsga_penalty.py:155-165
-            y = add_conv(OP_CONV, x, 2 * c, k, 1, 1, in_relu, 1.f, 0);
+            y = add_sepconv(x, 2 * c, k, 1, in_relu);
             if (bn) y = add_bn(y, 0, 1);
             y = add_pool(y, !bn);
         }
@@ -374,6 +397,12 @@ void Net::build_plan() {
         if (op.kind == OP_BN) {
             launch_fill(params_ + op.gamma_off, 1.f, op.Cout, stream_);
             launch_fill(params_ + op.mv_off, 1.f, op.Cout, stream_);
+        } else if (op.kind == OP_DWCONV) {
+            // Keras' fans of a depthwise kernel (k, k, C, 1): fan_in = k*k*C, fan_out = k*k
+            const double kk = (double)op.KS * op.KS;
+            const float scale = (float)(std::sqrt(6.0 / (kk * op.Cin + kk)) / 16777216.0);
+            launch_glorot_init(params_ + op.w_off, (int64_t)op.KS * op.KS * op.Cin, rng_prefix(seed_, STREAM_INIT + (uint32_t)op.tensor_index, 0),
+                               scale, stream_);
         } else if (op.kind == OP_CONV1 || op.kind == OP_CONV || op.kind == OP_DENSE) {
             // glorot_uniform: limit = sqrt(6 / (fan_in + fan_out)), fan = k*k*C  (oracle/rng.py twin)
             const double fan_in = (double)op.KS * op.KS * op.Cin, fan_out = (double)op.KS * op.KS * op.Cout;
@@ -420,6 +449,13 @@ void Net::build_plan() {
             op.slab_off = (int64_t)wgrad_ws_floats_;
             wgrad_ws_floats_ += (op.slab_floats + 3) / 4 * 4;
             red_ws_floats_ = std::max(red_ws_floats_, (size_t)colreduce_blocks((int64_t)Bmax_ * T_ * F_, op.Cout) * 2 * op.Cout + 2 * op.Cout);
+        }
+        if (op.kind == OP_DWCONV) {   // slice counts are not monotone in the batch: the worst train batch
+            const size_t per = (size_t)op.KS * op.KS * op.Cin;
+            for (int b = 1; b <= cfg_.batch; ++b)
+                op.slab_floats = std::max(op.slab_floats, per * dwconv_wgrad_slices(b, op.H, op.W, op.Cin, op.KS));
+            op.slab_off = (int64_t)wgrad_ws_floats_;
+            wgrad_ws_floats_ += (op.slab_floats + 3) / 4 * 4;
         }
         if (op.kind == OP_BN) {
             red_ws_floats_ = std::max(red_ws_floats_, stats_partials_floats((int64_t)Bmax_ * acts_[op.in].H * acts_[op.in].W, op.Cout));
@@ -707,6 +743,9 @@ void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool 
                                                     train && op.feeds_bn, buffers_of(op), stream_, this);
             break;
         }
+        case OP_DWCONV:
+            launch_dwconv_fwd(acts_[op.in].data, params_ + op.w_off, acts_[op.out].data, B, op.H, op.W, op.Cin, op.KS, 0, nullptr, stream_);
+            break;
         case OP_DENSE: {
             const bool drop = train && op.dropout_layer >= 0;
             const DropoutParams dp = dropout_params(cfg_.dropout);
@@ -799,6 +838,20 @@ void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, cons
             if (sg.slab) slab_segs_.push_back(sg);
             L.dgrad(dY, params_ + op.w_off, ia.grad, B, op.in_is_relu ? ia.data : nullptr, op.in_mask_scale, op.dgrad_accumulate,
                     true, buf, op.gemm_mode, stream_, this);
+            break;
+        }
+        case OP_DWCONV: {
+            const float* dY = acts_[op.out].grad;
+            Act& ia = acts_[op.in];
+            launch_dwconv_wgrad(ia.data, dY, wgrad_ws_ + op.slab_off, B, op.H, op.W, op.Cin, op.KS, stream_);
+            AdamSeg sg;
+            sg.off = op.w_off;
+            sg.n = sg.stride = (int64_t)op.KS * op.KS * op.Cin;
+            sg.slab = wgrad_ws_ + op.slab_off;
+            sg.S = dwconv_wgrad_slices(B, op.H, op.W, op.Cin, op.KS);
+            CMOOP_REQUIRE((size_t)sg.S * sg.n <= op.slab_floats, "depthwise slab region");
+            slab_segs_.push_back(sg);
+            launch_dwconv_fwd(dY, params_ + op.w_off, ia.grad, B, op.H, op.W, op.Cin, op.KS, 1, op.in_is_relu ? ia.data : nullptr, stream_);
             break;
         }
         case OP_BN: {
@@ -1340,8 +1393,11 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B) 
     const NetPlan plan = plan_net(gene, cfg, T, F);
     // first conv (C_in = 1, direct kernel): its output feeds the GEMM layers, so the same element bound applies to it
     CMOOP_REQUIRE((int64_t)B * T * F * gene[0] < (1ll << 29), "first-layer output exceeds 2^29 elements (32-bit byte offsets): lower the batch / eval_batch");
-    for (const Op& op : plan.ops)
+    for (const Op& op : plan.ops) {
         if (op.kind == OP_CONV) igemm_check_range(op.conv().geometry(B));
+        if (op.kind == OP_DWCONV)
+            CMOOP_REQUIRE((int64_t)B * op.H * op.W * op.Cin < (1ll << 29), "depthwise activation exceeds 2^29 elements (32-bit offsets): lower the batch / eval_batch");
+    }
 }
 
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,

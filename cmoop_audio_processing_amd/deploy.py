@@ -39,7 +39,7 @@ _PCEN_FIELDS = ("s", "alpha", "delta", "r", "eps", "input_scale")
 class TrainedModel:
     """One trained candidate: everything ``session()`` needs to rebuild the net, in plain numpy."""
     gene: Tuple[int, ...]
-    variant: str                       # "A" / "B"
+    variant: str                       # "A" / "B" / "A_ds" / "B_ds" (genes.VARIANT_NAMES)
     classes: int
     T: int
     F: int
@@ -53,8 +53,8 @@ class TrainedModel:
     def __post_init__(self):
         self.gene = tuple(int(v) for v in self.gene)
         G.validate_gene(self.gene)
-        if self.variant not in ("A", "B"):
-            raise ValueError(f"variant must be 'A' or 'B', got {self.variant!r}")
+        if self.variant not in G.VARIANT_CODES.values():
+            raise ValueError(f"variant must be one of {sorted(G.VARIANT_CODES.values())}, got {self.variant!r}")
         self.params = np.ascontiguousarray(self.params, np.float32).reshape(-1)
         want = G.param_count(self.gene, G.VARIANT_NAMES[self.variant], int(self.classes))
         if self.params.size != want:
@@ -124,7 +124,7 @@ class TrainedModel:
                                     **dict(zip(_FE_FLOAT, ff)), pcen=pcen)
             mean = z["mean"].copy() if "mean" in z.files else None
             scale = z["scale"].copy() if "scale" in z.files else None
-            return cls(gene=tuple(int(v) for v in z["gene"]), variant="AB"[variant], classes=classes, T=T, F=F, seed=seed,
+            return cls(gene=tuple(int(v) for v in z["gene"]), variant=G.VARIANT_CODES[variant], classes=classes, T=T, F=F, seed=seed,
                        params=z["params"].copy(), objectives=obj, frontend=fe, mean=mean, scale=scale)
 
     def session(self, config: Optional[EvalConfig] = None):

@@ -46,7 +46,7 @@ GEMM_CODES = {"fp32": 0, "bf16x3": 2, "bf16": 3}
 @dataclass(frozen=True)
 class EvalConfig:
     """The reference's module constants, frozen (defaults = nsga_penalty.py:159-208)."""
-    variant: str = "A"            # build_model topology
+    variant: str = "A"            # build_model topology: "A" / "B", or their depthwise-separable forms "A_ds" / "B_ds"
     classes: int = 10             # CLASSES
     epochs: int = 300             # EPOCHS
     batch: int = 64               # BATCH_SIZE

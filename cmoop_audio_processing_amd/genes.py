@@ -33,7 +33,23 @@ FC_LAYER_CONFIGS = {1: [64], 2: [128, 64], 3: [256, 128, 64], 4: [512, 256, 128,
 
 VARIANT_A = 0  # "deep":    nsga_penalty.py / mobo_penalty.py / acc_*_nsga_1.py / psi_mobo_2.py
 VARIANT_B = 1  # "shallow": sa_nsga_penalty.py and every sa_/psi_/init_ ablation script
-VARIANT_NAMES = {"A": VARIANT_A, "B": VARIANT_B, 0: VARIANT_A, 1: VARIANT_B}
+# The depthwise-separable search space (build-defined; the reference has none): A / B with every k x k stride-1 convolution
+# of C_in >= 16 replaced by a Keras-SeparableConv2D-style layer, depth multiplier 1 ("Depthwise-separable variants")
+VARIANT_A_DS = 2
+VARIANT_B_DS = 3
+VARIANT_NAMES = {"A": VARIANT_A, "B": VARIANT_B, "A_ds": VARIANT_A_DS, "B_ds": VARIANT_B_DS,
+                 0: VARIANT_A, 1: VARIANT_B, 2: VARIANT_A_DS, 3: VARIANT_B_DS}
+#: variant code -> name, the inverse of VARIANT_NAMES' string keys
+VARIANT_CODES = {VARIANT_A: "A", VARIANT_B: "B", VARIANT_A_DS: "A_ds", VARIANT_B_DS: "B_ds"}
+
+
+def variant_is_a(variant: int) -> bool:
+    """Topology A or its separable form."""
+    return variant in (VARIANT_A, VARIANT_A_DS)
+
+
+def variant_is_ds(variant: int) -> bool:
+    return variant in (VARIANT_A_DS, VARIANT_B_DS)
 
 Gene = Tuple[int, int, int, int, int, int]
 
@@ -117,16 +133,22 @@ def half_up(n: int) -> int:
 #   conv bias    [C_out]
 #   bn gamma, bn beta [C]      (trainable)      bn moving mean, var [C] (state)
 #   dense kernel [out][in]     dense bias [out]
+#   separable layer (A_ds / B_ds): depthwise_kernel [kh][kw][C_in], pointwise_kernel [C_out][1][1][C_in], bias [C_out]
 # --------------------------------------------------------------------------
 def layer_specs(g: Sequence[int], variant: int, classes: int) -> List[Dict]:
     """Flat description of every parameterised layer, forward order.
 
-    Each entry: {"kind": "conv"|"bn"|"dense", "name", shapes...}.  ``variant``
+    Each entry: {"kind": "conv"|"sepconv"|"bn"|"dense", "name", shapes...}.  ``variant``
     selects the reference topology (A: nsga_penalty.py:255-301,
-    B: sa_nsga_penalty.py:151-165).
+    B: sa_nsga_penalty.py:151-165) or its depthwise-separable form, in which the
+    k x k stride-1 convolutions after the first become kind "sepconv".
     """
     f, k, bn, R, fc, _ = g
     specs: List[Dict] = []
+    A, ds = variant_is_a(variant), variant_is_ds(variant)
+
+    def body_conv(name, cin, cout):
+        specs.append({"kind": "sepconv" if ds else "conv", "name": name, "cin": cin, "cout": cout, "k": k, "stride": 1})
 
     def conv(name, cin, cout, ks, stride=1):
         specs.append({"kind": "conv", "name": name, "cin": cin, "cout": cout, "k": ks, "stride": stride})
@@ -137,18 +159,18 @@ def layer_specs(g: Sequence[int], variant: int, classes: int) -> List[Dict]:
     conv("conv1", 1, f, k)
     if bn:
         bnl("bn1", f)
-    if variant == VARIANT_A:
-        conv("conv2", f, f, k)
+    if A:
+        body_conv("conv2", f, f)
         if bn:
             bnl("bn2", f)
     c = f
     for r in range(R):
         conv(f"res{r}_skip", c, 2 * c, 1, 2)
-        conv(f"res{r}_conv1", c, 2 * c, k)
+        body_conv(f"res{r}_conv1", c, 2 * c)
         if bn:
             bnl(f"res{r}_bn1", 2 * c)
-        if variant == VARIANT_A:
-            conv(f"res{r}_conv2", 2 * c, 2 * c, k)
+        if A:
+            body_conv(f"res{r}_conv2", 2 * c, 2 * c)
             if bn:
                 bnl(f"res{r}_bn2", 2 * c)
         c *= 2
@@ -167,6 +189,10 @@ def param_tensors(g: Sequence[int], variant: int, classes: int) -> List[Tuple[st
     for s in layer_specs(g, variant, classes):
         if s["kind"] == "conv":
             out.append((s["name"] + "/kernel", (s["cout"], s["k"], s["k"], s["cin"]), "kernel"))
+            out.append((s["name"] + "/bias", (s["cout"],), "bias"))
+        elif s["kind"] == "sepconv":
+            out.append((s["name"] + "/depthwise_kernel", (s["k"], s["k"], s["cin"]), "kernel"))
+            out.append((s["name"] + "/pointwise_kernel", (s["cout"], 1, 1, s["cin"]), "kernel"))
             out.append((s["name"] + "/bias", (s["cout"],), "bias"))
         elif s["kind"] == "bn":
             out.append((s["name"] + "/gamma", (s["c"],), "gamma"))
@@ -187,13 +213,19 @@ def param_count(g: Sequence[int], variant: int, classes: int) -> int:
     """
     f, k, bn, R, fc, _ = (int(v) for v in g)
     kk = k * k
-    if variant == VARIANT_A:
-        p = (kk * f + f) + (kk * f * f + f) + (8 * f if bn else 0)
+    ds = variant_is_ds(variant)
+
+    def convp(cin, cout):
+        """a k x k stride-1 body convolution: full, or depthwise + pointwise + bias"""
+        return kk * cin + cin * cout + cout if ds else kk * cin * cout + cout
+
+    if variant_is_a(variant):
+        p = (kk * f + f) + convp(f, f) + (8 * f if bn else 0)
         c = f
         for _ in range(R):
             p += c * 2 * c + 2 * c
-            p += kk * c * 2 * c + 2 * c
-            p += kk * (2 * c) * (2 * c) + 2 * c
+            p += convp(c, 2 * c)
+            p += convp(2 * c, 2 * c)
             p += 16 * c if bn else 0
             c *= 2
     else:
@@ -201,7 +233,7 @@ def param_count(g: Sequence[int], variant: int, classes: int) -> int:
         c = f
         for _ in range(R):
             p += c * 2 * c + 2 * c
-            p += kk * c * 2 * c + 2 * c
+            p += convp(c, 2 * c)
             p += 8 * c if bn else 0
             c *= 2
     prev = c
@@ -221,18 +253,23 @@ def fwd_flops_per_sample(g: Sequence[int], variant: int, classes: int, T: int, F
     """Algorithmic forward FLOPs per sample, 2*MAC for conv/dense only."""
     f, k, _, R, fc, _ = (int(v) for v in g)
     kk = k * k
+    A, ds = variant_is_a(variant), variant_is_ds(variant)
+
+    def convf(hw, cin, cout):
+        return 2 * hw * kk * cin + 2 * hw * cin * cout if ds else 2 * hw * kk * cin * cout
+
     H, W = T, F
     fl = 2 * H * W * kk * 1 * f
-    if variant == VARIANT_A:
-        fl += 2 * H * W * kk * f * f
+    if A:
+        fl += convf(H * W, f, f)
     h, w = half_up(H), half_up(W)
     c = f
     for _ in range(R):
         h2, w2 = half_up(h), half_up(w)
         fl += 2 * h2 * w2 * c * 2 * c
-        fl += 2 * h * w * kk * c * 2 * c
-        if variant == VARIANT_A:
-            fl += 2 * h * w * kk * 2 * c * 2 * c
+        fl += convf(h * w, c, 2 * c)
+        if A:
+            fl += convf(h * w, 2 * c, 2 * c)
         h, w, c = h2, w2, 2 * c
     prev = c
     for units in FC_LAYER_CONFIGS[fc]:

@@ -11,6 +11,7 @@ offspring, only max(1, int(pop * infill)) of them per generation get a TRUE eval
     python examples/run_sa_nsga_penalty.py --pop 64 --gen 20 --infill 0.334 --memetic --compute bf16      # BASELINE configs[4]
     python examples/run_sa_nsga_penalty.py --audio birdclef --pop 8 --gen 2 --clips 264 --epochs 6       # 128 x 128 dB-mel patches
     python examples/run_sa_nsga_penalty.py --audio birdclef --scale pcen --pop 8 --gen 2 --clips 264 --epochs 6   # ... PCEN patches
+    python examples/run_sa_nsga_penalty.py --audio birdclef --space ds --pop 20 --gen 20                 # BASELINE configs[3]: DS-CNN space
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_sa_nsga_penalty.py --pop 40 --gen 20
 """
 import argparse
@@ -45,6 +46,9 @@ def main():
                     help="--audio birdclef only: db = the preset's dB scale relative to each clip's loudest bin; pcen = the same "
                          "geometry with per-channel energy normalisation (PcenConfig.preset('bioacoustic')), which takes the "
                          "recording level and the stationary background out of the patch")
+    ap.add_argument("--space", default="full", choices=["full", "ds"],
+                    help="full: the reference's topology B; ds: its depthwise-separable form (variant B_ds: every k x k stride-1 "
+                         "convolution after the first becomes depthwise k x k + pointwise 1 x 1), the low-size end of the front")
     ap.add_argument("--out", default="sa_nsga_generations.csv")
     ap.add_argument("--trace", default="", help="write a JSON trace: per evaluate call wall-clock, epochs run, hypervolume")
     ap.add_argument("--augment", default="", choices=["", "kws"],
@@ -86,7 +90,8 @@ def main():
         loss = LossConfig.balanced(ytr, a.classes, mixup_alpha=a.mixup_alpha, label_smoothing=a.label_smoothing)
     ev = PopulationEvaluator(Xtr, ytr, Xva, yva, EvalConfig.preset(preset, classes=a.classes, epochs=a.epochs, seed=a.seed,
                                                                    verbose=(rank == 0), compute=a.compute, augment=augment,
-                                                                   loss=loss if loss.enabled else None))
+                                                                   loss=loss if loss.enabled else None,
+                                                                   **({"variant": "B_ds"} if a.space == "ds" else {})))
     calls = []
     t_start = time.perf_counter()
 

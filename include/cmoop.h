@@ -28,6 +28,12 @@ extern "C" {
 /* topologies hidden behind the reference's build_model(hparams) */
 #define CMOOP_VARIANT_A 0 /* "deep":    nsga_penalty.py:225-334, mobo_penalty.py:128-194 */
 #define CMOOP_VARIANT_B 1 /* "shallow": sa_nsga_penalty.py:137-177 and the sa_/psi_/init_ ablations */
+/* the depthwise-separable search space (build-defined, no reference counterpart): A / B with every k x k stride-1 convolution
+ * of C_in >= 16 replaced by a Keras-SeparableConv2D-style layer (depth multiplier 1): depthwise k x k (SAME, no bias, no
+ * activation), then pointwise 1 x 1 with the bias, the ReLU and the BatchNorm role of the convolution it replaces.
+ * Canonical tensors per separable layer: depthwise_kernel [k][k][C_in], pointwise_kernel [C_out][1][1][C_in], bias [C_out] */
+#define CMOOP_VARIANT_A_DS 2
+#define CMOOP_VARIANT_B_DS 3
 
 /* calculate_fpr variants */
 #define CMOOP_FPR_V1 0       /* nsga_penalty.py:351-364 (= sa_nsga_penalty.py:189-202) */
@@ -233,6 +239,11 @@ int cmoop_conv_launch_plan(int32_t op, int32_t B, int32_t H, int32_t W, int32_t 
 int cmoop_plan_convs(const int32_t gene[6], int32_t variant, int32_t T, int32_t F, int32_t* layers /* [cap][7] */, int32_t cap,
                      int32_t* count);
 
+/* host-only: the depthwise layers of a candidate (variants A_DS / B_DS; none for A / B) in forward order, the counterpart of
+ * cmoop_plan_convs, where their pointwise halves appear with KS = 1, stride = 1: layers[4 * i ..] = H, W, C, KS */
+int cmoop_plan_dwconvs(const int32_t gene[6], int32_t variant, int32_t T, int32_t F, int32_t* layers /* [cap][4] */, int32_t cap,
+                       int32_t* count);
+
 /* host-only: the launch-path variants, ';'-separated as in cmoop_last_kernels and in launch order, of the MFMA conv launches
  * a net created with (gene, cfg, T, F) makes in ONE train step at batch B (train != 0: forward with the statistics
  * epilogue where a layer feeds a BatchNorm, then weight and data gradients) or in one inference pass at batch B
@@ -252,6 +263,10 @@ int cmoop_halo_tile_check(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t 
 /* host-only: number of row slices the weight-gradient kernel splits a conv/dense layer into (workspace sizing;
  * NOT monotone in B -- tests pin that the trainer sizes its slab workspace for the worst batch 1..cfg.batch) */
 int cmoop_wgrad_slices(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t* out);
+
+/* host-only: row-run slices of the depthwise weight gradient, a function of the shape alone (NOT monotone in B: the trainer
+ * sizes the layer's slab region for the worst batch 1..cfg.batch) */
+int cmoop_dwconv_wgrad_slices(int32_t B, int32_t H, int32_t W, int32_t C, int32_t KS, int32_t* out);
 
 /* calculate_fpr on host label arrays (nsga_penalty.py:351-364 and variants) */
 int cmoop_calculate_fpr(const int32_t* y_true, const int32_t* y_pred, int64_t n, int32_t classes, int32_t fpr_variant,
@@ -470,6 +485,19 @@ int cmoop_dense_fwd_ex(const float* x_dev, const float* w_dev, const float* bias
  * launch of the trainer's default backward, 0: weight gradient and data gradient as two launches */
 int cmoop_dense_bwd_ex(const float* x_dev, const float* w_dev, const float* dy_dev, float* dx_dev, float* dw_dev, float* db_dev,
                        int32_t M, int32_t N, int32_t K, int32_t mask_relu, double mask_scale, int32_t gemm_mode, int32_t merged);
+/* depthwise k x k convolution (SAME, stride 1, depth multiplier 1, no bias; NHWC fp32 in every gemm_mode), launched as the
+ * trainer launches it.  C a power of two in 16..512, KS in {3, 5}, B H W C < 2^29; w_dev [KS][KS][C].
+ * y[b,h,w,c] = sum_{ky,kx} x[b,h+ky-p,w+kx-p,c] w[ky][kx][c], p = (KS-1)/2, zeros outside the image */
+int cmoop_dwconv_fwd(const float* x_dev, const float* w_dev, float* y_dev, int32_t B, int32_t H, int32_t W, int32_t C, int32_t KS);
+/* dw [KS][KS][C] (per-slice partials into a workspace allocated inside the call, summed in the optimiser launch's fixed order:
+ * bit-reproducible, no atomics) and, when dx_dev != NULL, dx = mask_relu ? (x > 0 ? dx : 0) : dx */
+int cmoop_dwconv_bwd(const float* x_dev, const float* w_dev, const float* dy_dev, float* dx_dev, float* dw_dev, int32_t B, int32_t H,
+                     int32_t W, int32_t C, int32_t KS, int32_t mask_relu);
+/* average milliseconds of `iters` back-to-back launches (HIP events on the library stream, after three warm-up launches) of
+ * one depthwise kernel alone.  mode 0: forward into out_dev; 1: data gradient of dy_dev with the x > 0 mask into out_dev;
+ * 2: the weight-gradient kernel (per-slice partials into a workspace of the call; out_dev unused) */
+int cmoop_dwconv_time(int32_t mode, const float* x_dev, const float* w_dev, const float* dy_dev, float* out_dev, int32_t B, int32_t H,
+                      int32_t W, int32_t C, int32_t KS, int32_t iters, double* avg_ms);
 int cmoop_maxpool_fwd(const float* x_dev, float* y_dev, uint8_t* arg_dev, int32_t B, int32_t H, int32_t W, int32_t C);
 int cmoop_maxpool_bwd(const float* dy_dev, const uint8_t* arg_dev, const float* y_dev, float* dx_dev, int32_t B, int32_t H,
                       int32_t W, int32_t C, int32_t mask_y_pos);
