@@ -52,6 +52,11 @@ class Loss(C.Structure):
                 ("class_weight", C.c_void_p), ("n_class_weight", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Distill(C.Structure):
+    """cmoop_distill (include/cmoop.h), 32 bytes."""
+    _fields_ = [("alpha", C.c_double), ("temperature", C.c_double), ("teacher_logits_dev", C.c_void_p), ("n_rows", C.c_int64)]
+
+
 #: cmoop_next_fn (include/cmoop.h): int32_t (*)(void* ctx)
 NEXT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
@@ -95,6 +100,20 @@ LOSS_PROTOTYPES = {
     "cmoop_net_loss_buffers": [C.c_void_p, C.c_void_p],
     "cmoop_eval_population_ex": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] +
                                 [C.c_void_p] * 7,
+}
+
+
+#: prototypes of the knowledge-distillation entry points (include/cmoop.h); structs travel as void* (C.byref), None is NULL
+DISTILL_PROTOTYPES = {
+    "cmoop_distill_default": [C.c_void_p],
+    "cmoop_distill_check": [C.c_void_p, C.c_int32, C.c_int64],
+    "cmoop_teacher_targets": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_uint32,
+                              C.c_uint32, C.c_void_p],
+    "cmoop_softmax_ce_distill": [C.c_void_p] * 5 + [C.c_double, C.c_double, C.c_int32, C.c_int32] + [C.c_void_p] * 3,
+    "cmoop_net_set_distill": [C.c_void_p, C.c_void_p],
+    "cmoop_net_train_step_distill_targets": [C.c_void_p] * 6 + [C.c_double, C.c_double, C.c_int32],
+    "cmoop_net_predict_logits": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "cmoop_eval_population_kd": [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 7,
 }
 
 
@@ -192,7 +211,8 @@ def lib():
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
         for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(PCEN_PROTOTYPES.items()) + \
-                list(ELEM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(DWCONV_PROTOTYPES.items()):
+                list(ELEM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(DWCONV_PROTOTYPES.items()) + \
+                list(DISTILL_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         _lib = L
         return L

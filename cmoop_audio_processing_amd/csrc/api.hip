@@ -149,6 +149,14 @@ static MixupParams scratch_mixup(const LossCfg& c, float* tab_dev, hipStream_t s
     return m;
 }
 
+static_assert(sizeof(cmoop_distill) == 32, "cmoop_distill is part of the ABI");
+static DistillCfg to_distill(const cmoop_distill* d) {   // the table stays the caller's
+    CMOOP_REQUIRE(d != nullptr, "distill config is NULL");
+    DistillCfg c;
+    c.alpha = d->alpha; c.temperature = d->temperature; c.teacher_logits = d->teacher_logits_dev; c.n_rows = d->n_rows;
+    return c;
+}
+
 static Dataset to_dataset(const cmoop_dataset* ds) {
     Dataset d;
     d.x_train = ds->x_train; d.y_train = ds->y_train; d.n_train = ds->n_train;
@@ -242,8 +250,8 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 }
 
 // every population call; next == NULL: candidates are taken longest-first from a process-local counter; aug == NULL: no augmentation
-static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_dataset* ds,
-                                const int32_t* genes,
+static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss,
+                                const cmoop_distill* distill, const cmoop_dataset* ds, const int32_t* genes,
                                 const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
                                 double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
     CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
@@ -261,11 +269,17 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* au
         lc = to_loss(loss);
         loss_check(lc, c.classes);
     }
+    DistillCfg dc;
+    if (distill) {
+        dc = to_distill(distill);
+        distill_check(dc, c.classes, d.n_train);
+    }
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
-    if (next) eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); }, aug ? &a : nullptr, loss ? &lc : nullptr);
-    else eval_population(c, d, genes, seeds, n, r.data(), {}, aug ? &a : nullptr, loss ? &lc : nullptr);
+    if (next) eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); }, aug ? &a : nullptr, loss ? &lc : nullptr,
+                              distill ? &dc : nullptr);
+    else eval_population(c, d, genes, seeds, n, r.data(), {}, aug ? &a : nullptr, loss ? &lc : nullptr, distill ? &dc : nullptr);
     for (int i = 0; i < n; ++i) {
         if (evaluated) evaluated[i] = r[i].evaluated;
         if (acc) acc[i] = r[i].acc;
@@ -302,8 +316,67 @@ int cmoop_eval_population_aug(const cmoop_config* cfg, const cmoop_augment* aug,
 int cmoop_eval_population_ex(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_dataset* ds,
                              const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc,
                              double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
+    return cmoop_eval_population_kd(cfg, aug, loss, nullptr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss,
+                                    seconds, evaluated);
+}
+
+int cmoop_eval_population_kd(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                             const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next,
+                             void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
+                             double* seconds, int32_t* evaluated) {
     return guard([&] {
-        eval_population_abi(cfg, aug, loss, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds, evaluated);
+        eval_population_abi(cfg, aug, loss, distill, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds,
+                            evaluated);
+    });
+}
+
+// ---- knowledge distillation ------------------------------------------------------
+int cmoop_distill_default(cmoop_distill* distill) {
+    return guard([&] {
+        CMOOP_REQUIRE(distill != nullptr, "distill config is NULL");
+        const DistillCfg c;
+        std::memset(distill, 0, sizeof(*distill));
+        distill->alpha = c.alpha; distill->temperature = c.temperature;
+    });
+}
+
+int cmoop_distill_check(const cmoop_distill* distill, int32_t classes, int64_t n_train) {
+    return guard([&] { distill_check(to_distill(distill), classes, n_train); });
+}
+
+int cmoop_teacher_targets(const cmoop_loss* loss, const float* zt_dev, const int32_t* idx_dev, int64_t row0, int64_t n_rows, int32_t B,
+                          int32_t C, double temperature, uint32_t seed, uint32_t step, float* q_dev) {
+    return guard([&] {
+        CMOOP_REQUIRE(B >= 0 && B < (1 << 27) && C >= 1 && row0 >= 0 && n_rows >= 1, "teacher_targets: 0 <= B < 2^27, C >= 1, row0 >= 0, n_rows >= 1");
+        CMOOP_REQUIRE(B == 0 || (zt_dev && q_dev), "teacher_targets: NULL buffer");
+        DistillCfg dc;
+        dc.temperature = temperature;
+        distill_check(dc, C, 0);
+        LossCfg c;
+        if (loss) {
+            c = to_loss(loss);
+            c.class_weight = nullptr;           // not read here
+            loss_check(c, 1);
+        }
+        hipStream_t s = lib_stream();
+        Scratch m(s);
+        const MixupParams mp = scratch_mixup(c, loss_mixup_on(c) ? m.floats(MIXUP_TABLE) : nullptr, s);
+        launch_teacher_targets(zt_dev, idx_dev, row0, n_rows, B, C, (float)temperature, mp, seed, step, q_dev, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_softmax_ce_distill(const float* z, const float* t, const float* w, const int32_t* primary, const float* q, double alpha,
+                             double temperature, int32_t B, int32_t C, float* dz, double* acc, int32_t* preds) {
+    return guard([&] {
+        CMOOP_REQUIRE(B >= 0 && C >= 1, "softmax_ce_distill: B >= 0, C >= 1");
+        CMOOP_REQUIRE(B == 0 || (z && t && q), "softmax_ce_distill: NULL logits, targets or teacher rows");
+        DistillCfg dc;
+        dc.alpha = alpha; dc.temperature = temperature;
+        distill_check(dc, C, 0);
+        hipStream_t s = lib_stream();
+        launch_softmax_ce_distill(z, t, w, primary, q, distill_params(dc), B, C, dz, acc, preds, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
 
@@ -890,6 +963,23 @@ int cmoop_net_train_step_targets(cmoop_net* h, const float* x_rows, const float*
         h->net->drain_profile();
     });
 }
+int cmoop_net_set_distill(cmoop_net* h, const cmoop_distill* distill) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "set_distill: NULL net");
+        if (!distill) { h->net->set_distill(nullptr); return; }
+        const DistillCfg c = to_distill(distill);
+        h->net->set_distill(&c);
+    });
+}
+int cmoop_net_train_step_distill_targets(cmoop_net* h, const float* x_rows, const float* t, const float* w, const int32_t* primary,
+                                         const float* q, double alpha, double temperature, int32_t B) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "train_step_distill_targets: NULL net");
+        h->net->train_step_distill_targets(x_rows, t, w, primary, q, alpha, temperature, B);
+        CMOOP_HIP(hipStreamSynchronize(h->net->stream()));
+        h->net->drain_profile();
+    });
+}
 int cmoop_net_loss_buffers(cmoop_net* h, int64_t out[4]) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net && out, "loss_buffers: NULL argument");
@@ -949,6 +1039,12 @@ int cmoop_net_predict(cmoop_net* h, const float* x, int64_t n, float* probs) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "predict: NULL net");
         h->net->predict(x, n, probs);
+    });
+}
+int cmoop_net_predict_logits(cmoop_net* h, const float* x, int64_t n, float* logits) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "predict_logits: NULL net");
+        h->net->predict_logits(x, n, logits);
     });
 }
 int cmoop_net_predict_stream(cmoop_net* h, const float* feat, int64_t n_frames, int32_t hop_frames, const cmoop_frontend_config* db,

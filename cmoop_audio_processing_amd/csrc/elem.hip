@@ -1589,6 +1589,197 @@ void launch_softmax_ce_soft(const float* Z, const float* t, const float* w, cons
     CMOOP_HIP(hipGetLastError());
 }
 
+// ===========================================================================
+// Knowledge distillation (kernels.h: semantics): the tempered teacher rows of a batch, and the loss against them.
+// ===========================================================================
+// One thread per batch row, as soft_targets_kernel: the row's draw, then max-subtracted softmax(zt[row] / T) with serial
+// loops in class order -- a row's result depends on its own logits (and its partner's) only, never on the batch or its
+// position in it.  An un-mixed row stores u's bits; a MIXED one lam u_j + mu v_j, two products and one add, no contraction
+__global__ __launch_bounds__(256) void teacher_targets_kernel(const float* __restrict__ Zt, const int32_t* __restrict__ idx,
+                                                              int64_t row0, int64_t n_rows, int B, int C, float T, MixupParams m,
+                                                              uint32_t seed, uint32_t step, float* __restrict__ Q,
+                                                              const StepState* __restrict__ st) {
+#pragma clang fp contract(off)
+    if (st) { row0 = st->row0; step = st->step; }
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    int32_t gate, p;
+    float lam;
+    mixup_row_draws(m, seed, step, (uint32_t)b, (uint32_t)B, &gate, &p, &lam);
+    const float mu = 1.0f - lam;
+    const float* zu = Zt + gather_row(idx, row0 + b, n_rows) * (int64_t)C;
+    float* q = Q + (size_t)b * C;
+    float mxu = zu[0];
+    for (int j = 1; j < C; ++j)
+        if (zu[j] > mxu) mxu = zu[j];
+    float seu = 0.f;
+    for (int j = 0; j < C; ++j) seu += expf((zu[j] - mxu) / T);
+    if (p == b) {
+        for (int j = 0; j < C; ++j) q[j] = expf((zu[j] - mxu) / T) / seu;
+        return;
+    }
+    const float* zv = Zt + gather_row(idx, row0 + p, n_rows) * (int64_t)C;
+    float mxv = zv[0];
+    for (int j = 1; j < C; ++j)
+        if (zv[j] > mxv) mxv = zv[j];
+    float sev = 0.f;
+    for (int j = 0; j < C; ++j) sev += expf((zv[j] - mxv) / T);
+    for (int j = 0; j < C; ++j) {
+        const float u = expf((zu[j] - mxu) / T) / seu;
+        const float v = expf((zv[j] - mxv) / T) / sev;
+        const float a = lam * u;
+        const float c = mu * v;
+        q[j] = a + c;
+    }
+}
+
+void launch_teacher_targets(const float* zt, const int32_t* idx, int64_t row0, int64_t n_rows, int B, int C, float T,
+                            const MixupParams& m, uint32_t seed, uint32_t step, float* q, hipStream_t s, const StepState* st) {
+    if (B == 0) return;
+    CMOOP_REQUIRE(B >= 1 && C >= 1 && n_rows >= 1 && zt && q, "teacher targets: bad arguments");
+    CMOOP_REQUIRE(T >= 1.0f && T <= 64.0f, "teacher targets: temperature must be in [1, 64]");
+    CMOOP_REQUIRE(!m.on || m.tab != nullptr, "teacher targets: the lam table is missing");
+    hipLaunchKernelGGL(teacher_targets_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, zt, idx, row0, n_rows, B, C, T, m, seed, step, q,
+                       st);
+    CMOOP_HIP(hipGetLastError());
+}
+
+// softmax_ce_soft_kernel plus the tempered term: the same loops in the same order for the maximum, the sum, p, pc, S, the
+// cross-entropy l and its gradient g, then s = softmax(z / T) held as an un-clipped log-softmax against the teacher row q.
+// The same fixed-order reduction
+__global__ __launch_bounds__(256) void softmax_ce_distill_kernel(const float* __restrict__ Z, const float* __restrict__ Tg,
+                                                                 const float* __restrict__ Wr, const int32_t* __restrict__ primary,
+                                                                 const float* __restrict__ Qt, DistillParams d, int B, int C,
+                                                                 float* __restrict__ dZ, double* __restrict__ acc,
+                                                                 int32_t* __restrict__ preds) {
+    __shared__ double lsum[4];
+    __shared__ int csum[4];
+    const int t = threadIdx.x;
+    const float lo = 1e-7f, hi = 1.0f - 1e-7f;
+    double myloss = 0.0;
+    int mycorrect = 0;
+    for (int r = t; r < B; r += 256) {
+        const float* z = Z + (size_t)r * C;
+        const float* tg = Tg + (size_t)r * C;
+        const float* qt = Qt + (size_t)r * C;
+        const float w = Wr ? Wr[r] : 1.0f;
+        int y;
+        if (primary) {
+            y = primary[r];
+        } else {                               // the first maximum of the target row
+            y = 0;
+            float tm = tg[0];
+            for (int j = 1; j < C; ++j)
+                if (tg[j] > tm) { tm = tg[j]; y = j; }
+        }
+        float mx = z[0];
+        int am = 0;
+        for (int j = 1; j < C; ++j)
+            if (z[j] > mx) { mx = z[j]; am = j; }
+        float se = 0.f;
+        for (int j = 0; j < C; ++j) se += expf(z[j] - mx);
+        float S = 0.f, Tsum = 0.f;
+        for (int j = 0; j < C; ++j) {
+            const float p = expf(z[j] - mx) / se;
+            const float pc = fminf(fmaxf(p, lo), hi);
+            S += pc;
+            Tsum += tg[j];
+        }
+        const float logS = logf(S);
+        float l = 0.f;
+        for (int j = 0; j < C; ++j) {
+            const float tj = tg[j];
+            if (tj > 0.f) {
+                const float p = expf(z[j] - mx) / se;
+                const float pc = fminf(fmaxf(p, lo), hi);
+                l += tj * (logf(pc) - logS);
+            }
+        }
+        // the tempered student: e_j = expf((z_j - mx) / T), seT = sum_j e_j, ls_j = (z_j - mx) / T - log seT;
+        // KD = sum q_j (log q_j - ls_j).  Both KD and the gradient term Qs s_i - q_i are small differences of large terms --
+        // where distillation converges to, s = q, they vanish -- and T^2 / T scale them: the sums seT and Qs, the two
+        // logarithms of KD, its sum and the difference Qs s_i - q_i are formed in double from the fp32 e_j and q_j.
+        // (The device's float32 log is low on average -- tools/device_log_bias.py, profiles/distill_logf_bias.txt -- and
+        // both logarithms enter KD with the same sign; tests/test_gpu_distill.py holds loss sum and dZ to 8 x the error of a
+        // float32 autograd restatement.)
+        double seT = 0.0, Qs = 0.0;
+        for (int j = 0; j < C; ++j) {
+            seT += (double)expf((z[j] - mx) / d.T);
+            Qs += (double)qt[j];
+        }
+        const double logseT = log(seT);
+        double kd = 0.0;
+        for (int j = 0; j < C; ++j) {
+            const float qj = qt[j];
+            if (qj > 0.f) kd += (double)qj * (log((double)qj) - ((double)((z[j] - mx) / d.T) - logseT));
+        }
+        myloss += (double)w * ((double)(d.one_minus_alpha * -l) + (double)d.alpha_t2 * kd);
+        mycorrect += (am == y);
+        if (preds) preds[r] = am;
+        if (dZ) {
+            float dot = 0.f;
+            for (int j = 0; j < C; ++j) {
+                const float p = expf(z[j] - mx) / se;
+                const float pc = fminf(fmaxf(p, lo), hi);
+                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
+                const float qj = gate * (Tsum / S - tg[j] / pc);
+                dot += p * qj;
+            }
+            const float invB = 1.f / (float)B;
+            const double rseT = 1.0 / seT;
+            for (int j = 0; j < C; ++j) {
+                const float p = expf(z[j] - mx) / se;
+                const float pc = fminf(fmaxf(p, lo), hi);
+                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
+                const float qj = gate * (Tsum / S - tg[j] / pc);
+                const float g = p * (qj - dot);
+                const float kg = (float)(Qs * ((double)expf((z[j] - mx) / d.T) * rseT) - (double)qt[j]);   // Qs s_j - q_j
+                dZ[(size_t)r * C + j] = w * ((d.one_minus_alpha * g + d.alpha_t * kg) * invB);
+            }
+        }
+    }
+    // wavefront reduction (fixed butterfly order: deterministic), then the four wave sums in wave order
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        myloss += __shfl_xor(myloss, off, 64);
+        mycorrect += __shfl_xor(mycorrect, off, 64);
+    }
+    if ((t & 63) == 0) { lsum[t >> 6] = myloss; csum[t >> 6] = mycorrect; }
+    __syncthreads();
+    if (t == 0 && acc) {
+        acc[0] += ((lsum[0] + lsum[1]) + lsum[2]) + lsum[3];
+        reinterpret_cast<long long*>(acc)[1] += (csum[0] + csum[1]) + (csum[2] + csum[3]);
+    }
+}
+
+void launch_softmax_ce_distill(const float* Z, const float* t, const float* w, const int32_t* primary, const float* q,
+                               const DistillParams& d, int B, int C, float* dZ, double* acc, int32_t* preds, hipStream_t s) {
+    if (B == 0) return;
+    CMOOP_REQUIRE(B >= 1 && C >= 1 && Z && t && q, "softmax_ce_distill: bad arguments");
+    CMOOP_REQUIRE(d.T >= 1.0f && d.T <= 64.0f, "softmax_ce_distill: temperature must be in [1, 64]");
+    hipLaunchKernelGGL(softmax_ce_distill_kernel, dim3(1), dim3(256), 0, s, Z, t, w, primary, q, d, B, C, dZ, acc, preds);
+    CMOOP_HIP(hipGetLastError());
+}
+
+void distill_check(const DistillCfg& c, int classes, int64_t n_train) {
+    CMOOP_REQUIRE(classes >= 1, "distill: classes must be >= 1");
+    CMOOP_REQUIRE(c.alpha >= 0.0 && c.alpha <= 1.0, "distill: alpha must be in [0, 1]");   // (a NaN fails)
+    CMOOP_REQUIRE(std::isfinite(c.temperature) && c.temperature >= 1.0 && c.temperature <= 64.0,
+                  "distill: temperature must be finite and in [1, 64]");
+    if (c.teacher_logits)
+        CMOOP_REQUIRE(c.n_rows >= 1 && c.n_rows == n_train, "distill: n_rows must equal the training rows = " + std::to_string(n_train) +
+                                                                " (got " + std::to_string(c.n_rows) + ")");
+}
+
+DistillParams distill_params(const DistillCfg& c) {
+    DistillParams d;
+    d.one_minus_alpha = (float)(1.0 - c.alpha);
+    d.alpha_t = (float)(c.alpha * c.temperature);
+    d.alpha_t2 = (float)(c.alpha * c.temperature * c.temperature);
+    d.T = (float)c.temperature;
+    return d;
+}
+
 void loss_check(const LossCfg& c, int classes) {
     CMOOP_REQUIRE(classes >= 1, "loss: classes must be >= 1");
     CMOOP_REQUIRE(c.label_smoothing >= 0.0 && c.label_smoothing < 1.0, "loss: label_smoothing must be in [0, 1)");   // (a NaN fails)

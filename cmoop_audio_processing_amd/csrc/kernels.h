@@ -302,6 +302,48 @@ void launch_softmax_ce_soft(const float* Z, const float* t, const float* w, cons
                             double* acc, int32_t* preds, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Knowledge distillation (opt-in; no reference counterpart, BUILD-DEFINED -- include/cmoop.h fixes the semantics): OFFLINE,
+// against one device table zt[n_rows][classes] of a teacher's logits of the resident training rows, computed once and
+// shared by every candidate.  The teacher saw the un-augmented, un-mixed row; a MIXED batch row blends the two teacher
+// rows with the blend kernel's own draws.  Validation never sees any of this.
+// ---------------------------------------------------------------------------
+struct DistillCfg {
+    double alpha = 0.0, temperature = 1.0;
+    const float* teacher_logits = nullptr;   // [n_rows][classes] fp32, device; null: off
+    int64_t n_rows = 0;
+};
+// host-only: throws with a message naming the offending field; n_rows is compared with n_train only when there is a table
+void distill_check(const DistillCfg& c, int classes, int64_t n_train);
+// alpha > 0 and a table.  A disabled config is no config
+inline bool distill_enabled(const DistillCfg& c) { return c.alpha > 0.0 && c.teacher_logits != nullptr; }
+// the config as the loss kernel reads it, each value rounded once from the double expression
+struct DistillParams {
+    float one_minus_alpha = 1.f;   // (float)(1 - alpha)
+    float alpha_t = 0.f;           // (float)(alpha T)
+    float alpha_t2 = 0.f;          // (float)(alpha T^2)
+    float T = 1.f;                 // (float)T
+};
+DistillParams distill_params(const DistillCfg& c);
+// q[B][C]: u = softmax(zt[row(b)] / T) -- mx = max_j z_j, e_j = expf((z_j - mx) / T), se = sum e_j over ascending j,
+// u_j = e_j / se -- with row(b) = idx[row0 + b] (idx null: row0 + b) ALWAYS clamped into [0, n_rows), n_rows >= 1 the rows
+// of the table.  Un-mixed row: q[b] = u (its bits); MIXED row (mixup_row_draws): v the same of row(partner),
+// q[b][j] = lam u_j + mu v_j, two fp32 products and one add, separately rounded.  st != null: row0 and step come from the
+// device state (graph replay)
+void launch_teacher_targets(const float* zt, const int32_t* idx, int64_t row0, int64_t n_rows, int B, int C, float T,
+                            const MixupParams& m, uint32_t seed, uint32_t step, float* q, hipStream_t s,
+                            const StepState* st = nullptr);
+// launch_softmax_ce_soft's CE_b = l_b and g_i = p_i (q'_i - dot) from z, t, plus the tempered term against the teacher row q:
+//   e_j = expf((z_j - mx) / T), seT = sum e_j, s_j = e_j / seT, ls_j = (z_j - mx) / T - log(seT) (no clipping), Qs = sum_j q_j
+//   KD_b = sum_{q_j > 0} q_j (log(q_j) - ls_j);   acc[0] += w_b ((1 - alpha) CE_b + alpha T^2 KD_b).  KD_b and Qs s_i - q_i
+//   are small differences of large terms that T^2 / T then scale: seT, Qs, the two logarithms, KD's sum and
+//   Qs s_i - q_i are formed in double from the fp32 e_j and q_j, the latter rounded to fp32 once
+//   dz_i = w_b ((1 - alpha) g_i + alpha T (Qs s_i - q_i)) / B;   acc[1] += (argmax z == primary[b])
+// w / primary null as launch_softmax_ce_soft.  It reads nothing of the batch position: t, w, primary and q were built for
+// the step by the two targets launches before it
+void launch_softmax_ce_distill(const float* Z, const float* t, const float* w, const int32_t* primary, const float* q,
+                               const DistillParams& d, int B, int C, float* dZ, double* acc, int32_t* preds, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Per-channel reductions over the M rows of an [M][C] tensor (C % 4 == 0).
 // Two-stage and order-fixed: `blocks` partials then a double-precision finalize.
 // ---------------------------------------------------------------------------

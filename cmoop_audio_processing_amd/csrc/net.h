@@ -229,8 +229,16 @@ class Net : public GemmHook {
     void set_loss(const LossCfg* loss);
     // floats (int32 words) allocated for the mixup batch buffer, t, w and primary: 0 where the buffer does not exist
     void loss_buffers(int64_t out[4]) const;
+    // Knowledge distillation (kernels.h) of every following train step, both step paths; null or a disabled config: off, and
+    // a step's launches and bits are those of a net that never had one.  Enabled: the config is checked against cfg.classes
+    // (n_rows against itself: the table's rows are what a step's gather rows must equal), q [cfg.batch][classes] and the
+    // target buffers are allocated on first use; each step then builds t / w / primary (one-hot, unit weight and the label
+    // under a default loss), the teacher rows q, and takes softmax_ce_distill_kernel as its loss.  The table stays the
+    // caller's and must outlive the steps.  Inference and the validation loss are untouched.  Drops a captured step graph
+    void set_distill(const DistillCfg* distill);
     // rows of the resident tensor the next train steps gather from (0: unknown, no clamp)
-    void set_gather_rows(int64_t n) { gather_rows_ = n; }
+    // with distillation on, n must be the rows of the teacher table: refused here, before any step is enqueued
+    void set_gather_rows(int64_t n);
     // ONE epoch of Model.fit on the production path (device permutation of (seed, epoch) when cfg.shuffle, device
     // StepState steps, last partial batch kept); idx_scratch: n_train int32 on the device
     void run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch, int32_t* idx_scratch);
@@ -241,6 +249,10 @@ class Net : public GemmHook {
     // (null: the first maximum of t), all on the device.  No augmentation, no mixing, no target construction, whatever
     // set_augment / set_loss say; dropout, Adam and the counters advance as in train_step
     void train_step_targets(const float* x_rows, const float* t, const float* w, const int32_t* primary, int B);
+    // train_step_targets with a caller-built teacher row q [B][classes] and the distillation loss at (alpha, temperature),
+    // whatever set_distill says
+    void train_step_distill_targets(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
+                                    double alpha, double temperature, int B);
     // The fit loop's form of the same step: the batch position, dropout counter and Adam iteration live in a device
     // StepState (kernels.h), so a full-batch step has no per-step host arguments; with CMOOP_GRAPH=1 it is captured ONCE
     // as a hipGraph and replayed (opt-in: measured no faster than eager launches, see begin_fit).
@@ -251,6 +263,8 @@ class Net : public GemmHook {
     void evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum, long long* correct, int32_t* preds);
     // Model.predict: probs [n][classes] (device) of n rows of X, inference mode, eval_batch rows per launch
     void predict(const float* X, int64_t n, float* probs);
+    // the same pass with the logits themselves copied out, logits [n][classes] (device): what predict's softmax reads
+    void predict_logits(const float* X, int64_t n, float* logits);
     // the same over the windows [i hop, i hop + T) of a feature stream [n_frames][F]: eval_batch windows at a time are
     // gathered (per-window dB tail when db_scale, StandardScaler when mean / scale: host doubles [F]) into one chunk buffer
     void predict_stream(const float* feat, int64_t n_frames, int hop, bool db_scale, bool db_ref_max, float db_amin, float top_db,
@@ -295,6 +309,11 @@ class Net : public GemmHook {
     float* mix_buf_ = nullptr;          // [cfg.batch][T][F], allocated by the first set_loss with mixup on
     float *tgt_t_ = nullptr, *tgt_w_ = nullptr;   // [cfg.batch][classes], [cfg.batch]: allocated by the first enabled set_loss
     int32_t* tgt_primary_ = nullptr;    // [cfg.batch]
+    bool distill_on_ = false;           // train steps take the distillation loss (set_distill)
+    DistillParams kdp_;
+    const float* kd_zt_ = nullptr;      // the caller's teacher table [kd_rows_][classes]
+    int64_t kd_rows_ = 0;
+    float* kd_q_ = nullptr;             // [cfg.batch][classes], allocated by the first enabled set_distill
     const float* batch_in_ = nullptr;   // this train step's gathered batch (mix_buf_ / aug_buf_), null: rows come from (X, idx, row0)
     StepState* st_dev_ = nullptr;       // device step state (train_step_stateful)
     float* alpha_tab_ = nullptr;        // Adam step size per iteration
@@ -332,9 +351,9 @@ struct FitHistory {
 EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, uint32_t seed, FitHistory* hist = nullptr);
 // train-to-early-stop + readouts for one candidate (evaluate_individual, nsga_penalty.py:368-395)
 // aug (optional): train-time augmentation of the candidate's fit (Net::set_augment); loss (optional): its soft-target
-// training loss (Net::set_loss)
+// training loss (Net::set_loss); distill (optional): distillation against a teacher's logit table (Net::set_distill)
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
-                         const AugmentCfg* aug = nullptr, const LossCfg* loss = nullptr);
+                         const AugmentCfg* aug = nullptr, const LossCfg* loss = nullptr, const DistillCfg* distill = nullptr);
 // host-only: every implicit-GEMM conv geometry of a candidate at batch B (a walk of plan_net's ops); throws
 // through igemm_check_range when a layer is beyond the kernels' 32-bit byte offsets (depthwise activations: 2^29 elements)
 void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
@@ -345,7 +364,7 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
 // n candidates are taken longest-first from a process-local counter.
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
                      EvalResult* out, const std::function<int()>& pull = {}, const AugmentCfg* aug = nullptr,
-                     const LossCfg* loss = nullptr);
+                     const LossCfg* loss = nullptr, const DistillCfg* distill = nullptr);
 
 // host-only: windows of T frames at hop frames in a stream of n_frames, 1 + (n_frames - T) / hop; throws when n_frames < T or hop < 1
 int64_t stream_windows(int64_t n_frames, int T, int hop);

@@ -910,6 +910,9 @@ void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, cons
 // one optimiser step: forward -> loss -> backward -> Adam.  st == null: explicit host arguments (session API);
 // st != null: batch position / dropout counter / Adam iteration come from the device state, which the step advances
 void Net::step_body(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B, const StepState* st) {
+    // before anything is enqueued: a teacher table of another length than the split the step gathers from is refused whole
+    CMOOP_REQUIRE(!distill_on_ || gather_rows_ == 0 || gather_rows_ == kd_rows_, "distill: the teacher table has " +
+                  std::to_string(kd_rows_) + " rows, the training split " + std::to_string(gather_rows_));
     // augmentation on: the batch's rows are gathered and augmented into aug_buf_ first (st != null: the kernel reads the
     // batch position and the step from the device state, so a replayed graph draws for the step it replays)
     if (aug_on_) launch_augment_gather(X, idx, row0, aug_buf_, B, T_, F_, aug_, seed_, (uint32_t)step_, stream_, st, gather_rows_);
@@ -920,7 +923,15 @@ void Net::step_body(const float* X, const int32_t* y, const int32_t* idx, int64_
     }
     batch_in_ = mix_on_ ? mix_buf_ : (aug_on_ ? aug_buf_ : nullptr);
     forward(X, idx, row0, B, true, st);
-    if (loss_on_) {
+    if (distill_on_) {
+        // t / w / primary as the soft-target loss builds them (a default loss: one-hot, unit weight, the label), then the
+        // teacher rows of the same batch positions under the same mixup draws
+        launch_soft_targets(y, idx, row0, B, cfg_.classes, mixp_, tgtp_, seed_, (uint32_t)step_, tgt_t_, tgt_w_, tgt_primary_, stream_,
+                            st, gather_rows_);
+        launch_teacher_targets(kd_zt_, idx, row0, kd_rows_, B, cfg_.classes, kdp_.T, mixp_, seed_, (uint32_t)step_, kd_q_, stream_, st);
+        launch_softmax_ce_distill(acts_[logits_].data, tgt_t_, tgt_w_, tgt_primary_, kd_q_, kdp_, B, cfg_.classes,
+                                  acts_[logits_].grad, acc_train_, nullptr, stream_);
+    } else if (loss_on_) {
         launch_soft_targets(y, idx, row0, B, cfg_.classes, mixp_, tgtp_, seed_, (uint32_t)step_, tgt_t_, tgt_w_, tgt_primary_, stream_,
                             st, gather_rows_);
         launch_softmax_ce_soft(acts_[logits_].data, tgt_t_, tgt_w_, tgt_primary_, B, cfg_.classes, acts_[logits_].grad, acc_train_,
@@ -986,6 +997,35 @@ void Net::train_step_targets(const float* x_rows, const float* t, const float* w
     try {
         forward(x_rows, nullptr, 0, B, true, nullptr);
         launch_softmax_ce_soft(acts_[logits_].data, t, w, primary, B, cfg_.classes, acts_[logits_].grad, acc_train_, nullptr, stream_);
+        backward(x_rows, nullptr, 0, B, nullptr);
+        optimiser_step(B, nullptr);
+    } catch (...) {
+        gather_rows_ = rows;
+        profiling_now_ = false;
+        throw;
+    }
+    gather_rows_ = rows;
+    ++iterations_;
+    ++step_;
+    profiling_now_ = false;
+}
+
+void Net::train_step_distill_targets(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
+                                     double alpha, double temperature, int B) {
+    CMOOP_REQUIRE(B >= 1 && B <= cfg_.batch, "train batch larger than configured");
+    CMOOP_REQUIRE(x_rows && t && q, "train_step_distill_targets: NULL rows, targets or teacher rows");
+    DistillCfg dc;
+    dc.alpha = alpha; dc.temperature = temperature;
+    distill_check(dc, cfg_.classes, 0);
+    const DistillParams dp = distill_params(dc);
+    profiling_now_ = cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0;
+    const int64_t rows = gather_rows_;
+    gather_rows_ = 0;          // x_rows holds exactly the B rows of this step: no resident tensor to clamp into
+    batch_in_ = nullptr;
+    try {
+        forward(x_rows, nullptr, 0, B, true, nullptr);
+        launch_softmax_ce_distill(acts_[logits_].data, t, w, primary, q, dp, B, cfg_.classes, acts_[logits_].grad, acc_train_, nullptr,
+                                  stream_);
         backward(x_rows, nullptr, 0, B, nullptr);
         optimiser_step(B, nullptr);
     } catch (...) {
@@ -1151,6 +1191,32 @@ void Net::set_loss(const LossCfg* loss) {
     if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }   // the captured step has the old launch sequence
 }
 
+void Net::set_gather_rows(int64_t n) {
+    CMOOP_REQUIRE(!distill_on_ || n == 0 || n == kd_rows_, "distill: the teacher table has " + std::to_string(kd_rows_) +
+                  " rows, the training split " + std::to_string(n));
+    gather_rows_ = n;
+}
+
+void Net::set_distill(const DistillCfg* distill) {
+    if (distill) distill_check(*distill, cfg_.classes, distill->n_rows);
+    const bool on = distill != nullptr && distill_enabled(*distill);
+    if (on) {
+        const size_t C = (size_t)cfg_.classes;
+        if (!tgt_t_) {
+            tgt_t_ = dalloc((size_t)cfg_.batch * C);
+            tgt_w_ = dalloc((size_t)cfg_.batch);
+            tgt_primary_ = reinterpret_cast<int32_t*>(dalloc((size_t)cfg_.batch));
+        }
+        if (!kd_q_) kd_q_ = dalloc((size_t)cfg_.batch * C);
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+    distill_on_ = on;
+    kdp_ = on ? distill_params(*distill) : DistillParams();
+    kd_zt_ = on ? distill->teacher_logits : nullptr;
+    kd_rows_ = on ? distill->n_rows : 0;
+    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }   // the captured step has the old launch sequence
+}
+
 void Net::loss_buffers(int64_t out[4]) const {
     out[0] = mix_buf_ ? (int64_t)cfg_.batch * T_ * F_ : 0;
     out[1] = tgt_t_ ? (int64_t)cfg_.batch * cfg_.classes : 0;
@@ -1164,6 +1230,7 @@ void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch
     // the device StepState / step-size table of the fit loop, (re)built when this epoch runs past what is there
     if (!st_dev_ || iterations_ + spe > alpha_tab_n_)
         begin_fit(std::max<int64_t>((int64_t)std::max(cfg_.epochs, 1) * spe, iterations_ + spe));
+    set_gather_rows(n_train);
     const int32_t* idx = nullptr;
     if (cfg_.shuffle) {
         CMOOP_REQUIRE(idx_scratch != nullptr, "run_epoch: shuffle needs an index buffer");
@@ -1177,7 +1244,6 @@ void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch
         }
         idx = idx_scratch;
     }
-    set_gather_rows(n_train);
     if (st_dev_) {   // explicit-argument steps (session API) do not advance the device state: start the epoch from the host's counters
         const StepState st0{0, (unsigned)step_, (unsigned)iterations_};
         CMOOP_HIP(hipMemcpyAsync(st_dev_, &st0, sizeof(StepState), hipMemcpyHostToDevice, stream_));
@@ -1209,6 +1275,17 @@ void Net::predict(const float* X, int64_t n, float* probs) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
         forward(X, nullptr, s, B, false);
         launch_softmax_probs(acts_[logits_].data, probs + s * cfg_.classes, B, cfg_.classes, stream_);
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+}
+
+void Net::predict_logits(const float* X, int64_t n, float* logits) {
+    CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && logits)), "predict_logits: NULL buffer");
+    for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
+        const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
+        forward(X, nullptr, s, B, false);
+        CMOOP_HIP(hipMemcpyAsync(logits + s * cfg_.classes, acts_[logits_].data, (size_t)B * cfg_.classes * 4, hipMemcpyDeviceToDevice,
+                                 stream_));
     }
     CMOOP_HIP(hipStreamSynchronize(stream_));
 }
@@ -1375,12 +1452,13 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
 }
 
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
-                         const AugmentCfg* aug, const LossCfg* loss) {
+                         const AugmentCfg* aug, const LossCfg* loss, const DistillCfg* distill) {
     const auto t0 = std::chrono::steady_clock::now();
     CMOOP_REQUIRE(ds.n_train >= 1 && ds.n_val >= 1, "empty train or validation split");
     Net net(gene, cfg, ds.T, ds.F, seed, stream);
     if (aug) net.set_augment(aug);
     if (loss) net.set_loss(loss);
+    if (distill) net.set_distill(distill);
     EvalResult res = fit_and_read_out(net, cfg, ds, seed, nullptr);
     res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return res;
@@ -1401,10 +1479,12 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B) 
 }
 
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
-                     EvalResult* out, const std::function<int()>& pull, const AugmentCfg* aug, const LossCfg* loss) {
+                     EvalResult* out, const std::function<int()>& pull, const AugmentCfg* aug, const LossCfg* loss,
+                     const DistillCfg* distill) {
     if (n <= 0) return;
     if (aug && !augment_enabled(*aug)) aug = nullptr;   // a disabled config is no config: today's path, call for call
     if (loss && !loss_enabled(*loss)) loss = nullptr;
+    if (distill && !distill_enabled(*distill)) distill = nullptr;
     for (int i = 0; i < n; ++i) validate_gene(genes + 6 * i);
     for (int i = 0; i < n; ++i) out[i].evaluated = 0;
     // longest first (closed-form FLOPs) so the tail of the generation is made of cheap candidates
@@ -1436,7 +1516,7 @@ void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* gen
                     if (j >= n) break;
                     i = order[j];
                 }
-                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream, aug, loss);
+                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream, aug, loss, distill);
                 out[i].evaluated = 1;
             }
         } catch (const std::exception& e) {

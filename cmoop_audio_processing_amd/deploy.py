@@ -144,6 +144,12 @@ class TrainedModel:
             raise
         return net
 
+    def logits(self, X, config: Optional[EvalConfig] = None):
+        """CUDA float32 [n, classes]: this model's logits of the rows X (CUDA float32 [n, T, F]) -- ``session(config)`` and
+        ``NetSession.predict_logits``; what ``PopulationEvaluator.set_teacher`` trains candidates against."""
+        with self.session(config) as net:
+            return net.predict_logits(X)
+
 
 class StreamScorer:
     """``score(recording)`` = ``log_mel_stream`` with the model's front end, then ``predict_stream`` every ``hop_frames``.

@@ -35,6 +35,7 @@ import numpy as np
 from . import _lib, genes as G
 from .augment import AugmentConfig
 from .loss import LossConfig
+from .distill import DistillConfig, check_teacher_table, require_teacher
 
 FPR_CODES = {"v1": 0, "v1_quirk": 1, "v3": 2}
 ACC_CODES = {"last": 0, "evaluate": 1}
@@ -83,6 +84,11 @@ class EvalConfig:
     # that does nothing = off, every number as without the field.  Validation stays the sparse cross-entropy.  Travels
     # beside cmoop_config like augment (cmoop_net_set_loss, cmoop_eval_population_ex)
     loss: Optional[LossConfig] = None
+    # knowledge distillation of every candidate's fit (distill.py) against the teacher PopulationEvaluator.set_teacher holds:
+    # None or alpha 0 = off, every number as without the field; enabled without a teacher is an error, raised before anything
+    # is launched.  Validation stays the sparse cross-entropy.  Travels beside cmoop_config (cmoop_net_set_distill,
+    # cmoop_eval_population_kd)
+    distill: Optional[DistillConfig] = None
 
     @staticmethod
     def preset(script: str, **over) -> "EvalConfig":
@@ -142,6 +148,15 @@ class EvalConfig:
         if self.loss is None or not self.loss.enabled:
             return None
         return self.loss.check(self.classes)._struct()
+
+    def distill_struct(self, teacher_logits, n_train: int) -> Optional["_lib.Distill"]:
+        """The enabled distillation as a ``cmoop_distill`` over the table ``teacher_logits`` (CUDA float32 [n_train,
+        classes]), checked; None when it is off.  Enabled without a table: ValueError."""
+        if self.distill is None or not self.distill.enabled:
+            return None
+        require_teacher(self.distill, teacher_logits)
+        check_teacher_table(teacher_logits, n_train, self.classes)
+        return self.distill.check(self.classes, teacher_logits, n_train)._struct(teacher_logits)
 
 
 def _as_device_features(x):
@@ -362,7 +377,23 @@ class PopulationEvaluator:
         self.last_seeds: List[int] = []     # seed of each candidate of the last evaluate_individual / population call (train_model)
         self.last_seconds: List[float] = []
         self.last_queue_stats: Dict = {}     # multi-GPU diagnostics of the last generation on THIS rank (queued_map's stats)
+        self.teacher_logits = None           # CUDA float32 [n_train, classes]: what config.distill trains against (set_teacher)
         torch.cuda.synchronize()
+
+    def set_teacher(self, teacher) -> None:
+        """The teacher ``config.distill`` trains every candidate against: a ``deploy.TrainedModel`` (any topology; its
+        classes, T and F must be this evaluator's -- its logits of the resident training rows are computed here, once) or
+        a CUDA float32 tensor [n_train, classes] of such logits; None removes it.  Offline distillation: the teacher sees
+        the plain training rows, whatever ``config.augment`` and mixup do to the candidates' batches."""
+        if teacher is None:
+            self.teacher_logits = None
+            return
+        if hasattr(teacher, "logits") and hasattr(teacher, "gene"):
+            if (int(teacher.classes), int(teacher.T), int(teacher.F)) != (int(self.config.classes), self.T, self.F):
+                raise ValueError(f"the teacher has {teacher.classes} classes on {teacher.T} x {teacher.F} patches, the evaluator "
+                                 f"{self.config.classes} on {self.T} x {self.F}")
+            teacher = teacher.logits(self.X_train)
+        self.teacher_logits = check_teacher_table(teacher, len(self.X_train), self.config.classes)
 
     # -- low level ------------------------------------------------------------
     def _dataset(self) -> "_lib.DatasetStruct":
@@ -386,7 +417,13 @@ class PopulationEvaluator:
         ep = np.zeros(n, np.int32)
         cfg, ds = self.config.to_struct(), self._dataset()
         aug, loss = self.config.augment_struct(self.T, self.F), self.config.loss_struct()
-        if loss is not None:
+        kd = self.config.distill_struct(self.teacher_logits, len(self.X_train))
+        if kd is not None:
+            _lib.check(_lib.lib().cmoop_eval_population_kd(
+                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None, C.byref(kd),
+                C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), None, None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr),
+                _lib.ptr(ep), None, _lib.ptr(secs), None))
+        elif loss is not None:
             _lib.check(_lib.lib().cmoop_eval_population_ex(
                 C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
                 C.c_int32(n), None, None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), None))
@@ -427,7 +464,13 @@ class PopulationEvaluator:
                 return -1
         cb = _lib.NEXT_FN(_next)
         aug, loss = self.config.augment_struct(self.T, self.F), self.config.loss_struct()
-        if loss is not None:
+        kd = self.config.distill_struct(self.teacher_logits, len(self.X_train))
+        if kd is not None:
+            _lib.check(_lib.lib().cmoop_eval_population_kd(
+                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None, C.byref(kd),
+                C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), C.cast(cb, C.c_void_p), None, _lib.ptr(acc), _lib.ptr(size),
+                _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
+        elif loss is not None:
             _lib.check(_lib.lib().cmoop_eval_population_ex(
                 C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
                 C.c_int32(n), C.cast(cb, C.c_void_p), None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None,
@@ -499,7 +542,7 @@ class PopulationEvaluator:
         """Train ONE candidate on the resident splits and keep its weights -> ``deploy.TrainedModel``.
 
         The body of the population call's per-candidate work (``NetSession.fit``) on the given seed and under the same
-        ``config.augment`` / ``config.loss``: with
+        ``config.augment`` / ``config.loss`` / ``config.distill`` (against the teacher of ``set_teacher``): with
         ``seed = last_seeds[i]`` it reproduces candidate i of the last generation, accuracy and FPR included.
         ``hparams`` is the reference's dict or a gene tuple; ``frontend`` / ``mean`` / ``scale`` (the front end and the
         StandardScaler the features were made with) ride along for ``StreamScorer``."""
@@ -507,7 +550,9 @@ class PopulationEvaluator:
         from .session import NetSession
         g = G.normalize_hparams(hparams) if isinstance(hparams, dict) else tuple(int(v) for v in hparams)
         G.validate_gene(g)
+        require_teacher(self.config.distill, self.teacher_logits)
         with NetSession(g, self.config, self.T, self.F, int(seed)) as net:
+            net.set_distill(teacher_logits=self.teacher_logits)      # config.distill, or off
             r = net.fit(self.X_train, self.y_train, self.X_val, self.y_val)
             params = net.get_params()
         v = G.VARIANT_NAMES[self.config.variant]

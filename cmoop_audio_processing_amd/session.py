@@ -10,6 +10,9 @@ from . import _lib, genes as G
 from .evaluator import EvalConfig
 
 
+FROM_CONFIG = object()      # set_distill's default: the session's config.distill
+
+
 class NetSession:
     def __init__(self, gene, config: EvalConfig, T: int, F: int, seed: int):
         self.gene = tuple(int(v) for v in gene)
@@ -38,6 +41,71 @@ class NetSession:
             except Exception:
                 self.close()
                 raise
+        self.distill, self._teacher_logits = None, None     # what the net trains against now (None: no distillation)
+        self._distill_pending = bool(getattr(getattr(config, "distill", None), "enabled", False))   # config.distill waits for a table
+
+    def set_distill(self, distill=FROM_CONFIG, teacher_logits=None) -> None:
+        """Knowledge distillation (``DistillConfig``) of every following train step of this net -- ``train_step``,
+        ``run_epoch`` and ``fit`` alike -- against ``teacher_logits``, a contiguous CUDA float32 [n_train, classes] table
+        of a teacher's logits of the rows those steps gather from (``predict_logits`` of the teacher); the session keeps it
+        alive.  ``distill`` defaults to the constructor's ``config.distill``: ``set_distill(teacher_logits=table)`` is how
+        that config is applied, a config alone having nothing to train against -- until then ``train_step``, ``run_epoch``
+        and ``fit`` of a session whose ``config.distill`` is enabled raise rather than train without it.  None, alpha 0 or
+        no table turns distillation off, and ``self.distill`` is then None.  Composes with ``set_loss`` and
+        ``set_augment``; ``evaluate``, ``predict_*`` and the validation loss of ``fit`` stay the sparse cross-entropy."""
+        from .distill import check_teacher_table
+        if distill is FROM_CONFIG:
+            distill = getattr(self.config, "distill", None)
+        if distill is None:
+            _lib.check(_lib.lib().cmoop_net_set_distill(self._h, None))
+            teacher_logits = None
+        else:
+            n_rows = 0
+            if teacher_logits is not None:
+                n_rows = int(getattr(teacher_logits, "shape", (0,))[0])
+                check_teacher_table(teacher_logits, n_rows, int(self.config.classes))
+            distill.check(int(self.config.classes), teacher_logits, n_rows)
+            st = distill._struct(teacher_logits)
+            _lib.check(_lib.lib().cmoop_net_set_distill(self._h, C.byref(st)))
+        on = distill is not None and distill.enabled and teacher_logits is not None
+        self.distill, self._teacher_logits = (distill, teacher_logits) if on else (None, None)
+        self._distill_pending = False
+
+    def _require_teacher(self) -> None:
+        if self._distill_pending:
+            from .distill import require_teacher
+            require_teacher(self.config.distill, None)
+
+    def predict_logits(self, X):
+        """X: CUDA float32 [n, T, F] -> CUDA float32 [n, classes]: the logits ``predict_proba`` takes the softmax of
+        (``cmoop_softmax_probs`` of them is ``predict_proba(X)`` bit for bit)."""
+        import torch
+        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 3):
+            raise ValueError("predict_logits expects a CUDA float32 tensor [n, T, F]")
+        if (int(X.shape[1]), int(X.shape[2])) != (self.T, self.F):
+            raise ValueError(f"predict_logits: rows are {int(X.shape[1])} x {int(X.shape[2])}, the net reads {self.T} x {self.F}")
+        X = X.contiguous()
+        n = int(X.shape[0])
+        out = torch.empty((n, int(self.config.classes)), dtype=torch.float32, device=X.device)
+        torch.cuda.synchronize()
+        _lib.check(_lib.lib().cmoop_net_predict_logits(self._h, _lib.ptr(X), C.c_int64(n), _lib.ptr(out)))
+        return out
+
+    def train_step_distill_targets(self, X_rows, t, q, alpha: float, temperature: float, w=None, primary=None) -> None:
+        """``train_step_targets`` with a caller-built teacher row per batch row, q CUDA float32 [B, classes], and the
+        distillation loss at (alpha, temperature), whatever ``set_distill`` says."""
+        import torch
+        B = int(X_rows.shape[0])
+        Cn = int(self.config.classes)
+        if tuple(X_rows.shape) != (B, self.T, self.F) or tuple(t.shape) != (B, Cn) or tuple(q.shape) != (B, Cn):
+            raise ValueError(f"train_step_distill_targets: rows must be [B, {self.T}, {self.F}], targets and teacher rows [B, {Cn}]")
+        for name, v, dt in (("X_rows", X_rows, torch.float32), ("t", t, torch.float32), ("q", q, torch.float32), ("w", w, torch.float32),
+                            ("primary", primary, torch.int32)):
+            if v is not None and not (v.is_cuda and v.dtype == dt and v.is_contiguous() and int(v.shape[0]) == B):
+                raise ValueError(f"train_step_distill_targets: {name} must be a contiguous CUDA {dt} tensor of {B} rows")
+        torch.cuda.synchronize()
+        _lib.check(_lib.lib().cmoop_net_train_step_distill_targets(self._h, _lib.ptr(X_rows), _lib.ptr(t), _lib.ptr(w), _lib.ptr(primary),
+                                                                   _lib.ptr(q), float(alpha), float(temperature), C.c_int32(B)))
 
     def set_loss(self, loss) -> None:
         """Soft-target training loss (``LossConfig``: mixup, label smoothing, class weights) of every following train step
@@ -118,6 +186,7 @@ class NetSession:
 
     def train_step(self, X, y, idx=None, row0: int = 0, B: int = None) -> None:
         """X: CUDA float32 [N,T,F]; y: CUDA int32 [N]; idx: CUDA int32 permutation or None."""
+        self._require_teacher()
         import torch
         torch.cuda.synchronize()
         if B is None:
@@ -199,6 +268,7 @@ class NetSession:
 
     def run_epoch(self, X, y, epoch: int) -> None:
         """One epoch of Model.fit on the trainer's own path (device permutation, device step state)."""
+        self._require_teacher()
         import torch
         torch.cuda.synchronize()
         _lib.check(_lib.lib().cmoop_net_run_epoch(self._h, _lib.ptr(X), _lib.ptr(y), C.c_int64(len(X)), C.c_int32(int(epoch))))
@@ -206,6 +276,7 @@ class NetSession:
     def fit(self, X_train, y_train, X_val, y_val):
         """evaluate_individual's fit + read-outs on this net -> dict(acc, fpr, val_loss, epochs_run, best_epoch,
         val_loss_history, val_accuracy_history)."""
+        self._require_teacher()
         import torch
         torch.cuda.synchronize()
         d = _lib.DatasetStruct()

@@ -25,7 +25,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import synth_waveforms  # noqa: E402
-from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, LossConfig, PopulationEvaluator, datasets, frontend, nsga, surrogate  # noqa: E402
+from cmoop_audio_processing_amd import (AugmentConfig, DistillConfig, EvalConfig, LossConfig, PopulationEvaluator, TrainedModel,  # noqa: E402
+                                        datasets, frontend, nsga, surrogate)
 
 
 def main():
@@ -60,6 +61,11 @@ def main():
     ap.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing eps of the training loss (0 = off)")
     ap.add_argument("--class-weight", default="", choices=["", "balanced"],
                     help="balanced: weight class c by n / (classes * count_c) of the training split (Keras' class_weight=)")
+    ap.add_argument("--teacher", default="", help="MODEL.npz (TrainedModel.save) of an already trained, larger model: every candidate is "
+                                                 "distilled against its logits of the training rows, computed once (DistillConfig; "
+                                                 "the reference has none).  Its classes and patch shape must be this run's")
+    ap.add_argument("--kd-alpha", type=float, default=0.7, help="--teacher: weight of the distillation term, in (0, 1]")
+    ap.add_argument("--kd-temperature", type=float, default=4.0, help="--teacher: temperature T of the distillation term, in [1, 64]")
     a = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -91,7 +97,10 @@ def main():
     ev = PopulationEvaluator(Xtr, ytr, Xva, yva, EvalConfig.preset(preset, classes=a.classes, epochs=a.epochs, seed=a.seed,
                                                                    verbose=(rank == 0), compute=a.compute, augment=augment,
                                                                    loss=loss if loss.enabled else None,
+                                                                   distill=DistillConfig(a.kd_alpha, a.kd_temperature) if a.teacher else None,
                                                                    **({"variant": "B_ds"} if a.space == "ds" else {})))
+    if a.teacher:
+        ev.set_teacher(TrainedModel.load(a.teacher))      # one pass of the teacher over the training rows, shared by every candidate
     calls = []
     t_start = time.perf_counter()
 

@@ -220,6 +220,57 @@ int cmoop_eval_population_ex(const cmoop_config* cfg, const cmoop_augment* aug, 
                              void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
                              double* seconds, int32_t* evaluated);
 
+/* ---- knowledge distillation: train a candidate against a teacher's tempered logits (opt-in, off by default).
+ * BUILD-DEFINED: the reference has no counterpart; with no distill config, or a disabled one, every launch and every bit is
+ * that of a build without it.  No accuracy gain is claimed.
+ * OFFLINE: the teacher's logits of the resident training rows are computed ONCE (cmoop_net_predict_logits) into one device
+ * table zt[n_rows][classes], fp32, shared by every candidate and owned by the caller for as long as anything trains on it.
+ * The teacher therefore sees the un-augmented, un-mixed row: a student row that augmentation has shifted or masked is still
+ * trained against the teacher's view of the clean row.  row(b) is the training row at batch position b, through the shuffle
+ * index, row0 and the device step state exactly as the labels, ALWAYS clamped into [0, n_rows).
+ * VALIDATION IS NEVER CHANGED, as with cmoop_loss.
+ * Teacher rows, fp32:  mx = max_j z_j, e_j = expf((z_j - mx) / T), se = sum_j e_j over ascending j, u_j = e_j / se, z =
+ *   zt[row(b)]: a row's u depends on its own logits and T only, never on the batch or its position in it.  With mixup on
+ *   and row b MIXED (the draws of cmoop_loss: the same gate, partner and lam as the row blend and the label targets),
+ *   v = the same of zt[row(partner)] and q[b][j] = lam * u_j + mu * v_j, two fp32 products and one fp32 add, each rounded
+ *   separately; an un-mixed row carries u's bits.
+ * Loss.  The step ALWAYS builds t / w / primary through cmoop_soft_targets' kernel (a default cmoop_loss: one-hot t, unit w,
+ *   primary = label), so smoothing, mixup and class weights compose.  CE_b and g_i = p_i (q'_i - sum_j p_j q'_j) are exactly
+ *   what cmoop_softmax_ce_soft forms from z, t (its l_b and, without w and / B, its dz).  With Tf = (float)T:
+ *   e_j = expf((z_j - mx) / Tf), seT = sum_j e_j, s_j = e_j / seT, ls_j = (z_j - mx) / Tf - log(seT) (no clipping), Qs = sum_j q_j
+ *   KD_b = sum over j with q_j > 0 of q_j (log(q_j) - ls_j).  KD_b and Qs s_i - q_i are small differences of large terms
+ *   (both vanish at s = q, where distillation converges to) that T^2 and T then scale: the sums seT and Qs, the two
+ *   logarithms, KD_b's sum and Qs s_i - q_i are formed in double from the fp32 e_j and q_j, the last rounded to fp32 once
+ *   loss sum += w_b ((float)(1 - alpha) CE_b + (float)(alpha T^2) KD_b);   correct += (argmax z == primary[b])
+ *   dz_i = w_b ((float)(1 - alpha) g_i + (float)(alpha T) (Qs s_i - q_i)) / B
+ * Domain: 0 <= alpha <= 1; T finite, 1 <= T <= 64; with a table, n_rows == the training rows of the call.  A config is
+ * ENABLED iff alpha > 0 and teacher_logits_dev != NULL; a disabled config is the same as no config. */
+typedef struct cmoop_distill {
+    double alpha;                    /* weight of the distillation term, 0 <= alpha <= 1; 0 = off */
+    double temperature;              /* T, finite, 1 <= T <= 64 */
+    const float* teacher_logits_dev; /* [n_rows][classes] fp32, device; NULL = off */
+    int64_t n_rows;                  /* must equal the training rows of the call (ds->n_train / gather rows) */
+} cmoop_distill;
+int cmoop_distill_default(cmoop_distill* distill); /* off: alpha 0, T 1, no table */
+/* host-only: non-zero + a message naming the offending field (alpha, temperature, n_rows) when the config is outside the
+ * domain for `classes` classes and `n_train` training rows.  n_rows is only compared when there is a table. */
+int cmoop_distill_check(const cmoop_distill* distill, int32_t classes, int64_t n_train);
+/* the teacher-targets kernel alone, on the library stream: q_dev [B][C] from zt_dev [n_rows][C] through idx_dev / row0.
+ * loss: read for the mixup draws only (NULL: no mixup). */
+int cmoop_teacher_targets(const cmoop_loss* loss /* may be NULL */, const float* zt_dev, const int32_t* idx_dev /* may be NULL */,
+                          int64_t row0, int64_t n_rows, int32_t B, int32_t C, double temperature, uint32_t seed, uint32_t step,
+                          float* q_dev);
+/* the distillation loss kernel alone: z, t, q [B][C]; w / primary / dz / preds may be NULL as in cmoop_softmax_ce_soft */
+int cmoop_softmax_ce_distill(const float* z_dev, const float* t_dev, const float* w_dev /* may be NULL */,
+                             const int32_t* primary_dev /* may be NULL */, const float* q_dev, double alpha, double temperature,
+                             int32_t B, int32_t C, float* dz_dev /* may be NULL */, double* acc_dev, int32_t* preds_dev /* may be NULL */);
+/* cmoop_eval_population_ex with every candidate's fit distilled against the table.  distill NULL or disabled: exactly
+ * cmoop_eval_population_ex. */
+int cmoop_eval_population_kd(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                             const cmoop_dataset* ds, const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n,
+                             cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
+                             double* val_loss, double* seconds, int32_t* evaluated);
+
 /* host-only: does every conv layer of this candidate at `batch` rows per launch (pass max(batch, eval_batch)) stay inside
  * the kernels' 32-bit byte offsets (each activation / kernel tensor below 2^29 elements)?  Non-zero + message if not;
  * cmoop_net_create and the population calls make the same check before they allocate anything. */
@@ -427,6 +478,18 @@ int cmoop_net_train_step_targets(cmoop_net* net, const float* x_rows_dev, const 
                                  const int32_t* primary_dev, int32_t B);
 /* floats the net has allocated for the loss: out = mixup batch buffer, t, w, primary (0: that buffer does not exist) */
 int cmoop_net_loss_buffers(cmoop_net* net, int64_t out[4]);
+/* Distillation (cmoop_distill above) of every following cmoop_net_train_step / _run_epoch / _fit step of this net (NULL or a
+ * disabled config: off, and the net steps bit for bit as one that never had one).  alpha and T are copied; the TABLE IS NOT:
+ * it must stay allocated while the net trains.  A step whose gather rows are known and differ from n_rows fails.
+ * cmoop_net_train_metrics then reports the distillation loss sum and the count of argmax z == primary. */
+int cmoop_net_set_distill(cmoop_net* net, const cmoop_distill* distill /* NULL = off */);
+/* cmoop_net_train_step_targets with a teacher row per batch row, q_dev [B][classes], and the distillation loss at
+ * (alpha, temperature), whatever cmoop_net_set_distill says. */
+int cmoop_net_train_step_distill_targets(cmoop_net* net, const float* x_rows_dev, const float* t_dev, const float* w_dev,
+                                         const int32_t* primary_dev, const float* q_dev, double alpha, double temperature, int32_t B);
+/* cmoop_net_predict with the logits themselves in place of their softmax: logits_dev [n][classes].  cmoop_softmax_probs of
+ * them is cmoop_net_predict's output bit for bit.  What a teacher hands to cmoop_distill. */
+int cmoop_net_predict_logits(cmoop_net* net, const float* x_dev /* [n][T][F] */, int64_t n, float* logits_dev /* [n][classes] */);
 /* rows the resident training tensor holds: gathered row indices are clamped into [0, n_rows) (0 = unknown, no clamp) */
 int cmoop_net_set_gather_rows(cmoop_net* net, int64_t n_rows);
 /* ONE epoch of Model.fit on the trainer's own path: epoch permutation of (seed, epoch) computed on the device when
