@@ -361,7 +361,7 @@ int cmoop_teacher_targets(const cmoop_loss* loss, const float* zt_dev, const int
         hipStream_t s = lib_stream();
         Scratch m(s);
         const MixupParams mp = scratch_mixup(c, loss_mixup_on(c) ? m.floats(MIXUP_TABLE) : nullptr, s);
-        launch_teacher_targets(zt_dev, idx_dev, row0, n_rows, B, C, (float)temperature, mp, seed, step, q_dev, s);
+        launch_teacher_targets(zt_dev, BatchRows{idx_dev, row0, n_rows}, B, C, (float)temperature, mp, seed, step, q_dev, s);
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
@@ -430,7 +430,7 @@ int cmoop_mixup_batch(const cmoop_loss* loss, const float* x_dev, const int32_t*
         hipStream_t s = lib_stream();
         Scratch m(s);
         const MixupParams mp = scratch_mixup(c, m.floats(MIXUP_TABLE), s);
-        launch_mixup_gather(x_dev, idx_dev, row0, 0, out_dev, B, T, F, mp, seed, step, s);
+        launch_mixup_gather(x_dev, BatchRows{idx_dev, row0}, 0, out_dev, B, T, F, mp, seed, step, s);
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
@@ -453,8 +453,8 @@ int cmoop_soft_targets(const cmoop_loss* loss, const int32_t* labels_dev, const 
             cw_dev = m.floats(C);
             CMOOP_HIP(hipMemcpyAsync(cw_dev, cw.data(), (size_t)C * 4, hipMemcpyHostToDevice, s));
         }
-        launch_soft_targets(labels_dev, idx_dev, row0, B, C, mp, target_params(c, C, cw_dev), seed, step, t_dev, w_dev, primary_dev, s,
-                            nullptr, n_rows);
+        launch_soft_targets(labels_dev, BatchRows{idx_dev, row0, n_rows}, B, C, mp, target_params(c, C, cw_dev), seed, step, t_dev, w_dev,
+                            primary_dev, s);
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
@@ -502,7 +502,7 @@ int cmoop_augment_batch(const cmoop_augment* aug, const float* x_dev, const int3
         augment_check(c, T, F);
         CMOOP_REQUIRE(B >= 0 && row0 >= 0 && (B == 0 || (x_dev && out_dev)), "augment_batch: bad arguments");
         hipStream_t s = lib_stream();
-        launch_augment_gather(x_dev, idx_dev, row0, out_dev, B, T, F, augment_params(c), seed, step, s);
+        launch_augment_gather(x_dev, BatchRows{idx_dev, row0}, out_dev, B, T, F, augment_params(c), seed, step, s);
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
@@ -1090,7 +1090,7 @@ int cmoop_conv_fwd(const float* x, const float* w, const float* bias, float* y, 
         Scratch m(s);
         if (Cin == 1) {
             CMOOP_REQUIRE(stride == 1 && bias, "first-layer conv: stride 1 with bias");
-            launch_conv1_fwd(x, nullptr, 0, w, bias, y, B, H, W, Cout, KS, relu, s);
+            launch_conv1_fwd(x, BatchRows(), w, bias, y, B, H, W, Cout, KS, relu, s);
         } else {
             GemmEpilogue e;
             e.bias = bias; e.relu = relu;
@@ -1113,7 +1113,7 @@ int cmoop_conv_bwd(const float* x, const float* w, const float* dy, float* dx, f
             const int nb = conv1_wgrad_blocks(B, H, W);
             const int64_t per = (int64_t)Cout * (KS * KS + 1);
             float *P = m.floats((size_t)nb * per), *tmp = m.floats((size_t)per);
-            launch_conv1_wgrad(x, nullptr, 0, dy, P, B, H, W, Cout, KS, s);
+            launch_conv1_wgrad(x, BatchRows(), dy, P, B, H, W, Cout, KS, s);
             launch_reduce_slices(P, tmp, nb, per, s);
             CMOOP_HIP(hipMemcpyAsync(dw, tmp, (size_t)Cout * KS * KS * 4, hipMemcpyDeviceToDevice, s));
             CMOOP_HIP(hipMemcpyAsync(db, tmp + (size_t)Cout * KS * KS, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
@@ -1475,7 +1475,7 @@ int cmoop_softmax_ce(const float* z, const int32_t* labels, const int32_t* idx, 
     return guard([&] {
         CMOOP_REQUIRE(B >= 0 && C >= 1 && row0 >= 0, "softmax_ce: B >= 0, C >= 1, row0 >= 0");
         hipStream_t s = lib_stream();
-        launch_softmax_ce(z, labels, idx, row0, B, C, dz, acc, preds, s, nullptr, n_rows);
+        launch_softmax_ce(z, labels, BatchRows{idx, row0, n_rows}, B, C, dz, acc, preds, s);
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }

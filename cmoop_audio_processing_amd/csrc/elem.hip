@@ -237,9 +237,8 @@ __global__ __launch_bounds__(256) void conv1_fwd_mfma_kernel(const float* __rest
     }
 }
 
-void launch_conv1_fwd(const float* X, const int32_t* idx, int64_t row0, const float* Wt, const float* bias, float* Y,
-                      int B, int H, int W, int Cout, int KS, int relu, hipStream_t s, const StepState* st, int64_t n_rows,
-                      float* stats, int* stats_blocks) {
+void launch_conv1_fwd(const float* X, const BatchRows& batch, const float* Wt, const float* bias, float* Y, int B, int H, int W,
+                      int Cout, int KS, int relu, hipStream_t s, float* stats, int* stats_blocks) {
     CMOOP_REQUIRE(Cout % 4 == 0 && Cout <= 64 && 64 % (Cout / 4) == 0 && (KS == 3 || KS == 5), "conv1: unsupported shape");
     if (stats_blocks) *stats_blocks = 0;
     // matrix-core form (default; CMOOP_CONV1_MFMA=0 keeps the VALU kernel): C_out a multiple of 16, halo image within the staging slots
@@ -257,7 +256,7 @@ void launch_conv1_fwd(const float* X, const int32_t* idx, int64_t row0, const fl
             c1_fastdiv_init(H + R, &g.vh_magic, &g.vh_shift);
             const size_t lds = std::max((size_t)rows * wp * 4 + (size_t)rows * 8, (size_t)4 * Cout * 2 * 4);
             const dim3 grid((unsigned)cdiv64(M, 256));
-#define CMOOP_C1(KS_, CT_) hipLaunchKernelGGL((conv1_fwd_mfma_kernel<KS_, CT_>), grid, dim3(256), lds, s, X, idx, row0, Wt, bias, Y, g, relu, st, n_rows, stats)
+#define CMOOP_C1(KS_, CT_) hipLaunchKernelGGL((conv1_fwd_mfma_kernel<KS_, CT_>), grid, dim3(256), lds, s, X, batch.idx, batch.row0, Wt, bias, Y, g, relu, batch.st, batch.n_rows, stats)
             if (KS == 3) { if (Cout == 16) CMOOP_C1(3, 1); else if (Cout == 32) CMOOP_C1(3, 2); else CMOOP_C1(3, 4); }
             else         { if (Cout == 16) CMOOP_C1(5, 1); else if (Cout == 32) CMOOP_C1(5, 2); else CMOOP_C1(5, 4); }
 #undef CMOOP_C1
@@ -270,8 +269,8 @@ void launch_conv1_fwd(const float* X, const int32_t* idx, int64_t row0, const fl
     const int64_t groups = (int64_t)B * H * ((W + 3) / 4);
     if (groups == 0) return;
     const dim3 grid((unsigned)cdiv64(groups, GPB));
-    if (KS == 3) hipLaunchKernelGGL(conv1_fwd_kernel<3>, grid, dim3(256), 0, s, X, idx, row0, Wt, bias, Y, B, H, W, Cout, relu, st, n_rows);
-    else hipLaunchKernelGGL(conv1_fwd_kernel<5>, grid, dim3(256), 0, s, X, idx, row0, Wt, bias, Y, B, H, W, Cout, relu, st, n_rows);
+    if (KS == 3) hipLaunchKernelGGL(conv1_fwd_kernel<3>, grid, dim3(256), 0, s, X, batch.idx, batch.row0, Wt, bias, Y, B, H, W, Cout, relu, batch.st, batch.n_rows);
+    else hipLaunchKernelGGL(conv1_fwd_kernel<5>, grid, dim3(256), 0, s, X, batch.idx, batch.row0, Wt, bias, Y, B, H, W, Cout, relu, batch.st, batch.n_rows);
     CMOOP_HIP(hipGetLastError());
 }
 
@@ -464,40 +463,40 @@ __global__ __launch_bounds__(256) void conv1_wgrad_mfma_kernel(const float* __re
 }
 
 template <int KS, int NCH>
-static void launch_conv1_wgrad_mfma(const float* X, const int32_t* idx, int64_t row0, const float* dY, float* P, int B, int H,
-                                    int W, hipStream_t s, const StepState* st, int64_t n_rows) {
+static void launch_conv1_wgrad_mfma(const float* X, const BatchRows& rows, const float* dY, float* P, int B, int H, int W,
+                                    hipStream_t s) {
     const int RC = conv1_row_chunks(B, H), W4 = (W + 3) / 4;
     const dim3 grid((unsigned)(B * RC));
     // groups of 4 pixels per row, U at a time: pick the U that wastes no masked group (W = 40: 10 groups = 2 x 5)
     if (W4 % 5 == 0)
-        hipLaunchKernelGGL((conv1_wgrad_mfma_kernel<KS, NCH, 5>), grid, dim3(256), 0, s, X, idx, row0, dY, P, H, W, RC, st, n_rows);
+        hipLaunchKernelGGL((conv1_wgrad_mfma_kernel<KS, NCH, 5>), grid, dim3(256), 0, s, X, rows.idx, rows.row0, dY, P, H, W, RC, rows.st, rows.n_rows);
     else if (W4 % 3 == 0 && W4 % 4 != 0)
-        hipLaunchKernelGGL((conv1_wgrad_mfma_kernel<KS, NCH, 3>), grid, dim3(256), 0, s, X, idx, row0, dY, P, H, W, RC, st, n_rows);
+        hipLaunchKernelGGL((conv1_wgrad_mfma_kernel<KS, NCH, 3>), grid, dim3(256), 0, s, X, rows.idx, rows.row0, dY, P, H, W, RC, rows.st, rows.n_rows);
     else
-        hipLaunchKernelGGL((conv1_wgrad_mfma_kernel<KS, NCH, 4>), grid, dim3(256), 0, s, X, idx, row0, dY, P, H, W, RC, st, n_rows);
+        hipLaunchKernelGGL((conv1_wgrad_mfma_kernel<KS, NCH, 4>), grid, dim3(256), 0, s, X, rows.idx, rows.row0, dY, P, H, W, RC, rows.st, rows.n_rows);
 }
 
-void launch_conv1_wgrad(const float* X, const int32_t* idx, int64_t row0, const float* dY, float* P, int B, int H,
-                        int W, int Cout, int KS, hipStream_t s, const StepState* st, int64_t n_rows) {
+void launch_conv1_wgrad(const float* X, const BatchRows& rows, const float* dY, float* P, int B, int H, int W, int Cout, int KS,
+                        hipStream_t s) {
     CMOOP_REQUIRE(Cout % 4 == 0 && Cout <= 64 && 64 % (Cout / 4) == 0, "conv1 wgrad: unsupported Cout");
     if (B == 0) return;
     if ((Cout == 16 || Cout == 32 || Cout == 64) && (KS == 3 || KS == 5)) {
         const int nch = Cout / 16;
         if (KS == 3) {
-            if (nch == 1) launch_conv1_wgrad_mfma<3, 1>(X, idx, row0, dY, P, B, H, W, s, st, n_rows);
-            else if (nch == 2) launch_conv1_wgrad_mfma<3, 2>(X, idx, row0, dY, P, B, H, W, s, st, n_rows);
-            else launch_conv1_wgrad_mfma<3, 4>(X, idx, row0, dY, P, B, H, W, s, st, n_rows);
+            if (nch == 1) launch_conv1_wgrad_mfma<3, 1>(X, rows, dY, P, B, H, W, s);
+            else if (nch == 2) launch_conv1_wgrad_mfma<3, 2>(X, rows, dY, P, B, H, W, s);
+            else launch_conv1_wgrad_mfma<3, 4>(X, rows, dY, P, B, H, W, s);
         } else {
-            if (nch == 1) launch_conv1_wgrad_mfma<5, 1>(X, idx, row0, dY, P, B, H, W, s, st, n_rows);
-            else if (nch == 2) launch_conv1_wgrad_mfma<5, 2>(X, idx, row0, dY, P, B, H, W, s, st, n_rows);
-            else launch_conv1_wgrad_mfma<5, 4>(X, idx, row0, dY, P, B, H, W, s, st, n_rows);
+            if (nch == 1) launch_conv1_wgrad_mfma<5, 1>(X, rows, dY, P, B, H, W, s);
+            else if (nch == 2) launch_conv1_wgrad_mfma<5, 2>(X, rows, dY, P, B, H, W, s);
+            else launch_conv1_wgrad_mfma<5, 4>(X, rows, dY, P, B, H, W, s);
         }
         CMOOP_HIP(hipGetLastError());
         return;
     }
     const int nb = conv1_wgrad_blocks(B, H, W);
-    if (KS == 3) hipLaunchKernelGGL(conv1_wgrad_kernel<3>, dim3(nb), dim3(256), 0, s, X, idx, row0, dY, P, B, H, W, Cout, st, n_rows);
-    else if (KS == 5) hipLaunchKernelGGL(conv1_wgrad_kernel<5>, dim3(nb), dim3(256), 0, s, X, idx, row0, dY, P, B, H, W, Cout, st, n_rows);
+    if (KS == 3) hipLaunchKernelGGL(conv1_wgrad_kernel<3>, dim3(nb), dim3(256), 0, s, X, rows.idx, rows.row0, dY, P, B, H, W, Cout, rows.st, rows.n_rows);
+    else if (KS == 5) hipLaunchKernelGGL(conv1_wgrad_kernel<5>, dim3(nb), dim3(256), 0, s, X, rows.idx, rows.row0, dY, P, B, H, W, Cout, rows.st, rows.n_rows);
     else CMOOP_REQUIRE(false, "conv1 wgrad: kernel size must be 3 or 5");
     CMOOP_HIP(hipGetLastError());
 }
@@ -1113,14 +1112,29 @@ void launch_gap_bwd(const float* dY, const float* X, float* dX, int B, int HW, i
 //   p = softmax(z); pc = clip(p, 1e-7, 1-1e-7); loss = -(log pc_y - log sum_j pc_j)
 // (nsga_penalty.py:377-379 via the TF backend).  One block; rows strided over
 // lanes; wavefront (shuffle) reductions for the loss / correct counters.
+//
+// ONE body for the three training losses (kernels.h: semantics), so that the loops they share -- the maximum, the sum, p,
+// pc and S, the gradient's dot product, the fixed-order reduction -- are the same text and the promise that one-hot
+// targets give the sparse loss's bits (kernels.h) cannot be broken by an edit to one of them:
+//   CE_SPARSE   the label y = labels[row(r)] read through the batch-row source
+//   CE_SOFT     a dense target row tg with weight w.  On a one-hot row with unit weight the only extra operations are
+//               1.0f * x and x + 0.0f, so the loss, dz, the predictions and the correct count carry CE_SPARSE's bits
+//   CE_DISTILL  CE_SOFT plus the tempered term: s = softmax(z / T) held as an un-clipped log-softmax against the teacher row qt
+// p and pc are recomputed in every loop that needs them, never carried from one to the next.
 // ===========================================================================
+enum CeMode { CE_SPARSE, CE_SOFT, CE_DISTILL };
+
+template <CeMode MODE>
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict__ Z, const int32_t* __restrict__ labels,
-                                                         const int32_t* __restrict__ idx, int64_t row0, int B, int C,
-                                                         float* __restrict__ dZ, double* __restrict__ acc,
-                                                         int32_t* __restrict__ preds, const StepState* __restrict__ st,
-                                                         int64_t n_rows) {
+                                                         const int32_t* __restrict__ idx, int64_t row0,
+                                                         const StepState* __restrict__ st, int64_t n_rows,
+                                                         const float* __restrict__ Tg, const float* __restrict__ Wr,
+                                                         const int32_t* __restrict__ primary, const float* __restrict__ Qt,
+                                                         DistillParams d, int B, int C, float* __restrict__ dZ,
+                                                         double* __restrict__ acc, int32_t* __restrict__ preds) {
+    constexpr bool SPARSE = MODE == CE_SPARSE, DISTILL = MODE == CE_DISTILL;
     __shared__ double lsum[4];
-    if (st) row0 = st->row0;
+    if constexpr (SPARSE) { if (st) row0 = st->row0; }
     __shared__ int csum[4];
     const int t = threadIdx.x;
     const float lo = 1e-7f, hi = 1.0f - 1e-7f;
@@ -1128,39 +1142,104 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     int mycorrect = 0;
     for (int r = t; r < B; r += 256) {
         const float* z = Z + (size_t)r * C;
-        const int y = labels[gather_row(idx, row0 + r, n_rows)];
+        const float* tg = SPARSE ? nullptr : Tg + (size_t)r * C;
+        const float* qt = DISTILL ? Qt + (size_t)r * C : nullptr;
+        float w = 1.0f;
+        int y;
+        if constexpr (SPARSE) {
+            y = labels[gather_row(idx, row0 + r, n_rows)];
+        } else {
+            if (Wr) w = Wr[r];
+            if (primary) {
+                y = primary[r];
+            } else {                           // the first maximum of the target row
+                y = 0;
+                float tm = tg[0];
+                for (int j = 1; j < C; ++j)
+                    if (tg[j] > tm) { tm = tg[j]; y = j; }
+            }
+        }
         float mx = z[0];
         int am = 0;
         for (int j = 1; j < C; ++j)
             if (z[j] > mx) { mx = z[j]; am = j; }
         float se = 0.f;
         for (int j = 0; j < C; ++j) se += expf(z[j] - mx);
-        float S = 0.f, py = 0.f, pyc = 1.f;
+        float S = 0.f, Tsum = 0.f, pyc = 1.f;
         for (int j = 0; j < C; ++j) {
             const float p = expf(z[j] - mx) / se;
             const float pc = fminf(fmaxf(p, lo), hi);
             S += pc;
-            if (j == y) { py = p; pyc = pc; }
+            if constexpr (SPARSE) { if (j == y) pyc = pc; }
+            else Tsum += tg[j];
         }
-        (void)py;
-        myloss += (double)(-(logf(pyc) - logf(S)));
+        [[maybe_unused]] double seT = 0.0, Qs = 0.0;
+        if constexpr (SPARSE) {
+            myloss += (double)(-(logf(pyc) - logf(S)));
+        } else {
+            const float logS = logf(S);
+            float l = 0.f;
+            for (int j = 0; j < C; ++j) {
+                const float tj = tg[j];
+                if (tj > 0.f) {
+                    const float p = expf(z[j] - mx) / se;
+                    const float pc = fminf(fmaxf(p, lo), hi);
+                    l += tj * (logf(pc) - logS);
+                }
+            }
+            if constexpr (!DISTILL) {
+                myloss += (double)(w * -l);
+            } else {
+                // the tempered student: e_j = expf((z_j - mx) / T), seT = sum_j e_j, ls_j = (z_j - mx) / T - log seT;
+                // KD = sum q_j (log q_j - ls_j).  Both KD and the gradient term Qs s_i - q_i are small differences of large
+                // terms -- where distillation converges to, s = q, they vanish -- and T^2 / T scale them: the sums seT and
+                // Qs, the two logarithms of KD, its sum and the difference Qs s_i - q_i are formed in double from the fp32
+                // e_j and q_j.  (The device's float32 log is low on average -- tools/device_log_bias.py,
+                // profiles/distill_logf_bias.txt -- and both logarithms enter KD with the same sign;
+                // tests/test_gpu_distill.py holds loss sum and dZ to 8 x the error of a float32 autograd restatement.)
+                for (int j = 0; j < C; ++j) {
+                    seT += (double)expf((z[j] - mx) / d.T);
+                    Qs += (double)qt[j];
+                }
+                const double logseT = log(seT);
+                double kd = 0.0;
+                for (int j = 0; j < C; ++j) {
+                    const float qj = qt[j];
+                    if (qj > 0.f) kd += (double)qj * (log((double)qj) - ((double)((z[j] - mx) / d.T) - logseT));
+                }
+                myloss += (double)w * ((double)(d.one_minus_alpha * -l) + (double)d.alpha_t2 * kd);
+            }
+        }
         mycorrect += (am == y);
         if (preds) preds[r] = am;
         if (dZ) {
-            // q_j = gate_j * (1/S - [j==y]/pc_y); dz_i = p_i * (q_i - sum_j p_j q_j), then / B
+            // q_j = gate_j * (1/S - [j==y]/pc_y), dense targets: gate_j * (Tsum/S - t_j/pc_j);
+            // g_i = p_i * (q_i - sum_j p_j q_j); dz_i = g_i / B, times w, distill: w ((1 - alpha) g_i + alpha T (Qs s_i - q_i)) / B
+            auto q_of = [&](int j, float p) -> float {
+                [[maybe_unused]] const float pc = fminf(fmaxf(p, lo), hi);
+                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
+                if constexpr (SPARSE) return gate * (1.f / S - (j == y ? 1.f / pyc : 0.f));
+                else return gate * (Tsum / S - tg[j] / pc);
+            };
             float dot = 0.f;
             for (int j = 0; j < C; ++j) {
                 const float p = expf(z[j] - mx) / se;
-                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
-                const float qj = gate * (1.f / S - (j == y ? 1.f / pyc : 0.f));
-                dot += p * qj;
+                dot += p * q_of(j, p);
             }
             const float invB = 1.f / (float)B;
+            [[maybe_unused]] const double rseT = DISTILL ? 1.0 / seT : 0.0;
             for (int j = 0; j < C; ++j) {
                 const float p = expf(z[j] - mx) / se;
-                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
-                const float qj = gate * (1.f / S - (j == y ? 1.f / pyc : 0.f));
-                dZ[(size_t)r * C + j] = p * (qj - dot) * invB;
+                const float qj = q_of(j, p);
+                if constexpr (SPARSE) {
+                    dZ[(size_t)r * C + j] = p * (qj - dot) * invB;
+                } else if constexpr (!DISTILL) {
+                    dZ[(size_t)r * C + j] = w * (p * (qj - dot) * invB);
+                } else {
+                    const float g = p * (qj - dot);
+                    const float kg = (float)(Qs * ((double)expf((z[j] - mx) / d.T) * rseT) - (double)qt[j]);   // Qs s_j - q_j
+                    dZ[(size_t)r * C + j] = w * ((d.one_minus_alpha * g + d.alpha_t * kg) * invB);
+                }
             }
         }
     }
@@ -1178,10 +1257,11 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
     }
 }
 
-void launch_softmax_ce(const float* Z, const int32_t* labels, const int32_t* idx, int64_t row0, int B, int C, float* dZ,
-                       double* acc, int32_t* preds, hipStream_t s, const StepState* st, int64_t n_rows) {
+void launch_softmax_ce(const float* Z, const int32_t* labels, const BatchRows& rows, int B, int C, float* dZ, double* acc,
+                       int32_t* preds, hipStream_t s) {
     if (B == 0) return;
-    hipLaunchKernelGGL(softmax_ce_kernel, dim3(1), dim3(256), 0, s, Z, labels, idx, row0, B, C, dZ, acc, preds, st, n_rows);
+    hipLaunchKernelGGL(softmax_ce_kernel<CE_SPARSE>, dim3(1), dim3(256), 0, s, Z, labels, rows.idx, rows.row0, rows.st, rows.n_rows,
+                       nullptr, nullptr, nullptr, nullptr, DistillParams(), B, C, dZ, acc, preds);
     CMOOP_HIP(hipGetLastError());
 }
 
@@ -1355,8 +1435,8 @@ AugmentParams augment_params(const AugmentCfg& c) {
     return a;
 }
 
-void launch_augment_gather(const float* X, const int32_t* idx, int64_t row0, float* out, int B, int T, int F, const AugmentParams& a,
-                           uint32_t seed, uint32_t step, hipStream_t s, const StepState* st, int64_t n_rows) {
+void launch_augment_gather(const float* X, const BatchRows& rows, float* out, int B, int T, int F, const AugmentParams& a,
+                           uint32_t seed, uint32_t step, hipStream_t s) {
     if (B == 0) return;
     CMOOP_REQUIRE(B >= 1 && T >= 1 && F >= 1 && X && out, "augment gather: bad arguments");
     CMOOP_REQUIRE((int64_t)T * F < (1ll << 30) && (int64_t)B * T * F < (1ll << 32), "augment gather: B * T * F must stay below 2^32");
@@ -1369,9 +1449,11 @@ void launch_augment_gather(const float* X, const int32_t* idx, int64_t row0, flo
     const int cpr = std::max(1, std::min(cdiv(TFV, 256), 2048 / B));
     const unsigned grid = (unsigned)std::min<int64_t>((int64_t)B * cpr, 2048);
     if (vec)
-        hipLaunchKernelGGL(augment_gather_kernel<4>, dim3(grid), dim3(256), 0, s, X, idx, row0, out, B, T, F, a, seed, step, cpr, st, n_rows);
+        hipLaunchKernelGGL(augment_gather_kernel<4>, dim3(grid), dim3(256), 0, s, X, rows.idx, rows.row0, out, B, T, F, a, seed, step, cpr, rows.st,
+                           rows.n_rows);
     else
-        hipLaunchKernelGGL(augment_gather_kernel<1>, dim3(grid), dim3(256), 0, s, X, idx, row0, out, B, T, F, a, seed, step, cpr, st, n_rows);
+        hipLaunchKernelGGL(augment_gather_kernel<1>, dim3(grid), dim3(256), 0, s, X, rows.idx, rows.row0, out, B, T, F, a, seed, step, cpr, rows.st,
+                           rows.n_rows);
     CMOOP_HIP(hipGetLastError());
 }
 
@@ -1432,8 +1514,8 @@ __global__ __launch_bounds__(256) void mixup_gather_kernel(const float* __restri
     }
 }
 
-void launch_mixup_gather(const float* src, const int32_t* idx, int64_t row0, int from_batch, float* out, int B, int T, int F,
-                         const MixupParams& m, uint32_t seed, uint32_t step, hipStream_t s, const StepState* st, int64_t n_rows) {
+void launch_mixup_gather(const float* src, const BatchRows& rows, int from_batch, float* out, int B, int T, int F,
+                         const MixupParams& m, uint32_t seed, uint32_t step, hipStream_t s) {
     if (B == 0) return;
     CMOOP_REQUIRE(B >= 1 && T >= 1 && F >= 1 && src && out && src != out, "mixup gather: bad arguments");
     CMOOP_REQUIRE((int64_t)T * F < (1ll << 30), "mixup gather: T * F must stay below 2^30");
@@ -1443,11 +1525,11 @@ void launch_mixup_gather(const float* src, const int32_t* idx, int64_t row0, int
     const int cpr = std::max(1, std::min(cdiv(TFV, 256), std::max(1, 2048 / B)));
     const unsigned grid = (unsigned)std::min<int64_t>((int64_t)B * cpr, 2048);
     if (vec)
-        hipLaunchKernelGGL(mixup_gather_kernel<4>, dim3(grid), dim3(256), 0, s, src, idx, row0, from_batch, out, B, TF, m, seed, step,
-                           cpr, st, n_rows);
+        hipLaunchKernelGGL(mixup_gather_kernel<4>, dim3(grid), dim3(256), 0, s, src, rows.idx, rows.row0, from_batch, out, B, TF, m,
+                           seed, step, cpr, rows.st, rows.n_rows);
     else
-        hipLaunchKernelGGL(mixup_gather_kernel<1>, dim3(grid), dim3(256), 0, s, src, idx, row0, from_batch, out, B, TF, m, seed, step,
-                           cpr, st, n_rows);
+        hipLaunchKernelGGL(mixup_gather_kernel<1>, dim3(grid), dim3(256), 0, s, src, rows.idx, rows.row0, from_batch, out, B, TF, m,
+                           seed, step, cpr, rows.st, rows.n_rows);
     CMOOP_HIP(hipGetLastError());
 }
 
@@ -1484,108 +1566,22 @@ __global__ __launch_bounds__(256) void soft_targets_kernel(const int32_t* __rest
     primary[b] = a;
 }
 
-void launch_soft_targets(const int32_t* labels, const int32_t* idx, int64_t row0, int B, int C, const MixupParams& m,
-                         const TargetParams& tp, uint32_t seed, uint32_t step, float* t, float* w, int32_t* primary, hipStream_t s,
-                         const StepState* st, int64_t n_rows) {
+void launch_soft_targets(const int32_t* labels, const BatchRows& rows, int B, int C, const MixupParams& m, const TargetParams& tp,
+                         uint32_t seed, uint32_t step, float* t, float* w, int32_t* primary, hipStream_t s) {
     if (B == 0) return;
     CMOOP_REQUIRE(B >= 1 && C >= 1 && labels && t && w && primary, "soft targets: bad arguments");
     CMOOP_REQUIRE(!m.on || m.tab != nullptr, "soft targets: the lam table is missing");
-    hipLaunchKernelGGL(soft_targets_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, labels, idx, row0, B, C, m, tp, seed, step, t, w,
-                       primary, st, n_rows);
+    hipLaunchKernelGGL(soft_targets_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, labels, rows.idx, rows.row0, B, C, m, tp, seed, step,
+                       t, w, primary, rows.st, rows.n_rows);
     CMOOP_HIP(hipGetLastError());
-}
-
-// softmax_ce_kernel with a dense target row in place of the label: the same loops in the same order for the maximum, the
-// sum, p, pc and S, the same fixed-order reduction.  On a one-hot row with unit weight the only extra operations are
-// 1.0f * x and x + 0.0f, so the loss, dz, the predictions and the correct count carry the sparse kernel's bits
-__global__ __launch_bounds__(256) void softmax_ce_soft_kernel(const float* __restrict__ Z, const float* __restrict__ Tg,
-                                                              const float* __restrict__ Wr, const int32_t* __restrict__ primary,
-                                                              int B, int C, float* __restrict__ dZ, double* __restrict__ acc,
-                                                              int32_t* __restrict__ preds) {
-    __shared__ double lsum[4];
-    __shared__ int csum[4];
-    const int t = threadIdx.x;
-    const float lo = 1e-7f, hi = 1.0f - 1e-7f;
-    double myloss = 0.0;
-    int mycorrect = 0;
-    for (int r = t; r < B; r += 256) {
-        const float* z = Z + (size_t)r * C;
-        const float* tg = Tg + (size_t)r * C;
-        const float w = Wr ? Wr[r] : 1.0f;
-        int y;
-        if (primary) {
-            y = primary[r];
-        } else {                               // the first maximum of the target row
-            y = 0;
-            float tm = tg[0];
-            for (int j = 1; j < C; ++j)
-                if (tg[j] > tm) { tm = tg[j]; y = j; }
-        }
-        float mx = z[0];
-        int am = 0;
-        for (int j = 1; j < C; ++j)
-            if (z[j] > mx) { mx = z[j]; am = j; }
-        float se = 0.f;
-        for (int j = 0; j < C; ++j) se += expf(z[j] - mx);
-        float S = 0.f, Tsum = 0.f;
-        for (int j = 0; j < C; ++j) {
-            const float p = expf(z[j] - mx) / se;
-            const float pc = fminf(fmaxf(p, lo), hi);
-            S += pc;
-            Tsum += tg[j];
-        }
-        const float logS = logf(S);
-        float l = 0.f;
-        for (int j = 0; j < C; ++j) {
-            const float tj = tg[j];
-            if (tj > 0.f) {
-                const float p = expf(z[j] - mx) / se;
-                const float pc = fminf(fmaxf(p, lo), hi);
-                l += tj * (logf(pc) - logS);
-            }
-        }
-        myloss += (double)(w * -l);
-        mycorrect += (am == y);
-        if (preds) preds[r] = am;
-        if (dZ) {
-            // q_j = gate_j * (Tsum/S - t_j/pc_j); dz_i = w * p_i * (q_i - sum_j p_j q_j), then / B
-            float dot = 0.f;
-            for (int j = 0; j < C; ++j) {
-                const float p = expf(z[j] - mx) / se;
-                const float pc = fminf(fmaxf(p, lo), hi);
-                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
-                const float qj = gate * (Tsum / S - tg[j] / pc);
-                dot += p * qj;
-            }
-            const float invB = 1.f / (float)B;
-            for (int j = 0; j < C; ++j) {
-                const float p = expf(z[j] - mx) / se;
-                const float pc = fminf(fmaxf(p, lo), hi);
-                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
-                const float qj = gate * (Tsum / S - tg[j] / pc);
-                dZ[(size_t)r * C + j] = w * (p * (qj - dot) * invB);
-            }
-        }
-    }
-    // wavefront reduction (fixed butterfly order: deterministic), then the four wave sums in wave order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        myloss += __shfl_xor(myloss, off, 64);
-        mycorrect += __shfl_xor(mycorrect, off, 64);
-    }
-    if ((t & 63) == 0) { lsum[t >> 6] = myloss; csum[t >> 6] = mycorrect; }
-    __syncthreads();
-    if (t == 0 && acc) {
-        acc[0] += ((lsum[0] + lsum[1]) + lsum[2]) + lsum[3];
-        reinterpret_cast<long long*>(acc)[1] += (csum[0] + csum[1]) + (csum[2] + csum[3]);
-    }
 }
 
 void launch_softmax_ce_soft(const float* Z, const float* t, const float* w, const int32_t* primary, int B, int C, float* dZ,
                             double* acc, int32_t* preds, hipStream_t s) {
     if (B == 0) return;
     CMOOP_REQUIRE(B >= 1 && C >= 1 && Z && t, "softmax_ce_soft: bad arguments");
-    hipLaunchKernelGGL(softmax_ce_soft_kernel, dim3(1), dim3(256), 0, s, Z, t, w, primary, B, C, dZ, acc, preds);
+    hipLaunchKernelGGL(softmax_ce_kernel<CE_SOFT>, dim3(1), dim3(256), 0, s, Z, nullptr, nullptr, 0, nullptr, 0, t, w, primary, nullptr,
+                       DistillParams(), B, C, dZ, acc, preds);
     CMOOP_HIP(hipGetLastError());
 }
 
@@ -1633,123 +1629,15 @@ __global__ __launch_bounds__(256) void teacher_targets_kernel(const float* __res
     }
 }
 
-void launch_teacher_targets(const float* zt, const int32_t* idx, int64_t row0, int64_t n_rows, int B, int C, float T,
-                            const MixupParams& m, uint32_t seed, uint32_t step, float* q, hipStream_t s, const StepState* st) {
+void launch_teacher_targets(const float* zt, const BatchRows& rows, int B, int C, float T, const MixupParams& m, uint32_t seed,
+                            uint32_t step, float* q, hipStream_t s) {
     if (B == 0) return;
-    CMOOP_REQUIRE(B >= 1 && C >= 1 && n_rows >= 1 && zt && q, "teacher targets: bad arguments");
+    CMOOP_REQUIRE(B >= 1 && C >= 1 && rows.n_rows >= 1 && zt && q, "teacher targets: bad arguments");
     CMOOP_REQUIRE(T >= 1.0f && T <= 64.0f, "teacher targets: temperature must be in [1, 64]");
     CMOOP_REQUIRE(!m.on || m.tab != nullptr, "teacher targets: the lam table is missing");
-    hipLaunchKernelGGL(teacher_targets_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, zt, idx, row0, n_rows, B, C, T, m, seed, step, q,
-                       st);
+    hipLaunchKernelGGL(teacher_targets_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, zt, rows.idx, rows.row0, rows.n_rows, B, C, T, m, seed,
+                       step, q, rows.st);
     CMOOP_HIP(hipGetLastError());
-}
-
-// softmax_ce_soft_kernel plus the tempered term: the same loops in the same order for the maximum, the sum, p, pc, S, the
-// cross-entropy l and its gradient g, then s = softmax(z / T) held as an un-clipped log-softmax against the teacher row q.
-// The same fixed-order reduction
-__global__ __launch_bounds__(256) void softmax_ce_distill_kernel(const float* __restrict__ Z, const float* __restrict__ Tg,
-                                                                 const float* __restrict__ Wr, const int32_t* __restrict__ primary,
-                                                                 const float* __restrict__ Qt, DistillParams d, int B, int C,
-                                                                 float* __restrict__ dZ, double* __restrict__ acc,
-                                                                 int32_t* __restrict__ preds) {
-    __shared__ double lsum[4];
-    __shared__ int csum[4];
-    const int t = threadIdx.x;
-    const float lo = 1e-7f, hi = 1.0f - 1e-7f;
-    double myloss = 0.0;
-    int mycorrect = 0;
-    for (int r = t; r < B; r += 256) {
-        const float* z = Z + (size_t)r * C;
-        const float* tg = Tg + (size_t)r * C;
-        const float* qt = Qt + (size_t)r * C;
-        const float w = Wr ? Wr[r] : 1.0f;
-        int y;
-        if (primary) {
-            y = primary[r];
-        } else {                               // the first maximum of the target row
-            y = 0;
-            float tm = tg[0];
-            for (int j = 1; j < C; ++j)
-                if (tg[j] > tm) { tm = tg[j]; y = j; }
-        }
-        float mx = z[0];
-        int am = 0;
-        for (int j = 1; j < C; ++j)
-            if (z[j] > mx) { mx = z[j]; am = j; }
-        float se = 0.f;
-        for (int j = 0; j < C; ++j) se += expf(z[j] - mx);
-        float S = 0.f, Tsum = 0.f;
-        for (int j = 0; j < C; ++j) {
-            const float p = expf(z[j] - mx) / se;
-            const float pc = fminf(fmaxf(p, lo), hi);
-            S += pc;
-            Tsum += tg[j];
-        }
-        const float logS = logf(S);
-        float l = 0.f;
-        for (int j = 0; j < C; ++j) {
-            const float tj = tg[j];
-            if (tj > 0.f) {
-                const float p = expf(z[j] - mx) / se;
-                const float pc = fminf(fmaxf(p, lo), hi);
-                l += tj * (logf(pc) - logS);
-            }
-        }
-        // the tempered student: e_j = expf((z_j - mx) / T), seT = sum_j e_j, ls_j = (z_j - mx) / T - log seT;
-        // KD = sum q_j (log q_j - ls_j).  Both KD and the gradient term Qs s_i - q_i are small differences of large terms --
-        // where distillation converges to, s = q, they vanish -- and T^2 / T scale them: the sums seT and Qs, the two
-        // logarithms of KD, its sum and the difference Qs s_i - q_i are formed in double from the fp32 e_j and q_j.
-        // (The device's float32 log is low on average -- tools/device_log_bias.py, profiles/distill_logf_bias.txt -- and
-        // both logarithms enter KD with the same sign; tests/test_gpu_distill.py holds loss sum and dZ to 8 x the error of a
-        // float32 autograd restatement.)
-        double seT = 0.0, Qs = 0.0;
-        for (int j = 0; j < C; ++j) {
-            seT += (double)expf((z[j] - mx) / d.T);
-            Qs += (double)qt[j];
-        }
-        const double logseT = log(seT);
-        double kd = 0.0;
-        for (int j = 0; j < C; ++j) {
-            const float qj = qt[j];
-            if (qj > 0.f) kd += (double)qj * (log((double)qj) - ((double)((z[j] - mx) / d.T) - logseT));
-        }
-        myloss += (double)w * ((double)(d.one_minus_alpha * -l) + (double)d.alpha_t2 * kd);
-        mycorrect += (am == y);
-        if (preds) preds[r] = am;
-        if (dZ) {
-            float dot = 0.f;
-            for (int j = 0; j < C; ++j) {
-                const float p = expf(z[j] - mx) / se;
-                const float pc = fminf(fmaxf(p, lo), hi);
-                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
-                const float qj = gate * (Tsum / S - tg[j] / pc);
-                dot += p * qj;
-            }
-            const float invB = 1.f / (float)B;
-            const double rseT = 1.0 / seT;
-            for (int j = 0; j < C; ++j) {
-                const float p = expf(z[j] - mx) / se;
-                const float pc = fminf(fmaxf(p, lo), hi);
-                const float gate = (p >= lo && p <= hi) ? 1.f : 0.f;
-                const float qj = gate * (Tsum / S - tg[j] / pc);
-                const float g = p * (qj - dot);
-                const float kg = (float)(Qs * ((double)expf((z[j] - mx) / d.T) * rseT) - (double)qt[j]);   // Qs s_j - q_j
-                dZ[(size_t)r * C + j] = w * ((d.one_minus_alpha * g + d.alpha_t * kg) * invB);
-            }
-        }
-    }
-    // wavefront reduction (fixed butterfly order: deterministic), then the four wave sums in wave order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        myloss += __shfl_xor(myloss, off, 64);
-        mycorrect += __shfl_xor(mycorrect, off, 64);
-    }
-    if ((t & 63) == 0) { lsum[t >> 6] = myloss; csum[t >> 6] = mycorrect; }
-    __syncthreads();
-    if (t == 0 && acc) {
-        acc[0] += ((lsum[0] + lsum[1]) + lsum[2]) + lsum[3];
-        reinterpret_cast<long long*>(acc)[1] += (csum[0] + csum[1]) + (csum[2] + csum[3]);
-    }
 }
 
 void launch_softmax_ce_distill(const float* Z, const float* t, const float* w, const int32_t* primary, const float* q,
@@ -1757,7 +1645,8 @@ void launch_softmax_ce_distill(const float* Z, const float* t, const float* w, c
     if (B == 0) return;
     CMOOP_REQUIRE(B >= 1 && C >= 1 && Z && t && q, "softmax_ce_distill: bad arguments");
     CMOOP_REQUIRE(d.T >= 1.0f && d.T <= 64.0f, "softmax_ce_distill: temperature must be in [1, 64]");
-    hipLaunchKernelGGL(softmax_ce_distill_kernel, dim3(1), dim3(256), 0, s, Z, t, w, primary, q, d, B, C, dZ, acc, preds);
+    hipLaunchKernelGGL(softmax_ce_kernel<CE_DISTILL>, dim3(1), dim3(256), 0, s, Z, nullptr, nullptr, 0, nullptr, 0, t, w, primary, q, d, B, C,
+                       dZ, acc, preds);
     CMOOP_HIP(hipGetLastError());
 }
 

@@ -122,6 +122,16 @@ struct StepState {
     unsigned iter;         // optimizer.iterations BEFORE this step's update (alpha_table[iter] is its step size)
 };
 void launch_step_advance(StepState* st, int batch, hipStream_t s);
+// Where the rows of a batch come from: batch position b is row idx[row0 + b] (idx null: row0 + b) of a resident tensor.
+// The default is "rows 0 .. B of the buffer handed in, no clamp, host arguments".
+struct BatchRows {
+    const int32_t* idx = nullptr;   // the epoch permutation (Keras' shuffle + batch gather, nsga_penalty.py:383, fused into the load)
+    int64_t row0 = 0;               // first position of the batch in idx
+    int64_t n_rows = 0;             // > 0: rows the resident tensor holds -- a gathered row is clamped into [0, n_rows) so that a
+                                    // corrupt idx can never address outside it (the only producer of idx is the device
+                                    // permutation; this is a fault fence)
+    const StepState* st = nullptr;  // non-null: row0 (and, where a kernel draws, the step) come from the device state (graph replay)
+};
 // w[i] = (float)(2 * (fmix32(prefix ^ i) >> 8) - 2^24) * scale: the seeded glorot-uniform twin of oracle/rng.py; constant fill
 void launch_glorot_init(float* w, int64_t n, uint32_t prefix, float scale, hipStream_t s);
 void launch_fill(float* w, float v, int64_t n, hipStream_t s);
@@ -150,14 +160,10 @@ void launch_dense_bwd(const float* X, const float* dY, const float* W, float* dW
 // X is the resident feature tensor [N_total, H, W]; `idx` (may be null) gathers the
 // batch rows, fusing Keras' shuffle+batch gather (nsga_penalty.py:383) into the load.
 // ---------------------------------------------------------------------------
-// st (optional): the batch's first row comes from st->row0 instead of row0
-// n_rows (optional, > 0): rows the resident tensor holds -- a gathered row index is clamped into [0, n_rows) so that a
-// corrupt idx can never address outside X (the only producer of idx is the device permutation; this is a fault fence)
 // stats / stats_blocks (optional): column partials (sum, sum of squares) of the stored output, [blocks][2][Cout] -- written by the
 // matrix-core form only (*stats_blocks = 0 otherwise: the caller then runs the stand-alone reduction)
-void launch_conv1_fwd(const float* X, const int32_t* idx, int64_t row0, const float* Wt, const float* bias,
-                      float* Y, int B, int H, int W, int Cout, int KS, int relu, hipStream_t s, const StepState* st = nullptr,
-                      int64_t n_rows = 0, float* stats = nullptr, int* stats_blocks = nullptr);
+void launch_conv1_fwd(const float* X, const BatchRows& rows, const float* Wt, const float* bias, float* Y, int B, int H, int W,
+                      int Cout, int KS, int relu, hipStream_t s, float* stats = nullptr, int* stats_blocks = nullptr);
 // Depthwise k x k convolution of the separable layers (dwconv.hip): SAME, stride 1, depth multiplier 1, no bias; NHWC fp32
 // in every gemm_mode.  C a power of two in 16..512, KS in {3, 5}, B H W C < 2^29.  Wt [KS][KS][C].
 // flip: the taps reversed -- the data gradient when X = dY; mask (optional, output-shaped): Y = mask > 0 ? Y : 0
@@ -169,8 +175,8 @@ int dwconv_wgrad_slices(int B, int H, int W, int C, int KS);
 void launch_dwconv_wgrad(const float* X, const float* dY, float* P, int B, int H, int W, int C, int KS, hipStream_t s);
 int conv1_wgrad_blocks(int B, int H, int W);
 // P[blk][Cout*(KS*KS) + Cout]: per-block partial kernel grads then bias grads
-void launch_conv1_wgrad(const float* X, const int32_t* idx, int64_t row0, const float* dY, float* P,
-                        int B, int H, int W, int Cout, int KS, hipStream_t s, const StepState* st = nullptr, int64_t n_rows = 0);
+void launch_conv1_wgrad(const float* X, const BatchRows& rows, const float* dY, float* P, int B, int H, int W, int Cout, int KS,
+                        hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Train-time augmentation of the [T][F] feature patches (opt-in; no reference counterpart): random time shift,
@@ -225,12 +231,12 @@ __host__ __device__ __forceinline__ void augment_row_draws(const AugmentParams& 
         d[11 + 2 * j] = (int32_t)augment_range(fmix32(prefix ^ (base + 11u + 2u * j)), (uint32_t)F - w + 1u);
     }
 }
-// out[B][T][F] = the augmented rows idx[row0 + b] (idx null: row0 + b) of the resident tensor X, b = 0 .. B-1.  A streaming
+// out[B][T][F] = the augmented rows (BatchRows) of the resident tensor X, b = 0 .. B-1.  A streaming
 // kernel: 16-byte loads / stores along F when F % 4 == 0 and both buffers are 16-byte aligned (a whole-frame shift keeps the
-// alignment), else element by element.  st != null: row0 and step are read from the device state (graph replay).
-// n_rows as launch_conv1_fwd's.  Needs B T F < 2^32 (the noise counter) and T F < 2^30.
-void launch_augment_gather(const float* X, const int32_t* idx, int64_t row0, float* out, int B, int T, int F, const AugmentParams& a,
-                           uint32_t seed, uint32_t step, hipStream_t s, const StepState* st = nullptr, int64_t n_rows = 0);
+// alignment), else element by element.  rows.st != null: row0 and step are read from the device state (graph replay).
+// Needs B T F < 2^32 (the noise counter) and T F < 2^30.
+void launch_augment_gather(const float* X, const BatchRows& rows, float* out, int B, int T, int F, const AugmentParams& a,
+                           uint32_t seed, uint32_t step, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Soft-target training loss (opt-in; no reference counterpart, BUILD-DEFINED -- include/cmoop.h fixes the semantics): mixup
@@ -281,23 +287,22 @@ __host__ __device__ __forceinline__ void mixup_row_draws(const MixupParams& m, u
     if (qq != b && l < 1.0f) { *q = (int32_t)qq; *lam = l; }
 }
 // out[B][T][F]: row b = lam x[b] + (1 - lam) x[q] (two fp32 products, one fp32 add, separately rounded) for a MIXED row,
-// a plain copy (bits kept, the sign of a zero included) otherwise.  from_batch == 0: x[b] = row idx[row0 + b] (idx null:
-// row0 + b) of the resident tensor src, clamped by n_rows as launch_conv1_fwd; from_batch != 0: x[b] = row b of the
-// already gathered batch buffer src (idx / row0 / n_rows unused).  st != null: step -- and, from_batch == 0 only, row0 --
-// come from the device state (graph replay).  16-byte accesses under launch_augment_gather's rule.  T F < 2^30.
-void launch_mixup_gather(const float* src, const int32_t* idx, int64_t row0, int from_batch, float* out, int B, int T, int F,
-                         const MixupParams& m, uint32_t seed, uint32_t step, hipStream_t s, const StepState* st = nullptr,
-                         int64_t n_rows = 0);
-// t[B][C], w[B], primary[B] from the labels a = y[row(b)], c = y[row(q)] (rows through idx / row0 / n_rows as above), fp32,
+// a plain copy (bits kept, the sign of a zero included) otherwise.  from_batch == 0: x[b] = row b of `rows` in the resident
+// tensor src; from_batch != 0: x[b] = row b of the already gathered batch buffer src (rows.idx / row0 / n_rows unused).
+// rows.st != null: step -- and, from_batch == 0 only, row0 -- come from the device state (graph replay).  16-byte accesses
+// under launch_augment_gather's rule.  T F < 2^30.
+void launch_mixup_gather(const float* src, const BatchRows& rows, int from_batch, float* out, int B, int T, int F,
+                         const MixupParams& m, uint32_t seed, uint32_t step, hipStream_t s);
+// t[B][C], w[B], primary[B] from the labels a = y[row(b)], c = y[row(q)] (rows through BatchRows as above), fp32,
 // every operation rounded separately:  m_j = (j == a ? lam : 0) + (j == c ? mu : 0),  mu = 1 - lam (exact);
 // t[b][j] = m_j (float)(1 - eps) + (float)(eps / C);  w[b] = lam cw[a] + mu cw[c] (1.0f without class weights);  primary[b] = a
-void launch_soft_targets(const int32_t* labels, const int32_t* idx, int64_t row0, int B, int C, const MixupParams& m,
-                         const TargetParams& tp, uint32_t seed, uint32_t step, float* t, float* w, int32_t* primary, hipStream_t s,
-                         const StepState* st = nullptr, int64_t n_rows = 0);
-// softmax + clipped cross-entropy against dense targets: p, pc = clip(p, 1e-7, 1 - 1e-7), S = sum pc by softmax_ce_kernel's
-// loops;  l_b = -sum_{t_j > 0} t_j (log pc_j - log S);  acc[0] += w_b l_b;  acc[1] += (argmax z == primary[b]);
+void launch_soft_targets(const int32_t* labels, const BatchRows& rows, int B, int C, const MixupParams& m, const TargetParams& tp,
+                         uint32_t seed, uint32_t step, float* t, float* w, int32_t* primary, hipStream_t s);
+// softmax + clipped cross-entropy against dense targets (softmax_ce_kernel<CE_SOFT>): p, pc = clip(p, 1e-7, 1 - 1e-7),
+// S = sum pc by the loops every instantiation of that kernel shares;  l_b = -sum_{t_j > 0} t_j (log pc_j - log S);
+// acc[0] += w_b l_b;  acc[1] += (argmax z == primary[b]);
 // dz_i = w_b p_i (q_i - sum_j p_j q_j) / B with q_j = gate_j (sum_j t_j / S - t_j / pc_j).  w null: 1; primary null: the
-// first maximum of t[b].  One-hot t and unit w give softmax_ce_kernel's bits (loss, dz, preds, correct)
+// first maximum of t[b].  One-hot t and unit w give softmax_ce_kernel<CE_SPARSE>'s bits (loss, dz, preds, correct)
 void launch_softmax_ce_soft(const float* Z, const float* t, const float* w, const int32_t* primary, int B, int C, float* dZ,
                             double* acc, int32_t* preds, hipStream_t s);
 
@@ -325,14 +330,14 @@ struct DistillParams {
 };
 DistillParams distill_params(const DistillCfg& c);
 // q[B][C]: u = softmax(zt[row(b)] / T) -- mx = max_j z_j, e_j = expf((z_j - mx) / T), se = sum e_j over ascending j,
-// u_j = e_j / se -- with row(b) = idx[row0 + b] (idx null: row0 + b) ALWAYS clamped into [0, n_rows), n_rows >= 1 the rows
-// of the table.  Un-mixed row: q[b] = u (its bits); MIXED row (mixup_row_draws): v the same of row(partner),
-// q[b][j] = lam u_j + mu v_j, two fp32 products and one add, separately rounded.  st != null: row0 and step come from the
-// device state (graph replay)
-void launch_teacher_targets(const float* zt, const int32_t* idx, int64_t row0, int64_t n_rows, int B, int C, float T,
-                            const MixupParams& m, uint32_t seed, uint32_t step, float* q, hipStream_t s,
-                            const StepState* st = nullptr);
-// launch_softmax_ce_soft's CE_b = l_b and g_i = p_i (q'_i - dot) from z, t, plus the tempered term against the teacher row q:
+// u_j = e_j / se -- with row(b) of `rows` ALWAYS clamped into [0, rows.n_rows), rows.n_rows >= 1 the rows of the table (no
+// "0 = no clamp" here).  Un-mixed row: q[b] = u (its bits); MIXED row (mixup_row_draws): v the same of row(partner),
+// q[b][j] = lam u_j + mu v_j, two fp32 products and one add, separately rounded.  rows.st != null: row0 and step come from
+// the device state (graph replay)
+void launch_teacher_targets(const float* zt, const BatchRows& rows, int B, int C, float T, const MixupParams& m, uint32_t seed,
+                            uint32_t step, float* q, hipStream_t s);
+// softmax_ce_kernel<CE_DISTILL>: launch_softmax_ce_soft's CE_b = l_b and g_i = p_i (q'_i - dot) from z, t (the same kernel
+// body) plus the tempered term against the teacher row q:
 //   e_j = expf((z_j - mx) / T), seT = sum e_j, s_j = e_j / seT, ls_j = (z_j - mx) / T - log(seT) (no clipping), Qs = sum_j q_j
 //   KD_b = sum_{q_j > 0} q_j (log(q_j) - ls_j);   acc[0] += w_b ((1 - alpha) CE_b + alpha T^2 KD_b).  KD_b and Qs s_i - q_i
 //   are small differences of large terms that T^2 / T then scale: seT, Qs, the two logarithms, KD's sum and
@@ -393,10 +398,11 @@ void launch_bn_pool_bwd_apply(const float* g_pooled, const uint8_t* arg, const f
 void launch_add_relu(const float* A, const float* Bt, float* Y, int64_t n, hipStream_t s);
 void launch_gap_fwd(const float* X, float* Y, int B, int HW, int C, hipStream_t s);
 void launch_gap_bwd(const float* dY, const float* X, float* dX, int B, int HW, int C, hipStream_t s);
-// softmax + clipped sparse CE (+ gradient wrt logits when dZ != null); adds into
-// acc[0] (double: sum of per-sample losses) and acc[1] (as int64: correct); writes preds when non-null.
-void launch_softmax_ce(const float* Z, const int32_t* labels, const int32_t* idx, int64_t row0, int B, int C,
-                       float* dZ, double* acc, int32_t* preds, hipStream_t s, const StepState* st = nullptr, int64_t n_rows = 0);
+// softmax + clipped sparse CE (+ gradient wrt logits when dZ != null) against labels[row(r)], rows through BatchRows
+// (softmax_ce_kernel<CE_SPARSE>); adds into acc[0] (double: sum of per-sample losses) and acc[1] (as int64: correct); writes
+// preds when non-null.
+void launch_softmax_ce(const float* Z, const int32_t* labels, const BatchRows& rows, int B, int C, float* dZ, double* acc,
+                       int32_t* preds, hipStream_t s);
 // P[r][j] = the p softmax_ce_kernel forms for row r (same loops, same order): Model.predict
 void launch_softmax_probs(const float* Z, float* P, int B, int C, hipStream_t s);
 // windows w0 .. w0 + B of a feature stream [n_frames][F] (window w = rows [w hop, w hop + T)) into chunk [B][T][F]; db: the

@@ -223,7 +223,7 @@ class Net : public GemmHook {
     // and a step's launches and allocations are those of a net that never had one.  Enabled: the domain is checked against
     // cfg.classes, the lam table and the class weights are uploaded, the target / weight / primary buffers (and, with mixup,
     // a second [cfg.batch][T][F] batch buffer) are allocated on first use; each step then blends its batch (mixup only),
-    // builds t / w / primary after the forward pass and takes softmax_ce_soft_kernel in place of softmax_ce_kernel.
+    // builds t / w / primary after the forward pass and takes softmax_ce_kernel<CE_SOFT> in place of <CE_SPARSE>.
     // evaluate / predict / predict_stream and the validation loss of a fit stay the sparse cross-entropy.  Drops a captured
     // step graph
     void set_loss(const LossCfg* loss);
@@ -233,7 +233,7 @@ class Net : public GemmHook {
     // a step's launches and bits are those of a net that never had one.  Enabled: the config is checked against cfg.classes
     // (n_rows against itself: the table's rows are what a step's gather rows must equal), q [cfg.batch][classes] and the
     // target buffers are allocated on first use; each step then builds t / w / primary (one-hot, unit weight and the label
-    // under a default loss), the teacher rows q, and takes softmax_ce_distill_kernel as its loss.  The table stays the
+    // under a default loss), the teacher rows q, and takes softmax_ce_kernel<CE_DISTILL> as its loss.  The table stays the
     // caller's and must outlive the steps.  Inference and the validation loss are untouched.  Drops a captured step graph
     void set_distill(const DistillCfg* distill);
     // rows of the resident tensor the next train steps gather from (0: unknown, no clamp)
@@ -281,9 +281,16 @@ class Net : public GemmHook {
 
   private:
     void build_plan();
-    void forward(const float* X, const int32_t* idx, int64_t row0, int B, bool train, const StepState* st = nullptr);
-    void backward(const float* X, const int32_t* idx, int64_t row0, int B, const StepState* st = nullptr);
-    void step_body(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B, const StepState* st);
+    // rows: where the batch's rows lie in X (kernels.h); the first layer clamps by rows.n_rows in training only
+    void forward(const float* X, const BatchRows& rows, int B, bool train);
+    void backward(const float* X, const BatchRows& rows, int B);
+    void step_body(const float* X, const int32_t* y, const BatchRows& rows, int B);
+    // the loss of step_body's step: the targets launches set_loss / set_distill ask for, then the matching softmax_ce launch
+    void launch_train_loss(const int32_t* y, const BatchRows& rows, int B);
+    // the explicit-targets step both train_step_*targets share: forward on the caller's B rows, the soft-target loss (kd
+    // null) or the distillation loss against q, backward, Adam, counters
+    void targets_step(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
+                      const DistillParams* kd, int B);
     void optimiser_step(int B, const StepState* st);   // the tail of a step: weight-gradient slabs summed + Adam (+ state advance)
     ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
@@ -314,7 +321,7 @@ class Net : public GemmHook {
     const float* kd_zt_ = nullptr;      // the caller's teacher table [kd_rows_][classes]
     int64_t kd_rows_ = 0;
     float* kd_q_ = nullptr;             // [cfg.batch][classes], allocated by the first enabled set_distill
-    const float* batch_in_ = nullptr;   // this train step's gathered batch (mix_buf_ / aug_buf_), null: rows come from (X, idx, row0)
+    const float* batch_in_ = nullptr;   // this train step's gathered batch (mix_buf_ / aug_buf_), null: rows come from (X, rows)
     StepState* st_dev_ = nullptr;       // device step state (train_step_stateful)
     float* alpha_tab_ = nullptr;        // Adam step size per iteration
     int64_t alpha_tab_n_ = 0, host_row0_ = 0, gather_rows_ = 0;

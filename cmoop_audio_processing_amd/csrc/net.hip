@@ -718,7 +718,7 @@ void Net::drain_profile() {
 }
 
 // ---------------------------------------------------------------------------
-void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool train, const StepState* st) {
+void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
     CMOOP_REQUIRE(B >= 1 && B <= Bmax_, "batch larger than the net was planned for");
     for (size_t oi = 0; oi < ops_.size(); ++oi) {
         const Op& op = ops_[oi];
@@ -726,10 +726,10 @@ void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool 
         case OP_CONV1: {
             fused_stats_blocks_ = 0;
             const float* bin = train ? batch_in_ : nullptr;   // the batch is rows 0 .. B of the buffer step_body's augment / mixup launch wrote
-            const bool aug = bin != nullptr;
-            launch_conv1_fwd(aug ? bin : X, aug ? nullptr : idx, aug ? 0 : row0, params_ + op.w_off, params_ + op.b_off,
-                             acts_[op.out].data, B, T_, F_, op.Cout, op.KS, op.relu, stream_, aug ? nullptr : st,
-                             (train && !aug) ? gather_rows_ : 0, (train && op.feeds_bn) ? red_ws_ : nullptr,
+            BatchRows first = bin ? BatchRows() : rows;
+            if (!train) first.n_rows = 0;
+            launch_conv1_fwd(bin ? bin : X, first, params_ + op.w_off, params_ + op.b_off, acts_[op.out].data, B, T_, F_, op.Cout,
+                             op.KS, op.relu, stream_, (train && op.feeds_bn) ? red_ws_ : nullptr,
                              (train && op.feeds_bn) ? &fused_stats_blocks_ : nullptr);
             break;
         }
@@ -752,7 +752,7 @@ void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool 
             const uint32_t drop_stream = drop ? DropoutParams::stream(op.dropout_layer) : 0u;
             launch_dense_fwd(acts_[op.in].data, params_ + op.w_off, params_ + op.b_off, acts_[op.out].data, B, op.Cout, op.Cin,
                              op.relu, drop ? 1 : 0, drop ? rng_prefix(seed_, drop_stream, (uint32_t)step_) : 0u, dp.thr,
-                             dp.keep_scale, op.gemm_mode, stream_, drop ? st : nullptr, seed_, drop_stream);
+                             dp.keep_scale, op.gemm_mode, stream_, drop ? rows.st : nullptr, seed_, drop_stream);
             break;
         }
         case OP_BN: {
@@ -801,7 +801,7 @@ void Net::forward(const float* X, const int32_t* idx, int64_t row0, int B, bool 
     }
 }
 
-void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, const StepState* st) {
+void Net::backward(const float* X, const BatchRows& rows, int B) {
     slab_segs_.clear();
     // dgrad operands: flip-transposed copies of every conv kernel, one launch for the whole net
     launch_flip_transpose_all(params_, wd_ws_, flip_table_, flip_layers_, flip_max_elems_, stream_);
@@ -887,12 +887,8 @@ void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, cons
             break;
         }
         case OP_CONV1: {
-            if (batch_in_)
-                launch_conv1_wgrad(batch_in_, nullptr, 0, acts_[op.out].grad, wgrad_ws_ + op.slab_off, B, T_, F_, op.Cout, op.KS, stream_,
-                                   nullptr, 0);
-            else
-                launch_conv1_wgrad(X, idx, row0, acts_[op.out].grad, wgrad_ws_ + op.slab_off, B, T_, F_, op.Cout, op.KS, stream_, st,
-                                   gather_rows_);
+            launch_conv1_wgrad(batch_in_ ? batch_in_ : X, batch_in_ ? BatchRows() : rows, acts_[op.out].grad, wgrad_ws_ + op.slab_off, B,
+                               T_, F_, op.Cout, op.KS, stream_);
             AdamSeg sg;
             sg.off = op.w_off;
             sg.n = sg.stride = (int64_t)op.Cout * (op.KS * op.KS + 1);
@@ -907,41 +903,43 @@ void Net::backward(const float* X, const int32_t* idx, int64_t row0, int B, cons
     }
 }
 
-// one optimiser step: forward -> loss -> backward -> Adam.  st == null: explicit host arguments (session API);
-// st != null: batch position / dropout counter / Adam iteration come from the device state, which the step advances
-void Net::step_body(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B, const StepState* st) {
+// one optimiser step: gather -> forward -> loss -> backward -> Adam.  rows.st == null: explicit host arguments (session API);
+// rows.st != null: batch position / dropout counter / Adam iteration come from the device state, which the step advances
+void Net::step_body(const float* X, const int32_t* y, const BatchRows& rows, int B) {
     // before anything is enqueued: a teacher table of another length than the split the step gathers from is refused whole
     CMOOP_REQUIRE(!distill_on_ || gather_rows_ == 0 || gather_rows_ == kd_rows_, "distill: the teacher table has " +
                   std::to_string(kd_rows_) + " rows, the training split " + std::to_string(gather_rows_));
-    // augmentation on: the batch's rows are gathered and augmented into aug_buf_ first (st != null: the kernel reads the
-    // batch position and the step from the device state, so a replayed graph draws for the step it replays)
-    if (aug_on_) launch_augment_gather(X, idx, row0, aug_buf_, B, T_, F_, aug_, seed_, (uint32_t)step_, stream_, st, gather_rows_);
+    // augmentation on: the batch's rows are gathered and augmented into aug_buf_ first (rows.st != null: the kernel reads
+    // the batch position and the step from the device state, so a replayed graph draws for the step it replays)
+    if (aug_on_) launch_augment_gather(X, rows, aug_buf_, B, T_, F_, aug_, seed_, (uint32_t)step_, stream_);
     // mixup on: the (augmented) rows are blended into mix_buf_ next; each row keeps its own batch position's augmentation
-    if (mix_on_) {
-        if (aug_on_) launch_mixup_gather(aug_buf_, nullptr, 0, 1, mix_buf_, B, T_, F_, mixp_, seed_, (uint32_t)step_, stream_, st, 0);
-        else launch_mixup_gather(X, idx, row0, 0, mix_buf_, B, T_, F_, mixp_, seed_, (uint32_t)step_, stream_, st, gather_rows_);
-    }
+    // (from the augment buffer the launch takes only the step from rows.st: the buffer always starts at its row 0)
+    if (mix_on_)
+        launch_mixup_gather(aug_on_ ? aug_buf_ : X, rows, aug_on_ ? 1 : 0, mix_buf_, B, T_, F_, mixp_, seed_, (uint32_t)step_, stream_);
     batch_in_ = mix_on_ ? mix_buf_ : (aug_on_ ? aug_buf_ : nullptr);
-    forward(X, idx, row0, B, true, st);
-    if (distill_on_) {
-        // t / w / primary as the soft-target loss builds them (a default loss: one-hot, unit weight, the label), then the
-        // teacher rows of the same batch positions under the same mixup draws
-        launch_soft_targets(y, idx, row0, B, cfg_.classes, mixp_, tgtp_, seed_, (uint32_t)step_, tgt_t_, tgt_w_, tgt_primary_, stream_,
-                            st, gather_rows_);
-        launch_teacher_targets(kd_zt_, idx, row0, kd_rows_, B, cfg_.classes, kdp_.T, mixp_, seed_, (uint32_t)step_, kd_q_, stream_, st);
-        launch_softmax_ce_distill(acts_[logits_].data, tgt_t_, tgt_w_, tgt_primary_, kd_q_, kdp_, B, cfg_.classes,
-                                  acts_[logits_].grad, acc_train_, nullptr, stream_);
-    } else if (loss_on_) {
-        launch_soft_targets(y, idx, row0, B, cfg_.classes, mixp_, tgtp_, seed_, (uint32_t)step_, tgt_t_, tgt_w_, tgt_primary_, stream_,
-                            st, gather_rows_);
-        launch_softmax_ce_soft(acts_[logits_].data, tgt_t_, tgt_w_, tgt_primary_, B, cfg_.classes, acts_[logits_].grad, acc_train_,
-                               nullptr, stream_);
-    } else {
-        launch_softmax_ce(acts_[logits_].data, y, idx, row0, B, cfg_.classes, acts_[logits_].grad, acc_train_, nullptr, stream_, st,
-                          gather_rows_);
+    forward(X, rows, B, true);
+    launch_train_loss(y, rows, B);
+    backward(X, rows, B);
+    optimiser_step(B, rows.st);
+}
+
+void Net::launch_train_loss(const int32_t* y, const BatchRows& rows, int B) {
+    float *z = acts_[logits_].data, *dz = acts_[logits_].grad;
+    if (!distill_on_ && !loss_on_) {
+        launch_softmax_ce(z, y, rows, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
+        return;
     }
-    backward(X, idx, row0, B, st);
-    optimiser_step(B, st);
+    // t / w / primary as the soft-target loss builds them (a default loss: one-hot, unit weight, the label)
+    launch_soft_targets(y, rows, B, cfg_.classes, mixp_, tgtp_, seed_, (uint32_t)step_, tgt_t_, tgt_w_, tgt_primary_, stream_);
+    if (!distill_on_) {
+        launch_softmax_ce_soft(z, tgt_t_, tgt_w_, tgt_primary_, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
+        return;
+    }
+    // the teacher rows of the same batch positions under the same mixup draws, always clamped into the teacher's own table
+    BatchRows teacher = rows;
+    teacher.n_rows = kd_rows_;
+    launch_teacher_targets(kd_zt_, teacher, B, cfg_.classes, kdp_.T, mixp_, seed_, (uint32_t)step_, kd_q_, stream_);
+    launch_softmax_ce_distill(z, tgt_t_, tgt_w_, tgt_primary_, kd_q_, kdp_, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
 }
 
 void Net::optimiser_step(int B, const StepState* st) {
@@ -978,36 +976,40 @@ void Net::optimiser_step(int B, const StepState* st) {
     if (st) launch_step_advance(st_dev_, B, stream_);
 }
 
+// profiling_now_ for the length of one step: false again however the step ends, a throw included
+struct ProfilingScope {
+    bool& flag;
+    ProfilingScope(bool& f, bool on) : flag(f) { flag = on; }
+    ~ProfilingScope() { flag = false; }
+};
+
 void Net::train_step(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B) {
     CMOOP_REQUIRE(B >= 1 && B <= cfg_.batch, "train batch larger than configured");
-    profiling_now_ = cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0;
-    step_body(X, y, idx, row0, B, nullptr);
+    ProfilingScope prof(profiling_now_, cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0);
+    step_body(X, y, BatchRows{idx, row0, gather_rows_, nullptr}, B);
     ++iterations_;
     ++step_;
-    profiling_now_ = false;
+}
+
+void Net::targets_step(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
+                       const DistillParams* kd, int B) {
+    ProfilingScope prof(profiling_now_, cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0);
+    batch_in_ = nullptr;
+    const BatchRows rows;      // x_rows holds exactly the B rows of this step: no resident tensor to clamp into
+    float *z = acts_[logits_].data, *dz = acts_[logits_].grad;
+    forward(x_rows, rows, B, true);
+    if (kd) launch_softmax_ce_distill(z, t, w, primary, q, *kd, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
+    else launch_softmax_ce_soft(z, t, w, primary, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
+    backward(x_rows, rows, B);
+    optimiser_step(B, nullptr);
+    ++iterations_;
+    ++step_;
 }
 
 void Net::train_step_targets(const float* x_rows, const float* t, const float* w, const int32_t* primary, int B) {
     CMOOP_REQUIRE(B >= 1 && B <= cfg_.batch, "train batch larger than configured");
     CMOOP_REQUIRE(x_rows && t, "train_step_targets: NULL rows or targets");
-    profiling_now_ = cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0;
-    const int64_t rows = gather_rows_;
-    gather_rows_ = 0;          // x_rows holds exactly the B rows of this step: no resident tensor to clamp into
-    batch_in_ = nullptr;
-    try {
-        forward(x_rows, nullptr, 0, B, true, nullptr);
-        launch_softmax_ce_soft(acts_[logits_].data, t, w, primary, B, cfg_.classes, acts_[logits_].grad, acc_train_, nullptr, stream_);
-        backward(x_rows, nullptr, 0, B, nullptr);
-        optimiser_step(B, nullptr);
-    } catch (...) {
-        gather_rows_ = rows;
-        profiling_now_ = false;
-        throw;
-    }
-    gather_rows_ = rows;
-    ++iterations_;
-    ++step_;
-    profiling_now_ = false;
+    targets_step(x_rows, t, w, primary, nullptr, nullptr, B);
 }
 
 void Net::train_step_distill_targets(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
@@ -1018,25 +1020,7 @@ void Net::train_step_distill_targets(const float* x_rows, const float* t, const 
     dc.alpha = alpha; dc.temperature = temperature;
     distill_check(dc, cfg_.classes, 0);
     const DistillParams dp = distill_params(dc);
-    profiling_now_ = cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0;
-    const int64_t rows = gather_rows_;
-    gather_rows_ = 0;          // x_rows holds exactly the B rows of this step: no resident tensor to clamp into
-    batch_in_ = nullptr;
-    try {
-        forward(x_rows, nullptr, 0, B, true, nullptr);
-        launch_softmax_ce_distill(acts_[logits_].data, t, w, primary, q, dp, B, cfg_.classes, acts_[logits_].grad, acc_train_, nullptr,
-                                  stream_);
-        backward(x_rows, nullptr, 0, B, nullptr);
-        optimiser_step(B, nullptr);
-    } catch (...) {
-        gather_rows_ = rows;
-        profiling_now_ = false;
-        throw;
-    }
-    gather_rows_ = rows;
-    ++iterations_;
-    ++step_;
-    profiling_now_ = false;
+    targets_step(x_rows, t, w, primary, q, &dp, B);
 }
 
 void Net::begin_fit(int64_t total_steps) {
@@ -1076,7 +1060,8 @@ void Net::train_step_stateful(const float* X, const int32_t* y, const int32_t* i
         return;
     }
     CMOOP_REQUIRE(iterations_ < alpha_tab_n_, "train_step_stateful outside begin_fit's step budget");
-    profiling_now_ = cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0;
+    ProfilingScope prof(profiling_now_, cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0);
+    const BatchRows rows{idx, 0, gather_rows_, st_dev_};
     bool replayed = false;
     if (graph_ok_ && B == cfg_.batch && !profiling_now_ && step_ >= 1) {
         if (!graph_exec_) {   // capture the step once (thread-local mode: the other candidates' threads keep launching)
@@ -1084,7 +1069,7 @@ void Net::train_step_stateful(const float* X, const int32_t* y, const int32_t* i
             bool ok = hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal) == hipSuccess;
             if (ok) {
                 try {
-                    step_body(X, y, idx, 0, B, st_dev_);
+                    step_body(X, y, rows, B);
                 } catch (...) {
                     hipStreamEndCapture(stream_, &graph);
                     if (graph) hipGraphDestroy(graph);
@@ -1105,10 +1090,9 @@ void Net::train_step_stateful(const float* X, const int32_t* y, const int32_t* i
             replayed = true;
         }
     }
-    if (!replayed) step_body(X, y, idx, 0, B, st_dev_);
+    if (!replayed) step_body(X, y, rows, B);
     ++iterations_;
     ++step_;
-    profiling_now_ = false;
 }
 
 void Net::get_state(float* params, float* m, float* v, long long* iterations, long long* steps) {
@@ -1258,9 +1242,9 @@ void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum
     CMOOP_HIP(hipMemsetAsync(acc_eval_, 0, 16, stream_));
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
-        forward(X, nullptr, s, B, false);
-        launch_softmax_ce(acts_[logits_].data, y, nullptr, s, B, cfg_.classes, nullptr, acc_eval_, preds ? preds + s : nullptr,
-                          stream_);
+        const BatchRows rows{nullptr, s};
+        forward(X, rows, B, false);
+        launch_softmax_ce(acts_[logits_].data, y, rows, B, cfg_.classes, nullptr, acc_eval_, preds ? preds + s : nullptr, stream_);
     }
     double host[2];
     CMOOP_HIP(hipMemcpyAsync(host, acc_eval_, 16, hipMemcpyDeviceToHost, stream_));
@@ -1273,7 +1257,7 @@ void Net::predict(const float* X, int64_t n, float* probs) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && probs)), "predict: NULL buffer");
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
-        forward(X, nullptr, s, B, false);
+        forward(X, BatchRows{nullptr, s}, B, false);
         launch_softmax_probs(acts_[logits_].data, probs + s * cfg_.classes, B, cfg_.classes, stream_);
     }
     CMOOP_HIP(hipStreamSynchronize(stream_));
@@ -1283,7 +1267,7 @@ void Net::predict_logits(const float* X, int64_t n, float* logits) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && logits)), "predict_logits: NULL buffer");
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
-        forward(X, nullptr, s, B, false);
+        forward(X, BatchRows{nullptr, s}, B, false);
         CMOOP_HIP(hipMemcpyAsync(logits + s * cfg_.classes, acts_[logits_].data, (size_t)B * cfg_.classes * 4, hipMemcpyDeviceToDevice,
                                  stream_));
     }
@@ -1314,7 +1298,7 @@ void Net::predict_stream(const float* feat, int64_t n_frames, int hop, bool db_s
             const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - w);
             launch_window_gather(feat, chunk, w, B, hop, T_, F_, db_scale ? 1 : 0, db_ref_max ? 1 : 0, db_amin, top_db, ms,
                                  ms ? ms + F_ : nullptr, stream_);
-            forward(chunk, nullptr, 0, B, false);
+            forward(chunk, BatchRows(), B, false);
             launch_softmax_probs(acts_[logits_].data, probs + w * cfg_.classes, B, cfg_.classes, stream_);
         }
     } catch (...) {

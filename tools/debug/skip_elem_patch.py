@@ -1,7 +1,8 @@
 # TEMPORARY timing experiment, never committed applied: rewrites elem.hip / dense.hip / gemm.hip so that the bit mask in
 # CMOOP_DEBUG_SKIP_ELEM drops whole kernel families (results are garbage, only the wall time means something):
 #   1 BatchNorm (statistics finalize, apply, fused pool forms, backward reduce / apply)   2 first conv (C_in = 1) fwd / wgrad
-#   4 dense head + GAP + softmax-CE                                                        8 max-pool, add+ReLU
+#   4 dense head + GAP + softmax-CE (softmax_ce_kernel<...>: all three training losses)
+#                                                                                          8 max-pool, add+ReLU
 #  16 Adam (with the slab sums), step state                                               32 split-K combine + flip-transpose
 # Apply, make, run tools/debug/skip_run.sh on the GPU, then `git checkout` the three files and rebuild.
 import re
