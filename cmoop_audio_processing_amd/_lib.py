@@ -57,6 +57,14 @@ class Distill(C.Structure):
     _fields_ = [("alpha", C.c_double), ("temperature", C.c_double), ("teacher_logits_dev", C.c_void_p), ("n_rows", C.c_int64)]
 
 
+class Optim(C.Structure):
+    """cmoop_optim (include/cmoop.h), 224 bytes."""
+    _fields_ = [("weight_decay", C.c_double), ("global_clipnorm", C.c_double), ("clipvalue", C.c_double), ("warmup_start", C.c_double),
+                ("alpha", C.c_double), ("decay_rate", C.c_double), ("values", C.c_double * 9), ("warmup_steps", C.c_int64),
+                ("decay_steps", C.c_int64), ("boundaries", C.c_int64 * 8), ("schedule", C.c_int32), ("staircase", C.c_int32),
+                ("decay_mask", C.c_int32), ("n_boundaries", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 #: cmoop_next_fn (include/cmoop.h): int32_t (*)(void* ctx)
 NEXT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
@@ -114,6 +122,20 @@ DISTILL_PROTOTYPES = {
     "cmoop_net_train_step_distill_targets": [C.c_void_p] * 6 + [C.c_double, C.c_double, C.c_int32],
     "cmoop_net_predict_logits": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "cmoop_eval_population_kd": [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 7,
+}
+
+
+#: prototypes of the optimiser-option entry points (include/cmoop.h); structs travel as void* (C.byref), None is NULL
+OPTIM_PROTOTYPES = {
+    "cmoop_optim_default": [C.c_void_p],
+    "cmoop_optim_check": [C.c_void_p],
+    "cmoop_optim_rates": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_param_kinds": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64],
+    "cmoop_grad_finish": [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+    "cmoop_adamw": [C.c_void_p] * 5 + [C.c_int64, C.c_void_p] + [C.c_double] * 6 + [C.c_int32, C.c_double],
+    "cmoop_net_set_optim": [C.c_void_p, C.c_void_p],
+    "cmoop_net_optim_stats": [C.c_void_p, C.c_void_p],
+    "cmoop_eval_population_opt": [C.c_void_p] * 8 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 7,
 }
 
 
@@ -212,7 +234,7 @@ def lib():
         L.cmoop_config_default.restype = None
         for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(PCEN_PROTOTYPES.items()) + \
                 list(ELEM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(DWCONV_PROTOTYPES.items()) + \
-                list(DISTILL_PROTOTYPES.items()):
+                list(DISTILL_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         _lib = L
         return L

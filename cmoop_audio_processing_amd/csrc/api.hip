@@ -157,6 +157,19 @@ static DistillCfg to_distill(const cmoop_distill* d) {   // the table stays the 
     return c;
 }
 
+static_assert(sizeof(cmoop_optim) == 224, "cmoop_optim is part of the ABI");
+static OptimCfg to_optim(const cmoop_optim* o) {
+    CMOOP_REQUIRE(o != nullptr, "optim config is NULL");
+    OptimCfg c;
+    c.schedule = o->schedule; c.staircase = o->staircase; c.decay_mask = o->decay_mask; c.n_boundaries = o->n_boundaries;
+    c.warmup_steps = o->warmup_steps; c.decay_steps = o->decay_steps;
+    c.warmup_start = o->warmup_start; c.alpha = o->alpha; c.decay_rate = o->decay_rate;
+    std::copy(o->boundaries, o->boundaries + OPTIM_MAX_BOUNDARIES, c.boundaries);
+    std::copy(o->values, o->values + OPTIM_MAX_BOUNDARIES + 1, c.values);
+    c.weight_decay = o->weight_decay; c.global_clipnorm = o->global_clipnorm; c.clipvalue = o->clipvalue;
+    return c;
+}
+
 static Dataset to_dataset(const cmoop_dataset* ds) {
     Dataset d;
     d.x_train = ds->x_train; d.y_train = ds->y_train; d.n_train = ds->n_train;
@@ -251,8 +264,8 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 
 // every population call; next == NULL: candidates are taken longest-first from a process-local counter; aug == NULL: no augmentation
 static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss,
-                                const cmoop_distill* distill, const cmoop_dataset* ds, const int32_t* genes,
-                                const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
+                                const cmoop_distill* distill, const cmoop_optim* optim, const cmoop_dataset* ds,
+                                const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
                                 double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
     CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
     CMOOP_REQUIRE(n >= 0, "negative population size");
@@ -274,12 +287,18 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* au
         dc = to_distill(distill);
         distill_check(dc, c.classes, d.n_train);
     }
+    OptimCfg oc;
+    if (optim) {
+        oc = to_optim(optim);
+        optim_check(oc);
+    }
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
     if (next) eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); }, aug ? &a : nullptr, loss ? &lc : nullptr,
-                              distill ? &dc : nullptr);
-    else eval_population(c, d, genes, seeds, n, r.data(), {}, aug ? &a : nullptr, loss ? &lc : nullptr, distill ? &dc : nullptr);
+                              distill ? &dc : nullptr, optim ? &oc : nullptr);
+    else eval_population(c, d, genes, seeds, n, r.data(), {}, aug ? &a : nullptr, loss ? &lc : nullptr, distill ? &dc : nullptr,
+                         optim ? &oc : nullptr);
     for (int i = 0; i < n; ++i) {
         if (evaluated) evaluated[i] = r[i].evaluated;
         if (acc) acc[i] = r[i].acc;
@@ -324,9 +343,55 @@ int cmoop_eval_population_kd(const cmoop_config* cfg, const cmoop_augment* aug, 
                              const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next,
                              void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
                              double* seconds, int32_t* evaluated) {
+    return cmoop_eval_population_opt(cfg, aug, loss, distill, nullptr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run,
+                                     val_loss, seconds, evaluated);
+}
+
+int cmoop_eval_population_opt(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                              const cmoop_optim* optim, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n,
+                              cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
+                              double* val_loss, double* seconds, int32_t* evaluated) {
     return guard([&] {
-        eval_population_abi(cfg, aug, loss, distill, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss, seconds,
-                            evaluated);
+        eval_population_abi(cfg, aug, loss, distill, optim, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss,
+                            seconds, evaluated);
+    });
+}
+
+// ---- optimiser options ----------------------------------------------------------
+int cmoop_optim_default(cmoop_optim* optim) {
+    return guard([&] {
+        CMOOP_REQUIRE(optim != nullptr, "optim config is NULL");
+        std::memset(optim, 0, sizeof(*optim));
+    });
+}
+
+int cmoop_optim_check(const cmoop_optim* optim) {
+    return guard([&] { optim_check(to_optim(optim)); });
+}
+
+int cmoop_optim_rates(const cmoop_optim* optim, const cmoop_config* cfg, int64_t iteration, double* lr, float* lr_f32, float* alpha_f32) {
+    return guard([&] {
+        CMOOP_REQUIRE(cfg != nullptr, "optim_rates: config is NULL");
+        OptimCfg c;
+        if (optim) {
+            c = to_optim(optim);
+            optim_check(c);
+        }
+        const OptimRates r = optim_rates(c, cfg->lr, cfg->beta1, cfg->beta2, iteration);
+        if (lr) *lr = r.lr;
+        if (lr_f32) *lr_f32 = r.lr_f32;
+        if (alpha_f32) *alpha_f32 = r.alpha_f32;
+    });
+}
+
+int cmoop_param_kinds(const int32_t gene[6], int32_t variant, int32_t classes, uint8_t* kinds, int64_t n) {
+    return guard([&] {
+        CMOOP_REQUIRE(gene && kinds, "param_kinds: NULL argument");
+        NetConfig c;
+        c.variant = variant; c.classes = classes;
+        const std::vector<uint8_t> k = plan_net(gene, c, 32, 32).param_kinds();   // parameter offsets do not depend on T, F
+        CMOOP_REQUIRE((int64_t)k.size() == n, "param_kinds: n must be the candidate's parameter count");
+        std::copy(k.begin(), k.end(), kinds);
     });
 }
 
@@ -971,6 +1036,20 @@ int cmoop_net_set_distill(cmoop_net* h, const cmoop_distill* distill) {
         h->net->set_distill(&c);
     });
 }
+int cmoop_net_set_optim(cmoop_net* h, const cmoop_optim* optim) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "set_optim: NULL net");
+        if (!optim) { h->net->set_optim(nullptr); return; }
+        const OptimCfg c = to_optim(optim);
+        h->net->set_optim(&c);
+    });
+}
+int cmoop_net_optim_stats(cmoop_net* h, double out[4]) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net && out, "optim_stats: NULL argument");
+        h->net->optim_stats(out);
+    });
+}
 int cmoop_net_train_step_distill_targets(cmoop_net* h, const float* x_rows, const float* t, const float* w, const int32_t* primary,
                                          const float* q, double alpha, double temperature, int32_t B) {
     return guard([&] {
@@ -1495,24 +1574,60 @@ int cmoop_adam(float* w, const float* g, float* m, float* v, int64_t n, double a
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
+// the segment table of the host arrays cmoop_adam_segments / cmoop_grad_finish take
+static AdamSegTable segment_table(const float* slab, int32_t count, const int64_t* off, const int64_t* n, const int32_t* S,
+                                  const int64_t* stride, const int64_t* slab_off) {
+    CMOOP_REQUIRE(count >= 0 && count <= ADAM_MAX_SEGS, "adam_segments: at most 64 segments");
+    CMOOP_REQUIRE(count == 0 || (off && n && S && stride && slab_off), "adam_segments: NULL segment array");
+    AdamSegTable tab;
+    for (int i = 0; i < count; ++i) {
+        AdamSeg sg;
+        sg.off = off[i]; sg.n = n[i];
+        CMOOP_REQUIRE(S[i] >= 0 && (S[i] == 0 || (slab && stride[i] >= n[i] && slab_off[i] >= 0)),
+                      "adam_segments: a slab segment needs the slab buffer, stride >= n and slab_off >= 0");
+        if (S[i] > 0) { sg.slab = slab + slab_off[i]; sg.stride = stride[i]; sg.S = S[i]; }
+        tab.seg[tab.count++] = sg;
+    }
+    adam_segments_finalize(tab);
+    return tab;
+}
 int cmoop_adam_segments(float* w, float* g, float* m, float* v, const float* slab, int32_t count, const int64_t* off,
                         const int64_t* n, const int32_t* S, const int64_t* stride, const int64_t* slab_off, double alpha,
                         double beta1, double beta2, double eps) {
     return guard([&] {
-        CMOOP_REQUIRE(count >= 0 && count <= ADAM_MAX_SEGS, "adam_segments: at most 64 segments");
-        CMOOP_REQUIRE(count == 0 || (off && n && S && stride && slab_off), "adam_segments: NULL segment array");
-        AdamSegTable tab;
-        for (int i = 0; i < count; ++i) {
-            AdamSeg sg;
-            sg.off = off[i]; sg.n = n[i];
-            CMOOP_REQUIRE(S[i] >= 0 && (S[i] == 0 || (slab && stride[i] >= n[i] && slab_off[i] >= 0)),
-                          "adam_segments: a slab segment needs the slab buffer, stride >= n and slab_off >= 0");
-            if (S[i] > 0) { sg.slab = slab + slab_off[i]; sg.stride = stride[i]; sg.S = S[i]; }
-            tab.seg[tab.count++] = sg;
-        }
-        adam_segments_finalize(tab);
+        const AdamSegTable tab = segment_table(slab, count, off, n, S, stride, slab_off);
         hipStream_t s = lib_stream();
         launch_adam_segments(w, g, m, v, tab, (float)alpha, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+int cmoop_grad_finish(float* g, const float* slab, int32_t count, const int64_t* off, const int64_t* n, const int32_t* S,
+                      const int64_t* stride, const int64_t* slab_off, const uint8_t* kinds, double global_clipnorm, float* partials,
+                      int32_t cap, int32_t* n_partials, void* record) {
+    return guard([&] {
+        CMOOP_REQUIRE(std::isfinite(global_clipnorm) && global_clipnorm >= 0, "grad_finish: global_clipnorm must be finite and >= 0");
+        CMOOP_REQUIRE(partials && record, "grad_finish: NULL partial buffer or record");
+        const AdamSegTable tab = segment_table(slab, count, off, n, S, stride, slab_off);
+        CMOOP_REQUIRE(tab.blocks <= cap, "grad_finish: the partial buffer holds fewer than " + std::to_string(tab.blocks) + " floats");
+        hipStream_t s = lib_stream();
+        launch_grad_finish(g, tab, kinds, partials, s);
+        launch_clip_scale(partials, tab.blocks, global_clipnorm, static_cast<OptimRecord*>(record), s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+        if (n_partials) *n_partials = tab.blocks;
+    });
+}
+int cmoop_adamw(float* w, const float* g, float* m, float* v, const uint8_t* kinds, int64_t n, const void* record, double alpha,
+                double lr, double beta1, double beta2, double eps, double weight_decay, int32_t decay_mask, double clipvalue) {
+    return guard([&] {
+        CMOOP_REQUIRE(n >= 0 && record, "adamw: n >= 0 and a record");
+        OptimCfg c;
+        c.weight_decay = weight_decay; c.decay_mask = decay_mask; c.clipvalue = clipvalue;
+        optim_check(c);
+        AdamwArgs a;
+        a.alpha = (float)alpha; a.lr = (float)lr; a.c1 = (float)(1.0 - beta1); a.c2 = (float)(1.0 - beta2); a.eps = (float)eps;
+        a.weight_decay = (float)weight_decay; a.clipvalue = (float)clipvalue; a.decay_all = decay_mask;
+        hipStream_t s = lib_stream();
+        launch_adamw(w, g, m, v, kinds, n, static_cast<const OptimRecord*>(record), a, s);
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }

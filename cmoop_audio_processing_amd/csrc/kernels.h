@@ -431,6 +431,50 @@ struct AdamSegTable {
 void adam_segments_finalize(AdamSegTable& tab);
 void launch_adam_segments(float* w, float* g, float* m, float* v, const AdamSegTable& tab, float alpha, float c1, float c2,
                           float eps, hipStream_t s, const StepState* st = nullptr, const float* alpha_table = nullptr);
+// ---------------------------------------------------------------------------
+// Optimiser options (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_optim): a learning-rate schedule,
+// decoupled weight decay, global-norm / value clipping.  A schedule alone only changes the step-size table of the fused
+// launch above.  Decay or a clip take the FINISH + UPDATE path, three launches on one stream: launch_grad_finish (slab
+// sums stored to g, one fp32 partial of sum g^2 per workgroup) -> launch_clip_scale (partials summed in double, the
+// OptimRecord written) -> launch_adamw (clip, decay, adam_update).
+// ---------------------------------------------------------------------------
+constexpr int OPTIM_MAX_BOUNDARIES = 8;
+struct OptimCfg {
+    int schedule = 0;              // 0 constant, 1 cosine (+ linear warm-up), 2 exponential, 3 piecewise constant
+    int staircase = 0, decay_mask = 0, n_boundaries = 0;
+    int64_t warmup_steps = 0, decay_steps = 0;
+    double warmup_start = 0, alpha = 0, decay_rate = 0;
+    int64_t boundaries[OPTIM_MAX_BOUNDARIES] = {};
+    double values[OPTIM_MAX_BOUNDARIES + 1] = {};
+    double weight_decay = 0, global_clipnorm = 0, clipvalue = 0;
+};
+// host-only: throws with a message naming the offending field
+void optim_check(const OptimCfg& c);
+inline bool optim_finish_path(const OptimCfg& c) { return c.weight_decay > 0 || c.global_clipnorm > 0 || c.clipvalue > 0; }
+inline bool optim_enabled(const OptimCfg& c) { return c.schedule != 0 || optim_finish_path(c); }
+// host-only, THE place of the rates: lr(i) = base_lr f(i) in double, and the two fp32 values the kernels consume --
+// (float)lr(i) (decay) and the bias-corrected step size (float)(lr(i) sqrt(1 - b2^t) / (1 - b1^t)), t = i + 1
+struct OptimRates { double lr; float lr_f32, alpha_f32; };
+OptimRates optim_rates(const OptimCfg& c, double base_lr, double beta1, double beta2, int64_t iteration);
+// tensor kind of a parameter (one byte per arena element): decay_mask 0 decays KIND_KERNEL only; KIND_FROZEN (BatchNorm
+// moving statistics) is never decayed, never in the norm, never updated
+enum ParamKind : uint8_t { KIND_KERNEL = 0, KIND_TRAINABLE = 1, KIND_FROZEN = 2 };
+struct OptimRecord { double sumsq; float norm, scale; };   // what launch_clip_scale leaves on the device
+// g finished as launch_adam_segments finishes it (no weight moves); partials[b] = workgroup b's sum of g^2 over its
+// non-frozen elements (kinds null: all trainable).  tab.blocks partials are written
+void launch_grad_finish(float* g, const AdamSegTable& tab, const uint8_t* kinds, float* partials, hipStream_t s);
+// rec = {sum of the partials in double, sqrt of it, clip / norm where norm > clip > 0 else exactly 1}
+void launch_clip_scale(const float* partials, int n_partials, double clip, OptimRecord* rec, hipStream_t s);
+struct AdamwArgs {
+    float alpha, lr, c1, c2, eps;  // alpha / lr: used when st is null
+    float weight_decay, clipvalue; // 0: off
+    int clip_norm, decay_all;      // clip_norm: g *= rec->scale; decay_all: decay_mask 1
+};
+// st != null: alpha = alpha_table[st->iter], lr = lr_table[st->iter]
+void launch_adamw(float* w, const float* g, float* m, float* v, const uint8_t* kinds, int64_t n, const OptimRecord* rec,
+                  const AdamwArgs& a, hipStream_t s, const StepState* st = nullptr, const float* alpha_table = nullptr,
+                  const float* lr_table = nullptr);
+
 // device twin of epoch_permutation (net.h): out[rank of key_i] = i; n <= EPOCH_PERMUTATION_DEVICE_MAX (O(n^2) rank sort)
 constexpr int64_t EPOCH_PERMUTATION_DEVICE_MAX = 262144;
 void launch_epoch_permutation(uint32_t seed, uint32_t epoch, int64_t n, int32_t* out, hipStream_t s);

@@ -185,6 +185,9 @@ struct NetPlan {
     std::vector<Op> ops;
     int logits = -1;
     int64_t n_params = 0;
+    // ParamKind of every arena element: conv / depthwise / pointwise / dense kernels, other trainable tensors (biases, gamma,
+    // beta), BatchNorm moving statistics
+    std::vector<uint8_t> param_kinds() const;
     // the net's shared split-K workspace for train batch `batch` and Bmax = max(batch, eval_batch)
     size_t splitk_floats(int batch, int Bmax) const;
     // ';'-joined launch-path variants (gemm_variant_name) of the MFMA conv launches of one train step (forward with the
@@ -236,6 +239,14 @@ class Net : public GemmHook {
     // under a default loss), the teacher rows q, and takes softmax_ce_kernel<CE_DISTILL> as its loss.  The table stays the
     // caller's and must outlive the steps.  Inference and the validation loss are untouched.  Drops a captured step graph
     void set_distill(const DistillCfg* distill);
+    // Optimiser options (kernels.h) of every following train step, both step paths; null or a disabled config: off, and a
+    // step's launches and bits are those of a net that never had one.  A schedule alone keeps the fused optimiser launch and
+    // only changes the step-size table (rebuilt here when a fit is under way).  Weight decay or a clip: the finish + update
+    // path (grad_finish -> clip_scale -> adamw); the kind arena, the partial buffer (sized once for the worst workgroup
+    // count) and the device record are allocated on first use, and the step is no longer captured as a graph
+    void set_optim(const OptimCfg* optim);
+    // the last step's {sum of squares, norm, scale, launch path (0 fused, 1 finish + update)}; path 0 computes no norm: 0, 0, 1
+    void optim_stats(double out[4]);
     // rows of the resident tensor the next train steps gather from (0: unknown, no clamp)
     // with distillation on, n must be the rows of the teacher table: refused here, before any step is enqueued
     void set_gather_rows(int64_t n);
@@ -292,6 +303,7 @@ class Net : public GemmHook {
     void targets_step(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
                       const DistillParams* kd, int B);
     void optimiser_step(int B, const StepState* st);   // the tail of a step: weight-gradient slabs summed + Adam (+ state advance)
+    void upload_rate_tables();                          // alpha_tab_ (and, on the finish + update path, lr_tab_) from optim_rates
     ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
 
@@ -324,6 +336,14 @@ class Net : public GemmHook {
     const float* batch_in_ = nullptr;   // this train step's gathered batch (mix_buf_ / aug_buf_), null: rows come from (X, rows)
     StepState* st_dev_ = nullptr;       // device step state (train_step_stateful)
     float* alpha_tab_ = nullptr;        // Adam step size per iteration
+    OptimCfg optim_;                    // set_optim; the default is today's constant-rate Adam
+    bool optim_finish_ = false;         // train steps take the finish + update path (decay or a clip is set)
+    float* lr_tab_ = nullptr;           // un-corrected rate per iteration (weight decay), alpha_tab_n_ entries; finish + update path only
+    uint8_t* kinds_dev_ = nullptr;      // ParamKind per arena element, uploaded once
+    float* optim_partials_ = nullptr;   // one sum of squares per grad_finish workgroup
+    int64_t optim_partials_cap_ = 0;
+    OptimRecord* optim_rec_ = nullptr;
+    int optim_last_path_ = 0;
     int64_t alpha_tab_n_ = 0, host_row0_ = 0, gather_rows_ = 0;
     hipGraphExec_t graph_exec_ = nullptr;   // the captured full-batch train step
     bool graph_ok_ = true;
@@ -358,9 +378,11 @@ struct FitHistory {
 EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, uint32_t seed, FitHistory* hist = nullptr);
 // train-to-early-stop + readouts for one candidate (evaluate_individual, nsga_penalty.py:368-395)
 // aug (optional): train-time augmentation of the candidate's fit (Net::set_augment); loss (optional): its soft-target
-// training loss (Net::set_loss); distill (optional): distillation against a teacher's logit table (Net::set_distill)
+// training loss (Net::set_loss); distill (optional): distillation against a teacher's logit table (Net::set_distill);
+// optim (optional): optimiser options (Net::set_optim)
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
-                         const AugmentCfg* aug = nullptr, const LossCfg* loss = nullptr, const DistillCfg* distill = nullptr);
+                         const AugmentCfg* aug = nullptr, const LossCfg* loss = nullptr, const DistillCfg* distill = nullptr,
+                         const OptimCfg* optim = nullptr);
 // host-only: every implicit-GEMM conv geometry of a candidate at batch B (a walk of plan_net's ops); throws
 // through igemm_check_range when a layer is beyond the kernels' 32-bit byte offsets (depthwise activations: 2^29 elements)
 void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
@@ -371,7 +393,7 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
 // n candidates are taken longest-first from a process-local counter.
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
                      EvalResult* out, const std::function<int()>& pull = {}, const AugmentCfg* aug = nullptr,
-                     const LossCfg* loss = nullptr, const DistillCfg* distill = nullptr);
+                     const LossCfg* loss = nullptr, const DistillCfg* distill = nullptr, const OptimCfg* optim = nullptr);
 
 // host-only: windows of T frames at hop frames in a stream of n_frames, 1 + (n_frames - T) / hop; throws when n_frames < T or hop < 1
 int64_t stream_windows(int64_t n_frames, int T, int hop);

@@ -338,6 +338,19 @@ NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F) {
     return plan;
 }
 
+std::vector<uint8_t> NetPlan::param_kinds() const {
+    std::vector<uint8_t> kinds((size_t)n_params, (uint8_t)KIND_TRAINABLE);
+    for (const Op& op : ops) {
+        if (op.kind == OP_CONV1 || op.kind == OP_CONV || op.kind == OP_DENSE)
+            std::fill(kinds.begin() + op.w_off, kinds.begin() + op.b_off, (uint8_t)KIND_KERNEL);
+        else if (op.kind == OP_DWCONV)
+            std::fill(kinds.begin() + op.w_off, kinds.begin() + op.w_off + (int64_t)op.KS * op.KS * op.Cin, (uint8_t)KIND_KERNEL);
+        else if (op.kind == OP_BN)
+            std::fill(kinds.begin() + op.mm_off, kinds.begin() + op.mv_off + op.Cout, (uint8_t)KIND_FROZEN);
+    }
+    return kinds;
+}
+
 size_t NetPlan::splitk_floats(int batch, int Bmax) const {
     size_t need = 0;
     for (const Op& op : ops)
@@ -943,9 +956,9 @@ void Net::launch_train_loss(const int32_t* y, const BatchRows& rows, int B) {
 }
 
 void Net::optimiser_step(int B, const StepState* st) {
-    const double t = (double)(iterations_ + 1);
     const double b1 = cfg_.beta1, b2 = cfg_.beta2;
-    const float alpha = (float)(cfg_.lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t)));
+    const OptimRates rates = optim_rates(optim_, cfg_.lr, b1, b2, iterations_);
+    const float alpha = rates.alpha_f32;
     // ONE launch finishes the weight gradients (fixed-order sum of every layer's row-slice slabs) and applies Adam to the
     // whole arena: the per-layer reduce_slices launches of round 1 are gone from the step
     std::sort(slab_segs_.begin(), slab_segs_.end(), [](const AdamSeg& a, const AdamSeg& b) { return a.off < b.off; });
@@ -962,6 +975,20 @@ void Net::optimiser_step(int B, const StepState* st) {
         pos = sg.off + sg.n;
     }
     if (pos < n_params_) { AdamSeg pl; pl.off = pos; pl.n = n_params_ - pos; push(pl); }
+    if (optim_finish_) {   // a global norm needs every finished gradient before any weight moves: finish, scale, update
+        adam_segments_finalize(tab);
+        CMOOP_REQUIRE(tab.blocks <= optim_partials_cap_, "optimiser partial buffer too small");
+        launch_grad_finish(grads_, tab, kinds_dev_, optim_partials_, stream_);
+        launch_clip_scale(optim_partials_, tab.blocks, optim_.global_clipnorm, optim_rec_, stream_);
+        AdamwArgs a;
+        a.alpha = alpha; a.lr = rates.lr_f32; a.c1 = (float)(1.0 - b1); a.c2 = (float)(1.0 - b2); a.eps = (float)cfg_.adam_eps;
+        a.weight_decay = (float)optim_.weight_decay; a.clipvalue = (float)optim_.clipvalue; a.decay_all = optim_.decay_mask;
+        launch_adamw(params_, grads_, adam_m_, adam_v_, kinds_dev_, n_params_, optim_rec_, a, stream_, st, alpha_tab_, lr_tab_);
+        if (st) launch_step_advance(st_dev_, B, stream_);
+        optim_last_path_ = 1;
+        return;
+    }
+    optim_last_path_ = 0;
     const bool unfused = getenv("CMOOP_ADAM_UNFUSED") != nullptr;   // A/B knob (read per step: tests flip it): round-1 launch sequence
     if (unfused) {
         for (const AdamSeg& sg : slab_segs_) launch_reduce_slices(sg.slab, grads_ + sg.off, sg.S, sg.n, stream_, sg.stride);
@@ -1027,24 +1054,67 @@ void Net::begin_fit(int64_t total_steps) {
     // total_steps counts from optimizer.iterations == 0; a net that has already trained (session API: state loaded with
     // set_state, or earlier epochs) continues from its own counters
     if (total_steps < 1 || total_steps > (1ll << 24)) { graph_ok_ = false; st_dev_ = nullptr; return; }   // explicit-argument steps beyond 16 M iterations
-    std::vector<float> tab(total_steps);
-    const double b1 = cfg_.beta1, b2 = cfg_.beta2;
-    for (int64_t i = 0; i < total_steps; ++i) {
-        const double t = (double)(i + 1);
-        tab[i] = (float)(cfg_.lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t)));
-    }
     alpha_tab_ = dalloc(total_steps);
+    lr_tab_ = nullptr;
     alpha_tab_n_ = total_steps;
     if (!st_dev_) st_dev_ = reinterpret_cast<StepState*>(dalloc(8));
-    CMOOP_HIP(hipMemcpyAsync(alpha_tab_, tab.data(), total_steps * 4, hipMemcpyHostToDevice, stream_));
+    upload_rate_tables();
     const StepState st0{0, (unsigned)step_, (unsigned)iterations_};
     CMOOP_HIP(hipMemcpyAsync(st_dev_, &st0, sizeof(StepState), hipMemcpyHostToDevice, stream_));
-    CMOOP_HIP(hipStreamSynchronize(stream_));     // tab and st0 are locals
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // st0 is a local
     // hipGraph replay of the captured step is OPT-IN (CMOOP_GRAPH=1).  Measured: a lone 16-filter candidate runs 2 591
     // steps/s replayed vs 2 625 launched eagerly (its stream is kept busy either way: ~50 kernels of ~8 us per step,
     // the host launches faster than that), and the pop-40 bench is 1.5 % slower replayed (2 089 vs 2 121 evals/h).
     static const bool use_graph = [] { const char* v = std::getenv("CMOOP_GRAPH"); return v && v[0] == '1'; }();
-    if (!use_graph) graph_ok_ = false;
+    if (!use_graph || optim_finish_) graph_ok_ = false;
+}
+
+// the per-iteration rates of the device-state steps, from the one host function the explicit-argument steps use
+void Net::upload_rate_tables() {
+    if (!alpha_tab_ || alpha_tab_n_ < 1) return;
+    if (optim_finish_ && !lr_tab_) lr_tab_ = dalloc(alpha_tab_n_);
+    std::vector<float> alpha(alpha_tab_n_), lr(optim_finish_ ? alpha_tab_n_ : 0);
+    for (int64_t i = 0; i < alpha_tab_n_; ++i) {
+        const OptimRates r = optim_rates(optim_, cfg_.lr, cfg_.beta1, cfg_.beta2, i);
+        alpha[i] = r.alpha_f32;
+        if (optim_finish_) lr[i] = r.lr_f32;
+    }
+    CMOOP_HIP(hipMemcpyAsync(alpha_tab_, alpha.data(), alpha_tab_n_ * 4, hipMemcpyHostToDevice, stream_));
+    if (optim_finish_) CMOOP_HIP(hipMemcpyAsync(lr_tab_, lr.data(), alpha_tab_n_ * 4, hipMemcpyHostToDevice, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // the tables are locals
+}
+
+void Net::set_optim(const OptimCfg* optim) {
+    if (optim) optim_check(*optim);
+    const OptimCfg c = optim && optim_enabled(*optim) ? *optim : OptimCfg();
+    const bool finish = optim_finish_path(c);
+    if (finish && !kinds_dev_) {
+        NetPlan plan;
+        plan.ops = ops_;
+        plan.n_params = n_params_;
+        const std::vector<uint8_t> kinds = plan.param_kinds();
+        kinds_dev_ = reinterpret_cast<uint8_t*>(dalloc((size_t)(n_params_ + 3) / 4));
+        // a slab segment takes a workgroup per 64 elements at the most, a plain one per 1024, each of the segments rounds up
+        optim_partials_cap_ = n_params_ / 64 + ADAM_MAX_SEGS + 1;
+        optim_partials_ = dalloc((size_t)optim_partials_cap_);
+        optim_rec_ = reinterpret_cast<OptimRecord*>(dalloc(sizeof(OptimRecord) / 4));
+        CMOOP_HIP(hipMemcpyAsync(kinds_dev_, kinds.data(), (size_t)n_params_, hipMemcpyHostToDevice, stream_));
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // kinds is a local; nothing of the old options is still running
+    optim_ = c;
+    optim_finish_ = finish;
+    upload_rate_tables();                         // takes effect from the next step
+    if (finish) graph_ok_ = false;                // nothing is promised under CMOOP_GRAPH=1
+    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
+}
+
+void Net::optim_stats(double out[4]) {
+    out[0] = 0.0; out[1] = 0.0; out[2] = 1.0; out[3] = (double)optim_last_path_;
+    if (optim_last_path_ != 1) { CMOOP_HIP(hipStreamSynchronize(stream_)); return; }
+    OptimRecord rec;
+    CMOOP_HIP(hipMemcpyAsync(&rec, optim_rec_, sizeof(rec), hipMemcpyDeviceToHost, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+    out[0] = rec.sumsq; out[1] = (double)rec.norm; out[2] = (double)rec.scale;
 }
 
 void Net::begin_epoch() {
@@ -1436,13 +1506,14 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
 }
 
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
-                         const AugmentCfg* aug, const LossCfg* loss, const DistillCfg* distill) {
+                         const AugmentCfg* aug, const LossCfg* loss, const DistillCfg* distill, const OptimCfg* optim) {
     const auto t0 = std::chrono::steady_clock::now();
     CMOOP_REQUIRE(ds.n_train >= 1 && ds.n_val >= 1, "empty train or validation split");
     Net net(gene, cfg, ds.T, ds.F, seed, stream);
     if (aug) net.set_augment(aug);
     if (loss) net.set_loss(loss);
     if (distill) net.set_distill(distill);
+    if (optim) net.set_optim(optim);
     EvalResult res = fit_and_read_out(net, cfg, ds, seed, nullptr);
     res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return res;
@@ -1464,11 +1535,12 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B) 
 
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
                      EvalResult* out, const std::function<int()>& pull, const AugmentCfg* aug, const LossCfg* loss,
-                     const DistillCfg* distill) {
+                     const DistillCfg* distill, const OptimCfg* optim) {
     if (n <= 0) return;
     if (aug && !augment_enabled(*aug)) aug = nullptr;   // a disabled config is no config: today's path, call for call
     if (loss && !loss_enabled(*loss)) loss = nullptr;
     if (distill && !distill_enabled(*distill)) distill = nullptr;
+    if (optim && !optim_enabled(*optim)) optim = nullptr;
     for (int i = 0; i < n; ++i) validate_gene(genes + 6 * i);
     for (int i = 0; i < n; ++i) out[i].evaluated = 0;
     // longest first (closed-form FLOPs) so the tail of the generation is made of cheap candidates
@@ -1500,7 +1572,7 @@ void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* gen
                     if (j >= n) break;
                     i = order[j];
                 }
-                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream, aug, loss, distill);
+                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream, aug, loss, distill, optim);
                 out[i].evaluated = 1;
             }
         } catch (const std::exception& e) {

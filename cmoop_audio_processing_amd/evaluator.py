@@ -36,6 +36,7 @@ from . import _lib, genes as G
 from .augment import AugmentConfig
 from .loss import LossConfig
 from .distill import DistillConfig, check_teacher_table, require_teacher
+from .optim import OptimConfig
 
 FPR_CODES = {"v1": 0, "v1_quirk": 1, "v3": 2}
 ACC_CODES = {"last": 0, "evaluate": 1}
@@ -89,6 +90,10 @@ class EvalConfig:
     # is launched.  Validation stays the sparse cross-entropy.  Travels beside cmoop_config (cmoop_net_set_distill,
     # cmoop_eval_population_kd)
     distill: Optional[DistillConfig] = None
+    # optimiser options of every candidate's fit (optim.py): learning-rate schedule, decoupled weight decay, gradient
+    # clipping.  None or a config with everything off = off, every number as without the field.  Travels beside cmoop_config
+    # (cmoop_net_set_optim, cmoop_eval_population_opt)
+    optim: Optional[OptimConfig] = None
 
     @staticmethod
     def preset(script: str, **over) -> "EvalConfig":
@@ -148,6 +153,12 @@ class EvalConfig:
         if self.loss is None or not self.loss.enabled:
             return None
         return self.loss.check(self.classes)._struct()
+
+    def optim_struct(self) -> Optional["_lib.Optim"]:
+        """The enabled optimiser options as a ``cmoop_optim``, checked; None when they are off."""
+        if self.optim is None or not self.optim.enabled:
+            return None
+        return self.optim.check()._struct()
 
     def distill_struct(self, teacher_logits, n_train: int) -> Optional["_lib.Distill"]:
         """The enabled distillation as a ``cmoop_distill`` over the table ``teacher_logits`` (CUDA float32 [n_train,
@@ -418,7 +429,13 @@ class PopulationEvaluator:
         cfg, ds = self.config.to_struct(), self._dataset()
         aug, loss = self.config.augment_struct(self.T, self.F), self.config.loss_struct()
         kd = self.config.distill_struct(self.teacher_logits, len(self.X_train))
-        if kd is not None:
+        opt = self.config.optim_struct()
+        if opt is not None:
+            _lib.check(_lib.lib().cmoop_eval_population_opt(
+                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None,
+                C.byref(kd) if kd is not None else None, C.byref(opt), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), None,
+                None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), None))
+        elif kd is not None:
             _lib.check(_lib.lib().cmoop_eval_population_kd(
                 C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None, C.byref(kd),
                 C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), None, None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr),
@@ -465,7 +482,14 @@ class PopulationEvaluator:
         cb = _lib.NEXT_FN(_next)
         aug, loss = self.config.augment_struct(self.T, self.F), self.config.loss_struct()
         kd = self.config.distill_struct(self.teacher_logits, len(self.X_train))
-        if kd is not None:
+        opt = self.config.optim_struct()
+        if opt is not None:
+            _lib.check(_lib.lib().cmoop_eval_population_opt(
+                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None,
+                C.byref(kd) if kd is not None else None, C.byref(opt), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n),
+                C.cast(cb, C.c_void_p), None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs),
+                _lib.ptr(done)))
+        elif kd is not None:
             _lib.check(_lib.lib().cmoop_eval_population_kd(
                 C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None, C.byref(kd),
                 C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), C.cast(cb, C.c_void_p), None, _lib.ptr(acc), _lib.ptr(size),
@@ -542,7 +566,7 @@ class PopulationEvaluator:
         """Train ONE candidate on the resident splits and keep its weights -> ``deploy.TrainedModel``.
 
         The body of the population call's per-candidate work (``NetSession.fit``) on the given seed and under the same
-        ``config.augment`` / ``config.loss`` / ``config.distill`` (against the teacher of ``set_teacher``): with
+        ``config.augment`` / ``config.loss`` / ``config.optim`` / ``config.distill`` (against the teacher of ``set_teacher``): with
         ``seed = last_seeds[i]`` it reproduces candidate i of the last generation, accuracy and FPR included.
         ``hparams`` is the reference's dict or a gene tuple; ``frontend`` / ``mean`` / ``scale`` (the front end and the
         StandardScaler the features were made with) ride along for ``StreamScorer``."""

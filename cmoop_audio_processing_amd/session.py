@@ -41,6 +41,13 @@ class NetSession:
             except Exception:
                 self.close()
                 raise
+        self.optim = None
+        if getattr(config, "optim", None) is not None:
+            try:
+                self.set_optim(config.optim)
+            except Exception:
+                self.close()
+                raise
         self.distill, self._teacher_logits = None, None     # what the net trains against now (None: no distillation)
         self._distill_pending = bool(getattr(getattr(config, "distill", None), "enabled", False))   # config.distill waits for a table
 
@@ -106,6 +113,26 @@ class NetSession:
         torch.cuda.synchronize()
         _lib.check(_lib.lib().cmoop_net_train_step_distill_targets(self._h, _lib.ptr(X_rows), _lib.ptr(t), _lib.ptr(w), _lib.ptr(primary),
                                                                    _lib.ptr(q), float(alpha), float(temperature), C.c_int32(B)))
+
+    def set_optim(self, optim) -> None:
+        """Optimiser options (``OptimConfig``: learning-rate schedule, decoupled weight decay, gradient clipping) of every
+        following train step of this net -- ``train_step``, ``run_epoch`` and ``fit`` alike -- from the next step on.  None
+        or a config with everything off turns them off (``self.optim`` is then None), and the net steps bit for bit as one
+        that never had any.  The schedule is a function of ``iterations``, so ``get_state`` / ``set_state`` carry it."""
+        if optim is None:
+            _lib.check(_lib.lib().cmoop_net_set_optim(self._h, None))
+        else:
+            st = optim.check()._struct()
+            _lib.check(_lib.lib().cmoop_net_set_optim(self._h, C.byref(st)))
+        self.optim = optim if optim is not None and optim.enabled else None
+
+    def optim_stats(self) -> dict:
+        """The last train step's optimiser read-out: dict(sumsq, norm, scale, path) -- the float64 sum of squares of the
+        trainable gradients as the device summed it, the float32 norm and clip scale, and the launch path (0: the fused
+        launch, which computes no norm and reports 0, 0, 1; 1: finish + update)."""
+        out = (C.c_double * 4)()
+        _lib.check(_lib.lib().cmoop_net_optim_stats(self._h, out))
+        return dict(sumsq=float(out[0]), norm=float(out[1]), scale=float(out[2]), path=int(out[3]))
 
     def set_loss(self, loss) -> None:
         """Soft-target training loss (``LossConfig``: mixup, label smoothing, class weights) of every following train step

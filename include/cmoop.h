@@ -271,6 +271,62 @@ int cmoop_eval_population_kd(const cmoop_config* cfg, const cmoop_augment* aug, 
                              cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
                              double* val_loss, double* seconds, int32_t* evaluated);
 
+/* ---- optimiser options: learning-rate schedule, decoupled weight decay, gradient clipping (opt-in, off by default).
+ * BUILD-DEFINED: the reference builds Adam() with none of them; with no optim config, or a disabled one, every launch and every
+ * bit is that of a build without it.  No accuracy gain is claimed.  i is optimizer.iterations BEFORE the update, t = i + 1.
+ * Schedule: lr(i) = cfg.lr f(i), evaluated in double on the host (the formulas of Keras' CosineDecay with warm-up,
+ *   ExponentialDecay and PiecewiseConstantDecay, cfg.lr as the initial rate):
+ *   cosine       i < warmup_steps: f = warmup_start + (1 - warmup_start) i / warmup_steps; after it s = min(i - warmup_steps,
+ *                decay_steps), f = (1 - alpha) 0.5 (1 + cos(pi s / decay_steps)) + alpha
+ *   exponential  f = decay_rate ^ (i / decay_steps), the exponent floored with staircase
+ *   piecewise    values[0] for i <= boundaries[0], values[k] for boundaries[k-1] < i <= boundaries[k], values[n_boundaries] after
+ *   The step size stays alpha(i) = (float)(lr(i) sqrt(1 - beta2^t) / (1 - beta1^t)), in double, rounded once.
+ * Per element, in Keras' order, every operation a separately rounded fp32 operation (no fused multiply-add):
+ *   g = g scale                         scale = (float)(clip / norm) where norm > global_clipnorm > 0, else EXACTLY 1.0f: an
+ *                                       inactive clip leaves the gradient's bits (Keras forms clip min(1 / norm, 1 / clip), which
+ *                                       can leave 1 by an ulp); norm = sqrt(sum of g^2 over every trainable tensor), the sum formed
+ *                                       as one fp32 partial per workgroup in a fixed order, the partials summed in double
+ *   g = g < -c ? -c : (g > c ? c : g)   c = (float)clipvalue > 0 (a NaN passes)
+ *   w = w - (w (float)weight_decay) (float)lr(i)      decay_mask 0: kernels only (conv, depthwise, pointwise, dense); 1: every
+ *                                       trainable tensor (Keras' default)
+ *   then the Adam update of cmoop_adam on the decayed weight.
+ * BatchNorm moving statistics live in the parameter arena and are NOT trainable: never decayed, never in the norm, w / m / v kept.
+ * Non-finite gradients propagate.  A config is ENABLED iff schedule != 0 or any of weight_decay, global_clipnorm, clipvalue > 0.
+ * A schedule alone keeps the fused optimiser launch; decay or a clip take three launches (cmoop_grad_finish's two, cmoop_adamw). */
+typedef struct cmoop_optim {
+    double weight_decay;     /* >= 0; 0 = off */
+    double global_clipnorm;  /* >= 0; 0 = off; not together with clipvalue */
+    double clipvalue;        /* >= 0; 0 = off */
+    double warmup_start;     /* cosine: f(0) of the linear warm-up, >= 0 */
+    double alpha;            /* cosine: the floor of f, >= 0 */
+    double decay_rate;       /* exponential, >= 0 */
+    double values[9];        /* piecewise: n_boundaries + 1 factors, >= 0 */
+    int64_t warmup_steps;    /* cosine, >= 0 */
+    int64_t decay_steps;     /* cosine / exponential, >= 1 */
+    int64_t boundaries[8];   /* piecewise: >= 0, strictly increasing */
+    int32_t schedule;        /* 0 constant, 1 cosine, 2 exponential, 3 piecewise */
+    int32_t staircase;       /* exponential: 0 / 1 */
+    int32_t decay_mask;      /* 0 kernels only, 1 every trainable tensor */
+    int32_t n_boundaries;    /* piecewise: 0 .. 8 */
+    int32_t reserved[2];     /* 0 */
+} cmoop_optim;               /* 224 bytes */
+int cmoop_optim_default(cmoop_optim* optim); /* everything off: all zero */
+/* host-only: non-zero + a message naming the offending field when the config is outside the domain (negative or non-finite
+ * values, both clips, decay_steps < 1 where the schedule reads it, boundaries that do not increase, unknown codes) */
+int cmoop_optim_check(const cmoop_optim* optim);
+/* host-only, the numbers the kernels consume at `iteration`: lr(i) in double, (float)lr(i), and the step size alpha(i).
+ * optim NULL: the constant schedule.  Any output may be NULL. */
+int cmoop_optim_rates(const cmoop_optim* optim, const cmoop_config* cfg, int64_t iteration, double* lr, float* lr_f32, float* alpha_f32);
+/* host-only: the tensor kind of every parameter of a candidate in arena order (cmoop_net_get_params), kinds[n]:
+ * 0 kernel, 1 other trainable (bias, gamma, beta), 2 not trainable (BatchNorm moving mean / variance); n must be its parameter count */
+int cmoop_param_kinds(const int32_t gene[6], int32_t variant, int32_t classes, uint8_t* kinds, int64_t n);
+/* cmoop_eval_population_kd with every candidate's fit under the optimiser options.  optim NULL or disabled: exactly
+ * cmoop_eval_population_kd. */
+int cmoop_eval_population_opt(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                              const cmoop_optim* optim, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
+                              const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
+                              double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated);
+
 /* host-only: does every conv layer of this candidate at `batch` rows per launch (pass max(batch, eval_batch)) stay inside
  * the kernels' 32-bit byte offsets (each activation / kernel tensor below 2^29 elements)?  Non-zero + message if not;
  * cmoop_net_create and the population calls make the same check before they allocate anything. */
@@ -483,6 +539,14 @@ int cmoop_net_loss_buffers(cmoop_net* net, int64_t out[4]);
  * it must stay allocated while the net trains.  A step whose gather rows are known and differ from n_rows fails.
  * cmoop_net_train_metrics then reports the distillation loss sum and the count of argmax z == primary. */
 int cmoop_net_set_distill(cmoop_net* net, const cmoop_distill* distill /* NULL = off */);
+/* Optimiser options (cmoop_optim above) of every following train step of this net, from the next step on (NULL or a disabled
+ * config: off, and the net steps bit for bit as one that never had one).  The config is copied; the rate tables of a fit under
+ * way are rebuilt.  The schedule is a function of `iterations`, so cmoop_net_get_state / _set_state carry it unchanged.  With
+ * decay or a clip on, the step is not captured as a graph. */
+int cmoop_net_set_optim(cmoop_net* net, const cmoop_optim* optim /* NULL = off */);
+/* the last train step's out = {sum of squares of the trainable gradients, their norm, the clip scale, launch path (0: the fused
+ * launch, which computes no norm: 0, 0, 1; 1: finish + update)} */
+int cmoop_net_optim_stats(cmoop_net* net, double out[4]);
 /* cmoop_net_train_step_targets with a teacher row per batch row, q_dev [B][classes], and the distillation loss at
  * (alpha, temperature), whatever cmoop_net_set_distill says. */
 int cmoop_net_train_step_distill_targets(cmoop_net* net, const float* x_rows_dev, const float* t_dev, const float* w_dev,
@@ -604,6 +668,18 @@ int cmoop_adam(float* w_dev, const float* g_dev, float* m_dev, float* v_dev, int
 int cmoop_adam_segments(float* w_dev, float* g_dev, float* m_dev, float* v_dev, const float* slab_dev, int32_t count,
                         const int64_t* off, const int64_t* n, const int32_t* S, const int64_t* stride, const int64_t* slab_off,
                         double alpha, double beta1, double beta2, double eps);
+/* the first two launches of the finish + update path on the segments of cmoop_adam_segments: g finished (slab sums stored,
+ * bit-equal to the fused launch's), no weight moved; partials_dev[b] (cap >= the workgroup count, returned in *n_partials) =
+ * workgroup b's fp32 sum of g^2 over its elements whose kind is not 2 (kinds_dev NULL: all); record_dev (16 bytes:
+ * double sum of squares, float norm, float scale) from the partials summed in double and global_clipnorm (0: scale 1) */
+int cmoop_grad_finish(float* g_dev, const float* slab_dev, int32_t count, const int64_t* off, const int64_t* n, const int32_t* S,
+                      const int64_t* stride, const int64_t* slab_off, const uint8_t* kinds_dev /* may be NULL */,
+                      double global_clipnorm, float* partials_dev, int32_t cap, int32_t* n_partials, void* record_dev);
+/* the third launch on n floats: g scale (read from record_dev), the value clamp, the masked decay with lr, then cmoop_adam's
+ * update with the step size alpha; kinds_dev NULL: every element is a kernel.  Elements of kind 2 keep w, m and v */
+int cmoop_adamw(float* w_dev, const float* g_dev, float* m_dev, float* v_dev, const uint8_t* kinds_dev /* may be NULL */, int64_t n,
+                const void* record_dev, double alpha, double lr, double beta1, double beta2, double eps, double weight_decay,
+                int32_t decay_mask, double clipvalue);
 /* cm[C][C] (int64) = confusion matrix of n label pairs (out-of-range labels ignored; force_true_zero: every true label 0) */
 int cmoop_confusion(const int32_t* y_true_dev, const int32_t* y_pred_dev, int64_t n, int32_t C, int32_t force_true_zero,
                     int64_t* cm_dev);
