@@ -232,10 +232,10 @@ def lib():
             if name not in ("cmoop_last_error", "cmoop_config_default"):
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
-        for name, argtypes in list(STREAM_PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(PCEN_PROTOTYPES.items()) + \
-                list(ELEM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(DWCONV_PROTOTYPES.items()) + \
-                list(DISTILL_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()):
-            getattr(L, name).argtypes = argtypes
+        for table in (STREAM_PROTOTYPES, AUGMENT_PROTOTYPES, PCEN_PROTOTYPES, ELEM_PROTOTYPES, LOSS_PROTOTYPES, DENSE_PROTOTYPES,
+                      DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES):
+            for name, argtypes in table.items():
+                getattr(L, name).argtypes = argtypes
         _lib = L
         return L
 

@@ -170,6 +170,26 @@ static OptimCfg to_optim(const cmoop_optim* o) {
     return c;
 }
 
+// The converted training options of one population call: to_* and the matching *_check of every struct handed in, in the
+// order augment, loss, distill, optim (what a call with two bad structs reports first); owns what opt points into
+namespace {
+struct AbiTrainOptions {
+    AugmentCfg aug;
+    LossCfg loss;
+    DistillCfg distill;
+    OptimCfg optim;
+    TrainOptions opt;
+    AbiTrainOptions(const cmoop_augment* a, const cmoop_loss* l, const cmoop_distill* d, const cmoop_optim* o, const NetConfig& c,
+                    const Dataset& ds) {
+        if (a) { aug = to_augment(a); augment_check(aug, ds.T, ds.F); opt.aug = &aug; }
+        if (l) { loss = to_loss(l); loss_check(loss, c.classes); opt.loss = &loss; }
+        if (d) { distill = to_distill(d); distill_check(distill, c.classes, ds.n_train); opt.distill = &distill; }
+        if (o) { optim = to_optim(o); optim_check(optim); opt.optim = &optim; }
+    }
+    AbiTrainOptions(const AbiTrainOptions&) = delete;
+};
+}  // namespace
+
 static Dataset to_dataset(const cmoop_dataset* ds) {
     Dataset d;
     d.x_train = ds->x_train; d.y_train = ds->y_train; d.n_train = ds->n_train;
@@ -197,16 +217,9 @@ static double time_launches(hipStream_t s, int iters, F&& once) {
 // the three PCEN launches on s with their pooled workspace; the workspace goes back once the stream has drained
 template <class F>
 static void with_pcen_workspace(int T, int n_bands, hipStream_t s, F&& body) {
-    float* ws = static_cast<float*>(pool_alloc(std::max<size_t>(pcen_stream_workspace_floats(T, n_bands), 4) * sizeof(float)));
-    try {
-        body(ws);
-        CMOOP_HIP(hipStreamSynchronize(s));
-    } catch (...) {
-        hipStreamSynchronize(s);
-        pool_free(ws);
-        throw;
-    }
-    pool_free(ws);
+    PoolScope pool(s);
+    body(pool.get<float>(std::max<size_t>(pcen_stream_workspace_floats(T, n_bands), 4) * sizeof(float)));
+    CMOOP_HIP(hipStreamSynchronize(s));
 }
 
 // device scratch of one call: released when the call ends, after its stream has drained
@@ -240,6 +253,21 @@ struct RecordingHook : GemmHook {
     }
 };
 
+struct cmoop_net {
+    Net* net;
+};
+
+// the body of cmoop_net_set_<who>: a NULL struct is sent on as null, anything else converted first
+template <class Abi, class Cfg>
+static int net_set_option(cmoop_net* h, const char* who, const Abi* abi, Cfg (*convert)(const Abi*), void (Net::*set)(const Cfg*)) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, std::string(who) + ": NULL net");
+        if (!abi) { (h->net->*set)(nullptr); return; }
+        const Cfg c = convert(abi);
+        (h->net->*set)(&c);
+    });
+}
+
 extern "C" {
 
 int cmoop_abi_version(void) { return CMOOP_ABI_VERSION; }
@@ -262,7 +290,7 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
     return guard([&] { *out = fwd_flops_per_sample(gene, variant, classes, T, F); });
 }
 
-// every population call; next == NULL: candidates are taken longest-first from a process-local counter; aug == NULL: no augmentation
+// every population call; next == NULL: candidates are taken longest-first from a process-local counter; a NULL option: off
 static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss,
                                 const cmoop_distill* distill, const cmoop_optim* optim, const cmoop_dataset* ds,
                                 const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
@@ -272,33 +300,13 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* au
     CMOOP_REQUIRE(!next || evaluated, "NULL argument");
     NetConfig c = to_cfg(cfg);
     const Dataset d = to_dataset(ds);
-    AugmentCfg a;
-    if (aug) {
-        a = to_augment(aug);
-        augment_check(a, d.T, d.F);
-    }
-    LossCfg lc;
-    if (loss) {
-        lc = to_loss(loss);
-        loss_check(lc, c.classes);
-    }
-    DistillCfg dc;
-    if (distill) {
-        dc = to_distill(distill);
-        distill_check(dc, c.classes, d.n_train);
-    }
-    OptimCfg oc;
-    if (optim) {
-        oc = to_optim(optim);
-        optim_check(oc);
-    }
+    const AbiTrainOptions options(aug, loss, distill, optim, c, d);
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
-    if (next) eval_population(c, d, genes, seeds, n, r.data(), [&]() { return (int)next(ctx); }, aug ? &a : nullptr, loss ? &lc : nullptr,
-                              distill ? &dc : nullptr, optim ? &oc : nullptr);
-    else eval_population(c, d, genes, seeds, n, r.data(), {}, aug ? &a : nullptr, loss ? &lc : nullptr, distill ? &dc : nullptr,
-                         optim ? &oc : nullptr);
+    std::function<int()> pull;   // empty: the process-local longest-first counter
+    if (next) pull = [&]() { return (int)next(ctx); };
+    eval_population(c, d, genes, seeds, n, r.data(), pull, options.opt);
     for (int i = 0; i < n; ++i) {
         if (evaluated) evaluated[i] = r[i].evaluated;
         if (acc) acc[i] = r[i].acc;
@@ -956,10 +964,6 @@ int cmoop_profile_variant(int32_t i, char* name, int32_t name_cap) {
 }
 
 // ---- session -------------------------------------------------------------------
-struct cmoop_net {
-    Net* net;
-};
-
 int cmoop_net_create(const int32_t gene[6], const cmoop_config* cfg, int32_t T, int32_t F, uint32_t seed, cmoop_net** out) {
     return guard([&] {
         NetConfig c = to_cfg(cfg);
@@ -1004,22 +1008,8 @@ int cmoop_net_set_state(cmoop_net* h, const float* params, const float* adam_m, 
                         int64_t steps) {
     return guard([&] { h->net->set_state(params, adam_m, adam_v, iterations, steps); });
 }
-int cmoop_net_set_augment(cmoop_net* h, const cmoop_augment* aug) {
-    return guard([&] {
-        CMOOP_REQUIRE(h && h->net, "set_augment: NULL net");
-        if (!aug) { h->net->set_augment(nullptr); return; }
-        const AugmentCfg c = to_augment(aug);
-        h->net->set_augment(&c);
-    });
-}
-int cmoop_net_set_loss(cmoop_net* h, const cmoop_loss* loss) {
-    return guard([&] {
-        CMOOP_REQUIRE(h && h->net, "set_loss: NULL net");
-        if (!loss) { h->net->set_loss(nullptr); return; }
-        const LossCfg c = to_loss(loss);
-        h->net->set_loss(&c);
-    });
-}
+int cmoop_net_set_augment(cmoop_net* h, const cmoop_augment* aug) { return net_set_option(h, "set_augment", aug, to_augment, &Net::set_augment); }
+int cmoop_net_set_loss(cmoop_net* h, const cmoop_loss* loss) { return net_set_option(h, "set_loss", loss, to_loss, &Net::set_loss); }
 int cmoop_net_train_step_targets(cmoop_net* h, const float* x_rows, const float* t, const float* w, const int32_t* primary, int32_t B) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "train_step_targets: NULL net");
@@ -1029,21 +1019,9 @@ int cmoop_net_train_step_targets(cmoop_net* h, const float* x_rows, const float*
     });
 }
 int cmoop_net_set_distill(cmoop_net* h, const cmoop_distill* distill) {
-    return guard([&] {
-        CMOOP_REQUIRE(h && h->net, "set_distill: NULL net");
-        if (!distill) { h->net->set_distill(nullptr); return; }
-        const DistillCfg c = to_distill(distill);
-        h->net->set_distill(&c);
-    });
+    return net_set_option(h, "set_distill", distill, to_distill, &Net::set_distill);
 }
-int cmoop_net_set_optim(cmoop_net* h, const cmoop_optim* optim) {
-    return guard([&] {
-        CMOOP_REQUIRE(h && h->net, "set_optim: NULL net");
-        if (!optim) { h->net->set_optim(nullptr); return; }
-        const OptimCfg c = to_optim(optim);
-        h->net->set_optim(&c);
-    });
-}
+int cmoop_net_set_optim(cmoop_net* h, const cmoop_optim* optim) { return net_set_option(h, "set_optim", optim, to_optim, &Net::set_optim); }
 int cmoop_net_optim_stats(cmoop_net* h, double out[4]) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net && out, "optim_stats: NULL argument");
@@ -1074,17 +1052,10 @@ int cmoop_net_set_gather_rows(cmoop_net* h, int64_t n_rows) {
 int cmoop_net_run_epoch(cmoop_net* h, const float* x, const int32_t* y, int64_t n_train, int32_t epoch) {
     return guard([&] {
         CMOOP_REQUIRE(x && y && n_train >= 1, "run_epoch: NULL / empty training split");
-        int32_t* idx = static_cast<int32_t*>(pool_alloc((size_t)n_train * 4));
-        try {
-            h->net->run_epoch(x, y, n_train, epoch, idx);
-            CMOOP_HIP(hipStreamSynchronize(h->net->stream()));
-            h->net->drain_profile();
-        } catch (...) {
-            hipStreamSynchronize(h->net->stream());
-            pool_free(idx);
-            throw;
-        }
-        pool_free(idx);
+        PoolScope pool(h->net->stream());
+        h->net->run_epoch(x, y, n_train, epoch, pool.get<int32_t>((size_t)n_train * 4));
+        CMOOP_HIP(hipStreamSynchronize(h->net->stream()));
+        h->net->drain_profile();
     });
 }
 int cmoop_net_fit(cmoop_net* h, const cmoop_dataset* ds, int32_t hist_cap, double* val_loss_hist, double* val_acc_hist,

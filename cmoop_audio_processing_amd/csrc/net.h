@@ -135,6 +135,16 @@ void* pool_alloc(size_t bytes);
 void pool_free(void* p);
 void* pool_alloc_pinned(size_t bytes);
 void pool_free_pinned(void* p);
+// pooled buffers of one call: at scope exit, a throw included, the stream is drained first, then the buffers go back
+struct PoolScope {
+    hipStream_t s;
+    std::vector<void*> bufs, pinned;
+    explicit PoolScope(hipStream_t stream) : s(stream) {}
+    PoolScope(const PoolScope&) = delete;
+    ~PoolScope() { hipStreamSynchronize(s); for (void* p : pinned) pool_free_pinned(p); for (void* p : bufs) pool_free(p); }
+    template <class T> T* get(size_t bytes) { bufs.push_back(pool_alloc(bytes)); return static_cast<T*>(bufs.back()); }
+    template <class T> T* get_pinned(size_t bytes) { pinned.push_back(pool_alloc_pinned(bytes)); return static_cast<T*>(pinned.back()); }
+};
 
 struct Act {
     float* data = nullptr;
@@ -197,6 +207,15 @@ struct NetPlan {
 };
 NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F);
 
+// The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
+// set_distill / set_optim say what each does).  The pointees stay the caller's for the length of the call
+struct TrainOptions {
+    const AugmentCfg* aug = nullptr;
+    const LossCfg* loss = nullptr;
+    const DistillCfg* distill = nullptr;
+    const OptimCfg* optim = nullptr;
+};
+
 class Net : public GemmHook {
   public:
     const GemmTiming* begin(int cls, double flops) override;
@@ -245,6 +264,9 @@ class Net : public GemmHook {
     // path (grad_finish -> clip_scale -> adamw); the kind arena, the partial buffer (sized once for the worst workgroup
     // count) and the device record are allocated on first use, and the step is no longer captured as a graph
     void set_optim(const OptimCfg* optim);
+    // the enabled ones of o through the four setters above, in that order: augment, loss, distill, optim.  THE place of "a
+    // disabled config is no config": null or disabled is not applied at all, and the net stays one that never had it
+    void set_options(const TrainOptions& o);
     // the last step's {sum of squares, norm, scale, launch path (0 fused, 1 finish + update)}; path 0 computes no norm: 0, 0, 1
     void optim_stats(double out[4]);
     // rows of the resident tensor the next train steps gather from (0: unknown, no clamp)
@@ -304,6 +326,9 @@ class Net : public GemmHook {
                       const DistillParams* kd, int B);
     void optimiser_step(int B, const StepState* st);   // the tail of a step: weight-gradient slabs summed + Adam (+ state advance)
     void upload_rate_tables();                          // alpha_tab_ (and, on the finish + update path, lr_tab_) from optim_rates
+    void drop_graph();                                  // the captured step has the old launch sequence or counters
+    void upload_step_state();                           // enqueues the device StepState at (0, step_, iterations_); no-op without one
+    void ensure_target_buffers();                       // t / w / primary, allocated by the first enabled set_loss or set_distill
     ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
 
@@ -326,7 +351,7 @@ class Net : public GemmHook {
     TargetParams tgtp_;                 // cw: cw_dev_ or null
     float *lam_tab_ = nullptr, *cw_dev_ = nullptr;
     float* mix_buf_ = nullptr;          // [cfg.batch][T][F], allocated by the first set_loss with mixup on
-    float *tgt_t_ = nullptr, *tgt_w_ = nullptr;   // [cfg.batch][classes], [cfg.batch]: allocated by the first enabled set_loss
+    float *tgt_t_ = nullptr, *tgt_w_ = nullptr;   // [cfg.batch][classes], [cfg.batch]: ensure_target_buffers
     int32_t* tgt_primary_ = nullptr;    // [cfg.batch]
     bool distill_on_ = false;           // train steps take the distillation loss (set_distill)
     DistillParams kdp_;
@@ -335,6 +360,7 @@ class Net : public GemmHook {
     float* kd_q_ = nullptr;             // [cfg.batch][classes], allocated by the first enabled set_distill
     const float* batch_in_ = nullptr;   // this train step's gathered batch (mix_buf_ / aug_buf_), null: rows come from (X, rows)
     StepState* st_dev_ = nullptr;       // device step state (train_step_stateful)
+    StepState st_up_{};                 // what upload_step_state copies from: outlives the enqueued copy
     float* alpha_tab_ = nullptr;        // Adam step size per iteration
     OptimCfg optim_;                    // set_optim; the default is today's constant-rate Adam
     bool optim_finish_ = false;         // train steps take the finish + update path (decay or a clip is set)
@@ -377,12 +403,9 @@ struct FitHistory {
 // Model.fit + EarlyStopping + the read-outs on an EXISTING net (the body of run_candidate); seed keys the epoch shuffle
 EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, uint32_t seed, FitHistory* hist = nullptr);
 // train-to-early-stop + readouts for one candidate (evaluate_individual, nsga_penalty.py:368-395)
-// aug (optional): train-time augmentation of the candidate's fit (Net::set_augment); loss (optional): its soft-target
-// training loss (Net::set_loss); distill (optional): distillation against a teacher's logit table (Net::set_distill);
-// optim (optional): optimiser options (Net::set_optim)
+// opt: the training options of the candidate's fit (Net::set_options)
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
-                         const AugmentCfg* aug = nullptr, const LossCfg* loss = nullptr, const DistillCfg* distill = nullptr,
-                         const OptimCfg* optim = nullptr);
+                         const TrainOptions& opt = {});
 // host-only: every implicit-GEMM conv geometry of a candidate at batch B (a walk of plan_net's ops); throws
 // through igemm_check_range when a layer is beyond the kernels' 32-bit byte offsets (depthwise activations: 2^29 elements)
 void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
@@ -390,10 +413,9 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B);
 // candidates in flight on their own HIP streams, longest-first
 // pull (optional): called by the worker threads (concurrently) for the next candidate index, < 0 = queue exhausted --
 // lets several ranks drain ONE longest-first queue (cross-rank dynamic scheduling, evaluator.py); without it the
-// n candidates are taken longest-first from a process-local counter.
+// n candidates are taken longest-first from a process-local counter.  opt: every candidate's training options.
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
-                     EvalResult* out, const std::function<int()>& pull = {}, const AugmentCfg* aug = nullptr,
-                     const LossCfg* loss = nullptr, const DistillCfg* distill = nullptr, const OptimCfg* optim = nullptr);
+                     EvalResult* out, const std::function<int()>& pull = {}, const TrainOptions& opt = {});
 
 // host-only: windows of T frames at hop frames in a stream of n_frames, 1 + (n_frames - T) / hop; throws when n_frames < T or hop < 1
 int64_t stream_windows(int64_t n_frames, int T, int hop);

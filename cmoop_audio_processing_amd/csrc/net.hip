@@ -984,22 +984,16 @@ void Net::optimiser_step(int B, const StepState* st) {
         a.alpha = alpha; a.lr = rates.lr_f32; a.c1 = (float)(1.0 - b1); a.c2 = (float)(1.0 - b2); a.eps = (float)cfg_.adam_eps;
         a.weight_decay = (float)optim_.weight_decay; a.clipvalue = (float)optim_.clipvalue; a.decay_all = optim_.decay_mask;
         launch_adamw(params_, grads_, adam_m_, adam_v_, kinds_dev_, n_params_, optim_rec_, a, stream_, st, alpha_tab_, lr_tab_);
-        if (st) launch_step_advance(st_dev_, B, stream_);
-        optim_last_path_ = 1;
-        return;
-    }
-    optim_last_path_ = 0;
-    const bool unfused = getenv("CMOOP_ADAM_UNFUSED") != nullptr;   // A/B knob (read per step: tests flip it): round-1 launch sequence
-    if (unfused) {
+    } else if (getenv("CMOOP_ADAM_UNFUSED") != nullptr) {   // A/B knob (read per step: tests flip it): round-1 launch sequence
         for (const AdamSeg& sg : slab_segs_) launch_reduce_slices(sg.slab, grads_ + sg.off, sg.S, sg.n, stream_, sg.stride);
         launch_adam(params_, grads_, adam_m_, adam_v_, n_params_, alpha, (float)(1.0 - b1), (float)(1.0 - b2),
                     (float)cfg_.adam_eps, stream_, st, alpha_tab_);
-        if (st) launch_step_advance(st_dev_, B, stream_);
-        return;
+    } else {
+        adam_segments_finalize(tab);
+        launch_adam_segments(params_, grads_, adam_m_, adam_v_, tab, alpha, (float)(1.0 - b1), (float)(1.0 - b2),
+                             (float)cfg_.adam_eps, stream_, st, alpha_tab_);
     }
-    adam_segments_finalize(tab);
-    launch_adam_segments(params_, grads_, adam_m_, adam_v_, tab, alpha, (float)(1.0 - b1), (float)(1.0 - b2),
-                         (float)cfg_.adam_eps, stream_, st, alpha_tab_);
+    optim_last_path_ = optim_finish_ ? 1 : 0;
     if (st) launch_step_advance(st_dev_, B, stream_);
 }
 
@@ -1059,9 +1053,8 @@ void Net::begin_fit(int64_t total_steps) {
     alpha_tab_n_ = total_steps;
     if (!st_dev_) st_dev_ = reinterpret_cast<StepState*>(dalloc(8));
     upload_rate_tables();
-    const StepState st0{0, (unsigned)step_, (unsigned)iterations_};
-    CMOOP_HIP(hipMemcpyAsync(st_dev_, &st0, sizeof(StepState), hipMemcpyHostToDevice, stream_));
-    CMOOP_HIP(hipStreamSynchronize(stream_));     // st0 is a local
+    upload_step_state();
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // the state is there before a step reads it
     // hipGraph replay of the captured step is OPT-IN (CMOOP_GRAPH=1).  Measured: a lone 16-filter candidate runs 2 591
     // steps/s replayed vs 2 625 launched eagerly (its stream is kept busy either way: ~50 kernels of ~8 us per step,
     // the host launches faster than that), and the pop-40 bench is 1.5 % slower replayed (2 089 vs 2 121 evals/h).
@@ -1082,6 +1075,30 @@ void Net::upload_rate_tables() {
     CMOOP_HIP(hipMemcpyAsync(alpha_tab_, alpha.data(), alpha_tab_n_ * 4, hipMemcpyHostToDevice, stream_));
     if (optim_finish_) CMOOP_HIP(hipMemcpyAsync(lr_tab_, lr.data(), alpha_tab_n_ * 4, hipMemcpyHostToDevice, stream_));
     CMOOP_HIP(hipStreamSynchronize(stream_));     // the tables are locals
+}
+
+void Net::drop_graph() {
+    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
+}
+
+void Net::upload_step_state() {
+    if (!st_dev_) return;
+    st_up_ = StepState{0, (unsigned)step_, (unsigned)iterations_};
+    CMOOP_HIP(hipMemcpyAsync(st_dev_, &st_up_, sizeof(StepState), hipMemcpyHostToDevice, stream_));
+}
+
+void Net::ensure_target_buffers() {
+    if (tgt_t_) return;
+    tgt_t_ = dalloc((size_t)cfg_.batch * cfg_.classes);
+    tgt_w_ = dalloc((size_t)cfg_.batch);
+    tgt_primary_ = reinterpret_cast<int32_t*>(dalloc((size_t)cfg_.batch));
+}
+
+void Net::set_options(const TrainOptions& o) {
+    if (o.aug && augment_enabled(*o.aug)) set_augment(o.aug);
+    if (o.loss && loss_enabled(*o.loss)) set_loss(o.loss);
+    if (o.distill && distill_enabled(*o.distill)) set_distill(o.distill);
+    if (o.optim && optim_enabled(*o.optim)) set_optim(o.optim);
 }
 
 void Net::set_optim(const OptimCfg* optim) {
@@ -1105,7 +1122,7 @@ void Net::set_optim(const OptimCfg* optim) {
     optim_finish_ = finish;
     upload_rate_tables();                         // takes effect from the next step
     if (finish) graph_ok_ = false;                // nothing is promised under CMOOP_GRAPH=1
-    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
+    drop_graph();
 }
 
 void Net::optim_stats(double out[4]) {
@@ -1181,12 +1198,9 @@ void Net::set_state(const float* params, const float* m, const float* v, long lo
     if (v) CMOOP_HIP(hipMemcpyAsync(adam_v_, v, n_params_ * 4, hipMemcpyHostToDevice, stream_));
     iterations_ = iterations;
     step_ = steps;
-    if (st_dev_) {
-        const StepState st0{0, (unsigned)step_, (unsigned)iterations_};
-        CMOOP_HIP(hipMemcpyAsync(st_dev_, &st0, sizeof(StepState), hipMemcpyHostToDevice, stream_));
-    }
+    upload_step_state();
     CMOOP_HIP(hipStreamSynchronize(stream_));
-    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
+    drop_graph();
 }
 
 void Net::set_augment(const AugmentCfg* aug) {
@@ -1199,7 +1213,7 @@ void Net::set_augment(const AugmentCfg* aug) {
     }
     CMOOP_HIP(hipStreamSynchronize(stream_));
     aug_on_ = on;
-    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }   // the captured step has the old launch sequence
+    drop_graph();
 }
 
 void Net::set_loss(const LossCfg* loss) {
@@ -1210,11 +1224,7 @@ void Net::set_loss(const LossCfg* loss) {
     TargetParams tp;
     if (on) {
         const size_t C = (size_t)cfg_.classes;
-        if (!tgt_t_) {
-            tgt_t_ = dalloc((size_t)cfg_.batch * C);
-            tgt_w_ = dalloc((size_t)cfg_.batch);
-            tgt_primary_ = reinterpret_cast<int32_t*>(dalloc((size_t)cfg_.batch));
-        }
+        ensure_target_buffers();
         std::vector<float> tab, cw;
         if (mix) {
             CMOOP_REQUIRE((int64_t)T_ * F_ < (1ll << 30), "mixup: T * F must stay below 2^30");
@@ -1242,7 +1252,7 @@ void Net::set_loss(const LossCfg* loss) {
     mix_on_ = mix;
     mixp_ = mp;
     tgtp_ = tp;
-    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }   // the captured step has the old launch sequence
+    drop_graph();
 }
 
 void Net::set_gather_rows(int64_t n) {
@@ -1255,20 +1265,15 @@ void Net::set_distill(const DistillCfg* distill) {
     if (distill) distill_check(*distill, cfg_.classes, distill->n_rows);
     const bool on = distill != nullptr && distill_enabled(*distill);
     if (on) {
-        const size_t C = (size_t)cfg_.classes;
-        if (!tgt_t_) {
-            tgt_t_ = dalloc((size_t)cfg_.batch * C);
-            tgt_w_ = dalloc((size_t)cfg_.batch);
-            tgt_primary_ = reinterpret_cast<int32_t*>(dalloc((size_t)cfg_.batch));
-        }
-        if (!kd_q_) kd_q_ = dalloc((size_t)cfg_.batch * C);
+        ensure_target_buffers();
+        if (!kd_q_) kd_q_ = dalloc((size_t)cfg_.batch * cfg_.classes);
     }
     CMOOP_HIP(hipStreamSynchronize(stream_));
     distill_on_ = on;
     kdp_ = on ? distill_params(*distill) : DistillParams();
     kd_zt_ = on ? distill->teacher_logits : nullptr;
     kd_rows_ = on ? distill->n_rows : 0;
-    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }   // the captured step has the old launch sequence
+    drop_graph();
 }
 
 void Net::loss_buffers(int64_t out[4]) const {
@@ -1299,8 +1304,7 @@ void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch
         idx = idx_scratch;
     }
     if (st_dev_) {   // explicit-argument steps (session API) do not advance the device state: start the epoch from the host's counters
-        const StepState st0{0, (unsigned)step_, (unsigned)iterations_};
-        CMOOP_HIP(hipMemcpyAsync(st_dev_, &st0, sizeof(StepState), hipMemcpyHostToDevice, stream_));
+        upload_step_state();
         CMOOP_HIP(hipStreamSynchronize(stream_));
     }
     begin_epoch();
@@ -1356,26 +1360,20 @@ void Net::predict_stream(const float* feat, int64_t n_frames, int hop, bool db_s
     CMOOP_REQUIRE(feat && probs, "predict_stream: NULL buffer");
     CMOOP_REQUIRE((mean == nullptr) == (scale == nullptr), "predict_stream: mean and scale come together (both or neither)");
     const int B0 = (int)std::min<int64_t>(cfg_.eval_batch, n);
-    float* chunk = static_cast<float*>(pool_alloc((size_t)B0 * T_ * F_ * 4));
-    double* ms = mean ? static_cast<double*>(pool_alloc((size_t)2 * F_ * 8)) : nullptr;
-    auto cleanup = [&]() { hipStreamSynchronize(stream_); pool_free(chunk); if (ms) pool_free(ms); };
-    try {
-        if (ms) {
-            CMOOP_HIP(hipMemcpyAsync(ms, mean, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
-            CMOOP_HIP(hipMemcpyAsync(ms + F_, scale, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
-        }
-        for (int64_t w = 0; w < n; w += cfg_.eval_batch) {       // window i sits at position i % eval_batch of chunk i / eval_batch
-            const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - w);
-            launch_window_gather(feat, chunk, w, B, hop, T_, F_, db_scale ? 1 : 0, db_ref_max ? 1 : 0, db_amin, top_db, ms,
-                                 ms ? ms + F_ : nullptr, stream_);
-            forward(chunk, BatchRows(), B, false);
-            launch_softmax_probs(acts_[logits_].data, probs + w * cfg_.classes, B, cfg_.classes, stream_);
-        }
-    } catch (...) {
-        cleanup();
-        throw;
+    PoolScope pool(stream_);   // the chunk and the scaler go back once the stream has drained
+    float* chunk = pool.get<float>((size_t)B0 * T_ * F_ * 4);
+    double* ms = mean ? pool.get<double>((size_t)2 * F_ * 8) : nullptr;
+    if (ms) {
+        CMOOP_HIP(hipMemcpyAsync(ms, mean, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
+        CMOOP_HIP(hipMemcpyAsync(ms + F_, scale, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
     }
-    cleanup();
+    for (int64_t w = 0; w < n; w += cfg_.eval_batch) {       // window i sits at position i % eval_batch of chunk i / eval_batch
+        const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - w);
+        launch_window_gather(feat, chunk, w, B, hop, T_, F_, db_scale ? 1 : 0, db_ref_max ? 1 : 0, db_amin, top_db, ms,
+                             ms ? ms + F_ : nullptr, stream_);
+        forward(chunk, BatchRows(), B, false);
+        launch_softmax_probs(acts_[logits_].data, probs + w * cfg_.classes, B, cfg_.classes, stream_);
+    }
 }
 
 void Net::read_train_metrics(double* loss_sum, long long* correct, bool reset) {
@@ -1427,93 +1425,81 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
     EvalResult res;
     res.size_mb = (double)(net.total_params() * 4) / (1024.0 * 1024.0);   // compute_model_size_mb, nsga_penalty.py:337-344
 
+    PoolScope pool(stream);   // everything below goes back once the stream has drained, however the fit ends
     int32_t* h_idx = nullptr;
-    int32_t* d_idx = nullptr;
-    int32_t* d_preds = nullptr;
-    int64_t* d_cm = nullptr;
-    d_idx = static_cast<int32_t*>(pool_alloc(ds.n_train * 4));
-    d_preds = static_cast<int32_t*>(pool_alloc(ds.n_val * 4));
-    d_cm = static_cast<int64_t*>(pool_alloc((size_t)cfg.classes * cfg.classes * 8));
-    auto cleanup = [&]() { hipStreamSynchronize(stream); if (h_idx) pool_free_pinned(h_idx); pool_free(d_idx); pool_free(d_preds); pool_free(d_cm); };
-    try {
-        // Model.fit + EarlyStopping(monitor='val_loss', patience) -- keras/src/callbacks/early_stopping.py (3.6)
-        double best = INFINITY, last_val_acc = 0.0, last_val_loss = 0.0;
-        long long last_corr = 0;
-        int wait = 0, best_epoch = -1;
-        bool have_best = false, preds_are_final = false;
-        net.set_gather_rows(ds.n_train);
-        // (a session net that has already trained continues from its own optimizer.iterations)
-        net.begin_fit(net.iterations_done() + (int64_t)cfg.epochs * ((ds.n_train + cfg.batch - 1) / cfg.batch));
-        for (int epoch = 0; epoch < cfg.epochs; ++epoch) {
-            if (cfg.shuffle && ds.n_train <= EPOCH_PERMUTATION_DEVICE_MAX) {
-                launch_epoch_permutation(seed, (uint32_t)epoch, ds.n_train, d_idx, stream);   // no host sort, no H2D
-            } else if (cfg.shuffle || epoch == 0) {
-                if (!h_idx) h_idx = static_cast<int32_t*>(pool_alloc_pinned(ds.n_train * 4));
-                if (cfg.shuffle) epoch_permutation(seed, (uint32_t)epoch, ds.n_train, h_idx);
-                else std::iota(h_idx, h_idx + ds.n_train, 0);
-                CMOOP_HIP(hipMemcpyAsync(d_idx, h_idx, ds.n_train * 4, hipMemcpyHostToDevice, stream));
-                CMOOP_HIP(hipStreamSynchronize(stream));   // h_idx is rewritten next epoch
-            }
-            net.begin_epoch();
-            for (int64_t s = 0; s < ds.n_train; s += cfg.batch)
-                net.train_step_stateful(ds.x_train, ds.y_train, d_idx, (int)std::min<int64_t>(cfg.batch, ds.n_train - s));
-            double ls; long long corr;
-            net.evaluate(ds.x_val, ds.y_val, ds.n_val, &ls, &corr, d_preds);   // keeps this epoch's predictions
-            net.drain_profile();
-            last_val_loss = ls / (double)ds.n_val;
-            last_val_acc = (double)corr / (double)ds.n_val;
-            last_corr = corr;
-            preds_are_final = true;     // d_preds / last_val_* describe the weights the net holds right now
-            res.epochs_run = epoch + 1;
-            if (hist) { hist->val_loss.push_back(last_val_loss); hist->val_acc.push_back(last_val_acc); }
-            if (!cfg.early_stop) continue;
-            if (cfg.restore_best && !have_best) { net.snapshot_params(); have_best = true; }
-            ++wait;
-            if (last_val_loss < best) {
-                best = last_val_loss;
-                if (cfg.restore_best) net.snapshot_params();
-                best_epoch = epoch;
-                wait = 0;
-                continue;
-            }
-            if (wait >= cfg.patience && epoch > 0) break;
+    int32_t* d_idx = pool.get<int32_t>(ds.n_train * 4);
+    int32_t* d_preds = pool.get<int32_t>(ds.n_val * 4);
+    int64_t* d_cm = pool.get<int64_t>((size_t)cfg.classes * cfg.classes * 8);
+    // Model.fit + EarlyStopping(monitor='val_loss', patience) -- keras/src/callbacks/early_stopping.py (3.6)
+    double best = INFINITY, last_val_acc = 0.0, last_val_loss = 0.0;
+    long long last_corr = 0;
+    int wait = 0, best_epoch = -1;
+    bool have_best = false, preds_are_final = false;
+    net.set_gather_rows(ds.n_train);
+    // (a session net that has already trained continues from its own optimizer.iterations)
+    net.begin_fit(net.iterations_done() + (int64_t)cfg.epochs * ((ds.n_train + cfg.batch - 1) / cfg.batch));
+    for (int epoch = 0; epoch < cfg.epochs; ++epoch) {
+        if (cfg.shuffle && ds.n_train <= EPOCH_PERMUTATION_DEVICE_MAX) {
+            launch_epoch_permutation(seed, (uint32_t)epoch, ds.n_train, d_idx, stream);   // no host sort, no H2D
+        } else if (cfg.shuffle || epoch == 0) {
+            if (!h_idx) h_idx = pool.get_pinned<int32_t>(ds.n_train * 4);
+            if (cfg.shuffle) epoch_permutation(seed, (uint32_t)epoch, ds.n_train, h_idx);
+            else std::iota(h_idx, h_idx + ds.n_train, 0);
+            CMOOP_HIP(hipMemcpyAsync(d_idx, h_idx, ds.n_train * 4, hipMemcpyHostToDevice, stream));
+            CMOOP_HIP(hipStreamSynchronize(stream));   // h_idx is rewritten next epoch
         }
-        if (hist) hist->best_epoch = best_epoch;
-        if (cfg.early_stop && cfg.restore_best && have_best && best_epoch != res.epochs_run - 1) {
-            net.restore_snapshot();      // weights of an earlier epoch: the last pass's predictions no longer apply
-            preds_are_final = false;
+        net.begin_epoch();
+        for (int64_t s = 0; s < ds.n_train; s += cfg.batch)
+            net.train_step_stateful(ds.x_train, ds.y_train, d_idx, (int)std::min<int64_t>(cfg.batch, ds.n_train - s));
+        double ls; long long corr;
+        net.evaluate(ds.x_val, ds.y_val, ds.n_val, &ls, &corr, d_preds);   // keeps this epoch's predictions
+        net.drain_profile();
+        last_val_loss = ls / (double)ds.n_val;
+        last_val_acc = (double)corr / (double)ds.n_val;
+        last_corr = corr;
+        preds_are_final = true;     // d_preds / last_val_* describe the weights the net holds right now
+        res.epochs_run = epoch + 1;
+        if (hist) { hist->val_loss.push_back(last_val_loss); hist->val_acc.push_back(last_val_acc); }
+        if (!cfg.early_stop) continue;
+        if (cfg.restore_best && !have_best) { net.snapshot_params(); have_best = true; }
+        ++wait;
+        if (last_val_loss < best) {
+            best = last_val_loss;
+            if (cfg.restore_best) net.snapshot_params();
+            best_epoch = epoch;
+            wait = 0;
+            continue;
         }
-        // readouts: model.evaluate / model.predict + argmax + confusion matrix (one inference pass yields both).  When
-        // the net still holds the weights of its last epoch, that epoch's validation pass IS this pass (inference is
-        // deterministic): its loss, accuracy and predictions are reused instead of recomputing N_val forward passes.
-        double ls = last_val_loss * (double)ds.n_val;
-        long long corr = last_corr;
-        if (!preds_are_final) net.evaluate(ds.x_val, ds.y_val, ds.n_val, &ls, &corr, d_preds);
-        res.val_loss = cfg.acc_readout == 0 ? last_val_loss : ls / (double)ds.n_val;
-        res.acc = cfg.acc_readout == 0 ? last_val_acc : (double)corr / (double)ds.n_val;
-        launch_confusion(ds.y_val, d_preds, ds.n_val, cfg.classes, cfg.fpr_variant == 1, d_cm, stream);
-        std::vector<int64_t> cm((size_t)cfg.classes * cfg.classes);
-        CMOOP_HIP(hipMemcpyAsync(cm.data(), d_cm, cm.size() * 8, hipMemcpyDeviceToHost, stream));
-        CMOOP_HIP(hipStreamSynchronize(stream));
-        res.fpr = fpr_from_confusion(cm.data(), cfg.classes, cfg.fpr_variant == 2 ? 2 : 0);
-    } catch (...) {
-        cleanup();
-        throw;
+        if (wait >= cfg.patience && epoch > 0) break;
     }
-    cleanup();
+    if (hist) hist->best_epoch = best_epoch;
+    if (cfg.early_stop && cfg.restore_best && have_best && best_epoch != res.epochs_run - 1) {
+        net.restore_snapshot();      // weights of an earlier epoch: the last pass's predictions no longer apply
+        preds_are_final = false;
+    }
+    // readouts: model.evaluate / model.predict + argmax + confusion matrix (one inference pass yields both).  When
+    // the net still holds the weights of its last epoch, that epoch's validation pass IS this pass (inference is
+    // deterministic): its loss, accuracy and predictions are reused instead of recomputing N_val forward passes.
+    double ls = last_val_loss * (double)ds.n_val;
+    long long corr = last_corr;
+    if (!preds_are_final) net.evaluate(ds.x_val, ds.y_val, ds.n_val, &ls, &corr, d_preds);
+    res.val_loss = cfg.acc_readout == 0 ? last_val_loss : ls / (double)ds.n_val;
+    res.acc = cfg.acc_readout == 0 ? last_val_acc : (double)corr / (double)ds.n_val;
+    launch_confusion(ds.y_val, d_preds, ds.n_val, cfg.classes, cfg.fpr_variant == 1, d_cm, stream);
+    std::vector<int64_t> cm((size_t)cfg.classes * cfg.classes);
+    CMOOP_HIP(hipMemcpyAsync(cm.data(), d_cm, cm.size() * 8, hipMemcpyDeviceToHost, stream));
+    CMOOP_HIP(hipStreamSynchronize(stream));
+    res.fpr = fpr_from_confusion(cm.data(), cfg.classes, cfg.fpr_variant == 2 ? 2 : 0);
     res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return res;
 }
 
 EvalResult run_candidate(const int32_t gene[6], const NetConfig& cfg, const Dataset& ds, uint32_t seed, hipStream_t stream,
-                         const AugmentCfg* aug, const LossCfg* loss, const DistillCfg* distill, const OptimCfg* optim) {
+                         const TrainOptions& opt) {
     const auto t0 = std::chrono::steady_clock::now();
     CMOOP_REQUIRE(ds.n_train >= 1 && ds.n_val >= 1, "empty train or validation split");
     Net net(gene, cfg, ds.T, ds.F, seed, stream);
-    if (aug) net.set_augment(aug);
-    if (loss) net.set_loss(loss);
-    if (distill) net.set_distill(distill);
-    if (optim) net.set_optim(optim);
+    net.set_options(opt);
     EvalResult res = fit_and_read_out(net, cfg, ds, seed, nullptr);
     res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return res;
@@ -1534,13 +1520,8 @@ void check_plan_ranges(const int32_t gene[6], int variant, int T, int F, int B) 
 }
 
 void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* genes, const uint32_t* seeds, int n,
-                     EvalResult* out, const std::function<int()>& pull, const AugmentCfg* aug, const LossCfg* loss,
-                     const DistillCfg* distill, const OptimCfg* optim) {
+                     EvalResult* out, const std::function<int()>& pull, const TrainOptions& opt) {
     if (n <= 0) return;
-    if (aug && !augment_enabled(*aug)) aug = nullptr;   // a disabled config is no config: today's path, call for call
-    if (loss && !loss_enabled(*loss)) loss = nullptr;
-    if (distill && !distill_enabled(*distill)) distill = nullptr;
-    if (optim && !optim_enabled(*optim)) optim = nullptr;
     for (int i = 0; i < n; ++i) validate_gene(genes + 6 * i);
     for (int i = 0; i < n; ++i) out[i].evaluated = 0;
     // longest first (closed-form FLOPs) so the tail of the generation is made of cheap candidates
@@ -1572,7 +1553,7 @@ void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* gen
                     if (j >= n) break;
                     i = order[j];
                 }
-                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream, aug, loss, distill, optim);
+                out[i] = run_candidate(genes + 6 * i, cfg, ds, seeds[i], stream, opt);
                 out[i].evaluated = 1;
             }
         } catch (const std::exception& e) {

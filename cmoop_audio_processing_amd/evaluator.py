@@ -79,20 +79,19 @@ class EvalConfig:
     # "size_fpr" (size_fpr_nsga_1.py:283-310, 'acc_metric')
     objectives: str = "all"
     # train-time augmentation of every candidate's fit (augment.py): None or a config that does nothing = off, every number
-    # as without the field.  Not part of cmoop_config: it travels beside it (cmoop_net_set_augment, cmoop_eval_population_aug)
+    # as without the field.  Not part of cmoop_config: like the three below it travels beside it (cmoop_net_set_augment for a
+    # session, option_structs -> the one population call)
     augment: Optional[AugmentConfig] = None
     # soft-target training loss of every candidate's fit (loss.py: mixup, label smoothing, class weights): None or a config
-    # that does nothing = off, every number as without the field.  Validation stays the sparse cross-entropy.  Travels
-    # beside cmoop_config like augment (cmoop_net_set_loss, cmoop_eval_population_ex)
+    # that does nothing = off, every number as without the field.  Validation stays the sparse cross-entropy
+    # (cmoop_net_set_loss)
     loss: Optional[LossConfig] = None
     # knowledge distillation of every candidate's fit (distill.py) against the teacher PopulationEvaluator.set_teacher holds:
     # None or alpha 0 = off, every number as without the field; enabled without a teacher is an error, raised before anything
-    # is launched.  Validation stays the sparse cross-entropy.  Travels beside cmoop_config (cmoop_net_set_distill,
-    # cmoop_eval_population_kd)
+    # is launched.  Validation stays the sparse cross-entropy (cmoop_net_set_distill)
     distill: Optional[DistillConfig] = None
     # optimiser options of every candidate's fit (optim.py): learning-rate schedule, decoupled weight decay, gradient
-    # clipping.  None or a config with everything off = off, every number as without the field.  Travels beside cmoop_config
-    # (cmoop_net_set_optim, cmoop_eval_population_opt)
+    # clipping.  None or a config with everything off = off, every number as without the field (cmoop_net_set_optim)
     optim: Optional[OptimConfig] = None
 
     @staticmethod
@@ -147,7 +146,6 @@ class EvalConfig:
             return None
         return self.augment.check(T, F)._struct()
 
-
     def loss_struct(self) -> Optional["_lib.Loss"]:
         """The enabled training loss as a ``cmoop_loss``, checked for ``classes``; None when it is off."""
         if self.loss is None or not self.loss.enabled:
@@ -159,6 +157,11 @@ class EvalConfig:
         if self.optim is None or not self.optim.enabled:
             return None
         return self.optim.check()._struct()
+
+    def option_structs(self, T: int, F: int, teacher_logits, n_train: int):
+        """(augment, loss, distill, optim) of a fit on [T, F] patches against ``teacher_logits``: the four ``*_struct``
+        results in the order every C entry point takes them, None for whatever is off."""
+        return (self.augment_struct(T, F), self.loss_struct(), self.distill_struct(teacher_logits, n_train), self.optim_struct())
 
     def distill_struct(self, teacher_logits, n_train: int) -> Optional["_lib.Distill"]:
         """The enabled distillation as a ``cmoop_distill`` over the table ``teacher_logits`` (CUDA float32 [n_train,
@@ -414,44 +417,35 @@ class PopulationEvaluator:
         d.T, d.F = self.T, self.F
         return d
 
+    def _population_call(self, genes, sd, n, cfg, next_cb, acc, size, fpr, ep, secs, done) -> None:
+        """THE population call: ``cmoop_eval_population_opt`` with ``config.option_structs`` by reference, None (NULL) for
+        whatever is off; next_cb None: the library's own longest-first counter, and ``done`` is then None too."""
+        ds = self._dataset()
+        opts = self.config.option_structs(self.T, self.F, self.teacher_logits, len(self.X_train))
+        _lib.check(_lib.lib().cmoop_eval_population_opt(
+            C.byref(cfg), *(C.byref(o) if o is not None else None for o in opts), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
+            C.c_int32(n), C.cast(next_cb, C.c_void_p) if next_cb is not None else None, None, _lib.ptr(acc), _lib.ptr(size),
+            _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
+
+    @staticmethod
+    def _population_arrays(gene_list, seeds):
+        """(genes int32 [n, 6], seeds uint32 [n], acc, size_mb, fpr, seconds float64 [n], epochs_run int32 [n]) of a call."""
+        n = len(gene_list)
+        for g in gene_list:
+            G.validate_gene(g)
+        genes = np.ascontiguousarray(np.asarray(gene_list, dtype=np.int32).reshape(n, 6))
+        sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).astype(np.uint32))
+        acc, size, fpr, secs = (np.zeros(n, np.float64) for _ in range(4))
+        return genes, sd, acc, size, fpr, secs, np.zeros(n, np.int32)
+
     def evaluate_genes(self, gene_list: Sequence[Sequence[int]], seeds: Sequence[int]) -> np.ndarray:
         """[n,6] genes -> float64 [n,5] = (accuracy, size_mb, fpr, epochs_run, seconds) on THIS GPU."""
         n = len(gene_list)
         out = np.zeros((n, 5), dtype=np.float64)
         if n == 0:
             return out
-        for g in gene_list:
-            G.validate_gene(g)
-        genes = np.ascontiguousarray(np.asarray(gene_list, dtype=np.int32).reshape(n, 6))
-        sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).astype(np.uint32))
-        acc, size, fpr, secs = (np.zeros(n, np.float64) for _ in range(4))
-        ep = np.zeros(n, np.int32)
-        cfg, ds = self.config.to_struct(), self._dataset()
-        aug, loss = self.config.augment_struct(self.T, self.F), self.config.loss_struct()
-        kd = self.config.distill_struct(self.teacher_logits, len(self.X_train))
-        opt = self.config.optim_struct()
-        if opt is not None:
-            _lib.check(_lib.lib().cmoop_eval_population_opt(
-                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None,
-                C.byref(kd) if kd is not None else None, C.byref(opt), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), None,
-                None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), None))
-        elif kd is not None:
-            _lib.check(_lib.lib().cmoop_eval_population_kd(
-                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None, C.byref(kd),
-                C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), None, None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr),
-                _lib.ptr(ep), None, _lib.ptr(secs), None))
-        elif loss is not None:
-            _lib.check(_lib.lib().cmoop_eval_population_ex(
-                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
-                C.c_int32(n), None, None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), None))
-        elif aug is not None:
-            _lib.check(_lib.lib().cmoop_eval_population_aug(
-                C.byref(cfg), C.byref(aug), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), None, None, _lib.ptr(acc),
-                _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), None))
-        else:
-            _lib.check(_lib.lib().cmoop_eval_population(
-                C.byref(cfg), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), _lib.ptr(acc), _lib.ptr(size),
-                _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs)))
+        genes, sd, acc, size, fpr, secs, ep = self._population_arrays(gene_list, seeds)
+        self._population_call(genes, sd, n, self.config.to_struct(), None, acc, size, fpr, ep, secs, None)
         out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4] = acc, size, fpr, ep, secs
         return out
 
@@ -462,13 +456,9 @@ class PopulationEvaluator:
         n = len(gene_list)
         if n == 0:
             return {}
-        for g in gene_list:
-            G.validate_gene(g)
-        genes = np.ascontiguousarray(np.asarray(gene_list, dtype=np.int32).reshape(n, 6))
-        sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).astype(np.uint32))
-        acc, size, fpr, secs = (np.zeros(n, np.float64) for _ in range(4))
-        ep, done = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        cfg, ds = self.config.to_struct(), self._dataset()
+        genes, sd, acc, size, fpr, secs, ep = self._population_arrays(gene_list, seeds)
+        done = np.zeros(n, np.int32)
+        cfg = self.config.to_struct()
         if workers is not None:
             cfg.n_slots = max(1, int(workers))
         errors: List[BaseException] = []
@@ -479,34 +469,7 @@ class PopulationEvaluator:
             except BaseException as e:      # never let an exception cross the C boundary: end this worker, re-raise below
                 errors.append(e)
                 return -1
-        cb = _lib.NEXT_FN(_next)
-        aug, loss = self.config.augment_struct(self.T, self.F), self.config.loss_struct()
-        kd = self.config.distill_struct(self.teacher_logits, len(self.X_train))
-        opt = self.config.optim_struct()
-        if opt is not None:
-            _lib.check(_lib.lib().cmoop_eval_population_opt(
-                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None,
-                C.byref(kd) if kd is not None else None, C.byref(opt), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n),
-                C.cast(cb, C.c_void_p), None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs),
-                _lib.ptr(done)))
-        elif kd is not None:
-            _lib.check(_lib.lib().cmoop_eval_population_kd(
-                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss) if loss is not None else None, C.byref(kd),
-                C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), C.cast(cb, C.c_void_p), None, _lib.ptr(acc), _lib.ptr(size),
-                _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
-        elif loss is not None:
-            _lib.check(_lib.lib().cmoop_eval_population_ex(
-                C.byref(cfg), C.byref(aug) if aug is not None else None, C.byref(loss), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
-                C.c_int32(n), C.cast(cb, C.c_void_p), None, _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None,
-                _lib.ptr(secs), _lib.ptr(done)))
-        elif aug is not None:
-            _lib.check(_lib.lib().cmoop_eval_population_aug(
-                C.byref(cfg), C.byref(aug), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), C.cast(cb, C.c_void_p), None,
-                _lib.ptr(acc), _lib.ptr(size), _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
-        else:
-            _lib.check(_lib.lib().cmoop_eval_population_pull(
-                C.byref(cfg), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd), C.c_int32(n), cb, None, _lib.ptr(acc), _lib.ptr(size),
-                _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
+        self._population_call(genes, sd, n, cfg, _lib.NEXT_FN(_next), acc, size, fpr, ep, secs, done)
         if errors:
             raise errors[0]
         return {int(i): np.array([acc[i], size[i], fpr[i], ep[i], secs[i]], dtype=np.float64) for i in np.nonzero(done)[0]}

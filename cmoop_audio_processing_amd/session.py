@@ -27,29 +27,20 @@ class NetSession:
         _lib.check(_lib.lib().cmoop_net_total_params(self._h, C.byref(n)))
         self.n_params = int(n.value)
         self.T, self.F = int(T), int(F)
-        self.augment = None
-        if getattr(config, "augment", None) is not None:
-            try:
-                self.set_augment(config.augment)
-            except Exception:
-                self.close()
-                raise
-        self.loss = None
-        if getattr(config, "loss", None) is not None:
-            try:
-                self.set_loss(config.loss)
-            except Exception:
-                self.close()
-                raise
-        self.optim = None
-        if getattr(config, "optim", None) is not None:
-            try:
-                self.set_optim(config.optim)
-            except Exception:
-                self.close()
-                raise
+        self.augment = self.loss = self.optim = None
+        for name, setter in (("augment", self.set_augment), ("loss", self.set_loss), ("optim", self.set_optim)):
+            if getattr(config, name, None) is not None:
+                try:
+                    setter(getattr(config, name))
+                except Exception:
+                    self.close()
+                    raise
         self.distill, self._teacher_logits = None, None     # what the net trains against now (None: no distillation)
         self._distill_pending = bool(getattr(getattr(config, "distill", None), "enabled", False))   # config.distill waits for a table
+
+    def _set(self, symbol: str, struct) -> None:
+        """One ``cmoop_net_set_*`` call: None travels as NULL, a struct by reference."""
+        _lib.check(getattr(_lib.lib(), symbol)(self._h, C.byref(struct) if struct is not None else None))
 
     def set_distill(self, distill=FROM_CONFIG, teacher_logits=None) -> None:
         """Knowledge distillation (``DistillConfig``) of every following train step of this net -- ``train_step``,
@@ -64,7 +55,7 @@ class NetSession:
         if distill is FROM_CONFIG:
             distill = getattr(self.config, "distill", None)
         if distill is None:
-            _lib.check(_lib.lib().cmoop_net_set_distill(self._h, None))
+            self._set("cmoop_net_set_distill", None)
             teacher_logits = None
         else:
             n_rows = 0
@@ -72,8 +63,7 @@ class NetSession:
                 n_rows = int(getattr(teacher_logits, "shape", (0,))[0])
                 check_teacher_table(teacher_logits, n_rows, int(self.config.classes))
             distill.check(int(self.config.classes), teacher_logits, n_rows)
-            st = distill._struct(teacher_logits)
-            _lib.check(_lib.lib().cmoop_net_set_distill(self._h, C.byref(st)))
+            self._set("cmoop_net_set_distill", distill._struct(teacher_logits))
         on = distill is not None and distill.enabled and teacher_logits is not None
         self.distill, self._teacher_logits = (distill, teacher_logits) if on else (None, None)
         self._distill_pending = False
@@ -119,11 +109,7 @@ class NetSession:
         following train step of this net -- ``train_step``, ``run_epoch`` and ``fit`` alike -- from the next step on.  None
         or a config with everything off turns them off (``self.optim`` is then None), and the net steps bit for bit as one
         that never had any.  The schedule is a function of ``iterations``, so ``get_state`` / ``set_state`` carry it."""
-        if optim is None:
-            _lib.check(_lib.lib().cmoop_net_set_optim(self._h, None))
-        else:
-            st = optim.check()._struct()
-            _lib.check(_lib.lib().cmoop_net_set_optim(self._h, C.byref(st)))
+        self._set("cmoop_net_set_optim", None if optim is None else optim.check()._struct())
         self.optim = optim if optim is not None and optim.enabled else None
 
     def optim_stats(self) -> dict:
@@ -139,11 +125,7 @@ class NetSession:
         of this net -- ``train_step``, ``run_epoch`` and ``fit`` alike; None or a config that does nothing turns it off.
         ``evaluate``, ``predict_proba``, ``predict_stream`` and the validation loss of ``fit`` stay the sparse cross-entropy;
         ``train_metrics`` then reports the weighted soft-target loss sum and the rows whose arg max is their own label."""
-        if loss is None:
-            _lib.check(_lib.lib().cmoop_net_set_loss(self._h, None))
-        else:
-            st = loss.check(int(self.config.classes))._struct()
-            _lib.check(_lib.lib().cmoop_net_set_loss(self._h, C.byref(st)))
+        self._set("cmoop_net_set_loss", None if loss is None else loss.check(int(self.config.classes))._struct())
         self.loss = loss
 
     def loss_buffers(self):
@@ -172,11 +154,7 @@ class NetSession:
         """Train-time augmentation (``AugmentConfig``) of every following train step of this net -- ``train_step``,
         ``run_epoch`` and ``fit`` alike; None or a config that does nothing turns it off.  ``evaluate``, ``predict_proba``
         and ``predict_stream`` never augment; ``train_metrics`` then reports the loss and accuracy of the augmented batches."""
-        if augment is None:
-            _lib.check(_lib.lib().cmoop_net_set_augment(self._h, None))
-        else:
-            st = augment.check(self.T, self.F)._struct()
-            _lib.check(_lib.lib().cmoop_net_set_augment(self._h, C.byref(st)))
+        self._set("cmoop_net_set_augment", None if augment is None else augment.check(self.T, self.F)._struct())
         self.augment = augment
 
     def close(self):

@@ -95,12 +95,17 @@ int cmoop_param_count(const int32_t gene[6], int32_t variant, int32_t classes, i
 int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, double* out);
 
 /* compute_objectives_and_constraints' inner loop (nsga_penalty.py:426-427): evaluate n
- * candidates; outputs are host arrays of length n (any may be NULL). */
+ * candidates; outputs are host arrays of length n (any may be NULL).
+ * THE POPULATION CALL.  The six cmoop_eval_population* symbols are ONE call, cmoop_eval_population_opt, each with fewer
+ * of its arguments: next (with ctx and evaluated; NULL: the library's own longest-first queue, evaluated may then be
+ * NULL too) and the four training options aug, loss, distill, optim (cmoop_augment, cmoop_loss, cmoop_distill,
+ * cmoop_optim below, checked in that order).  An option that is NULL or disabled gives exactly -- launch for launch, bit for
+ * bit -- the call without it, so a caller may always take _opt and pass NULL for what is off. */
 int cmoop_eval_population(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
                           const uint32_t* seeds /* [n] */, int32_t n, double* acc, double* size_mb, double* fpr,
                           int32_t* epochs_run, double* val_loss, double* seconds);
 
-/* The same loop drained through a caller-supplied queue: the library's worker threads (cfg.n_slots of them,
+/* The population call drained through a caller-supplied queue (next and evaluated required): the library's worker threads (cfg.n_slots of them,
  * concurrently) call next(ctx) for the index in [0,n) of the next candidate to train; a negative return ends that
  * worker.  Several processes (one per GPU) that share one counter therefore drain ONE longest-first queue, which
  * balances the early-stopped protocol where epochs run are unknown in advance (the reference's loop is serial,
@@ -145,9 +150,7 @@ int cmoop_augment_draws(const cmoop_augment* aug, uint32_t seed, uint32_t step, 
  * row0 + b) of x_dev [.][T][F].  Any config of the domain, enabled or not (p = 0 is a plain gather).  B * T * F < 2^32. */
 int cmoop_augment_batch(const cmoop_augment* aug, const float* x_dev, const int32_t* idx_dev /* may be NULL */, int64_t row0,
                         int32_t B, int32_t T, int32_t F, uint32_t seed, uint32_t step, float* out_dev);
-/* compute_objectives_and_constraints' inner loop with train-time augmentation: cmoop_eval_population (next == NULL: the
- * library's own longest-first queue; evaluated may then be NULL) or cmoop_eval_population_pull (next != NULL) with every
- * candidate's fit augmented by aug.  aug NULL or disabled: exactly those two calls. */
+/* the population call (above) with next and aug */
 int cmoop_eval_population_aug(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_dataset* ds,
                               const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next,
                               void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
@@ -213,8 +216,7 @@ int cmoop_soft_targets(const cmoop_loss* loss, const int32_t* labels_dev, const 
 int cmoop_softmax_ce_soft(const float* z_dev, const float* t_dev, const float* w_dev /* may be NULL */,
                           const int32_t* primary_dev /* may be NULL */, int32_t B, int32_t C, float* dz_dev /* may be NULL */,
                           double* acc_dev, int32_t* preds_dev /* may be NULL */);
-/* cmoop_eval_population_aug with every candidate's fit trained on the soft-target loss.  loss NULL or disabled: exactly
- * cmoop_eval_population_aug. */
+/* the population call (above) with next, aug and loss */
 int cmoop_eval_population_ex(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_dataset* ds,
                              const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next,
                              void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss,
@@ -264,8 +266,7 @@ int cmoop_teacher_targets(const cmoop_loss* loss /* may be NULL */, const float*
 int cmoop_softmax_ce_distill(const float* z_dev, const float* t_dev, const float* w_dev /* may be NULL */,
                              const int32_t* primary_dev /* may be NULL */, const float* q_dev, double alpha, double temperature,
                              int32_t B, int32_t C, float* dz_dev /* may be NULL */, double* acc_dev, int32_t* preds_dev /* may be NULL */);
-/* cmoop_eval_population_ex with every candidate's fit distilled against the table.  distill NULL or disabled: exactly
- * cmoop_eval_population_ex. */
+/* the population call (above) with next, aug, loss and distill */
 int cmoop_eval_population_kd(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
                              const cmoop_dataset* ds, const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n,
                              cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
@@ -320,8 +321,7 @@ int cmoop_optim_rates(const cmoop_optim* optim, const cmoop_config* cfg, int64_t
 /* host-only: the tensor kind of every parameter of a candidate in arena order (cmoop_net_get_params), kinds[n]:
  * 0 kernel, 1 other trainable (bias, gamma, beta), 2 not trainable (BatchNorm moving mean / variance); n must be its parameter count */
 int cmoop_param_kinds(const int32_t gene[6], int32_t variant, int32_t classes, uint8_t* kinds, int64_t n);
-/* cmoop_eval_population_kd with every candidate's fit under the optimiser options.  optim NULL or disabled: exactly
- * cmoop_eval_population_kd. */
+/* the population call (above) with every argument: the other five forward here */
 int cmoop_eval_population_opt(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
                               const cmoop_optim* optim, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
                               const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,

@@ -125,6 +125,24 @@ def test_compute_mode_reaches_the_abi_struct():
     assert "#define CMOOP_GEMM_BF16X3 2" in hdr and "#define CMOOP_GEMM_BF16 3" in hdr and "int32_t gemm_mode;" in hdr
 
 
+def test_option_structs_is_the_four_struct_methods_in_abi_order(monkeypatch):
+    """EvalConfig.option_structs -> (augment, loss, distill, optim), None for whatever is off.  Nothing here loads the library:
+    the enabled cases, whose check() does, are in tests/test_gpu_train_options.py."""
+    import pytest
+    from cmoop_audio_processing_amd import AugmentConfig, DistillConfig, EvalConfig, LossConfig, OptimConfig
+    assert EvalConfig().option_structs(21, 12, None, 40) == (None, None, None, None)
+    off = EvalConfig(augment=AugmentConfig(), loss=LossConfig(), distill=DistillConfig(alpha=0.0), optim=OptimConfig())
+    assert off.option_structs(21, 12, None, 40) == (None, None, None, None)
+    with pytest.raises(ValueError, match="no teacher is set"):
+        EvalConfig(distill=DistillConfig(alpha=0.5)).option_structs(21, 12, None, 40)
+    # the composition itself: each method's result in its slot, called with what it takes
+    monkeypatch.setattr(EvalConfig, "augment_struct", lambda self, T, F: ("aug", T, F))
+    monkeypatch.setattr(EvalConfig, "loss_struct", lambda self: "loss")
+    monkeypatch.setattr(EvalConfig, "distill_struct", lambda self, table, n_train: ("kd", table, n_train))
+    monkeypatch.setattr(EvalConfig, "optim_struct", lambda self: "optim")
+    assert EvalConfig().option_structs(21, 12, "table", 40) == (("aug", 21, 12), "loss", ("kd", "table", 40), "optim")
+
+
 def test_queued_map_without_process_group_is_a_local_longest_first_queue():
     from cmoop_audio_processing_amd import queued_map
     seen = []
