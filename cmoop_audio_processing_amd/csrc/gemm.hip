@@ -172,7 +172,7 @@ std::string gemm_kernel_name(int cls, int code) {
         return "igemm_fwd_kernel<" + std::to_string(bm) + ", " + std::to_string(bn) + ", " + std::to_string(bk) + ", " +
                std::to_string(wm) + ", " + std::to_string(mode) + ">";
     }
-    // launch_igemm_wgrad's code: mode * 10^7 + (64-row chunks ? 10^6 : 0) + BCO * 1000 + BKI
+    // WgradChoice::code(): mode * 10^7 + (64-row chunks ? 10^6 : 0) + BCO * 1000 + BKI; the halo kernel: KS * 1000 + W / 4
     const int mode = code / 10000000, mc = (code / 1000000) % 10 ? 64 : 32, c = code % 1000000;
     if (mode == GEMM_FP32_HALO) return "halo_wgrad_kernel<" + std::to_string(c / 1000) + ", " + std::to_string(c % 1000) + ">";
     const std::string tile = std::to_string(c / 1000) + ", " + std::to_string(c % 1000);
@@ -1226,6 +1226,20 @@ __global__ __launch_bounds__(256) void splitk_combine_kernel(const float* __rest
     }
 }
 
+// One 256-thread kernel launch on s, timed when tm asks for it (GemmTiming): tm->ext fills the events with the kernel's own
+// begin / end, otherwise an event pair is recorded around the launch.  Every timed launch of this file goes through here, so
+// the two timing modes cannot see different argument lists.
+template <class... KA, class... A>
+static void launch_timed(void (*kernel)(KA...), dim3 grid, size_t lds, hipStream_t s, const GemmTiming* tm, A&&... args) {
+    if (tm && tm->start && tm->ext) {
+        hipExtLaunchKernelGGL(kernel, grid, dim3(256), (uint32_t)lds, s, tm->start, tm->stop, 0, static_cast<KA>(args)...);
+    } else {
+        if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->start, s));
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, static_cast<KA>(args)...);
+        if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->stop, s));
+    }
+}
+
 template <int BM, int BN, int BK, int WM, int MODE = 0>
 static void launch_fwd_t(const float* X, const float* Wt, float* Y, const GeomDev& g, const EpiDev& e_in, hipStream_t s,
                          const GemmTiming* tm, float* slab, int splits, int balanced_wgs = 0, const uint2* rowtab = nullptr,
@@ -1245,14 +1259,7 @@ static void launch_fwd_t(const float* X, const float* Wt, float* Y, const GeomDe
         sl = slab;
         splits = 2;            // any value > 1: take the combine path below
     }
-    if (tm && tm->start && tm->ext) {
-        hipExtLaunchKernelGGL((igemm_fwd_kernel<BM, BN, BK, WM, MODE>), grid, dim3(256), 0, s, tm->start, tm->stop, 0, X, Wt, Y, g,
-                              e, sl, cps, rowtab, tab_rows);
-    } else {
-        if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->start, s));
-        hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, BK, WM, MODE>), grid, dim3(256), 0, s, X, Wt, Y, g, e, sl, cps, rowtab, tab_rows);
-        if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->stop, s));
-    }
+    launch_timed(igemm_fwd_kernel<BM, BN, BK, WM, MODE>, grid, 0, s, tm, X, Wt, Y, g, e, sl, cps, rowtab, tab_rows);
     CMOOP_HIP(hipGetLastError());
     if (splits > 1) {
         const size_t total = (size_t)g.M * g.Cout;
@@ -1433,6 +1440,20 @@ void halo_rows_bound_and_need(const ConvGeom& cg, int* bound, int* need, int* it
     *bound = hd.rows_max; *need = worst; *items_cap = halo_nst(bm) * 256 / (hd.WP * 4);
 }
 
+// Workgroups per CU of the halo kernels: their registers allow three, their LDS image usually too.  A grid of one to three
+// rounds is quantised by the slot count -- 1 020 workgroups (128->128 @51x20 as two 64-column halves) are 1.33 rounds of 768
+// slots but 1.99 rounds of 512 -- so the LDS request is padded past a third of the CU's 160 KiB when two per CU fill their
+// last round better.  Isolated: 128->128 k5 @51x20 116 -> 140.8 TFLOP/s, k3 106 -> 124, 64->128 k5 113 -> 133; grids of more
+// than two rounds keep three per CU (64->64 k5 @101x40, 2 020 workgroups: 137.5 vs 133.7 with two).
+// occ_env >= 0, the forward launch: CMOOP_HALO_OCC (2 / 3 forces either, 0 decides here) and only images of <= 53 KiB are
+// padded; occ_env < 0, the weight-gradient launch: neither the switch nor the size condition.
+static size_t halo_lds_for_occupancy(size_t lds, long wgs, int occ_env) {
+    auto fill = [&](long slots) { return (double)wgs / (double)(((wgs + slots - 1) / slots) * slots); };
+    const bool better = wgs <= 1536 && fill(512) > fill(768) + 0.05;
+    const bool two = occ_env < 0 ? better : (occ_env == 2 || (occ_env != 3 && lds <= 53 * 1024 && better));
+    return two ? std::max(lds, (size_t)55 * 1024) : lds;
+}
+
 static FwdChoice choose_fwd(const ConvGeom& cg, const GemmEpilogue& ep, size_t ws_floats, bool want_stats, bool have_rowtab) {
     FwdChoice c;
     const int M = cg.M(), N = cg.Cout, K = cg.K();
@@ -1535,39 +1556,18 @@ int launch_igemm_fwd(const float* X, const float* Wt, float* Y, const ConvGeom& 
             grid = dim3((unsigned)((units + bal.L - 1) / bal.L), 1, 1);
             lds = std::max(lds, (size_t)55 * 1024);                   // one round of two workgroups per CU
         }
-        // Workgroups per CU: the kernel's registers allow three, its LDS image usually too.  A grid of one to three rounds
-        // is quantised by the slot count -- 1 020 workgroups (128->128 @51x20 as two 64-column halves) are 1.33 rounds of 768
-        // slots but 1.99 rounds of 512 -- so the LDS request is padded past a third of the CU's 160 KiB when two per CU
-        // fill their last round better (CMOOP_HALO_OCC=2 / 3 forces either).  Isolated: 128->128 k5 @51x20 116 -> 140.8 TFLOP/s,
-        // k3 106 -> 124, 64->128 k5 113 -> 133; grids of more than two rounds keep three per CU (64->64 k5 @101x40, 2 020
-        // workgroups: 137.5 vs 133.7 with two).
-        {
-            static const int occ_env = [] { const char* v = std::getenv("CMOOP_HALO_OCC"); return v ? std::atoi(v) : 0; }();
-            const long wgs = (long)grid.x * grid.y;
-            auto fill = [&](long slots) { return (double)wgs / (double)(((wgs + slots - 1) / slots) * slots); };
-            const bool two = occ_env == 2 || (occ_env != 3 && lds <= 53 * 1024 && wgs <= 1536 && fill(512) > fill(768) + 0.05);
-            if (two) lds = std::max(lds, (size_t)55 * 1024);
-        }
-#define CMOOP_HALO_LAUNCH(KS_, BM_, BN_, WM_, BAL_)                                                                                        \
-        do {                                                                                                                 \
-            if (tm && tm->start && tm->ext) {                                                                                \
-                hipExtLaunchKernelGGL((halo_fwd_kernel<KS_, BM_, BN_, WM_, BAL_>), grid, dim3(256), lds, s, tm->start, tm->stop, 0, X, Wt, Y, g, e, hd, splitk_ws); \
-            } else {                                                                                                         \
-                if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->start, s));                                                \
-                hipLaunchKernelGGL((halo_fwd_kernel<KS_, BM_, BN_, WM_, BAL_>), grid, dim3(256), lds, s, X, Wt, Y, g, e, hd, splitk_ws);    \
-                if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->stop, s));                                                 \
-            }                                                                                                                \
-        } while (0)
+        static const int occ_env = [] { const char* v = std::getenv("CMOOP_HALO_OCC"); const int o = v ? std::atoi(v) : 0; return o == 2 || o == 3 ? o : 0; }();
+        lds = halo_lds_for_occupancy(lds, (long)grid.x * grid.y, occ_env);
+        auto run = [&](auto kernel) { launch_timed(kernel, grid, lds, s, tm, X, Wt, Y, g, e, hd, splitk_ws); };
 #define CMOOP_HALO_KS(KS_)                                                                     \
         do {                                                                                   \
-            if (ch.halo_L > 0) CMOOP_HALO_LAUNCH(KS_, 128, 64, 2, true);                       \
-            else if (bn == 64) CMOOP_HALO_LAUNCH(KS_, 128, 64, 2, false);                      \
-            else if (bn == 32) CMOOP_HALO_LAUNCH(KS_, 256, 32, 4, false);                      \
-            else CMOOP_HALO_LAUNCH(KS_, 256, 16, 4, false);                                    \
+            if (ch.halo_L > 0) run(halo_fwd_kernel<KS_, 128, 64, 2, true>);                    \
+            else if (bn == 64) run(halo_fwd_kernel<KS_, 128, 64, 2, false>);                   \
+            else if (bn == 32) run(halo_fwd_kernel<KS_, 256, 32, 4, false>);                   \
+            else run(halo_fwd_kernel<KS_, 256, 16, 4, false>);                                 \
         } while (0)
         if (cg.KH == 5) CMOOP_HALO_KS(5); else CMOOP_HALO_KS(3);
 #undef CMOOP_HALO_KS
-#undef CMOOP_HALO_LAUNCH
         CMOOP_HIP(hipGetLastError());
         if (ch.halo_L > 0) {     // fixed-order sum of every tile's pieces + the epilogue
             const size_t total = (size_t)g.M * g.Cout;
@@ -2203,14 +2203,15 @@ __global__ __launch_bounds__(256) void igemm_wgrad_bf16_kernel(const float* __re
         }
 }
 
-// 128-wide K tiles double the MFMA work per barrier but halve the number of tiles: use them only
+// tile of the weight-gradient kernels: BCO output channels x BKI columns of K, and the LDS bytes of one workgroup (two 32-row
+// images, or one of 64 rows).  128-wide K tiles double the MFMA work per barrier but halve the number of tiles: use them only
 // when the grid still covers the chip with the row slices available (M / 256)
-static inline int wgrad_bco(int N) { return N <= 16 ? 16 : (N <= 32 ? 32 : (N <= 64 ? 64 : 128)); }
-static inline int wgrad_bki(int M, int N, int K) {
-    if (K < 512) return 64;
-    const int bco = wgrad_bco(N);
+struct WgradTile { int bco, bki, lds_bytes; };
+static WgradTile wgrad_tile(int M, int N, int K) {
+    const int bco = N <= 16 ? 16 : (N <= 32 ? 32 : (N <= 64 ? 64 : 128));
     const long blocks = (long)cdiv(K, 128) * cdiv(N, bco) * std::max(1, M / 256);
-    return blocks >= 1024 ? 128 : 64;
+    const int bki = (K >= 512 && blocks >= 1024) ? 128 : 64;
+    return {bco, bki, 2 * 32 * ((bki + 16) + (bco == 16 ? 16 : bco + 16)) * 4};
 }
 
 // XCD-grouped wgrad grid: OFF by default.  Measured round 2 (after the row-table loader, slice count chosen per XCD so
@@ -2246,18 +2247,20 @@ static int halo_wgrad_slices(const ConvGeom& g) {
 }
 
 int wgrad_slices(const ConvGeom& g) {
+    // The halo slice count follows the DEFAULT mode, not the op's: a net configured for a bf16 mode launches the implicit-GEMM
+    // kernel (choose_wgrad) with the halo kernel's slice count.  Using the op's mode here would change the slice count, and
+    // with it the summation order, of those nets: left as it is until that is decided as a change of behaviour.
     if (halo_wgrad_geometry(g)) return halo_wgrad_slices(g);
     const int M = g.M(), K = g.K(), N = g.Cout;
-    const int bco = wgrad_bco(N);
-    const int tiles = cdiv(K, wgrad_bki(M, N, K)) * cdiv(N, bco);
+    const WgradTile t = wgrad_tile(M, N, K);
+    const int tiles = cdiv(K, t.bki) * cdiv(N, t.bco);
+    const int wgs_per_cu = std::max(1, std::min(8, (160 * 1024) / t.lds_bytes));            // LDS-limited occupancy
+    const int64_t nk = (int64_t)N * K;
+    const int cap = (int)std::max<int64_t>(8, (16ll << 20) / std::max<int64_t>(nk, 1));     // <= ~16M slab floats, but >= 8 slices
     if (wgrad_xcd_grouped() && resolve_mode(GEMM_DEFAULT) == GEMM_FP32 && M / 256 >= 8) {
         // XCD-grouped grid: S = 8 G, each XCD runs G * tiles workgroups on its 32 CUs: choose the G whose last wave of
-        // co-resident workgroups (LDS-limited occupancy) is >= 90 % full, within the slab budget and >= 256 rows per slice
-        const int bki = wgrad_bki(M, N, K);
-        const int lds_bytes = 2 * 32 * ((bki + 16) + (bco == 16 ? 16 : bco + 16)) * 4;
-        const int slots = 32 * std::max(1, std::min(8, (160 * 1024) / lds_bytes));
-        const int64_t nk = (int64_t)N * K;
-        const int cap = (int)std::max<int64_t>(8, (16ll << 20) / std::max<int64_t>(nk, 1));
+        // co-resident workgroups is >= 90 % full, within the slab budget and >= 256 rows per slice
+        const int slots = 32 * wgs_per_cu;
         const int maxG = std::max(1, std::min(std::min(cap, M / 256) / 8, 64));
         const int wantG = std::max(1, std::min(maxG, cdiv(2048, tiles * 8)));      // aim at >= ~2048 workgroups chip-wide
         int best = wantG;
@@ -2272,51 +2275,63 @@ int wgrad_slices(const ConvGeom& g) {
         return 8 * best;
     }
     static const int target_wgs = [] { const char* e = std::getenv("CMOOP_WGRAD_WGS"); const int v = e ? std::atoi(e) : 0; return v >= 256 && v <= 8192 ? v : 2048; }();
-    int S = cdiv((int)(target_wgs * par_scale()), tiles);
-    // cap the slab traffic (S*N*K floats written and read back): at most ~16M floats, but keep >= 8 slices
-    const int64_t nk = (int64_t)N * K;
-    const int cap = (int)std::max<int64_t>(8, (16ll << 20) / std::max<int64_t>(nk, 1));
-    if (S > cap) S = cap;
-    const int maxS0 = std::max(1, M / 256);
-    if (S > maxS0) S = maxS0;
-    // few-wave grids: choose the slice count that fills whole waves of co-resident workgroups
-    // (LDS-limited occupancy of each instantiation: 160 KiB / LDS per workgroup)
-    const int bki = wgrad_bki(M, N, K);
-    const int lds_bytes = 2 * 32 * ((bki + 16) + (bco == 16 ? 16 : bco + 16)) * 4;
-    const int resident = std::max(32, (int)(par_scale() * 256 * std::max(1, std::min(8, (160 * 1024) / lds_bytes))));
-    if ((long)tiles * S < 4l * resident) S = fill_waves(tiles, S, resident, 0.95);
     const int maxS = std::max(1, M / 256);
-    if (S > maxS) S = maxS;
-    if (S < 1) S = 1;
-    return S;
+    int S = std::min(std::min(cdiv((int)(target_wgs * par_scale()), tiles), cap), maxS);
+    // few-wave grids: choose the slice count that fills whole waves of co-resident workgroups
+    const int resident = std::max(32, (int)(par_scale() * 256 * wgs_per_cu));
+    if ((long)tiles * S < 4l * resident) S = fill_waves(tiles, S, resident, 0.95);
+    return std::max(1, std::min(S, maxS));
 }
 
-// 64-row chunks on a SINGLE LDS image for the <= 64-channel weight-gradient tiles (row-table gather only): the same LDS footprint
-// as two 32-row images, twice the MFMAs per chunk of fixed loop / wait / barrier overhead (the <64,128> tile runs 64 MFMAs per
-// wave and chunk against ~110 other instructions; PMC: 0.70 of the SIMD cycles in MFMA against 0.81 for <128,128>).  Round 3:
-// 64->64 k5 @101x40 107.2 -> 113.0 TFLOP/s, k3 95.8 -> 99.6, 32->32 k5 89.6 -> 92.1, 16->16 k3 43.3 -> 47.7; the job 2 179 -> 2 181 / 2 187
-// evals/h (two A/B pairs).  CMOOP_WGRAD_MC64=0 restores 32-row chunks everywhere.
-static bool wgrad_mc64(bool rowtab_gather, int mode, int bco) {
-    static const bool on = [] { const char* v = std::getenv("CMOOP_WGRAD_MC64"); return !(v && v[0] == '0'); }();
+// instantiation / row-table / chunk-depth choice of a weight-gradient launch with S row slices: pure host arithmetic on the
+// geometry (no HIP call), shared by the launcher and by the host-only launch plan the parity-coverage tests read
+// (igemm_wgrad_plan).  tab_rows: entries of the row table the launch is given, 0: none.
+struct WgradChoice {
+    int mode, bco, bki, mc /* pixel rows per chunk: 32 | 64 */, flags;
+    bool halo, use_tab;
+    int ks, steps;           // halo kernel: window size, W / 4 MFMA steps per image row
+    int code() const { return mode * 10000000 + (halo ? ks * 1000 + steps : (mc == 64 ? 1000000 : 0) + bco * 1000 + bki); }
+};
+
+static WgradChoice choose_wgrad(const ConvGeom& g, int S, int mode_req, int tab_rows) {
+    WgradChoice c;
+    const int M = g.M(), N = g.Cout;
+    const WgradTile t = wgrad_tile(M, N, g.K());
+    c.bco = t.bco; c.bki = t.bki; c.mc = 32; c.use_tab = false; c.ks = g.KH; c.steps = g.W / 4;
+    // the bf16 loaders read dY as aligned float4: the classifier layer (10 / 11 / 35 columns) stays on the fp32 kernel
+    c.mode = (N % 4 == 0) ? resolve_mode(mode_req) : (int)GEMM_FP32;
+    // bf16x3 pays the split VALU work per loaded element: with fewer than 128 output channels per block there are too
+    // few MFMAs per element to hide it (measured 58 vs 73 TFLOP/s on 64->64 k5) -- the exact kernel is the better
+    // fp32-accurate choice there.  (GEMM_BF16 must round everywhere to stay consistent with its definition.)
+    if (c.mode == GEMM_BF16X3 && c.bco < 128) c.mode = GEMM_FP32;
+    c.flags = S > 1 ? GEMM_FLAG_SLABS : 0;
+    c.halo = c.mode == GEMM_FP32 && halo_wgrad_geometry(g);
+    if (c.halo) { c.mode = GEMM_FP32_HALO; return c; }
+    // Row-table gather: the fp32 kernel only, float4 columns, a padding mask of <= 32 taps, and a table that covers every
+    // row a chunk can touch -- rows are consumed mc at a time, so cdiv(M, mc) * mc of them for the chunk depth chosen.
+    auto covers = [&](int mc) { return tab_rows > 0 && tab_rows >= cdiv(M, mc) * mc; };
+    const bool gather = c.mode == GEMM_FP32 && (N & 3) == 0 && g.KH * g.KW <= 32;
+    // 64-row chunks on a SINGLE LDS image for the <= 64-channel tiles (row-table gather only): the same LDS footprint as two
+    // 32-row images, twice the MFMAs per chunk of fixed loop / wait / barrier overhead (the <64,128> tile runs 64 MFMAs per
+    // wave and chunk against ~110 other instructions; PMC: 0.70 of the SIMD cycles in MFMA against 0.81 for <128,128>).  Round 3:
+    // 64->64 k5 @101x40 107.2 -> 113.0 TFLOP/s, k3 95.8 -> 99.6, 32->32 k5 89.6 -> 92.1, 16->16 k3 43.3 -> 47.7; the job 2 179 -> 2 181 / 2 187
+    // evals/h (two A/B pairs).  CMOOP_WGRAD_MC64=0 restores 32-row chunks everywhere.
     // (the 128-channel tile does NOT gain: <128,128> 130.6 -> 126.8 TFLOP/s on 128->128 k5, 120.6 -> 112.4 on 512->512 k3 -- it already runs
     // 128 MFMAs per chunk and the second barrier costs more than the amortisation buys)
-    return on && rowtab_gather && mode == GEMM_FP32 && bco <= 64;
+    static const bool mc64_on = [] { const char* v = std::getenv("CMOOP_WGRAD_MC64"); return !(v && v[0] == '0'); }();
+    // a table that covers the 32-row rounding but not the 64-row one keeps the 32-row kernel with the table
+    if (gather && mc64_on && c.bco <= 64 && covers(64)) { c.mc = 64; c.use_tab = true; }
+    else c.use_tab = gather && covers(32);
+    if (c.use_tab) c.flags |= GEMM_FLAG_ROWTAB;
+    return c;
 }
 
 // instantiation code + flags of the weight-gradient launch for this geometry with S row slices (host arithmetic only)
 int igemm_wgrad_plan(const ConvGeom& g, int S, int mode_req, bool have_rowtab, int* flags_out) {
     igemm_check_range(g);
-    const int N = g.Cout, M = g.M();
-    const int bco = wgrad_bco(N), bki = wgrad_bki(M, N, g.K());
-    int mode = (N % 4 == 0) ? resolve_mode(mode_req) : (int)GEMM_FP32;
-    if (mode == GEMM_BF16X3 && bco < 128) mode = GEMM_FP32;
-    const bool rt = have_rowtab && g.KH * g.KW <= 32;
-    if (mode == GEMM_FP32 && halo_wgrad_geometry(g)) {
-        if (flags_out) *flags_out = S > 1 ? GEMM_FLAG_SLABS : 0;
-        return GEMM_FP32_HALO * 10000000 + g.KH * 1000 + g.W / 4;
-    }
-    if (flags_out) *flags_out = ((rt && mode == GEMM_FP32 && (N & 3) == 0) ? GEMM_FLAG_ROWTAB : 0) | (S > 1 ? GEMM_FLAG_SLABS : 0);
-    return mode * 10000000 + (wgrad_mc64(rt && (N & 3) == 0, mode, bco) ? 1000000 : 0) + bco * 1000 + bki;
+    const WgradChoice c = choose_wgrad(g, S, mode_req, have_rowtab ? rowtab_rows(g) : 0);
+    if (flags_out) *flags_out = c.flags;
+    return c.code();
 }
 
 int launch_igemm_wgrad(const float* X, const float* dY, float* P, const ConvGeom& cg, int S, hipStream_t s,
@@ -2326,102 +2341,54 @@ int launch_igemm_wgrad(const float* X, const float* dY, float* P, const ConvGeom
     GeomDev g = to_dev(cg);
     if (g.M == 0) return 0;
     const size_t stride = slab_stride ? slab_stride : (size_t)g.Cout * g.K;
-    int rps = cdiv(g.M, S);
-    const int N = g.Cout;
-    const int bco = wgrad_bco(N);
-    const int bki = wgrad_bki(g.M, g.Cout, g.K);
-    // the bf16 loaders read dY as aligned float4: the classifier layer (10 / 11 / 35 columns) stays on the fp32 kernel
-    int mode = (N % 4 == 0) ? resolve_mode(mode_req) : (int)GEMM_FP32;
-    // bf16x3 pays the split VALU work per loaded element: with fewer than 128 output channels per block there are too
-    // few MFMAs per element to hide it (measured 58 vs 73 TFLOP/s on 64->64 k5) -- the exact kernel is the better
-    // fp32-accurate choice there.  (GEMM_BF16 must round everywhere to stay consistent with its definition.)
-    if (mode == GEMM_BF16X3 && bco < 128) mode = GEMM_FP32;
-    if (mode == GEMM_FP32 && halo_wgrad_geometry(cg)) {
-        const int ks = cg.KH, steps = cg.W / 4;
+    const WgradChoice ch = choose_wgrad(cg, S, mode_req, rowtab ? tab_rows : 0);
+    if (flags_out) *flags_out = ch.flags;
+    if (ch.halo) {
         const dim3 hgrid(cg.Cin / 16, cg.Cout / 64, S);
         const int hrps = cdiv(cg.B * cg.H, S);
-        size_t lds = ((size_t)(ks + 1) * (cg.W + ks - 1) * 16 + 2 * (size_t)cg.W * 80) * sizeof(float);
-        // two workgroups per CU when that fills the last round better (see the forward halo launch)
-        {
-            const long wgs = (long)hgrid.x * hgrid.y * hgrid.z;
-            auto fill = [&](long slots) { return (double)wgs / (double)(((wgs + slots - 1) / slots) * slots); };
-            if (wgs <= 1536 && fill(512) > fill(768) + 0.05) lds = std::max(lds, (size_t)55 * 1024);
-        }
-        if (flags_out) *flags_out = S > 1 ? GEMM_FLAG_SLABS : 0;
-#define CMOOP_HWG(KS_, ST_)                                                                                                  \
-        do {                                                                                                                 \
-            if (tm && tm->start && tm->ext) {                                                                                \
-                hipExtLaunchKernelGGL((halo_wgrad_kernel<KS_, ST_>), hgrid, dim3(256), lds, s, tm->start, tm->stop, 0, X, dY, P, g, hrps, Pbias, stride); \
-            } else {                                                                                                         \
-                if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->start, s));                                                \
-                hipLaunchKernelGGL((halo_wgrad_kernel<KS_, ST_>), hgrid, dim3(256), lds, s, X, dY, P, g, hrps, Pbias, stride); \
-                if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->stop, s));                                                 \
-            }                                                                                                                \
-        } while (0)
-        if (ks == 5) { if (steps == 10) CMOOP_HWG(5, 10); else CMOOP_HWG(5, 5); }
-        else         { if (steps == 10) CMOOP_HWG(3, 10); else CMOOP_HWG(3, 5); }
-#undef CMOOP_HWG
+        const size_t image = ((size_t)(ch.ks + 1) * (cg.W + ch.ks - 1) * 16 + 2 * (size_t)cg.W * 80) * sizeof(float);
+        const size_t lds = halo_lds_for_occupancy(image, (long)hgrid.x * hgrid.y * hgrid.z, -1);
+        auto run = [&](auto kernel) { launch_timed(kernel, hgrid, lds, s, tm, X, dY, P, g, hrps, Pbias, stride); };
+        if (ch.ks == 5) { if (ch.steps == 10) run(halo_wgrad_kernel<5, 10>); else run(halo_wgrad_kernel<5, 5>); }
+        else            { if (ch.steps == 10) run(halo_wgrad_kernel<3, 10>); else run(halo_wgrad_kernel<3, 5>); }
         CMOOP_HIP(hipGetLastError());
-        return GEMM_FP32_HALO * 10000000 + ks * 1000 + steps;
+        return ch.code();
     }
-    dim3 grid(cdiv(g.K, bki), cdiv(N, bco), S);
+    dim3 grid(cdiv(g.K, ch.bki), cdiv(g.Cout, ch.bco), S);
     int gkt = 0, gct = 0;
     // (Measured, not adopted, round 3: row slices on the FASTEST grid axis, so that with round-robin dispatch every K tile of a
     // slice runs on XCD s % 8 and co-resident K tiles share the slice's dY / input rows in one L2 -- PMC shows 36 % L2 hit
     // rate and 1.1 GB of fabric reads per launch on 64->64 k5 @101x40 with K tiles fastest.  95.2 vs 107.2 TFLOP/s there,
     // 89.1 vs 99.2 @51x20, no change on 128->128: like the XCD-grouped grid, concentrating a slice's lines on one L2 is slower
     // than spreading them over eight L2s and the Infinity Cache.)
-    if (wgrad_xcd_grouped() && mode == GEMM_FP32 && S >= 8) {
+    if (wgrad_xcd_grouped() && ch.mode == GEMM_FP32 && S >= 8) {
         gkt = (int)grid.x; gct = (int)grid.y;
         grid = dim3((unsigned)(cdiv(S, 8) * 8 * gkt * gct), 1, 1);
     }
-    // the row table must cover every row a chunk can touch (rows are consumed 32 at a time)
-    const uint2* rt = (rowtab && tab_rows >= cdiv(g.M, 32) * 32 && g.KH * g.KW <= 32) ? static_cast<const uint2*>(rowtab) : nullptr;
-    if (flags_out) *flags_out = ((rt && mode == GEMM_FP32 && (g.Cout & 3) == 0) ? GEMM_FLAG_ROWTAB : 0) | (S > 1 ? GEMM_FLAG_SLABS : 0);
-#define CMOOP_WGK(KERNEL)                                                                                       \
-    do {                                                                                                       \
-        if (tm && tm->start && tm->ext) {                                                                      \
-            hipExtLaunchKernelGGL(KERNEL, grid, dim3(256), 0, s, tm->start, tm->stop, 0, X, dY, P, g, rps, Pbias, stride); \
-        } else {                                                                                               \
-            if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->start, s));                                      \
-            hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, s, X, dY, P, g, rps, Pbias, stride);                 \
-            if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->stop, s));                                       \
-        }                                                                                                      \
-    } while (0)
-#define CMOOP_WGF(KERNEL)                                                                                       \
-    do {                                                                                                       \
-        if (tm && tm->start && tm->ext) {                                                                      \
-            hipExtLaunchKernelGGL(KERNEL, grid, dim3(256), 0, s, tm->start, tm->stop, 0, X, dY, P, g, rps, Pbias, stride, rt, tab_rows, gkt, gct, S); \
-        } else {                                                                                               \
-            if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->start, s));                                      \
-            hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, s, X, dY, P, g, rps, Pbias, stride, rt, tab_rows, gkt, gct, S);   \
-            if (tm && tm->start) CMOOP_HIP(hipEventRecord(tm->stop, s));                                       \
-        }                                                                                                      \
-    } while (0)
-    const bool use_mc64 = wgrad_mc64(rt != nullptr && (N & 3) == 0, mode, bco);     // (tab_rows covers whole 256-row tiles: rowtab_rows)
-    rps = use_mc64 ? cdiv(rps, 64) * 64 : cdiv(rps, 32) * 32;      // slices are whole chunks of the kernel's chunk depth
+    const uint2* rt = ch.use_tab ? static_cast<const uint2*>(rowtab) : nullptr;
+    const int rps = cdiv(cdiv(g.M, S), ch.mc) * ch.mc;      // slices are whole chunks of the kernel's chunk depth
+    auto run_bf16 = [&](auto kernel) { launch_timed(kernel, grid, 0, s, tm, X, dY, P, g, rps, Pbias, stride); };
+    auto run_fp32 = [&](auto kernel) { launch_timed(kernel, grid, 0, s, tm, X, dY, P, g, rps, Pbias, stride, rt, tab_rows, gkt, gct, S); };
 #define CMOOP_WG2(BCO_, BKI_)                                                          \
     do {                                                                               \
-        if (mode == GEMM_BF16X3) CMOOP_WGK((igemm_wgrad_bf16_kernel<BCO_, BKI_, 3>));  \
-        else if (mode == GEMM_BF16) CMOOP_WGK((igemm_wgrad_bf16_kernel<BCO_, BKI_, 1>)); \
-        else if (use_mc64 && BCO_ <= 64) CMOOP_WGF((igemm_wgrad_kernel<(BCO_ <= 64 ? BCO_ : 64), BKI_, 64>)); \
-        else CMOOP_WGF((igemm_wgrad_kernel<BCO_, BKI_>));                              \
+        if (ch.mode == GEMM_BF16X3) run_bf16(igemm_wgrad_bf16_kernel<BCO_, BKI_, 3>);  \
+        else if (ch.mode == GEMM_BF16) run_bf16(igemm_wgrad_bf16_kernel<BCO_, BKI_, 1>); \
+        else if (ch.mc == 64 && BCO_ <= 64) run_fp32(igemm_wgrad_kernel<(BCO_ <= 64 ? BCO_ : 64), BKI_, 64>); \
+        else run_fp32(igemm_wgrad_kernel<BCO_, BKI_>);                                 \
     } while (0)
 #define CMOOP_WG(BCO_)                    \
     do {                                  \
-        if (bki == 128) CMOOP_WG2(BCO_, 128); \
+        if (ch.bki == 128) CMOOP_WG2(BCO_, 128); \
         else CMOOP_WG2(BCO_, 64);         \
     } while (0)
-    if (bco == 16) CMOOP_WG(16);
-    else if (bco == 32) CMOOP_WG(32);
-    else if (bco == 64) CMOOP_WG(64);
+    if (ch.bco == 16) CMOOP_WG(16);
+    else if (ch.bco == 32) CMOOP_WG(32);
+    else if (ch.bco == 64) CMOOP_WG(64);
     else CMOOP_WG(128);
 #undef CMOOP_WG
 #undef CMOOP_WG2
-#undef CMOOP_WGF
-#undef CMOOP_WGK
     CMOOP_HIP(hipGetLastError());
-    return mode * 10000000 + (use_mc64 ? 1000000 : 0) + bco * 1000 + bki;
+    return ch.code();
 }
 
 // out[i] = sum_s P[s][i], fixed summation order.  Vector form: each thread owns one float4 column group,

@@ -94,8 +94,10 @@ int wgrad_slices(const ConvGeom& g);
 // slab_stride: floats between consecutive slices of P and of Pbias (0 = N*K, bias slabs packed [S][N]);
 // the trainer lays slices out as [S][N*K + N] so one reduction yields kernel and bias gradients.
 // rowtab (optional, fp32 kernel): the layer's row table (launch_build_rowtab, tab_rows = rowtab_rows(geometry it was
-// built for) >= this launch's rows rounded up to 32) -- switches the gather to buffer loads without per-element
-// divisions / bounds arithmetic.  A table built for the full batch serves every smaller batch of the same layer.
+// built for)) -- switches the gather to buffer loads without per-element divisions / bounds arithmetic.  It is used only
+// when tab_rows covers this launch's rows rounded up to the kernel's chunk depth: 64 rows for the single-image kernel of the
+// <= 64-channel tiles, which a table covering only the 32-row rounding demotes to the 32-row kernel; 32 rows otherwise.
+// A table built for the full batch serves every smaller batch of the same layer.
 int launch_igemm_wgrad(const float* X, const float* dY, float* P, const ConvGeom& g, int S, hipStream_t s,
                        const GemmTiming* tm = nullptr, float* Pbias = nullptr, size_t slab_stride = 0,
                        int mode = GEMM_DEFAULT, const void* rowtab = nullptr, int tab_rows = 0, int* flags_out = nullptr);

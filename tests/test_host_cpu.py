@@ -485,3 +485,75 @@ def test_every_launch_a_net_plans_is_a_variant_of_the_geometry_sweep():
     # a batch the net was not planned for is refused, not planned
     with pytest.raises(_lib.CmoopError):
         _lib.net_launch_plan((16, 3, 1, 1, 1, 0), EvalConfig(batch=64, eval_batch=256).to_struct(), 101, 40, 65, 1)
+
+
+#: the layers whose weight gradient crosses the table-less / 32- / 64-row-chunk boundaries as the batch grows: (H, W, Cin, Cout, KS, stride)
+PLAN_BATCH_SWEEP_LAYERS = [(51, 20, 64, 64, 3, 1), (101, 40, 64, 64, 5, 1), (101, 40, 16, 16, 3, 1), (51, 20, 128, 128, 5, 1)]
+
+
+def _recorded_conv_cases():
+    """The conv cases of tests/golden/conv_launch_plans.json: every case of the three shape lists, then the four layers above
+    at every batch 1..64; first occurrence only."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _ds_shapes import DS_POINTWISE_CONVS
+    from _production_shapes import PRODUCTION_CONVS
+    from _sweep_shapes import SWEEP_CONVS
+    cases = list(SWEEP_CONVS) + list(PRODUCTION_CONVS) + list(DS_POINTWISE_CONVS)
+    cases += [(B,) + layer for layer in PLAN_BATCH_SWEEP_LAYERS for B in range(1, 65)]
+    return list(dict.fromkeys(tuple(c) for c in cases))
+
+
+def _conv_plan_record(case):
+    """[forward without statistics, forward with statistics, dgrad, wgrad, wgrad row slices] of one conv case."""
+    L, buf, out, rec = _lib.lib(), C.create_string_buffer(200), C.c_int32(), []
+    for op, stats in ((0, 0), (0, 1), (1, 0), (2, 0)):
+        _lib.check(L.cmoop_conv_launch_plan(op, *case, stats, buf, 200))
+        rec.append(buf.value.decode())
+    _lib.check(L.cmoop_wgrad_slices(*case, C.byref(out)))
+    return rec + [int(out.value)]
+
+
+def _net_plan_digests():
+    """{"T F variant gene": sha256 of the cmoop_net_launch_plan strings} over the domain that
+    test_every_launch_a_net_plans_is_a_variant_of_the_geometry_sweep walks: one train step at every batch of SWEEP_BWD_BATCHES,
+    then one inference pass at every batch of SWEEP_FWD_BATCHES, one line per plan.  (The strings themselves are some 60 MB.)"""
+    import hashlib
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import launch_variants as LV
+    from _sweep_shapes import SWEEP_BWD_BATCHES, SWEEP_FEATURE_SIZES, SWEEP_FWD_BATCHES
+    out = {}
+    for (T, F) in SWEEP_FEATURE_SIZES:
+        for variant in ("A", "B"):
+            cfg = EvalConfig(variant=variant, batch=64, eval_batch=256).to_struct()
+            for gene in LV.ALL_CONV_GENES:
+                h = hashlib.sha256()
+                for train, batches in ((1, SWEEP_BWD_BATCHES), (0, SWEEP_FWD_BATCHES)):
+                    for B in batches:
+                        h.update((";".join(_lib.net_launch_plan(gene, cfg, T, F, B, train)) + "\n").encode())
+                out[f"{T} {F} {variant} {' '.join(map(str, gene))}"] = h.hexdigest()
+    return out
+
+
+def test_launch_plans_reproduce_the_recorded_fixture(golden_dir):
+    """tests/golden/conv_launch_plans.json was recorded from the library BEFORE the weight-gradient launcher and its host-only
+    plan were given one shared choice (WgradChoice, gemm.hip), in the default environment.  Every launch plan must come out
+    string for string as recorded: cmoop_conv_launch_plan for forward (without / with the statistics epilogue), dgrad and
+    wgrad, and cmoop_wgrad_slices, for every case of SWEEP_CONVS, PRODUCTION_CONVS and DS_POINTWISE_CONVS and for the layers of
+    PLAN_BATCH_SWEEP_LAYERS at every batch 1..64; cmoop_net_launch_plan over the whole net-plan domain (as digests).  A change
+    that is MEANT to move a plan re-records the fixture and says so."""
+    import json
+    fx = json.load(open(os.path.join(golden_dir, "conv_launch_plans.json")))
+    cases = _recorded_conv_cases()
+    assert [tuple(r[:7]) for r in fx["convs"]] == cases, "the shape lists changed: re-record the fixture"
+    wrong = []
+    for r in fx["convs"]:
+        want = [fx["names"][i] for i in r[7:11]] + [r[11]]
+        got = _conv_plan_record(tuple(r[:7]))
+        if got != want:
+            wrong.append((tuple(r[:7]), want, got))
+    assert not wrong, f"{len(wrong)} conv cases plan differently than recorded, e.g. {wrong[:3]}"
+    nets = _net_plan_digests()
+    assert sorted(nets) == sorted(fx["nets"])
+    moved = sorted(k for k in nets if nets[k] != fx["nets"][k])
+    assert not moved, f"{len(moved)} nets plan differently than recorded, e.g. {moved[:3]}"
