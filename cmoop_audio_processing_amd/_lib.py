@@ -65,6 +65,11 @@ class Optim(C.Structure):
                 ("decay_mask", C.c_int32), ("n_boundaries", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class Ema(C.Structure):
+    """cmoop_ema (include/cmoop.h), 16 bytes."""
+    _fields_ = [("momentum", C.c_double), ("warmup", C.c_int32), ("reserved", C.c_int32)]
+
+
 #: cmoop_next_fn (include/cmoop.h): int32_t (*)(void* ctx)
 NEXT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
@@ -136,6 +141,21 @@ OPTIM_PROTOTYPES = {
     "cmoop_net_set_optim": [C.c_void_p, C.c_void_p],
     "cmoop_net_optim_stats": [C.c_void_p, C.c_void_p],
     "cmoop_eval_population_opt": [C.c_void_p] * 8 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 7,
+}
+
+
+#: prototypes of the weight-EMA entry points (include/cmoop.h); structs travel as void* (C.byref), None is NULL
+EMA_PROTOTYPES = {
+    "cmoop_ema_default": [C.c_void_p],
+    "cmoop_ema_check": [C.c_void_p],
+    "cmoop_ema_rates": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_ema_update": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64],
+    "cmoop_net_set_ema": [C.c_void_p, C.c_void_p],
+    "cmoop_net_get_ema": [C.c_void_p, C.c_void_p],
+    "cmoop_net_set_ema_params": [C.c_void_p, C.c_void_p],
+    "cmoop_net_use_ema": [C.c_void_p, C.c_int32],
+    "cmoop_net_finalize_ema": [C.c_void_p],
+    "cmoop_eval_population_avg": [C.c_void_p] * 9 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 7,
 }
 
 
@@ -233,7 +253,7 @@ def lib():
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
         for table in (STREAM_PROTOTYPES, AUGMENT_PROTOTYPES, PCEN_PROTOTYPES, ELEM_PROTOTYPES, LOSS_PROTOTYPES, DENSE_PROTOTYPES,
-                      DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES):
+                      DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         _lib = L

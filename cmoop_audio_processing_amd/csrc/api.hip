@@ -170,21 +170,31 @@ static OptimCfg to_optim(const cmoop_optim* o) {
     return c;
 }
 
+static_assert(sizeof(cmoop_ema) == 16, "cmoop_ema is part of the ABI");
+static EmaCfg to_ema(const cmoop_ema* e) {
+    CMOOP_REQUIRE(e != nullptr, "ema config is NULL");
+    EmaCfg c;
+    c.momentum = e->momentum; c.warmup = e->warmup; c.reserved = e->reserved;
+    return c;
+}
+
 // The converted training options of one population call: to_* and the matching *_check of every struct handed in, in the
-// order augment, loss, distill, optim (what a call with two bad structs reports first); owns what opt points into
+// order augment, loss, distill, optim, ema (what a call with two bad structs reports first); owns what opt points into
 namespace {
 struct AbiTrainOptions {
     AugmentCfg aug;
     LossCfg loss;
     DistillCfg distill;
     OptimCfg optim;
+    EmaCfg ema;
     TrainOptions opt;
-    AbiTrainOptions(const cmoop_augment* a, const cmoop_loss* l, const cmoop_distill* d, const cmoop_optim* o, const NetConfig& c,
-                    const Dataset& ds) {
+    AbiTrainOptions(const cmoop_augment* a, const cmoop_loss* l, const cmoop_distill* d, const cmoop_optim* o, const cmoop_ema* e,
+                    const NetConfig& c, const Dataset& ds) {
         if (a) { aug = to_augment(a); augment_check(aug, ds.T, ds.F); opt.aug = &aug; }
         if (l) { loss = to_loss(l); loss_check(loss, c.classes); opt.loss = &loss; }
         if (d) { distill = to_distill(d); distill_check(distill, c.classes, ds.n_train); opt.distill = &distill; }
         if (o) { optim = to_optim(o); optim_check(optim); opt.optim = &optim; }
+        if (e) { ema = to_ema(e); ema_check(ema); opt.ema = &ema; }
     }
     AbiTrainOptions(const AbiTrainOptions&) = delete;
 };
@@ -292,7 +302,7 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 
 // every population call; next == NULL: candidates are taken longest-first from a process-local counter; a NULL option: off
 static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss,
-                                const cmoop_distill* distill, const cmoop_optim* optim, const cmoop_dataset* ds,
+                                const cmoop_distill* distill, const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_dataset* ds,
                                 const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
                                 double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
     CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
@@ -300,7 +310,7 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* au
     CMOOP_REQUIRE(!next || evaluated, "NULL argument");
     NetConfig c = to_cfg(cfg);
     const Dataset d = to_dataset(ds);
-    const AbiTrainOptions options(aug, loss, distill, optim, c, d);
+    const AbiTrainOptions options(aug, loss, distill, optim, ema, c, d);
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
@@ -359,9 +369,52 @@ int cmoop_eval_population_opt(const cmoop_config* cfg, const cmoop_augment* aug,
                               const cmoop_optim* optim, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n,
                               cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
                               double* val_loss, double* seconds, int32_t* evaluated) {
+    return cmoop_eval_population_avg(cfg, aug, loss, distill, optim, nullptr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr,
+                                     epochs_run, val_loss, seconds, evaluated);
+}
+
+int cmoop_eval_population_avg(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                              const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_dataset* ds, const int32_t* genes,
+                              const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr,
+                              int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
     return guard([&] {
-        eval_population_abi(cfg, aug, loss, distill, optim, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run, val_loss,
-                            seconds, evaluated);
+        eval_population_abi(cfg, aug, loss, distill, optim, ema, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run,
+                            val_loss, seconds, evaluated);
+    });
+}
+
+// ---- weight EMA ------------------------------------------------------------------
+int cmoop_ema_default(cmoop_ema* ema) {
+    return guard([&] {
+        CMOOP_REQUIRE(ema != nullptr, "ema config is NULL");
+        std::memset(ema, 0, sizeof(*ema));
+    });
+}
+
+int cmoop_ema_check(const cmoop_ema* ema) {
+    return guard([&] { ema_check(to_ema(ema)); });
+}
+
+int cmoop_ema_rates(const cmoop_ema* ema, int64_t iteration, double* m, float* mf, float* omf) {
+    return guard([&] {
+        const EmaCfg c = to_ema(ema);
+        ema_check(c);
+        const EmaRates r = ema_rates(c, iteration);
+        if (m) *m = r.m;
+        if (mf) *mf = r.mf;
+        if (omf) *omf = r.omf;
+    });
+}
+
+int cmoop_ema_update(const cmoop_ema* ema, int64_t iteration, float* a_dev, const float* w_dev, const uint8_t* kinds_dev, int64_t n) {
+    return guard([&] {
+        CMOOP_REQUIRE(n >= 0 && (n == 0 || (a_dev && w_dev)), "ema_update: n >= 0 and both arenas");
+        const EmaCfg c = to_ema(ema);
+        ema_check(c);
+        const EmaRates r = ema_rates(c, iteration);
+        hipStream_t s = lib_stream();
+        launch_ema(a_dev, w_dev, kinds_dev, n, r.mf, r.omf, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
 
@@ -1026,6 +1079,32 @@ int cmoop_net_optim_stats(cmoop_net* h, double out[4]) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net && out, "optim_stats: NULL argument");
         h->net->optim_stats(out);
+    });
+}
+int cmoop_net_set_ema(cmoop_net* h, const cmoop_ema* ema) { return net_set_option(h, "set_ema", ema, to_ema, &Net::set_ema); }
+int cmoop_net_get_ema(cmoop_net* h, float* host) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "get_ema: NULL net");
+        h->net->get_average(host);
+    });
+}
+int cmoop_net_set_ema_params(cmoop_net* h, const float* host) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "set_ema_params: NULL net");
+        h->net->set_average(host);
+    });
+}
+int cmoop_net_use_ema(cmoop_net* h, int32_t on) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "use_ema: NULL net");
+        h->net->use_average(on != 0);
+    });
+}
+int cmoop_net_finalize_ema(cmoop_net* h) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "finalize_ema: NULL net");
+        h->net->finalize_average();
+        CMOOP_HIP(hipStreamSynchronize(h->net->stream()));
     });
 }
 int cmoop_net_train_step_distill_targets(cmoop_net* h, const float* x_rows, const float* t, const float* w, const int32_t* primary,

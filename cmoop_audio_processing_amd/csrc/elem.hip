@@ -2154,6 +2154,67 @@ void launch_adamw(float* w, const float* g, float* m, float* v, const uint8_t* k
     CMOOP_HIP(hipGetLastError());
 }
 
+// ---- weight EMA: an averaged copy of the parameter arena (kernels.h) -----------------------------------------------------------
+void ema_check(const EmaCfg& c) {
+    CMOOP_REQUIRE(std::isfinite(c.momentum) && c.momentum >= 0 && c.momentum < 1, "ema: momentum must be finite and in [0, 1)");
+    CMOOP_REQUIRE(c.warmup == 0 || c.warmup == 1, "ema: warmup must be 0 or 1");
+    CMOOP_REQUIRE(c.reserved == 0, "ema: reserved must be 0");
+}
+
+EmaRates ema_rates(const EmaCfg& c, int64_t iteration) {
+    CMOOP_REQUIRE(iteration >= 0, "ema rates: iteration must be >= 0");
+    double m = c.momentum;
+    if (c.warmup) m = std::min(m, (1.0 + (double)iteration) / (10.0 + (double)iteration));
+    EmaRates r;
+    r.m = m;
+    r.mf = (float)m;
+    r.omf = (float)(1.0 - m);
+    return r;
+}
+
+// one element of the average: two products and one add, each rounded separately, for adam_update's reason; a frozen
+// element (BatchNorm moving statistics) is a copy of the weight, so the average is a complete inference parameter set
+__device__ __forceinline__ float ema_element(float ai, float wi, unsigned kind, float mf, float omf) {
+#pragma clang fp contract(off)
+    if (kind == KIND_FROZEN) return wi;
+    const float keep = mf * ai;
+    const float take = omf * wi;
+    return keep + take;
+}
+
+// A launch of its own after the optimiser's: reads w (already updated), a and the kind bytes, writes a only.  Shaped as
+// adamw_kernel: grid-stride, 16-byte accesses (4 kind bytes per float4) when vec, the last n % 4 elements and an unaligned
+// arena one element at a time.  kinds null: every element is trainable
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ a, const float* __restrict__ w,
+                                                  const uint8_t* __restrict__ kinds, int64_t n, float mf, float omf,
+                                                  const StepState* __restrict__ st, const EmaPair* __restrict__ table, int vec) {
+    if (st) { const EmaPair p = table[st->iter]; mf = p.mf; omf = p.omf; }
+    const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const int64_t n4 = vec ? n / 4 : 0;
+    for (int64_t q = t0; q < n4; q += stride) {
+        f32x4 aq = reinterpret_cast<f32x4*>(a)[q];
+        const f32x4 wq = reinterpret_cast<const f32x4*>(w)[q];
+        const uint32_t kq = kinds ? reinterpret_cast<const uint32_t*>(kinds)[q] : 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) aq[j] = ema_element(aq[j], wq[j], (kq >> (8 * j)) & 0xffu, mf, omf);
+        reinterpret_cast<f32x4*>(a)[q] = aq;
+    }
+    for (int64_t i = 4 * n4 + t0; i < n; i += stride) a[i] = ema_element(a[i], w[i], kinds ? kinds[i] : 0u, mf, omf);
+}
+
+void launch_ema(float* a, const float* w, const uint8_t* kinds, int64_t n, float mf, float omf, hipStream_t s, const StepState* st,
+                const EmaPair* table) {
+    if (n == 0) return;
+    CMOOP_REQUIRE(a && w && a != w, "ema: the average and the weights are two arenas");
+    CMOOP_REQUIRE(!st || table, "ema: a device step state needs the rate table");
+    auto al = [](const void* p, size_t k) { return reinterpret_cast<uintptr_t>(p) % k == 0; };
+    const int vec = al(a, 16) && al(w, 16) && al(kinds, 4);
+    const int64_t items = vec ? std::max<int64_t>(n / 4, 1) : n;
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(items, 256), ADAMW_MAX_BLOCKS);
+    hipLaunchKernelGGL(ema_kernel, dim3(grid), dim3(256), 0, s, a, w, kinds, n, mf, omf, st, table, vec);
+    CMOOP_HIP(hipGetLastError());
+}
+
 // Epoch shuffle on the device (Keras fit(shuffle=True), nsga_penalty.py:383; seeded here): the permutation that sorts
 // the keys (fmix32(prefix ^ i) << 32 | i), i.e. exactly what the host twin (net.hip epoch_permutation, oracle/rng.py)
 // produces with std::sort -- computed as a rank sort: out[#{j : key_j < key_i}] = i.  O(n^2) compares on LDS tiles

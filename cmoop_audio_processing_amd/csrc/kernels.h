@@ -476,6 +476,26 @@ struct AdamwArgs {
 void launch_adamw(float* w, const float* g, float* m, float* v, const uint8_t* kinds, int64_t n, const OptimRecord* rec,
                   const AdamwArgs& a, hipStream_t s, const StepState* st = nullptr, const float* alpha_table = nullptr,
                   const float* lr_table = nullptr);
+// ---------------------------------------------------------------------------
+// Weight EMA (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_ema): an average arena a in the parameter
+// arena's layout, advanced by ONE launch after the optimiser's launch(es) of a step.  The optimiser kernels are untouched.
+// ---------------------------------------------------------------------------
+struct EmaCfg {
+    double momentum = 0;           // m, 0 <= m < 1; 0 = off
+    int warmup = 0, reserved = 0;  // warmup 1: m(i) = min(m, (1 + i) / (10 + i))
+};
+// host-only: throws with a message naming the offending field
+void ema_check(const EmaCfg& c);
+inline bool ema_enabled(const EmaCfg& c) { return c.momentum > 0; }
+// host-only, THE place of the rates: m(i) in double, and the two fp32 values the kernel consumes -- (float)m(i) and
+// (float)(1.0 - m(i)), the subtraction in double, each rounded once
+struct EmaRates { double m; float mf, omf; };
+EmaRates ema_rates(const EmaCfg& c, int64_t iteration);
+struct EmaPair { float mf, omf; };   // one entry of the device-state steps' rate table
+// a[i] = (mf a[i]) + (omf w[i]) for trainable elements (no fused multiply-add), a[i] = w[i] for KIND_FROZEN ones; kinds
+// null: all trainable.  st != null: (mf, omf) = table[st->iter].  Writes a only
+void launch_ema(float* a, const float* w, const uint8_t* kinds, int64_t n, float mf, float omf, hipStream_t s,
+                const StepState* st = nullptr, const EmaPair* table = nullptr);
 
 // device twin of epoch_permutation (net.h): out[rank of key_i] = i; n <= EPOCH_PERMUTATION_DEVICE_MAX (O(n^2) rank sort)
 constexpr int64_t EPOCH_PERMUTATION_DEVICE_MAX = 262144;

@@ -208,12 +208,13 @@ struct NetPlan {
 NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F);
 
 // The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
-// set_distill / set_optim say what each does).  The pointees stay the caller's for the length of the call
+// set_distill / set_optim / set_ema say what each does).  The pointees stay the caller's for the length of the call
 struct TrainOptions {
     const AugmentCfg* aug = nullptr;
     const LossCfg* loss = nullptr;
     const DistillCfg* distill = nullptr;
     const OptimCfg* optim = nullptr;
+    const EmaCfg* ema = nullptr;
 };
 
 class Net : public GemmHook {
@@ -229,11 +230,13 @@ class Net : public GemmHook {
     void get_params(float* host);
     void set_params(const float* host);
     void get_grads(float* host);
-    void snapshot_params();   // device copy (restore_best_weights)
-    void restore_snapshot();
+    void snapshot_params();   // device copy (restore_best_weights) of the arena inference currently reads (use_average)
+    void restore_snapshot();  // into the parameter arena
     // full training state: parameters (BatchNorm moving statistics included), Adam m / v, optimizer.iterations and the
     // global step that keys the dropout masks -- what a checker needs to re-synchronise with this net at an epoch boundary
     void get_state(float* params, float* m, float* v, long long* iterations, long long* steps);
+    // the average arena of set_ema is NOT part of this state: set_state leaves it untouched, and a re-synchronising checker
+    // calls set_average as well
     void set_state(const float* params, const float* m, const float* v, long long iterations, long long steps);
     // Train-time augmentation (kernels.h) of every following train step, both step paths; null or a disabled config: off,
     // and a step's launches and allocations are those of a net that never had one.  Enabled: each step first writes its
@@ -264,7 +267,23 @@ class Net : public GemmHook {
     // path (grad_finish -> clip_scale -> adamw); the kind arena, the partial buffer (sized once for the worst workgroup
     // count) and the device record are allocated on first use, and the step is no longer captured as a graph
     void set_optim(const OptimCfg* optim);
-    // the enabled ones of o through the four setters above, in that order: augment, loss, distill, optim.  THE place of "a
+    // Weight EMA (kernels.h) of every following train step, every step path and both optimiser paths; null or a disabled
+    // config: off, and a step's launches and bits are those of a net that never had one (an average arena that already
+    // exists is kept but no longer advanced).  Enabled: the domain is checked; on first use the average arena, the kind
+    // arena and (when a fit is under way) the rate table are allocated and the average becomes a bit copy of the parameter
+    // arena -- a later call with other values keeps the average.  Each step then launches launch_ema after the optimiser's
+    // launch(es): the training trajectory is never touched.  The step is no longer captured as a graph
+    void set_ema(const EmaCfg* ema);
+    bool has_average() const { return ema_ != nullptr; }
+    bool average_on() const { return ema_on_; }            // train steps advance the average
+    // inference switch: while on, evaluate / predict / predict_logits / predict_stream (and snapshot_params) read the average
+    // arena in place of the parameters -- a host-side pointer swap, no copy.  Must be off again before the next train step
+    // (a step refuses otherwise); get_params / set_params / get_state / set_state always mean the raw parameters
+    void use_average(bool on);
+    void get_average(float* host);
+    void set_average(const float* host);
+    void finalize_average();   // w := a (Keras' finalize_variable_values); Adam's moments, the counters and a stay
+    // the enabled ones of o through the five setters above, in that order: augment, loss, distill, optim, ema.  THE place of "a
     // disabled config is no config": null or disabled is not applied at all, and the net stays one that never had it
     void set_options(const TrainOptions& o);
     // the last step's {sum of squares, norm, scale, launch path (0 fused, 1 finish + update)}; path 0 computes no norm: 0, 0, 1
@@ -325,7 +344,8 @@ class Net : public GemmHook {
     void targets_step(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
                       const DistillParams* kd, int B);
     void optimiser_step(int B, const StepState* st);   // the tail of a step: weight-gradient slabs summed + Adam (+ state advance)
-    void upload_rate_tables();                          // alpha_tab_ (and, on the finish + update path, lr_tab_) from optim_rates
+    void upload_rate_tables();                          // alpha_tab_ (and, on the finish + update path, lr_tab_) from optim_rates; ema_tab_ from ema_rates
+    void ensure_kinds();                                // kinds_dev_, uploaded once (set_optim's finish path and set_ema share it)
     void drop_graph();                                  // the captured step has the old launch sequence or counters
     void upload_step_state();                           // enqueues the device StepState at (0, step_, iterations_); no-op without one
     void ensure_target_buffers();                       // t / w / primary, allocated by the first enabled set_loss or set_distill
@@ -342,6 +362,11 @@ class Net : public GemmHook {
     std::vector<void*> allocs_;
     int64_t n_params_ = 0;
     float *params_ = nullptr, *grads_ = nullptr, *adam_m_ = nullptr, *adam_v_ = nullptr, *snap_ = nullptr;
+    float* weights_ = nullptr;          // the parameter arena; params_ (what forward reads) is this, or ema_ under use_average
+    float* ema_ = nullptr;              // the average arena, allocated by the first enabled set_ema
+    EmaCfg ema_cfg_;                    // set_ema; the default is off
+    bool ema_on_ = false;               // train steps advance ema_ after the optimiser launch(es)
+    EmaPair* ema_tab_ = nullptr;        // (mf, omf) per iteration, alpha_tab_n_ entries, next to alpha_tab_
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;
     bool aug_on_ = false;               // train steps read aug_buf_ (set_augment)
     AugmentParams aug_;

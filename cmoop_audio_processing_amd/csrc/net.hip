@@ -397,7 +397,7 @@ void Net::build_plan() {
             acts_[op.in2].grad = acts_[op.out].grad;
         }
     // ---- parameters / optimiser state ---------------------------------------
-    params_ = dalloc(n_params_); grads_ = dalloc(n_params_);
+    params_ = weights_ = dalloc(n_params_); grads_ = dalloc(n_params_);
     adam_m_ = dalloc(n_params_); adam_v_ = dalloc(n_params_);
     CMOOP_HIP(hipMemsetAsync(grads_, 0, n_params_ * 4, stream_));
     CMOOP_HIP(hipMemsetAsync(adam_m_, 0, n_params_ * 4, stream_));
@@ -519,11 +519,11 @@ ConvBuffers Net::buffers_of(const Op& op) const {
 }
 
 void Net::get_params(float* host) {
-    CMOOP_HIP(hipMemcpyAsync(host, params_, n_params_ * 4, hipMemcpyDeviceToHost, stream_));
+    CMOOP_HIP(hipMemcpyAsync(host, weights_, n_params_ * 4, hipMemcpyDeviceToHost, stream_));
     CMOOP_HIP(hipStreamSynchronize(stream_));
 }
 void Net::set_params(const float* host) {
-    CMOOP_HIP(hipMemcpyAsync(params_, host, n_params_ * 4, hipMemcpyHostToDevice, stream_));
+    CMOOP_HIP(hipMemcpyAsync(weights_, host, n_params_ * 4, hipMemcpyHostToDevice, stream_));
     CMOOP_HIP(hipStreamSynchronize(stream_));
 }
 void Net::get_grads(float* host) {
@@ -535,7 +535,7 @@ void Net::snapshot_params() {
     CMOOP_HIP(hipMemcpyAsync(snap_, params_, n_params_ * 4, hipMemcpyDeviceToDevice, stream_));
 }
 void Net::restore_snapshot() {
-    if (snap_) CMOOP_HIP(hipMemcpyAsync(params_, snap_, n_params_ * 4, hipMemcpyDeviceToDevice, stream_));
+    if (snap_) CMOOP_HIP(hipMemcpyAsync(weights_, snap_, n_params_ * 4, hipMemcpyDeviceToDevice, stream_));
 }
 
 const GemmTiming* Net::begin(int cls, double flops) {
@@ -919,6 +919,7 @@ void Net::backward(const float* X, const BatchRows& rows, int B) {
 // one optimiser step: gather -> forward -> loss -> backward -> Adam.  rows.st == null: explicit host arguments (session API);
 // rows.st != null: batch position / dropout counter / Adam iteration come from the device state, which the step advances
 void Net::step_body(const float* X, const int32_t* y, const BatchRows& rows, int B) {
+    CMOOP_REQUIRE(params_ == weights_, "train step while inference reads the average: use_average(false) first");
     // before anything is enqueued: a teacher table of another length than the split the step gathers from is refused whole
     CMOOP_REQUIRE(!distill_on_ || gather_rows_ == 0 || gather_rows_ == kd_rows_, "distill: the teacher table has " +
                   std::to_string(kd_rows_) + " rows, the training split " + std::to_string(gather_rows_));
@@ -994,6 +995,10 @@ void Net::optimiser_step(int B, const StepState* st) {
                              (float)cfg_.adam_eps, stream_, st, alpha_tab_);
     }
     optim_last_path_ = optim_finish_ ? 1 : 0;
+    if (ema_on_) {   // the average follows the updated weights, whichever of the three paths moved them; it reads st->iter before the advance
+        const EmaRates er = ema_rates(ema_cfg_, iterations_);
+        launch_ema(ema_, weights_, kinds_dev_, n_params_, er.mf, er.omf, stream_, st, ema_tab_);
+    }
     if (st) launch_step_advance(st_dev_, B, stream_);
 }
 
@@ -1014,6 +1019,7 @@ void Net::train_step(const float* X, const int32_t* y, const int32_t* idx, int64
 
 void Net::targets_step(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
                        const DistillParams* kd, int B) {
+    CMOOP_REQUIRE(params_ == weights_, "train step while inference reads the average: use_average(false) first");
     ProfilingScope prof(profiling_now_, cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0);
     batch_in_ = nullptr;
     const BatchRows rows;      // x_rows holds exactly the B rows of this step: no resident tensor to clamp into
@@ -1050,6 +1056,7 @@ void Net::begin_fit(int64_t total_steps) {
     if (total_steps < 1 || total_steps > (1ll << 24)) { graph_ok_ = false; st_dev_ = nullptr; return; }   // explicit-argument steps beyond 16 M iterations
     alpha_tab_ = dalloc(total_steps);
     lr_tab_ = nullptr;
+    ema_tab_ = nullptr;
     alpha_tab_n_ = total_steps;
     if (!st_dev_) st_dev_ = reinterpret_cast<StepState*>(dalloc(8));
     upload_rate_tables();
@@ -1059,7 +1066,7 @@ void Net::begin_fit(int64_t total_steps) {
     // steps/s replayed vs 2 625 launched eagerly (its stream is kept busy either way: ~50 kernels of ~8 us per step,
     // the host launches faster than that), and the pop-40 bench is 1.5 % slower replayed (2 089 vs 2 121 evals/h).
     static const bool use_graph = [] { const char* v = std::getenv("CMOOP_GRAPH"); return v && v[0] == '1'; }();
-    if (!use_graph || optim_finish_) graph_ok_ = false;
+    if (!use_graph || optim_finish_ || ema_on_) graph_ok_ = false;
 }
 
 // the per-iteration rates of the device-state steps, from the one host function the explicit-argument steps use
@@ -1074,6 +1081,15 @@ void Net::upload_rate_tables() {
     }
     CMOOP_HIP(hipMemcpyAsync(alpha_tab_, alpha.data(), alpha_tab_n_ * 4, hipMemcpyHostToDevice, stream_));
     if (optim_finish_) CMOOP_HIP(hipMemcpyAsync(lr_tab_, lr.data(), alpha_tab_n_ * 4, hipMemcpyHostToDevice, stream_));
+    std::vector<EmaPair> ema(ema_on_ ? alpha_tab_n_ : 0);
+    if (ema_on_) {   // the same iterations, indexed by the same st->iter
+        if (!ema_tab_) ema_tab_ = reinterpret_cast<EmaPair*>(dalloc(2 * alpha_tab_n_));
+        for (int64_t i = 0; i < alpha_tab_n_; ++i) {
+            const EmaRates r = ema_rates(ema_cfg_, i);
+            ema[i] = EmaPair{r.mf, r.omf};
+        }
+        CMOOP_HIP(hipMemcpyAsync(ema_tab_, ema.data(), alpha_tab_n_ * sizeof(EmaPair), hipMemcpyHostToDevice, stream_));
+    }
     CMOOP_HIP(hipStreamSynchronize(stream_));     // the tables are locals
 }
 
@@ -1099,30 +1115,81 @@ void Net::set_options(const TrainOptions& o) {
     if (o.loss && loss_enabled(*o.loss)) set_loss(o.loss);
     if (o.distill && distill_enabled(*o.distill)) set_distill(o.distill);
     if (o.optim && optim_enabled(*o.optim)) set_optim(o.optim);
+    if (o.ema && ema_enabled(*o.ema)) set_ema(o.ema);
+}
+
+void Net::ensure_kinds() {
+    if (kinds_dev_) return;
+    NetPlan plan;
+    plan.ops = ops_;
+    plan.n_params = n_params_;
+    const std::vector<uint8_t> kinds = plan.param_kinds();
+    kinds_dev_ = reinterpret_cast<uint8_t*>(dalloc((size_t)(n_params_ + 3) / 4));
+    CMOOP_HIP(hipMemcpyAsync(kinds_dev_, kinds.data(), (size_t)n_params_, hipMemcpyHostToDevice, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // kinds is a local
 }
 
 void Net::set_optim(const OptimCfg* optim) {
     if (optim) optim_check(*optim);
     const OptimCfg c = optim && optim_enabled(*optim) ? *optim : OptimCfg();
     const bool finish = optim_finish_path(c);
-    if (finish && !kinds_dev_) {
-        NetPlan plan;
-        plan.ops = ops_;
-        plan.n_params = n_params_;
-        const std::vector<uint8_t> kinds = plan.param_kinds();
-        kinds_dev_ = reinterpret_cast<uint8_t*>(dalloc((size_t)(n_params_ + 3) / 4));
+    if (finish) ensure_kinds();
+    if (finish && !optim_rec_) {
         // a slab segment takes a workgroup per 64 elements at the most, a plain one per 1024, each of the segments rounds up
         optim_partials_cap_ = n_params_ / 64 + ADAM_MAX_SEGS + 1;
         optim_partials_ = dalloc((size_t)optim_partials_cap_);
         optim_rec_ = reinterpret_cast<OptimRecord*>(dalloc(sizeof(OptimRecord) / 4));
-        CMOOP_HIP(hipMemcpyAsync(kinds_dev_, kinds.data(), (size_t)n_params_, hipMemcpyHostToDevice, stream_));
     }
-    CMOOP_HIP(hipStreamSynchronize(stream_));     // kinds is a local; nothing of the old options is still running
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old options is still running
     optim_ = c;
     optim_finish_ = finish;
     upload_rate_tables();                         // takes effect from the next step
     if (finish) graph_ok_ = false;                // nothing is promised under CMOOP_GRAPH=1
     drop_graph();
+}
+
+void Net::set_ema(const EmaCfg* ema) {
+    if (ema) ema_check(*ema);
+    const bool on = ema != nullptr && ema_enabled(*ema);
+    if (on) {
+        ensure_kinds();
+        if (!ema_) {   // first use: the average starts as the parameter arena of this moment, moving statistics included
+            ema_ = dalloc(n_params_);
+            CMOOP_HIP(hipMemcpyAsync(ema_, weights_, n_params_ * 4, hipMemcpyDeviceToDevice, stream_));
+        }
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+    ema_cfg_ = on ? *ema : EmaCfg();
+    ema_on_ = on;
+    if (on) {
+        upload_rate_tables();                     // a fit under way: its table, from the next step
+        graph_ok_ = false;                        // nothing is promised under CMOOP_GRAPH=1
+    }
+    drop_graph();
+}
+
+void Net::use_average(bool on) {
+    CMOOP_REQUIRE(ema_ != nullptr, "use_average: the net has no average (set_ema with momentum > 0 first)");
+    params_ = on ? ema_ : weights_;
+}
+
+void Net::get_average(float* host) {
+    CMOOP_REQUIRE(ema_ != nullptr, "get_average: the net has no average (set_ema with momentum > 0 first)");
+    CMOOP_REQUIRE(host != nullptr, "get_average: NULL buffer");
+    CMOOP_HIP(hipMemcpyAsync(host, ema_, n_params_ * 4, hipMemcpyDeviceToHost, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+}
+
+void Net::set_average(const float* host) {
+    CMOOP_REQUIRE(ema_ != nullptr, "set_average: the net has no average (set_ema with momentum > 0 first)");
+    CMOOP_REQUIRE(host != nullptr, "set_average: NULL buffer");
+    CMOOP_HIP(hipMemcpyAsync(ema_, host, n_params_ * 4, hipMemcpyHostToDevice, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+}
+
+void Net::finalize_average() {
+    CMOOP_REQUIRE(ema_ != nullptr, "finalize_average: the net has no average (set_ema with momentum > 0 first)");
+    CMOOP_HIP(hipMemcpyAsync(weights_, ema_, n_params_ * 4, hipMemcpyDeviceToDevice, stream_));
 }
 
 void Net::optim_stats(double out[4]) {
@@ -1183,7 +1250,7 @@ void Net::train_step_stateful(const float* X, const int32_t* y, const int32_t* i
 }
 
 void Net::get_state(float* params, float* m, float* v, long long* iterations, long long* steps) {
-    if (params) CMOOP_HIP(hipMemcpyAsync(params, params_, n_params_ * 4, hipMemcpyDeviceToHost, stream_));
+    if (params) CMOOP_HIP(hipMemcpyAsync(params, weights_, n_params_ * 4, hipMemcpyDeviceToHost, stream_));
     if (m) CMOOP_HIP(hipMemcpyAsync(m, adam_m_, n_params_ * 4, hipMemcpyDeviceToHost, stream_));
     if (v) CMOOP_HIP(hipMemcpyAsync(v, adam_v_, n_params_ * 4, hipMemcpyDeviceToHost, stream_));
     CMOOP_HIP(hipStreamSynchronize(stream_));
@@ -1193,7 +1260,7 @@ void Net::get_state(float* params, float* m, float* v, long long* iterations, lo
 
 void Net::set_state(const float* params, const float* m, const float* v, long long iterations, long long steps) {
     CMOOP_REQUIRE(iterations >= 0 && steps >= 0 && iterations < (1ll << 31) && steps < (1ll << 31), "set_state: counters out of range");
-    if (params) CMOOP_HIP(hipMemcpyAsync(params_, params, n_params_ * 4, hipMemcpyHostToDevice, stream_));
+    if (params) CMOOP_HIP(hipMemcpyAsync(weights_, params, n_params_ * 4, hipMemcpyHostToDevice, stream_));
     if (m) CMOOP_HIP(hipMemcpyAsync(adam_m_, m, n_params_ * 4, hipMemcpyHostToDevice, stream_));
     if (v) CMOOP_HIP(hipMemcpyAsync(adam_v_, v, n_params_ * 4, hipMemcpyHostToDevice, stream_));
     iterations_ = iterations;
@@ -1438,7 +1505,15 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
     net.set_gather_rows(ds.n_train);
     // (a session net that has already trained continues from its own optimizer.iterations)
     net.begin_fit(net.iterations_done() + (int64_t)cfg.epochs * ((ds.n_train + cfg.batch - 1) / cfg.batch));
+    // Weight EMA on: every validation pass (and so the monitored loss, the history, the snapshot and the read-outs) is that
+    // of the average arena; training between them continues on the raw weights.  Off: nothing below changes
+    const bool avg = net.average_on();
+    struct AverageScope {   // inference reads the parameters again however the fit ends, a throw included
+        Net& net; bool avg;
+        ~AverageScope() { if (avg) net.use_average(false); }
+    } average_scope{net, avg};
     for (int epoch = 0; epoch < cfg.epochs; ++epoch) {
+        if (avg) net.use_average(false);
         if (cfg.shuffle && ds.n_train <= EPOCH_PERMUTATION_DEVICE_MAX) {
             launch_epoch_permutation(seed, (uint32_t)epoch, ds.n_train, d_idx, stream);   // no host sort, no H2D
         } else if (cfg.shuffle || epoch == 0) {
@@ -1452,6 +1527,7 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
         for (int64_t s = 0; s < ds.n_train; s += cfg.batch)
             net.train_step_stateful(ds.x_train, ds.y_train, d_idx, (int)std::min<int64_t>(cfg.batch, ds.n_train - s));
         double ls; long long corr;
+        if (avg) net.use_average(true);   // until the next epoch's first step: snapshot_params below copies what this pass read
         net.evaluate(ds.x_val, ds.y_val, ds.n_val, &ls, &corr, d_preds);   // keeps this epoch's predictions
         net.drain_profile();
         last_val_loss = ls / (double)ds.n_val;
@@ -1473,9 +1549,14 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
         if (wait >= cfg.patience && epoch > 0) break;
     }
     if (hist) hist->best_epoch = best_epoch;
+    if (avg) net.use_average(false);
     if (cfg.early_stop && cfg.restore_best && have_best && best_epoch != res.epochs_run - 1) {
         net.restore_snapshot();      // weights of an earlier epoch: the last pass's predictions no longer apply
         preds_are_final = false;
+    } else if (avg) {
+        // the parameter arena becomes the weights that were scored (Keras' finalize_variable_values): the average of the last
+        // epoch, which the last validation pass read -- so that pass still IS the read-out pass below
+        net.finalize_average();
     }
     // readouts: model.evaluate / model.predict + argmax + confusion matrix (one inference pass yields both).  When
     // the net still holds the weights of its last epoch, that epoch's validation pass IS this pass (inference is

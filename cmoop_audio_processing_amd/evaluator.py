@@ -37,6 +37,7 @@ from .augment import AugmentConfig
 from .loss import LossConfig
 from .distill import DistillConfig, check_teacher_table, require_teacher
 from .optim import OptimConfig
+from .ema import EmaConfig
 
 FPR_CODES = {"v1": 0, "v1_quirk": 1, "v3": 2}
 ACC_CODES = {"last": 0, "evaluate": 1}
@@ -93,6 +94,10 @@ class EvalConfig:
     # optimiser options of every candidate's fit (optim.py): learning-rate schedule, decoupled weight decay, gradient
     # clipping.  None or a config with everything off = off, every number as without the field (cmoop_net_set_optim)
     optim: Optional[OptimConfig] = None
+    # weight EMA of every candidate's fit (ema.py): validation, early stopping and the read-outs take the averaged weights.
+    # None or momentum 0 = off, every number as without the field (cmoop_net_set_ema).  It travels beside option_structs'
+    # four-tuple, as ema_struct()
+    ema: Optional[EmaConfig] = None
 
     @staticmethod
     def preset(script: str, **over) -> "EvalConfig":
@@ -157,6 +162,12 @@ class EvalConfig:
         if self.optim is None or not self.optim.enabled:
             return None
         return self.optim.check()._struct()
+
+    def ema_struct(self) -> Optional["_lib.Ema"]:
+        """The enabled weight EMA as a ``cmoop_ema``, checked; None when it is off."""
+        if self.ema is None or not self.ema.enabled:
+            return None
+        return self.ema.check()._struct()
 
     def option_structs(self, T: int, F: int, teacher_logits, n_train: int):
         """(augment, loss, distill, optim) of a fit on [T, F] patches against ``teacher_logits``: the four ``*_struct``
@@ -418,11 +429,12 @@ class PopulationEvaluator:
         return d
 
     def _population_call(self, genes, sd, n, cfg, next_cb, acc, size, fpr, ep, secs, done) -> None:
-        """THE population call: ``cmoop_eval_population_opt`` with ``config.option_structs`` by reference, None (NULL) for
-        whatever is off; next_cb None: the library's own longest-first counter, and ``done`` is then None too."""
+        """THE population call: ``cmoop_eval_population_avg`` with ``config.option_structs`` and ``config.ema_struct`` by
+        reference, None (NULL) for whatever is off; next_cb None: the library's own longest-first counter, and ``done`` is
+        then None too."""
         ds = self._dataset()
-        opts = self.config.option_structs(self.T, self.F, self.teacher_logits, len(self.X_train))
-        _lib.check(_lib.lib().cmoop_eval_population_opt(
+        opts = self.config.option_structs(self.T, self.F, self.teacher_logits, len(self.X_train)) + (self.config.ema_struct(),)
+        _lib.check(_lib.lib().cmoop_eval_population_avg(
             C.byref(cfg), *(C.byref(o) if o is not None else None for o in opts), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
             C.c_int32(n), C.cast(next_cb, C.c_void_p) if next_cb is not None else None, None, _lib.ptr(acc), _lib.ptr(size),
             _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
@@ -529,7 +541,7 @@ class PopulationEvaluator:
         """Train ONE candidate on the resident splits and keep its weights -> ``deploy.TrainedModel``.
 
         The body of the population call's per-candidate work (``NetSession.fit``) on the given seed and under the same
-        ``config.augment`` / ``config.loss`` / ``config.optim`` / ``config.distill`` (against the teacher of ``set_teacher``): with
+        ``config.augment`` / ``config.loss`` / ``config.optim`` / ``config.ema`` / ``config.distill`` (against the teacher of ``set_teacher``): with
         ``seed = last_seeds[i]`` it reproduces candidate i of the last generation, accuracy and FPR included.
         ``hparams`` is the reference's dict or a gene tuple; ``frontend`` / ``mean`` / ``scale`` (the front end and the
         StandardScaler the features were made with) ride along for ``StreamScorer``."""

@@ -27,8 +27,9 @@ class NetSession:
         _lib.check(_lib.lib().cmoop_net_total_params(self._h, C.byref(n)))
         self.n_params = int(n.value)
         self.T, self.F = int(T), int(F)
-        self.augment = self.loss = self.optim = None
-        for name, setter in (("augment", self.set_augment), ("loss", self.set_loss), ("optim", self.set_optim)):
+        self.augment = self.loss = self.optim = self.ema = None
+        for name, setter in (("augment", self.set_augment), ("loss", self.set_loss), ("optim", self.set_optim),
+                             ("ema", self.set_ema)):
             if getattr(config, name, None) is not None:
                 try:
                     setter(getattr(config, name))
@@ -111,6 +112,35 @@ class NetSession:
         that never had any.  The schedule is a function of ``iterations``, so ``get_state`` / ``set_state`` carry it."""
         self._set("cmoop_net_set_optim", None if optim is None else optim.check()._struct())
         self.optim = optim if optim is not None and optim.enabled else None
+
+    def set_ema(self, ema) -> None:
+        """Weight EMA (``EmaConfig``) of every following train step of this net -- ``train_step``, ``run_epoch`` and ``fit``
+        alike -- from the next step on.  The first enabled config makes the average a bit copy of the parameters; a later one
+        keeps it.  None or momentum 0 turns it off (``self.ema`` is then None), and the net steps bit for bit as one that
+        never had any.  ``fit`` then validates, early-stops and reads out on the average and leaves ``get_params()`` equal to
+        the weights that were scored.  ``set_state`` does not touch the average: ``set_ema_params`` does."""
+        self._set("cmoop_net_set_ema", None if ema is None else ema.check()._struct())
+        self.ema = ema if ema is not None and ema.enabled else None
+
+    def get_ema(self) -> np.ndarray:
+        """The average arena, in ``get_params``' layout; raises when the net has no average."""
+        out = np.empty(self.n_params, np.float32)
+        _lib.check(_lib.lib().cmoop_net_get_ema(self._h, _lib.ptr(out)))
+        return out
+
+    def set_ema_params(self, flat) -> None:
+        flat = np.ascontiguousarray(flat, np.float32)
+        assert flat.size == self.n_params
+        _lib.check(_lib.lib().cmoop_net_set_ema_params(self._h, _lib.ptr(flat)))
+
+    def use_ema(self, on) -> None:
+        """While on, ``evaluate`` / ``predict_proba`` / ``predict_logits`` / ``predict_stream`` read the average in place of
+        the parameters (no copy).  Turn it off again before the next train step: a step refuses otherwise."""
+        _lib.check(_lib.lib().cmoop_net_use_ema(self._h, C.c_int32(int(bool(on)))))
+
+    def finalize_ema(self) -> None:
+        """parameters := average (Keras' ``finalize_variable_values``); ``fit`` does this itself."""
+        _lib.check(_lib.lib().cmoop_net_finalize_ema(self._h))
 
     def optim_stats(self) -> dict:
         """The last train step's optimiser read-out: dict(sumsq, norm, scale, path) -- the float64 sum of squares of the

@@ -19,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import synth_waveforms  # noqa: E402
-from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, PopulationEvaluator, frontend, nsga  # noqa: E402
+from cmoop_audio_processing_amd import AugmentConfig, EmaConfig, EvalConfig, PopulationEvaluator, frontend, nsga  # noqa: E402
 
 
 def main():
@@ -41,6 +41,10 @@ def main():
     ap.add_argument("--augment", default="", choices=["", "kws"],
                     help="train-time augmentation of every candidate's fit (AugmentConfig.preset; the reference has none): "
                          "kws = time shift <= 10 frames, 2 time masks <= 10, 2 frequency masks <= 5")
+    ap.add_argument("--ema", type=float, default=0.0,
+                    help="weight EMA momentum of every candidate's fit (EmaConfig, Keras' ema_momentum; the reference has none): "
+                         "validation, early stopping and the read-outs take the averaged weights (0 = off, 0.99 is Keras' default)")
+    ap.add_argument("--ema-warmup", action="store_true", help="--ema: m(i) = min(m, (1 + i) / (10 + i))")
     a = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -56,7 +60,8 @@ def main():
     ev = PopulationEvaluator(Xtr, y[:n_tr], Xva, y[n_tr:n_tr + n_va],
                              EvalConfig.preset("nsga_penalty", epochs=a.epochs, seed=a.seed, verbose=(rank == 0),
                                                compute=a.compute, fpr_variant=a.fpr,
-                                               augment=AugmentConfig.preset(a.augment) if a.augment else None))
+                                               augment=AugmentConfig.preset(a.augment) if a.augment else None,
+                                               ema=EmaConfig(a.ema, a.ema_warmup) if a.ema > 0 else None))
     calls = []
     t_start = time.perf_counter()
     if rank == 0:      # a generation at full size takes minutes: keep stderr alive (job runners kill silent commands)

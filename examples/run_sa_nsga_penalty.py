@@ -25,7 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import synth_waveforms  # noqa: E402
-from cmoop_audio_processing_amd import (AugmentConfig, DistillConfig, EvalConfig, LossConfig, PopulationEvaluator, TrainedModel,  # noqa: E402
+from cmoop_audio_processing_amd import (AugmentConfig, DistillConfig, EmaConfig, EvalConfig, LossConfig, PopulationEvaluator, TrainedModel,  # noqa: E402
                                         datasets, frontend, nsga, surrogate)
 
 
@@ -66,6 +66,10 @@ def main():
                                                  "the reference has none).  Its classes and patch shape must be this run's")
     ap.add_argument("--kd-alpha", type=float, default=0.7, help="--teacher: weight of the distillation term, in (0, 1]")
     ap.add_argument("--kd-temperature", type=float, default=4.0, help="--teacher: temperature T of the distillation term, in [1, 64]")
+    ap.add_argument("--ema", type=float, default=0.0,
+                    help="weight EMA momentum of every candidate's fit (EmaConfig, Keras' ema_momentum; the reference has none): "
+                         "validation, early stopping and the read-outs take the averaged weights (0 = off, 0.99 is Keras' default)")
+    ap.add_argument("--ema-warmup", action="store_true", help="--ema: m(i) = min(m, (1 + i) / (10 + i))")
     a = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -98,6 +102,7 @@ def main():
                                                                    verbose=(rank == 0), compute=a.compute, augment=augment,
                                                                    loss=loss if loss.enabled else None,
                                                                    distill=DistillConfig(a.kd_alpha, a.kd_temperature) if a.teacher else None,
+                                                                   ema=EmaConfig(a.ema, a.ema_warmup) if a.ema > 0 else None,
                                                                    **({"variant": "B_ds"} if a.space == "ds" else {})))
     if a.teacher:
         ev.set_teacher(TrainedModel.load(a.teacher))      # one pass of the teacher over the training rows, shared by every candidate

@@ -96,11 +96,11 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 
 /* compute_objectives_and_constraints' inner loop (nsga_penalty.py:426-427): evaluate n
  * candidates; outputs are host arrays of length n (any may be NULL).
- * THE POPULATION CALL.  The six cmoop_eval_population* symbols are ONE call, cmoop_eval_population_opt, each with fewer
+ * THE POPULATION CALL.  The seven cmoop_eval_population* symbols are ONE call, cmoop_eval_population_avg, each with fewer
  * of its arguments: next (with ctx and evaluated; NULL: the library's own longest-first queue, evaluated may then be
- * NULL too) and the four training options aug, loss, distill, optim (cmoop_augment, cmoop_loss, cmoop_distill,
- * cmoop_optim below, checked in that order).  An option that is NULL or disabled gives exactly -- launch for launch, bit for
- * bit -- the call without it, so a caller may always take _opt and pass NULL for what is off. */
+ * NULL too) and the five training options aug, loss, distill, optim, ema (cmoop_augment, cmoop_loss, cmoop_distill,
+ * cmoop_optim, cmoop_ema below, checked in that order).  An option that is NULL or disabled gives exactly -- launch for launch,
+ * bit for bit -- the call without it, so a caller may always take _avg and pass NULL for what is off. */
 int cmoop_eval_population(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
                           const uint32_t* seeds /* [n] */, int32_t n, double* acc, double* size_mb, double* fpr,
                           int32_t* epochs_run, double* val_loss, double* seconds);
@@ -321,9 +321,49 @@ int cmoop_optim_rates(const cmoop_optim* optim, const cmoop_config* cfg, int64_t
 /* host-only: the tensor kind of every parameter of a candidate in arena order (cmoop_net_get_params), kinds[n]:
  * 0 kernel, 1 other trainable (bias, gamma, beta), 2 not trainable (BatchNorm moving mean / variance); n must be its parameter count */
 int cmoop_param_kinds(const int32_t gene[6], int32_t variant, int32_t classes, uint8_t* kinds, int64_t n);
-/* the population call (above) with every argument: the other five forward here */
+/* the population call (above) with every argument but ema: forwards to cmoop_eval_population_avg with NULL */
 int cmoop_eval_population_opt(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
                               const cmoop_optim* optim, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
+                              const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
+                              double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated);
+
+/* ---- weight EMA: an exponential moving average of the weights, read by validation, early stopping and the read-outs (opt-in,
+ * off by default).  BUILD-DEFINED: the reference builds Adam() without it (Keras' use_ema=True, ema_momentum); with no ema
+ * config, or a disabled one, every launch and every bit is that of a build without it.  No accuracy gain is claimed.
+ * i is optimizer.iterations BEFORE the update, the counter the step-size table is indexed by.
+ *   m(i) = momentum, or with warmup min(momentum, (1 + i) / (10 + i)) (TF's ExponentialMovingAverage(num_updates) rule),
+ *   evaluated in double on the host; mf(i) = (float)m(i), omf(i) = (float)(1.0 - m(i)), the subtraction in double, each
+ *   rounded once.  A config is ENABLED iff momentum > 0.
+ * The average arena a holds one float per parameter in the parameter arena's layout.  When an enabled config is first set on
+ * a net, a becomes a bit copy of the whole parameter arena at that moment; setting a config again keeps a.  After the optimiser
+ * launch(es) of every train step (every step path, both optimiser paths), with w' the weight after the update:
+ *   trainable element (kind 0 or 1, cmoop_param_kinds):  a' = (mf a) + (omf w')   two fp32 products and one fp32 add, each
+ *                                                         rounded separately (no fused multiply-add)
+ *   BatchNorm moving mean / variance (kind 2):            a' = w'                 a copy of the bits
+ * so a is at all times a complete parameter set inference can run on.  Non-finite values propagate.  The training trajectory
+ * is never touched: w, Adam's m / v, the gradients, dropout and the counters carry the bits of the same net without the
+ * average.  One extra launch per step; the step is not captured as a graph.
+ * A fit with the average on (cmoop_net_fit, the population call): every per-epoch validation pass runs on a -- the val_loss
+ * EarlyStopping monitors, the history, acc_readout "last" and the predictions behind the FPR are those of a; with restore_best
+ * the best-epoch snapshot is a snapshot of a.  At the end of the fit the parameter arena is overwritten (Keras'
+ * finalize_variable_values) with exactly the weights that were read out: the restored best-epoch snapshot, else a of the last
+ * epoch.  Adam's moments, the counters and a itself stay.  Training between validations continues on the raw weights. */
+typedef struct cmoop_ema {
+    double  momentum;   /* m, 0 <= m < 1, finite; 0 = off.  Keras' ema_momentum (its default is 0.99) */
+    int32_t warmup;     /* 0 / 1: m(i) = min(m, (1 + i) / (10 + i)) */
+    int32_t reserved;   /* 0 */
+} cmoop_ema;            /* 16 bytes */
+int cmoop_ema_default(cmoop_ema* ema);   /* off: all zero */
+/* host-only: non-zero + a message naming the offending field (momentum, warmup, reserved) when the config is outside the domain */
+int cmoop_ema_check(const cmoop_ema* ema);
+/* host-only, the numbers the kernel consumes at `iteration`: m(i) in double, mf(i), omf(i).  Any output may be NULL. */
+int cmoop_ema_rates(const cmoop_ema* ema, int64_t iteration, double* m, float* mf, float* omf);
+/* the kernel alone on the library stream: a_dev [n] advanced against w_dev [n] at the rates of `iteration`; kinds_dev [n]
+ * bytes (NULL: every element trainable).  Reads w, a and kinds, writes a only. */
+int cmoop_ema_update(const cmoop_ema* ema, int64_t iteration, float* a_dev, const float* w_dev, const uint8_t* kinds_dev, int64_t n);
+/* the population call (above) with every argument: the other six forward here */
+int cmoop_eval_population_avg(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                              const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
                               const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
                               double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated);
 
@@ -547,6 +587,22 @@ int cmoop_net_set_optim(cmoop_net* net, const cmoop_optim* optim /* NULL = off *
 /* the last train step's out = {sum of squares of the trainable gradients, their norm, the clip scale, launch path (0: the fused
  * launch, which computes no norm: 0, 0, 1; 1: finish + update)} */
 int cmoop_net_optim_stats(cmoop_net* net, double out[4]);
+/* Weight EMA (cmoop_ema above) of every following train step of this net, from the next step on (NULL or a disabled config:
+ * off, and the net steps bit for bit as one that never had one; an average that already exists is kept, no longer advanced).
+ * The first enabled config makes the average a bit copy of the parameter arena; a later one keeps it.  The config is copied; the
+ * rate table of a fit under way is rebuilt.  cmoop_net_set_state leaves the average untouched: a re-synchronising checker calls
+ * cmoop_net_set_ema_params as well. */
+int cmoop_net_set_ema(cmoop_net* net, const cmoop_ema* ema /* NULL = off */);
+/* the average arena to / from a host array of cmoop_net_total_params floats; an error when the net has no average */
+int cmoop_net_get_ema(cmoop_net* net, float* host);
+int cmoop_net_set_ema_params(cmoop_net* net, const float* host);
+/* on != 0: cmoop_net_evaluate / _predict / _predict_logits / _predict_stream read the average in place of the parameters (a
+ * pointer swap, no copy) until on == 0.  An error when the net has no average; a train step while it is on is refused.
+ * cmoop_net_get_params / _set_params / _get_state / _set_state always mean the raw parameters. */
+int cmoop_net_use_ema(cmoop_net* net, int32_t on);
+/* w := a (Keras' finalize_variable_values), for callers that step by hand; cmoop_net_fit does it itself.  Adam's moments, the
+ * counters and the average stay. */
+int cmoop_net_finalize_ema(cmoop_net* net);
 /* cmoop_net_train_step_targets with a teacher row per batch row, q_dev [B][classes], and the distillation loss at
  * (alpha, temperature), whatever cmoop_net_set_distill says. */
 int cmoop_net_train_step_distill_targets(cmoop_net* net, const float* x_rows_dev, const float* t_dev, const float* w_dev,

@@ -11,6 +11,9 @@ per step; compare the ms per step with and without it.
 --mixup-alpha A / --label-smoothing E / --class-weight balanced train on the soft-target loss (LossConfig): two more launches
 per step (targets, soft cross-entropy in place of the sparse one: one net launch more), and with mixup a third, the blend,
 another streaming pass over one batch.
+--ema M [--ema-warmup] trains with the weight EMA (EmaConfig): one more launch per step (12 bytes plus a kind byte per
+parameter), and validation reads the averaged weights.  --history adds the per-epoch validation loss and accuracy of one
+more fit of the same candidate and seed (NetSession.fit) to the line.
 """
 import argparse
 import json
@@ -22,7 +25,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cmoop_audio_processing_amd import AugmentConfig, EvalConfig, LossConfig, PopulationEvaluator, genes as G  # noqa: E402
+from cmoop_audio_processing_amd import AugmentConfig, EmaConfig, EvalConfig, LossConfig, PopulationEvaluator, genes as G  # noqa: E402
+from cmoop_audio_processing_amd.session import NetSession  # noqa: E402
 
 
 def main():
@@ -37,6 +41,9 @@ def main():
     ap.add_argument("--mixup-alpha", type=float, default=0.0, help="mixup with lam from Beta(alpha, alpha); 0: off")
     ap.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing eps; 0: off")
     ap.add_argument("--class-weight", default="", choices=["", "balanced"], help="balanced: n / (classes * count_c) of the train labels")
+    ap.add_argument("--ema", type=float, default=0.0, help="weight EMA momentum (Keras' ema_momentum, e.g. 0.99); 0: off")
+    ap.add_argument("--ema-warmup", action="store_true", help="--ema: m(i) = min(m, (1 + i) / (10 + i))")
+    ap.add_argument("--history", action="store_true", help="add the per-epoch validation loss / accuracy of one more fit")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     g = torch.Generator(device="cuda")
@@ -49,7 +56,8 @@ def main():
     if args.class_weight == "balanced":
         loss = LossConfig.balanced(y[:n_tr], 10, mixup_alpha=args.mixup_alpha, label_smoothing=args.label_smoothing)
     cfg = EvalConfig.preset("nsga_penalty", variant=args.variant, epochs=args.epochs, early_stop=False, n_slots=1, seed=0,
-                            augment=augment, loss=loss if loss.enabled else None)
+                            augment=augment, loss=loss if loss.enabled else None,
+                            ema=EmaConfig(momentum=args.ema, warmup=args.ema_warmup) if args.ema > 0 else None)
     ev = PopulationEvaluator(X[:n_tr], y[:n_tr], X[n_tr:], y[n_tr:], cfg)
     steps = args.epochs * ((n_tr + cfg.batch - 1) // cfg.batch)
     for gs in args.genes:
@@ -61,9 +69,16 @@ def main():
             t0 = time.perf_counter()
             ev.evaluate_individual(hp)
             best = min(best, time.perf_counter() - t0)
+        hist = {}
+        if args.history:      # the seed evaluate_individual gave the candidate's first evaluation
+            with NetSession(gene, cfg, 101, 40, cfg.seed) as net:
+                r = net.fit(ev.X_train, ev.y_train, ev.X_val, ev.y_val)
+            hist = {"val_loss_history": [float(v) for v in r["val_loss_history"]],
+                    "val_accuracy_history": [float(v) for v in r["val_accuracy_history"]]}
         fl = G.eval_flops(gene, G.VARIANT_NAMES[args.variant], 10, 101, 40, n_tr, n_va, args.epochs, 1)
         print(json.dumps({"gene": gene, "variant": args.variant, "augment": args.augment or None, "noise_std": args.noise_std,
                           "mixup_alpha": args.mixup_alpha, "label_smoothing": args.label_smoothing, "class_weight": args.class_weight or None,
+                          "ema": args.ema or None, "ema_warmup": bool(args.ema_warmup), **hist,
                           "train_steps": steps, "wall_s": round(best, 4),
                           "steps_per_s": round(steps / best, 1), "ms_per_step_incl_val": round(best / steps * 1e3, 4),
                           "tflops": round(fl / best / 1e12, 2)}), flush=True)
