@@ -241,7 +241,12 @@ struct Scratch {
     ~Scratch() { hipStreamSynchronize(s); for (void* p : ptrs) hipFree(p); }
     float* floats(size_t n) {   // null for n == 0
         void* p = nullptr;
-        if (n) { CMOOP_HIP(hipMalloc(&p, n * 4)); ptrs.push_back(p); }
+        if (n) {
+            const int fill = pool_fill_value();
+            CMOOP_HIP(hipMalloc(&p, n * 4));
+            ptrs.push_back(p);
+            pool_fill_device(p, n * 4, fill);
+        }
         return static_cast<float*>(p);
     }
     void* rowtab(const ConvGeom& g, int rows) {   // a lone layer's row table of geometry g (rows == 0: it has none)

@@ -132,6 +132,9 @@ struct ConvLayer {
 
 // cached device allocations (net.hip): get may return stale contents, free never blocks on other streams
 void* pool_alloc(size_t bytes);
+// CMOOP_POOL_FILL (net.hip): its byte, -1 when unset; and the fill of a device buffer about to be handed out (fill < 0: nothing)
+int pool_fill_value();
+void pool_fill_device(void* p, size_t bytes, int fill);
 void pool_free(void* p);
 void* pool_alloc_pinned(size_t bytes);
 void pool_free_pinned(void* p);

@@ -3,6 +3,8 @@
 #include "net.h"
 
 #include <algorithm>
+#include <cctype>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -100,32 +102,64 @@ ProfileTotals& profile_totals() {
 // stream of the device, so tearing a candidate down buffer by buffer (~100 buffers) stalls its worker while the other
 // streams' queues drain; candidates of one search reuse a handful of buffer sizes, so finished candidates hand their
 // buffers to the next one instead.  Buffers are handed out with stale contents (as hipMalloc may): every consumer
-// writes before it reads.  CMOOP_POOL_GB caps the cached bytes (default 96; 0 disables the cache).
+// writes before it reads -- tests/test_gpu_stale_memory.py holds that sentence: under CMOOP_POOL_FILL=<byte> (below) every
+// result the library returns is bit-identical whatever the buffers held.  CMOOP_POOL_GB caps the cached bytes (default 96;
+// 0 disables the cache).
+
+// CMOOP_POOL_FILL=<byte> (decimal or 0x.., 0..255; read at each allocation, as CMOOP_ADAM_UNFUSED is per step: tests flip it):
+// -1 when unset or empty -- the plain path -- and a throw naming the variable for anything else that is no byte
+int pool_fill_value() {
+    const char* e = std::getenv("CMOOP_POOL_FILL");
+    if (!e || !e[0]) return -1;
+    char* end = nullptr;
+    errno = 0;
+    const long v = std::strtol(e, &end, 0);
+    CMOOP_REQUIRE(errno == 0 && end != e && *end == 0 && v >= 0 && v <= 255 && e[0] != '-' && e[0] != '+' && !std::isspace((unsigned char)e[0]),
+                  std::string("CMOOP_POOL_FILL must be a byte 0..255, decimal or 0x.. (got '") + e + "')");
+    return (int)v;
+}
+
+// the whole of a buffer about to be handed out := fill (a blocking memset: the caller's stream sees it whatever its flags)
+void pool_fill_device(void* p, size_t bytes, int fill) {
+    if (fill < 0 || !p || !bytes) return;
+    CMOOP_HIP(hipMemset(p, fill, bytes));
+    CMOOP_HIP(hipStreamSynchronize(nullptr));
+}
+
 namespace {
 class DevicePool {
   public:
     explicit DevicePool(bool host) : host_(host) {}
     void* get(size_t bytes) {
+        const int fill = pool_fill_value();   // before anything is taken: a bad value fails the call and leaks nothing
         const size_t want = round_up(bytes);
         int dev = 0;
         CMOOP_HIP(hipGetDevice(&dev));
+        void* p = nullptr;
+        size_t have = 0;
         if (cap_bytes() > 0) {
             std::lock_guard<std::mutex> l(mu_);
             auto& fl = free_[dev];
             auto it = fl.lower_bound(want);
             if (it != fl.end() && it->first <= want + want / 8) {
-                void* p = it->second;
+                p = it->second;
+                have = it->first;
                 cached_ -= it->first;
                 sizes_[p] = it->first;
                 fl.erase(it);
-                return p;
             }
         }
-        void* p = nullptr;
-        if (host_) CMOOP_HIP(hipHostMalloc(&p, want));
-        else CMOOP_HIP(hipMalloc(&p, want));
-        std::lock_guard<std::mutex> l(mu_);
-        sizes_[p] = want;
+        if (!p) {
+            if (host_) CMOOP_HIP(hipHostMalloc(&p, want));
+            else CMOOP_HIP(hipMalloc(&p, want));
+            have = want;
+            std::lock_guard<std::mutex> l(mu_);
+            sizes_[p] = want;
+        }
+        if (fill >= 0) {
+            if (host_) std::memset(p, fill, have);
+            else pool_fill_device(p, have, fill);
+        }
         return p;
     }
     void put(void* p) {
