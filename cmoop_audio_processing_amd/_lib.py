@@ -70,6 +70,17 @@ class Ema(C.Structure):
     _fields_ = [("momentum", C.c_double), ("warmup", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Opoint(C.Structure):
+    """cmoop_opoint (include/cmoop.h), 16 bytes."""
+    _fields_ = [("recall", C.c_double), ("objective", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OpointClass(C.Structure):
+    """cmoop_opoint_class (include/cmoop.h), 32 bytes."""
+    _fields_ = [("u2", C.c_int64), ("P", C.c_int32), ("N", C.c_int32), ("k", C.c_int32), ("tp", C.c_int32), ("fp", C.c_int32),
+                ("thr", C.c_float)]
+
+
 #: cmoop_next_fn (include/cmoop.h): int32_t (*)(void* ctx)
 NEXT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 
@@ -156,6 +167,22 @@ EMA_PROTOTYPES = {
     "cmoop_net_use_ema": [C.c_void_p, C.c_int32],
     "cmoop_net_finalize_ema": [C.c_void_p],
     "cmoop_eval_population_avg": [C.c_void_p] * 9 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 7,
+}
+
+
+#: prototypes of the operating-point entry points (include/cmoop.h); structs travel as void* (C.byref), None is NULL
+OPOINT_PROTOTYPES = {
+    "cmoop_opoint_default": [C.c_void_p],
+    "cmoop_opoint_check": [C.c_void_p],
+    "cmoop_roc_counts": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
+    "cmoop_operating_point": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_opoint_summary": [C.c_void_p, C.c_int32, C.c_void_p],
+    "cmoop_operating_point_time": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p],
+    "cmoop_net_set_opoint": [C.c_void_p, C.c_void_p],
+    "cmoop_net_last_opoint": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_net_operating_point": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    # cmoop_eval_population_avg with one more struct pointer after ema and one more output after evaluated
+    "cmoop_eval_population_op": [C.c_void_p] * 10 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 8,
 }
 
 
@@ -253,7 +280,7 @@ def lib():
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
         for table in (STREAM_PROTOTYPES, AUGMENT_PROTOTYPES, PCEN_PROTOTYPES, ELEM_PROTOTYPES, LOSS_PROTOTYPES, DENSE_PROTOTYPES,
-                      DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES):
+                      DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES, OPOINT_PROTOTYPES):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         _lib = L

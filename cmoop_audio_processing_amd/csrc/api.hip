@@ -2,6 +2,7 @@
 #include "../../include/cmoop.h"
 #include "net.h"
 
+#include <cstddef>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -178,8 +179,25 @@ static EmaCfg to_ema(const cmoop_ema* e) {
     return c;
 }
 
+static_assert(sizeof(cmoop_opoint) == 16, "cmoop_opoint is part of the ABI");
+static_assert(sizeof(cmoop_opoint_class) == 32 && sizeof(cmoop_opoint_class) == sizeof(OpointClass), "cmoop_opoint_class is part of the ABI");
+static OpointCfg to_opoint(const cmoop_opoint* p) {
+    CMOOP_REQUIRE(p != nullptr, "opoint config is NULL");
+    OpointCfg c;
+    c.recall = p->recall; c.objective = p->objective; c.reserved = p->reserved;
+    return c;
+}
+// cmoop_opoint_class and OpointClass are one layout (asserted above and field by field here)
+static OpointClass* as_classes(cmoop_opoint_class* c) {
+    static_assert(offsetof(cmoop_opoint_class, u2) == offsetof(OpointClass, u2) && offsetof(cmoop_opoint_class, P) == offsetof(OpointClass, P) &&
+                  offsetof(cmoop_opoint_class, N) == offsetof(OpointClass, N) && offsetof(cmoop_opoint_class, k) == offsetof(OpointClass, k) &&
+                  offsetof(cmoop_opoint_class, tp) == offsetof(OpointClass, tp) && offsetof(cmoop_opoint_class, fp) == offsetof(OpointClass, fp) &&
+                  offsetof(cmoop_opoint_class, thr) == offsetof(OpointClass, thr), "cmoop_opoint_class layout");
+    return reinterpret_cast<OpointClass*>(c);
+}
+
 // The converted training options of one population call: to_* and the matching *_check of every struct handed in, in the
-// order augment, loss, distill, optim, ema (what a call with two bad structs reports first); owns what opt points into
+// order augment, loss, distill, optim, ema, opoint (what a call with two bad structs reports first); owns what opt points into
 namespace {
 struct AbiTrainOptions {
     AugmentCfg aug;
@@ -187,14 +205,16 @@ struct AbiTrainOptions {
     DistillCfg distill;
     OptimCfg optim;
     EmaCfg ema;
+    OpointCfg opoint;
     TrainOptions opt;
     AbiTrainOptions(const cmoop_augment* a, const cmoop_loss* l, const cmoop_distill* d, const cmoop_optim* o, const cmoop_ema* e,
-                    const NetConfig& c, const Dataset& ds) {
+                    const cmoop_opoint* p, const NetConfig& c, const Dataset& ds) {
         if (a) { aug = to_augment(a); augment_check(aug, ds.T, ds.F); opt.aug = &aug; }
         if (l) { loss = to_loss(l); loss_check(loss, c.classes); opt.loss = &loss; }
         if (d) { distill = to_distill(d); distill_check(distill, c.classes, ds.n_train); opt.distill = &distill; }
         if (o) { optim = to_optim(o); optim_check(optim); opt.optim = &optim; }
         if (e) { ema = to_ema(e); ema_check(ema); opt.ema = &ema; }
+        if (p) { opoint = to_opoint(p); opoint_check(opoint); opt.opoint = &opoint; }
     }
     AbiTrainOptions(const AbiTrainOptions&) = delete;
 };
@@ -307,15 +327,16 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 
 // every population call; next == NULL: candidates are taken longest-first from a process-local counter; a NULL option: off
 static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss,
-                                const cmoop_distill* distill, const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_dataset* ds,
-                                const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
-                                double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
+                                const cmoop_distill* distill, const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op,
+                                const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx,
+                                double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds,
+                                int32_t* evaluated, double* opoint) {
     CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
     CMOOP_REQUIRE(n >= 0, "negative population size");
     CMOOP_REQUIRE(!next || evaluated, "NULL argument");
     NetConfig c = to_cfg(cfg);
     const Dataset d = to_dataset(ds);
-    const AbiTrainOptions options(aug, loss, distill, optim, ema, c, d);
+    const AbiTrainOptions options(aug, loss, distill, optim, ema, op, c, d);
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
@@ -330,6 +351,7 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* au
         if (epochs_run) epochs_run[i] = r[i].epochs_run;
         if (val_loss) val_loss[i] = r[i].val_loss;
         if (seconds) seconds[i] = r[i].seconds;
+        if (opoint) std::memcpy(opoint + 4 * (size_t)i, r[i].opoint, sizeof(r[i].opoint));
     }
 }
 
@@ -382,9 +404,83 @@ int cmoop_eval_population_avg(const cmoop_config* cfg, const cmoop_augment* aug,
                               const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_dataset* ds, const int32_t* genes,
                               const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr,
                               int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated) {
+    return cmoop_eval_population_op(cfg, aug, loss, distill, optim, ema, nullptr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr,
+                                    epochs_run, val_loss, seconds, evaluated, nullptr);
+}
+
+int cmoop_eval_population_op(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                             const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_dataset* ds,
+                             const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc,
+                             double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated,
+                             double* opoint) {
     return guard([&] {
-        eval_population_abi(cfg, aug, loss, distill, optim, ema, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run,
-                            val_loss, seconds, evaluated);
+        eval_population_abi(cfg, aug, loss, distill, optim, ema, op, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run,
+                            val_loss, seconds, evaluated, opoint);
+    });
+}
+
+// ---- operating-point read-out ----------------------------------------------------
+int cmoop_opoint_default(cmoop_opoint* op) {
+    return guard([&] {
+        CMOOP_REQUIRE(op != nullptr, "opoint config is NULL");
+        std::memset(op, 0, sizeof(*op));
+    });
+}
+
+int cmoop_opoint_check(const cmoop_opoint* op) {
+    return guard([&] { opoint_check(to_opoint(op)); });
+}
+
+int cmoop_roc_counts(const float* probs, const int32_t* y, int64_t n, int32_t C, int32_t* counts) {
+    return guard([&] {
+        opoint_check_shape(n, C);
+        CMOOP_REQUIRE(n == 0 || (probs && y && counts), "roc_counts: NULL buffer");
+        if (n == 0) return;
+        hipStream_t s = lib_stream();
+        PoolScope pool(s);
+        uint32_t* key = pool.get<uint32_t>((size_t)n * C * 4);
+        launch_score_keys(probs, key, n, C, s);
+        launch_roc_counts(key, y, counts, n, C, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_operating_point(const float* probs, const int32_t* y, int64_t n, int32_t C, const cmoop_opoint* op,
+                          cmoop_opoint_class* classes, double* summary) {
+    return guard([&] {
+        const OpointCfg c = to_opoint(op);
+        opoint_check(c);
+        operating_point(probs, y, n, C, c.recall, as_classes(classes), summary, lib_stream());
+    });
+}
+
+int cmoop_operating_point_time(const float* probs, const int32_t* y, int64_t n, int32_t C, const cmoop_opoint* op, int32_t iters,
+                               double* avg_ms) {
+    return guard([&] {
+        const OpointCfg c = to_opoint(op);
+        opoint_check(c);
+        opoint_check_shape(n, C);
+        CMOOP_REQUIRE(n >= 1 && probs && y && avg_ms && iters >= 1, "operating_point_time: n >= 1, iters >= 1 and every buffer");
+        hipStream_t s = lib_stream();
+        PoolScope pool(s);
+        uint32_t* key = pool.get<uint32_t>((size_t)n * C * 4);
+        int32_t* cnt = pool.get<int32_t>((size_t)n * C * 16);
+        OpointClass* rec = pool.get<OpointClass>((size_t)C * sizeof(OpointClass));
+        auto keys = [&] { launch_score_keys(probs, key, n, C, s); };
+        auto counts = [&] { launch_roc_counts(key, y, cnt, n, C, s); };
+        auto select = [&] { launch_opoint_select(key, y, cnt, n, C, c.recall, rec, s); };
+        avg_ms[0] = time_launches(s, iters, [&] { keys(); counts(); select(); });
+        avg_ms[1] = time_launches(s, iters, keys);
+        avg_ms[2] = time_launches(s, iters, counts);
+        avg_ms[3] = time_launches(s, iters, select);
+    });
+}
+
+int cmoop_opoint_summary(const cmoop_opoint_class* classes, int32_t C, double* summary) {
+    return guard([&] {
+        CMOOP_REQUIRE(classes && summary, "opoint_summary: NULL argument");
+        CMOOP_REQUIRE(C >= 1 && C <= OPOINT_MAX_CLASSES, "opoint_summary: classes must be in [1, 64]");
+        opoint_summary(as_classes(const_cast<cmoop_opoint_class*>(classes)), C, summary);
     });
 }
 
@@ -1110,6 +1206,28 @@ int cmoop_net_finalize_ema(cmoop_net* h) {
         CMOOP_REQUIRE(h && h->net, "finalize_ema: NULL net");
         h->net->finalize_average();
         CMOOP_HIP(hipStreamSynchronize(h->net->stream()));
+    });
+}
+int cmoop_net_set_opoint(cmoop_net* h, const cmoop_opoint* op) { return net_set_option(h, "set_opoint", op, to_opoint, &Net::set_opoint); }
+int cmoop_net_last_opoint(cmoop_net* h, cmoop_opoint_class* classes, double* summary) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "last_opoint: NULL net");
+        h->net->last_opoint(classes ? as_classes(classes) : nullptr, summary);
+    });
+}
+int cmoop_net_operating_point(cmoop_net* h, const float* x, const int32_t* y, int64_t n, const cmoop_opoint* op,
+                              cmoop_opoint_class* classes, double* summary) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "operating_point: NULL net");
+        const OpointCfg c = to_opoint(op);
+        opoint_check(c);
+        const int C = h->net->config().classes;
+        opoint_check_shape(n, C);
+        CMOOP_REQUIRE(classes && summary && (n == 0 || (x && y)), "operating_point: NULL buffer");
+        PoolScope pool(h->net->stream());
+        float* probs = pool.get<float>(std::max<size_t>((size_t)n * C, 1) * 4);
+        h->net->predict(x, n, probs);
+        operating_point(probs, y, n, C, c.recall, as_classes(classes), summary, h->net->stream());
     });
 }
 int cmoop_net_train_step_distill_targets(cmoop_net* h, const float* x_rows, const float* t, const float* w, const int32_t* primary,

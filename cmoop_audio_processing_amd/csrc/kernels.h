@@ -504,6 +504,39 @@ void launch_confusion(const int32_t* y_true, const int32_t* y_pred, int64_t n, i
                       int64_t* cm, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Operating-point read-out (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_opoint): per class, one-vs-rest,
+// the threshold that still catches `recall` of the positives, the false positives at it, and twice the Mann-Whitney U.
+// Defined in integers on the total order of the score bit patterns: three launches (keys, counts, select), no atomics.
+// ---------------------------------------------------------------------------
+struct OpointCfg {
+    double recall = 0;               // 0 <= recall <= 1; 0 = off
+    int objective = 0, reserved = 0; // objective 1: the evaluator ranks candidates by fpr_at_recall (read by the host layers only)
+};
+// host-only: throws with a message naming the offending field
+void opoint_check(const OpointCfg& c);
+inline bool opoint_enabled(const OpointCfg& c) { return c.recall > 0; }
+struct OpointClass {                 // cmoop_opoint_class, 32 bytes
+    int64_t u2;
+    int32_t P, N, k, tp, fp;
+    float thr;
+};
+static_assert(sizeof(OpointClass) == 32, "the select kernel writes 32-byte records");
+constexpr int64_t OPOINT_MAX_ROWS = EPOCH_PERMUTATION_DEVICE_MAX;   // n^2 compares, as the device epoch permutation
+constexpr int OPOINT_MAX_CLASSES = 64;
+constexpr int ROC_TILE = 1024;       // rows j a workgroup of roc_counts_kernel stages in LDS per run
+// throws naming the bound when (n, C) is outside 0 <= n <= OPOINT_MAX_ROWS, 1 <= C <= OPOINT_MAX_CLASSES
+void opoint_check_shape(int64_t n, int C);
+// key[c][i] = the order key of p[i][c] (p [n][C] row-major): b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000) of its IEEE bits b
+void launch_score_keys(const float* p, uint32_t* key, int64_t n, int C, hipStream_t s);
+// cnt[c][i] = {ge_pos, ge_neg, gt_pos, gt_neg}: rows j with key[c][j] >= (>) key[c][i], split by y[j] == c
+void launch_roc_counts(const uint32_t* key, const int32_t* y, int32_t* cnt, int64_t n, int C, hipStream_t s);
+// rec[c] from key, y and cnt: one workgroup per class, every reduction in a fixed order
+void launch_opoint_select(const uint32_t* key, const int32_t* y, const int32_t* cnt, int64_t n, int C, double recall,
+                          OpointClass* rec, hipStream_t s);
+// host-only, the float64 finish: out = {fpr_at_recall, recall_achieved, macro_auc, n_scored}, sums left to right in class order
+void opoint_summary(const OpointClass* rec, int C, double out[4]);
+
+// ---------------------------------------------------------------------------
 // Audio front end (north-star addition; no reference counterpart)
 // ---------------------------------------------------------------------------
 constexpr int FRONTEND_MAX_MELS = 128;

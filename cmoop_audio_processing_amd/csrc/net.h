@@ -211,13 +211,14 @@ struct NetPlan {
 NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F);
 
 // The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
-// set_distill / set_optim / set_ema say what each does).  The pointees stay the caller's for the length of the call
+// set_distill / set_optim / set_ema / set_opoint say what each does).  The pointees stay the caller's for the length of the call
 struct TrainOptions {
     const AugmentCfg* aug = nullptr;
     const LossCfg* loss = nullptr;
     const DistillCfg* distill = nullptr;
     const OptimCfg* optim = nullptr;
     const EmaCfg* ema = nullptr;
+    const OpointCfg* opoint = nullptr;
 };
 
 class Net : public GemmHook {
@@ -286,7 +287,16 @@ class Net : public GemmHook {
     void get_average(float* host);
     void set_average(const float* host);
     void finalize_average();   // w := a (Keras' finalize_variable_values); Adam's moments, the counters and a stay
-    // the enabled ones of o through the five setters above, in that order: augment, loss, distill, optim, ema.  THE place of "a
+    // Operating-point read-out (kernels.h) of every following fit_and_read_out on this net; null or a disabled config: off, and
+    // the fit's launches and allocations are those of a net that never had one.  Enabled: the domain is checked and the config
+    // copied.  No train step, validation pass or earlier read-out changes: after the weights are final the fit runs ONE more
+    // predict over the validation split and the three read-out launches, and keeps the record for last_opoint
+    void set_opoint(const OpointCfg* op);
+    const OpointCfg& opoint() const { return opoint_cfg_; }
+    // the record of the last fit_and_read_out: classes [cfg.classes] and summary [4]; throws when that fit ran without the option
+    void last_opoint(OpointClass* classes, double summary[4]) const;
+    void store_opoint(const OpointClass* classes, const double summary[4]);   // classes null: the last fit had none
+    // the enabled ones of o through the six setters above, in that order: augment, loss, distill, optim, ema, opoint.  THE place of "a
     // disabled config is no config": null or disabled is not applied at all, and the net stays one that never had it
     void set_options(const TrainOptions& o);
     // the last step's {sum of squares, norm, scale, launch path (0 fused, 1 finish + update)}; path 0 computes no norm: 0, 0, 1
@@ -370,6 +380,9 @@ class Net : public GemmHook {
     EmaCfg ema_cfg_;                    // set_ema; the default is off
     bool ema_on_ = false;               // train steps advance ema_ after the optimiser launch(es)
     EmaPair* ema_tab_ = nullptr;        // (mf, omf) per iteration, alpha_tab_n_ entries, next to alpha_tab_
+    OpointCfg opoint_cfg_;              // set_opoint; the default is off
+    std::vector<OpointClass> last_op_classes_;   // store_opoint: empty when the last fit ran without the read-out
+    double last_op_summary_[4] = {0, 0, 0, 0};
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;
     bool aug_on_ = false;               // train steps read aug_buf_ (set_augment)
     AugmentParams aug_;
@@ -421,6 +434,8 @@ struct EvalResult {
     double acc = 0, size_mb = 0, fpr = 0, val_loss = 0, seconds = 0;
     int epochs_run = 0;
     int evaluated = 0;   // 1 when THIS call trained the candidate (always, unless a pull callback handed it to another rank)
+    // the operating-point read-out (Net::set_opoint): fpr_at_recall, recall_achieved, macro_auc, n_scored; zeros when it is off
+    double opoint[4] = {0, 0, 0, 0};
 };
 
 // per-epoch record of a fit (tests: the early-stopping decisions are checked against the validation-loss history)
@@ -448,6 +463,10 @@ void eval_population(const NetConfig& cfg, const Dataset& ds, const int32_t* gen
 // host-only: windows of T frames at hop frames in a stream of n_frames, 1 + (n_frames - T) / hop; throws when n_frames < T or hop < 1
 int64_t stream_windows(int64_t n_frames, int T, int hop);
 double fpr_from_confusion(const int64_t* cm, int C, int variant);
+// the operating-point read-out of probs [n][C] against y [n] (device pointers) at `recall`: keys, counts and select on s with
+// pooled workspaces, every byte written before it is read; classes [C] and summary [4] are host arrays (kernels.h, OpointClass)
+void operating_point(const float* probs, const int32_t* y, int64_t n, int C, double recall, OpointClass* classes, double summary[4],
+                     hipStream_t s);
 void epoch_permutation(uint32_t seed, uint32_t epoch, int64_t n, int32_t* out);
 
 }  // namespace cmoop

@@ -1150,6 +1150,25 @@ void Net::set_options(const TrainOptions& o) {
     if (o.distill && distill_enabled(*o.distill)) set_distill(o.distill);
     if (o.optim && optim_enabled(*o.optim)) set_optim(o.optim);
     if (o.ema && ema_enabled(*o.ema)) set_ema(o.ema);
+    if (o.opoint && opoint_enabled(*o.opoint)) set_opoint(o.opoint);
+}
+
+void Net::set_opoint(const OpointCfg* op) {
+    if (op) opoint_check(*op);
+    opoint_cfg_ = op && opoint_enabled(*op) ? *op : OpointCfg();   // read by fit_and_read_out alone: no step changes, the graph stays
+}
+
+void Net::store_opoint(const OpointClass* classes, const double summary[4]) {
+    last_op_classes_.clear();
+    if (!classes) return;
+    last_op_classes_.assign(classes, classes + cfg_.classes);
+    std::memcpy(last_op_summary_, summary, sizeof(last_op_summary_));
+}
+
+void Net::last_opoint(OpointClass* classes, double summary[4]) const {
+    CMOOP_REQUIRE(!last_op_classes_.empty(), "last_opoint: the last fit ran without the operating-point read-out (set_opoint with recall > 0 first)");
+    if (classes) std::memcpy(classes, last_op_classes_.data(), last_op_classes_.size() * sizeof(OpointClass));
+    if (summary) std::memcpy(summary, last_op_summary_, sizeof(last_op_summary_));
 }
 
 void Net::ensure_kinds() {
@@ -1518,10 +1537,28 @@ double fpr_from_confusion(const int64_t* cm, int C, int variant) {
     return cnt ? sum / cnt : 0.0;
 }
 
+void operating_point(const float* probs, const int32_t* y, int64_t n, int C, double recall, OpointClass* classes, double summary[4],
+                     hipStream_t s) {
+    opoint_check_shape(n, C);
+    CMOOP_REQUIRE(classes && summary && (n == 0 || (probs && y)), "operating_point: NULL buffer");
+    PoolScope pool(s);   // key, counts and records go back once the stream has drained
+    const size_t cells = std::max<size_t>((size_t)n * C, 1);
+    uint32_t* d_key = pool.get<uint32_t>(cells * 4);
+    int32_t* d_cnt = pool.get<int32_t>(cells * 16);
+    OpointClass* d_rec = pool.get<OpointClass>((size_t)C * sizeof(OpointClass));
+    launch_score_keys(probs, d_key, n, C, s);
+    launch_roc_counts(d_key, y, d_cnt, n, C, s);
+    launch_opoint_select(d_key, y, d_cnt, n, C, recall, d_rec, s);
+    CMOOP_HIP(hipMemcpyAsync(classes, d_rec, (size_t)C * sizeof(OpointClass), hipMemcpyDeviceToHost, s));
+    CMOOP_HIP(hipStreamSynchronize(s));
+    opoint_summary(classes, C, summary);
+}
+
 EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, uint32_t seed, FitHistory* hist) {
     const auto t0 = std::chrono::steady_clock::now();
     CMOOP_REQUIRE(ds.n_train >= 1 && ds.n_val >= 1, "empty train or validation split");
     CMOOP_REQUIRE(ds.n_train < (1ll << 31) && ds.n_val < (1ll << 31), "split too large");
+    if (opoint_enabled(net.opoint())) opoint_check_shape(ds.n_val, cfg.classes);   // fail before the fit, not after it
     hipStream_t stream = net.stream();
     EvalResult res;
     res.size_mb = (double)(net.total_params() * 4) / (1024.0 * 1024.0);   // compute_model_size_mb, nsga_penalty.py:337-344
@@ -1605,6 +1642,18 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
     CMOOP_HIP(hipMemcpyAsync(cm.data(), d_cm, cm.size() * 8, hipMemcpyDeviceToHost, stream));
     CMOOP_HIP(hipStreamSynchronize(stream));
     res.fpr = fpr_from_confusion(cm.data(), cfg.classes, cfg.fpr_variant == 2 ? 2 : 0);
+    // Operating-point read-out (opt-in): the weights are final here -- the restored snapshot, the finalised average or the last
+    // epoch -- so one predict over the validation split gives the scores a deployed model would give; always against the true
+    // labels (the y_true quirk belongs to the arg-max FPR above).  Off: nothing is launched or allocated
+    if (opoint_enabled(net.opoint())) {
+        float* d_probs = pool.get<float>((size_t)ds.n_val * cfg.classes * 4);
+        net.predict(ds.x_val, ds.n_val, d_probs);
+        std::vector<OpointClass> classes(cfg.classes);
+        operating_point(d_probs, ds.y_val, ds.n_val, cfg.classes, net.opoint().recall, classes.data(), res.opoint, stream);
+        net.store_opoint(classes.data(), res.opoint);
+    } else {
+        net.store_opoint(nullptr, nullptr);
+    }
     res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return res;
 }

@@ -49,6 +49,9 @@ class TrainedModel:
     frontend: Optional[FrontendConfig] = None
     mean: Optional[np.ndarray] = None  # StandardScaler of the training features, float64 [F]
     scale: Optional[np.ndarray] = None
+    # one detection threshold per class, float32 [classes]: the operating point of the validation split under
+    # EvalConfig.operating_point (opoint.py), what detect_events takes; None when the model was trained without it
+    thresholds: Optional[np.ndarray] = None
 
     def __post_init__(self):
         self.gene = tuple(int(v) for v in self.gene)
@@ -66,6 +69,10 @@ class TrainedModel:
             self.scale = np.ascontiguousarray(self.scale, np.float64).reshape(-1)
             if self.mean.size != self.F or self.scale.size != self.F:
                 raise ValueError(f"mean and scale must hold F = {self.F} values each")
+        if self.thresholds is not None:
+            self.thresholds = np.ascontiguousarray(self.thresholds, np.float32).reshape(-1)
+            if self.thresholds.size != int(self.classes):
+                raise ValueError(f"thresholds must hold classes = {self.classes} values")
         self.objectives = {k: (int(self.objectives[k]) if k == "epochs_run" else float(self.objectives[k]))
                            for k in _OBJECTIVE_KEYS if k in self.objectives}
 
@@ -85,7 +92,7 @@ class TrainedModel:
         ``frontend_float`` as ever; ``frontend_scale`` (index into log / db / power / pcen) only for a power or PCEN
         front end, whose ``frontend_int[5]`` is 0; ``frontend_pcen`` (s, alpha, delta, r, eps, input_scale) only when
         the front end carries a ``PcenConfig``.  A model without a front end, or with a log or dB one, writes the keys
-        it always wrote."""
+        it always wrote.  ``thresholds`` (float32 [classes]) only when the model carries them."""
         d = {"gene": np.asarray(self.gene, np.int32),
              "meta": np.asarray([G.VARIANT_NAMES[self.variant], self.classes, self.T, self.F, self.seed], np.int64),
              "params": self.params,
@@ -103,6 +110,8 @@ class TrainedModel:
                 d["frontend_pcen"] = np.asarray([getattr(fe.pcen, k) for k in _PCEN_FIELDS], np.float64)
         if self.mean is not None:
             d["mean"], d["scale"] = self.mean, self.scale
+        if self.thresholds is not None:
+            d["thresholds"] = self.thresholds
         with open(path, "wb") as f:
             np.savez(f, **d)
 
@@ -124,8 +133,10 @@ class TrainedModel:
                                     **dict(zip(_FE_FLOAT, ff)), pcen=pcen)
             mean = z["mean"].copy() if "mean" in z.files else None
             scale = z["scale"].copy() if "scale" in z.files else None
+            thresholds = z["thresholds"].copy() if "thresholds" in z.files else None
             return cls(gene=tuple(int(v) for v in z["gene"]), variant=G.VARIANT_CODES[variant], classes=classes, T=T, F=F, seed=seed,
-                       params=z["params"].copy(), objectives=obj, frontend=fe, mean=mean, scale=scale)
+                       params=z["params"].copy(), objectives=obj, frontend=fe, mean=mean, scale=scale,
+                       thresholds=thresholds)
 
     def session(self, config: Optional[EvalConfig] = None):
         """A ``NetSession`` holding these parameters (needs the GPU).  ``config`` supplies ``eval_batch`` and the like;
@@ -199,10 +210,12 @@ def smooth_posteriors(p, w: int) -> np.ndarray:
     return out
 
 
-def detect_events(t, p, threshold: float, keyword_classes: Sequence[int], refractory_windows: int) -> List[Tuple[float, int, float]]:
+def detect_events(t, p, threshold, keyword_classes: Sequence[int], refractory_windows: int) -> List[Tuple[float, int, float]]:
     """[(t[i], class, score)]: scan the windows in order; outside a refractory span, when the largest posterior among
     ``keyword_classes`` reaches ``threshold`` emit that class (ties: the lowest class id) and skip the next
-    ``refractory_windows`` windows."""
+    ``refractory_windows`` windows.  ``threshold`` is one scalar for every class, or one value per class -- a sequence of
+    length ``classes``, ``TrainedModel.thresholds`` for one: each keyword class is then compared with its own threshold, and
+    the emitted class is the largest posterior among those that reach theirs (ties: the lowest class id)."""
     t, p = np.asarray(t, np.float64).reshape(-1), np.asarray(p, np.float64)
     if p.ndim != 2 or len(t) != len(p):
         raise ValueError("detect_events expects t [n] and p [n, classes]")
@@ -212,6 +225,21 @@ def detect_events(t, p, threshold: float, keyword_classes: Sequence[int], refrac
     if int(refractory_windows) < 0:
         raise ValueError("refractory_windows must not be negative")
     events, i = [], 0
+    if np.ndim(threshold) != 0:
+        thr = np.asarray(threshold, np.float64).reshape(-1)
+        if thr.size != p.shape[1]:
+            raise ValueError(f"per-class thresholds must hold classes = {p.shape[1]} values")
+        thr = thr[kw]
+        while i < len(p):
+            scores = p[i, kw]
+            reach = scores >= thr
+            if reach.any():
+                j = int(np.argmax(np.where(reach, scores, -np.inf)))     # first maximum among those that reach = lowest class id
+                events.append((float(t[i]), kw[j], float(scores[j])))
+                i += 1 + int(refractory_windows)
+            else:
+                i += 1
+        return events
     while i < len(p):
         scores = p[i, kw]
         j = int(np.argmax(scores))          # first maximum = lowest class id

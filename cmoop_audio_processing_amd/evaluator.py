@@ -38,6 +38,7 @@ from .loss import LossConfig
 from .distill import DistillConfig, check_teacher_table, require_teacher
 from .optim import OptimConfig
 from .ema import EmaConfig
+from .opoint import OperatingPointConfig
 
 FPR_CODES = {"v1": 0, "v1_quirk": 1, "v3": 2}
 ACC_CODES = {"last": 0, "evaluate": 1}
@@ -98,6 +99,11 @@ class EvalConfig:
     # None or momentum 0 = off, every number as without the field (cmoop_net_set_ema).  It travels beside option_structs'
     # four-tuple, as ema_struct()
     ema: Optional[EmaConfig] = None
+    # operating-point read-out of every candidate (opoint.py): the FPR at the threshold that still catches `recall` of each
+    # class, the AUC and the thresholds themselves, from one more inference pass after the fit.  None or recall 0 = off, every
+    # number, row and dict as without the field (cmoop_net_set_opoint).  It only adds numbers, unless objective=True, which
+    # puts fpr_at_recall in the place of the arg-max FPR in the objectives.  Travels beside ema_struct(), as opoint_struct()
+    operating_point: Optional[OperatingPointConfig] = None
 
     @staticmethod
     def preset(script: str, **over) -> "EvalConfig":
@@ -168,6 +174,12 @@ class EvalConfig:
         if self.ema is None or not self.ema.enabled:
             return None
         return self.ema.check()._struct()
+
+    def opoint_struct(self) -> Optional["_lib.Opoint"]:
+        """The enabled operating-point read-out as a ``cmoop_opoint``, checked; None when it is off."""
+        if self.operating_point is None or not self.operating_point.enabled:
+            return None
+        return self.operating_point.check()._struct()
 
     def option_structs(self, T: int, F: int, teacher_logits, n_train: int):
         """(augment, loss, distill, optim) of a fit on [T, F] patches against ``teacher_logits``: the four ``*_struct``
@@ -428,16 +440,22 @@ class PopulationEvaluator:
         d.T, d.F = self.T, self.F
         return d
 
-    def _population_call(self, genes, sd, n, cfg, next_cb, acc, size, fpr, ep, secs, done) -> None:
-        """THE population call: ``cmoop_eval_population_avg`` with ``config.option_structs`` and ``config.ema_struct`` by
-        reference, None (NULL) for whatever is off; next_cb None: the library's own longest-first counter, and ``done`` is
-        then None too."""
+    def _population_call(self, genes, sd, n, cfg, next_cb, acc, size, fpr, ep, secs, done, op=None) -> None:
+        """THE population call: ``cmoop_eval_population_op`` with ``config.option_structs``, ``config.ema_struct`` and
+        ``config.opoint_struct`` by reference, None (NULL) for whatever is off; next_cb None: the library's own longest-first
+        counter, and ``done`` is then None too.  ``op``: float64 [n, 4] for the operating-point summaries, or None."""
         ds = self._dataset()
-        opts = self.config.option_structs(self.T, self.F, self.teacher_logits, len(self.X_train)) + (self.config.ema_struct(),)
-        _lib.check(_lib.lib().cmoop_eval_population_avg(
+        opts = self.config.option_structs(self.T, self.F, self.teacher_logits, len(self.X_train)) + \
+            (self.config.ema_struct(), self.config.opoint_struct())
+        _lib.check(_lib.lib().cmoop_eval_population_op(
             C.byref(cfg), *(C.byref(o) if o is not None else None for o in opts), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
             C.c_int32(n), C.cast(next_cb, C.c_void_p) if next_cb is not None else None, None, _lib.ptr(acc), _lib.ptr(size),
-            _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done)))
+            _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done), _lib.ptr(op)))
+
+    @property
+    def row_width(self) -> int:
+        """Values per candidate of ``evaluate_genes`` / ``evaluate_genes_pull``: 5, or 9 with the operating-point read-out on."""
+        return 9 if self.config.opoint_struct() is not None else 5
 
     @staticmethod
     def _population_arrays(gene_list, seeds):
@@ -451,25 +469,32 @@ class PopulationEvaluator:
         return genes, sd, acc, size, fpr, secs, np.zeros(n, np.int32)
 
     def evaluate_genes(self, gene_list: Sequence[Sequence[int]], seeds: Sequence[int]) -> np.ndarray:
-        """[n,6] genes -> float64 [n,5] = (accuracy, size_mb, fpr, epochs_run, seconds) on THIS GPU."""
+        """[n,6] genes -> float64 [n,5] = (accuracy, size_mb, fpr, epochs_run, seconds) on THIS GPU; with
+        ``config.operating_point`` on, [n,9]: (fpr_at_recall, recall_achieved, auc, classes_scored) appended."""
         n = len(gene_list)
-        out = np.zeros((n, 5), dtype=np.float64)
+        width = self.row_width
+        out = np.zeros((n, width), dtype=np.float64)
         if n == 0:
             return out
         genes, sd, acc, size, fpr, secs, ep = self._population_arrays(gene_list, seeds)
-        self._population_call(genes, sd, n, self.config.to_struct(), None, acc, size, fpr, ep, secs, None)
+        op = np.zeros((n, 4), np.float64) if width == 9 else None
+        self._population_call(genes, sd, n, self.config.to_struct(), None, acc, size, fpr, ep, secs, None, op)
         out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4] = acc, size, fpr, ep, secs
+        if op is not None:
+            out[:, 5:9] = op
         return out
 
     def evaluate_genes_pull(self, gene_list: Sequence[Sequence[int]], seeds: Sequence[int], pull: Callable[[], int],
                             workers: Optional[int] = None) -> Dict[int, np.ndarray]:
         """Train the candidates ``pull()`` hands to this GPU's worker threads (``workers`` of them, default cfg.n_slots,
-        call it concurrently, from C++); returns {index: (accuracy, size_mb, fpr, epochs_run, seconds)}."""
+        call it concurrently, from C++); returns {index: (accuracy, size_mb, fpr, epochs_run, seconds)}, each row with the
+        four operating-point numbers appended when ``config.operating_point`` is on, as in ``evaluate_genes``."""
         n = len(gene_list)
         if n == 0:
             return {}
         genes, sd, acc, size, fpr, secs, ep = self._population_arrays(gene_list, seeds)
         done = np.zeros(n, np.int32)
+        op = np.zeros((n, 4), np.float64) if self.row_width == 9 else None
         cfg = self.config.to_struct()
         if workers is not None:
             cfg.n_slots = max(1, int(workers))
@@ -481,10 +506,11 @@ class PopulationEvaluator:
             except BaseException as e:      # never let an exception cross the C boundary: end this worker, re-raise below
                 errors.append(e)
                 return -1
-        self._population_call(genes, sd, n, cfg, _lib.NEXT_FN(_next), acc, size, fpr, ep, secs, done)
+        self._population_call(genes, sd, n, cfg, _lib.NEXT_FN(_next), acc, size, fpr, ep, secs, done, op)
         if errors:
             raise errors[0]
-        return {int(i): np.array([acc[i], size[i], fpr[i], ep[i], secs[i]], dtype=np.float64) for i in np.nonzero(done)[0]}
+        return {int(i): np.array([acc[i], size[i], fpr[i], ep[i], secs[i]] + ([] if op is None else list(op[i])), dtype=np.float64)
+                for i in np.nonzero(done)[0]}
 
     # -- the reference's surface ------------------------------------------------
     def evaluate_individual(self, hparams: Dict):
@@ -507,24 +533,25 @@ class PopulationEvaluator:
         dist = _dist()
         multi = _multi(dist)
         self._generation += 1
+        w = self.row_width + 1     # a candidate's row and the rank that trained it
         if not n:
-            res = np.zeros((0, 6))
+            res = np.zeros((0, w))
             if multi:   # keep the SPMD ranks in step: the empty generation still does its (empty) exchange
-                queued_map(lambda pull: {}, [], 6, f"{self._queue_prefix}/{self._generation}", device="cuda")
+                queued_map(lambda pull: {}, [], w, f"{self._queue_prefix}/{self._generation}", device="cuda")
         elif not multi:
             res = np.concatenate([self.evaluate_genes(gl, seeds), np.zeros((n, 1))], axis=1)
         elif self.config.schedule == "static":     # LPT buckets by closed-form FLOPs (fixed-epoch throughput runs)
             rank = float(dist.get_rank())
             res = sharded_map(lambda idx: np.concatenate([self.evaluate_genes([gl[i] for i in idx], [seeds[i] for i in idx]),
-                                                          np.full((len(idx), 1), rank)], axis=1), costs, 6, device="cuda")
+                                                          np.full((len(idx), 1), rank)], axis=1), costs, w, device="cuda")
         else:                                       # one longest-first queue drained by all ranks (default)
             rank = float(dist.get_rank())
             self.last_queue_stats = {}
             res = queued_map(lambda pull, workers: {i: np.append(r, rank)
                                                     for i, r in self.evaluate_genes_pull(gl, seeds, pull, workers).items()},
-                             costs, 6, f"{self._queue_prefix}/{self._generation}", device="cuda", slots=self.config.n_slots,
+                             costs, w, f"{self._queue_prefix}/{self._generation}", device="cuda", slots=self.config.n_slots,
                              stats=self.last_queue_stats)
-        self.last_rank_of = [int(r) for r in res[:, 5]]
+        self.last_rank_of = [int(r) for r in res[:, w - 1]]
         self.last_seeds = [int(sd) for sd in seeds]
         self.evals_done += n
         self.last_epochs_run = [int(e) for e in res[:, 3]]
@@ -534,7 +561,7 @@ class PopulationEvaluator:
         for ind, r in zip(population, res):
             acc, size_mb, fpr = float(r[0]), float(r[1]), float(r[2])
             self._print(r)
-            results.append(pack_result(ind, acc, size_mb, fpr, c))
+            results.append(pack_result(ind, acc, size_mb, fpr, c, r[5:9] if w == 10 else None))
         return results
 
     def train_model(self, hparams, seed: int, frontend=None, mean=None, scale=None):
@@ -557,17 +584,24 @@ class PopulationEvaluator:
         v = G.VARIANT_NAMES[self.config.variant]
         objectives = {"acc": float(r["acc"]), "size_mb": float(G.model_size_mb(g, v, self.config.classes)), "fpr": float(r["fpr"]),
                       "epochs_run": int(r["epochs_run"])}
+        thresholds = r["operating_point"]["thresholds"] if "operating_point" in r else None     # config.operating_point on
         return TrainedModel(gene=g, variant=self.config.variant, classes=int(self.config.classes), T=self.T, F=self.F,
-                            seed=int(seed), params=params, objectives=objectives, frontend=frontend, mean=mean, scale=scale)
+                            seed=int(seed), params=params, objectives=objectives, frontend=frontend, mean=mean, scale=scale,
+                            thresholds=thresholds)
 
     def _print(self, r):
         if self.config.verbose:
             print(f"  -> True Eval: Acc={r[0]:.4f}, Size={r[1]:.2f}MB, FPR={r[2]:.4f}")
 
 
-def pack_result(ind: Dict, acc: float, size_mb: float, fpr: float, c: EvalConfig) -> Dict:
+def pack_result(ind: Dict, acc: float, size_mb: float, fpr: float, c: EvalConfig, opoint=None) -> Dict:
     """One entry of compute_objectives_and_constraints' result list, in the schema of the script ``c.objectives`` names
-    (holding a REFERENCE to the caller's hparams dict, as nsga_penalty.py:438 does)."""
+    (holding a REFERENCE to the caller's hparams dict, as nsga_penalty.py:438 does).  ``opoint``: the candidate's four
+    operating-point numbers (``c.operating_point`` on), else None and the dict is the reference's, key for key.  With them the
+    dict gains ``"operating_point"``; with ``operating_point.objective`` as well, ``fpr_at_recall`` takes the place of the
+    arg-max ``fpr`` in ``objs`` / ``fpr_metric`` and in the FPR constraint, and the arg-max value stays as ``"fpr_argmax"``."""
+    if opoint is not None:
+        return _pack_opoint(ind, acc, size_mb, fpr, c, [float(v) for v in opoint])
     g1 = max(0.0, c.min_accuracy - acc)
     g2 = max(0.0, size_mb - c.max_model_size)
     g3 = max(0.0, fpr - c.max_fpr)
@@ -580,6 +614,15 @@ def pack_result(ind: Dict, acc: float, size_mb: float, fpr: float, c: EvalConfig
     if c.objectives == "size_fpr":
         return {"hparams": ind, "acc_metric": acc, "objs": [size_mb, fpr], "CV": g2 + g3}
     raise ValueError(f"unknown objectives {c.objectives!r}")
+
+
+def _pack_opoint(ind: Dict, acc: float, size_mb: float, fpr: float, c: EvalConfig, op) -> Dict:
+    as_objective = c.operating_point is not None and bool(c.operating_point.objective)
+    d = pack_result(ind, acc, size_mb, op[0] if as_objective else fpr, c)
+    d["operating_point"] = {"fpr_at_recall": op[0], "recall_achieved": op[1], "auc": op[2], "classes_scored": int(op[3])}
+    if as_objective:
+        d["fpr_argmax"] = fpr
+    return d
 
 
 class AudioNASProblem:

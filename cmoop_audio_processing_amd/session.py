@@ -27,9 +27,9 @@ class NetSession:
         _lib.check(_lib.lib().cmoop_net_total_params(self._h, C.byref(n)))
         self.n_params = int(n.value)
         self.T, self.F = int(T), int(F)
-        self.augment = self.loss = self.optim = self.ema = None
+        self.augment = self.loss = self.optim = self.ema = self.opoint = None
         for name, setter in (("augment", self.set_augment), ("loss", self.set_loss), ("optim", self.set_optim),
-                             ("ema", self.set_ema)):
+                             ("ema", self.set_ema), ("operating_point", self.set_operating_point)):
             if getattr(config, name, None) is not None:
                 try:
                     setter(getattr(config, name))
@@ -141,6 +141,45 @@ class NetSession:
     def finalize_ema(self) -> None:
         """parameters := average (Keras' ``finalize_variable_values``); ``fit`` does this itself."""
         _lib.check(_lib.lib().cmoop_net_finalize_ema(self._h))
+
+    def set_operating_point(self, opoint) -> None:
+        """Operating-point read-out (``OperatingPointConfig``) of every following ``fit`` of this net.  None or recall 0 turns
+        it off (``self.opoint`` is then None), and ``fit`` is launch for launch the one of a net that never had it.  On, ``fit``
+        changes none of its numbers and gains the key ``"operating_point"``: after the weights are final, one more inference
+        pass over the validation split and the read-out of it (``operating_point`` below, at the config's recall)."""
+        self._set("cmoop_net_set_opoint", None if opoint is None else opoint.check()._struct())
+        self.opoint = opoint if opoint is not None and opoint.enabled else None
+
+    def operating_point(self, X, y, recall=None) -> dict:
+        """X: CUDA float32 [n, T, F], y: CUDA int32 [n] -> the read-out of ``predict_proba(X)`` against ``y`` at ``recall``
+        (default: the recall of ``set_operating_point``): dict(thresholds float32 [classes], tp, fp, positives, negatives, k
+        int32 [classes], u2 int64 [classes], fpr_at_recall, recall_achieved, auc, classes_scored, summary float64 [4]).
+        Equal, value for value, to ``opoint.operating_point_reference(predict_proba(X), y, recall)``."""
+        import torch
+        from . import opoint as OP
+        if recall is None:
+            if self.opoint is None:
+                raise ValueError("operating_point: no recall given and the session has no operating-point config")
+            recall = self.opoint.recall
+        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 3):
+            raise ValueError("operating_point expects a CUDA float32 tensor [n, T, F]")
+        if (int(X.shape[1]), int(X.shape[2])) != (self.T, self.F):
+            raise ValueError(f"operating_point: rows are {int(X.shape[1])} x {int(X.shape[2])}, the net reads {self.T} x {self.F}")
+        if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.int32 and y.dim() == 1 and len(y) == len(X)):
+            raise ValueError("operating_point expects CUDA int32 labels [n]")
+        X, y = X.contiguous(), y.contiguous()
+        st = OP.OperatingPointConfig(recall=float(recall)).check()._struct()
+        rec, summary = (_lib.OpointClass * int(self.config.classes))(), (C.c_double * 4)()
+        torch.cuda.synchronize()
+        _lib.check(_lib.lib().cmoop_net_operating_point(self._h, _lib.ptr(X), _lib.ptr(y), C.c_int64(len(X)), C.byref(st), rec, summary))
+        return OP.from_records(rec, summary)
+
+    def last_operating_point(self) -> dict:
+        """The read-out the last ``fit`` recorded (``cmoop_net_last_opoint``); raises when that fit ran without the option."""
+        from . import opoint as OP
+        rec, summary = (_lib.OpointClass * int(self.config.classes))(), (C.c_double * 4)()
+        _lib.check(_lib.lib().cmoop_net_last_opoint(self._h, rec, summary))
+        return OP.from_records(rec, summary)
 
     def optim_stats(self) -> dict:
         """The last train step's optimiser read-out: dict(sumsq, norm, scale, path) -- the float64 sum of squares of the
@@ -310,7 +349,8 @@ class NetSession:
 
     def fit(self, X_train, y_train, X_val, y_val):
         """evaluate_individual's fit + read-outs on this net -> dict(acc, fpr, val_loss, epochs_run, best_epoch,
-        val_loss_history, val_accuracy_history)."""
+        val_loss_history, val_accuracy_history), and ``operating_point`` (the dict of ``operating_point``, of the validation
+        split under the final weights) when ``set_operating_point`` is on."""
         self._require_teacher()
         import torch
         torch.cuda.synchronize()
@@ -325,8 +365,11 @@ class NetSession:
         _lib.check(_lib.lib().cmoop_net_fit(self._h, C.byref(d), C.c_int32(cap), _lib.ptr(hl), _lib.ptr(ha), C.byref(ep), C.byref(be),
                                             C.byref(acc), C.byref(fpr), C.byref(vl)))
         n = int(ep.value)
-        return {"acc": acc.value, "fpr": fpr.value, "val_loss": vl.value, "epochs_run": n, "best_epoch": int(be.value),
-                "val_loss_history": hl[:n].copy(), "val_accuracy_history": ha[:n].copy()}
+        out = {"acc": acc.value, "fpr": fpr.value, "val_loss": vl.value, "epochs_run": n, "best_epoch": int(be.value),
+               "val_loss_history": hl[:n].copy(), "val_accuracy_history": ha[:n].copy()}
+        if self.opoint is not None:
+            out["operating_point"] = self.last_operating_point()
+        return out
 
     def train_metrics(self, reset=True):
         ls, corr = C.c_double(), C.c_int64()

@@ -96,11 +96,11 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 
 /* compute_objectives_and_constraints' inner loop (nsga_penalty.py:426-427): evaluate n
  * candidates; outputs are host arrays of length n (any may be NULL).
- * THE POPULATION CALL.  The seven cmoop_eval_population* symbols are ONE call, cmoop_eval_population_avg, each with fewer
+ * THE POPULATION CALL.  The eight cmoop_eval_population* symbols are ONE call, cmoop_eval_population_op, each with fewer
  * of its arguments: next (with ctx and evaluated; NULL: the library's own longest-first queue, evaluated may then be
- * NULL too) and the five training options aug, loss, distill, optim, ema (cmoop_augment, cmoop_loss, cmoop_distill,
- * cmoop_optim, cmoop_ema below, checked in that order).  An option that is NULL or disabled gives exactly -- launch for launch,
- * bit for bit -- the call without it, so a caller may always take _avg and pass NULL for what is off. */
+ * NULL too) and the six options aug, loss, distill, optim, ema, op (cmoop_augment, cmoop_loss, cmoop_distill,
+ * cmoop_optim, cmoop_ema, cmoop_opoint below, checked in that order).  An option that is NULL or disabled gives exactly -- launch
+ * for launch, bit for bit -- the call without it, so a caller may always take _op and pass NULL for what is off. */
 int cmoop_eval_population(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
                           const uint32_t* seeds /* [n] */, int32_t n, double* acc, double* size_mb, double* fpr,
                           int32_t* epochs_run, double* val_loss, double* seconds);
@@ -361,11 +361,72 @@ int cmoop_ema_rates(const cmoop_ema* ema, int64_t iteration, double* m, float* m
 /* the kernel alone on the library stream: a_dev [n] advanced against w_dev [n] at the rates of `iteration`; kinds_dev [n]
  * bytes (NULL: every element trainable).  Reads w, a and kinds, writes a only. */
 int cmoop_ema_update(const cmoop_ema* ema, int64_t iteration, float* a_dev, const float* w_dev, const uint8_t* kinds_dev, int64_t n);
-/* the population call (above) with every argument: the other six forward here */
+/* the population call (above) with every argument but the operating point: forwards to cmoop_eval_population_op with NULL, NULL */
 int cmoop_eval_population_avg(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
                               const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
                               const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
                               double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated);
+
+/* ---- operating-point read-out: FPR at a target recall, AUC, one threshold per class (opt-in, off by default).
+ * BUILD-DEFINED: the reference scores arg-max predictions only (calculate_fpr, which stays the third objective); with no opoint
+ * config, or a disabled one, every launch and every bit is that of a build without it.  The read-out only ADDS numbers: with it
+ * on, acc, size_mb, fpr, epochs_run and val_loss are still the bytes of the fit without it.
+ * Inputs: scores p[n][C] float32 row-major (in the trainer: cmoop_net_predict's output on the validation split with the final
+ * weights), labels y[n] int32 -- always the TRUE labels; fpr_variant and its y_true quirk belong to the arg-max FPR only.
+ * 1 <= C <= 64, 0 <= n <= 262144 (n^2 compares, as cmoop_epoch_permutation_device); beyond it is an error naming the bound.
+ * Everything below is defined in integers and tested for equality:
+ *   Order        key(s) = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000), b the IEEE bits of s as uint32: a total order on bit patterns,
+ *                -0 < +0, positive NaNs above +inf, negative NaNs below -inf.  No value is special-cased.
+ *   One-vs-rest  row j is positive for class c iff y[j] == c; a label outside [0, C) is negative for every class.
+ *                P_c = positives, N_c = n - P_c.
+ *   Counts       cnt[c][i][0..3] = ge_pos, ge_neg, gt_pos, gt_neg: the rows j with key(p[j][c]) >= key(p[i][c]) that are
+ *                positive, the same for negative rows, then both again with >.  Row i counts itself in ge.
+ *   Per class with P_c >= 1 (a "scored" class):
+ *     U2_c  = sum over positive i of 2 (N_c - ge_neg_i) + (ge_neg_i - gt_neg_i), int64: twice the Mann-Whitney U, ties at 1/2
+ *     k_c   = min(P_c, max(1, (int)ceil(recall * (double)P_c))): one double product, one ceil
+ *     among positives i with ge_pos_i >= k_c the one with the largest key: thr_c = its score, TP_c = its ge_pos, FP_c = its
+ *     ge_neg (both counts are monotone in the key: they are the minima over that set).  A detector that fires on
+ *     p[.][c] >= thr_c catches TP_c of the P_c positives and raises FP_c false alarms on these rows.
+ *   A class with P_c = 0: thr = +inf, TP = FP = k = 0, U2 = 0.
+ *   Summary, float64, sums left to right in class order, as double[4]:
+ *     [0] fpr_at_recall    mean over scored classes of (N_c > 0 ? FP_c / N_c : 0.0); 0.0 when no class is scored
+ *     [1] recall_achieved  mean over scored classes of TP_c / P_c; 0.0 when no class is scored
+ *     [2] macro_auc        mean over classes with P_c >= 1 and N_c >= 1 of U2_c / (2.0 * P_c * N_c); NaN when there is none
+ *     [3] n_scored
+ * Domain: 0 <= recall <= 1 and finite, objective in {0, 1}, reserved 0.  A config is ENABLED iff recall > 0.  objective is read
+ * by the host layers only (1: the evaluator puts fpr_at_recall in the place of the arg-max FPR); the library checks it. */
+typedef struct cmoop_opoint {
+    double  recall;     /* target recall per class, 0 <= recall <= 1; 0 = off */
+    int32_t objective;  /* 0 / 1 */
+    int32_t reserved;   /* 0 */
+} cmoop_opoint;         /* 16 bytes */
+typedef struct cmoop_opoint_class {
+    int64_t u2;
+    int32_t P, N, k, tp, fp;
+    float   thr;
+} cmoop_opoint_class;   /* 32 bytes */
+int cmoop_opoint_default(cmoop_opoint* op);   /* off: all zero */
+/* host-only: non-zero + a message naming the offending field (recall, objective, reserved) when the config is outside the domain */
+int cmoop_opoint_check(const cmoop_opoint* op);
+/* the key and count kernels alone, on the library stream: counts_dev [C][n][4] int32 from probs_dev [n][C] and y_dev [n] */
+int cmoop_roc_counts(const float* probs_dev, const int32_t* y_dev, int64_t n, int32_t C, int32_t* counts_dev /* [C][n][4] */);
+/* the three launches (keys, counts, select) on the library stream and the float64 finish: classes_host [C], summary [4].
+ * Any config of the domain, enabled or not (recall 0 gives k = 1: the highest-scoring positive) */
+int cmoop_operating_point(const float* probs_dev, const int32_t* y_dev, int64_t n, int32_t C, const cmoop_opoint* op,
+                          cmoop_opoint_class* classes_host /* [C] */, double* summary /* [4] */);
+/* average milliseconds per iteration over `iters` back-to-back iterations between two HIP events on the library stream, after 3
+ * warm-up iterations each: avg_ms [4] = the three launches together, then the key, count and select launch alone.  n >= 1 */
+int cmoop_operating_point_time(const float* probs_dev, const int32_t* y_dev, int64_t n, int32_t C, const cmoop_opoint* op,
+                               int32_t iters, double* avg_ms /* [4] */);
+/* host-only: the float64 finish alone, summary [4] from classes_host [C] */
+int cmoop_opoint_summary(const cmoop_opoint_class* classes_host, int32_t C, double* summary /* [4] */);
+/* the population call (above) with every argument: the other seven forward here.  op NULL or disabled: cmoop_eval_population_avg's
+ * launches and bytes, and opoint (may be NULL) receives zeros; enabled: opoint [n][4] receives every candidate's summary */
+int cmoop_eval_population_op(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                             const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_dataset* ds,
+                             const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next, void* ctx,
+                             double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds,
+                             int32_t* evaluated, double* opoint /* [n][4], may be NULL */);
 
 /* host-only: does every conv layer of this candidate at `batch` rows per launch (pass max(batch, eval_batch)) stay inside
  * the kernels' 32-bit byte offsets (each activation / kernel tensor below 2^29 elements)?  Non-zero + message if not;
@@ -603,6 +664,17 @@ int cmoop_net_use_ema(cmoop_net* net, int32_t on);
 /* w := a (Keras' finalize_variable_values), for callers that step by hand; cmoop_net_fit does it itself.  Adam's moments, the
  * counters and the average stay. */
 int cmoop_net_finalize_ema(cmoop_net* net);
+/* Operating-point read-out (cmoop_opoint above) of every following cmoop_net_fit of this net (NULL or a disabled config: off,
+ * and the fit is launch for launch the one of a net that never had it).  The config is copied.  No train step and no earlier
+ * read-out changes: after the weights are final -- the restored snapshot, the finalised average or the last epoch -- the fit
+ * runs one more cmoop_net_predict pass over the validation split and the three read-out launches. */
+int cmoop_net_set_opoint(cmoop_net* net, const cmoop_opoint* op /* NULL = off */);
+/* the record of the last cmoop_net_fit: classes_host [classes] and summary [4] (either may be NULL); an error when that fit ran
+ * without the option */
+int cmoop_net_last_opoint(cmoop_net* net, cmoop_opoint_class* classes_host, double* summary);
+/* cmoop_net_predict's pass over x_dev [n][T][F] into a pooled buffer, then cmoop_operating_point against y_dev [n] */
+int cmoop_net_operating_point(cmoop_net* net, const float* x_dev, const int32_t* y_dev, int64_t n, const cmoop_opoint* op,
+                              cmoop_opoint_class* classes_host /* [classes] */, double* summary /* [4] */);
 /* cmoop_net_train_step_targets with a teacher row per batch row, q_dev [B][classes], and the distillation loss at
  * (alpha, temperature), whatever cmoop_net_set_distill says. */
 int cmoop_net_train_step_distill_targets(cmoop_net* net, const float* x_rows_dev, const float* t_dev, const float* w_dev,
