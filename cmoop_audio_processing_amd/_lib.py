@@ -75,6 +75,11 @@ class Opoint(C.Structure):
     _fields_ = [("recall", C.c_double), ("objective", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Quant(C.Structure):
+    """cmoop_quant (include/cmoop.h), 16 bytes."""
+    _fields_ = [("bits", C.c_int32), ("objective", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class OpointClass(C.Structure):
     """cmoop_opoint_class (include/cmoop.h), 32 bytes."""
     _fields_ = [("u2", C.c_int64), ("P", C.c_int32), ("N", C.c_int32), ("k", C.c_int32), ("tp", C.c_int32), ("fp", C.c_int32),
@@ -186,6 +191,22 @@ OPOINT_PROTOTYPES = {
 }
 
 
+#: prototypes of the quantisation-aware-training entry points (include/cmoop.h); structs travel as void* (C.byref), None is NULL
+QUANT_PROTOTYPES = {
+    "cmoop_quant_default": [C.c_void_p],
+    "cmoop_quant_check": [C.c_void_p],
+    "cmoop_quant_table": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+    "cmoop_quant_size_bytes": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
+    "cmoop_quantize_weights": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_quantize_weights_time": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int32, C.c_void_p],
+    "cmoop_net_set_quant": [C.c_void_p, C.c_void_p],
+    "cmoop_net_get_quantized": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    # cmoop_eval_population_op with one more struct pointer after op and one more output after opoint
+    "cmoop_eval_population_q": [C.c_void_p] * 11 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 9,
+}
+
+
 #: prototypes of the PCEN entry points (include/cmoop.h); structs travel as void* (C.byref)
 PCEN_PROTOTYPES = {
     "cmoop_pcen_default": [C.c_void_p],
@@ -280,7 +301,7 @@ def lib():
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
         for table in (STREAM_PROTOTYPES, AUGMENT_PROTOTYPES, PCEN_PROTOTYPES, ELEM_PROTOTYPES, LOSS_PROTOTYPES, DENSE_PROTOTYPES,
-                      DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES, OPOINT_PROTOTYPES):
+                      DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES, OPOINT_PROTOTYPES, QUANT_PROTOTYPES):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         _lib = L

@@ -187,6 +187,25 @@ static OpointCfg to_opoint(const cmoop_opoint* p) {
     c.recall = p->recall; c.objective = p->objective; c.reserved = p->reserved;
     return c;
 }
+static_assert(sizeof(cmoop_quant) == 16, "cmoop_quant is part of the ABI");
+static QuantCfg to_quant(const cmoop_quant* q) {
+    CMOOP_REQUIRE(q != nullptr, "quant config is NULL");
+    QuantCfg c;
+    c.bits = q->bits; c.objective = q->objective; c.reserved[0] = q->reserved[0]; c.reserved[1] = q->reserved[1];
+    return c;
+}
+// the finalised table of rows_host [count][5] against an arena of n elements
+static QuantTable to_quant_table(const int64_t* rows, int32_t count, int64_t n) {
+    CMOOP_REQUIRE(count >= 0 && count <= QUANT_MAX_ROWS && (count == 0 || rows), "quant: 0 <= count <= 128 and the rows");
+    QuantTable tab;
+    for (int i = 0; i < count; ++i) {
+        const int64_t* r = rows + 5 * (size_t)i;
+        for (int k = 0; k < 5; ++k) CMOOP_REQUIRE(r[k] >= 0 && r[k] <= QUANT_MAX_ARENA, "quant: a table value is outside [0, 2^31)");
+        tab.rows.push_back(QuantRow{(int32_t)r[0], (int32_t)r[1], (int32_t)r[2], (int32_t)r[3], (int32_t)r[4], 0, 0});
+    }
+    quant_table_finalize(tab, n);
+    return tab;
+}
 // cmoop_opoint_class and OpointClass are one layout (asserted above and field by field here)
 static OpointClass* as_classes(cmoop_opoint_class* c) {
     static_assert(offsetof(cmoop_opoint_class, u2) == offsetof(OpointClass, u2) && offsetof(cmoop_opoint_class, P) == offsetof(OpointClass, P) &&
@@ -197,7 +216,7 @@ static OpointClass* as_classes(cmoop_opoint_class* c) {
 }
 
 // The converted training options of one population call: to_* and the matching *_check of every struct handed in, in the
-// order augment, loss, distill, optim, ema, opoint (what a call with two bad structs reports first); owns what opt points into
+// order augment, loss, distill, optim, ema, opoint, quant (what a call with two bad structs reports first); owns what opt points into
 namespace {
 struct AbiTrainOptions {
     AugmentCfg aug;
@@ -206,15 +225,17 @@ struct AbiTrainOptions {
     OptimCfg optim;
     EmaCfg ema;
     OpointCfg opoint;
+    QuantCfg quant;
     TrainOptions opt;
     AbiTrainOptions(const cmoop_augment* a, const cmoop_loss* l, const cmoop_distill* d, const cmoop_optim* o, const cmoop_ema* e,
-                    const cmoop_opoint* p, const NetConfig& c, const Dataset& ds) {
+                    const cmoop_opoint* p, const cmoop_quant* q, const NetConfig& c, const Dataset& ds) {
         if (a) { aug = to_augment(a); augment_check(aug, ds.T, ds.F); opt.aug = &aug; }
         if (l) { loss = to_loss(l); loss_check(loss, c.classes); opt.loss = &loss; }
         if (d) { distill = to_distill(d); distill_check(distill, c.classes, ds.n_train); opt.distill = &distill; }
         if (o) { optim = to_optim(o); optim_check(optim); opt.optim = &optim; }
         if (e) { ema = to_ema(e); ema_check(ema); opt.ema = &ema; }
         if (p) { opoint = to_opoint(p); opoint_check(opoint); opt.opoint = &opoint; }
+        if (q) { quant = to_quant(q); quant_check(quant); opt.quant = &quant; }
     }
     AbiTrainOptions(const AbiTrainOptions&) = delete;
 };
@@ -328,15 +349,15 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 // every population call; next == NULL: candidates are taken longest-first from a process-local counter; a NULL option: off
 static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss,
                                 const cmoop_distill* distill, const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op,
-                                const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx,
-                                double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds,
-                                int32_t* evaluated, double* opoint) {
+                                const cmoop_quant* q, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n,
+                                cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
+                                double* val_loss, double* seconds, int32_t* evaluated, double* opoint, double* quant) {
     CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
     CMOOP_REQUIRE(n >= 0, "negative population size");
     CMOOP_REQUIRE(!next || evaluated, "NULL argument");
     NetConfig c = to_cfg(cfg);
     const Dataset d = to_dataset(ds);
-    const AbiTrainOptions options(aug, loss, distill, optim, ema, op, c, d);
+    const AbiTrainOptions options(aug, loss, distill, optim, ema, op, q, c, d);
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
@@ -352,6 +373,7 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* au
         if (val_loss) val_loss[i] = r[i].val_loss;
         if (seconds) seconds[i] = r[i].seconds;
         if (opoint) std::memcpy(opoint + 4 * (size_t)i, r[i].opoint, sizeof(r[i].opoint));
+        if (quant) std::memcpy(quant + 2 * (size_t)i, r[i].quant, sizeof(r[i].quant));
     }
 }
 
@@ -413,9 +435,92 @@ int cmoop_eval_population_op(const cmoop_config* cfg, const cmoop_augment* aug, 
                              const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc,
                              double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated,
                              double* opoint) {
+    return cmoop_eval_population_q(cfg, aug, loss, distill, optim, ema, op, nullptr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr,
+                                   epochs_run, val_loss, seconds, evaluated, opoint, nullptr);
+}
+
+int cmoop_eval_population_q(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                            const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_quant* q,
+                            const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx,
+                            double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds,
+                            int32_t* evaluated, double* opoint, double* quant) {
     return guard([&] {
-        eval_population_abi(cfg, aug, loss, distill, optim, ema, op, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run,
-                            val_loss, seconds, evaluated, opoint);
+        eval_population_abi(cfg, aug, loss, distill, optim, ema, op, q, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run,
+                            val_loss, seconds, evaluated, opoint, quant);
+    });
+}
+
+// ---- quantisation-aware training ---------------------------------------------------
+int cmoop_quant_default(cmoop_quant* q) {
+    return guard([&] {
+        CMOOP_REQUIRE(q != nullptr, "quant config is NULL");
+        std::memset(q, 0, sizeof(*q));
+    });
+}
+
+int cmoop_quant_check(const cmoop_quant* q) {
+    return guard([&] { quant_check(to_quant(q)); });
+}
+
+static QuantTable quant_table_of(const int32_t gene[6], int32_t variant, int32_t classes) {
+    CMOOP_REQUIRE(gene != nullptr, "quant_table: NULL gene");
+    NetConfig cfg;
+    cfg.variant = variant; cfg.classes = classes;
+    return quant_table(plan_net(gene, cfg, 26, 10));   // offsets and kernel shapes do not depend on the patch size
+}
+
+int cmoop_quant_table(const int32_t gene[6], int32_t variant, int32_t classes, int64_t* rows, int32_t cap, int32_t* count,
+                      int64_t* total_channels) {
+    return guard([&] {
+        const QuantTable tab = quant_table_of(gene, variant, classes);
+        CMOOP_REQUIRE(rows && cap >= (int32_t)tab.rows.size(), "quant_table: the rows buffer is too small");
+        for (size_t i = 0; i < tab.rows.size(); ++i) {
+            const QuantRow& r = tab.rows[i];
+            const int64_t v[5] = {r.off, r.channels, r.len, r.chan_stride, r.elem_stride};
+            std::memcpy(rows + 5 * i, v, sizeof(v));
+        }
+        if (count) *count = (int32_t)tab.rows.size();
+        if (total_channels) *total_channels = tab.total_channels;
+    });
+}
+
+int cmoop_quant_size_bytes(const int32_t gene[6], int32_t variant, int32_t classes, int32_t bits, int64_t* out) {
+    return guard([&] {
+        CMOOP_REQUIRE(out != nullptr, "quant_size_bytes: NULL output");
+        *out = quant_size_bytes(quant_table_of(gene, variant, classes), param_count(gene, variant, classes), bits);
+    });
+}
+
+// the body of cmoop_quantize_weights(_time): the table uploaded to a pooled buffer, then iters < 0: one launch, else timed launches
+static void quantize_weights_abi(const cmoop_quant* q, const float* w, int64_t n, const int64_t* rows, int32_t count, float* wq,
+                                 int8_t* codes, float* scales, int32_t iters, double* avg_ms) {
+    const QuantCfg c = to_quant(q);
+    quant_check(c);
+    CMOOP_REQUIRE(quant_enabled(c), "quantize_weights: the config is disabled (bits 0)");
+    const QuantTable tab = to_quant_table(rows, count, n);
+    if (tab.blocks == 0) { if (avg_ms) *avg_ms = 0.0; return; }
+    CMOOP_REQUIRE(w && wq, "quantize_weights: NULL arena");
+    hipStream_t s = lib_stream();
+    PoolScope pool(s);
+    QuantRow* rows_dev = pool.get<QuantRow>(tab.rows.size() * sizeof(QuantRow));
+    CMOOP_HIP(hipMemcpyAsync(rows_dev, tab.rows.data(), tab.rows.size() * sizeof(QuantRow), hipMemcpyHostToDevice, s));
+    CMOOP_HIP(hipStreamSynchronize(s));
+    auto once = [&] { launch_quantize_weights(w, wq, codes, scales, tab, rows_dev, c.bits, s); };
+    if (avg_ms) *avg_ms = time_launches(s, iters, once);
+    else once();
+    CMOOP_HIP(hipStreamSynchronize(s));
+}
+
+int cmoop_quantize_weights(const cmoop_quant* q, const float* w_dev, int64_t n, const int64_t* rows_host, int32_t count, float* wq_dev,
+                           int8_t* codes_dev, float* scales_dev) {
+    return guard([&] { quantize_weights_abi(q, w_dev, n, rows_host, count, wq_dev, codes_dev, scales_dev, 0, nullptr); });
+}
+
+int cmoop_quantize_weights_time(const cmoop_quant* q, const float* w_dev, int64_t n, const int64_t* rows_host, int32_t count,
+                                float* wq_dev, int8_t* codes_dev, float* scales_dev, int32_t iters, double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "quantize_weights_time: iters >= 1 and avg_ms");
+        quantize_weights_abi(q, w_dev, n, rows_host, count, wq_dev, codes_dev, scales_dev, iters, avg_ms);
     });
 }
 
@@ -1209,6 +1314,13 @@ int cmoop_net_finalize_ema(cmoop_net* h) {
     });
 }
 int cmoop_net_set_opoint(cmoop_net* h, const cmoop_opoint* op) { return net_set_option(h, "set_opoint", op, to_opoint, &Net::set_opoint); }
+int cmoop_net_set_quant(cmoop_net* h, const cmoop_quant* q) { return net_set_option(h, "set_quant", q, to_quant, &Net::set_quant); }
+int cmoop_net_get_quantized(cmoop_net* h, float* wq_params_host, int8_t* codes_host, float* scales_host) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "get_quantized: NULL net");
+        h->net->get_quantized(wq_params_host, codes_host, scales_host);
+    });
+}
 int cmoop_net_last_opoint(cmoop_net* h, cmoop_opoint_class* classes, double* summary) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "last_opoint: NULL net");

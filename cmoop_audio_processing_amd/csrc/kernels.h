@@ -497,6 +497,42 @@ struct EmaPair { float mf, omf; };   // one entry of the device-state steps' rat
 void launch_ema(float* a, const float* w, const uint8_t* kinds, int64_t n, float mf, float omf, hipStream_t s,
                 const StepState* st = nullptr, const EmaPair* table = nullptr);
 
+// ---------------------------------------------------------------------------
+// Quantisation-aware training (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_quant): symmetric,
+// per-output-channel, weight-only fake quantisation of every KIND_KERNEL tensor, ONE launch for a whole arena (quant.hip).
+// ---------------------------------------------------------------------------
+struct QuantCfg {
+    int bits = 0;                    // 0 = off, else 2 .. 8
+    int objective = 0;               // 1: the evaluator ranks candidates by the quantised size (read by the host layers only)
+    int reserved[2] = {0, 0};
+};
+// host-only: throws with a message naming the offending field
+void quant_check(const QuantCfg& c);
+inline bool quant_enabled(const QuantCfg& c) { return c.bits != 0; }
+inline int quant_qmax(int bits) { return (1 << (bits - 1)) - 1; }
+constexpr int64_t QUANT_MAX_ARENA = ((int64_t)1 << 31) - 1;   // elements: the kernel's index math is 32-bit
+constexpr int QUANT_MAX_ROWS = 128;                           // tensors of one table
+constexpr int QUANT_ROW_CHANNELS = 4;                         // channels per workgroup of a row tensor: one wave64 each
+constexpr int QUANT_LANE_CHANNELS = 256;                      // channels per workgroup of a strided (depthwise) tensor: one lane each
+// One kernel tensor: channel c holds the len elements off + c chan_stride + t elem_stride, t < len.  elem_stride == 1: a row
+// tensor ([C_out][kh][kw][C_in], [out][in]: chan_stride == len), one wave per channel; else a strided one (depthwise
+// [kh][kw][C]: chan_stride 1, elem_stride C), one lane per channel.  scale_off: the tensor's first scale; block0: its first workgroup
+struct QuantRow { int32_t off, channels, len, chan_stride, elem_stride, scale_off, block0; };
+struct QuantTable {
+    std::vector<QuantRow> rows;
+    int32_t blocks = 0, total_channels = 0;
+    int64_t kernel_elems = 0;
+};
+// fills scale_off / block0 / blocks / total_channels / kernel_elems from the first five fields of every row and checks every
+// row against an arena of n elements (n <= QUANT_MAX_ARENA, at most QUANT_MAX_ROWS rows, nothing past the arena)
+void quant_table_finalize(QuantTable& tab, int64_t n);
+// sum over the tensors of ceil(elements bits / 8) + 4 total_channels + 4 (n_params - kernel_elems)
+int64_t quant_size_bytes(const QuantTable& tab, int64_t n_params, int bits);
+// wq / codes / scales of every tensor of the table (rows_dev: tab.rows on the device) from w, as cmoop_quant defines them.
+// codes and scales may be null.  Writes ONLY the tensors' elements of wq and codes, and tab.total_channels scales
+void launch_quantize_weights(const float* w, float* wq, int8_t* codes, float* scales, const QuantTable& tab, const QuantRow* rows_dev,
+                             int bits, hipStream_t s);
+
 // device twin of epoch_permutation (net.h): out[rank of key_i] = i; n <= EPOCH_PERMUTATION_DEVICE_MAX (O(n^2) rank sort)
 constexpr int64_t EPOCH_PERMUTATION_DEVICE_MAX = 262144;
 void launch_epoch_permutation(uint32_t seed, uint32_t epoch, int64_t n, int32_t* out, hipStream_t s);

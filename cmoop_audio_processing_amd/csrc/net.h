@@ -209,9 +209,12 @@ struct NetPlan {
     std::string launch_plan(int batch, int Bmax, int B, bool train) const;
 };
 NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F);
+// host-only: the quantisation table of a plan (kernels.h, QuantTable), one row per KIND_KERNEL tensor in arena order, finalised
+// against plan.n_params: the elements it covers are exactly those param_kinds() calls KIND_KERNEL
+QuantTable quant_table(const NetPlan& plan);
 
 // The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
-// set_distill / set_optim / set_ema / set_opoint say what each does).  The pointees stay the caller's for the length of the call
+// set_distill / set_optim / set_ema / set_opoint / set_quant say what each does).  The pointees stay the caller's for the length of the call
 struct TrainOptions {
     const AugmentCfg* aug = nullptr;
     const LossCfg* loss = nullptr;
@@ -219,6 +222,7 @@ struct TrainOptions {
     const OptimCfg* optim = nullptr;
     const EmaCfg* ema = nullptr;
     const OpointCfg* opoint = nullptr;
+    const QuantCfg* quant = nullptr;
 };
 
 class Net : public GemmHook {
@@ -296,8 +300,24 @@ class Net : public GemmHook {
     // the record of the last fit_and_read_out: classes [cfg.classes] and summary [4]; throws when that fit ran without the option
     void last_opoint(OpointClass* classes, double summary[4]) const;
     void store_opoint(const OpointClass* classes, const double summary[4]);   // classes null: the last fit had none
-    // the enabled ones of o through the six setters above, in that order: augment, loss, distill, optim, ema, opoint.  THE place of "a
-    // disabled config is no config": null or disabled is not applied at all, and the net stays one that never had it
+    // Quantisation-aware training (kernels.h) of every following train step and inference call; null or a disabled config: off,
+    // and every launch and bit is that of a net that never had one (the quantised arena, once allocated, is kept).  Enabled:
+    // the domain is checked; on first use the table is built from the plan and uploaded and the quantised arena allocated.
+    // Every train step then first runs launch_quantize_weights on the latent weights; forward, backward and the flip-transposed
+    // dgrad operands read the kernels from the quantised arena and everything else (biases, gamma, beta, moving statistics --
+    // and BatchNorm's moving-statistics writes) from the parameter arena; the gradients go unchanged to the latent weights
+    // (straight-through).  evaluate / predict / predict_logits / predict_stream run the launch once at their start on the arena
+    // they are about to read (the average under use_average).  The optimiser, Adam's moments, the EMA, get/set_params and the
+    // snapshots keep meaning the latent weights.  The step is no longer captured as a graph
+    void set_quant(const QuantCfg* quant);
+    bool quant_on() const { return quant_on_; }
+    const QuantCfg& quant() const { return quant_cfg_; }
+    // the arena inference would read now, quantised: wq [n_params] (kernels dequantised, every other element copied), codes
+    // [n_params] (0 outside the kernel tensors), scales [the table's total_channels]; any may be null.  Throws while the option is off
+    void get_quantized(float* wq_host, int8_t* codes_host, float* scales_host);
+    int64_t quant_size_bytes();          // kernels.h, at the bits of the config; throws while the option is off
+    // the enabled ones of o through the seven setters above, in that order: augment, loss, distill, optim, ema, opoint, quant.  THE
+    // place of "a disabled config is no config": null or disabled is not applied at all, and the net stays one that never had it
     void set_options(const TrainOptions& o);
     // the last step's {sum of squares, norm, scale, launch path (0 fused, 1 finish + update)}; path 0 computes no norm: 0, 0, 1
     void optim_stats(double out[4]);
@@ -362,6 +382,9 @@ class Net : public GemmHook {
     void drop_graph();                                  // the captured step has the old launch sequence or counters
     void upload_step_state();                           // enqueues the device StepState at (0, step_, iterations_); no-op without one
     void ensure_target_buffers();                       // t / w / primary, allocated by the first enabled set_loss or set_distill
+    void ensure_quant_table();                          // qtab_ from the plan, once (host only)
+    void quantize_now();                                // quant on: wq_ := quantised kernels of the arena forward reads (params_)
+    const float* kernels() const { return quant_on_ ? wq_ : params_; }   // where forward / backward read KIND_KERNEL tensors
     ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
 
@@ -381,6 +404,12 @@ class Net : public GemmHook {
     bool ema_on_ = false;               // train steps advance ema_ after the optimiser launch(es)
     EmaPair* ema_tab_ = nullptr;        // (mf, omf) per iteration, alpha_tab_n_ entries, next to alpha_tab_
     OpointCfg opoint_cfg_;              // set_opoint; the default is off
+    QuantCfg quant_cfg_;                // set_quant; the default is off
+    bool quant_on_ = false;             // steps and inference calls quantise first and read kernels from wq_
+    float* wq_ = nullptr;               // the quantised arena (only kernel elements are ever written or read), first enabled set_quant
+    QuantTable qtab_;                   // host table of the plan's kernel tensors
+    bool qtab_ready_ = false;
+    QuantRow* qtab_dev_ = nullptr;
     std::vector<OpointClass> last_op_classes_;   // store_opoint: empty when the last fit ran without the read-out
     double last_op_summary_[4] = {0, 0, 0, 0};
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;
@@ -436,6 +465,8 @@ struct EvalResult {
     int evaluated = 0;   // 1 when THIS call trained the candidate (always, unless a pull callback handed it to another rank)
     // the operating-point read-out (Net::set_opoint): fpr_at_recall, recall_achieved, macro_auc, n_scored; zeros when it is off
     double opoint[4] = {0, 0, 0, 0};
+    // quantisation-aware training (Net::set_quant): quant_size_bytes / 2^20, bits; zeros when it is off
+    double quant[2] = {0, 0};
 };
 
 // per-epoch record of a fit (tests: the early-stopping decisions are checked against the validation-loss history)

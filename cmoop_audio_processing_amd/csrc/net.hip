@@ -385,6 +385,21 @@ std::vector<uint8_t> NetPlan::param_kinds() const {
     return kinds;
 }
 
+QuantTable quant_table(const NetPlan& plan) {
+    QuantTable tab;
+    for (const Op& op : plan.ops) {
+        CMOOP_REQUIRE(op.w_off <= QUANT_MAX_ARENA, "quant: the arena must stay below 2^31 elements (QUANT_MAX_ARENA)");
+        if (op.kind == OP_CONV1 || op.kind == OP_CONV || op.kind == OP_DENSE) {
+            const int len = op.KS * op.KS * op.Cin;
+            tab.rows.push_back(QuantRow{(int32_t)op.w_off, op.Cout, len, len, 1, 0, 0});
+        } else if (op.kind == OP_DWCONV) {
+            tab.rows.push_back(QuantRow{(int32_t)op.w_off, op.Cin, op.KS * op.KS, 1, op.Cin, 0, 0});
+        }
+    }
+    quant_table_finalize(tab, plan.n_params);
+    return tab;
+}
+
 size_t NetPlan::splitk_floats(int batch, int Bmax) const {
     size_t need = 0;
     for (const Op& op : ops)
@@ -767,6 +782,7 @@ void Net::drain_profile() {
 // ---------------------------------------------------------------------------
 void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
     CMOOP_REQUIRE(B >= 1 && B <= Bmax_, "batch larger than the net was planned for");
+    const float* kern = kernels();   // the parameter arena, or the quantised one (set_quant): kernel tensors only
     for (size_t oi = 0; oi < ops_.size(); ++oi) {
         const Op& op = ops_[oi];
         switch (op.kind) {
@@ -775,7 +791,7 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
             const float* bin = train ? batch_in_ : nullptr;   // the batch is rows 0 .. B of the buffer step_body's augment / mixup launch wrote
             BatchRows first = bin ? BatchRows() : rows;
             if (!train) first.n_rows = 0;
-            launch_conv1_fwd(bin ? bin : X, first, params_ + op.w_off, params_ + op.b_off, acts_[op.out].data, B, T_, F_, op.Cout,
+            launch_conv1_fwd(bin ? bin : X, first, kern + op.w_off, params_ + op.b_off, acts_[op.out].data, B, T_, F_, op.Cout,
                              op.KS, op.relu, stream_, (train && op.feeds_bn) ? red_ws_ : nullptr,
                              (train && op.feeds_bn) ? &fused_stats_blocks_ : nullptr);
             break;
@@ -786,18 +802,18 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
             e.bias = params_ + op.b_off;
             e.relu = op.relu;
             // train && feeds_bn: the BatchNorm batch statistics come with the conv (its epilogue, or the reduction after it)
-            fused_stats_blocks_ = op.conv().forward(acts_[op.in].data, params_ + op.w_off, acts_[op.out].data, B, e,
+            fused_stats_blocks_ = op.conv().forward(acts_[op.in].data, kern + op.w_off, acts_[op.out].data, B, e,
                                                     train && op.feeds_bn, buffers_of(op), stream_, this);
             break;
         }
         case OP_DWCONV:
-            launch_dwconv_fwd(acts_[op.in].data, params_ + op.w_off, acts_[op.out].data, B, op.H, op.W, op.Cin, op.KS, 0, nullptr, stream_);
+            launch_dwconv_fwd(acts_[op.in].data, kern + op.w_off, acts_[op.out].data, B, op.H, op.W, op.Cin, op.KS, 0, nullptr, stream_);
             break;
         case OP_DENSE: {
             const bool drop = train && op.dropout_layer >= 0;
             const DropoutParams dp = dropout_params(cfg_.dropout);
             const uint32_t drop_stream = drop ? DropoutParams::stream(op.dropout_layer) : 0u;
-            launch_dense_fwd(acts_[op.in].data, params_ + op.w_off, params_ + op.b_off, acts_[op.out].data, B, op.Cout, op.Cin,
+            launch_dense_fwd(acts_[op.in].data, kern + op.w_off, params_ + op.b_off, acts_[op.out].data, B, op.Cout, op.Cin,
                              op.relu, drop ? 1 : 0, drop ? rng_prefix(seed_, drop_stream, (uint32_t)step_) : 0u, dp.thr,
                              dp.keep_scale, op.gemm_mode, stream_, drop ? rows.st : nullptr, seed_, drop_stream);
             break;
@@ -850,8 +866,9 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
 
 void Net::backward(const float* X, const BatchRows& rows, int B) {
     slab_segs_.clear();
+    const float* kern = kernels();   // as forward: the gradients formed with it go unchanged to the latent weights (straight-through)
     // dgrad operands: flip-transposed copies of every conv kernel, one launch for the whole net
-    launch_flip_transpose_all(params_, wd_ws_, flip_table_, flip_layers_, flip_max_elems_, stream_);
+    launch_flip_transpose_all(kern, wd_ws_, flip_table_, flip_layers_, flip_max_elems_, stream_);
     for (int oi = (int)ops_.size() - 1; oi >= 0; --oi) {
         const Op& op = ops_[oi];
         switch (op.kind) {
@@ -862,12 +879,12 @@ void Net::backward(const float* X, const BatchRows& rows, int B) {
             const char* du = std::getenv("CMOOP_DENSE_UNFUSED");
             const bool unfused = du && du[0] == '1';
             if (!unfused) {
-                launch_dense_bwd(ia.data, dY, params_ + op.w_off, grads_ + op.w_off, grads_ + op.b_off, ia.grad, B, op.Cout, op.Cin,
+                launch_dense_bwd(ia.data, dY, kern + op.w_off, grads_ + op.w_off, grads_ + op.b_off, ia.grad, B, op.Cout, op.Cin,
                                  op.in_is_relu ? ia.data : nullptr, op.in_mask_scale, op.gemm_mode, stream_);
                 break;
             }
             launch_dense_wgrad(ia.data, dY, grads_ + op.w_off, grads_ + op.b_off, B, op.Cout, op.Cin, op.gemm_mode, stream_);
-            launch_dense_dgrad(dY, params_ + op.w_off, ia.grad, B, op.Cout, op.Cin, op.in_is_relu ? ia.data : nullptr,
+            launch_dense_dgrad(dY, kern + op.w_off, ia.grad, B, op.Cout, op.Cin, op.in_is_relu ? ia.data : nullptr,
                                op.in_mask_scale, op.gemm_mode, stream_);
             break;
         }
@@ -883,7 +900,7 @@ void Net::backward(const float* X, const BatchRows& rows, int B) {
             sg.off = op.w_off;
             L.wgrad(ia.data, dY, grads_ + op.w_off, grads_ + op.b_off, B, buf, op.gemm_mode, stream_, this, &sg);
             if (sg.slab) slab_segs_.push_back(sg);
-            L.dgrad(dY, params_ + op.w_off, ia.grad, B, op.in_is_relu ? ia.data : nullptr, op.in_mask_scale, op.dgrad_accumulate,
+            L.dgrad(dY, kern + op.w_off, ia.grad, B, op.in_is_relu ? ia.data : nullptr, op.in_mask_scale, op.dgrad_accumulate,
                     true, buf, op.gemm_mode, stream_, this);
             break;
         }
@@ -898,7 +915,7 @@ void Net::backward(const float* X, const BatchRows& rows, int B) {
             sg.S = dwconv_wgrad_slices(B, op.H, op.W, op.Cin, op.KS);
             CMOOP_REQUIRE((size_t)sg.S * sg.n <= op.slab_floats, "depthwise slab region");
             slab_segs_.push_back(sg);
-            launch_dwconv_fwd(dY, params_ + op.w_off, ia.grad, B, op.H, op.W, op.Cin, op.KS, 1, op.in_is_relu ? ia.data : nullptr, stream_);
+            launch_dwconv_fwd(dY, kern + op.w_off, ia.grad, B, op.H, op.W, op.Cin, op.KS, 1, op.in_is_relu ? ia.data : nullptr, stream_);
             break;
         }
         case OP_BN: {
@@ -959,6 +976,7 @@ void Net::step_body(const float* X, const int32_t* y, const BatchRows& rows, int
                   std::to_string(kd_rows_) + " rows, the training split " + std::to_string(gather_rows_));
     // augmentation on: the batch's rows are gathered and augmented into aug_buf_ first (rows.st != null: the kernel reads
     // the batch position and the step from the device state, so a replayed graph draws for the step it replays)
+    quantize_now();   // quant on: the step's first launch, on the latent weights of this moment
     if (aug_on_) launch_augment_gather(X, rows, aug_buf_, B, T_, F_, aug_, seed_, (uint32_t)step_, stream_);
     // mixup on: the (augmented) rows are blended into mix_buf_ next; each row keeps its own batch position's augmentation
     // (from the augment buffer the launch takes only the step from rows.st: the buffer always starts at its row 0)
@@ -1058,6 +1076,7 @@ void Net::targets_step(const float* x_rows, const float* t, const float* w, cons
     batch_in_ = nullptr;
     const BatchRows rows;      // x_rows holds exactly the B rows of this step: no resident tensor to clamp into
     float *z = acts_[logits_].data, *dz = acts_[logits_].grad;
+    quantize_now();
     forward(x_rows, rows, B, true);
     if (kd) launch_softmax_ce_distill(z, t, w, primary, q, *kd, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
     else launch_softmax_ce_soft(z, t, w, primary, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
@@ -1100,7 +1119,7 @@ void Net::begin_fit(int64_t total_steps) {
     // steps/s replayed vs 2 625 launched eagerly (its stream is kept busy either way: ~50 kernels of ~8 us per step,
     // the host launches faster than that), and the pop-40 bench is 1.5 % slower replayed (2 089 vs 2 121 evals/h).
     static const bool use_graph = [] { const char* v = std::getenv("CMOOP_GRAPH"); return v && v[0] == '1'; }();
-    if (!use_graph || optim_finish_ || ema_on_) graph_ok_ = false;
+    if (!use_graph || optim_finish_ || ema_on_ || quant_on_) graph_ok_ = false;
 }
 
 // the per-iteration rates of the device-state steps, from the one host function the explicit-argument steps use
@@ -1151,6 +1170,7 @@ void Net::set_options(const TrainOptions& o) {
     if (o.optim && optim_enabled(*o.optim)) set_optim(o.optim);
     if (o.ema && ema_enabled(*o.ema)) set_ema(o.ema);
     if (o.opoint && opoint_enabled(*o.opoint)) set_opoint(o.opoint);
+    if (o.quant && quant_enabled(*o.quant)) set_quant(o.quant);
 }
 
 void Net::set_opoint(const OpointCfg* op) {
@@ -1243,6 +1263,57 @@ void Net::set_average(const float* host) {
 void Net::finalize_average() {
     CMOOP_REQUIRE(ema_ != nullptr, "finalize_average: the net has no average (set_ema with momentum > 0 first)");
     CMOOP_HIP(hipMemcpyAsync(weights_, ema_, n_params_ * 4, hipMemcpyDeviceToDevice, stream_));
+}
+
+void Net::ensure_quant_table() {
+    if (qtab_ready_) return;
+    NetPlan plan;
+    plan.ops = ops_;
+    plan.n_params = n_params_;
+    qtab_ = quant_table(plan);
+    qtab_ready_ = true;
+}
+
+void Net::set_quant(const QuantCfg* quant) {
+    if (quant) quant_check(*quant);
+    const bool on = quant != nullptr && quant_enabled(*quant);
+    if (on && !wq_) {
+        ensure_quant_table();
+        wq_ = dalloc(n_params_);
+        qtab_dev_ = reinterpret_cast<QuantRow*>(dalloc(qtab_.rows.size() * sizeof(QuantRow) / sizeof(float) + 4));
+        CMOOP_HIP(hipMemcpyAsync(qtab_dev_, qtab_.rows.data(), qtab_.rows.size() * sizeof(QuantRow), hipMemcpyHostToDevice, stream_));
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running; the table's upload is done
+    quant_cfg_ = on ? *quant : QuantCfg();
+    quant_on_ = on;
+    if (on) graph_ok_ = false;                    // nothing is promised under CMOOP_GRAPH=1
+    drop_graph();
+}
+
+void Net::quantize_now() {
+    if (!quant_on_) return;
+    launch_quantize_weights(params_, wq_, nullptr, nullptr, qtab_, qtab_dev_, quant_cfg_.bits, stream_);
+}
+
+int64_t Net::quant_size_bytes() {
+    CMOOP_REQUIRE(quant_on_, "quant_size_bytes: the option is off (set_quant with bits in [2, 8] first)");
+    return cmoop::quant_size_bytes(qtab_, n_params_, quant_cfg_.bits);
+}
+
+void Net::get_quantized(float* wq_host, int8_t* codes_host, float* scales_host) {
+    CMOOP_REQUIRE(quant_on_, "get_quantized: the option is off (set_quant with bits in [2, 8] first)");
+    PoolScope pool(stream_);   // full-arena copies of this call: the net's own quantised arena holds kernel elements only
+    const size_t n = (size_t)n_params_;
+    float* d_wq = pool.get<float>(std::max<size_t>(n, 1) * 4);
+    int8_t* d_codes = pool.get<int8_t>(std::max<size_t>(n, 4));
+    float* d_scales = pool.get<float>(std::max<size_t>((size_t)qtab_.total_channels, 1) * 4);
+    CMOOP_HIP(hipMemcpyAsync(d_wq, params_, n * 4, hipMemcpyDeviceToDevice, stream_));
+    CMOOP_HIP(hipMemsetAsync(d_codes, 0, n, stream_));
+    launch_quantize_weights(params_, d_wq, d_codes, d_scales, qtab_, qtab_dev_, quant_cfg_.bits, stream_);
+    if (wq_host) CMOOP_HIP(hipMemcpyAsync(wq_host, d_wq, n * 4, hipMemcpyDeviceToHost, stream_));
+    if (codes_host) CMOOP_HIP(hipMemcpyAsync(codes_host, d_codes, n, hipMemcpyDeviceToHost, stream_));
+    if (scales_host) CMOOP_HIP(hipMemcpyAsync(scales_host, d_scales, (size_t)qtab_.total_channels * 4, hipMemcpyDeviceToHost, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));
 }
 
 void Net::optim_stats(double out[4]) {
@@ -1434,6 +1505,7 @@ void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch
 
 void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum, long long* correct, int32_t* preds) {
     CMOOP_HIP(hipMemsetAsync(acc_eval_, 0, 16, stream_));
+    quantize_now();   // quant on: once per call, on the arena this pass reads
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
         const BatchRows rows{nullptr, s};
@@ -1449,6 +1521,7 @@ void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum
 
 void Net::predict(const float* X, int64_t n, float* probs) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && probs)), "predict: NULL buffer");
+    quantize_now();
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
         forward(X, BatchRows{nullptr, s}, B, false);
@@ -1459,6 +1532,7 @@ void Net::predict(const float* X, int64_t n, float* probs) {
 
 void Net::predict_logits(const float* X, int64_t n, float* logits) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && logits)), "predict_logits: NULL buffer");
+    quantize_now();
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
         forward(X, BatchRows{nullptr, s}, B, false);
@@ -1487,6 +1561,7 @@ void Net::predict_stream(const float* feat, int64_t n_frames, int hop, bool db_s
         CMOOP_HIP(hipMemcpyAsync(ms, mean, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
         CMOOP_HIP(hipMemcpyAsync(ms + F_, scale, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
     }
+    quantize_now();
     for (int64_t w = 0; w < n; w += cfg_.eval_batch) {       // window i sits at position i % eval_batch of chunk i / eval_batch
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - w);
         launch_window_gather(feat, chunk, w, B, hop, T_, F_, db_scale ? 1 : 0, db_ref_max ? 1 : 0, db_amin, top_db, ms,
@@ -1562,6 +1637,10 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
     hipStream_t stream = net.stream();
     EvalResult res;
     res.size_mb = (double)(net.total_params() * 4) / (1024.0 * 1024.0);   // compute_model_size_mb, nsga_penalty.py:337-344
+    if (net.quant_on()) {   // the size of the model the fit trains and scores; size_mb stays the fp32 bytes
+        res.quant[0] = (double)net.quant_size_bytes() / (1024.0 * 1024.0);
+        res.quant[1] = (double)net.quant().bits;
+    }
 
     PoolScope pool(stream);   // everything below goes back once the stream has drained, however the fit ends
     int32_t* h_idx = nullptr;

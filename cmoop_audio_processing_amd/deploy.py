@@ -52,6 +52,12 @@ class TrainedModel:
     # one detection threshold per class, float32 [classes]: the operating point of the validation split under
     # EvalConfig.operating_point (opoint.py), what detect_events takes; None when the model was trained without it
     thresholds: Optional[np.ndarray] = None
+    # a model trained under EvalConfig.quant (quant.py): the bit width, the int8 code of every kernel element at its index in
+    # ``params`` (0 elsewhere) and one float32 scale per channel; ``params`` then holds the dequantised kernels,
+    # float32(codes) * scales bit for bit, so every fp32 path scores the quantised model.  All three or none
+    quant_bits: Optional[int] = None
+    quant_codes: Optional[np.ndarray] = None
+    quant_scales: Optional[np.ndarray] = None
 
     def __post_init__(self):
         self.gene = tuple(int(v) for v in self.gene)
@@ -75,6 +81,23 @@ class TrainedModel:
                 raise ValueError(f"thresholds must hold classes = {self.classes} values")
         self.objectives = {k: (int(self.objectives[k]) if k == "epochs_run" else float(self.objectives[k]))
                            for k in _OBJECTIVE_KEYS if k in self.objectives}
+        present = [v is not None for v in (self.quant_bits, self.quant_codes, self.quant_scales)]
+        if any(present) and not all(present):
+            raise ValueError("quant_bits, quant_codes and quant_scales come together (all three or none)")
+        if all(present):
+            from . import quant as Q
+            self.quant_bits = int(self.quant_bits)
+            qmax = Q.qmax_of(self.quant_bits)
+            self.quant_codes = np.ascontiguousarray(self.quant_codes, np.int8).reshape(-1)
+            self.quant_scales = np.ascontiguousarray(self.quant_scales, np.float32).reshape(-1)
+            rows = Q.quant_table(self.gene, G.VARIANT_NAMES[self.variant], int(self.classes))
+            if self.quant_codes.size != want or self.quant_scales.size != sum(r[1] for r in rows):
+                raise ValueError("quant_codes must hold one value per parameter and quant_scales one per kernel channel")
+            if int(np.abs(self.quant_codes.astype(np.int32)).max(initial=0)) > qmax:
+                raise ValueError(f"quant_codes exceed the {self.quant_bits}-bit range [-{qmax}, {qmax}]")
+            back = Q.dequantize(self.quant_codes, self.quant_scales, rows, like=self.params)
+            if not np.array_equal(back.view(np.uint32), self.params.view(np.uint32)):
+                raise ValueError("params do not equal float32(quant_codes) * quant_scales at the kernel tensors")
 
     def tensors(self) -> Dict[str, np.ndarray]:
         """{name: array} in the shapes of ``genes.param_tensors`` (views of ``params``)."""
@@ -85,6 +108,21 @@ class TrainedModel:
             off += n
         return out
 
+    def int8_tensors(self) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
+        """{kernel tensor name: (int8 codes in the shape of ``genes.param_tensors``, float32 scales: one per channel -- per
+        leading index, or per c of a depthwise kernel [kh][kw][C])} of a model that carries codes; raises otherwise."""
+        if self.quant_codes is None:
+            raise ValueError("the model carries no quantised weights (train it under EvalConfig.quant)")
+        out, off, pos = {}, 0, 0
+        for name, shape, role in G.param_tensors(self.gene, G.VARIANT_NAMES[self.variant], self.classes):
+            n = int(np.prod(shape))
+            if role == "kernel":
+                ch = int(shape[2]) if name.endswith("/depthwise_kernel") else int(shape[0])
+                out[name] = (self.quant_codes[off:off + n].reshape(shape), self.quant_scales[pos:pos + ch])
+                pos += ch
+            off += n
+        return out
+
     def save(self, path) -> None:
         """One ``.npz`` (numeric arrays only, no pickle), written to exactly ``path``.
 
@@ -92,7 +130,8 @@ class TrainedModel:
         ``frontend_float`` as ever; ``frontend_scale`` (index into log / db / power / pcen) only for a power or PCEN
         front end, whose ``frontend_int[5]`` is 0; ``frontend_pcen`` (s, alpha, delta, r, eps, input_scale) only when
         the front end carries a ``PcenConfig``.  A model without a front end, or with a log or dB one, writes the keys
-        it always wrote.  ``thresholds`` (float32 [classes]) only when the model carries them."""
+        it always wrote.  ``thresholds`` (float32 [classes]) only when the model carries them; ``quant_bits`` (int64 [1]),
+        ``quant_codes`` (int8) and ``quant_scales`` (float32) only when it carries quantised weights."""
         d = {"gene": np.asarray(self.gene, np.int32),
              "meta": np.asarray([G.VARIANT_NAMES[self.variant], self.classes, self.T, self.F, self.seed], np.int64),
              "params": self.params,
@@ -112,6 +151,9 @@ class TrainedModel:
             d["mean"], d["scale"] = self.mean, self.scale
         if self.thresholds is not None:
             d["thresholds"] = self.thresholds
+        if self.quant_codes is not None:
+            d["quant_bits"] = np.asarray([self.quant_bits], np.int64)
+            d["quant_codes"], d["quant_scales"] = self.quant_codes, self.quant_scales
         with open(path, "wb") as f:
             np.savez(f, **d)
 
@@ -134,9 +176,13 @@ class TrainedModel:
             mean = z["mean"].copy() if "mean" in z.files else None
             scale = z["scale"].copy() if "scale" in z.files else None
             thresholds = z["thresholds"].copy() if "thresholds" in z.files else None
+            quant = {}
+            if "quant_codes" in z.files:
+                quant = dict(quant_bits=int(z["quant_bits"][0]), quant_codes=z["quant_codes"].copy(),
+                             quant_scales=z["quant_scales"].copy())
             return cls(gene=tuple(int(v) for v in z["gene"]), variant=G.VARIANT_CODES[variant], classes=classes, T=T, F=F, seed=seed,
                        params=z["params"].copy(), objectives=obj, frontend=fe, mean=mean, scale=scale,
-                       thresholds=thresholds)
+                       thresholds=thresholds, **quant)
 
     def session(self, config: Optional[EvalConfig] = None):
         """A ``NetSession`` holding these parameters (needs the GPU).  ``config`` supplies ``eval_batch`` and the like;

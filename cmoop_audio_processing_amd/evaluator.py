@@ -39,6 +39,7 @@ from .distill import DistillConfig, check_teacher_table, require_teacher
 from .optim import OptimConfig
 from .ema import EmaConfig
 from .opoint import OperatingPointConfig
+from .quant import QuantConfig
 
 FPR_CODES = {"v1": 0, "v1_quirk": 1, "v3": 2}
 ACC_CODES = {"last": 0, "evaluate": 1}
@@ -104,6 +105,12 @@ class EvalConfig:
     # number, row and dict as without the field (cmoop_net_set_opoint).  It only adds numbers, unless objective=True, which
     # puts fpr_at_recall in the place of the arg-max FPR in the objectives.  Travels beside ema_struct(), as opoint_struct()
     operating_point: Optional[OperatingPointConfig] = None
+    # quantisation-aware training of every candidate's fit (quant.py): forward, backward, validation, early stopping and the
+    # read-outs see per-channel `bits`-bit kernels; the gradients go straight through to the latent fp32 weights.  None or bits 0
+    # = off, every number, row and dict as without the field (cmoop_net_set_quant).  Result dicts gain "quant": {"size_mb",
+    # "bits"}; with objective=True (the default) that size takes the place of size_mb in objs and in the size constraint, so
+    # the objective vector describes one model.  Travels beside opoint_struct(), as quant_struct()
+    quant: Optional[QuantConfig] = None
 
     @staticmethod
     def preset(script: str, **over) -> "EvalConfig":
@@ -180,6 +187,12 @@ class EvalConfig:
         if self.operating_point is None or not self.operating_point.enabled:
             return None
         return self.operating_point.check()._struct()
+
+    def quant_struct(self) -> Optional["_lib.Quant"]:
+        """The enabled quantiser as a ``cmoop_quant``, checked; None when it is off."""
+        if self.quant is None or not self.quant.enabled:
+            return None
+        return self.quant.check()._struct()
 
     def option_structs(self, T: int, F: int, teacher_logits, n_train: int):
         """(augment, loss, distill, optim) of a fit on [T, F] patches against ``teacher_logits``: the four ``*_struct``
@@ -441,16 +454,18 @@ class PopulationEvaluator:
         return d
 
     def _population_call(self, genes, sd, n, cfg, next_cb, acc, size, fpr, ep, secs, done, op=None) -> None:
-        """THE population call: ``cmoop_eval_population_op`` with ``config.option_structs``, ``config.ema_struct`` and
-        ``config.opoint_struct`` by reference, None (NULL) for whatever is off; next_cb None: the library's own longest-first
-        counter, and ``done`` is then None too.  ``op``: float64 [n, 4] for the operating-point summaries, or None."""
+        """THE population call: ``cmoop_eval_population_q`` with ``config.option_structs``, ``config.ema_struct``,
+        ``config.opoint_struct`` and ``config.quant_struct`` by reference, None (NULL) for whatever is off; next_cb None: the
+        library's own longest-first counter, and ``done`` is then None too.  ``op``: float64 [n, 4] for the operating-point
+        summaries, or None.  The quantised size is a closed form of the gene (``genes.quant_size_mb``, equal to what the call
+        would return): the result rows do not carry it."""
         ds = self._dataset()
         opts = self.config.option_structs(self.T, self.F, self.teacher_logits, len(self.X_train)) + \
-            (self.config.ema_struct(), self.config.opoint_struct())
-        _lib.check(_lib.lib().cmoop_eval_population_op(
+            (self.config.ema_struct(), self.config.opoint_struct(), self.config.quant_struct())
+        _lib.check(_lib.lib().cmoop_eval_population_q(
             C.byref(cfg), *(C.byref(o) if o is not None else None for o in opts), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
             C.c_int32(n), C.cast(next_cb, C.c_void_p) if next_cb is not None else None, None, _lib.ptr(acc), _lib.ptr(size),
-            _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done), _lib.ptr(op)))
+            _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done), _lib.ptr(op), None))
 
     @property
     def row_width(self) -> int:
@@ -561,7 +576,14 @@ class PopulationEvaluator:
         for ind, r in zip(population, res):
             acc, size_mb, fpr = float(r[0]), float(r[1]), float(r[2])
             self._print(r)
-            results.append(pack_result(ind, acc, size_mb, fpr, c, r[5:9] if w == 10 else None))
+            d = pack_result(ind, acc, size_mb, fpr, c, r[5:9] if w == 10 else None)
+            if c.quant_struct() is not None:    # a closed form of the gene: nothing of it travels in the rows
+                q_mb = float(G.quant_size_mb(G.normalize_hparams(ind), v, c.classes, c.quant.bits))
+                if c.quant.objective:           # the objective vector describes one model: the quantised one
+                    d = pack_result(ind, acc, q_mb, fpr, c, r[5:9] if w == 10 else None)
+                    d["size_fp32_mb"] = size_mb
+                d["quant"] = {"size_mb": q_mb, "bits": int(c.quant.bits)}
+            results.append(d)
         return results
 
     def train_model(self, hparams, seed: int, frontend=None, mean=None, scale=None):
@@ -570,6 +592,10 @@ class PopulationEvaluator:
         The body of the population call's per-candidate work (``NetSession.fit``) on the given seed and under the same
         ``config.augment`` / ``config.loss`` / ``config.optim`` / ``config.ema`` / ``config.distill`` (against the teacher of ``set_teacher``): with
         ``seed = last_seeds[i]`` it reproduces candidate i of the last generation, accuracy and FPR included.
+        Under ``config.quant`` the model's ``params`` are the quantised arena (``NetSession.get_quantized``: kernels
+        dequantised), so a plain fp32 ``session()``, ``logits()`` and ``StreamScorer`` score exactly the model the fit scored,
+        and it carries ``quant_bits`` / ``quant_codes`` / ``quant_scales``; ``objectives["size_mb"]`` is then the quantised
+        size when ``quant.objective``.
         ``hparams`` is the reference's dict or a gene tuple; ``frontend`` / ``mean`` / ``scale`` (the front end and the
         StandardScaler the features were made with) ride along for ``StreamScorer``."""
         from .deploy import TrainedModel
@@ -580,14 +606,20 @@ class PopulationEvaluator:
         with NetSession(g, self.config, self.T, self.F, int(seed)) as net:
             net.set_distill(teacher_logits=self.teacher_logits)      # config.distill, or off
             r = net.fit(self.X_train, self.y_train, self.X_val, self.y_val)
-            params = net.get_params()
+            params, codes, scales = net.get_params(), None, None
+            if net.quant is not None:
+                params, codes, scales = net.get_quantized()
         v = G.VARIANT_NAMES[self.config.variant]
-        objectives = {"acc": float(r["acc"]), "size_mb": float(G.model_size_mb(g, v, self.config.classes)), "fpr": float(r["fpr"]),
+        size_mb = G.model_size_mb(g, v, self.config.classes)
+        if codes is not None and self.config.quant.objective:
+            size_mb = G.quant_size_mb(g, v, self.config.classes, self.config.quant.bits)
+        objectives = {"acc": float(r["acc"]), "size_mb": float(size_mb), "fpr": float(r["fpr"]),
                       "epochs_run": int(r["epochs_run"])}
         thresholds = r["operating_point"]["thresholds"] if "operating_point" in r else None     # config.operating_point on
         return TrainedModel(gene=g, variant=self.config.variant, classes=int(self.config.classes), T=self.T, F=self.F,
                             seed=int(seed), params=params, objectives=objectives, frontend=frontend, mean=mean, scale=scale,
-                            thresholds=thresholds)
+                            thresholds=thresholds, quant_bits=int(self.config.quant.bits) if codes is not None else None,
+                            quant_codes=codes, quant_scales=scales)
 
     def _print(self, r):
         if self.config.verbose:

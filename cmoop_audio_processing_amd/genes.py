@@ -249,6 +249,31 @@ def model_size_mb(g: Sequence[int], variant: int, classes: int) -> float:
     return (param_count(g, variant, classes) * 4) / (1024 ** 2)
 
 
+def quant_size_bytes(g: Sequence[int], variant: int, classes: int, bits: int) -> int:
+    """Bytes of the candidate with ``bits``-bit per-channel kernels (quant.py; the twin of ``cmoop_quant_size_bytes``):
+    sum over kernel tensors of ceil(elements * bits / 8) + 4 * (total channels: one float32 scale each) + 4 * (every other
+    parameter, kept float32).  A depthwise kernel [kh][kw][C] has C channels, every other kernel one per leading index."""
+    bits = int(bits)
+    if not 2 <= bits <= 8:
+        raise ValueError("bits must be in [2, 8]")
+    packed = channels = kernel_elems = 0
+    for name, shape, role in param_tensors(g, variant, classes):
+        if role != "kernel":
+            continue
+        n = 1
+        for d in shape:
+            n *= int(d)
+        packed += (n * bits + 7) // 8
+        channels += int(shape[2]) if name.endswith("/depthwise_kernel") else int(shape[0])
+        kernel_elems += n
+    return packed + 4 * channels + 4 * (param_count(g, variant, classes) - kernel_elems)
+
+
+def quant_size_mb(g: Sequence[int], variant: int, classes: int, bits: int) -> float:
+    """``quant_size_bytes`` / 2**20, in float64: what the population call returns next to ``size_mb``."""
+    return quant_size_bytes(g, variant, classes, bits) / (1024 ** 2)
+
+
 def fwd_flops_per_sample(g: Sequence[int], variant: int, classes: int, T: int, F: int) -> int:
     """Algorithmic forward FLOPs per sample, 2*MAC for conv/dense only."""
     f, k, _, R, fc, _ = (int(v) for v in g)

@@ -27,9 +27,9 @@ class NetSession:
         _lib.check(_lib.lib().cmoop_net_total_params(self._h, C.byref(n)))
         self.n_params = int(n.value)
         self.T, self.F = int(T), int(F)
-        self.augment = self.loss = self.optim = self.ema = self.opoint = None
+        self.augment = self.loss = self.optim = self.ema = self.opoint = self.quant = None
         for name, setter in (("augment", self.set_augment), ("loss", self.set_loss), ("optim", self.set_optim),
-                             ("ema", self.set_ema), ("operating_point", self.set_operating_point)):
+                             ("ema", self.set_ema), ("operating_point", self.set_operating_point), ("quant", self.set_quant)):
             if getattr(config, name, None) is not None:
                 try:
                     setter(getattr(config, name))
@@ -180,6 +180,27 @@ class NetSession:
         rec, summary = (_lib.OpointClass * int(self.config.classes))(), (C.c_double * 4)()
         _lib.check(_lib.lib().cmoop_net_last_opoint(self._h, rec, summary))
         return OP.from_records(rec, summary)
+
+    def set_quant(self, quant) -> None:
+        """Quantisation-aware training (``QuantConfig``) of every following train step and inference call of this net.  None
+        or bits 0 turns it off (``self.quant`` is then None), and the net is bit for bit one that never had it.  On, every
+        train step first quantises the latent kernels and runs forward and backward on them (the gradients go unchanged to the
+        latent weights), and ``evaluate`` / ``predict_proba`` / ``predict_logits`` / ``predict_stream`` quantise the arena they
+        read first; ``get_params`` / ``set_params`` / ``get_state`` keep meaning the latent fp32 weights.  Switched on after a
+        plain fit it is post-training quantisation."""
+        self._set("cmoop_net_set_quant", None if quant is None else quant.check()._struct())
+        self.quant = quant if quant is not None and quant.enabled else None
+
+    def get_quantized(self):
+        """(wq_params float32 [n_params]: kernels dequantised, every other element a copy; codes int8 [n_params]: 0 outside
+        the kernel tensors; scales float32 [total channels]) of the arena inference would read now; raises while the option is
+        off.  Equal, bit for bit, to ``quant.quantize_params_ref`` of that arena."""
+        from . import quant as Q
+        v = G.VARIANT_NAMES[self.config.variant]
+        channels = sum(r[1] for r in Q.quant_table(self.gene, v, int(self.config.classes)))
+        wq, codes, scales = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.int8), np.empty(channels, np.float32)
+        _lib.check(_lib.lib().cmoop_net_get_quantized(self._h, _lib.ptr(wq), _lib.ptr(codes), _lib.ptr(scales)))
+        return wq, codes, scales
 
     def optim_stats(self) -> dict:
         """The last train step's optimiser read-out: dict(sumsq, norm, scale, path) -- the float64 sum of squares of the

@@ -96,11 +96,11 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 
 /* compute_objectives_and_constraints' inner loop (nsga_penalty.py:426-427): evaluate n
  * candidates; outputs are host arrays of length n (any may be NULL).
- * THE POPULATION CALL.  The eight cmoop_eval_population* symbols are ONE call, cmoop_eval_population_op, each with fewer
+ * THE POPULATION CALL.  The nine cmoop_eval_population* symbols are ONE call, cmoop_eval_population_q, each with fewer
  * of its arguments: next (with ctx and evaluated; NULL: the library's own longest-first queue, evaluated may then be
- * NULL too) and the six options aug, loss, distill, optim, ema, op (cmoop_augment, cmoop_loss, cmoop_distill,
- * cmoop_optim, cmoop_ema, cmoop_opoint below, checked in that order).  An option that is NULL or disabled gives exactly -- launch
- * for launch, bit for bit -- the call without it, so a caller may always take _op and pass NULL for what is off. */
+ * NULL too) and the seven options aug, loss, distill, optim, ema, op, q (cmoop_augment, cmoop_loss, cmoop_distill,
+ * cmoop_optim, cmoop_ema, cmoop_opoint, cmoop_quant below, checked in that order).  An option that is NULL or disabled gives
+ * exactly -- launch for launch, bit for bit -- the call without it, so a caller may always take _q and pass NULL for what is off. */
 int cmoop_eval_population(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
                           const uint32_t* seeds /* [n] */, int32_t n, double* acc, double* size_mb, double* fpr,
                           int32_t* epochs_run, double* val_loss, double* seconds);
@@ -420,13 +420,84 @@ int cmoop_operating_point_time(const float* probs_dev, const int32_t* y_dev, int
                                int32_t iters, double* avg_ms /* [4] */);
 /* host-only: the float64 finish alone, summary [4] from classes_host [C] */
 int cmoop_opoint_summary(const cmoop_opoint_class* classes_host, int32_t C, double* summary /* [4] */);
-/* the population call (above) with every argument: the other seven forward here.  op NULL or disabled: cmoop_eval_population_avg's
- * launches and bytes, and opoint (may be NULL) receives zeros; enabled: opoint [n][4] receives every candidate's summary */
+/* the population call (above) with every argument but the quantiser: forwards to cmoop_eval_population_q with NULL, NULL.  op NULL
+ * or disabled: cmoop_eval_population_avg's launches and bytes, and opoint (may be NULL) receives zeros; enabled: opoint [n][4]
+ * receives every candidate's summary */
 int cmoop_eval_population_op(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
                              const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_dataset* ds,
                              const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next, void* ctx,
                              double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds,
                              int32_t* evaluated, double* opoint /* [n][4], may be NULL */);
+
+/* ---- quantisation-aware training (QAT): int8 (or narrower) per-channel weights inside the train step, their size, their export
+ * (opt-in, off by default).  BUILD-DEFINED: the reference trains and sizes an fp32 model and has no counterpart; with no quant
+ * config, or a disabled one, every launch and every bit is that of a build without it.  No accuracy gain is claimed.
+ * Symmetric, per-output-channel, WEIGHT-ONLY fake quantisation of every kernel tensor (kind 0 of cmoop_param_kinds: conv, first
+ * conv, depthwise, pointwise, dense, output layer).  bits in 2..8, qmax = 2^(bits-1) - 1.
+ *   Channels   a tensor stored [C_out][kh][kw][C_in] or [out][in] has one channel per leading index, its elements the contiguous
+ *              row; a depthwise kernel [kh][kw][C] has one channel per c, its elements the kh kw taps at stride C.
+ *   Per channel with elements w_i:
+ *     a    = the float whose bits are max_i (bits(w_i) & 0x7FFFFFFF), compared as uint32: exact and order-free; a NaN outranks
+ *            inf and propagates.  No value is special-cased.
+ *     s    = a / (float)qmax, one correctly rounded fp32 division.
+ *     if s > 0 is false (a is zero, a / qmax underflows to zero, or NaN): every code is 0 and s is stored as computed.
+ *     else r_i = rintf(w_i / s): one fp32 division, then round half to even; a NaN r_i (a = inf: inf / inf) is code 0;
+ *          q_i = (int8) clamp(r_i, -qmax, qmax).
+ *     wq_i = (float)(int)q_i * s, one fp32 product.  A zero code gives +0.0f for every s > 0.
+ *     NaNs are stored in ONE form: a scale or a product that is NaN (a NaN; 0 * inf) is stored as the quiet NaN 0x7FC00000.
+ *     Non-finite weights are not a supported regime, only a deterministic one.
+ *   Straight-through gradient: the gradients the backward pass forms with wq in place of w are applied unchanged to the latent
+ *     fp32 w.  The absmax scale never clips (|r_i| <= qmax before the clamp for every finite row with a normal s), so there is no
+ *     mask; the scale's own gradient is ignored.
+ *   With an enabled config on a net: every train step first runs ONE launch that quantises the current latent kernels of the whole
+ *     arena; the flip-transposed dgrad operands are built from the quantised kernels; forward and backward read kernels from the
+ *     quantised copy and biases, gamma, beta and the moving statistics from the parameter arena (BatchNorm's moving-statistics
+ *     writes land there).  The optimiser, Adam's moments, the EMA and the snapshots keep operating on the latent weights.  Every
+ *     inference call (cmoop_net_evaluate, _predict, _predict_logits, _predict_stream) runs the launch once at its start on the arena
+ *     it is about to read: the average under cmoop_net_use_ema.  A fit therefore validates, early-stops and reads out the quantised
+ *     model; restore_best snapshots latent weights and the read-out re-quantises them, which is deterministic, so it is the same
+ *     model.  The step is not captured as a graph.
+ *   Out of scope: activations stay fp32 (weight-only); BatchNorm folding; TFLite / ONNX writers.  It composes with every
+ *     gemm_mode (the bf16 bodies round wq); only fp32 is tested.
+ *   Size: quant_size_bytes = sum over kernel tensors of ceil(elements * bits / 8) + 4 * (total channels) + 4 * (n_params -
+ *     kernel elements).  size_mb of the population call stays count_params * 4 / 2^20; the new number is returned next to it.
+ * Domain: bits in {0, 2..8}, objective in {0, 1}, reserved 0.  A config is ENABLED iff bits != 0.  objective is read by the host
+ * layers only (1: the evaluator puts the quantised size in the place of size_mb); the library checks it. */
+typedef struct cmoop_quant {
+    int32_t bits;         /* 0 = off, else 2 .. 8 */
+    int32_t objective;    /* 0 / 1 */
+    int32_t reserved[2];  /* 0 */
+} cmoop_quant;            /* 16 bytes */
+int cmoop_quant_default(cmoop_quant* q);   /* off: all zero */
+/* host-only: non-zero + a message naming the offending field (bits, objective, reserved) when the config is outside the domain */
+int cmoop_quant_check(const cmoop_quant* q);
+/* host-only: the kernel tensors of a candidate in arena order, rows [count][5] = {off, channels, len, chan_stride, elem_stride}:
+ * channel c holds the elements off + c chan_stride + t elem_stride, t < len (row tensors: chan_stride = len, elem_stride = 1;
+ * depthwise: chan_stride = 1, elem_stride = C).  cap: rows the buffer holds (an error when too small); count and total_channels
+ * (the number of scales) may be NULL.  The elements covered are exactly those of kind 0 in cmoop_param_kinds. */
+int cmoop_quant_table(const int32_t gene[6], int32_t variant, int32_t classes, int64_t* rows /* [cap][5] */, int32_t cap,
+                      int32_t* count, int64_t* total_channels);
+/* host-only: quant_size_bytes of a candidate at `bits` in 2..8 */
+int cmoop_quant_size_bytes(const int32_t gene[6], int32_t variant, int32_t classes, int32_t bits, int64_t* out);
+/* the kernel alone on the library stream: the tensors of rows_host [count][5] (as cmoop_quant_table gives them; at most 128 rows,
+ * every one inside the arena of n < 2^31 elements, else an error) of w_dev [n] into wq_dev [n], codes_dev [n] int8 (may be NULL)
+ * and scales_dev [total channels, in row order] (may be NULL).  q must be enabled.  Writes ONLY the tensors' elements of wq_dev
+ * and codes_dev and exactly total-channels scales. */
+int cmoop_quantize_weights(const cmoop_quant* q, const float* w_dev, int64_t n, const int64_t* rows_host /* [count][5] */,
+                           int32_t count, float* wq_dev, int8_t* codes_dev, float* scales_dev);
+/* average milliseconds of that launch over `iters` back-to-back launches between two HIP events on the library stream, after 3
+ * warm-up launches */
+int cmoop_quantize_weights_time(const cmoop_quant* q, const float* w_dev, int64_t n, const int64_t* rows_host, int32_t count,
+                                float* wq_dev, int8_t* codes_dev, float* scales_dev, int32_t iters, double* avg_ms);
+/* the population call (above) with every argument: the other eight forward here.  q NULL or disabled: cmoop_eval_population_op's
+ * launches and bytes, and quant (may be NULL) receives zeros; enabled: quant [n][2] receives every candidate's
+ * {quant_size_bytes / 2^20, bits} */
+int cmoop_eval_population_q(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                            const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_quant* q,
+                            const cmoop_dataset* ds, const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n,
+                            cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
+                            double* val_loss, double* seconds, int32_t* evaluated, double* opoint /* [n][4], may be NULL */,
+                            double* quant /* [n][2], may be NULL */);
 
 /* host-only: does every conv layer of this candidate at `batch` rows per launch (pass max(batch, eval_batch)) stay inside
  * the kernels' 32-bit byte offsets (each activation / kernel tensor below 2^29 elements)?  Non-zero + message if not;
@@ -675,6 +746,15 @@ int cmoop_net_last_opoint(cmoop_net* net, cmoop_opoint_class* classes_host, doub
 /* cmoop_net_predict's pass over x_dev [n][T][F] into a pooled buffer, then cmoop_operating_point against y_dev [n] */
 int cmoop_net_operating_point(cmoop_net* net, const float* x_dev, const int32_t* y_dev, int64_t n, const cmoop_opoint* op,
                               cmoop_opoint_class* classes_host /* [classes] */, double* summary /* [4] */);
+/* Quantisation-aware training (cmoop_quant above) of every following train step and inference call of this net (NULL or a disabled
+ * config: off, and the net is one that never had it, launch for launch and bit for bit).  The config is copied.  Switching it on
+ * after a plain fit and evaluating is post-training quantisation.  cmoop_net_get_params / _set_params / _get_state / _set_state
+ * always mean the latent fp32 weights. */
+int cmoop_net_set_quant(cmoop_net* net, const cmoop_quant* q /* NULL = off */);
+/* the arena inference would read now (the average under cmoop_net_use_ema), quantised: wq_params_host [total params] (kernels
+ * dequantised, every other element copied), codes_host [total params] int8 (the code of every kernel element at its arena
+ * index, 0 elsewhere), scales_host [total channels of cmoop_quant_table]; any may be NULL.  An error while the option is off. */
+int cmoop_net_get_quantized(cmoop_net* net, float* wq_params_host, int8_t* codes_host, float* scales_host);
 /* cmoop_net_train_step_targets with a teacher row per batch row, q_dev [B][classes], and the distillation loss at
  * (alpha, temperature), whatever cmoop_net_set_distill says. */
 int cmoop_net_train_step_distill_targets(cmoop_net* net, const float* x_rows_dev, const float* t_dev, const float* w_dev,

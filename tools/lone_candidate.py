@@ -14,6 +14,8 @@ another streaming pass over one batch.
 --ema M [--ema-warmup] trains with the weight EMA (EmaConfig): one more launch per step (12 bytes plus a kind byte per
 parameter), and validation reads the averaged weights.  --history adds the per-epoch validation loss and accuracy of one
 more fit of the same candidate and seed (NetSession.fit) to the line.
+--quant-bits N trains quantisation-aware (QuantConfig): one more launch at the head of every step and of every validation
+pass, 8 bytes per kernel parameter.
 """
 import argparse
 import json
@@ -25,7 +27,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cmoop_audio_processing_amd import AugmentConfig, EmaConfig, EvalConfig, LossConfig, PopulationEvaluator, genes as G  # noqa: E402
+from cmoop_audio_processing_amd import (AugmentConfig, EmaConfig, EvalConfig, LossConfig, PopulationEvaluator, QuantConfig,  # noqa: E402
+                                        genes as G)
 from cmoop_audio_processing_amd.session import NetSession  # noqa: E402
 
 
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--class-weight", default="", choices=["", "balanced"], help="balanced: n / (classes * count_c) of the train labels")
     ap.add_argument("--ema", type=float, default=0.0, help="weight EMA momentum (Keras' ema_momentum, e.g. 0.99); 0: off")
     ap.add_argument("--ema-warmup", action="store_true", help="--ema: m(i) = min(m, (1 + i) / (10 + i))")
+    ap.add_argument("--quant-bits", type=int, default=0, help="quantisation-aware training at this width (2..8); 0: off")
     ap.add_argument("--history", action="store_true", help="add the per-epoch validation loss / accuracy of one more fit")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -57,7 +61,8 @@ def main():
         loss = LossConfig.balanced(y[:n_tr], 10, mixup_alpha=args.mixup_alpha, label_smoothing=args.label_smoothing)
     cfg = EvalConfig.preset("nsga_penalty", variant=args.variant, epochs=args.epochs, early_stop=False, n_slots=1, seed=0,
                             augment=augment, loss=loss if loss.enabled else None,
-                            ema=EmaConfig(momentum=args.ema, warmup=args.ema_warmup) if args.ema > 0 else None)
+                            ema=EmaConfig(momentum=args.ema, warmup=args.ema_warmup) if args.ema > 0 else None,
+                            quant=QuantConfig(bits=args.quant_bits) if args.quant_bits else None)
     ev = PopulationEvaluator(X[:n_tr], y[:n_tr], X[n_tr:], y[n_tr:], cfg)
     steps = args.epochs * ((n_tr + cfg.batch - 1) // cfg.batch)
     for gs in args.genes:
@@ -78,7 +83,7 @@ def main():
         fl = G.eval_flops(gene, G.VARIANT_NAMES[args.variant], 10, 101, 40, n_tr, n_va, args.epochs, 1)
         print(json.dumps({"gene": gene, "variant": args.variant, "augment": args.augment or None, "noise_std": args.noise_std,
                           "mixup_alpha": args.mixup_alpha, "label_smoothing": args.label_smoothing, "class_weight": args.class_weight or None,
-                          "ema": args.ema or None, "ema_warmup": bool(args.ema_warmup), **hist,
+                          "ema": args.ema or None, "ema_warmup": bool(args.ema_warmup), "quant_bits": args.quant_bits or None, **hist,
                           "train_steps": steps, "wall_s": round(best, 4),
                           "steps_per_s": round(steps / best, 1), "ms_per_step_incl_val": round(best / steps * 1e3, 4),
                           "tflops": round(fl / best / 1e12, 2)}), flush=True)
