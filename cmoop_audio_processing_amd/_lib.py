@@ -80,6 +80,12 @@ class Quant(C.Structure):
     _fields_ = [("bits", C.c_int32), ("objective", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class Prune(C.Structure):
+    """cmoop_prune (include/cmoop.h), 24 bytes."""
+    _fields_ = [("sparsity", C.c_double), ("begin_step", C.c_int32), ("end_step", C.c_int32), ("objective", C.c_int32),
+                ("skip_small", C.c_int32)]
+
+
 class OpointClass(C.Structure):
     """cmoop_opoint_class (include/cmoop.h), 32 bytes."""
     _fields_ = [("u2", C.c_int64), ("P", C.c_int32), ("N", C.c_int32), ("k", C.c_int32), ("tp", C.c_int32), ("fp", C.c_int32),
@@ -207,6 +213,23 @@ QUANT_PROTOTYPES = {
 }
 
 
+#: prototypes of the magnitude-pruning entry points (include/cmoop.h); structs travel as void* (C.byref), None is NULL
+PRUNE_PROTOTYPES = {
+    "cmoop_prune_default": [C.c_void_p],
+    "cmoop_prune_check": [C.c_void_p],
+    "cmoop_prune_sparsity_at": [C.c_void_p, C.c_int64, C.c_void_p],
+    "cmoop_prune_table": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p],
+    "cmoop_prune_size_bytes": [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_void_p],
+    "cmoop_prune_weights": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_prune_weights_time": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int32,
+                                 C.c_void_p],
+    "cmoop_net_set_prune": [C.c_void_p, C.c_void_p],
+    "cmoop_net_get_pruned": [C.c_void_p, C.c_void_p, C.c_void_p],
+    # cmoop_eval_population_q with one more struct pointer after q and one more output after quant
+    "cmoop_eval_population_p": [C.c_void_p] * 12 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 10,
+}
+
+
 #: prototypes of the PCEN entry points (include/cmoop.h); structs travel as void* (C.byref)
 PCEN_PROTOTYPES = {
     "cmoop_pcen_default": [C.c_void_p],
@@ -301,7 +324,8 @@ def lib():
                 fn.restype = C.c_int
         L.cmoop_config_default.restype = None
         for table in (STREAM_PROTOTYPES, AUGMENT_PROTOTYPES, PCEN_PROTOTYPES, ELEM_PROTOTYPES, LOSS_PROTOTYPES, DENSE_PROTOTYPES,
-                      DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES, OPOINT_PROTOTYPES, QUANT_PROTOTYPES):
+                      DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES, OPOINT_PROTOTYPES, QUANT_PROTOTYPES,
+                      PRUNE_PROTOTYPES):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         _lib = L

@@ -206,6 +206,26 @@ static QuantTable to_quant_table(const int64_t* rows, int32_t count, int64_t n) 
     quant_table_finalize(tab, n);
     return tab;
 }
+static_assert(sizeof(cmoop_prune) == 24, "cmoop_prune is part of the ABI");
+static PruneCfg to_prune(const cmoop_prune* p) {
+    CMOOP_REQUIRE(p != nullptr, "prune config is NULL");
+    PruneCfg c;
+    c.sparsity = p->sparsity; c.begin_step = p->begin_step; c.end_step = p->end_step; c.objective = p->objective;
+    c.skip_small = p->skip_small;
+    return c;
+}
+// the finalised table of rows_host [count][3] against an arena of n elements
+static PruneTable to_prune_table(const int64_t* rows, int32_t count, int64_t n) {
+    CMOOP_REQUIRE(count >= 0 && count <= PRUNE_MAX_ROWS && (count == 0 || rows), "prune: 0 <= count <= 128 and the rows");
+    PruneTable tab;
+    for (int i = 0; i < count; ++i) {
+        const int64_t* r = rows + 3 * (size_t)i;
+        for (int k = 0; k < 3; ++k) CMOOP_REQUIRE(r[k] >= -1 && r[k] <= PRUNE_MAX_ARENA, "prune: a table value is outside [-1, 2^31)");
+        tab.rows.push_back(PruneRow{(int32_t)r[0], (int32_t)r[1], (int32_t)r[2], 0});
+    }
+    prune_table_finalize(tab, n);
+    return tab;
+}
 // cmoop_opoint_class and OpointClass are one layout (asserted above and field by field here)
 static OpointClass* as_classes(cmoop_opoint_class* c) {
     static_assert(offsetof(cmoop_opoint_class, u2) == offsetof(OpointClass, u2) && offsetof(cmoop_opoint_class, P) == offsetof(OpointClass, P) &&
@@ -216,7 +236,7 @@ static OpointClass* as_classes(cmoop_opoint_class* c) {
 }
 
 // The converted training options of one population call: to_* and the matching *_check of every struct handed in, in the
-// order augment, loss, distill, optim, ema, opoint, quant (what a call with two bad structs reports first); owns what opt points into
+// order augment, loss, distill, optim, ema, opoint, quant, prune (what a call with two bad structs reports first); owns what opt points into
 namespace {
 struct AbiTrainOptions {
     AugmentCfg aug;
@@ -226,9 +246,10 @@ struct AbiTrainOptions {
     EmaCfg ema;
     OpointCfg opoint;
     QuantCfg quant;
+    PruneCfg prune;
     TrainOptions opt;
     AbiTrainOptions(const cmoop_augment* a, const cmoop_loss* l, const cmoop_distill* d, const cmoop_optim* o, const cmoop_ema* e,
-                    const cmoop_opoint* p, const cmoop_quant* q, const NetConfig& c, const Dataset& ds) {
+                    const cmoop_opoint* p, const cmoop_quant* q, const cmoop_prune* pr, const NetConfig& c, const Dataset& ds) {
         if (a) { aug = to_augment(a); augment_check(aug, ds.T, ds.F); opt.aug = &aug; }
         if (l) { loss = to_loss(l); loss_check(loss, c.classes); opt.loss = &loss; }
         if (d) { distill = to_distill(d); distill_check(distill, c.classes, ds.n_train); opt.distill = &distill; }
@@ -236,6 +257,7 @@ struct AbiTrainOptions {
         if (e) { ema = to_ema(e); ema_check(ema); opt.ema = &ema; }
         if (p) { opoint = to_opoint(p); opoint_check(opoint); opt.opoint = &opoint; }
         if (q) { quant = to_quant(q); quant_check(quant); opt.quant = &quant; }
+        if (pr) { prune = to_prune(pr); prune_check(prune); opt.prune = &prune; }
     }
     AbiTrainOptions(const AbiTrainOptions&) = delete;
 };
@@ -349,15 +371,16 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 // every population call; next == NULL: candidates are taken longest-first from a process-local counter; a NULL option: off
 static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss,
                                 const cmoop_distill* distill, const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op,
-                                const cmoop_quant* q, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n,
-                                cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
-                                double* val_loss, double* seconds, int32_t* evaluated, double* opoint, double* quant) {
+                                const cmoop_quant* q, const cmoop_prune* pr, const cmoop_dataset* ds, const int32_t* genes,
+                                const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr,
+                                int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated, double* opoint, double* quant,
+                                double* prune) {
     CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
     CMOOP_REQUIRE(n >= 0, "negative population size");
     CMOOP_REQUIRE(!next || evaluated, "NULL argument");
     NetConfig c = to_cfg(cfg);
     const Dataset d = to_dataset(ds);
-    const AbiTrainOptions options(aug, loss, distill, optim, ema, op, q, c, d);
+    const AbiTrainOptions options(aug, loss, distill, optim, ema, op, q, pr, c, d);
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
@@ -374,6 +397,7 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* au
         if (seconds) seconds[i] = r[i].seconds;
         if (opoint) std::memcpy(opoint + 4 * (size_t)i, r[i].opoint, sizeof(r[i].opoint));
         if (quant) std::memcpy(quant + 2 * (size_t)i, r[i].quant, sizeof(r[i].quant));
+        if (prune) std::memcpy(prune + 3 * (size_t)i, r[i].prune, sizeof(r[i].prune));
     }
 }
 
@@ -444,9 +468,18 @@ int cmoop_eval_population_q(const cmoop_config* cfg, const cmoop_augment* aug, c
                             const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx,
                             double* acc, double* size_mb, double* fpr, int32_t* epochs_run, double* val_loss, double* seconds,
                             int32_t* evaluated, double* opoint, double* quant) {
+    return cmoop_eval_population_p(cfg, aug, loss, distill, optim, ema, op, q, nullptr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr,
+                                   epochs_run, val_loss, seconds, evaluated, opoint, quant, nullptr);
+}
+
+int cmoop_eval_population_p(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                            const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_quant* q,
+                            const cmoop_prune* pr, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n,
+                            cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
+                            double* val_loss, double* seconds, int32_t* evaluated, double* opoint, double* quant, double* prune) {
     return guard([&] {
-        eval_population_abi(cfg, aug, loss, distill, optim, ema, op, q, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run,
-                            val_loss, seconds, evaluated, opoint, quant);
+        eval_population_abi(cfg, aug, loss, distill, optim, ema, op, q, pr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run,
+                            val_loss, seconds, evaluated, opoint, quant, prune);
     });
 }
 
@@ -521,6 +554,97 @@ int cmoop_quantize_weights_time(const cmoop_quant* q, const float* w_dev, int64_
     return guard([&] {
         CMOOP_REQUIRE(avg_ms && iters >= 1, "quantize_weights_time: iters >= 1 and avg_ms");
         quantize_weights_abi(q, w_dev, n, rows_host, count, wq_dev, codes_dev, scales_dev, iters, avg_ms);
+    });
+}
+
+// ---- magnitude pruning in training -------------------------------------------------
+int cmoop_prune_default(cmoop_prune* p) {
+    return guard([&] {
+        CMOOP_REQUIRE(p != nullptr, "prune config is NULL");
+        std::memset(p, 0, sizeof(*p));
+        p->skip_small = 1;
+    });
+}
+
+int cmoop_prune_check(const cmoop_prune* p) {
+    return guard([&] { prune_check(to_prune(p)); });
+}
+
+int cmoop_prune_sparsity_at(const cmoop_prune* p, int64_t it, double* out) {
+    return guard([&] {
+        CMOOP_REQUIRE(out != nullptr, "prune_sparsity_at: NULL output");
+        const PruneCfg c = to_prune(p);
+        prune_check(c);
+        *out = prune_sparsity_at(c, it);
+    });
+}
+
+static NetPlan prune_plan_of(const int32_t gene[6], int32_t variant, int32_t classes) {
+    CMOOP_REQUIRE(gene != nullptr, "prune_table: NULL gene");
+    NetConfig cfg;
+    cfg.variant = variant; cfg.classes = classes;
+    return plan_net(gene, cfg, 26, 10);   // offsets and kernel shapes do not depend on the patch size
+}
+
+int cmoop_prune_table(const int32_t gene[6], int32_t variant, int32_t classes, int32_t skip_small, int64_t* rows, int32_t cap,
+                      int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(skip_small == 0 || skip_small == 1, "prune: skip_small must be 0 or 1");
+        const PruneTable tab = prune_table(prune_plan_of(gene, variant, classes), skip_small != 0);
+        CMOOP_REQUIRE(rows && cap >= (int32_t)tab.rows.size(), "prune_table: the rows buffer is too small");
+        for (size_t i = 0; i < tab.rows.size(); ++i) {
+            const int64_t v[3] = {tab.rows[i].off, tab.rows[i].len, tab.rows[i].k};
+            std::memcpy(rows + 3 * i, v, sizeof(v));
+        }
+        if (count) *count = (int32_t)tab.rows.size();
+    });
+}
+
+int cmoop_prune_size_bytes(const int32_t gene[6], int32_t variant, int32_t classes, double sparsity, int32_t bits, int32_t skip_small,
+                           int64_t* out) {
+    return guard([&] {
+        CMOOP_REQUIRE(out != nullptr, "prune_size_bytes: NULL output");
+        CMOOP_REQUIRE(skip_small == 0 || skip_small == 1, "prune: skip_small must be 0 or 1");
+        const NetPlan plan = prune_plan_of(gene, variant, classes);
+        *out = prune_size_bytes(prune_table(plan, skip_small != 0), param_count(gene, variant, classes), sparsity, bits,
+                                bits ? quant_table(plan).total_channels : 0);
+    });
+}
+
+// the body of cmoop_prune_weights(_time): table and zeroed workspace on pooled buffers, then iters < 1: one call, else timed calls
+static void prune_weights_abi(const float* w, int64_t n, const int64_t* rows, int32_t count, double sp, float* out, uint32_t* zeros,
+                              int32_t* launches, int32_t iters, double* avg_ms) {
+    CMOOP_REQUIRE(sp >= 0.0 && sp < 1.0, "prune_weights: s must be in [0, 1)");
+    const PruneTable tab = to_prune_table(rows, count, n);
+    if (launches) *launches = 0;
+    if (tab.blocks == 0) { if (avg_ms) *avg_ms = 0.0; return; }
+    CMOOP_REQUIRE(w && out, "prune_weights: NULL arena");
+    hipStream_t s = lib_stream();
+    PoolScope pool(s);
+    PruneRow* rows_dev = pool.get<PruneRow>(tab.rows.size() * sizeof(PruneRow));
+    uint32_t* words = pool.get<uint32_t>(prune_workspace_words(count) * sizeof(uint32_t));
+    PruneWorkspace ws;
+    prune_workspace_init(ws, words, count, s);   // once per workspace, not per call: the calls below keep it clean themselves
+    CMOOP_HIP(hipMemcpyAsync(rows_dev, tab.rows.data(), tab.rows.size() * sizeof(PruneRow), hipMemcpyHostToDevice, s));
+    CMOOP_HIP(hipStreamSynchronize(s));
+    int did = 0;
+    auto once = [&] { did = launch_prune_weights(w, out, zeros, tab, rows_dev, ws, sp, s); };
+    if (avg_ms) *avg_ms = time_launches(s, iters, once);
+    else once();
+    if (launches) *launches = did;
+    CMOOP_HIP(hipStreamSynchronize(s));
+}
+
+int cmoop_prune_weights(const float* w_dev, int64_t n, const int64_t* rows_host, int32_t count, double s, float* out_dev,
+                        uint32_t* zeros_dev, int32_t* launches) {
+    return guard([&] { prune_weights_abi(w_dev, n, rows_host, count, s, out_dev, zeros_dev, launches, 0, nullptr); });
+}
+
+int cmoop_prune_weights_time(const float* w_dev, int64_t n, const int64_t* rows_host, int32_t count, double s, float* out_dev,
+                             uint32_t* zeros_dev, int32_t iters, double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "prune_weights_time: iters >= 1 and avg_ms");
+        prune_weights_abi(w_dev, n, rows_host, count, s, out_dev, zeros_dev, nullptr, iters, avg_ms);
     });
 }
 
@@ -1315,6 +1439,13 @@ int cmoop_net_finalize_ema(cmoop_net* h) {
 }
 int cmoop_net_set_opoint(cmoop_net* h, const cmoop_opoint* op) { return net_set_option(h, "set_opoint", op, to_opoint, &Net::set_opoint); }
 int cmoop_net_set_quant(cmoop_net* h, const cmoop_quant* q) { return net_set_option(h, "set_quant", q, to_quant, &Net::set_quant); }
+int cmoop_net_set_prune(cmoop_net* h, const cmoop_prune* p) { return net_set_option(h, "set_prune", p, to_prune, &Net::set_prune); }
+int cmoop_net_get_pruned(cmoop_net* h, float* weff_params_host, uint32_t* zeros_host) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "get_pruned: NULL net");
+        h->net->get_pruned(weff_params_host, zeros_host);
+    });
+}
 int cmoop_net_get_quantized(cmoop_net* h, float* wq_params_host, int8_t* codes_host, float* scales_host) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "get_quantized: NULL net");

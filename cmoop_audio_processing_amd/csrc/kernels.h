@@ -533,6 +533,55 @@ int64_t quant_size_bytes(const QuantTable& tab, int64_t n_params, int bits);
 void launch_quantize_weights(const float* w, float* wq, int8_t* codes, float* scales, const QuantTable& tab, const QuantRow* rows_dev,
                              int bits, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// Magnitude pruning in training (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_prune): per kernel tensor
+// the k = floor(s len) elements of smallest magnitude become +0.0f, the threshold found by an exact radix select on the
+// integer keys bits(w) & 0x7FFFFFFF; FOUR launches for a whole arena (prune.hip).
+// ---------------------------------------------------------------------------
+struct PruneCfg {
+    double sparsity = 0.0;           // the final sparsity, 0 = off, else in (0, 1)
+    int begin_step = 0, end_step = 0;   // the cubic ramp of prune_sparsity_at, in Adam iterations
+    int objective = 0;               // 1: the evaluator ranks candidates by the pruned size (read by the host layers only)
+    int skip_small = 1;              // 1: the first convolution and the depthwise kernels are copied, not pruned
+};
+// host-only: throws with a message naming the offending field
+void prune_check(const PruneCfg& c);
+inline bool prune_enabled(const PruneCfg& c) { return c.sparsity != 0.0; }
+// TF-MOT's PolynomialDecay, power 3 from 0: 0 before begin_step, sparsity from end_step on (or when end_step <= begin_step),
+// else sparsity (1 - (1-u)(1-u)(1-u)), u = (it - begin) / (double)(end - begin); IEEE double products only, no pow
+double prune_sparsity_at(const PruneCfg& c, int64_t it);
+constexpr int64_t PRUNE_MAX_ARENA = ((int64_t)1 << 31) - 1;   // elements: the kernels' index math is 32-bit
+constexpr int PRUNE_MAX_ROWS = 128;                           // tensors of one table
+constexpr int PRUNE_BLOCK_ELEMS = 8192;                       // elements of a tensor per workgroup
+constexpr int PRUNE_BINS_TOP = 2048, PRUNE_BINS_LOW = 1024;   // the digits of the radix select: 11, 10 and 10 bits of the 31
+// One kernel tensor: the len contiguous elements from off.  k: how many to prune (0: the tensor is copied; -1: floor(s len)
+// at the s of the launch).  block0: its first workgroup
+struct PruneRow { int32_t off, len, k, block0; };
+struct PruneTable {
+    std::vector<PruneRow> rows;
+    int32_t blocks = 0;
+    int64_t kernel_elems = 0;
+};
+// fills block0 / blocks / kernel_elems and checks every row against an arena of n elements (n <= PRUNE_MAX_ARENA, at most
+// PRUNE_MAX_ROWS rows in arena order without overlap, k in [-1, len], nothing past the arena)
+void prune_table_finalize(PruneTable& tab, int64_t n);
+int32_t prune_row_k(const PruneRow& r, double s);   // the k of a row at sparsity s (host twin of the kernels' own)
+// The stored bytes of a model pruned at `sparsity`: per tensor with k > 0 a ceil(len / 8) byte mask and its len - k values, 4
+// bytes each or (bits in 2..8) packed ceil((len - k) bits / 8); every other tensor and parameter as size_mb (bits 0) or
+// quant_size_bytes (bits 2..8, with 4 quant_channels bytes of scales) counts it.  An upper bound when keys tie at the threshold
+int64_t prune_size_bytes(const PruneTable& tab, int64_t n_params, double sparsity, int bits, int64_t quant_channels);
+// The select's device words for a table of `rows` tensors: histograms of the three digits and two state words per tensor.
+// prune_workspace_init slices words_dev [prune_workspace_words(rows)] and zeroes it ONCE; every launch_prune_weights leaves
+// hist1 / hist2 zero again, so no later call clears anything in a launch of its own
+struct PruneWorkspace { uint32_t *hist1 = nullptr, *hist2 = nullptr, *hist3 = nullptr, *state = nullptr; int rows = 0; };
+size_t prune_workspace_words(int rows);
+void prune_workspace_init(PruneWorkspace& ws, uint32_t* words_dev, int rows, hipStream_t s);
+// out := w at every element of every tensor of the table (rows_dev: tab.rows on the device), the k elements of smallest key
+// (and every key tied with the k-th) as +0.0f; zeros (may be null) [rows]: how many elements of each tensor became zero.
+// Writes ONLY the tensors' elements of out.  Returns the number of launches: 4, or 1 when every k is 0 (the same bytes)
+int launch_prune_weights(const float* w, float* out, uint32_t* zeros, const PruneTable& tab, const PruneRow* rows_dev,
+                         const PruneWorkspace& ws, double s, hipStream_t stream);
+
 // device twin of epoch_permutation (net.h): out[rank of key_i] = i; n <= EPOCH_PERMUTATION_DEVICE_MAX (O(n^2) rank sort)
 constexpr int64_t EPOCH_PERMUTATION_DEVICE_MAX = 262144;
 void launch_epoch_permutation(uint32_t seed, uint32_t epoch, int64_t n, int32_t* out, hipStream_t s);

@@ -212,9 +212,13 @@ NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F);
 // host-only: the quantisation table of a plan (kernels.h, QuantTable), one row per KIND_KERNEL tensor in arena order, finalised
 // against plan.n_params: the elements it covers are exactly those param_kinds() calls KIND_KERNEL
 QuantTable quant_table(const NetPlan& plan);
+// host-only: the pruning table of a plan (kernels.h, PruneTable), one row per KIND_KERNEL tensor in arena order, finalised
+// against plan.n_params.  OP_CONV and OP_DENSE kernels have k = -1 (pruned at the sparsity of each launch); the first
+// convolution and the depthwise kernels have k = 0 (copied) unless skip_small is false
+PruneTable prune_table(const NetPlan& plan, bool skip_small = true);
 
 // The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
-// set_distill / set_optim / set_ema / set_opoint / set_quant say what each does).  The pointees stay the caller's for the length of the call
+// set_distill / set_optim / set_ema / set_opoint / set_quant / set_prune say what each does).  The pointees stay the caller's for the length of the call
 struct TrainOptions {
     const AugmentCfg* aug = nullptr;
     const LossCfg* loss = nullptr;
@@ -223,6 +227,7 @@ struct TrainOptions {
     const EmaCfg* ema = nullptr;
     const OpointCfg* opoint = nullptr;
     const QuantCfg* quant = nullptr;
+    const PruneCfg* prune = nullptr;
 };
 
 class Net : public GemmHook {
@@ -316,7 +321,27 @@ class Net : public GemmHook {
     // [n_params] (0 outside the kernel tensors), scales [the table's total_channels]; any may be null.  Throws while the option is off
     void get_quantized(float* wq_host, int8_t* codes_host, float* scales_host);
     int64_t quant_size_bytes();          // kernels.h, at the bits of the config; throws while the option is off
-    // the enabled ones of o through the seven setters above, in that order: augment, loss, distill, optim, ema, opoint, quant.  THE
+    // Magnitude pruning (kernels.h) of every following train step and inference call; null or a disabled config: off, and every
+    // launch and bit is that of a net that never had one (the pruned arena, once allocated, is kept).  Enabled: the domain is
+    // checked; on first use the table is built from the plan and uploaded, the pruned arena and the select's workspace allocated.
+    // Every train step then first runs launch_prune_weights on the latent weights at prune_sparsity_at(cfg, iterations_);
+    // forward, backward and the flip-transposed dgrad operands read the kernels from the pruned arena (quant on as well: the
+    // quantiser reads the pruned arena, and they read the quantised one); the gradients go unchanged to the dense latent
+    // weights (straight-through), so a pruned weight can regrow.  evaluate / predict / predict_logits / predict_stream prune
+    // the arena they are about to read (the average under use_average) at the FINAL sparsity, whatever the iteration.  The
+    // optimiser, Adam's moments, the EMA, get/set_params and the snapshots keep meaning the latent weights.  The step is no
+    // longer captured as a graph
+    void set_prune(const PruneCfg* prune);
+    bool prune_on() const { return prune_on_; }
+    const PruneCfg& prune() const { return prune_cfg_; }
+    // the arena inference would read now, pruned at the final sparsity (not quantised): weff [n_params] (every other element
+    // copied) and zeros [rows of the table]: the elements of each tensor that became zero; either may be null.  Throws while off
+    void get_pruned(float* weff_host, uint32_t* zeros_host);
+    int prune_rows();                    // rows of the table (the length of zeros)
+    // sum of zeros / sum of len over the tensors with k > 0 at the final sparsity (0 when there is none)
+    double prune_achieved(const uint32_t* zeros);
+    int64_t prune_size_bytes();          // kernels.h, at the final sparsity and the quantiser's bits; throws while the option is off
+    // the enabled ones of o through the eight setters above, in that order: augment, loss, distill, optim, ema, opoint, quant, prune.  THE
     // place of "a disabled config is no config": null or disabled is not applied at all, and the net stays one that never had it
     void set_options(const TrainOptions& o);
     // the last step's {sum of squares, norm, scale, launch path (0 fused, 1 finish + update)}; path 0 computes no norm: 0, 0, 1
@@ -383,8 +408,11 @@ class Net : public GemmHook {
     void upload_step_state();                           // enqueues the device StepState at (0, step_, iterations_); no-op without one
     void ensure_target_buffers();                       // t / w / primary, allocated by the first enabled set_loss or set_distill
     void ensure_quant_table();                          // qtab_ from the plan, once (host only)
-    void quantize_now();                                // quant on: wq_ := quantised kernels of the arena forward reads (params_)
-    const float* kernels() const { return quant_on_ ? wq_ : params_; }   // where forward / backward read KIND_KERNEL tensors
+    void ensure_prune_table();                          // ptab_ from the plan and the config's skip_small (host only)
+    void prune_now(double s);                           // prune on: wp_ := kernels of the arena forward reads (params_), pruned at s
+    void quantize_now();                                // quant on: wq_ := quantised kernels of that arena, or of wp_ when prune is on
+    // where forward / backward read KIND_KERNEL tensors
+    const float* kernels() const { return quant_on_ ? wq_ : prune_on_ ? wp_ : params_; }
     ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
 
@@ -410,6 +438,13 @@ class Net : public GemmHook {
     QuantTable qtab_;                   // host table of the plan's kernel tensors
     bool qtab_ready_ = false;
     QuantRow* qtab_dev_ = nullptr;
+    PruneCfg prune_cfg_;                // set_prune; the default is off
+    bool prune_on_ = false;             // steps and inference calls prune first and read kernels from wp_ (or quantise wp_)
+    float* wp_ = nullptr;               // the pruned arena (only kernel elements are ever written or read), first enabled set_prune
+    PruneTable ptab_;                   // host table of the plan's kernel tensors
+    int ptab_skip_small_ = -1;          // the skip_small ptab_ was built with; -1: not built
+    PruneRow* ptab_dev_ = nullptr;
+    PruneWorkspace prune_ws_;
     std::vector<OpointClass> last_op_classes_;   // store_opoint: empty when the last fit ran without the read-out
     double last_op_summary_[4] = {0, 0, 0, 0};
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;
@@ -467,6 +502,9 @@ struct EvalResult {
     double opoint[4] = {0, 0, 0, 0};
     // quantisation-aware training (Net::set_quant): quant_size_bytes / 2^20, bits; zeros when it is off
     double quant[2] = {0, 0};
+    // magnitude pruning (Net::set_prune): prune_size_bytes / 2^20, the final sparsity, the zero fraction of the pruned tensors
+    // of the scored model; zeros when it is off
+    double prune[3] = {0, 0, 0};
 };
 
 // per-epoch record of a fit (tests: the early-stopping decisions are checked against the validation-loss history)

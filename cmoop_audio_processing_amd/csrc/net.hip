@@ -400,6 +400,21 @@ QuantTable quant_table(const NetPlan& plan) {
     return tab;
 }
 
+PruneTable prune_table(const NetPlan& plan, bool skip_small) {
+    PruneTable tab;
+    for (const Op& op : plan.ops) {
+        CMOOP_REQUIRE(op.w_off <= PRUNE_MAX_ARENA, "prune: the arena must stay below 2^31 elements (PRUNE_MAX_ARENA)");
+        if (op.kind == OP_CONV || op.kind == OP_DENSE)
+            tab.rows.push_back(PruneRow{(int32_t)op.w_off, op.Cout * op.KS * op.KS * op.Cin, -1, 0});
+        else if (op.kind == OP_CONV1)
+            tab.rows.push_back(PruneRow{(int32_t)op.w_off, op.Cout * op.KS * op.KS * op.Cin, skip_small ? 0 : -1, 0});
+        else if (op.kind == OP_DWCONV)
+            tab.rows.push_back(PruneRow{(int32_t)op.w_off, op.KS * op.KS * op.Cin, skip_small ? 0 : -1, 0});
+    }
+    prune_table_finalize(tab, plan.n_params);
+    return tab;
+}
+
 size_t NetPlan::splitk_floats(int batch, int Bmax) const {
     size_t need = 0;
     for (const Op& op : ops)
@@ -976,7 +991,8 @@ void Net::step_body(const float* X, const int32_t* y, const BatchRows& rows, int
                   std::to_string(kd_rows_) + " rows, the training split " + std::to_string(gather_rows_));
     // augmentation on: the batch's rows are gathered and augmented into aug_buf_ first (rows.st != null: the kernel reads
     // the batch position and the step from the device state, so a replayed graph draws for the step it replays)
-    quantize_now();   // quant on: the step's first launch, on the latent weights of this moment
+    prune_now(prune_sparsity_at(prune_cfg_, iterations_));   // prune on: the step's first launches, on the latent weights of this moment
+    quantize_now();   // quant on: the next launch, on the latent weights or on what the pruning left of them
     if (aug_on_) launch_augment_gather(X, rows, aug_buf_, B, T_, F_, aug_, seed_, (uint32_t)step_, stream_);
     // mixup on: the (augmented) rows are blended into mix_buf_ next; each row keeps its own batch position's augmentation
     // (from the augment buffer the launch takes only the step from rows.st: the buffer always starts at its row 0)
@@ -1076,6 +1092,7 @@ void Net::targets_step(const float* x_rows, const float* t, const float* w, cons
     batch_in_ = nullptr;
     const BatchRows rows;      // x_rows holds exactly the B rows of this step: no resident tensor to clamp into
     float *z = acts_[logits_].data, *dz = acts_[logits_].grad;
+    prune_now(prune_sparsity_at(prune_cfg_, iterations_));
     quantize_now();
     forward(x_rows, rows, B, true);
     if (kd) launch_softmax_ce_distill(z, t, w, primary, q, *kd, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
@@ -1119,7 +1136,7 @@ void Net::begin_fit(int64_t total_steps) {
     // steps/s replayed vs 2 625 launched eagerly (its stream is kept busy either way: ~50 kernels of ~8 us per step,
     // the host launches faster than that), and the pop-40 bench is 1.5 % slower replayed (2 089 vs 2 121 evals/h).
     static const bool use_graph = [] { const char* v = std::getenv("CMOOP_GRAPH"); return v && v[0] == '1'; }();
-    if (!use_graph || optim_finish_ || ema_on_ || quant_on_) graph_ok_ = false;
+    if (!use_graph || optim_finish_ || ema_on_ || quant_on_ || prune_on_) graph_ok_ = false;
 }
 
 // the per-iteration rates of the device-state steps, from the one host function the explicit-argument steps use
@@ -1171,6 +1188,7 @@ void Net::set_options(const TrainOptions& o) {
     if (o.ema && ema_enabled(*o.ema)) set_ema(o.ema);
     if (o.opoint && opoint_enabled(*o.opoint)) set_opoint(o.opoint);
     if (o.quant && quant_enabled(*o.quant)) set_quant(o.quant);
+    if (o.prune && prune_enabled(*o.prune)) set_prune(o.prune);
 }
 
 void Net::set_opoint(const OpointCfg* op) {
@@ -1292,7 +1310,7 @@ void Net::set_quant(const QuantCfg* quant) {
 
 void Net::quantize_now() {
     if (!quant_on_) return;
-    launch_quantize_weights(params_, wq_, nullptr, nullptr, qtab_, qtab_dev_, quant_cfg_.bits, stream_);
+    launch_quantize_weights(prune_on_ ? wp_ : params_, wq_, nullptr, nullptr, qtab_, qtab_dev_, quant_cfg_.bits, stream_);
 }
 
 int64_t Net::quant_size_bytes() {
@@ -1309,10 +1327,86 @@ void Net::get_quantized(float* wq_host, int8_t* codes_host, float* scales_host) 
     float* d_scales = pool.get<float>(std::max<size_t>((size_t)qtab_.total_channels, 1) * 4);
     CMOOP_HIP(hipMemcpyAsync(d_wq, params_, n * 4, hipMemcpyDeviceToDevice, stream_));
     CMOOP_HIP(hipMemsetAsync(d_codes, 0, n, stream_));
-    launch_quantize_weights(params_, d_wq, d_codes, d_scales, qtab_, qtab_dev_, quant_cfg_.bits, stream_);
+    const float* src = params_;
+    if (prune_on_) {   // prune, then quantise the pruned kernels: what inference reads
+        prune_now(prune_cfg_.sparsity);
+        src = wp_;
+    }
+    launch_quantize_weights(src, d_wq, d_codes, d_scales, qtab_, qtab_dev_, quant_cfg_.bits, stream_);
     if (wq_host) CMOOP_HIP(hipMemcpyAsync(wq_host, d_wq, n * 4, hipMemcpyDeviceToHost, stream_));
     if (codes_host) CMOOP_HIP(hipMemcpyAsync(codes_host, d_codes, n, hipMemcpyDeviceToHost, stream_));
     if (scales_host) CMOOP_HIP(hipMemcpyAsync(scales_host, d_scales, (size_t)qtab_.total_channels * 4, hipMemcpyDeviceToHost, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+}
+
+void Net::ensure_prune_table() {
+    if (ptab_skip_small_ == prune_cfg_.skip_small) return;
+    NetPlan plan;
+    plan.ops = ops_;
+    plan.n_params = n_params_;
+    ptab_ = prune_table(plan, prune_cfg_.skip_small != 0);
+    ptab_skip_small_ = prune_cfg_.skip_small;
+}
+
+void Net::set_prune(const PruneCfg* prune) {
+    if (prune) prune_check(*prune);
+    const bool on = prune != nullptr && prune_enabled(*prune);
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running
+    prune_cfg_ = on ? *prune : PruneCfg();
+    if (on) {
+        const bool fresh = wp_ == nullptr;
+        const int before = ptab_skip_small_;
+        ensure_prune_table();
+        if (fresh) {
+            wp_ = dalloc(n_params_);
+            ptab_dev_ = reinterpret_cast<PruneRow*>(dalloc(ptab_.rows.size() * sizeof(PruneRow) / sizeof(float) + 4));
+            uint32_t* words = reinterpret_cast<uint32_t*>(dalloc(prune_workspace_words((int)ptab_.rows.size())));
+            prune_workspace_init(prune_ws_, words, (int)ptab_.rows.size(), stream_);
+        }
+        if (fresh || before != ptab_skip_small_)   // the rows differ only in k: the same count, the same buffer
+            CMOOP_HIP(hipMemcpyAsync(ptab_dev_, ptab_.rows.data(), ptab_.rows.size() * sizeof(PruneRow), hipMemcpyHostToDevice, stream_));
+        CMOOP_HIP(hipStreamSynchronize(stream_)); // the table's upload is done: ptab_ may be rebuilt by a later call
+    }
+    prune_on_ = on;
+    if (on) graph_ok_ = false;                    // nothing is promised under CMOOP_GRAPH=1
+    drop_graph();
+}
+
+void Net::prune_now(double s) {
+    if (!prune_on_) return;
+    launch_prune_weights(params_, wp_, nullptr, ptab_, ptab_dev_, prune_ws_, s, stream_);
+}
+
+int Net::prune_rows() {
+    CMOOP_REQUIRE(prune_on_, "prune_rows: the option is off (set_prune with sparsity in (0, 1) first)");
+    return (int)ptab_.rows.size();
+}
+
+double Net::prune_achieved(const uint32_t* zeros) {
+    CMOOP_REQUIRE(prune_on_ && zeros, "prune_achieved: the option is off, or zeros is NULL");
+    int64_t z = 0, len = 0;
+    for (size_t i = 0; i < ptab_.rows.size(); ++i)
+        if (prune_row_k(ptab_.rows[i], prune_cfg_.sparsity) > 0) { z += zeros[i]; len += ptab_.rows[i].len; }
+    return len ? (double)z / (double)len : 0.0;
+}
+
+int64_t Net::prune_size_bytes() {
+    CMOOP_REQUIRE(prune_on_, "prune_size_bytes: the option is off (set_prune with sparsity in (0, 1) first)");
+    if (quant_on_) ensure_quant_table();
+    return cmoop::prune_size_bytes(ptab_, n_params_, prune_cfg_.sparsity, quant_on_ ? quant_cfg_.bits : 0,
+                                   quant_on_ ? qtab_.total_channels : 0);
+}
+
+void Net::get_pruned(float* weff_host, uint32_t* zeros_host) {
+    CMOOP_REQUIRE(prune_on_, "get_pruned: the option is off (set_prune with sparsity in (0, 1) first)");
+    PoolScope pool(stream_);   // a full-arena copy of this call: the net's own pruned arena holds kernel elements only
+    const size_t n = (size_t)n_params_, rows = ptab_.rows.size();
+    float* d_w = pool.get<float>(std::max<size_t>(n, 1) * 4);
+    uint32_t* d_zeros = pool.get<uint32_t>(std::max<size_t>(rows, 1) * 4);
+    CMOOP_HIP(hipMemcpyAsync(d_w, params_, n * 4, hipMemcpyDeviceToDevice, stream_));
+    launch_prune_weights(params_, d_w, d_zeros, ptab_, ptab_dev_, prune_ws_, prune_cfg_.sparsity, stream_);
+    if (weff_host) CMOOP_HIP(hipMemcpyAsync(weff_host, d_w, n * 4, hipMemcpyDeviceToHost, stream_));
+    if (zeros_host) CMOOP_HIP(hipMemcpyAsync(zeros_host, d_zeros, rows * 4, hipMemcpyDeviceToHost, stream_));
     CMOOP_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -1505,6 +1599,7 @@ void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch
 
 void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum, long long* correct, int32_t* preds) {
     CMOOP_HIP(hipMemsetAsync(acc_eval_, 0, 16, stream_));
+    prune_now(prune_cfg_.sparsity);   // prune on: once per call, the arena this pass reads at the FINAL sparsity
     quantize_now();   // quant on: once per call, on the arena this pass reads
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
@@ -1521,6 +1616,7 @@ void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum
 
 void Net::predict(const float* X, int64_t n, float* probs) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && probs)), "predict: NULL buffer");
+    prune_now(prune_cfg_.sparsity);
     quantize_now();
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
@@ -1532,6 +1628,7 @@ void Net::predict(const float* X, int64_t n, float* probs) {
 
 void Net::predict_logits(const float* X, int64_t n, float* logits) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && logits)), "predict_logits: NULL buffer");
+    prune_now(prune_cfg_.sparsity);
     quantize_now();
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
@@ -1561,6 +1658,7 @@ void Net::predict_stream(const float* feat, int64_t n_frames, int hop, bool db_s
         CMOOP_HIP(hipMemcpyAsync(ms, mean, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
         CMOOP_HIP(hipMemcpyAsync(ms + F_, scale, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
     }
+    prune_now(prune_cfg_.sparsity);
     quantize_now();
     for (int64_t w = 0; w < n; w += cfg_.eval_batch) {       // window i sits at position i % eval_batch of chunk i / eval_batch
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - w);
@@ -1640,6 +1738,10 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
     if (net.quant_on()) {   // the size of the model the fit trains and scores; size_mb stays the fp32 bytes
         res.quant[0] = (double)net.quant_size_bytes() / (1024.0 * 1024.0);
         res.quant[1] = (double)net.quant().bits;
+    }
+    if (net.prune_on()) {   // the size of the sparse model the fit scores (with the quantiser's bits when both are on)
+        res.prune[0] = (double)net.prune_size_bytes() / (1024.0 * 1024.0);
+        res.prune[1] = net.prune().sparsity;
     }
 
     PoolScope pool(stream);   // everything below goes back once the stream has drained, however the fit ends
@@ -1732,6 +1834,11 @@ EvalResult fit_and_read_out(Net& net, const NetConfig& cfg, const Dataset& ds, u
         net.store_opoint(classes.data(), res.opoint);
     } else {
         net.store_opoint(nullptr, nullptr);
+    }
+    if (net.prune_on()) {   // the zero fraction of the pruned tensors of the model that was just scored
+        std::vector<uint32_t> zeros((size_t)net.prune_rows());
+        net.get_pruned(nullptr, zeros.data());
+        res.prune[2] = net.prune_achieved(zeros.data());
     }
     res.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return res;

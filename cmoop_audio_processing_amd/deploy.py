@@ -58,6 +58,11 @@ class TrainedModel:
     quant_bits: Optional[int] = None
     quant_codes: Optional[np.ndarray] = None
     quant_scales: Optional[np.ndarray] = None
+    # a model trained under EvalConfig.prune (prune.py): the final sparsity and, per kernel tensor in arena order, the number
+    # of elements k the pruning had to zero (0 for a tensor it copied); ``params`` then holds the pruned kernels (quantised on
+    # top when the model carries codes as well), so every fp32 path scores the sparse model.  Both or neither
+    prune_sparsity: Optional[float] = None
+    prune_k: Optional[np.ndarray] = None
 
     def __post_init__(self):
         self.gene = tuple(int(v) for v in self.gene)
@@ -99,6 +104,46 @@ class TrainedModel:
             if not np.array_equal(back.view(np.uint32), self.params.view(np.uint32)):
                 raise ValueError("params do not equal float32(quant_codes) * quant_scales at the kernel tensors")
 
+        if (self.prune_sparsity is None) != (self.prune_k is None):
+            raise ValueError("prune_sparsity and prune_k come together (both or neither)")
+        if self.prune_k is not None:
+            self.prune_sparsity = float(self.prune_sparsity)
+            if not 0.0 < self.prune_sparsity < 1.0:
+                raise ValueError("prune_sparsity must be in (0, 1)")
+            self.prune_k = np.ascontiguousarray(self.prune_k, np.int64).reshape(-1)
+            spans = self._kernel_spans()
+            if self.prune_k.size != len(spans):
+                raise ValueError(f"prune_k must hold one value per kernel tensor ({len(spans)})")
+            for (name, off, n), k in zip(spans, self.prune_k):
+                zeros = int(((self.params[off:off + n].view(np.uint32) & np.uint32(0x7FFFFFFF)) == 0).sum())
+                if not 0 <= k <= n or zeros < k:
+                    raise ValueError(f"{name} holds {zeros} zeros, its prune_k asks for at least {int(k)}")
+
+    def _kernel_spans(self):
+        """[(name, offset in ``params``, elements)] of the kernel tensors in arena order (the rows of ``prune.prune_table``)."""
+        out, off = [], 0
+        for name, shape, role in G.param_tensors(self.gene, G.VARIANT_NAMES[self.variant], self.classes):
+            n = int(np.prod(shape))
+            if role == "kernel":
+                out.append((name, off, n))
+            off += n
+        return out
+
+    def sparsity_report(self) -> Dict[str, Dict[str, float]]:
+        """{kernel tensor name: {"elements", "zeros", "k", "sparsity"}} plus "total" over the tensors with k > 0 (zeros /
+        elements there, 0.0 when there is none) of a model that carries ``prune_k``; raises otherwise.  ``zeros`` counts +0.0
+        and -0.0 in ``params``, so it is at least ``k`` and more when keys tied at the threshold or weights were zero anyway."""
+        if self.prune_k is None:
+            raise ValueError("the model carries no pruned weights (train it under EvalConfig.prune)")
+        out, tz, tn = {}, 0, 0
+        for (name, off, n), k in zip(self._kernel_spans(), self.prune_k):
+            zeros = int(((self.params[off:off + n].view(np.uint32) & np.uint32(0x7FFFFFFF)) == 0).sum())
+            out[name] = {"elements": n, "zeros": zeros, "k": int(k), "sparsity": zeros / n}
+            if k > 0:
+                tz, tn = tz + zeros, tn + n
+        out["total"] = {"elements": tn, "zeros": tz, "k": int(self.prune_k.sum()), "sparsity": tz / tn if tn else 0.0}
+        return out
+
     def tensors(self) -> Dict[str, np.ndarray]:
         """{name: array} in the shapes of ``genes.param_tensors`` (views of ``params``)."""
         out, off = {}, 0
@@ -131,7 +176,8 @@ class TrainedModel:
         front end, whose ``frontend_int[5]`` is 0; ``frontend_pcen`` (s, alpha, delta, r, eps, input_scale) only when
         the front end carries a ``PcenConfig``.  A model without a front end, or with a log or dB one, writes the keys
         it always wrote.  ``thresholds`` (float32 [classes]) only when the model carries them; ``quant_bits`` (int64 [1]),
-        ``quant_codes`` (int8) and ``quant_scales`` (float32) only when it carries quantised weights."""
+        ``quant_codes`` (int8) and ``quant_scales`` (float32) only when it carries quantised weights; ``prune_sparsity`` (float64
+        [1]) and ``prune_k`` (int64) only when it carries pruned ones."""
         d = {"gene": np.asarray(self.gene, np.int32),
              "meta": np.asarray([G.VARIANT_NAMES[self.variant], self.classes, self.T, self.F, self.seed], np.int64),
              "params": self.params,
@@ -154,6 +200,8 @@ class TrainedModel:
         if self.quant_codes is not None:
             d["quant_bits"] = np.asarray([self.quant_bits], np.int64)
             d["quant_codes"], d["quant_scales"] = self.quant_codes, self.quant_scales
+        if self.prune_k is not None:
+            d["prune_sparsity"], d["prune_k"] = np.asarray([self.prune_sparsity], np.float64), self.prune_k
         with open(path, "wb") as f:
             np.savez(f, **d)
 
@@ -180,9 +228,12 @@ class TrainedModel:
             if "quant_codes" in z.files:
                 quant = dict(quant_bits=int(z["quant_bits"][0]), quant_codes=z["quant_codes"].copy(),
                              quant_scales=z["quant_scales"].copy())
+            prune = {}
+            if "prune_k" in z.files:
+                prune = dict(prune_sparsity=float(z["prune_sparsity"][0]), prune_k=z["prune_k"].copy())
             return cls(gene=tuple(int(v) for v in z["gene"]), variant=G.VARIANT_CODES[variant], classes=classes, T=T, F=F, seed=seed,
                        params=z["params"].copy(), objectives=obj, frontend=fe, mean=mean, scale=scale,
-                       thresholds=thresholds, **quant)
+                       thresholds=thresholds, **quant, **prune)
 
     def session(self, config: Optional[EvalConfig] = None):
         """A ``NetSession`` holding these parameters (needs the GPU).  ``config`` supplies ``eval_batch`` and the like;

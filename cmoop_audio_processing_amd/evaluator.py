@@ -40,6 +40,7 @@ from .optim import OptimConfig
 from .ema import EmaConfig
 from .opoint import OperatingPointConfig
 from .quant import QuantConfig
+from .prune import PruneConfig
 
 FPR_CODES = {"v1": 0, "v1_quirk": 1, "v3": 2}
 ACC_CODES = {"last": 0, "evaluate": 1}
@@ -111,6 +112,13 @@ class EvalConfig:
     # "bits"}; with objective=True (the default) that size takes the place of size_mb in objs and in the size constraint, so
     # the objective vector describes one model.  Travels beside opoint_struct(), as quant_struct()
     quant: Optional[QuantConfig] = None
+    # magnitude pruning of every candidate's fit (prune.py): train steps prune the latent kernels along a cubic sparsity ramp,
+    # validation, early stopping and the read-outs see the model at the FINAL sparsity (so val_loss before end_step is that of a
+    # net not yet adapted to it); the gradients go straight through to the dense latent weights.  None or sparsity 0 = off,
+    # every number, row and dict as without the field (cmoop_net_set_prune).  Result dicts gain "prune": {"size_mb",
+    # "sparsity"}; with objective=True (the default) that size -- pruned and, with quant on, quantised -- takes the place of
+    # size_mb in objs and in the size constraint.  Travels beside quant_struct(), as prune_struct()
+    prune: Optional[PruneConfig] = None
 
     @staticmethod
     def preset(script: str, **over) -> "EvalConfig":
@@ -193,6 +201,21 @@ class EvalConfig:
         if self.quant is None or not self.quant.enabled:
             return None
         return self.quant.check()._struct()
+
+    def prune_struct(self) -> Optional["_lib.Prune"]:
+        """The enabled pruner as a ``cmoop_prune``, checked; None when it is off."""
+        if self.prune is None or not self.prune.enabled:
+            return None
+        return self.prune.check()._struct()
+
+    def prune_size_mb(self, gene) -> Optional[float]:
+        """``genes.prune_size_mb`` of a candidate under this config (with the quantiser's bits when that is on too); None
+        when pruning is off."""
+        if self.prune_struct() is None:
+            return None
+        bits = int(self.quant.bits) if self.quant_struct() is not None else 0
+        return float(G.prune_size_mb(gene, G.VARIANT_NAMES[self.variant], self.classes,
+                                     self.prune.sparsity, bits, self.prune.skip_small))
 
     def option_structs(self, T: int, F: int, teacher_logits, n_train: int):
         """(augment, loss, distill, optim) of a fit on [T, F] patches against ``teacher_logits``: the four ``*_struct``
@@ -454,18 +477,18 @@ class PopulationEvaluator:
         return d
 
     def _population_call(self, genes, sd, n, cfg, next_cb, acc, size, fpr, ep, secs, done, op=None) -> None:
-        """THE population call: ``cmoop_eval_population_q`` with ``config.option_structs``, ``config.ema_struct``,
-        ``config.opoint_struct`` and ``config.quant_struct`` by reference, None (NULL) for whatever is off; next_cb None: the
+        """THE population call: ``cmoop_eval_population_p`` with ``config.option_structs``, ``config.ema_struct``,
+        ``config.opoint_struct``, ``config.quant_struct`` and ``config.prune_struct`` by reference, None (NULL) for whatever is off; next_cb None: the
         library's own longest-first counter, and ``done`` is then None too.  ``op``: float64 [n, 4] for the operating-point
         summaries, or None.  The quantised size is a closed form of the gene (``genes.quant_size_mb``, equal to what the call
-        would return): the result rows do not carry it."""
+        would return), and so is the pruned size (``genes.prune_size_mb``): the result rows do not carry them."""
         ds = self._dataset()
         opts = self.config.option_structs(self.T, self.F, self.teacher_logits, len(self.X_train)) + \
-            (self.config.ema_struct(), self.config.opoint_struct(), self.config.quant_struct())
-        _lib.check(_lib.lib().cmoop_eval_population_q(
+            (self.config.ema_struct(), self.config.opoint_struct(), self.config.quant_struct(), self.config.prune_struct())
+        _lib.check(_lib.lib().cmoop_eval_population_p(
             C.byref(cfg), *(C.byref(o) if o is not None else None for o in opts), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
             C.c_int32(n), C.cast(next_cb, C.c_void_p) if next_cb is not None else None, None, _lib.ptr(acc), _lib.ptr(size),
-            _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done), _lib.ptr(op), None))
+            _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done), _lib.ptr(op), None, None))
 
     @property
     def row_width(self) -> int:
@@ -583,6 +606,14 @@ class PopulationEvaluator:
                     d = pack_result(ind, acc, q_mb, fpr, c, r[5:9] if w == 10 else None)
                     d["size_fp32_mb"] = size_mb
                 d["quant"] = {"size_mb": q_mb, "bits": int(c.quant.bits)}
+            if c.prune_struct() is not None:    # as the quantised size: a closed form of the gene
+                p_mb = c.prune_size_mb(G.normalize_hparams(ind))
+                if c.prune.objective:           # the model the fit scored: pruned and, with quant on, quantised
+                    extra = {k: d[k] for k in ("quant",) if k in d}
+                    d = pack_result(ind, acc, p_mb, fpr, c, r[5:9] if w == 10 else None)
+                    d.update(extra)
+                    d["size_fp32_mb"] = size_mb
+                d["prune"] = {"size_mb": p_mb, "sparsity": float(c.prune.sparsity)}
             results.append(d)
         return results
 
@@ -595,7 +626,9 @@ class PopulationEvaluator:
         Under ``config.quant`` the model's ``params`` are the quantised arena (``NetSession.get_quantized``: kernels
         dequantised), so a plain fp32 ``session()``, ``logits()`` and ``StreamScorer`` score exactly the model the fit scored,
         and it carries ``quant_bits`` / ``quant_codes`` / ``quant_scales``; ``objectives["size_mb"]`` is then the quantised
-        size when ``quant.objective``.
+        size when ``quant.objective``.  Under ``config.prune`` ``params`` are the arena pruned at the final sparsity
+        (``NetSession.get_pruned``; quantised on top when both are on) and the model carries ``prune_sparsity`` and the
+        per-tensor ``prune_k``; ``objectives["size_mb"]`` is then the pruned size when ``prune.objective``.
         ``hparams`` is the reference's dict or a gene tuple; ``frontend`` / ``mean`` / ``scale`` (the front end and the
         StandardScaler the features were made with) ride along for ``StreamScorer``."""
         from .deploy import TrainedModel
@@ -606,20 +639,29 @@ class PopulationEvaluator:
         with NetSession(g, self.config, self.T, self.F, int(seed)) as net:
             net.set_distill(teacher_logits=self.teacher_logits)      # config.distill, or off
             r = net.fit(self.X_train, self.y_train, self.X_val, self.y_val)
-            params, codes, scales = net.get_params(), None, None
+            params, codes, scales, prune_k = net.get_params(), None, None, None
+            if net.prune is not None:   # the pruned arena; under quant as well get_quantized returns it quantised
+                from . import prune as PR
+                params, zeros = net.get_pruned()
+                rows = PR.prune_table(g, G.VARIANT_NAMES[self.config.variant], int(self.config.classes), net.prune.skip_small)
+                prune_k = np.asarray([PR.row_k(row, net.prune.sparsity) for row in rows], np.int64)
+                assert (zeros.astype(np.int64) >= prune_k).all()
             if net.quant is not None:
                 params, codes, scales = net.get_quantized()
         v = G.VARIANT_NAMES[self.config.variant]
         size_mb = G.model_size_mb(g, v, self.config.classes)
         if codes is not None and self.config.quant.objective:
             size_mb = G.quant_size_mb(g, v, self.config.classes, self.config.quant.bits)
+        if prune_k is not None and self.config.prune.objective:
+            size_mb = self.config.prune_size_mb(g)
         objectives = {"acc": float(r["acc"]), "size_mb": float(size_mb), "fpr": float(r["fpr"]),
                       "epochs_run": int(r["epochs_run"])}
         thresholds = r["operating_point"]["thresholds"] if "operating_point" in r else None     # config.operating_point on
         return TrainedModel(gene=g, variant=self.config.variant, classes=int(self.config.classes), T=self.T, F=self.F,
                             seed=int(seed), params=params, objectives=objectives, frontend=frontend, mean=mean, scale=scale,
                             thresholds=thresholds, quant_bits=int(self.config.quant.bits) if codes is not None else None,
-                            quant_codes=codes, quant_scales=scales)
+                            quant_codes=codes, quant_scales=scales,
+                            prune_sparsity=float(self.config.prune.sparsity) if prune_k is not None else None, prune_k=prune_k)
 
     def _print(self, r):
         if self.config.verbose:

@@ -274,6 +274,42 @@ def quant_size_mb(g: Sequence[int], variant: int, classes: int, bits: int) -> fl
     return quant_size_bytes(g, variant, classes, bits) / (1024 ** 2)
 
 
+def prune_size_bytes(g: Sequence[int], variant: int, classes: int, sparsity: float, bits: int = 0, skip_small: bool = True) -> int:
+    """Bytes of the candidate pruned at ``sparsity`` (prune.py; the twin of ``cmoop_prune_size_bytes``): per pruned tensor
+    with k = floor(sparsity * len) > 0 a ceil(len / 8) byte mask and its len - k values, 4 bytes each, or with ``bits`` in 2..8
+    (quantisation on as well) packed ceil((len - k) * bits / 8); every other kernel tensor and parameter as ``model_size_mb``
+    (``bits`` 0) or ``quant_size_bytes`` counts it (packed kernels, 4 bytes per channel scale).  The first convolution and the
+    depthwise kernels are not pruned under ``skip_small``.  An upper bound on the stored model when keys tie at the threshold."""
+    import math
+    bits, sparsity = int(bits), float(sparsity)
+    if bits != 0 and not 2 <= bits <= 8:
+        raise ValueError("bits must be 0 or in [2, 8]")
+    if not 0.0 <= sparsity < 1.0:
+        raise ValueError("sparsity must be in [0, 1)")
+    total = channels = kernel_elems = 0
+    first = True
+    for name, shape, role in param_tensors(g, variant, classes):
+        if role != "kernel":
+            continue
+        n = 1
+        for d in shape:
+            n *= int(d)
+        small = first or name.endswith("/depthwise_kernel")
+        first = False
+        k = 0 if (small and skip_small) else int(math.floor(sparsity * float(n)))
+        if k > 0:
+            total += (n + 7) // 8
+        total += ((n - k) * bits + 7) // 8 if bits else 4 * (n - k)
+        channels += int(shape[2]) if name.endswith("/depthwise_kernel") else int(shape[0])
+        kernel_elems += n
+    return total + (4 * channels if bits else 0) + 4 * (param_count(g, variant, classes) - kernel_elems)
+
+
+def prune_size_mb(g: Sequence[int], variant: int, classes: int, sparsity: float, bits: int = 0, skip_small: bool = True) -> float:
+    """``prune_size_bytes`` / 2**20, in float64: what the population call returns next to ``size_mb``."""
+    return prune_size_bytes(g, variant, classes, sparsity, bits, skip_small) / (1024 ** 2)
+
+
 def fwd_flops_per_sample(g: Sequence[int], variant: int, classes: int, T: int, F: int) -> int:
     """Algorithmic forward FLOPs per sample, 2*MAC for conv/dense only."""
     f, k, _, R, fc, _ = (int(v) for v in g)

@@ -27,9 +27,10 @@ class NetSession:
         _lib.check(_lib.lib().cmoop_net_total_params(self._h, C.byref(n)))
         self.n_params = int(n.value)
         self.T, self.F = int(T), int(F)
-        self.augment = self.loss = self.optim = self.ema = self.opoint = self.quant = None
+        self.augment = self.loss = self.optim = self.ema = self.opoint = self.quant = self.prune = None
         for name, setter in (("augment", self.set_augment), ("loss", self.set_loss), ("optim", self.set_optim),
-                             ("ema", self.set_ema), ("operating_point", self.set_operating_point), ("quant", self.set_quant)):
+                             ("ema", self.set_ema), ("operating_point", self.set_operating_point), ("quant", self.set_quant),
+                             ("prune", self.set_prune)):
             if getattr(config, name, None) is not None:
                 try:
                     setter(getattr(config, name))
@@ -201,6 +202,28 @@ class NetSession:
         wq, codes, scales = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.int8), np.empty(channels, np.float32)
         _lib.check(_lib.lib().cmoop_net_get_quantized(self._h, _lib.ptr(wq), _lib.ptr(codes), _lib.ptr(scales)))
         return wq, codes, scales
+
+    def set_prune(self, prune) -> None:
+        """Magnitude pruning (``PruneConfig``) of every following train step and inference call of this net.  None or sparsity
+        0 turns it off (``self.prune`` is then None), and the net is bit for bit one that never had it.  On, every train step
+        first prunes the latent kernels at ``prune.sparsity_at(cfg, iteration)`` and runs forward and backward on them (the
+        gradients go unchanged to the dense latent weights), and ``evaluate`` / ``predict_proba`` / ``predict_logits`` /
+        ``predict_stream`` prune the arena they read at the final sparsity; with ``set_quant`` on as well the pruned kernels
+        are quantised.  ``get_params`` / ``set_params`` / ``get_state`` keep meaning the latent fp32 weights.  Switched on after
+        a plain fit it is one-shot magnitude pruning."""
+        self._set("cmoop_net_set_prune", None if prune is None else prune.check()._struct())
+        self.prune = prune if prune is not None and prune.enabled else None
+
+    def get_pruned(self):
+        """(w_eff float32 [n_params]: the arena inference would read now pruned at the final sparsity, not quantised, every
+        element outside the pruned tensors a copy; zeros uint32 [kernel tensors]: the elements of each tensor that became
+        zero); raises while the option is off.  Equal, bit for bit, to ``prune.prune_params_ref`` of that arena."""
+        from . import prune as PR
+        v = G.VARIANT_NAMES[self.config.variant]
+        rows = len(PR.prune_table(self.gene, v, int(self.config.classes)))
+        w, zeros = np.empty(self.n_params, np.float32), np.empty(rows, np.uint32)
+        _lib.check(_lib.lib().cmoop_net_get_pruned(self._h, _lib.ptr(w), _lib.ptr(zeros)))
+        return w, zeros
 
     def optim_stats(self) -> dict:
         """The last train step's optimiser read-out: dict(sumsq, norm, scale, path) -- the float64 sum of squares of the

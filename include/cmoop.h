@@ -96,11 +96,11 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 
 /* compute_objectives_and_constraints' inner loop (nsga_penalty.py:426-427): evaluate n
  * candidates; outputs are host arrays of length n (any may be NULL).
- * THE POPULATION CALL.  The nine cmoop_eval_population* symbols are ONE call, cmoop_eval_population_q, each with fewer
+ * THE POPULATION CALL.  The ten cmoop_eval_population* symbols are ONE call, cmoop_eval_population_p, each with fewer
  * of its arguments: next (with ctx and evaluated; NULL: the library's own longest-first queue, evaluated may then be
- * NULL too) and the seven options aug, loss, distill, optim, ema, op, q (cmoop_augment, cmoop_loss, cmoop_distill,
- * cmoop_optim, cmoop_ema, cmoop_opoint, cmoop_quant below, checked in that order).  An option that is NULL or disabled gives
- * exactly -- launch for launch, bit for bit -- the call without it, so a caller may always take _q and pass NULL for what is off. */
+ * NULL too) and the eight options aug, loss, distill, optim, ema, op, q, pr (cmoop_augment, cmoop_loss, cmoop_distill,
+ * cmoop_optim, cmoop_ema, cmoop_opoint, cmoop_quant, cmoop_prune below, checked in that order).  An option that is NULL or disabled
+ * gives exactly -- launch for launch, bit for bit -- the call without it, so a caller may always take _p and pass NULL for what is off. */
 int cmoop_eval_population(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
                           const uint32_t* seeds /* [n] */, int32_t n, double* acc, double* size_mb, double* fpr,
                           int32_t* epochs_run, double* val_loss, double* seconds);
@@ -489,15 +489,91 @@ int cmoop_quantize_weights(const cmoop_quant* q, const float* w_dev, int64_t n, 
  * warm-up launches */
 int cmoop_quantize_weights_time(const cmoop_quant* q, const float* w_dev, int64_t n, const int64_t* rows_host, int32_t count,
                                 float* wq_dev, int8_t* codes_dev, float* scales_dev, int32_t iters, double* avg_ms);
-/* the population call (above) with every argument: the other eight forward here.  q NULL or disabled: cmoop_eval_population_op's
- * launches and bytes, and quant (may be NULL) receives zeros; enabled: quant [n][2] receives every candidate's
- * {quant_size_bytes / 2^20, bits} */
+/* the population call (above) with every argument but the pruner: forwards to cmoop_eval_population_p with NULL, NULL.  q NULL or
+ * disabled: cmoop_eval_population_op's launches and bytes, and quant (may be NULL) receives zeros; enabled: quant [n][2] receives
+ * every candidate's {quant_size_bytes / 2^20, bits} */
 int cmoop_eval_population_q(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
                             const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_quant* q,
                             const cmoop_dataset* ds, const int32_t* genes /* [n][6] */, const uint32_t* seeds /* [n] */, int32_t n,
                             cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
                             double* val_loss, double* seconds, int32_t* evaluated, double* opoint /* [n][4], may be NULL */,
                             double* quant /* [n][2], may be NULL */);
+
+/* ---- magnitude pruning in training: sparse kernels inside the train step, their size, their export (opt-in, off by default).
+ * BUILD-DEFINED: the reference trains and sizes a dense model and has no counterpart; with no prune config, or a disabled one,
+ * every launch and every bit is that of a build without it.  No accuracy figure is claimed.
+ *   Pruned tensors   every convolution kernel after the first one ([C_out][kh][kw][C_in], the pointwise kernels of the
+ *              depthwise-separable variants included) and every dense kernel ([out][in]), each as ONE tensor of len elements.
+ *              The first convolution and the depthwise kernels (a small share of the parameters) are copied unchanged unless
+ *              skip_small = 0.  Biases, BatchNorm and the moving statistics are never touched.
+ *   The operator, per tensor, at sparsity s (a double), with no floating-point compare:
+ *     key_i = bits(w_i) & 0x7FFFFFFF as uint32: a NaN outranks inf, -0.0 has key 0.
+ *     k     = floor(s * len) in IEEE double.  k = 0: the tensor is copied bit for bit.
+ *     else t = the k-th smallest key (1-indexed) and w_eff_i = (key_i <= t) ? +0.0f : w_i.
+ *     So at least k elements are pruned, exactly k unless keys tie at t, and the result does not depend on any order.
+ *     numpy: t = np.partition(keys, k-1)[k-1]; keep = keys > t.
+ *   Schedule (TF-MOT's PolynomialDecay, power 3, initial sparsity 0), `it` the Adam iteration the step is about to take:
+ *     s(it) = 0 for it < begin_step; s(it) = sparsity for it >= end_step or end_step <= begin_step; otherwise
+ *     s(it) = sparsity * (1 - (1-u)*(1-u)*(1-u)), u = (it - begin_step) / (double)(end_step - begin_step): double products, no pow.
+ *   Straight-through: every train step first prunes the latent kernels at s(it) into an effective arena (FOUR launches: an exact
+ *     radix select on the keys, 11 / 10 / 10 bits, then the threshold pass; one launch when every k is 0); forward, backward and
+ *     the flip-transposed dgrad operands read kernels from that arena; the gradients go unchanged to the DENSE latent fp32
+ *     weights, so a pruned weight can regrow.  The optimiser, Adam's moments, the EMA, the snapshots and cmoop_net_get_params /
+ *     _set_params / _get_state / _set_state see latent weights only.
+ *   Inference ALWAYS prunes at the final `sparsity`, whatever the iteration: cmoop_net_evaluate, _predict, _predict_logits,
+ *     _predict_stream, the operating-point pass and every validation pass of a fit prune the arena they are about to read (the
+ *     average under cmoop_net_use_ema).  A fit therefore validates, early-stops and snapshots on the model it would ship if it
+ *     stopped now; restore_best restores latent weights and the read-out re-prunes them, which is deterministic, so it is the
+ *     same model.  CONSEQUENCE: val_loss before end_step is that of a net that has not yet adapted to its final sparsity, and
+ *     early stopping sees it; choose end_step (and patience) accordingly.
+ *   With cmoop_quant on as well: prune, then quantise the pruned kernels; a pruned element has code 0.
+ *   The step is not captured as a graph while the option is on.
+ *   Size: prune_size_bytes = per pruned tensor with k > 0 at the final sparsity ceil(len / 8) mask bytes + its (len - k) values,
+ *     4 bytes each, or with the quantiser on packed ceil((len - k) * bits / 8); every other tensor and parameter as size_mb or
+ *     quant_size_bytes counts it.  An upper bound on the stored model when keys tie at t.
+ * Domain: sparsity 0 or in (0, 1), begin_step >= 0, end_step >= 0, objective and skip_small in {0, 1}.  A config is ENABLED iff
+ * sparsity != 0.  objective is read by the host layers only (1: the evaluator puts the pruned size in the place of size_mb). */
+typedef struct cmoop_prune {
+    double sparsity;      /* the final sparsity; 0 = off, else in (0, 1) */
+    int32_t begin_step;   /* Adam iterations */
+    int32_t end_step;
+    int32_t objective;    /* 0 / 1 */
+    int32_t skip_small;   /* 1 (default): the first convolution and the depthwise kernels are copied */
+} cmoop_prune;            /* 24 bytes */
+int cmoop_prune_default(cmoop_prune* p);   /* off: all zero but skip_small = 1 */
+/* host-only: non-zero + a message naming the offending field when the config is outside the domain */
+int cmoop_prune_check(const cmoop_prune* p);
+/* host-only: s(it) of the schedule above */
+int cmoop_prune_sparsity_at(const cmoop_prune* p, int64_t it, double* out);
+/* host-only: the kernel tensors of a candidate in arena order, rows [count][3] = {off, len, k}: k = -1 for a pruned tensor
+ * (k = floor(s len) at the s of each call), k = 0 for a copied one.  cap: rows the buffer holds (an error when too small); count
+ * may be NULL.  The elements covered are exactly those of kind 0 in cmoop_param_kinds. */
+int cmoop_prune_table(const int32_t gene[6], int32_t variant, int32_t classes, int32_t skip_small, int64_t* rows /* [cap][3] */,
+                      int32_t cap, int32_t* count);
+/* host-only: prune_size_bytes of a candidate at `sparsity` in [0, 1) and `bits` (0: fp32 values, else 2..8) */
+int cmoop_prune_size_bytes(const int32_t gene[6], int32_t variant, int32_t classes, double sparsity, int32_t bits, int32_t skip_small,
+                           int64_t* out);
+/* the launch sequence alone on the library stream: the tensors of rows_host [count][3] = {off, len, k} (as cmoop_prune_table
+ * gives them, or with an explicit k in [0, len]; at most 128 rows in arena order without overlap, every one inside the arena of
+ * n < 2^31 elements, else an error before any launch) of w_dev [n] into out_dev [n]; zeros_dev [count] uint32 (may be NULL)
+ * receives how many elements of each tensor became zero; launches (may be NULL) how many launches the call made (4, or 1 when
+ * every k is 0).  Writes ONLY the tensors' elements of out_dev. */
+int cmoop_prune_weights(const float* w_dev, int64_t n, const int64_t* rows_host /* [count][3] */, int32_t count, double s,
+                        float* out_dev, uint32_t* zeros_dev, int32_t* launches);
+/* average milliseconds of that sequence over `iters` back-to-back calls between two HIP events on the library stream, after 3
+ * warm-up calls */
+int cmoop_prune_weights_time(const float* w_dev, int64_t n, const int64_t* rows_host, int32_t count, double s, float* out_dev,
+                             uint32_t* zeros_dev, int32_t iters, double* avg_ms);
+/* the population call (above) with every argument: the other nine forward here.  pr NULL or disabled: cmoop_eval_population_q's
+ * launches and bytes, and prune (may be NULL) receives zeros; enabled: prune [n][3] receives every candidate's
+ * {prune_size_bytes / 2^20, sparsity, zero fraction of the pruned tensors of the scored model} */
+int cmoop_eval_population_p(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                            const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_quant* q,
+                            const cmoop_prune* pr, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
+                            const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
+                            double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated,
+                            double* opoint /* [n][4], may be NULL */, double* quant /* [n][2], may be NULL */,
+                            double* prune /* [n][3], may be NULL */);
 
 /* host-only: does every conv layer of this candidate at `batch` rows per launch (pass max(batch, eval_batch)) stay inside
  * the kernels' 32-bit byte offsets (each activation / kernel tensor below 2^29 elements)?  Non-zero + message if not;
@@ -755,6 +831,15 @@ int cmoop_net_set_quant(cmoop_net* net, const cmoop_quant* q /* NULL = off */);
  * dequantised, every other element copied), codes_host [total params] int8 (the code of every kernel element at its arena
  * index, 0 elsewhere), scales_host [total channels of cmoop_quant_table]; any may be NULL.  An error while the option is off. */
 int cmoop_net_get_quantized(cmoop_net* net, float* wq_params_host, int8_t* codes_host, float* scales_host);
+/* Magnitude pruning (cmoop_prune above) of every following train step and inference call of this net (NULL or a disabled config:
+ * off, and the net is one that never had it, launch for launch and bit for bit).  The config is copied.  Switching it on after a
+ * plain fit and evaluating is one-shot magnitude pruning.  With cmoop_net_set_quant on as well, cmoop_net_get_quantized returns
+ * the pruned kernels quantised. */
+int cmoop_net_set_prune(cmoop_net* net, const cmoop_prune* p /* NULL = off */);
+/* the arena inference would read now (the average under cmoop_net_use_ema) pruned at the final sparsity, not quantised:
+ * weff_params_host [total params] (every element outside the pruned tensors copied) and zeros_host [count of cmoop_prune_table]
+ * uint32, the elements of each tensor that became zero; either may be NULL.  An error while the option is off. */
+int cmoop_net_get_pruned(cmoop_net* net, float* weff_params_host, uint32_t* zeros_host);
 /* cmoop_net_train_step_targets with a teacher row per batch row, q_dev [B][classes], and the distillation loss at
  * (alpha, temperature), whatever cmoop_net_set_distill says. */
 int cmoop_net_train_step_distill_targets(cmoop_net* net, const float* x_rows_dev, const float* t_dev, const float* w_dev,
