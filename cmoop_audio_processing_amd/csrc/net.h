@@ -191,6 +191,16 @@ struct Op {
     int fused_into_bn = 0;     // pool: executed inside the preceding BatchNorm's fused kernels
 };
 
+// One KIND_KERNEL tensor of a plan (ops[op], of that kind): `channels` output channels of `len` elements, element e of channel
+// c at off + c * chan_stride + e * elem_stride ([Cout][k k Cin] kernels: (len, 1); a depthwise [k][k][C] kernel: (1, C))
+struct KernelTensor {
+    int op;
+    OpKind kind;
+    int64_t off;
+    int channels, len, chan_stride, elem_stride;
+    int64_t elems() const { return (int64_t)channels * len; }
+};
+
 // The op list and activation shapes of a candidate, from the six genes: host arithmetic only.  Net::build_plan allocates
 // for it; check_plan_ranges, cmoop_plan_convs and cmoop_net_launch_plan walk it without a device.
 struct NetPlan {
@@ -198,6 +208,8 @@ struct NetPlan {
     std::vector<Op> ops;
     int logits = -1;
     int64_t n_params = 0;
+    // THE walk over the kernel tensors, in arena order (under param_kinds, the quant / prune tables, the seeded init, the flip table)
+    std::vector<KernelTensor> kernel_tensors() const;
     // ParamKind of every arena element: conv / depthwise / pointwise / dense kernels, other trainable tensors (biases, gamma,
     // beta), BatchNorm moving statistics
     std::vector<uint8_t> param_kinds() const;
@@ -209,12 +221,10 @@ struct NetPlan {
     std::string launch_plan(int batch, int Bmax, int B, bool train) const;
 };
 NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F);
-// host-only: the quantisation table of a plan (kernels.h, QuantTable), one row per KIND_KERNEL tensor in arena order, finalised
-// against plan.n_params: the elements it covers are exactly those param_kinds() calls KIND_KERNEL
+// host-only: the quantisation and the pruning table of a plan (kernels.h), one row per kernel_tensors() entry, finalised against
+// plan.n_params.  Pruning rows have k = -1 (pruned at the sparsity of each launch); with skip_small the first convolution and
+// the depthwise kernels have k = 0 (copied)
 QuantTable quant_table(const NetPlan& plan);
-// host-only: the pruning table of a plan (kernels.h, PruneTable), one row per KIND_KERNEL tensor in arena order, finalised
-// against plan.n_params.  OP_CONV and OP_DENSE kernels have k = -1 (pruned at the sparsity of each launch); the first
-// convolution and the depthwise kernels have k = 0 (copied) unless skip_small is false
 PruneTable prune_table(const NetPlan& plan, bool skip_small = true);
 
 // The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
@@ -308,12 +318,10 @@ class Net : public GemmHook {
     // Quantisation-aware training (kernels.h) of every following train step and inference call; null or a disabled config: off,
     // and every launch and bit is that of a net that never had one (the quantised arena, once allocated, is kept).  Enabled:
     // the domain is checked; on first use the table is built from the plan and uploaded and the quantised arena allocated.
-    // Every train step then first runs launch_quantize_weights on the latent weights; forward, backward and the flip-transposed
-    // dgrad operands read the kernels from the quantised arena and everything else (biases, gamma, beta, moving statistics --
-    // and BatchNorm's moving-statistics writes) from the parameter arena; the gradients go unchanged to the latent weights
-    // (straight-through).  evaluate / predict / predict_logits / predict_stream run the launch once at their start on the arena
-    // they are about to read (the average under use_average).  The optimiser, Adam's moments, the EMA, get/set_params and the
-    // snapshots keep meaning the latent weights.  The step is no longer captured as a graph
+    // Every train step and inference call then starts with the weight stage (stage_kernels); forward, backward and the
+    // flip-transposed dgrad operands read the kernels from the arena it returns and everything else (biases, gamma, beta, moving
+    // statistics and their writes) from the parameter arena; the gradients go unchanged to the latent weights (straight-through),
+    // which the optimiser, the EMA, get/set_params and the snapshots keep meaning.  The step is no longer captured as a graph
     void set_quant(const QuantCfg* quant);
     bool quant_on() const { return quant_on_; }
     const QuantCfg& quant() const { return quant_cfg_; }
@@ -324,13 +332,8 @@ class Net : public GemmHook {
     // Magnitude pruning (kernels.h) of every following train step and inference call; null or a disabled config: off, and every
     // launch and bit is that of a net that never had one (the pruned arena, once allocated, is kept).  Enabled: the domain is
     // checked; on first use the table is built from the plan and uploaded, the pruned arena and the select's workspace allocated.
-    // Every train step then first runs launch_prune_weights on the latent weights at prune_sparsity_at(cfg, iterations_);
-    // forward, backward and the flip-transposed dgrad operands read the kernels from the pruned arena (quant on as well: the
-    // quantiser reads the pruned arena, and they read the quantised one); the gradients go unchanged to the dense latent
-    // weights (straight-through), so a pruned weight can regrow.  evaluate / predict / predict_logits / predict_stream prune
-    // the arena they are about to read (the average under use_average) at the FINAL sparsity, whatever the iteration.  The
-    // optimiser, Adam's moments, the EMA, get/set_params and the snapshots keep meaning the latent weights.  The step is no
-    // longer captured as a graph
+    // As set_quant from there on: the weight stage of a train step prunes at prune_sparsity_at(cfg, iterations_), that of an
+    // inference call at the FINAL sparsity, whatever the iteration; straight-through, so a pruned weight can regrow
     void set_prune(const PruneCfg* prune);
     bool prune_on() const { return prune_on_; }
     const PruneCfg& prune() const { return prune_cfg_; }
@@ -394,25 +397,29 @@ class Net : public GemmHook {
     // rows: where the batch's rows lie in X (kernels.h); the first layer clamps by rows.n_rows in training only
     void forward(const float* X, const BatchRows& rows, int B, bool train);
     void backward(const float* X, const BatchRows& rows, int B);
-    void step_body(const float* X, const int32_t* y, const BatchRows& rows, int B);
-    // the loss of step_body's step: the targets launches set_loss / set_distill ask for, then the matching softmax_ce launch
+    // THE step: refused under use_average; weight stage at this iteration's sparsity, [gather: augment / mixup into batch_in_],
+    // forward, loss(), backward, optimiser_step.  rows.st: the device state the step reads and advances, null: host arguments
+    template <class Loss> void step_body(const float* X, const BatchRows& rows, int B, bool gather, Loss&& loss);
+    void gathered_step(const float* X, const int32_t* y, const BatchRows& rows, int B);   // step_body, gathering, with launch_train_loss
+    // the targets launches set_loss / set_distill ask for, then the matching softmax_ce launch
     void launch_train_loss(const int32_t* y, const BatchRows& rows, int B);
-    // the explicit-targets step both train_step_*targets share: forward on the caller's B rows, the soft-target loss (kd
-    // null) or the distillation loss against q, backward, Adam, counters
-    void targets_step(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
-                      const DistillParams* kd, int B);
+    template <class Body> void counted_step(Body&& body);   // body() under the step's ProfilingScope, then the counters advance
+    // THE inference pass: weight stage at the final sparsity, then per chunk of eval_batch rows (the last one partial)
+    // source(s, B) -> {X, rows} of rows [s, s + B), forward in inference mode, sink(s, B) on their logits
+    template <class Source, class Sink> void inference_pass(int64_t n, Source&& source, Sink&& sink);
     void optimiser_step(int B, const StepState* st);   // the tail of a step: weight-gradient slabs summed + Adam (+ state advance)
     void upload_rate_tables();                          // alpha_tab_ (and, on the finish + update path, lr_tab_) from optim_rates; ema_tab_ from ema_rates
     void ensure_kinds();                                // kinds_dev_, uploaded once (set_optim's finish path and set_ema share it)
-    void drop_graph();                                  // the captured step has the old launch sequence or counters
+    void option_changed(bool breaks_graph);             // every setter's tail: the captured step is stale; breaks_graph: and none is captured again
     void upload_step_state();                           // enqueues the device StepState at (0, step_, iterations_); no-op without one
     void ensure_target_buffers();                       // t / w / primary, allocated by the first enabled set_loss or set_distill
     void ensure_quant_table();                          // qtab_ from the plan, once (host only)
     void ensure_prune_table();                          // ptab_ from the plan and the config's skip_small (host only)
-    void prune_now(double s);                           // prune on: wp_ := kernels of the arena forward reads (params_), pruned at s
-    void quantize_now();                                // quant on: wq_ := quantised kernels of that arena, or of wp_ when prune is on
-    // where forward / backward read KIND_KERNEL tensors
-    const float* kernels() const { return quant_on_ ? wq_ : prune_on_ ? wp_ : params_; }
+    // THE weight stage, from params_ (the average under use_average).  Prune on: its kernels pruned at `sparsity` into wp (zeros:
+    // per-row counts, or null).  Quant on and wq given: the kernels of wp, else of params_, quantised into wq (codes / scales or
+    // null).  Returns the arena of the last stage that ran, params_ when none did: where forward / backward read kernel tensors
+    const float* stage_kernels(double sparsity, float* wp, uint32_t* zeros, float* wq, int8_t* codes, float* scales);
+    void refresh_kernels(double sparsity) { kernels_ = stage_kernels(sparsity, wp_, nullptr, wq_, nullptr, nullptr); }
     ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
 
@@ -421,11 +428,14 @@ class Net : public GemmHook {
     int T_, F_, Bmax_;
     uint32_t seed_;
     hipStream_t stream_;
-    std::vector<Act> acts_;
-    std::vector<Op> ops_;
+    NetPlan plan_;                      // the plan the net was built from; build_plan fills its acts' and ops' device pointers in place
+    std::vector<Act>& acts_ = plan_.acts;
+    std::vector<Op>& ops_ = plan_.ops;
+    const int& logits_ = plan_.logits;
+    const int64_t& n_params_ = plan_.n_params;
     std::vector<void*> allocs_;
-    int64_t n_params_ = 0;
     float *params_ = nullptr, *grads_ = nullptr, *adam_m_ = nullptr, *adam_v_ = nullptr, *snap_ = nullptr;
+    const float* kernels_ = nullptr;    // refresh_kernels
     float* weights_ = nullptr;          // the parameter arena; params_ (what forward reads) is this, or ema_ under use_average
     float* ema_ = nullptr;              // the average arena, allocated by the first enabled set_ema
     EmaCfg ema_cfg_;                    // set_ema; the default is off
@@ -485,7 +495,6 @@ class Net : public GemmHook {
     size_t wgrad_ws_floats_ = 0, wd_ws_floats_ = 0, red_ws_floats_ = 0, splitk_ws_floats_ = 0;
     double* acc_train_ = nullptr;   // [2]: loss sum, correct (int64 bits)
     double* acc_eval_ = nullptr;
-    int logits_ = -1;
     long long step_ = 0, iterations_ = 0;
     bool profiling_now_ = false, hook_live_ = false;
     int fused_stats_blocks_ = 0;   // > 0: the conv just launched left this many BatchNorm statistic partials in red_ws_

@@ -372,29 +372,33 @@ NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F) {
     return plan;
 }
 
+std::vector<KernelTensor> NetPlan::kernel_tensors() const {
+    std::vector<KernelTensor> out;
+    for (int i = 0; i < (int)ops.size(); ++i) {
+        const Op& op = ops[i];
+        const int kk = op.KS * op.KS;
+        if (op.kind == OP_CONV1 || op.kind == OP_CONV || op.kind == OP_DENSE)
+            out.push_back(KernelTensor{i, op.kind, op.w_off, op.Cout, kk * op.Cin, kk * op.Cin, 1});
+        else if (op.kind == OP_DWCONV)
+            out.push_back(KernelTensor{i, op.kind, op.w_off, op.Cin, kk, 1, op.Cin});
+    }
+    return out;
+}
+
 std::vector<uint8_t> NetPlan::param_kinds() const {
     std::vector<uint8_t> kinds((size_t)n_params, (uint8_t)KIND_TRAINABLE);
-    for (const Op& op : ops) {
-        if (op.kind == OP_CONV1 || op.kind == OP_CONV || op.kind == OP_DENSE)
-            std::fill(kinds.begin() + op.w_off, kinds.begin() + op.b_off, (uint8_t)KIND_KERNEL);
-        else if (op.kind == OP_DWCONV)
-            std::fill(kinds.begin() + op.w_off, kinds.begin() + op.w_off + (int64_t)op.KS * op.KS * op.Cin, (uint8_t)KIND_KERNEL);
-        else if (op.kind == OP_BN)
-            std::fill(kinds.begin() + op.mm_off, kinds.begin() + op.mv_off + op.Cout, (uint8_t)KIND_FROZEN);
-    }
+    for (const KernelTensor& t : kernel_tensors())
+        std::fill(kinds.begin() + t.off, kinds.begin() + t.off + t.elems(), (uint8_t)KIND_KERNEL);
+    for (const Op& op : ops)
+        if (op.kind == OP_BN) std::fill(kinds.begin() + op.mm_off, kinds.begin() + op.mv_off + op.Cout, (uint8_t)KIND_FROZEN);
     return kinds;
 }
 
 QuantTable quant_table(const NetPlan& plan) {
     QuantTable tab;
-    for (const Op& op : plan.ops) {
-        CMOOP_REQUIRE(op.w_off <= QUANT_MAX_ARENA, "quant: the arena must stay below 2^31 elements (QUANT_MAX_ARENA)");
-        if (op.kind == OP_CONV1 || op.kind == OP_CONV || op.kind == OP_DENSE) {
-            const int len = op.KS * op.KS * op.Cin;
-            tab.rows.push_back(QuantRow{(int32_t)op.w_off, op.Cout, len, len, 1, 0, 0});
-        } else if (op.kind == OP_DWCONV) {
-            tab.rows.push_back(QuantRow{(int32_t)op.w_off, op.Cin, op.KS * op.KS, 1, op.Cin, 0, 0});
-        }
+    for (const KernelTensor& t : plan.kernel_tensors()) {
+        CMOOP_REQUIRE(t.off <= QUANT_MAX_ARENA, "quant: the arena must stay below 2^31 elements (QUANT_MAX_ARENA)");
+        tab.rows.push_back(QuantRow{(int32_t)t.off, t.channels, t.len, t.chan_stride, t.elem_stride, 0, 0});
     }
     quant_table_finalize(tab, plan.n_params);
     return tab;
@@ -402,14 +406,10 @@ QuantTable quant_table(const NetPlan& plan) {
 
 PruneTable prune_table(const NetPlan& plan, bool skip_small) {
     PruneTable tab;
-    for (const Op& op : plan.ops) {
-        CMOOP_REQUIRE(op.w_off <= PRUNE_MAX_ARENA, "prune: the arena must stay below 2^31 elements (PRUNE_MAX_ARENA)");
-        if (op.kind == OP_CONV || op.kind == OP_DENSE)
-            tab.rows.push_back(PruneRow{(int32_t)op.w_off, op.Cout * op.KS * op.KS * op.Cin, -1, 0});
-        else if (op.kind == OP_CONV1)
-            tab.rows.push_back(PruneRow{(int32_t)op.w_off, op.Cout * op.KS * op.KS * op.Cin, skip_small ? 0 : -1, 0});
-        else if (op.kind == OP_DWCONV)
-            tab.rows.push_back(PruneRow{(int32_t)op.w_off, op.KS * op.KS * op.Cin, skip_small ? 0 : -1, 0});
+    for (const KernelTensor& t : plan.kernel_tensors()) {
+        CMOOP_REQUIRE(t.off <= PRUNE_MAX_ARENA, "prune: the arena must stay below 2^31 elements (PRUNE_MAX_ARENA)");
+        const bool small = t.kind == OP_CONV1 || t.kind == OP_DWCONV;   // a few hundred weights that every pixel goes through
+        tab.rows.push_back(PruneRow{(int32_t)t.off, (int32_t)t.elems(), small && skip_small ? 0 : -1, 0});
     }
     prune_table_finalize(tab, plan.n_params);
     return tab;
@@ -439,12 +439,9 @@ std::string NetPlan::launch_plan(int batch, int Bmax, int B, bool train) const {
 }
 
 void Net::build_plan() {
-    NetPlan plan = plan_net(gene_, cfg_, T_, F_);
-    splitk_ws_floats_ = plan.splitk_floats(cfg_.batch, Bmax_);
-    acts_ = std::move(plan.acts);
-    ops_ = std::move(plan.ops);
-    logits_ = plan.logits;
-    n_params_ = plan.n_params;
+    plan_ = plan_net(gene_, cfg_, T_, F_);
+    splitk_ws_floats_ = plan_.splitk_floats(cfg_.batch, Bmax_);
+    const std::vector<KernelTensor> tensors = plan_.kernel_tensors();
 
     // ---- activations ------------------------------------------------------
     for (size_t i = 1; i < acts_.size(); ++i)
@@ -470,23 +467,20 @@ void Net::build_plan() {
     // arithmetic and (float)(2 u24 - 2^24) * scale is one exact conversion and one correctly rounded multiply): a
     // 13.6 M-parameter candidate no longer spends ~50 ms of host hashing + an H2D copy with its stream idle
     CMOOP_HIP(hipMemsetAsync(params_, 0, n_params_ * 4, stream_));
-    for (const auto& op : ops_) {
+    auto kt = tensors.begin();   // in op order, as the launches always were
+    for (int oi = 0; oi < (int)ops_.size(); ++oi) {
+        const Op& op = ops_[oi];
         if (op.kind == OP_BN) {
             launch_fill(params_ + op.gamma_off, 1.f, op.Cout, stream_);
             launch_fill(params_ + op.mv_off, 1.f, op.Cout, stream_);
-        } else if (op.kind == OP_DWCONV) {
-            // Keras' fans of a depthwise kernel (k, k, C, 1): fan_in = k*k*C, fan_out = k*k
+        } else if (kt != tensors.end() && kt->op == oi) {
+            // glorot_uniform: limit = sqrt(6 / (fan_in + fan_out)), fan = k*k*C  (oracle/rng.py twin); Keras' fans of a
+            // depthwise kernel (k, k, C, 1): fan_in = k*k*C, fan_out = k*k
             const double kk = (double)op.KS * op.KS;
-            const float scale = (float)(std::sqrt(6.0 / (kk * op.Cin + kk)) / 16777216.0);
-            launch_glorot_init(params_ + op.w_off, (int64_t)op.KS * op.KS * op.Cin, rng_prefix(seed_, STREAM_INIT + (uint32_t)op.tensor_index, 0),
-                               scale, stream_);
-        } else if (op.kind == OP_CONV1 || op.kind == OP_CONV || op.kind == OP_DENSE) {
-            // glorot_uniform: limit = sqrt(6 / (fan_in + fan_out)), fan = k*k*C  (oracle/rng.py twin)
-            const double fan_in = (double)op.KS * op.KS * op.Cin, fan_out = (double)op.KS * op.KS * op.Cout;
-            const double limit = std::sqrt(6.0 / (fan_in + fan_out));
-            const float scale = (float)(limit / 16777216.0);
-            const int64_t n = (int64_t)op.Cout * op.KS * op.KS * op.Cin;
-            launch_glorot_init(params_ + op.w_off, n, rng_prefix(seed_, STREAM_INIT + (uint32_t)op.tensor_index, 0), scale, stream_);
+            const double fan_in = kk * op.Cin, fan_out = op.kind == OP_DWCONV ? kk : kk * op.Cout;
+            const float scale = (float)(std::sqrt(6.0 / (fan_in + fan_out)) / 16777216.0);
+            launch_glorot_init(params_ + kt->off, kt->elems(), rng_prefix(seed_, STREAM_INIT + (uint32_t)op.tensor_index, 0), scale, stream_);
+            ++kt;
         }
     }
 
@@ -542,11 +536,13 @@ void Net::build_plan() {
     wd_ws_ = dalloc(wd_ws_floats_);
     {   // one table row per conv layer with a data gradient: refreshed by ONE flip-transpose launch per train step
         std::vector<FlipEntry> tab;
-        for (const auto& op : ops_)
-            if (op.kind == OP_CONV && op.wd_off >= 0) {
-                tab.push_back(FlipEntry{op.w_off, op.wd_off, op.Cout, op.KS, op.KS, op.Cin});
-                flip_max_elems_ = std::max<int64_t>(flip_max_elems_, (int64_t)op.Cout * op.KS * op.KS * op.Cin);
+        for (const KernelTensor& t : tensors) {
+            const Op& op = ops_[t.op];
+            if (t.kind == OP_CONV && op.wd_off >= 0) {
+                tab.push_back(FlipEntry{t.off, op.wd_off, op.Cout, op.KS, op.KS, op.Cin});
+                flip_max_elems_ = std::max(flip_max_elems_, t.elems());
             }
+        }
         flip_layers_ = (int)tab.size();
         if (flip_layers_) {
             flip_table_ = reinterpret_cast<FlipEntry*>(dalloc(tab.size() * sizeof(FlipEntry) / sizeof(float) + 4));
@@ -797,7 +793,7 @@ void Net::drain_profile() {
 // ---------------------------------------------------------------------------
 void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
     CMOOP_REQUIRE(B >= 1 && B <= Bmax_, "batch larger than the net was planned for");
-    const float* kern = kernels();   // the parameter arena, or the quantised one (set_quant): kernel tensors only
+    const float* kern = kernels_;   // what the caller's weight stage left: the source arena, the pruned or the quantised one
     for (size_t oi = 0; oi < ops_.size(); ++oi) {
         const Op& op = ops_[oi];
         switch (op.kind) {
@@ -881,7 +877,7 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
 
 void Net::backward(const float* X, const BatchRows& rows, int B) {
     slab_segs_.clear();
-    const float* kern = kernels();   // as forward: the gradients formed with it go unchanged to the latent weights (straight-through)
+    const float* kern = kernels_;   // as forward: the gradients formed with it go unchanged to the latent weights (straight-through)
     // dgrad operands: flip-transposed copies of every conv kernel, one launch for the whole net
     launch_flip_transpose_all(kern, wd_ws_, flip_table_, flip_layers_, flip_max_elems_, stream_);
     for (int oi = (int)ops_.size() - 1; oi >= 0; --oi) {
@@ -982,27 +978,44 @@ void Net::backward(const float* X, const BatchRows& rows, int B) {
     }
 }
 
-// one optimiser step: gather -> forward -> loss -> backward -> Adam.  rows.st == null: explicit host arguments (session API);
-// rows.st != null: batch position / dropout counter / Adam iteration come from the device state, which the step advances
-void Net::step_body(const float* X, const int32_t* y, const BatchRows& rows, int B) {
+const float* Net::stage_kernels(double sparsity, float* wp, uint32_t* zeros, float* wq, int8_t* codes, float* scales) {
+    const float* src = params_;
+    if (prune_on_) {
+        launch_prune_weights(src, wp, zeros, ptab_, ptab_dev_, prune_ws_, sparsity, stream_);
+        src = wp;
+    }
+    if (quant_on_ && wq) {
+        launch_quantize_weights(src, wq, codes, scales, qtab_, qtab_dev_, quant_cfg_.bits, stream_);
+        src = wq;
+    }
+    return src;
+}
+
+template <class Loss> void Net::step_body(const float* X, const BatchRows& rows, int B, bool gather, Loss&& loss) {
     CMOOP_REQUIRE(params_ == weights_, "train step while inference reads the average: use_average(false) first");
     // before anything is enqueued: a teacher table of another length than the split the step gathers from is refused whole
-    CMOOP_REQUIRE(!distill_on_ || gather_rows_ == 0 || gather_rows_ == kd_rows_, "distill: the teacher table has " +
+    CMOOP_REQUIRE(!gather || !distill_on_ || gather_rows_ == 0 || gather_rows_ == kd_rows_, "distill: the teacher table has " +
                   std::to_string(kd_rows_) + " rows, the training split " + std::to_string(gather_rows_));
-    // augmentation on: the batch's rows are gathered and augmented into aug_buf_ first (rows.st != null: the kernel reads
-    // the batch position and the step from the device state, so a replayed graph draws for the step it replays)
-    prune_now(prune_sparsity_at(prune_cfg_, iterations_));   // prune on: the step's first launches, on the latent weights of this moment
-    quantize_now();   // quant on: the next launch, on the latent weights or on what the pruning left of them
-    if (aug_on_) launch_augment_gather(X, rows, aug_buf_, B, T_, F_, aug_, seed_, (uint32_t)step_, stream_);
-    // mixup on: the (augmented) rows are blended into mix_buf_ next; each row keeps its own batch position's augmentation
-    // (from the augment buffer the launch takes only the step from rows.st: the buffer always starts at its row 0)
-    if (mix_on_)
-        launch_mixup_gather(aug_on_ ? aug_buf_ : X, rows, aug_on_ ? 1 : 0, mix_buf_, B, T_, F_, mixp_, seed_, (uint32_t)step_, stream_);
-    batch_in_ = mix_on_ ? mix_buf_ : (aug_on_ ? aug_buf_ : nullptr);
+    refresh_kernels(prune_sparsity_at(prune_cfg_, iterations_));   // the step's first launches, on the latent weights of this moment
+    batch_in_ = nullptr;
+    if (gather) {
+        // augmentation on: the batch's rows are gathered and augmented into aug_buf_ first (rows.st != null: the kernel reads
+        // the batch position and the step from the device state, so a replayed graph draws for the step it replays)
+        if (aug_on_) launch_augment_gather(X, rows, aug_buf_, B, T_, F_, aug_, seed_, (uint32_t)step_, stream_);
+        // mixup on: the (augmented) rows are blended into mix_buf_ next; each row keeps its own batch position's augmentation
+        // (from the augment buffer the launch takes only the step from rows.st: the buffer always starts at its row 0)
+        if (mix_on_)
+            launch_mixup_gather(aug_on_ ? aug_buf_ : X, rows, aug_on_ ? 1 : 0, mix_buf_, B, T_, F_, mixp_, seed_, (uint32_t)step_, stream_);
+        batch_in_ = mix_on_ ? mix_buf_ : (aug_on_ ? aug_buf_ : nullptr);
+    }
     forward(X, rows, B, true);
-    launch_train_loss(y, rows, B);
+    loss();
     backward(X, rows, B);
     optimiser_step(B, rows.st);
+}
+
+void Net::gathered_step(const float* X, const int32_t* y, const BatchRows& rows, int B) {
+    step_body(X, rows, B, true, [&] { launch_train_loss(y, rows, B); });
 }
 
 void Net::launch_train_loss(const int32_t* y, const BatchRows& rows, int B) {
@@ -1077,36 +1090,27 @@ struct ProfilingScope {
     ~ProfilingScope() { flag = false; }
 };
 
+template <class Body> void Net::counted_step(Body&& body) {
+    ProfilingScope prof(profiling_now_, cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0);
+    body();
+    ++iterations_;
+    ++step_;
+}
+
 void Net::train_step(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B) {
     CMOOP_REQUIRE(B >= 1 && B <= cfg_.batch, "train batch larger than configured");
-    ProfilingScope prof(profiling_now_, cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0);
-    step_body(X, y, BatchRows{idx, row0, gather_rows_, nullptr}, B);
-    ++iterations_;
-    ++step_;
+    counted_step([&] { gathered_step(X, y, BatchRows{idx, row0, gather_rows_, nullptr}, B); });
 }
 
-void Net::targets_step(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
-                       const DistillParams* kd, int B) {
-    CMOOP_REQUIRE(params_ == weights_, "train step while inference reads the average: use_average(false) first");
-    ProfilingScope prof(profiling_now_, cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0);
-    batch_in_ = nullptr;
-    const BatchRows rows;      // x_rows holds exactly the B rows of this step: no resident tensor to clamp into
-    float *z = acts_[logits_].data, *dz = acts_[logits_].grad;
-    prune_now(prune_sparsity_at(prune_cfg_, iterations_));
-    quantize_now();
-    forward(x_rows, rows, B, true);
-    if (kd) launch_softmax_ce_distill(z, t, w, primary, q, *kd, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
-    else launch_softmax_ce_soft(z, t, w, primary, B, cfg_.classes, dz, acc_train_, nullptr, stream_);
-    backward(x_rows, rows, B);
-    optimiser_step(B, nullptr);
-    ++iterations_;
-    ++step_;
-}
-
+// the explicit-targets steps.  BatchRows(): x_rows holds exactly the B rows of the step, no resident tensor to clamp into
 void Net::train_step_targets(const float* x_rows, const float* t, const float* w, const int32_t* primary, int B) {
     CMOOP_REQUIRE(B >= 1 && B <= cfg_.batch, "train batch larger than configured");
     CMOOP_REQUIRE(x_rows && t, "train_step_targets: NULL rows or targets");
-    targets_step(x_rows, t, w, primary, nullptr, nullptr, B);
+    Act& z = acts_[logits_];
+    counted_step([&] {
+        step_body(x_rows, BatchRows(), B, false,
+                  [&] { launch_softmax_ce_soft(z.data, t, w, primary, B, cfg_.classes, z.grad, acc_train_, nullptr, stream_); });
+    });
 }
 
 void Net::train_step_distill_targets(const float* x_rows, const float* t, const float* w, const int32_t* primary, const float* q,
@@ -1117,7 +1121,11 @@ void Net::train_step_distill_targets(const float* x_rows, const float* t, const 
     dc.alpha = alpha; dc.temperature = temperature;
     distill_check(dc, cfg_.classes, 0);
     const DistillParams dp = distill_params(dc);
-    targets_step(x_rows, t, w, primary, q, &dp, B);
+    Act& z = acts_[logits_];
+    counted_step([&] {
+        step_body(x_rows, BatchRows(), B, false,
+                  [&] { launch_softmax_ce_distill(z.data, t, w, primary, q, dp, B, cfg_.classes, z.grad, acc_train_, nullptr, stream_); });
+    });
 }
 
 void Net::begin_fit(int64_t total_steps) {
@@ -1163,7 +1171,8 @@ void Net::upload_rate_tables() {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // the tables are locals
 }
 
-void Net::drop_graph() {
+void Net::option_changed(bool breaks_graph) {
+    if (breaks_graph) graph_ok_ = false;          // nothing is promised under CMOOP_GRAPH=1
     if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
 }
 
@@ -1211,10 +1220,7 @@ void Net::last_opoint(OpointClass* classes, double summary[4]) const {
 
 void Net::ensure_kinds() {
     if (kinds_dev_) return;
-    NetPlan plan;
-    plan.ops = ops_;
-    plan.n_params = n_params_;
-    const std::vector<uint8_t> kinds = plan.param_kinds();
+    const std::vector<uint8_t> kinds = plan_.param_kinds();
     kinds_dev_ = reinterpret_cast<uint8_t*>(dalloc((size_t)(n_params_ + 3) / 4));
     CMOOP_HIP(hipMemcpyAsync(kinds_dev_, kinds.data(), (size_t)n_params_, hipMemcpyHostToDevice, stream_));
     CMOOP_HIP(hipStreamSynchronize(stream_));     // kinds is a local
@@ -1235,8 +1241,7 @@ void Net::set_optim(const OptimCfg* optim) {
     optim_ = c;
     optim_finish_ = finish;
     upload_rate_tables();                         // takes effect from the next step
-    if (finish) graph_ok_ = false;                // nothing is promised under CMOOP_GRAPH=1
-    drop_graph();
+    option_changed(finish);
 }
 
 void Net::set_ema(const EmaCfg* ema) {
@@ -1252,11 +1257,8 @@ void Net::set_ema(const EmaCfg* ema) {
     CMOOP_HIP(hipStreamSynchronize(stream_));
     ema_cfg_ = on ? *ema : EmaCfg();
     ema_on_ = on;
-    if (on) {
-        upload_rate_tables();                     // a fit under way: its table, from the next step
-        graph_ok_ = false;                        // nothing is promised under CMOOP_GRAPH=1
-    }
-    drop_graph();
+    if (on) upload_rate_tables();                 // a fit under way: its table, from the next step
+    option_changed(on);
 }
 
 void Net::use_average(bool on) {
@@ -1285,10 +1287,7 @@ void Net::finalize_average() {
 
 void Net::ensure_quant_table() {
     if (qtab_ready_) return;
-    NetPlan plan;
-    plan.ops = ops_;
-    plan.n_params = n_params_;
-    qtab_ = quant_table(plan);
+    qtab_ = quant_table(plan_);
     qtab_ready_ = true;
 }
 
@@ -1304,13 +1303,7 @@ void Net::set_quant(const QuantCfg* quant) {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running; the table's upload is done
     quant_cfg_ = on ? *quant : QuantCfg();
     quant_on_ = on;
-    if (on) graph_ok_ = false;                    // nothing is promised under CMOOP_GRAPH=1
-    drop_graph();
-}
-
-void Net::quantize_now() {
-    if (!quant_on_) return;
-    launch_quantize_weights(prune_on_ ? wp_ : params_, wq_, nullptr, nullptr, qtab_, qtab_dev_, quant_cfg_.bits, stream_);
+    option_changed(on);
 }
 
 int64_t Net::quant_size_bytes() {
@@ -1327,12 +1320,7 @@ void Net::get_quantized(float* wq_host, int8_t* codes_host, float* scales_host) 
     float* d_scales = pool.get<float>(std::max<size_t>((size_t)qtab_.total_channels, 1) * 4);
     CMOOP_HIP(hipMemcpyAsync(d_wq, params_, n * 4, hipMemcpyDeviceToDevice, stream_));
     CMOOP_HIP(hipMemsetAsync(d_codes, 0, n, stream_));
-    const float* src = params_;
-    if (prune_on_) {   // prune, then quantise the pruned kernels: what inference reads
-        prune_now(prune_cfg_.sparsity);
-        src = wp_;
-    }
-    launch_quantize_weights(src, d_wq, d_codes, d_scales, qtab_, qtab_dev_, quant_cfg_.bits, stream_);
+    stage_kernels(prune_cfg_.sparsity, wp_, nullptr, d_wq, d_codes, d_scales);   // what inference reads
     if (wq_host) CMOOP_HIP(hipMemcpyAsync(wq_host, d_wq, n * 4, hipMemcpyDeviceToHost, stream_));
     if (codes_host) CMOOP_HIP(hipMemcpyAsync(codes_host, d_codes, n, hipMemcpyDeviceToHost, stream_));
     if (scales_host) CMOOP_HIP(hipMemcpyAsync(scales_host, d_scales, (size_t)qtab_.total_channels * 4, hipMemcpyDeviceToHost, stream_));
@@ -1341,10 +1329,7 @@ void Net::get_quantized(float* wq_host, int8_t* codes_host, float* scales_host) 
 
 void Net::ensure_prune_table() {
     if (ptab_skip_small_ == prune_cfg_.skip_small) return;
-    NetPlan plan;
-    plan.ops = ops_;
-    plan.n_params = n_params_;
-    ptab_ = prune_table(plan, prune_cfg_.skip_small != 0);
+    ptab_ = prune_table(plan_, prune_cfg_.skip_small != 0);
     ptab_skip_small_ = prune_cfg_.skip_small;
 }
 
@@ -1368,13 +1353,7 @@ void Net::set_prune(const PruneCfg* prune) {
         CMOOP_HIP(hipStreamSynchronize(stream_)); // the table's upload is done: ptab_ may be rebuilt by a later call
     }
     prune_on_ = on;
-    if (on) graph_ok_ = false;                    // nothing is promised under CMOOP_GRAPH=1
-    drop_graph();
-}
-
-void Net::prune_now(double s) {
-    if (!prune_on_) return;
-    launch_prune_weights(params_, wp_, nullptr, ptab_, ptab_dev_, prune_ws_, s, stream_);
+    option_changed(on);
 }
 
 int Net::prune_rows() {
@@ -1404,7 +1383,7 @@ void Net::get_pruned(float* weff_host, uint32_t* zeros_host) {
     float* d_w = pool.get<float>(std::max<size_t>(n, 1) * 4);
     uint32_t* d_zeros = pool.get<uint32_t>(std::max<size_t>(rows, 1) * 4);
     CMOOP_HIP(hipMemcpyAsync(d_w, params_, n * 4, hipMemcpyDeviceToDevice, stream_));
-    launch_prune_weights(params_, d_w, d_zeros, ptab_, ptab_dev_, prune_ws_, prune_cfg_.sparsity, stream_);
+    stage_kernels(prune_cfg_.sparsity, d_w, d_zeros, nullptr, nullptr, nullptr);   // pruned, not quantised
     if (weff_host) CMOOP_HIP(hipMemcpyAsync(weff_host, d_w, n * 4, hipMemcpyDeviceToHost, stream_));
     if (zeros_host) CMOOP_HIP(hipMemcpyAsync(zeros_host, d_zeros, rows * 4, hipMemcpyDeviceToHost, stream_));
     CMOOP_HIP(hipStreamSynchronize(stream_));
@@ -1432,39 +1411,37 @@ void Net::train_step_stateful(const float* X, const int32_t* y, const int32_t* i
         return;
     }
     CMOOP_REQUIRE(iterations_ < alpha_tab_n_, "train_step_stateful outside begin_fit's step budget");
-    ProfilingScope prof(profiling_now_, cfg_.profile_every > 0 && (step_ % cfg_.profile_every) == 0);
     const BatchRows rows{idx, 0, gather_rows_, st_dev_};
-    bool replayed = false;
-    if (graph_ok_ && B == cfg_.batch && !profiling_now_ && step_ >= 1) {
-        if (!graph_exec_) {   // capture the step once (thread-local mode: the other candidates' threads keep launching)
-            hipGraph_t graph = nullptr;
-            bool ok = hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            if (ok) {
-                try {
-                    step_body(X, y, rows, B);
-                } catch (...) {
-                    hipStreamEndCapture(stream_, &graph);
-                    if (graph) hipGraphDestroy(graph);
-                    throw;
+    counted_step([&] {
+        if (graph_ok_ && B == cfg_.batch && !profiling_now_ && step_ >= 1) {
+            if (!graph_exec_) {   // capture the step once (thread-local mode: the other candidates' threads keep launching)
+                hipGraph_t graph = nullptr;
+                bool ok = hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal) == hipSuccess;
+                if (ok) {
+                    try {
+                        gathered_step(X, y, rows, B);
+                    } catch (...) {
+                        hipStreamEndCapture(stream_, &graph);
+                        if (graph) hipGraphDestroy(graph);
+                        throw;
+                    }
+                    ok = hipStreamEndCapture(stream_, &graph) == hipSuccess && graph != nullptr;
                 }
-                ok = hipStreamEndCapture(stream_, &graph) == hipSuccess && graph != nullptr;
+                if (ok) ok = hipGraphInstantiate(&graph_exec_, graph, nullptr, nullptr, 0) == hipSuccess;
+                if (graph) hipGraphDestroy(graph);
+                if (!ok) {
+                    (void)hipGetLastError();
+                    graph_exec_ = nullptr;
+                    graph_ok_ = false;      // fall back to eager steps for this candidate
+                }
             }
-            if (ok) ok = hipGraphInstantiate(&graph_exec_, graph, nullptr, nullptr, 0) == hipSuccess;
-            if (graph) hipGraphDestroy(graph);
-            if (!ok) {
-                (void)hipGetLastError();
-                graph_exec_ = nullptr;
-                graph_ok_ = false;      // fall back to eager steps for this candidate
+            if (graph_exec_) {
+                CMOOP_HIP(hipGraphLaunch(graph_exec_, stream_));
+                return;
             }
         }
-        if (graph_exec_) {
-            CMOOP_HIP(hipGraphLaunch(graph_exec_, stream_));
-            replayed = true;
-        }
-    }
-    if (!replayed) step_body(X, y, rows, B);
-    ++iterations_;
-    ++step_;
+        gathered_step(X, y, rows, B);
+    });
 }
 
 void Net::get_state(float* params, float* m, float* v, long long* iterations, long long* steps) {
@@ -1485,7 +1462,7 @@ void Net::set_state(const float* params, const float* m, const float* v, long lo
     step_ = steps;
     upload_step_state();
     CMOOP_HIP(hipStreamSynchronize(stream_));
-    drop_graph();
+    option_changed(false);
 }
 
 void Net::set_augment(const AugmentCfg* aug) {
@@ -1498,7 +1475,7 @@ void Net::set_augment(const AugmentCfg* aug) {
     }
     CMOOP_HIP(hipStreamSynchronize(stream_));
     aug_on_ = on;
-    drop_graph();
+    option_changed(false);
 }
 
 void Net::set_loss(const LossCfg* loss) {
@@ -1537,7 +1514,7 @@ void Net::set_loss(const LossCfg* loss) {
     mix_on_ = mix;
     mixp_ = mp;
     tgtp_ = tp;
-    drop_graph();
+    option_changed(false);
 }
 
 void Net::set_gather_rows(int64_t n) {
@@ -1558,7 +1535,7 @@ void Net::set_distill(const DistillCfg* distill) {
     kdp_ = on ? distill_params(*distill) : DistillParams();
     kd_zt_ = on ? distill->teacher_logits : nullptr;
     kd_rows_ = on ? distill->n_rows : 0;
-    drop_graph();
+    option_changed(false);
 }
 
 void Net::loss_buffers(int64_t out[4]) const {
@@ -1597,16 +1574,25 @@ void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch
         train_step_stateful(X, y, idx, (int)std::min<int64_t>(cfg_.batch, n_train - s));
 }
 
-void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum, long long* correct, int32_t* preds) {
-    CMOOP_HIP(hipMemsetAsync(acc_eval_, 0, 16, stream_));
-    prune_now(prune_cfg_.sparsity);   // prune on: once per call, the arena this pass reads at the FINAL sparsity
-    quantize_now();   // quant on: once per call, on the arena this pass reads
+template <class Source, class Sink> void Net::inference_pass(int64_t n, Source&& source, Sink&& sink) {
+    refresh_kernels(prune_cfg_.sparsity);   // once per call, on the arena this pass reads
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
-        const BatchRows rows{nullptr, s};
-        forward(X, rows, B, false);
-        launch_softmax_ce(acts_[logits_].data, y, rows, B, cfg_.classes, nullptr, acc_eval_, preds ? preds + s : nullptr, stream_);
+        const std::pair<const float*, BatchRows> in = source(s, B);
+        forward(in.first, in.second, B, false);
+        sink(s, B);
     }
+}
+// the chunk source of a resident tensor: rows [s, s + B) of X
+static auto resident_rows(const float* X) {
+    return [X](int64_t s, int) { return std::make_pair(X, BatchRows{nullptr, s}); };
+}
+
+void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum, long long* correct, int32_t* preds) {
+    CMOOP_HIP(hipMemsetAsync(acc_eval_, 0, 16, stream_));
+    inference_pass(n, resident_rows(X), [&](int64_t s, int B) {
+        launch_softmax_ce(acts_[logits_].data, y, BatchRows{nullptr, s}, B, cfg_.classes, nullptr, acc_eval_, preds ? preds + s : nullptr, stream_);
+    });
     double host[2];
     CMOOP_HIP(hipMemcpyAsync(host, acc_eval_, 16, hipMemcpyDeviceToHost, stream_));
     CMOOP_HIP(hipStreamSynchronize(stream_));
@@ -1616,26 +1602,17 @@ void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum
 
 void Net::predict(const float* X, int64_t n, float* probs) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && probs)), "predict: NULL buffer");
-    prune_now(prune_cfg_.sparsity);
-    quantize_now();
-    for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
-        const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
-        forward(X, BatchRows{nullptr, s}, B, false);
-        launch_softmax_probs(acts_[logits_].data, probs + s * cfg_.classes, B, cfg_.classes, stream_);
-    }
+    inference_pass(n, resident_rows(X),
+                   [&](int64_t s, int B) { launch_softmax_probs(acts_[logits_].data, probs + s * cfg_.classes, B, cfg_.classes, stream_); });
     CMOOP_HIP(hipStreamSynchronize(stream_));
 }
 
 void Net::predict_logits(const float* X, int64_t n, float* logits) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && logits)), "predict_logits: NULL buffer");
-    prune_now(prune_cfg_.sparsity);
-    quantize_now();
-    for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
-        const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
-        forward(X, BatchRows{nullptr, s}, B, false);
+    inference_pass(n, resident_rows(X), [&](int64_t s, int B) {
         CMOOP_HIP(hipMemcpyAsync(logits + s * cfg_.classes, acts_[logits_].data, (size_t)B * cfg_.classes * 4, hipMemcpyDeviceToDevice,
                                  stream_));
-    }
+    });
     CMOOP_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -1658,15 +1635,12 @@ void Net::predict_stream(const float* feat, int64_t n_frames, int hop, bool db_s
         CMOOP_HIP(hipMemcpyAsync(ms, mean, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
         CMOOP_HIP(hipMemcpyAsync(ms + F_, scale, (size_t)F_ * 8, hipMemcpyHostToDevice, stream_));
     }
-    prune_now(prune_cfg_.sparsity);
-    quantize_now();
-    for (int64_t w = 0; w < n; w += cfg_.eval_batch) {       // window i sits at position i % eval_batch of chunk i / eval_batch
-        const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - w);
+    auto gather = [&](int64_t w, int B) {   // window i sits at position i % eval_batch of chunk i / eval_batch
         launch_window_gather(feat, chunk, w, B, hop, T_, F_, db_scale ? 1 : 0, db_ref_max ? 1 : 0, db_amin, top_db, ms,
                              ms ? ms + F_ : nullptr, stream_);
-        forward(chunk, BatchRows(), B, false);
-        launch_softmax_probs(acts_[logits_].data, probs + w * cfg_.classes, B, cfg_.classes, stream_);
-    }
+        return std::make_pair((const float*)chunk, BatchRows());
+    };
+    inference_pass(n, gather, [&](int64_t w, int B) { launch_softmax_probs(acts_[logits_].data, probs + w * cfg_.classes, B, cfg_.classes, stream_); });
 }
 
 void Net::read_train_metrics(double* loss_sum, long long* correct, bool reset) {
