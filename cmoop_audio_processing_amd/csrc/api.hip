@@ -1113,14 +1113,23 @@ int cmoop_frontend_mel_basis(const cmoop_frontend_config* c, float* out_host) {
     });
 }
 
+// The front end's entry points and their timed twins share a body each, as quantize_weights_abi: the entry point makes its own
+// argument checks (no device needed), the body then takes the tables and the stream; avg_ms null: one launch, else timed launches
+static void logmel_ex_abi(const FrontendCfg& f, const float* wav, int64_t n_clips, int32_t n_samples, float* out, int32_t iters,
+                          double* avg_ms) {
+    const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+    hipStream_t s = lib_stream();
+    auto once = [&] { launch_logmel(wav, n_clips, n_samples, out, tables.get(), s); };
+    if (avg_ms) *avg_ms = time_launches(s, iters, once);
+    else once();
+    CMOOP_HIP(hipStreamSynchronize(s));
+}
+
 int cmoop_logmel_ex(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_clips, int32_t n_samples, float* out_dev) {
     return guard([&] {
         const FrontendCfg f = to_frontend_cfg(c);
         CMOOP_REQUIRE(n_samples >= 1 && n_clips >= 0, "logmel_ex: n_samples >= 1, n_clips >= 0");
-        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
-        hipStream_t s = lib_stream();
-        launch_logmel(wav_dev, n_clips, n_samples, out_dev, tables.get(), s);
-        CMOOP_HIP(hipStreamSynchronize(s));
+        logmel_ex_abi(f, wav_dev, n_clips, n_samples, out_dev, 0, nullptr);
     });
 }
 
@@ -1129,9 +1138,7 @@ int cmoop_logmel_ex_time(const cmoop_frontend_config* c, const float* wav_dev, i
     return guard([&] {
         const FrontendCfg f = to_frontend_cfg(c);
         CMOOP_REQUIRE(n_samples >= 1 && n_clips >= 1 && iters >= 1 && avg_ms, "logmel_ex_time: n_samples, n_clips, iters >= 1");
-        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
-        hipStream_t s = lib_stream();
-        *avg_ms = time_launches(s, iters, [&] { launch_logmel(wav_dev, n_clips, n_samples, out_dev, tables.get(), s); });
+        logmel_ex_abi(f, wav_dev, n_clips, n_samples, out_dev, iters, avg_ms);
     });
 }
 
@@ -1142,14 +1149,18 @@ static int compute_units_of_current_device() {
     return cu > 0 ? cu : 256;
 }
 
+static void logmel_stream_abi(const FrontendCfg& f, const float* wav, int64_t n_samples, float* out, int32_t iters, double* avg_ms) {
+    const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+    const int cu = compute_units_of_current_device();
+    hipStream_t s = lib_stream();
+    auto once = [&] { launch_logmel_stream(wav, n_samples, out, tables.get(), cu, s); };
+    if (avg_ms) *avg_ms = time_launches(s, iters, once);
+    else once();
+    CMOOP_HIP(hipStreamSynchronize(s));
+}
+
 int cmoop_logmel_stream(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_samples, float* out_dev) {
-    return guard([&] {
-        const FrontendCfg f = to_frontend_cfg(c);
-        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
-        hipStream_t s = lib_stream();
-        launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), compute_units_of_current_device(), s);
-        CMOOP_HIP(hipStreamSynchronize(s));
-    });
+    return guard([&] { logmel_stream_abi(to_frontend_cfg(c), wav_dev, n_samples, out_dev, 0, nullptr); });
 }
 
 int cmoop_logmel_stream_time(const cmoop_frontend_config* c, const float* wav_dev, int64_t n_samples, float* out_dev, int32_t iters,
@@ -1157,10 +1168,7 @@ int cmoop_logmel_stream_time(const cmoop_frontend_config* c, const float* wav_de
     return guard([&] {
         const FrontendCfg f = to_frontend_cfg(c);
         CMOOP_REQUIRE(iters >= 1 && avg_ms, "logmel_stream_time: iters >= 1");
-        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
-        const int cu = compute_units_of_current_device();
-        hipStream_t s = lib_stream();
-        *avg_ms = time_launches(s, iters, [&] { launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s); });
+        logmel_stream_abi(f, wav_dev, n_samples, out_dev, iters, avg_ms);
     });
 }
 
@@ -1226,20 +1234,30 @@ int cmoop_pcen_stream(const cmoop_pcen* p, float* e_dev, int64_t n_frames, int32
     });
 }
 
+// (the n_samples check sits after lib_stream(), where both entry points always had it)
+static void logmel_pcen_stream_abi(const FrontendCfg& f, const PcenParams& pp, const float* wav, int64_t n_samples, float* out,
+                                   int32_t iters, double* avg_ms) {
+    const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
+    const int cu = compute_units_of_current_device();
+    hipStream_t s = lib_stream();
+    CMOOP_REQUIRE(n_samples >= 1 && n_samples <= 0x7fffffffll - 2 * f.n_fft, "stream front end: 1 <= n_samples < 2^31 - 2 n_fft");
+    const int T = frontend_frames(f, (int)n_samples);
+    with_pcen_workspace(T, f.n_mels, s, [&](float* ws) {
+        auto once = [&] {
+            launch_logmel_stream(wav, n_samples, out, tables.get(), cu, s);
+            launch_pcen_stream(pp, out, T, f.n_mels, ws, s);
+        };
+        if (avg_ms) *avg_ms = time_launches(s, iters, once);
+        else once();
+    });
+}
+
 int cmoop_logmel_pcen_stream(const cmoop_frontend_config* c, const cmoop_pcen* p, const float* wav_dev, int64_t n_samples,
                              float* out_dev) {
     return guard([&] {
         const FrontendCfg f = to_pcen_frontend_cfg(c, "logmel_pcen_stream");
         const PcenParams pp = to_pcen(p);
-        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
-        const int cu = compute_units_of_current_device();
-        hipStream_t s = lib_stream();
-        CMOOP_REQUIRE(n_samples >= 1 && n_samples <= 0x7fffffffll - 2 * f.n_fft, "stream front end: 1 <= n_samples < 2^31 - 2 n_fft");
-        const int T = frontend_frames(f, (int)n_samples);
-        with_pcen_workspace(T, f.n_mels, s, [&](float* ws) {
-            launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s);
-            launch_pcen_stream(pp, out_dev, T, f.n_mels, ws, s);
-        });
+        logmel_pcen_stream_abi(f, pp, wav_dev, n_samples, out_dev, 0, nullptr);
     });
 }
 
@@ -1249,17 +1267,7 @@ int cmoop_logmel_pcen_stream_time(const cmoop_frontend_config* c, const cmoop_pc
         const FrontendCfg f = to_pcen_frontend_cfg(c, "logmel_pcen_stream_time");
         const PcenParams pp = to_pcen(p);
         CMOOP_REQUIRE(iters >= 1 && avg_ms, "logmel_pcen_stream_time: iters >= 1");
-        const std::shared_ptr<const FrontendTables> tables = frontend_tables_for(f);
-        const int cu = compute_units_of_current_device();
-        hipStream_t s = lib_stream();
-        CMOOP_REQUIRE(n_samples >= 1 && n_samples <= 0x7fffffffll - 2 * f.n_fft, "stream front end: 1 <= n_samples < 2^31 - 2 n_fft");
-        const int T = frontend_frames(f, (int)n_samples);
-        with_pcen_workspace(T, f.n_mels, s, [&](float* ws) {
-            *avg_ms = time_launches(s, iters, [&] {
-                launch_logmel_stream(wav_dev, n_samples, out_dev, tables.get(), cu, s);
-                launch_pcen_stream(pp, out_dev, T, f.n_mels, ws, s);
-            });
-        });
+        logmel_pcen_stream_abi(f, pp, wav_dev, n_samples, out_dev, iters, avg_ms);
     });
 }
 
@@ -1872,9 +1880,9 @@ int cmoop_maxpool_bwd(const float* dy, const uint8_t* arg, const float* y, float
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
-// ---- kernel-level entry points of elem.hip (per-kernel parity tests): each launches what Net::forward / Net::backward /
-//      Net::step_body launch for the operation, in their order and with their argument casts; reduction workspaces live
-//      for the length of the call
+// ---- kernel-level entry points of bn.hip, elem.hip, loss.hip and optim.hip (per-kernel parity tests): each launches what
+//      Net::forward / Net::backward / Net::step_body launch for the operation, in their order and with their argument
+//      casts; reduction workspaces live for the length of the call
 static int reduce_blocks_arg(int32_t blocks, int64_t M, int32_t C) {
     CMOOP_REQUIRE(M >= 1 && C >= 4 && C % 4 == 0, "M >= 1 and C a multiple of 4 (>= 4)");
     CMOOP_REQUIRE(blocks >= 0 && blocks <= 4096, "blocks must be 0 (the trainer's count) or 1..4096");

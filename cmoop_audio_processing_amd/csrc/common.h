@@ -1,6 +1,7 @@
 // Shared host/device helpers for libcmoop_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <stdexcept>
@@ -51,5 +52,32 @@ static inline int ilog2_exact(int v) {
 }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---------------------------------------------------------------------------
+// What several kernel files share ("File map of csrc/").
+// ---------------------------------------------------------------------------
+// 16 / 8 bytes of floats: one global or LDS access per lane, one MFMA accumulator
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// row of the resident tensor a batch position maps to: idx[pos] (the epoch permutation) or pos itself; with n_rows > 0
+// the result is clamped into [0, n_rows): a corrupt index can then mis-train but never fault
+__device__ __forceinline__ int64_t gather_row(const int32_t* __restrict__ idx, int64_t pos, int64_t n_rows) {
+    int64_t src = idx ? (int64_t)idx[pos] : pos;
+    if (n_rows > 0) src = src < 0 ? 0 : (src >= n_rows ? n_rows - 1 : src);
+    return src;
+}
+
+// grid of a grid-stride elementwise launch over n items, 256 threads per workgroup
+static inline unsigned ew_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv64(n, 256), 8192)); }
+
+// Granlund-Montgomery division by an invariant: q = (umulhi(n, magic) + n) >> shift, exact for n < 2^31.  The host half;
+// each user keeps its own one-line device half beside its kernels
+static inline void fastdiv_init(int d, uint32_t* magic, uint32_t* shift) {
+    uint32_t s = 0;
+    while ((1u << s) < (uint32_t)d) ++s;
+    *shift = s;
+    *magic = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << s) - (uint64_t)d)) / (uint64_t)d + 1);
+}
 
 }  // namespace cmoop

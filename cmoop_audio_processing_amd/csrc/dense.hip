@@ -16,7 +16,6 @@
 
 namespace cmoop {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
@@ -262,6 +261,40 @@ void launch_dense_wgrad(const float* X, const float* dY, float* dW, float* dB, i
     check_dense(M, N, K);
     const unsigned grid = (unsigned)(cdiv(N, 16) * (K / 16));
     hipLaunchKernelGGL(dense_wgrad_kernel, dim3(grid), dim3(256), 0, s, X, dY, dW, dB, M, N, K, mode == GEMM_BF16 ? 1 : 0);
+    CMOOP_HIP(hipGetLastError());
+}
+
+// tiny helpers for the output layer (C_out = classes is not a multiple of 4 / power of two)
+__global__ void colsum_small_kernel(const float* __restrict__ X, float* __restrict__ out, int M, int C) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    float s = 0.f;
+    for (int m = 0; m < M; ++m) s += X[(size_t)m * C + c];
+    out[c] = s;
+}
+
+void launch_colsum_small(const float* X, float* out, int M, int C, hipStream_t s) {
+    hipLaunchKernelGGL(colsum_small_kernel, dim3(cdiv(C, 64)), dim3(64), 0, s, X, out, M, C);
+    CMOOP_HIP(hipGetLastError());
+}
+
+// dX[m][i] = sum_o dY[m][o] * W[o][i], optionally masked by (mask[m][i] > 0) * scale
+__global__ __launch_bounds__(256) void dense_dgrad_small_kernel(const float* __restrict__ dY, const float* __restrict__ W,
+                                                                float* __restrict__ dX, int M, int N, int K,
+                                                                const float* __restrict__ mask, float scale) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= M * K) return;
+    const int m = i / K, k = i - m * K;
+    float s = 0.f;
+    for (int o = 0; o < N; ++o) s = fmaf(dY[(size_t)m * N + o], W[(size_t)o * K + k], s);
+    if (mask) s = mask[i] > 0.f ? s * scale : 0.f;
+    dX[i] = s;
+}
+
+void launch_dense_dgrad_small(const float* dY, const float* W, float* dX, int M, int N, int K, const float* mask,
+                              float scale, hipStream_t s) {
+    if (M * K == 0) return;
+    hipLaunchKernelGGL(dense_dgrad_small_kernel, dim3(cdiv(M * K, 256)), dim3(256), 0, s, dY, W, dX, M, N, K, mask, scale);
     CMOOP_HIP(hipGetLastError());
 }
 

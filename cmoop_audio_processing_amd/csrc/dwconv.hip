@@ -14,8 +14,6 @@
 namespace cmoop {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int DW_MAX_CB4 = 16;         // channel quads per workgroup (64 channels = 256 contiguous bytes per pixel)
 constexpr int DW_TARGET_THREADS = 256 * 1024;
 constexpr int DW_ITEMS_PER_SLOT = 4;   // weight gradient: items a lane walks before the workgroup reduction

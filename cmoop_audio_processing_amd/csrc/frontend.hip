@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace cmoop {
@@ -177,8 +178,6 @@ void frontend_tables_destroy(FrontendTables* t) {
 }
 
 constexpr int NFFT = 512, NC = 256;   // real points, packed complex points
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Each wave owns its scratch, so the phases only need the wave's own LDS writes to be visible to its
 // other lanes: LDS operations of one wave complete in issue order; the fences only stop the compiler
@@ -557,7 +556,7 @@ __global__ __launch_bounds__(256) void logmel_ex_kernel(const float* __restrict_
 
 // Stream form of the general kernel: ONE recording, workgroup b owns frames [b run, min((b + 1) run, T)).  No dB tail:
 // a recording has no clip maximum; the reference and the top_db floor belong to the windows cut from the stream later
-// (window_gather_kernel, elem.hip), so the dB scale leaves the un-referenced 10 log10(max(amin, mel)) here.
+// (window_gather_kernel, augment.hip), so the dB scale leaves the un-referenced 10 log10(max(amin, mel)) here.
 template <int NC>
 __global__ __launch_bounds__(256) void logmel_ex_stream_kernel(const float* __restrict__ wav, int n_samples, float* __restrict__ out,
                                                                int T, int run, int hop, int n_mels, int scale, float log_eps,
@@ -569,11 +568,14 @@ __global__ __launch_bounds__(256) void logmel_ex_stream_kernel(const float* __re
                          g_band, nnz);
 }
 
-template <int NC>
-static void launch_logmel_ex(const float* wav, int64_t n_clips, int n_samples, float* out, int T, const FrontendTables* t, hipStream_t s) {
-    const FrontendCfg& c = t->cfg;
-    hipLaunchKernelGGL(logmel_ex_kernel<NC>, dim3((unsigned)n_clips), dim3(256), 0, s, wav, n_samples, out, T, c.hop, c.n_mels,
-                       c.scale, c.db_ref_max, c.log_eps, c.db_amin, c.top_db, t->tw, t->win, t->melw, t->meltask, t->nnz);
+// The general kernels exist for the four FFT sizes: f(std::integral_constant<int, n_fft / 2>()) hands the launcher its
+// packed complex point count as a compile-time constant (the kernels' template argument)
+template <class F>
+static void with_fft_points(int n_fft, F&& f) {
+    if (n_fft == 256) f(std::integral_constant<int, 128>());
+    else if (n_fft == 512) f(std::integral_constant<int, 256>());
+    else if (n_fft == 1024) f(std::integral_constant<int, 512>());
+    else f(std::integral_constant<int, 1024>());
 }
 
 int frontend_frames(const FrontendCfg& c, int n_samples) {
@@ -593,14 +595,12 @@ void launch_logmel(const float* wav, int64_t n_clips, int n_samples, float* out,
     if (!t->general) {
         hipLaunchKernelGGL(logmel_kernel, dim3((unsigned)n_clips), dim3(256), 0, s, wav, n_samples, out, T, c.hop, c.n_mels,
                            c.log_eps, t->tw, t->win, t->melw, t->meltask, t->nnz);
-    } else if (c.n_fft == 256) {
-        launch_logmel_ex<128>(wav, n_clips, n_samples, out, T, t, s);
-    } else if (c.n_fft == 512) {
-        launch_logmel_ex<256>(wav, n_clips, n_samples, out, T, t, s);
-    } else if (c.n_fft == 1024) {
-        launch_logmel_ex<512>(wav, n_clips, n_samples, out, T, t, s);
     } else {
-        launch_logmel_ex<1024>(wav, n_clips, n_samples, out, T, t, s);
+        with_fft_points(c.n_fft, [&](auto nc) {
+            hipLaunchKernelGGL(logmel_ex_kernel<decltype(nc)::value>, dim3((unsigned)n_clips), dim3(256), 0, s, wav, n_samples, out, T,
+                               c.hop, c.n_mels, c.scale, c.db_ref_max, c.log_eps, c.db_amin, c.top_db, t->tw, t->win, t->melw,
+                               t->meltask, t->nnz);
+        });
     }
     CMOOP_HIP(hipGetLastError());
 }
@@ -614,13 +614,6 @@ int frontend_stream_run(int T, int compute_units) {
     return (int)std::min<int64_t>(64, std::max<int64_t>(8, (want + 3) & ~(int64_t)3));
 }
 
-template <int NC>
-static void launch_logmel_ex_stream(const float* wav, int n_samples, float* out, int T, int run, const FrontendTables* t, hipStream_t s) {
-    const FrontendCfg& c = t->cfg;
-    hipLaunchKernelGGL(logmel_ex_stream_kernel<NC>, dim3((unsigned)cdiv(T, run)), dim3(256), 0, s, wav, n_samples, out, T, run, c.hop,
-                       c.n_mels, c.scale, c.log_eps, c.db_amin, t->tw, t->win, t->melw, t->meltask, t->nnz);
-}
-
 void launch_logmel_stream(const float* wav, int64_t n_samples, float* out, const FrontendTables* t, int compute_units, hipStream_t s) {
     const FrontendCfg& c = t->cfg;
     // frame * hop + n_fft stays inside int32 in the kernels' sample index
@@ -632,14 +625,12 @@ void launch_logmel_stream(const float* wav, int64_t n_samples, float* out, const
     if (!t->general) {
         hipLaunchKernelGGL(logmel_stream_kernel, dim3((unsigned)cdiv(T, run)), dim3(256), 0, s, wav, (int)n_samples, out, T, run, c.hop,
                            c.n_mels, c.log_eps, t->tw, t->win, t->melw, t->meltask, t->nnz);
-    } else if (c.n_fft == 256) {
-        launch_logmel_ex_stream<128>(wav, (int)n_samples, out, T, run, t, s);
-    } else if (c.n_fft == 512) {
-        launch_logmel_ex_stream<256>(wav, (int)n_samples, out, T, run, t, s);
-    } else if (c.n_fft == 1024) {
-        launch_logmel_ex_stream<512>(wav, (int)n_samples, out, T, run, t, s);
     } else {
-        launch_logmel_ex_stream<1024>(wav, (int)n_samples, out, T, run, t, s);
+        with_fft_points(c.n_fft, [&](auto nc) {
+            hipLaunchKernelGGL(logmel_ex_stream_kernel<decltype(nc)::value>, dim3((unsigned)cdiv(T, run)), dim3(256), 0, s, wav,
+                               (int)n_samples, out, T, run, c.hop, c.n_mels, c.scale, c.log_eps, c.db_amin, t->tw, t->win, t->melw,
+                               t->meltask, t->nnz);
+        });
     }
     CMOOP_HIP(hipGetLastError());
 }
@@ -831,14 +822,6 @@ void launch_pcen_apply(const PcenParams& p, float* e, int64_t n, int T, int F, h
     CMOOP_HIP(hipGetLastError());
 }
 
-template <int NC>
-static void launch_logmel_pcen_nc(const float* wav, int64_t n_clips, int n_samples, float* out, int T, const FrontendTables* t,
-                                  const PcenParams& p, hipStream_t s) {
-    const FrontendCfg& c = t->cfg;
-    hipLaunchKernelGGL(logmel_pcen_kernel<NC>, dim3((unsigned)n_clips), dim3(256), 0, s, wav, n_samples, out, T, c.hop, c.n_mels, p,
-                       t->tw, t->win, t->melw, t->meltask, t->nnz);
-}
-
 void launch_logmel_pcen(const float* wav, int64_t n_clips, int n_samples, float* out, const FrontendTables* t, const PcenParams& p,
                         hipStream_t s) {
     const FrontendCfg& c = t->cfg;
@@ -847,10 +830,10 @@ void launch_logmel_pcen(const float* wav, int64_t n_clips, int n_samples, float*
     CMOOP_REQUIRE(n_clips >= 0 && n_clips <= 0x7fffffff && (int64_t)T * c.n_mels <= 0x7fffffff, "front end: clip count / clip length out of range");
     if (n_clips == 0) return;
     CMOOP_REQUIRE(wav && out, "front end: NULL buffer");
-    if (c.n_fft == 256) launch_logmel_pcen_nc<128>(wav, n_clips, n_samples, out, T, t, p, s);
-    else if (c.n_fft == 512) launch_logmel_pcen_nc<256>(wav, n_clips, n_samples, out, T, t, p, s);
-    else if (c.n_fft == 1024) launch_logmel_pcen_nc<512>(wav, n_clips, n_samples, out, T, t, p, s);
-    else launch_logmel_pcen_nc<1024>(wav, n_clips, n_samples, out, T, t, p, s);
+    with_fft_points(c.n_fft, [&](auto nc) {
+        hipLaunchKernelGGL(logmel_pcen_kernel<decltype(nc)::value>, dim3((unsigned)n_clips), dim3(256), 0, s, wav, n_samples, out, T,
+                           c.hop, c.n_mels, p, t->tw, t->win, t->melw, t->meltask, t->nnz);
+    });
     CMOOP_HIP(hipGetLastError());
 }
 

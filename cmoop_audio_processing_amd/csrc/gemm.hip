@@ -15,8 +15,6 @@
 
 namespace cmoop {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
@@ -33,7 +31,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // (8 consecutive k of one row) is a single conflict-free ds_read_b128.
 // ---------------------------------------------------------------------------
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // (x, y) -> packed bf16 pair per plane, x in the low half.  NP = 3: exact truncation split; NP = 1: RNE rounding
 template <int NP>
@@ -100,13 +97,7 @@ static double par_scale() {
     return v;
 }
 
-// Granlund-Montgomery division by an invariant: q = (umulhi(n, magic) + n) >> shift, exact for n < 2^31
-static void fastdiv_init(int d, uint32_t* magic, uint32_t* shift) {
-    uint32_t s = 0;
-    while ((1u << s) < (uint32_t)d) ++s;
-    *shift = s;
-    *magic = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << s) - (uint64_t)d)) / (uint64_t)d + 1);
-}
+// Granlund-Montgomery division by an invariant (magic and shift from fastdiv_init, common.h): exact for n < 2^31
 __device__ __forceinline__ int fastdiv(int n, uint32_t magic, uint32_t shift) {
     return (int)((__umulhi((uint32_t)n, magic) + (uint32_t)n) >> shift);
 }

@@ -158,7 +158,7 @@ void launch_dense_bwd(const float* X, const float* dY, const float* W, float* dW
                       const float* mask, float mask_scale, int mode, hipStream_t s);
 
 // ---------------------------------------------------------------------------
-// First layer (C_in = 1, K = 9 or 25: too small for MFMA) -- direct conv on the VALU.
+// First layer (conv1.hip; C_in = 1, K = 9 or 25: too small for MFMA) -- direct conv on the VALU.
 // X is the resident feature tensor [N_total, H, W]; `idx` (may be null) gathers the
 // batch rows, fusing Keras' shuffle+batch gather (nsga_penalty.py:383) into the load.
 // ---------------------------------------------------------------------------
@@ -181,7 +181,7 @@ void launch_conv1_wgrad(const float* X, const BatchRows& rows, const float* dY, 
                         hipStream_t s);
 
 // ---------------------------------------------------------------------------
-// Train-time augmentation of the [T][F] feature patches (opt-in; no reference counterpart): random time shift,
+// Train-time augmentation of the [T][F] feature patches (augment.hip; opt-in; no reference counterpart): random time shift,
 // SpecAugment time / frequency masks and additive feature noise, keyed by (net seed, global train step, position in the
 // batch) on the counter RNG -- the same bits on the device, in augment_row_draws on the host and in augment.py.
 //   u(k)    = rng_u32(seed, STREAM_AUGMENT, step, 32 b + k),   R(u, n) = ((uint64)u n) >> 32
@@ -241,7 +241,8 @@ void launch_augment_gather(const float* X, const BatchRows& rows, float* out, in
                            uint32_t seed, uint32_t step, hipStream_t s);
 
 // ---------------------------------------------------------------------------
-// Soft-target training loss (opt-in; no reference counterpart, BUILD-DEFINED -- include/cmoop.h fixes the semantics): mixup
+// Soft-target training loss (loss.hip, the blend of the rows: augment.hip; opt-in; no reference counterpart, BUILD-DEFINED --
+// include/cmoop.h fixes the semantics): mixup
 // of two rows of a batch, label smoothing and class weights, all funnelled into cross-entropy against a dense target
 // distribution t[B][C] with a per-row weight w[B].  Draws on the counter RNG, keyed like dropout and augmentation:
 //   u(k) = rng_u32(seed, STREAM_MIXUP, step, 4 b + k),   R(u, n) = ((uint64)u n) >> 32
@@ -309,7 +310,7 @@ void launch_softmax_ce_soft(const float* Z, const float* t, const float* w, cons
                             double* acc, int32_t* preds, hipStream_t s);
 
 // ---------------------------------------------------------------------------
-// Knowledge distillation (opt-in; no reference counterpart, BUILD-DEFINED -- include/cmoop.h fixes the semantics): OFFLINE,
+// Knowledge distillation (loss.hip; opt-in; no reference counterpart, BUILD-DEFINED -- include/cmoop.h fixes the semantics): OFFLINE,
 // against one device table zt[n_rows][classes] of a teacher's logits of the resident training rows, computed once and
 // shared by every candidate.  The teacher saw the un-augmented, un-mixed row; a MIXED batch row blends the two teacher
 // rows with the blend kernel's own draws.  Validation never sees any of this.
@@ -351,7 +352,8 @@ void launch_softmax_ce_distill(const float* Z, const float* t, const float* w, c
                                const DistillParams& d, int B, int C, float* dZ, double* acc, int32_t* preds, hipStream_t s);
 
 // ---------------------------------------------------------------------------
-// Per-channel reductions over the M rows of an [M][C] tensor (C % 4 == 0).
+// Per-channel reductions over the M rows of an [M][C] tensor (C % 4 == 0) and BatchNorm (bn.hip; the two output-layer
+// helpers: dense.hip).
 // Two-stage and order-fixed: `blocks` partials then a double-precision finalize.
 // ---------------------------------------------------------------------------
 int colreduce_blocks(int64_t M, int C);
@@ -383,7 +385,8 @@ void launch_dense_dgrad_small(const float* dY, const float* W, float* dX, int M,
 void launch_colsum_finalize(const float* P, int blocks, int C, float* out, hipStream_t s);
 
 // ---------------------------------------------------------------------------
-// Pool / residual / GAP / loss / optimiser
+// Pool / residual / GAP (elem.hip; BatchNorm + pool in one pass: bn.hip) / loss (loss.hip; the window gather: augment.hip) /
+// optimiser (optim.hip)
 // ---------------------------------------------------------------------------
 void launch_maxpool_fwd(const float* X, float* Y, uint8_t* arg, int B, int H, int W, int C, hipStream_t s);
 void launch_maxpool_bwd(const float* dY, const uint8_t* arg, const float* Y, float* dX, int B, int H, int W, int C,
@@ -434,7 +437,7 @@ void adam_segments_finalize(AdamSegTable& tab);
 void launch_adam_segments(float* w, float* g, float* m, float* v, const AdamSegTable& tab, float alpha, float c1, float c2,
                           float eps, hipStream_t s, const StepState* st = nullptr, const float* alpha_table = nullptr);
 // ---------------------------------------------------------------------------
-// Optimiser options (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_optim): a learning-rate schedule,
+// Optimiser options (optim.hip; opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_optim): a learning-rate schedule,
 // decoupled weight decay, global-norm / value clipping.  A schedule alone only changes the step-size table of the fused
 // launch above.  Decay or a clip take the FINISH + UPDATE path, three launches on one stream: launch_grad_finish (slab
 // sums stored to g, one fp32 partial of sum g^2 per workgroup) -> launch_clip_scale (partials summed in double, the
@@ -477,7 +480,7 @@ void launch_adamw(float* w, const float* g, float* m, float* v, const uint8_t* k
                   const AdamwArgs& a, hipStream_t s, const StepState* st = nullptr, const float* alpha_table = nullptr,
                   const float* lr_table = nullptr);
 // ---------------------------------------------------------------------------
-// Weight EMA (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_ema): an average arena a in the parameter
+// Weight EMA (optim.hip; opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_ema): an average arena a in the parameter
 // arena's layout, advanced by ONE launch after the optimiser's launch(es) of a step.  The optimiser kernels are untouched.
 // ---------------------------------------------------------------------------
 struct EmaCfg {
@@ -589,7 +592,7 @@ void launch_confusion(const int32_t* y_true, const int32_t* y_pred, int64_t n, i
                       int64_t* cm, hipStream_t s);
 
 // ---------------------------------------------------------------------------
-// Operating-point read-out (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_opoint): per class, one-vs-rest,
+// Operating-point read-out (opoint.hip; opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_opoint): per class, one-vs-rest,
 // the threshold that still catches `recall` of the positives, the false positives at it, and twice the Mann-Whitney U.
 // Defined in integers on the total order of the score bit patterns: three launches (keys, counts, select), no atomics.
 // ---------------------------------------------------------------------------

@@ -14,7 +14,6 @@
 namespace cmoop {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t ABS_MASK = 0x7FFFFFFFu, CANONICAL_NAN = 0x7FC00000u;

@@ -1,4 +1,4 @@
-"""Float64 references of the BatchNorm / pooling / loss / optimiser kernels (csrc/elem.hip), the numpy float32
+"""Float64 references of the BatchNorm / pooling / loss / optimiser kernels (csrc/bn.hip, elem.hip, loss.hip, optim.hip), the numpy float32
 restatement of adam_update, the host twins of the launchers' shape arithmetic, and the input generators of
 tests/test_gpu_elem_kernels.py.  Everything here runs on the CPU; tests/test_elem_reference_cpu.py pins the references
 to oracle/net.py and the generators to their stated conditions."""
@@ -23,7 +23,7 @@ def f64(a):
     return np.asarray(a, np.float64)
 
 
-# ---- host twins of the launchers' shape arithmetic (elem.hip) ---------------------------------------------------------------
+# ---- host twins of the launchers' shape arithmetic (bn.hip, elem.hip) ---------------------------------------------------------------
 def cdiv(a, b):
     return -(-a // b)
 

@@ -1,5 +1,5 @@
-"""GPU parity, kernel by kernel, of the BatchNorm / pooling / loss / optimiser kernels of csrc/elem.hip (through the
-per-kernel C ABI entries) against the float64 references of tests/_elem_reference.py.
+"""GPU parity, kernel by kernel, of the BatchNorm / pooling / loss / optimiser kernels of csrc/bn.hip, elem.hip, loss.hip
+and optim.hip (through the per-kernel C ABI entries) against the float64 references of tests/_elem_reference.py.
 
 Two regimes.  EXACT: small-integer inputs, integer means, power-of-two invstd / gamma -- every fp32 sum is exact in any
 order, so the device result must EQUAL the float64 reference cast to float32.  FLOAT: random normal inputs, gated by

@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 
 P = _lib.ptr
 LR, B1, B2, AEPS = 1e-3, 0.9, 0.999, 1e-7               # cmoop_config_default's optimiser constants
-# grad_finish_kernel's structure (elem.hip): 256 threads, a plain workgroup covers 1024 elements (4 per thread), a vector slab
+# grad_finish_kernel's structure (optim.hip): 256 threads, a plain workgroup covers 1024 elements (4 per thread), a vector slab
 # workgroup 64 x 4 and a scalar slab workgroup 64; the longest fp32 chain of a partial is one square, 3 adds in the thread,
 # 6 shuffle levels in the wave of 64, 3 adds over the four waves
 PLAIN_PER_BLOCK, SLAB_COLS = 1024, 64

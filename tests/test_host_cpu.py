@@ -24,6 +24,18 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert L.cmoop_abi_version() == 3
 
 
+def test_makefile_lists_every_hip_source():
+    """SRCS of csrc/Makefile is exactly the set of csrc/*.hip: a file left out would link a library that fails to load (an
+    undefined launcher), a name without a file would not build."""
+    import glob
+    import re
+    mk = open(os.path.join(_lib.CSRC, "Makefile")).read().replace("\\\n", " ")
+    srcs = re.search(r"^SRCS\s*=(.*)$", mk, re.M).group(1).split()
+    on_disk = sorted(os.path.basename(p) for p in glob.glob(os.path.join(_lib.CSRC, "*.hip")))
+    assert len(srcs) == len(set(srcs)), srcs
+    assert sorted(srcs) == on_disk
+
+
 def test_abi_host_only_closed_forms_match_python():
     L = _lib.lib()
     for variant in (0, 1):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Signed error of the device's float32 log and exp against float64, in ulps of the result: the measurement behind the
-double-precision logarithms of softmax_ce_kernel<CE_DISTILL> (csrc/elem.hip), recorded in profiles/distill_logf_bias.txt.
+double-precision logarithms of softmax_ce_kernel<CE_DISTILL> (csrc/loss.hip), recorded in profiles/distill_logf_bias.txt.
 
   python tools/device_log_bias.py
 
