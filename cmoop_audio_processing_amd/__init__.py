@@ -12,6 +12,7 @@ from .evaluator import (AudioNASProblem, EvalConfig, PopulationEvaluator, calcul
                         compute_model_size_mb, compute_objectives_and_constraints, evaluate_individual, install,
                         queued_map, sharded_map)
 from .frontend import FrontendConfig, PcenConfig, log_mel_stream  # noqa: F401
+from .resample import resample_poly  # noqa: F401
 from .augment import AugmentConfig  # noqa: F401
 from .loss import LossConfig  # noqa: F401
 from .distill import DistillConfig  # noqa: F401
@@ -24,4 +25,4 @@ from .deploy import StreamScorer, TrainedModel, detect_events, smooth_posteriors
 
 __all__ = ["genes", "AugmentConfig", "LossConfig", "DistillConfig", "OptimConfig", "EmaConfig", "OperatingPointConfig", "QuantConfig", "PruneConfig", "EvalConfig", "PopulationEvaluator", "AudioNASProblem", "install", "evaluate_individual",
            "compute_objectives_and_constraints", "compute_model_size_mb", "calculate_fpr", "sharded_map", "queued_map", "FrontendConfig", "PcenConfig",
-           "log_mel_stream", "TrainedModel", "StreamScorer", "smooth_posteriors", "detect_events"]
+           "log_mel_stream", "resample_poly", "TrainedModel", "StreamScorer", "smooth_posteriors", "detect_events"]

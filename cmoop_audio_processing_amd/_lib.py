@@ -244,6 +244,17 @@ PCEN_PROTOTYPES = {
 }
 
 
+#: prototypes of the resampling entry points (include/cmoop.h); pointers travel as void*, None is NULL
+RESAMPLE_PROTOTYPES = {
+    "cmoop_resample_filter": [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p],
+    "cmoop_resample_plan": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_resample_tile_span": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cmoop_resample": [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p],
+    "cmoop_resample_time": [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                            C.c_void_p],
+}
+
+
 #: prototypes of the per-kernel entry points of the BatchNorm / pooling / loss / optimiser kernels (include/cmoop.h)
 _V, _I32, _I64, _F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 ELEM_PROTOTYPES = {
@@ -325,7 +336,7 @@ def lib():
         L.cmoop_config_default.restype = None
         for table in (STREAM_PROTOTYPES, AUGMENT_PROTOTYPES, PCEN_PROTOTYPES, ELEM_PROTOTYPES, LOSS_PROTOTYPES, DENSE_PROTOTYPES,
                       DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES, OPOINT_PROTOTYPES, QUANT_PROTOTYPES,
-                      PRUNE_PROTOTYPES):
+                      PRUNE_PROTOTYPES, RESAMPLE_PROTOTYPES):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         _lib = L

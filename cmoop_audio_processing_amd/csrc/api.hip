@@ -1278,6 +1278,72 @@ int cmoop_stream_windows(int64_t n_frames, int32_t T, int32_t hop_frames, int64_
     });
 }
 
+// ---- resampling ----------------------------------------------------------------
+int cmoop_resample_filter(int32_t up, int32_t down, int32_t half_width, double beta, float* taps_host, int32_t cap, int32_t* n_taps) {
+    return guard([&] {
+        const int n = resample_filter_taps(up, down, half_width);
+        if (n_taps) *n_taps = n;
+        if (!taps_host) return;                                       // the size query
+        if (cap < n) throw std::runtime_error("resample: cap must hold n_taps = " + std::to_string(n) + " values (got " + std::to_string(cap) + ")");
+        resample_filter(up, down, half_width, beta, taps_host);
+    });
+}
+
+int cmoop_resample_plan(int64_t n_samples, int32_t up, int32_t down, int32_t n_taps, int64_t* n_out, int32_t* tile, int64_t* n_tiles,
+                        int32_t* taps_per_output) {
+    return guard([&] {
+        const ResamplePlan p = resample_plan(n_samples, up, down, n_taps);
+        if (n_out) *n_out = p.n_out;
+        if (tile) *tile = p.tile;
+        if (n_tiles) *n_tiles = p.n_tiles;
+        if (taps_per_output) *taps_per_output = p.tpp;
+    });
+}
+
+int cmoop_resample_tile_span(int64_t n_samples, int32_t up, int32_t down, int32_t n_taps, int64_t tile_index, int64_t* out_first,
+                             int32_t* out_count, int64_t* in_first, int32_t* in_count) {
+    return guard([&] {
+        const ResampleSpan s = resample_tile_span(resample_plan(n_samples, up, down, n_taps), tile_index);
+        if (out_first) *out_first = s.out_first;
+        if (out_count) *out_count = s.out_count;
+        if (in_first) *in_first = s.in_first;
+        if (in_count) *in_count = s.in_count;
+    });
+}
+
+// the whole domain is checked before the stream is taken; avg_ms null: one launch, else timed launches (the table goes up once)
+static void resample_abi(const float* wav, int64_t n_clips, int64_t n_samples, int32_t up, int32_t down, const float* taps, int32_t n_taps,
+                         float* out, int32_t iters, double* avg_ms) {
+    const ResamplePlan p = resample_plan(n_samples, up, down, n_taps);
+    resample_check_rows(p, n_clips);
+    if (!taps) throw std::runtime_error("resample: taps_host must not be NULL (got NULL)");
+    if (n_clips > 0 && (!wav || !out || wav == out))
+        throw std::runtime_error("resample: wav_dev and out_dev must be two device buffers (got NULL or the same pointer)");
+    const std::vector<float> tab = resample_polyphase_table(p, taps);
+    const int cu = compute_units_of_current_device();
+    hipStream_t s = lib_stream();
+    PoolScope pool(s);
+    float* tab_dev = pool.get<float>(tab.size() * sizeof(float));
+    CMOOP_HIP(hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    auto once = [&] { launch_resample(wav, n_clips, p, tab_dev, out, cu, s); };
+    if (avg_ms) *avg_ms = time_launches(s, iters, once);
+    else once();
+    CMOOP_HIP(hipStreamSynchronize(s));
+}
+
+int cmoop_resample(const float* wav_dev, int64_t n_clips, int64_t n_samples, int32_t up, int32_t down, const float* taps_host,
+                   int32_t n_taps, float* out_dev) {
+    return guard([&] { resample_abi(wav_dev, n_clips, n_samples, up, down, taps_host, n_taps, out_dev, 0, nullptr); });
+}
+
+int cmoop_resample_time(const float* wav_dev, int64_t n_clips, int64_t n_samples, int32_t up, int32_t down, const float* taps_host,
+                        int32_t n_taps, float* out_dev, int32_t iters, double* avg_ms) {
+    return guard([&] {
+        if (iters < 1 || !avg_ms) throw std::runtime_error("resample: iters must be >= 1 with an avg_ms to write (got " + std::to_string(iters) + ")");
+        resample_abi(wav_dev, n_clips, n_samples, up, down, taps_host, n_taps, out_dev, iters, avg_ms);
+    });
+}
+
 int cmoop_mfcc(const float* logmel_dev, int64_t rows, int32_t n_mels, int32_t n_mfcc, float* out_dev) {
     return guard([&] {
         CMOOP_REQUIRE(rows >= 0 && (rows == 0 || (logmel_dev && out_dev && logmel_dev != out_dev)), "mfcc: out of place, rows >= 0");

@@ -686,4 +686,42 @@ void launch_mfcc(const float* X, float* Y, int64_t rows, int n_mels, int n_mfcc,
 void launch_standardize(float* X, const double* mean, const double* scale, int64_t rows, int C, hipStream_t s);
 void colstats_finalize_f64(const float* P, int blocks, int64_t M, int C, double* mean, double* scale, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// Polyphase resampler (resample.hip; north-star addition, the reference has no front end): audio at any rate -> the front
+// end's rate.  y[n] = sum_i x[i] h[n down - i up + half], n_out = ceil(L up / down); include/cmoop.h fixes the semantics.
+// ---------------------------------------------------------------------------
+constexpr int RESAMPLE_MAX_RATE = 1024;            // 1 <= up, down
+constexpr int RESAMPLE_MAX_HALF_WIDTH = 4096;      // of the designed filter, in periods of the slower rate
+constexpr int RESAMPLE_MAX_TPP = 256;              // taps per output, ceil(n_taps / up)
+constexpr int RESAMPLE_MAX_TILE = 512;             // outputs per workgroup
+constexpr int RESAMPLE_LDS_FLOATS = 8192;          // 32 KiB: the input span a workgroup stages, at most
+constexpr int RESAMPLE_LDS_BYTES = 64 * 1024;      // span and, where it fits beside it, the polyphase table: one workgroup's LDS
+constexpr int RESAMPLE_CU_LDS_BYTES = 160 * 1024;  // of a compute unit: how many table-holding workgroups stay resident
+constexpr int64_t RESAMPLE_MAX_ELEMS = 1ll << 36;  // n_clips * max(n_samples, n_out) stays below
+constexpr int64_t RESAMPLE_MAX_GRID = 1 << 16;     // workgroups of a launch; they stride over the (row, tile) pairs
+struct ResamplePlan {
+    int up = 1, down = 1, n_taps = 1, half = 0, tpp = 1, tile = 1;
+    int span_floats = 4, tab_stride = 1;             // LDS floats of the widest span; floats between two rows of the table
+    bool tab_in_lds = false;                         // the table is copied into LDS beside the span (up > 1, both within 64 KiB)
+    int64_t n_samples = 0, n_out = 0, n_tiles = 0;   // per row
+};
+struct ResampleSpan {                               // what the workgroup of one tile writes and stages
+    int64_t out_first = 0, in_first = 0;            // in_first may be negative, in_first + in_count may pass n_samples
+    int out_count = 0, in_count = 0;
+};
+// host-only; each throws "resample: <argument> <rule> (got ..)" outside the domain
+int resample_filter_taps(int up, int down, int half_width);   // 2 half_width max(up, down) + 1
+// the Kaiser-windowed sinc of scipy.signal.resample_poly, designed in double, rounded once to fp32: taps[n_taps]
+void resample_filter(int up, int down, int half_width, double beta, float* taps);
+// tile is a function of (up, down, n_taps) alone: min(512, (8192 - tpp - 2) up / down), whole waves from 64 on, at least 1
+ResamplePlan resample_plan(int64_t n_samples, int up, int down, int n_taps);
+// out_first = tile_index tile; in_first = (out_first down + half) / up - tpp + 1;
+// in_count = ((out_first + out_count - 1) down + half) / up - in_first + 1
+ResampleSpan resample_tile_span(const ResamplePlan& p, int64_t tile_index);
+void resample_check_rows(const ResamplePlan& p, int64_t n_clips);
+// [up][tab_stride], row p = the tpp taps of phase p = (n down + half) mod up in ascending input index, zero-padded
+std::vector<float> resample_polyphase_table(const ResamplePlan& p, const float* taps);
+void launch_resample(const float* x, int64_t n_clips, const ResamplePlan& p, const float* tab_dev, float* y, int compute_units,
+                     hipStream_t s);
+
 }  // namespace cmoop

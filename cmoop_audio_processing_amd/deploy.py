@@ -27,6 +27,7 @@ import numpy as np
 from . import genes as G
 from .evaluator import EvalConfig
 from .frontend import FrontendConfig, PcenConfig, log_mel_stream
+from .resample import to_rate
 
 _OBJECTIVE_KEYS = ("acc", "size_mb", "fpr", "epochs_run")
 _FE_INT = ("sr", "n_fft", "win", "hop", "n_mels")
@@ -283,10 +284,14 @@ class StreamScorer:
     def __exit__(self, *a):
         self.close()
 
-    def score(self, wav):
+    def score(self, wav, sr=None):
         """wav: CUDA float32 [n_samples] -> (t_start seconds float64 [n_windows], CUDA float32 probs [n_windows, classes]);
-        window i starts at frame i * hop_frames, i.e. at ``i * hop_frames * hop / sr`` seconds."""
+        window i starts at frame i * hop_frames, i.e. at ``i * hop_frames * hop / sr`` seconds of the front end's rate.
+        ``sr``: the rate the recording arrives at; when it differs from the front end's, the recording is resampled to that
+        rate first (``resample_poly``).  ``t_start`` is in seconds either way.  A non-positive or non-integer ``sr`` raises
+        ValueError; None or the front end's own rate is the plain path."""
         fe = self.frontend
+        wav = to_rate(wav, sr, fe.sr, "StreamScorer.score")
         feat = log_mel_stream(wav, fe)
         probs = self.net.predict_stream(feat, self.hop_frames, frontend_config=fe if fe.scale == "db" else None,
                                         mean=self.model.mean, scale=self.model.scale)

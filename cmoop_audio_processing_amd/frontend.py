@@ -27,6 +27,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from .resample import resample_poly, to_rate  # noqa: F401  (frontend.resample_poly)
 
 HOP, N_MELS = 160, 40
 MFCC_MAX_MELS = 64      # cmoop_mfcc's DCT kernel holds at most a 64 x 64 basis
@@ -231,9 +232,13 @@ def _log_mel_config(wav, config: FrontendConfig):
     return out
 
 
-def log_mel(wav, config: FrontendConfig | None = None):
-    """wav: CUDA float32 [N, L] -> CUDA float32 [N, 1 + L//160, 40]; with a config, [N, 1 + L//hop, n_mels] in its scale."""
+def log_mel(wav, config: FrontendConfig | None = None, sr: int | None = None):
+    """wav: CUDA float32 [N, L] -> CUDA float32 [N, 1 + L//160, 40]; with a config, [N, 1 + L//hop, n_mels] in its scale.
+    ``sr``: the rate the clips arrive at; when it differs from the config's (16000 without one) they are resampled to it first
+    (``resample_poly``), so L above is then the resampled length."""
     import torch
+    if sr is not None:
+        wav = to_rate(wav, sr, 16000 if config is None else config.sr, "log_mel")
     if config is not None:
         return _log_mel_config(wav, config)
     if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2):
@@ -246,7 +251,7 @@ def log_mel(wav, config: FrontendConfig | None = None):
     return out
 
 
-def log_mel_stream(wav, config: FrontendConfig | None = None):
+def log_mel_stream(wav, config: FrontendConfig | None = None, sr: int | None = None):
     """ONE recording, CUDA float32 [L] -> CUDA float32 [1 + L//hop, n_mels], its frames spread over the whole chip.
 
     Log scale: frame for frame the bits of ``log_mel(wav[None], config)[0]``.  dB scale: the UN-REFERENCED
@@ -255,10 +260,13 @@ def log_mel_stream(wav, config: FrontendConfig | None = None):
     the recording is normalised ONCE, from its first frame, by the chunked three-launch scan (``pcen`` on the power
     stream, bit for bit); windows cut from it need no per-window step, and a recording of at most
     ``pcen_stream_plan(T)[0]`` frames carries the bits of ``log_mel(wav[None], config)[0]``.
-    ``config=None`` is ``FrontendConfig()``."""
+    ``config=None`` is ``FrontendConfig()``.  ``sr``: the rate the recording arrives at; when it differs from the config's it
+    is resampled to it first (``resample_poly``), so L above is then the resampled length."""
     import torch
     if config is None:
         config = FrontendConfig()
+    if sr is not None:
+        wav = to_rate(wav, sr, config.sr, "log_mel_stream")
     if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 1):
         raise ValueError("log_mel_stream expects a CUDA float32 tensor [n_samples]")
     wav = wav.contiguous()

@@ -709,6 +709,49 @@ int cmoop_logmel_pcen_stream(const cmoop_frontend_config* c, const cmoop_pcen* p
 /* as cmoop_logmel_stream_time, for the four launches of the call above */
 int cmoop_logmel_pcen_stream_time(const cmoop_frontend_config* c, const cmoop_pcen* p, const float* wav_dev, int64_t n_samples,
                                   float* out_dev, int32_t iters, double* avg_ms);
+/* ---- resampling: clips and recordings at any sample rate, brought to the front end's rate on the GPU (north-star addition;
+ *      the reference has no front end).  No audio-quality or accuracy claim is made beyond "this is the default filter of
+ *      scipy.signal.resample_poly".
+ * Rational rate change by up / down with gcd(up, down) = 1 and an odd-length centred FIR h of n_taps = 2 half + 1 taps.
+ * For a row x[0..L), x = 0 outside:
+ *     n_out = ceil(L up / down)
+ *     y[n]  = sum_i x[i] h[n down - i up + half]      over all i with 0 <= n down - i up + half <= 2 half and 0 <= i < L
+ * With the default filter this is scipy.signal.resample_poly(x, up, down) (float64: equal lengths, outputs to 1e-15 of the maximum).
+ * Default filter (cmoop_resample_filter): half = half_width max(up, down) (half_width 10 is scipy's), fc = 1 / max(up, down),
+ *     h[k] = up w[k] fc sinc(fc (k - half)) / sum_k(w[k] fc sinc(fc (k - half)))
+ * w the Kaiser window of n_taps points (beta 5.0 is scipy's), designed in double on the host with I0 from its power series
+ * (scipy.signal.firwin(n_taps, fc, window=("kaiser", beta)) * up to 1.3e-15 of the maximum) and rounded once to fp32.
+ * A caller may pass any odd number of any fp32 taps instead (scipy's window=<array> form).
+ * Device arithmetic: one fp32 accumulator per output, started at 0.0f, terms in ascending i, one fmaf per term; the order is
+ * part of the definition, so every launch shape gives the same bits.
+ * Domain: 1 <= up, down <= 1024 (reduced); n_taps odd; taps per output tpp = ceil(n_taps / up) <= 256 (the default filter
+ * therefore serves every down <= 12 up); n_clips >= 0; 1 <= n_samples; n_clips * max(n_samples, n_out) < 2^36.  up = down = 1
+ * is a plain FIR.  Errors start with "resample: " and name the offending argument.
+ * Launch: a workgroup owns `tile` consecutive outputs of one row and stages the inputs they read, zero outside [0, L) of its
+ * own row.  tile = min(512, (8192 - tpp - 2) up / down), rounded down to a multiple of 64 from 64 on and at least 1: a function
+ * of (up, down, n_taps) alone, never of the device, that keeps the staged span within 8192 floats.  Tile j of a row holds
+ * outputs out_first = j tile .. + out_count and stages in_count inputs from
+ *     in_first = (out_first down + half) / up - tpp + 1      up to      ((out_first + out_count - 1) down + half) / up
+ * (64-bit, computed once per workgroup; indices inside the tile are 32-bit).  in_first may be negative and the span may run
+ * past n_samples: the zero-filled part counts.  HBM-bound: 4 L + 4 n_out bytes and tpp n_out FMA per row. */
+/* host-only: the default filter.  *n_taps = 2 half_width max(up, down) + 1 always (taps_host NULL: only that); otherwise
+ * cap >= *n_taps values are needed.  1 <= half_width <= 4096, beta >= 0 */
+int cmoop_resample_filter(int32_t up, int32_t down, int32_t half_width, double beta, float* taps_host, int32_t cap, int32_t* n_taps);
+/* host-only: output length, tile, tiles per row and taps per output of a row of n_samples; NULL outputs are skipped */
+int cmoop_resample_plan(int64_t n_samples, int32_t up, int32_t down, int32_t n_taps, int64_t* n_out, int32_t* tile, int64_t* n_tiles,
+                        int32_t* taps_per_output);
+/* host-only: what workgroup `tile_index` of a row stages -- the launcher's own arithmetic */
+int cmoop_resample_tile_span(int64_t n_samples, int32_t up, int32_t down, int32_t n_taps, int64_t tile_index, int64_t* out_first,
+                             int32_t* out_count, int64_t* in_first, int32_t* in_count);
+/* One launch on the library's stream for clip batches and for one long recording (n_clips 1) alike; out of place.  The
+ * polyphase table [up][tpp] (86 KB at most for the default filter) is built on the host per call and uploaded into pooled
+ * device memory; where it fits a workgroup's LDS beside the span, persistent workgroups copy it there once. */
+int cmoop_resample(const float* wav_dev /* [n_clips][n_samples] */, int64_t n_clips, int64_t n_samples, int32_t up, int32_t down,
+                   const float* taps_host /* [n_taps] */, int32_t n_taps, float* out_dev /* [n_clips][n_out] */);
+/* as cmoop_logmel_stream_time: average milliseconds of `iters` launches between two HIP events after 3 warm-up launches
+ * (the table upload is outside the timed window) */
+int cmoop_resample_time(const float* wav_dev, int64_t n_clips, int64_t n_samples, int32_t up, int32_t down, const float* taps_host,
+                        int32_t n_taps, float* out_dev, int32_t iters, double* avg_ms);
 /* optional MFCC features: DCT-II, ortho-normalised, along the mel axis of log-mel rows; first n_mfcc coefficients.
  * The reference ships no front end; its comment at ablation_study/sa_nsga_init.py:68 calls the stored features MFCCs. */
 int cmoop_mfcc(const float* logmel_dev /* [rows][n_mels] */, int64_t rows, int32_t n_mels, int32_t n_mfcc,
