@@ -21,8 +21,9 @@ from .ema import EmaConfig  # noqa: F401
 from .opoint import OperatingPointConfig  # noqa: F401
 from .quant import QuantConfig  # noqa: F401
 from .prune import PruneConfig  # noqa: F401
+from .quant import ActQuantConfig  # noqa: F401
 from .deploy import StreamScorer, TrainedModel, detect_events, smooth_posteriors  # noqa: F401
 
-__all__ = ["genes", "AugmentConfig", "LossConfig", "DistillConfig", "OptimConfig", "EmaConfig", "OperatingPointConfig", "QuantConfig", "PruneConfig", "EvalConfig", "PopulationEvaluator", "AudioNASProblem", "install", "evaluate_individual",
+__all__ = ["genes", "AugmentConfig", "LossConfig", "DistillConfig", "OptimConfig", "EmaConfig", "OperatingPointConfig", "QuantConfig", "PruneConfig", "ActQuantConfig", "EvalConfig", "PopulationEvaluator", "AudioNASProblem", "install", "evaluate_individual",
            "compute_objectives_and_constraints", "compute_model_size_mb", "calculate_fpr", "sharded_map", "queued_map", "FrontendConfig", "PcenConfig",
            "log_mel_stream", "resample_poly", "TrainedModel", "StreamScorer", "smooth_posteriors", "detect_events"]

@@ -86,6 +86,16 @@ class Prune(C.Structure):
                 ("skip_small", C.c_int32)]
 
 
+class ActQuant(C.Structure):
+    """cmoop_actquant (include/cmoop.h), 16 bytes."""
+    _fields_ = [("bits", C.c_int32), ("momentum", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class ActRange(C.Structure):
+    """cmoop_act_range (include/cmoop.h), 16 bytes."""
+    _fields_ = [("m_b", C.c_float), ("r", C.c_float), ("count", C.c_int32), ("reserved", C.c_int32)]
+
+
 class OpointClass(C.Structure):
     """cmoop_opoint_class (include/cmoop.h), 32 bytes."""
     _fields_ = [("u2", C.c_int64), ("P", C.c_int32), ("N", C.c_int32), ("k", C.c_int32), ("tp", C.c_int32), ("fp", C.c_int32),
@@ -230,6 +240,22 @@ PRUNE_PROTOTYPES = {
 }
 
 
+#: prototypes of the activation-fake-quantisation entry points (include/cmoop.h); structs travel as void* (C.byref), None is NULL
+ACTQUANT_PROTOTYPES = {
+    "cmoop_actquant_default": [C.c_void_p],
+    "cmoop_actquant_check": [C.c_void_p],
+    "cmoop_actquant_sites": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p],
+    "cmoop_fake_quant_act": [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float],
+    "cmoop_fake_quant_act_time": [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_void_p],
+    "cmoop_net_set_actquant": [C.c_void_p, C.c_void_p],
+    "cmoop_net_get_act_ranges": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
+    "cmoop_net_set_act_ranges": [C.c_void_p, C.c_void_p, C.c_int32],
+    "cmoop_net_get_act": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    # cmoop_eval_population_p with one more struct pointer after pr
+    "cmoop_eval_population_aq": [C.c_void_p] * 13 + [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_void_p] * 10,
+}
+
+
 #: prototypes of the PCEN entry points (include/cmoop.h); structs travel as void* (C.byref)
 PCEN_PROTOTYPES = {
     "cmoop_pcen_default": [C.c_void_p],
@@ -336,7 +362,7 @@ def lib():
         L.cmoop_config_default.restype = None
         for table in (STREAM_PROTOTYPES, AUGMENT_PROTOTYPES, PCEN_PROTOTYPES, ELEM_PROTOTYPES, LOSS_PROTOTYPES, DENSE_PROTOTYPES,
                       DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES, OPOINT_PROTOTYPES, QUANT_PROTOTYPES,
-                      PRUNE_PROTOTYPES, RESAMPLE_PROTOTYPES):
+                      PRUNE_PROTOTYPES, ACTQUANT_PROTOTYPES, RESAMPLE_PROTOTYPES):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         _lib = L

@@ -226,6 +226,17 @@ static PruneTable to_prune_table(const int64_t* rows, int32_t count, int64_t n) 
     prune_table_finalize(tab, n);
     return tab;
 }
+static_assert(sizeof(cmoop_actquant) == 16, "cmoop_actquant is part of the ABI");
+static ActQuantCfg to_actquant(const cmoop_actquant* a) {
+    CMOOP_REQUIRE(a != nullptr, "actquant config is NULL");
+    ActQuantCfg c;
+    c.bits = a->bits; c.momentum = a->momentum; c.reserved[0] = a->reserved[0]; c.reserved[1] = a->reserved[1];
+    return c;
+}
+// cmoop_act_range and ActRange are one layout
+static_assert(sizeof(cmoop_act_range) == sizeof(ActRange) && offsetof(cmoop_act_range, m_b) == offsetof(ActRange, m_b) &&
+              offsetof(cmoop_act_range, r) == offsetof(ActRange, r) && offsetof(cmoop_act_range, count) == offsetof(ActRange, count) &&
+              offsetof(cmoop_act_range, reserved) == offsetof(ActRange, reserved), "cmoop_act_range layout");
 // cmoop_opoint_class and OpointClass are one layout (asserted above and field by field here)
 static OpointClass* as_classes(cmoop_opoint_class* c) {
     static_assert(offsetof(cmoop_opoint_class, u2) == offsetof(OpointClass, u2) && offsetof(cmoop_opoint_class, P) == offsetof(OpointClass, P) &&
@@ -236,7 +247,7 @@ static OpointClass* as_classes(cmoop_opoint_class* c) {
 }
 
 // The converted training options of one population call: to_* and the matching *_check of every struct handed in, in the
-// order augment, loss, distill, optim, ema, opoint, quant, prune (what a call with two bad structs reports first); owns what opt points into
+// order augment, loss, distill, optim, ema, opoint, quant, prune, actquant (what a call with two bad structs reports first); owns what opt points into
 namespace {
 struct AbiTrainOptions {
     AugmentCfg aug;
@@ -247,9 +258,11 @@ struct AbiTrainOptions {
     OpointCfg opoint;
     QuantCfg quant;
     PruneCfg prune;
+    ActQuantCfg actq;
     TrainOptions opt;
     AbiTrainOptions(const cmoop_augment* a, const cmoop_loss* l, const cmoop_distill* d, const cmoop_optim* o, const cmoop_ema* e,
-                    const cmoop_opoint* p, const cmoop_quant* q, const cmoop_prune* pr, const NetConfig& c, const Dataset& ds) {
+                    const cmoop_opoint* p, const cmoop_quant* q, const cmoop_prune* pr, const cmoop_actquant* aq, const NetConfig& c,
+                    const Dataset& ds) {
         if (a) { aug = to_augment(a); augment_check(aug, ds.T, ds.F); opt.aug = &aug; }
         if (l) { loss = to_loss(l); loss_check(loss, c.classes); opt.loss = &loss; }
         if (d) { distill = to_distill(d); distill_check(distill, c.classes, ds.n_train); opt.distill = &distill; }
@@ -258,6 +271,7 @@ struct AbiTrainOptions {
         if (p) { opoint = to_opoint(p); opoint_check(opoint); opt.opoint = &opoint; }
         if (q) { quant = to_quant(q); quant_check(quant); opt.quant = &quant; }
         if (pr) { prune = to_prune(pr); prune_check(prune); opt.prune = &prune; }
+        if (aq) { actq = to_actquant(aq); actquant_check(actq); opt.actq = &actq; }
     }
     AbiTrainOptions(const AbiTrainOptions&) = delete;
 };
@@ -371,8 +385,8 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 // every population call; next == NULL: candidates are taken longest-first from a process-local counter; a NULL option: off
 static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss,
                                 const cmoop_distill* distill, const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op,
-                                const cmoop_quant* q, const cmoop_prune* pr, const cmoop_dataset* ds, const int32_t* genes,
-                                const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr,
+                                const cmoop_quant* q, const cmoop_prune* pr, const cmoop_actquant* aq, const cmoop_dataset* ds,
+                                const int32_t* genes, const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr,
                                 int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated, double* opoint, double* quant,
                                 double* prune) {
     CMOOP_REQUIRE(ds && genes && seeds, "NULL argument");
@@ -380,7 +394,7 @@ static void eval_population_abi(const cmoop_config* cfg, const cmoop_augment* au
     CMOOP_REQUIRE(!next || evaluated, "NULL argument");
     NetConfig c = to_cfg(cfg);
     const Dataset d = to_dataset(ds);
-    const AbiTrainOptions options(aug, loss, distill, optim, ema, op, q, pr, c, d);
+    const AbiTrainOptions options(aug, loss, distill, optim, ema, op, q, pr, aq, c, d);
     CMOOP_REQUIRE(n == 0 || (d.x_train && d.y_train && d.x_val && d.y_val), "dataset pointers are NULL");
     for (int i = 0; i < n; ++i) check_plan_ranges(genes + 6 * i, c.variant, d.T, d.F, std::max(c.batch, c.eval_batch));
     std::vector<EvalResult> r(n);
@@ -477,9 +491,91 @@ int cmoop_eval_population_p(const cmoop_config* cfg, const cmoop_augment* aug, c
                             const cmoop_prune* pr, const cmoop_dataset* ds, const int32_t* genes, const uint32_t* seeds, int32_t n,
                             cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr, int32_t* epochs_run,
                             double* val_loss, double* seconds, int32_t* evaluated, double* opoint, double* quant, double* prune) {
+    return cmoop_eval_population_aq(cfg, aug, loss, distill, optim, ema, op, q, pr, nullptr, ds, genes, seeds, n, next, ctx, acc, size_mb,
+                                    fpr, epochs_run, val_loss, seconds, evaluated, opoint, quant, prune);
+}
+
+int cmoop_eval_population_aq(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                             const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_quant* q,
+                             const cmoop_prune* pr, const cmoop_actquant* aq, const cmoop_dataset* ds, const int32_t* genes,
+                             const uint32_t* seeds, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb, double* fpr,
+                             int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated, double* opoint, double* quant,
+                             double* prune) {
     return guard([&] {
-        eval_population_abi(cfg, aug, loss, distill, optim, ema, op, q, pr, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr, epochs_run,
-                            val_loss, seconds, evaluated, opoint, quant, prune);
+        eval_population_abi(cfg, aug, loss, distill, optim, ema, op, q, pr, aq, ds, genes, seeds, n, next, ctx, acc, size_mb, fpr,
+                            epochs_run, val_loss, seconds, evaluated, opoint, quant, prune);
+    });
+}
+
+// ---- activation fake quantisation ----------------------------------------------------
+int cmoop_actquant_default(cmoop_actquant* aq) {
+    return guard([&] {
+        CMOOP_REQUIRE(aq != nullptr, "actquant config is NULL");
+        std::memset(aq, 0, sizeof(*aq));
+        aq->momentum = 0.99f;
+    });
+}
+
+int cmoop_actquant_check(const cmoop_actquant* aq) {
+    return guard([&] { actquant_check(to_actquant(aq)); });
+}
+
+int cmoop_actquant_sites(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int32_t* rows, int32_t cap,
+                         int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(gene != nullptr && T >= 1 && F >= 1, "actquant_sites: NULL gene or an empty patch");
+        NetConfig cfg;
+        cfg.variant = variant; cfg.classes = classes;
+        const NetPlan plan = plan_net(gene, cfg, T, F);
+        CMOOP_REQUIRE(rows && cap >= plan.n_sites, "actquant_sites: the rows buffer is too small");
+        for (int i = 0; i < (int)plan.acts.size(); ++i) {
+            const Act& a = plan.acts[i];
+            if (a.site < 0) continue;
+            const int32_t v[4] = {i, a.H, a.W, a.C};
+            std::memcpy(rows + 4 * (size_t)a.site, v, sizeof(v));
+        }
+        if (count) *count = plan.n_sites;
+    });
+}
+
+// the body of cmoop_fake_quant_act(_time): record and partials on pooled buffers, then avg_ms null: one call, else timed calls
+static void fake_quant_act_abi(float* x, int64_t n, int32_t bits, const float* a_in, cmoop_act_range* record, float momentum,
+                               int32_t iters, double* avg_ms) {
+    ActQuantCfg c;
+    c.bits = bits; c.momentum = momentum;
+    actquant_check(c);
+    CMOOP_REQUIRE(actquant_enabled(c), "fake_quant_act: bits must be in [2, 8]");
+    CMOOP_REQUIRE(n >= 0 && n <= ACT_QUANT_MAX_ELEMS, "fake_quant_act: n must stay below 2^31 elements");
+    const bool tracked = a_in != nullptr;
+    CMOOP_REQUIRE(tracked || record || avg_ms, "fake_quant_act: batch mode needs record_inout");
+    if (n == 0) { if (avg_ms) *avg_ms = 0.0; return; }
+    CMOOP_REQUIRE(x != nullptr && reinterpret_cast<uintptr_t>(x) % 4 == 0, "fake_quant_act: x_dev is NULL or not aligned to 4 bytes");
+    ActRange rec{0.f, 0.f, 0, 0};
+    if (record) std::memcpy(&rec, record, sizeof(rec));
+    CMOOP_REQUIRE(rec.count >= 0, "fake_quant_act: the record's count must not be negative");
+    if (tracked) rec.r = *a_in;
+    const EmaPair m = actquant_rates(c.momentum);
+    hipStream_t s = lib_stream();
+    PoolScope pool(s);
+    ActRange* rec_dev = pool.get<ActRange>(sizeof(ActRange));
+    uint32_t* partials = pool.get<uint32_t>((size_t)ACT_QUANT_MAX_BLOCKS * 4);
+    CMOOP_HIP(hipMemcpyAsync(rec_dev, &rec, sizeof(rec), hipMemcpyHostToDevice, s));
+    CMOOP_HIP(hipStreamSynchronize(s));
+    auto once = [&] { launch_fake_quant_act(x, n, c.bits, tracked, partials, rec_dev, m.mf, m.omf, s); };
+    if (avg_ms) *avg_ms = time_launches(s, iters, once);
+    else once();
+    if (record && !tracked) CMOOP_HIP(hipMemcpyAsync(record, rec_dev, sizeof(rec), hipMemcpyDeviceToHost, s));
+    CMOOP_HIP(hipStreamSynchronize(s));
+}
+
+int cmoop_fake_quant_act(float* x_dev, int64_t n, int32_t bits, const float* a_in, cmoop_act_range* record_inout, float momentum) {
+    return guard([&] { fake_quant_act_abi(x_dev, n, bits, a_in, record_inout, momentum, 0, nullptr); });
+}
+
+int cmoop_fake_quant_act_time(float* x_dev, int64_t n, int32_t bits, const float* a_in, float momentum, int32_t iters, double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "fake_quant_act_time: iters >= 1 and avg_ms");
+        fake_quant_act_abi(x_dev, n, bits, a_in, nullptr, momentum, iters, avg_ms);
     });
 }
 
@@ -1514,6 +1610,31 @@ int cmoop_net_finalize_ema(cmoop_net* h) {
 int cmoop_net_set_opoint(cmoop_net* h, const cmoop_opoint* op) { return net_set_option(h, "set_opoint", op, to_opoint, &Net::set_opoint); }
 int cmoop_net_set_quant(cmoop_net* h, const cmoop_quant* q) { return net_set_option(h, "set_quant", q, to_quant, &Net::set_quant); }
 int cmoop_net_set_prune(cmoop_net* h, const cmoop_prune* p) { return net_set_option(h, "set_prune", p, to_prune, &Net::set_prune); }
+int cmoop_net_set_actquant(cmoop_net* h, const cmoop_actquant* aq) {
+    return net_set_option(h, "set_actquant", aq, to_actquant, &Net::set_actquant);
+}
+int cmoop_net_get_act_ranges(cmoop_net* h, cmoop_act_range* host, int32_t cap, int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "get_act_ranges: NULL net");
+        if (count) *count = h->net->act_sites();
+        if (!host && count) return;   // the number of sites alone
+        CMOOP_REQUIRE(host && cap >= h->net->act_sites(), "get_act_ranges: the buffer is too small");
+        h->net->get_act_ranges(reinterpret_cast<ActRange*>(host));
+    });
+}
+int cmoop_net_set_act_ranges(cmoop_net* h, const cmoop_act_range* host, int32_t count) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "set_act_ranges: NULL net");
+        CMOOP_REQUIRE(host && count == h->net->act_sites(), "set_act_ranges: count must be the number of sites");
+        h->net->set_act_ranges(reinterpret_cast<const ActRange*>(host));
+    });
+}
+int cmoop_net_get_act(cmoop_net* h, int32_t i, int32_t B, int32_t dims[6], float* data_host, float* grad_host) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "get_act: NULL net");
+        h->net->get_act(i, B, dims, data_host, grad_host);
+    });
+}
 int cmoop_net_get_pruned(cmoop_net* h, float* weff_params_host, uint32_t* zeros_host) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "get_pruned: NULL net");

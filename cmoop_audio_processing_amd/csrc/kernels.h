@@ -537,6 +537,39 @@ void launch_quantize_weights(const float* w, float* wq, int8_t* codes, float* sc
                              int bits, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Activation fake quantisation (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_actquant): symmetric, signed,
+// PER-TENSOR fake quantisation of an fp32 tensor in place, the weight quantiser's element arithmetic (quant_math.h) on one channel
+// that spans the whole tensor.  Batch mode (train steps): the range is this tensor's own absmax, TWO launches (act_absmax_kernel
+// leaves one partial per workgroup, act_quant_apply_kernel folds them, quantises and advances the site's record).  Tracked mode
+// (inference): the range is the record's r, ONE launch.  No atomics, nothing to zero: every partial is written before it is read.
+// ---------------------------------------------------------------------------
+struct ActQuantCfg {
+    int bits = 0;                    // 0 = off, else 2 .. 8
+    float momentum = 0.99f;          // of the tracked range, in [0, 1)
+    int reserved[2] = {0, 0};
+};
+// host-only: throws with a message naming the offending field
+void actquant_check(const ActQuantCfg& c);
+inline bool actquant_enabled(const ActQuantCfg& c) { return c.bits != 0; }
+// the record of one site: the absmax of the last train step's tensor, the tracked range, the train steps seen (saturating)
+struct ActRange { float m_b, r; int32_t count, reserved; };
+// (mu, omu) = ((float)momentum, (float)(1.0 - (double)momentum)), each rounded once (as ema_rates forms an EmaPair)
+EmaPair actquant_rates(float momentum);
+constexpr int64_t ACT_QUANT_MAX_ELEMS = ((int64_t)1 << 31) - 1;   // the kernels' index math is 32-bit
+constexpr int ACT_QUANT_MAX_BLOCKS = 1024;                        // workgroup cap: the partials one workgroup folds with one load per lane
+constexpr int ACT_QUANT_BLOCK_ELEMS = 1024;                       // elements a workgroup takes per grid stride: 256 lanes x 16 bytes
+// workgroups of both kernels (and partials of the first): a function of n alone
+inline int act_quant_blocks(int64_t n) {
+    const int64_t b = (n + ACT_QUANT_BLOCK_ELEMS - 1) / ACT_QUANT_BLOCK_ELEMS;
+    return (int)(b < 1 ? 1 : (b > ACT_QUANT_MAX_BLOCKS ? ACT_QUANT_MAX_BLOCKS : b));
+}
+// x [n] quantised in place at `bits`.  tracked: a = rec->r, rec is only read, partials unused (may be null).  Else batch mode:
+// a = absmax(x) through partials [act_quant_blocks(n)], and rec becomes {a, count == 0 ? a : (mu r) + (omu a), count + 1}.
+// n == 0: nothing is launched
+void launch_fake_quant_act(float* x, int64_t n, int bits, bool tracked, uint32_t* partials, ActRange* rec, float mu, float omu,
+                           hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Magnitude pruning in training (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_prune): per kernel tensor
 // the k = floor(s len) elements of smallest magnitude become +0.0f, the threshold found by an exact radix select on the
 // integer keys bits(w) & 0x7FFFFFFF; FOUR launches for a whole arena (prune.hip).

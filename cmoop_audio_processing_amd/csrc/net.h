@@ -155,6 +155,7 @@ struct Act {
     int H = 0, W = 0, C = 0;
     bool own_grad = false;
     bool virt = false;         // never materialised (BatchNorm output consumed by a fused max-pool)
+    int site = -1;             // activation-quantisation site number (plan_net), -1: not a site
     size_t per_sample() const { return (size_t)H * W * C; }
 };
 
@@ -207,6 +208,7 @@ struct NetPlan {
     std::vector<Act> acts;
     std::vector<Op> ops;
     int logits = -1;
+    int n_sites = 0;           // activation-quantisation sites: the acts with site >= 0, numbered in act order
     int64_t n_params = 0;
     // THE walk over the kernel tensors, in arena order (under param_kinds, the quant / prune tables, the seeded init, the flip table)
     std::vector<KernelTensor> kernel_tensors() const;
@@ -228,7 +230,7 @@ QuantTable quant_table(const NetPlan& plan);
 PruneTable prune_table(const NetPlan& plan, bool skip_small = true);
 
 // The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
-// set_distill / set_optim / set_ema / set_opoint / set_quant / set_prune say what each does).  The pointees stay the caller's for the length of the call
+// set_distill / set_optim / set_ema / set_opoint / set_quant / set_prune / set_actquant say what each does).  The pointees stay the caller's for the length of the call
 struct TrainOptions {
     const AugmentCfg* aug = nullptr;
     const LossCfg* loss = nullptr;
@@ -238,6 +240,7 @@ struct TrainOptions {
     const OpointCfg* opoint = nullptr;
     const QuantCfg* quant = nullptr;
     const PruneCfg* prune = nullptr;
+    const ActQuantCfg* actq = nullptr;
 };
 
 class Net : public GemmHook {
@@ -254,7 +257,7 @@ class Net : public GemmHook {
     void set_params(const float* host);
     void get_grads(float* host);
     void snapshot_params();   // device copy (restore_best_weights) of the arena inference currently reads (use_average)
-    void restore_snapshot();  // into the parameter arena
+    void restore_snapshot();  // into the parameter arena; both carry the activation-quantisation site records with the weights
     // full training state: parameters (BatchNorm moving statistics included), Adam m / v, optimizer.iterations and the
     // global step that keys the dropout masks -- what a checker needs to re-synchronise with this net at an epoch boundary
     void get_state(float* params, float* m, float* v, long long* iterations, long long* steps);
@@ -344,7 +347,25 @@ class Net : public GemmHook {
     // sum of zeros / sum of len over the tensors with k > 0 at the final sparsity (0 when there is none)
     double prune_achieved(const uint32_t* zeros);
     int64_t prune_size_bytes();          // kernels.h, at the final sparsity and the quantiser's bits; throws while the option is off
-    // the enabled ones of o through the eight setters above, in that order: augment, loss, distill, optim, ema, opoint, quant, prune.  THE
+    // Activation fake quantisation (kernels.h) of every following train step and inference call; null or a disabled config: off,
+    // and every launch and bit is that of a net that never had one (the site records, once allocated, are kept).  Enabled: the
+    // domain is checked; on first use the per-site records (zeroed: count 0) and the partials workspace are allocated.  forward
+    // then quantises every site (plan_net) in place right after the op that writes it: train steps in batch mode, which also
+    // advances the site's record, inference in tracked mode -- refused, before anything is launched, while no train step has run
+    // with the option on and no ranges were loaded.  backward is unchanged.  Independent of set_quant / set_prune.  Under
+    // use_average the ranges stay those of the raw-weight trajectory.  The step is no longer captured as a graph
+    void set_actquant(const ActQuantCfg* actq);
+    bool actquant_on() const { return actq_on_; }
+    const ActQuantCfg& actquant() const { return actq_cfg_; }
+    int act_sites() const { return plan_.n_sites; }
+    // the site records {m_b, r, count}, [act_sites()]; throws while no records exist (the option was never on).  set: count >= 0
+    // and r not negative; a record with count > 0 makes inference possible
+    void get_act_ranges(ActRange* host);
+    void set_act_ranges(const ActRange* host);
+    // debug read-out: dims = {H, W, C, materialised, has a gradient, number of acts} of act i; data / grad (either may be null)
+    // receive the first B rows as the last step or pass left them (grad: B <= cfg.batch)
+    void get_act(int i, int B, int32_t dims[6], float* data_host, float* grad_host);
+    // the enabled ones of o through the nine setters above, in that order: augment, loss, distill, optim, ema, opoint, quant, prune, actq.  THE
     // place of "a disabled config is no config": null or disabled is not applied at all, and the net stays one that never had it
     void set_options(const TrainOptions& o);
     // the last step's {sum of squares, norm, scale, launch path (0 fused, 1 finish + update)}; path 0 computes no norm: 0, 0, 1
@@ -415,6 +436,8 @@ class Net : public GemmHook {
     void ensure_target_buffers();                       // t / w / primary, allocated by the first enabled set_loss or set_distill
     void ensure_quant_table();                          // qtab_ from the plan, once (host only)
     void ensure_prune_table();                          // ptab_ from the plan and the config's skip_small (host only)
+    void require_act_ranges() const;                    // first line of every public inference entry: with set_actquant on, tracked ranges
+    void quantise_site(int act, int B, bool train);     // forward's launch(es) for a site the op just wrote
     // THE weight stage, from params_ (the average under use_average).  Prune on: its kernels pruned at `sparsity` into wp (zeros:
     // per-row counts, or null).  Quant on and wq given: the kernels of wp, else of params_, quantised into wq (codes / scales or
     // null).  Returns the arena of the last stage that ran, params_ when none did: where forward / backward read kernel tensors
@@ -455,6 +478,11 @@ class Net : public GemmHook {
     int ptab_skip_small_ = -1;          // the skip_small ptab_ was built with; -1: not built
     PruneRow* ptab_dev_ = nullptr;
     PruneWorkspace prune_ws_;
+    ActQuantCfg actq_cfg_;              // set_actquant; the default is off
+    bool actq_on_ = false;              // forward quantises the sites
+    ActRange *act_rec_ = nullptr, *act_rec_snap_ = nullptr;   // [n_sites] records and their snapshot_params copy, first enabled set_actquant
+    uint32_t* act_partials_ = nullptr;  // [ACT_QUANT_MAX_BLOCKS] absmax partials of the site being quantised
+    bool act_ranges_ready_ = false, act_ranges_ready_snap_ = false;   // host mirror of "every record has count > 0", and of the snapshot's
     std::vector<OpointClass> last_op_classes_;   // store_opoint: empty when the last fit ran without the read-out
     double last_op_summary_[4] = {0, 0, 0, 0};
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;

@@ -367,6 +367,24 @@ NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F) {
     x = add_conv(OP_DENSE, x, cfg.classes, 1, 1, 0, 1, dr ? keep_scale : 1.f, 0);
     ops.back().gemm_mode = GEMM_FP32;   // the classifier layer stays fp32 in every mode (as does the C_in = 1 first conv)
     plan.logits = x;
+    // Activation-quantisation sites (Net::set_actquant): the materialised operand tensors of the MAC layers and of the global
+    // pool, but for the input features (act 0, the resident tensor) and the logits; numbered in act order.  Every consumer of a
+    // site reads the quantised tensor, and none should see the unquantised one: in all four variants a site (a block input, a
+    // BatchNorm / pool / add+ReLU / depthwise / conv / dense output that feeds a conv, a dense layer or the global pool) is read
+    // by OP_CONV / OP_DWCONV / OP_DENSE / OP_GAP only -- the tensors BatchNorm, max-pool and add+ReLU read (conv outputs, the
+    // skip projection, the block's pooled branch) feed nothing else, so they are no sites
+    for (int i = 1; i < (int)acts.size(); ++i) {
+        if (i == plan.logits || acts[i].virt) continue;
+        bool mac = false;
+        for (const Op& op : ops)
+            mac = mac || (op.in == i && (op.kind == OP_CONV || op.kind == OP_DWCONV || op.kind == OP_DENSE || op.kind == OP_GAP));
+        if (mac) acts[i].site = plan.n_sites++;
+    }
+    for (const Op& op : ops) {   // the comment above, checked: a site has no other reader
+        const bool mac = op.kind == OP_CONV || op.kind == OP_DWCONV || op.kind == OP_DENSE || op.kind == OP_GAP;
+        CMOOP_REQUIRE(mac || ((op.in < 0 || acts[op.in].site < 0) && (op.in2 < 0 || acts[op.in2].site < 0)),
+                      "plan: an activation-quantisation site is read by an op that is no MAC layer");
+    }
     plan.n_params = off;
     CMOOP_REQUIRE(plan.n_params == param_count(gene, cfg.variant, cfg.classes), "plan / closed-form parameter count mismatch");
     return plan;
@@ -593,9 +611,17 @@ void Net::get_grads(float* host) {
 void Net::snapshot_params() {
     if (!snap_) snap_ = dalloc(n_params_);
     CMOOP_HIP(hipMemcpyAsync(snap_, params_, n_params_ * 4, hipMemcpyDeviceToDevice, stream_));
+    if (act_rec_) {   // the ranges this model was validated with travel with its weights
+        CMOOP_HIP(hipMemcpyAsync(act_rec_snap_, act_rec_, (size_t)plan_.n_sites * sizeof(ActRange), hipMemcpyDeviceToDevice, stream_));
+        act_ranges_ready_snap_ = act_ranges_ready_;
+    }
 }
 void Net::restore_snapshot() {
     if (snap_) CMOOP_HIP(hipMemcpyAsync(weights_, snap_, n_params_ * 4, hipMemcpyDeviceToDevice, stream_));
+    if (snap_ && act_rec_) {   // (a snapshot older than the records holds count 0 everywhere: the ranges start over)
+        CMOOP_HIP(hipMemcpyAsync(act_rec_, act_rec_snap_, (size_t)plan_.n_sites * sizeof(ActRange), hipMemcpyDeviceToDevice, stream_));
+        act_ranges_ready_ = act_ranges_ready_snap_;
+    }
 }
 
 const GemmTiming* Net::begin(int cls, double flops) {
@@ -872,7 +898,24 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
             break;
         }
         }
+        if (actq_on_) {   // the act this op's launches just wrote: a fused BatchNorm + pool writes the pool's output
+            const int written = (op.kind == OP_BN && op.fuse_pool) ? ops_[oi + 1].out : (op.kind == OP_POOL && op.fused_into_bn) ? -1 : op.out;
+            if (written >= 0 && acts_[written].site >= 0) quantise_site(written, B, train);
+        }
     }
+}
+
+void Net::quantise_site(int act, int B, bool train) {
+    const Act& a = acts_[act];
+    const EmaPair m = actquant_rates(actq_cfg_.momentum);
+    // train: batch mode over the B rows of this step, and the site's record advances; inference: the tracked range
+    launch_fake_quant_act(a.data, (int64_t)B * (int64_t)a.per_sample(), actq_cfg_.bits, !train, act_partials_, act_rec_ + a.site, m.mf, m.omf,
+                          stream_);
+}
+
+void Net::require_act_ranges() const {
+    CMOOP_REQUIRE(!actq_on_ || act_ranges_ready_,
+                  "actquant: inference needs tracked ranges -- run a train step with the option on or load them (set_act_ranges) first");
 }
 
 void Net::backward(const float* X, const BatchRows& rows, int B) {
@@ -1009,6 +1052,7 @@ template <class Loss> void Net::step_body(const float* X, const BatchRows& rows,
         batch_in_ = mix_on_ ? mix_buf_ : (aug_on_ ? aug_buf_ : nullptr);
     }
     forward(X, rows, B, true);
+    if (actq_on_) act_ranges_ready_ = true;   // every site's record has seen a step
     loss();
     backward(X, rows, B);
     optimiser_step(B, rows.st);
@@ -1144,7 +1188,7 @@ void Net::begin_fit(int64_t total_steps) {
     // steps/s replayed vs 2 625 launched eagerly (its stream is kept busy either way: ~50 kernels of ~8 us per step,
     // the host launches faster than that), and the pop-40 bench is 1.5 % slower replayed (2 089 vs 2 121 evals/h).
     static const bool use_graph = [] { const char* v = std::getenv("CMOOP_GRAPH"); return v && v[0] == '1'; }();
-    if (!use_graph || optim_finish_ || ema_on_ || quant_on_ || prune_on_) graph_ok_ = false;
+    if (!use_graph || optim_finish_ || ema_on_ || quant_on_ || prune_on_ || actq_on_) graph_ok_ = false;
 }
 
 // the per-iteration rates of the device-state steps, from the one host function the explicit-argument steps use
@@ -1198,6 +1242,7 @@ void Net::set_options(const TrainOptions& o) {
     if (o.opoint && opoint_enabled(*o.opoint)) set_opoint(o.opoint);
     if (o.quant && quant_enabled(*o.quant)) set_quant(o.quant);
     if (o.prune && prune_enabled(*o.prune)) set_prune(o.prune);
+    if (o.actq && actquant_enabled(*o.actq)) set_actquant(o.actq);
 }
 
 void Net::set_opoint(const OpointCfg* op) {
@@ -1386,6 +1431,61 @@ void Net::get_pruned(float* weff_host, uint32_t* zeros_host) {
     stage_kernels(prune_cfg_.sparsity, d_w, d_zeros, nullptr, nullptr, nullptr);   // pruned, not quantised
     if (weff_host) CMOOP_HIP(hipMemcpyAsync(weff_host, d_w, n * 4, hipMemcpyDeviceToHost, stream_));
     if (zeros_host) CMOOP_HIP(hipMemcpyAsync(zeros_host, d_zeros, rows * 4, hipMemcpyDeviceToHost, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+}
+
+void Net::set_actquant(const ActQuantCfg* actq) {
+    if (actq) actquant_check(*actq);
+    const bool on = actq != nullptr && actquant_enabled(*actq);
+    if (on && !act_rec_) {   // first use: every site starts unseen (count 0); the partials need no initial value
+        const size_t words = (size_t)std::max(plan_.n_sites, 1) * sizeof(ActRange) / sizeof(float);
+        act_rec_ = reinterpret_cast<ActRange*>(dalloc(words));
+        act_rec_snap_ = reinterpret_cast<ActRange*>(dalloc(words));
+        act_partials_ = reinterpret_cast<uint32_t*>(dalloc(ACT_QUANT_MAX_BLOCKS));
+        CMOOP_HIP(hipMemsetAsync(act_rec_, 0, words * sizeof(float), stream_));
+        CMOOP_HIP(hipMemsetAsync(act_rec_snap_, 0, words * sizeof(float), stream_));   // a snapshot of "no step seen" until the first real one
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running
+    actq_cfg_ = on ? *actq : ActQuantCfg();
+    actq_on_ = on;
+    option_changed(on);
+}
+
+void Net::get_act_ranges(ActRange* host) {
+    CMOOP_REQUIRE(act_rec_ && host, "get_act_ranges: no site records (set_actquant with bits in [2, 8] first), or NULL output");
+    CMOOP_HIP(hipMemcpyAsync(host, act_rec_, (size_t)plan_.n_sites * sizeof(ActRange), hipMemcpyDeviceToHost, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+}
+
+void Net::set_act_ranges(const ActRange* host) {
+    CMOOP_REQUIRE(act_rec_ && host, "set_act_ranges: no site records (set_actquant with bits in [2, 8] first), or NULL input");
+    bool ready = plan_.n_sites > 0 ? true : act_ranges_ready_;
+    for (int i = 0; i < plan_.n_sites; ++i) {
+        CMOOP_REQUIRE(host[i].count >= 0, "set_act_ranges: count must not be negative");
+        CMOOP_REQUIRE(!(host[i].r < 0.f) && !(host[i].m_b < 0.f), "set_act_ranges: r and m_b must not be negative");
+        ready = ready && host[i].count > 0;
+    }
+    CMOOP_HIP(hipMemcpyAsync(act_rec_, host, (size_t)plan_.n_sites * sizeof(ActRange), hipMemcpyHostToDevice, stream_));
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // host is the caller's
+    act_ranges_ready_ = ready;
+}
+
+void Net::get_act(int i, int B, int32_t dims[6], float* data_host, float* grad_host) {
+    CMOOP_REQUIRE(i >= 0 && i < (int)acts_.size(), "get_act: act index out of range");
+    const Act& a = acts_[i];
+    if (dims) {
+        dims[0] = a.H; dims[1] = a.W; dims[2] = a.C; dims[3] = a.data != nullptr; dims[4] = a.grad != nullptr;
+        dims[5] = (int32_t)acts_.size();
+    }
+    if (!data_host && !grad_host) return;
+    CMOOP_REQUIRE(a.data != nullptr, "get_act: this act is never materialised (the input features, or a BatchNorm output fused into its pool)");
+    CMOOP_REQUIRE(B >= 1 && B <= Bmax_ && (!grad_host || B <= cfg_.batch), "get_act: B outside the rows the net holds");
+    const size_t bytes = (size_t)B * a.per_sample() * 4;
+    if (data_host) CMOOP_HIP(hipMemcpyAsync(data_host, a.data, bytes, hipMemcpyDeviceToHost, stream_));
+    if (grad_host) {
+        CMOOP_REQUIRE(a.grad != nullptr, "get_act: this act has no gradient buffer");
+        CMOOP_HIP(hipMemcpyAsync(grad_host, a.grad, bytes, hipMemcpyDeviceToHost, stream_));
+    }
     CMOOP_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -1589,6 +1689,7 @@ static auto resident_rows(const float* X) {
 }
 
 void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum, long long* correct, int32_t* preds) {
+    require_act_ranges();   // before the accumulator's memset: a refused call enqueues nothing
     CMOOP_HIP(hipMemsetAsync(acc_eval_, 0, 16, stream_));
     inference_pass(n, resident_rows(X), [&](int64_t s, int B) {
         launch_softmax_ce(acts_[logits_].data, y, BatchRows{nullptr, s}, B, cfg_.classes, nullptr, acc_eval_, preds ? preds + s : nullptr, stream_);
@@ -1602,6 +1703,7 @@ void Net::evaluate(const float* X, const int32_t* y, int64_t n, double* loss_sum
 
 void Net::predict(const float* X, int64_t n, float* probs) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && probs)), "predict: NULL buffer");
+    require_act_ranges();
     inference_pass(n, resident_rows(X),
                    [&](int64_t s, int B) { launch_softmax_probs(acts_[logits_].data, probs + s * cfg_.classes, B, cfg_.classes, stream_); });
     CMOOP_HIP(hipStreamSynchronize(stream_));
@@ -1609,6 +1711,7 @@ void Net::predict(const float* X, int64_t n, float* probs) {
 
 void Net::predict_logits(const float* X, int64_t n, float* logits) {
     CMOOP_REQUIRE(n >= 0 && (n == 0 || (X && logits)), "predict_logits: NULL buffer");
+    require_act_ranges();
     inference_pass(n, resident_rows(X), [&](int64_t s, int B) {
         CMOOP_HIP(hipMemcpyAsync(logits + s * cfg_.classes, acts_[logits_].data, (size_t)B * cfg_.classes * 4, hipMemcpyDeviceToDevice,
                                  stream_));
@@ -1627,6 +1730,7 @@ void Net::predict_stream(const float* feat, int64_t n_frames, int hop, bool db_s
     const int64_t n = stream_windows(n_frames, T_, hop);
     CMOOP_REQUIRE(feat && probs, "predict_stream: NULL buffer");
     CMOOP_REQUIRE((mean == nullptr) == (scale == nullptr), "predict_stream: mean and scale come together (both or neither)");
+    require_act_ranges();
     const int B0 = (int)std::min<int64_t>(cfg_.eval_batch, n);
     PoolScope pool(stream_);   // the chunk and the scaler go back once the stream has drained
     float* chunk = pool.get<float>((size_t)B0 * T_ * F_ * 4);

@@ -8,6 +8,7 @@
 // the codes.  Strided tensor (depthwise [kh][kw][C]): one lane per channel walks the kh kw taps, consecutive lanes on
 // consecutive addresses.
 #include "kernels.h"
+#include "quant_math.h"
 
 #include <algorithm>
 
@@ -16,27 +17,7 @@ namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t ABS_MASK = 0x7FFFFFFFu, CANONICAL_NAN = 0x7FC00000u;
-
-// s = a / qmax, one correctly rounded fp32 division; a NaN is stored as the canonical quiet NaN
-__device__ __forceinline__ float quant_scale(uint32_t abits, float qmaxf) {
-    const float s = __uint_as_float(abits) / qmaxf;
-    return s == s ? s : __uint_as_float(CANONICAL_NAN);
-}
-
-// the code and the dequantised value of w under scale s; live: s > 0
-__device__ __forceinline__ void quant_element(float w, float s, bool live, float qmaxf, int& q, float& wq) {
-#pragma clang fp contract(off)
-    float r = 0.f;
-    if (live) {
-        r = rintf(w / s);                          // one fp32 division, then round half to even
-        if (!(r == r)) r = 0.f;                    // inf / inf
-        r = fminf(fmaxf(r, -qmaxf), qmaxf);
-    }
-    q = (int)r;
-    const float x = (float)q * s;                  // one fp32 product; 0 * s = +0 for every s > 0
-    wq = x == x ? x : __uint_as_float(CANONICAL_NAN);
-}
+constexpr uint32_t ABS_MASK = QUANT_ABS_MASK;
 
 __device__ __forceinline__ uint32_t pack_codes(int q0, int q1, int q2, int q3) {
     return ((uint32_t)q0 & 0xFFu) | (((uint32_t)q1 & 0xFFu) << 8) | (((uint32_t)q2 & 0xFFu) << 16) | (((uint32_t)q3 & 0xFFu) << 24);
@@ -118,7 +99,133 @@ __global__ __launch_bounds__(256) void quantize_weights_kernel(const float* __re
     }
 }
 
+// ---- activation fake quantisation: one tensor, one range ---------------------------------------------------------------
+// Both kernels split x [n] the same way: `head` elements up to the first 16-byte boundary (0 .. 3, all of x when n is smaller),
+// nv whole 16-byte groups, then the rest (0 .. 3).  Groups go through 16-byte accesses in a grid stride; the at most 6 edge
+// elements through 4-byte ones, one per lane of the first lanes of the grid.
+struct ActSpan { int head, nv, tail0; };
+__device__ __forceinline__ ActSpan act_span(const float* x, int n) {
+    ActSpan sp;
+    sp.head = min(n, (int)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(x) & 15u)) & 15u) >> 2);
+    sp.nv = (n - sp.head) >> 2;
+    sp.tail0 = sp.head + 4 * sp.nv;
+    return sp;
+}
+
+// the maximum of m over the workgroup's 256 lanes, the same value in every lane (red: 4 words of LDS)
+__device__ __forceinline__ uint32_t block_max_256(uint32_t m, uint32_t* red) {
+    for (int off = 32; off >= 1; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    if (((int)threadIdx.x & 63) == 0) red[(int)threadIdx.x >> 6] = m;
+    __syncthreads();
+    return max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
+__global__ __launch_bounds__(256) void act_absmax_kernel(const float* __restrict__ x, int n, uint32_t* __restrict__ partials) {
+    __shared__ uint32_t red[4];
+    const ActSpan sp = act_span(x, n);
+    const int gid = (int)(blockIdx.x * 256u + threadIdx.x), stride = (int)(gridDim.x * 256u);
+    const u32x4* xv = reinterpret_cast<const u32x4*>(x + sp.head);
+    uint32_t m = 0;
+    for (int i = gid; i < sp.nv; i += stride) {
+        const u32x4 v = xv[i];
+        m = max(max(m, v.x & ABS_MASK), max(v.y & ABS_MASK, max(v.z & ABS_MASK, v.w & ABS_MASK)));
+    }
+    if (gid < sp.head) m = max(m, __float_as_uint(x[gid]) & ABS_MASK);
+    if (gid < n - sp.tail0) m = max(m, __float_as_uint(x[sp.tail0 + gid]) & ABS_MASK);
+    m = block_max_256(m, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = m;
+}
+
+// the record after a train step whose tensor had the absmax bits `abits`
+__device__ __forceinline__ void act_range_advance(ActRange* rec, uint32_t abits, float mu, float omu) {
+#pragma clang fp contract(off)
+    const float nan = __uint_as_float(QUANT_CANONICAL_NAN);
+    float mb = __uint_as_float(abits);
+    if (!(mb == mb)) mb = nan;
+    const int count = rec->count;
+    float r = mb;
+    if (count != 0) {
+        const float keep = mu * rec->r;            // three fp32 operations, each rounded on its own
+        const float add = omu * mb;
+        r = keep + add;
+        if (!(r == r)) r = nan;
+    }
+    rec->m_b = mb;
+    rec->r = r;
+    rec->count = count == 0x7FFFFFFF ? count : count + 1;
+    rec->reserved = 0;
+}
+
+template <bool TRACKED>
+__global__ __launch_bounds__(256) void act_quant_apply_kernel(float* __restrict__ x, int n, const uint32_t* __restrict__ partials,
+                                                              int nparts, ActRange* __restrict__ rec, float qmaxf, float mu, float omu) {
+    __shared__ uint32_t red[4];
+    uint32_t abits;
+    if (TRACKED) {
+        abits = __float_as_uint(rec->r);           // read only: no workgroup writes the record in this mode
+    } else {
+        uint32_t m = 0;                            // every workgroup folds all the partials: at most 4 per lane
+        for (int i = (int)threadIdx.x; i < nparts; i += 256) m = max(m, partials[i]);
+        abits = block_max_256(m, red);
+        // no other lane of the grid reads the record in this mode
+        if (blockIdx.x == 0 && threadIdx.x == 0) act_range_advance(rec, abits, mu, omu);
+    }
+    const float s = quant_scale(abits, qmaxf);
+    const bool live = s > 0.f;
+    const ActSpan sp = act_span(x, n);
+    const int gid = (int)(blockIdx.x * 256u + threadIdx.x), stride = (int)(gridDim.x * 256u);
+    f32x4* xv = reinterpret_cast<f32x4*>(x + sp.head);
+    for (int i = gid; i < sp.nv; i += stride) {
+        const f32x4 v = xv[i];
+        int q;
+        float y0, y1, y2, y3;
+        quant_element(v.x, s, live, qmaxf, q, y0);
+        quant_element(v.y, s, live, qmaxf, q, y1);
+        quant_element(v.z, s, live, qmaxf, q, y2);
+        quant_element(v.w, s, live, qmaxf, q, y3);
+        const f32x4 y = {y0, y1, y2, y3};
+        xv[i] = y;
+    }
+    if (gid < sp.head) {
+        int q; float y;
+        quant_element(x[gid], s, live, qmaxf, q, y);
+        x[gid] = y;
+    }
+    if (gid < n - sp.tail0) {
+        int q; float y;
+        quant_element(x[sp.tail0 + gid], s, live, qmaxf, q, y);
+        x[sp.tail0 + gid] = y;
+    }
+}
+
 }  // namespace
+
+void actquant_check(const ActQuantCfg& c) {
+    CMOOP_REQUIRE(c.bits == 0 || (c.bits >= 2 && c.bits <= 8), "actquant: bits must be 0 (off) or in [2, 8]");
+    CMOOP_REQUIRE(c.momentum >= 0.f && c.momentum < 1.f, "actquant: momentum must be in [0, 1)");
+    CMOOP_REQUIRE(c.reserved[0] == 0 && c.reserved[1] == 0, "actquant: reserved must be 0");
+}
+
+EmaPair actquant_rates(float momentum) { return EmaPair{momentum, (float)(1.0 - (double)momentum)}; }
+
+void launch_fake_quant_act(float* x, int64_t n, int bits, bool tracked, uint32_t* partials, ActRange* rec, float mu, float omu,
+                           hipStream_t s) {
+    CMOOP_REQUIRE(bits >= 2 && bits <= 8, "fake_quant_act: bits must be in [2, 8]");
+    CMOOP_REQUIRE(n >= 0 && n <= ACT_QUANT_MAX_ELEMS, "fake_quant_act: n must stay below 2^31 elements (ACT_QUANT_MAX_ELEMS: 32-bit index math)");
+    if (n == 0) return;
+    CMOOP_REQUIRE(x && rec && (tracked || partials), "fake_quant_act: NULL buffer");
+    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(x) % 4 == 0, "fake_quant_act: x must be aligned to 4 bytes");
+    const int blocks = act_quant_blocks(n);
+    const float qmaxf = (float)quant_qmax(bits);
+    if (tracked) {
+        hipLaunchKernelGGL(act_quant_apply_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, (int)n, nullptr, 0, rec, qmaxf, mu, omu);
+    } else {
+        hipLaunchKernelGGL(act_absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, (int)n, partials);
+        hipLaunchKernelGGL(act_quant_apply_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, x, (int)n, partials, blocks, rec, qmaxf, mu,
+                           omu);
+    }
+    CMOOP_HIP(hipGetLastError());
+}
 
 void quant_check(const QuantCfg& c) {
     CMOOP_REQUIRE(c.bits == 0 || (c.bits >= 2 && c.bits <= 8), "quant: bits must be 0 (off) or in [2, 8]");

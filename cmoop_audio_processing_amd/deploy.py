@@ -64,6 +64,13 @@ class TrainedModel:
     # top when the model carries codes as well), so every fp32 path scores the sparse model.  Both or neither
     prune_sparsity: Optional[float] = None
     prune_k: Optional[np.ndarray] = None
+    # a model trained under EvalConfig.act_quant (quant.ActQuantConfig): the bit width and the tracked range records of the
+    # sites, a structured array [sites] of (m_b, r, count, reserved) in site order (NetSession.get_act_ranges); ``session()``
+    # turns the option on with them, so it scores exactly the model the fit scored.  Both or neither.  ``act_momentum``: the
+    # momentum the fit tracked the ranges with (0.99 when absent), so that training on from ``session()`` continues as the fit did
+    act_bits: Optional[int] = None
+    act_ranges: Optional[np.ndarray] = None
+    act_momentum: Optional[float] = None
 
     def __post_init__(self):
         self.gene = tuple(int(v) for v in self.gene)
@@ -119,6 +126,19 @@ class TrainedModel:
                 zeros = int(((self.params[off:off + n].view(np.uint32) & np.uint32(0x7FFFFFFF)) == 0).sum())
                 if not 0 <= k <= n or zeros < k:
                     raise ValueError(f"{name} holds {zeros} zeros, its prune_k asks for at least {int(k)}")
+
+        if (self.act_bits is None) != (self.act_ranges is None):
+            raise ValueError("act_bits and act_ranges come together (both or neither)")
+        if self.act_ranges is not None:
+            from . import quant as Q
+            self.act_bits = int(self.act_bits)
+            self.act_momentum = float(np.float32(0.99 if self.act_momentum is None else self.act_momentum))
+            Q.ActQuantConfig(bits=self.act_bits, momentum=self.act_momentum).check()
+            Q.qmax_of(self.act_bits)
+            self.act_ranges = np.ascontiguousarray(self.act_ranges, Q.ACT_RANGE_DTYPE).reshape(-1)
+            sites = Q.act_sites(self.gene, self.variant, int(self.classes), int(self.T), int(self.F))
+            if self.act_ranges.size != len(sites):
+                raise ValueError(f"act_ranges must hold one record per site ({len(sites)})")
 
     def _kernel_spans(self):
         """[(name, offset in ``params``, elements)] of the kernel tensors in arena order (the rows of ``prune.prune_table``)."""
@@ -178,7 +198,8 @@ class TrainedModel:
         the front end carries a ``PcenConfig``.  A model without a front end, or with a log or dB one, writes the keys
         it always wrote.  ``thresholds`` (float32 [classes]) only when the model carries them; ``quant_bits`` (int64 [1]),
         ``quant_codes`` (int8) and ``quant_scales`` (float32) only when it carries quantised weights; ``prune_sparsity`` (float64
-        [1]) and ``prune_k`` (int64) only when it carries pruned ones."""
+        [1]) and ``prune_k`` (int64) only when it carries pruned ones; ``act_bits`` (int64 [1]), ``act_ranges`` (float32 [sites, 2]:
+        m_b, r), ``act_counts`` (int64 [sites]) and ``act_momentum`` (float64 [1]) only when it carries activation ranges."""
         d = {"gene": np.asarray(self.gene, np.int32),
              "meta": np.asarray([G.VARIANT_NAMES[self.variant], self.classes, self.T, self.F, self.seed], np.int64),
              "params": self.params,
@@ -203,6 +224,11 @@ class TrainedModel:
             d["quant_codes"], d["quant_scales"] = self.quant_codes, self.quant_scales
         if self.prune_k is not None:
             d["prune_sparsity"], d["prune_k"] = np.asarray([self.prune_sparsity], np.float64), self.prune_k
+        if self.act_ranges is not None:
+            d["act_bits"] = np.asarray([self.act_bits], np.int64)
+            d["act_ranges"] = np.stack([self.act_ranges["m_b"], self.act_ranges["r"]], axis=1).astype(np.float32)
+            d["act_counts"] = self.act_ranges["count"].astype(np.int64)
+            d["act_momentum"] = np.asarray([self.act_momentum], np.float64)
         with open(path, "wb") as f:
             np.savez(f, **d)
 
@@ -232,13 +258,21 @@ class TrainedModel:
             prune = {}
             if "prune_k" in z.files:
                 prune = dict(prune_sparsity=float(z["prune_sparsity"][0]), prune_k=z["prune_k"].copy())
+            act = {}
+            if "act_ranges" in z.files:
+                from . import quant as Q
+                rec = np.zeros(len(z["act_counts"]), Q.ACT_RANGE_DTYPE)
+                rec["m_b"], rec["r"], rec["count"] = z["act_ranges"][:, 0], z["act_ranges"][:, 1], z["act_counts"]
+                act = dict(act_bits=int(z["act_bits"][0]), act_ranges=rec,
+                           act_momentum=float(z["act_momentum"][0]) if "act_momentum" in z.files else None)
             return cls(gene=tuple(int(v) for v in z["gene"]), variant=G.VARIANT_CODES[variant], classes=classes, T=T, F=F, seed=seed,
                        params=z["params"].copy(), objectives=obj, frontend=fe, mean=mean, scale=scale,
-                       thresholds=thresholds, **quant, **prune)
+                       thresholds=thresholds, **quant, **prune, **act)
 
     def session(self, config: Optional[EvalConfig] = None):
         """A ``NetSession`` holding these parameters (needs the GPU).  ``config`` supplies ``eval_batch`` and the like;
-        its variant and class count must be the model's."""
+        its variant and class count must be the model's.  A model that carries ``act_ranges`` gets the activation quantiser
+        at ``act_bits`` and ``act_momentum`` with those ranges, whatever ``config.act_quant`` says."""
         from .session import NetSession
         if config is None:
             config = EvalConfig(variant=self.variant, classes=self.classes)
@@ -248,6 +282,10 @@ class TrainedModel:
         net = NetSession(self.gene, config, self.T, self.F, self.seed)
         try:
             net.set_params(self.params)
+            if self.act_ranges is not None:   # the activation quantiser the fit scored with, under its tracked ranges
+                from .quant import ActQuantConfig
+                net.set_act_quant(ActQuantConfig(bits=self.act_bits, momentum=self.act_momentum))
+                net.set_act_ranges(self.act_ranges)
         except Exception:
             net.close()
             raise

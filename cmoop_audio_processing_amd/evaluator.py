@@ -39,7 +39,7 @@ from .distill import DistillConfig, check_teacher_table, require_teacher
 from .optim import OptimConfig
 from .ema import EmaConfig
 from .opoint import OperatingPointConfig
-from .quant import QuantConfig
+from .quant import ActQuantConfig, QuantConfig
 from .prune import PruneConfig
 
 FPR_CODES = {"v1": 0, "v1_quirk": 1, "v3": 2}
@@ -119,6 +119,12 @@ class EvalConfig:
     # "sparsity"}; with objective=True (the default) that size -- pruned and, with quant on, quantised -- takes the place of
     # size_mb in objs and in the size constraint.  Travels beside quant_struct(), as prune_struct()
     prune: Optional[PruneConfig] = None
+    # activation fake quantisation of every candidate's fit (quant.ActQuantConfig): the operand tensors of every MAC layer and of
+    # the global pool are quantised per tensor, with the batch's range in train steps and the tracked range in validation, early
+    # stopping and the read-outs, so acc and fpr describe a full-int8 model.  None or bits 0 = off, every number, row and dict
+    # as without the field (cmoop_net_set_actquant).  Result dicts gain "act_quant": {"bits"}.  Travels beside prune_struct(), as
+    # act_quant_struct()
+    act_quant: Optional[ActQuantConfig] = None
 
     @staticmethod
     def preset(script: str, **over) -> "EvalConfig":
@@ -207,6 +213,12 @@ class EvalConfig:
         if self.prune is None or not self.prune.enabled:
             return None
         return self.prune.check()._struct()
+
+    def act_quant_struct(self) -> Optional["_lib.ActQuant"]:
+        """The enabled activation quantiser as a ``cmoop_actquant``, checked; None when it is off."""
+        if self.act_quant is None or not self.act_quant.enabled:
+            return None
+        return self.act_quant.check()._struct()
 
     def prune_size_mb(self, gene) -> Optional[float]:
         """``genes.prune_size_mb`` of a candidate under this config (with the quantiser's bits when that is on too); None
@@ -477,15 +489,16 @@ class PopulationEvaluator:
         return d
 
     def _population_call(self, genes, sd, n, cfg, next_cb, acc, size, fpr, ep, secs, done, op=None) -> None:
-        """THE population call: ``cmoop_eval_population_p`` with ``config.option_structs``, ``config.ema_struct``,
-        ``config.opoint_struct``, ``config.quant_struct`` and ``config.prune_struct`` by reference, None (NULL) for whatever is off; next_cb None: the
+        """THE population call: ``cmoop_eval_population_aq`` with ``config.option_structs``, ``config.ema_struct``,
+        ``config.opoint_struct``, ``config.quant_struct``, ``config.prune_struct`` and ``config.act_quant_struct`` by reference, None (NULL) for whatever is off; next_cb None: the
         library's own longest-first counter, and ``done`` is then None too.  ``op``: float64 [n, 4] for the operating-point
         summaries, or None.  The quantised size is a closed form of the gene (``genes.quant_size_mb``, equal to what the call
         would return), and so is the pruned size (``genes.prune_size_mb``): the result rows do not carry them."""
         ds = self._dataset()
         opts = self.config.option_structs(self.T, self.F, self.teacher_logits, len(self.X_train)) + \
-            (self.config.ema_struct(), self.config.opoint_struct(), self.config.quant_struct(), self.config.prune_struct())
-        _lib.check(_lib.lib().cmoop_eval_population_p(
+            (self.config.ema_struct(), self.config.opoint_struct(), self.config.quant_struct(), self.config.prune_struct(),
+             self.config.act_quant_struct())
+        _lib.check(_lib.lib().cmoop_eval_population_aq(
             C.byref(cfg), *(C.byref(o) if o is not None else None for o in opts), C.byref(ds), _lib.ptr(genes), _lib.ptr(sd),
             C.c_int32(n), C.cast(next_cb, C.c_void_p) if next_cb is not None else None, None, _lib.ptr(acc), _lib.ptr(size),
             _lib.ptr(fpr), _lib.ptr(ep), None, _lib.ptr(secs), _lib.ptr(done), _lib.ptr(op), None, None))
@@ -614,6 +627,8 @@ class PopulationEvaluator:
                     d.update(extra)
                     d["size_fp32_mb"] = size_mb
                 d["prune"] = {"size_mb": p_mb, "sparsity": float(c.prune.sparsity)}
+            if c.act_quant_struct() is not None:
+                d["act_quant"] = {"bits": int(c.act_quant.bits)}
             results.append(d)
         return results
 
@@ -628,7 +643,8 @@ class PopulationEvaluator:
         and it carries ``quant_bits`` / ``quant_codes`` / ``quant_scales``; ``objectives["size_mb"]`` is then the quantised
         size when ``quant.objective``.  Under ``config.prune`` ``params`` are the arena pruned at the final sparsity
         (``NetSession.get_pruned``; quantised on top when both are on) and the model carries ``prune_sparsity`` and the
-        per-tensor ``prune_k``; ``objectives["size_mb"]`` is then the pruned size when ``prune.objective``.
+        per-tensor ``prune_k``; ``objectives["size_mb"]`` is then the pruned size when ``prune.objective``.  Under
+        ``config.act_quant`` the model carries ``act_bits`` and the tracked ``act_ranges``, which ``session()`` turns on again.
         ``hparams`` is the reference's dict or a gene tuple; ``frontend`` / ``mean`` / ``scale`` (the front end and the
         StandardScaler the features were made with) ride along for ``StreamScorer``."""
         from .deploy import TrainedModel
@@ -648,6 +664,8 @@ class PopulationEvaluator:
                 assert (zeros.astype(np.int64) >= prune_k).all()
             if net.quant is not None:
                 params, codes, scales = net.get_quantized()
+            # the tracked ranges the fit validated and scored with: session() / logits() / StreamScorer load them
+            act_ranges = net.get_act_ranges() if net.act_quant is not None else None
         v = G.VARIANT_NAMES[self.config.variant]
         size_mb = G.model_size_mb(g, v, self.config.classes)
         if codes is not None and self.config.quant.objective:
@@ -661,7 +679,9 @@ class PopulationEvaluator:
                             seed=int(seed), params=params, objectives=objectives, frontend=frontend, mean=mean, scale=scale,
                             thresholds=thresholds, quant_bits=int(self.config.quant.bits) if codes is not None else None,
                             quant_codes=codes, quant_scales=scales,
-                            prune_sparsity=float(self.config.prune.sparsity) if prune_k is not None else None, prune_k=prune_k)
+                            prune_sparsity=float(self.config.prune.sparsity) if prune_k is not None else None, prune_k=prune_k,
+                            act_bits=int(self.config.act_quant.bits) if act_ranges is not None else None, act_ranges=act_ranges,
+                            act_momentum=float(self.config.act_quant.momentum) if act_ranges is not None else None)
 
     def _print(self, r):
         if self.config.verbose:

@@ -10,8 +10,13 @@ fixes the semantics at ``cmoop_quant``).  Symmetric, per-output-channel, weight-
 * ``wq_i = float32(q_i) * s``, one float32 product; a NaN scale or product is stored as the quiet NaN ``0x7FC00000``.
 
 The gradients formed with ``wq`` go unchanged to the latent ``w`` (straight-through; the absmax scale never clips, so there
-is no mask).  Activations stay fp32.  ``fake_quant_ref`` (numpy float32, one rounding per operation) is the statement the
-kernel is tested against; no accuracy figure is measured or claimed.
+is no mask).  Under ``QuantConfig`` activations stay fp32.  ``fake_quant_ref`` (numpy float32, one rounding per operation) is
+the statement the kernel is tested against; no accuracy figure is measured or claimed.
+
+``ActQuantConfig`` is the separate, opt-in activation quantiser (``cmoop_actquant``): the same element arithmetic on ONE
+channel that spans a whole activation tensor, at the operand tensors of every MAC layer and of the global pool.  Train steps
+take the batch's own absmax (never clips) and track it with a momentum; inference takes the tracked range (clips).
+``fake_quant_act_ref`` / ``act_range_update_ref`` / ``act_sites`` are its numpy statements.
 """
 from __future__ import annotations
 
@@ -76,9 +81,17 @@ def fake_quant_ref(w, bits: int):
     w = np.ascontiguousarray(w, f)
     if w.ndim != 2:
         raise ValueError("fake_quant_ref expects [channels, len]")
-    qmax = f(qmax_of(bits))
     mag = w.view(np.uint32) & np.uint32(0x7FFFFFFF)
     a = (mag.max(axis=1) if w.shape[1] else np.zeros(w.shape[0], np.uint32)).astype(np.uint32).view(f)
+    s, q, wq = _quant_elements(w, a, bits)
+    return a, s, q, wq
+
+
+def _quant_elements(w, a, bits: int):
+    """THE element arithmetic of both fake quantisers: ``w`` float32 [channels, len] under the ranges ``a`` float32 [channels]
+    -> (scales, codes int8, wq).  One IEEE single operation per line."""
+    f = np.float32
+    qmax = f(qmax_of(bits))
     with np.errstate(all="ignore"):
         s = (a / qmax).astype(f)
         s.view(np.uint32)[np.isnan(s)] = CANONICAL_NAN
@@ -90,7 +103,216 @@ def fake_quant_ref(w, bits: int):
         q = np.clip(r, -qmax, qmax).astype(np.int32)
         wq = (q.astype(f) * s[:, None]).astype(f)
         wq.view(np.uint32)[np.isnan(wq)] = CANONICAL_NAN
-    return a, s, q.astype(np.int8), wq
+    return s, q.astype(np.int8), wq
+
+
+# ---- activation fake quantisation (include/cmoop.h fixes the semantics at cmoop_actquant) -------------------------------
+ActQuantStruct = _lib.ActQuant      # cmoop_actquant
+ActRangeStruct = _lib.ActRange      # cmoop_act_range
+ACT_RANGE_DTYPE = np.dtype([("m_b", np.float32), ("r", np.float32), ("count", np.int32), ("reserved", np.int32)])
+
+
+@dataclasses.dataclass(frozen=True)
+class ActQuantConfig:
+    """Mirrors ``cmoop_actquant``: per-tensor, symmetric, signed fake quantisation of the operand tensors of every MAC layer
+    and of the global pool, inside the train step (batch ranges, tracked with ``momentum``) and every inference pass (tracked
+    ranges).  Domain: ``bits`` 0 (off) or 2..8; ``momentum`` in [0, 1).  Build-defined; no accuracy figure is claimed."""
+    bits: int = 8
+    momentum: float = 0.99
+
+    @property
+    def enabled(self) -> bool:
+        return int(self.bits) != 0
+
+    def _struct(self) -> ActQuantStruct:
+        st = ActQuantStruct()
+        st.bits, st.momentum = int(self.bits), float(self.momentum)
+        st.reserved[0] = st.reserved[1] = 0
+        return st
+
+    def check(self) -> "ActQuantConfig":
+        """Raise ValueError naming the offending field when the config is outside the domain (host only)."""
+        return check_act_struct(self._struct(), self)
+
+
+def check_act_struct(st: ActQuantStruct, ret=None):
+    L = _lib.lib()
+    if L.cmoop_actquant_check(C.byref(st)) != 0:
+        raise ValueError(L.cmoop_last_error().decode("utf-8", "replace"))
+    return ret
+
+
+def default_act_quant_config() -> ActQuantConfig:
+    """cmoop_actquant_default as an ActQuantConfig: off, momentum 0.99 as float32 holds it."""
+    st = ActQuantStruct()
+    _lib.check(_lib.lib().cmoop_actquant_default(C.byref(st)))
+    return ActQuantConfig(bits=int(st.bits), momentum=float(st.momentum))
+
+
+def fake_quant_act_ref(x, bits: int, a=None):
+    """The operator restated in numpy: ``x`` float32 of any shape, ONE channel that spans the whole tensor -> (a float32: the
+    range that was used, y float32 in the shape of ``x``).  ``a`` None: batch mode, the tensor's own absmax; else tracked
+    mode under that range (the clamp then works).  The element arithmetic is ``fake_quant_ref``'s."""
+    x = np.ascontiguousarray(x, np.float32)
+    flat = x.reshape(1, -1)
+    if a is None:
+        mag = flat.view(np.uint32) & np.uint32(0x7FFFFFFF)
+        a = (mag.max(axis=1) if flat.shape[1] else np.zeros(1, np.uint32)).astype(np.uint32).view(np.float32)
+    else:
+        a = np.asarray([a], np.float32)
+    _s, _q, y = _quant_elements(flat, a, bits)
+    return a[0], y.reshape(x.shape)
+
+
+def act_momentum_pair(momentum):
+    """(mu, omu) = (float32(momentum), float32(1.0 - float64(float32(momentum)))): what the kernel multiplies by."""
+    mu = np.float32(momentum)
+    return mu, np.float32(1.0 - np.float64(mu))
+
+
+def act_range_update_ref(r, m_b, count: int, momentum):
+    """The tracked range after a train step whose tensor had absmax ``m_b``: ``m_b`` when ``count == 0``, else
+    ``fl(fl(mu * r) + fl(omu * m_b))`` in float32; a NaN in the canonical form."""
+    f = np.float32
+    m_b = np.asarray(m_b, f).reshape(1).copy()
+    m_b.view(np.uint32)[np.isnan(m_b)] = CANONICAL_NAN
+    if int(count) == 0:
+        return m_b[0]
+    mu, omu = act_momentum_pair(momentum)
+    with np.errstate(all="ignore"):
+        keep = f(mu * f(r))
+        add = f(omu * m_b[0])
+        out = np.asarray([f(keep + add)], f)
+    out.view(np.uint32)[np.isnan(out)] = CANONICAL_NAN
+    return out[0]
+
+
+_MAC_KINDS = ("conv", "dwconv", "dense", "gap")
+
+
+def act_plan(hparams, variant, classes: int, T: int, F: int):
+    """The act / op walk of a candidate, restating plan_net: (acts [(H, W, C, virt)], ops [(kind, in, in2, out)], logits index).
+    kinds: conv1, conv, dwconv, bn, pool, addrelu, gap, dense.  ``variant``: a name or a code."""
+    g = G.normalize_hparams(hparams) if isinstance(hparams, dict) else tuple(int(v) for v in hparams)
+    G.validate_gene(g)
+    v = G.VARIANT_NAMES[variant] if isinstance(variant, str) else int(variant)
+    f, _k, bn, R, fc, _dr = g
+    A, ds = (v & 1) == 0, v >= 2
+    acts, ops = [[int(T), int(F), 1, False]], []
+
+    def new(H, W, Cn):
+        acts.append([H, W, Cn, False])
+        return len(acts) - 1
+
+    def conv(kind, i, cout, stride=1):
+        H, W = acts[i][0], acts[i][1]
+        o = new((H + stride - 1) // stride, (W + stride - 1) // stride, cout)
+        ops.append((kind, i, -1, o))
+        return o
+
+    def sepconv(i, cout):
+        if not ds:
+            return conv("conv", i, cout)
+        return conv("conv", conv("dwconv", i, acts[i][2]), cout)
+
+    def bnorm(i):
+        o = new(*acts[i][:3])
+        ops.append(("bn", i, -1, o))
+        return o
+
+    def pool(i, mask_y_pos):
+        if ops and ops[-1][0] == "bn" and ops[-1][3] == i and not mask_y_pos:
+            acts[i][3] = True                               # fused into the BatchNorm: never materialised
+        o = new((acts[i][0] + 1) // 2, (acts[i][1] + 1) // 2, acts[i][2])
+        ops.append(("pool", i, -1, o))
+        return o
+
+    x = conv("conv1", 0, f)
+    if A:
+        if bn:
+            x = bnorm(x)
+        x = sepconv(x, f)
+        if bn:
+            x = bnorm(x)
+        x = pool(x, 0)
+    else:
+        if bn:
+            x = bnorm(x)
+        x = pool(x, not bn)
+    c = f
+    for _ in range(R):
+        skip = conv("conv", x, 2 * c, 2)
+        y = sepconv(x, 2 * c)
+        if A:
+            if bn:
+                y = bnorm(y)
+            y = sepconv(y, 2 * c)
+            if bn:
+                y = bnorm(y)
+            y = pool(y, 0)
+        else:
+            if bn:
+                y = bnorm(y)
+            y = pool(y, not bn)
+        o = new(*acts[y][:3])
+        ops.append(("addrelu", y, skip, o))
+        x, c = o, 2 * c
+    o = new(1, 1, acts[x][2])
+    ops.append(("gap", x, -1, o))
+    x = o
+    for width in G.FC_LAYER_CONFIGS[fc]:
+        x = conv("dense", x, int(width))
+    x = conv("dense", x, int(classes))
+    return [tuple(a) for a in acts], ops, x
+
+
+def act_sites(hparams, variant, classes: int, T: int, F: int) -> List[Tuple[int, int, int, int]]:
+    """[(act, H, W, C)] of the activation-quantisation sites in site order, the rule restated: act i is a site iff it is not
+    the input (0), not the logits, is materialised, and is the input of at least one conv / depthwise / dense / global-pool
+    op.  The twin of ``cmoop_actquant_sites``."""
+    acts, ops, logits = act_plan(hparams, variant, classes, T, F)
+    out = []
+    for i, (H, W, Cn, virt) in enumerate(acts):
+        if i == 0 or i == logits or virt:
+            continue
+        if any(op[1] == i and op[0] in _MAC_KINDS for op in ops):
+            out.append((i, H, W, Cn))
+    return out
+
+
+def c_act_sites(gene, variant: int, classes: int, T: int, F: int) -> List[Tuple[int, int, int, int]]:
+    """``cmoop_actquant_sites``."""
+    g, cap = (C.c_int32 * 6)(*(int(v) for v in gene)), 64
+    rows, n = np.zeros((cap, 4), np.int32), C.c_int32()
+    _lib.check(_lib.lib().cmoop_actquant_sites(g, C.c_int32(int(variant)), C.c_int32(int(classes)), C.c_int32(int(T)), C.c_int32(int(F)),
+                                               _lib.ptr(rows), C.c_int32(cap), C.byref(n)))
+    return [tuple(int(v) for v in r) for r in rows[:n.value]]
+
+
+def fake_quant_act(x, bits: int, a=None, record=None, momentum: float = 0.99):
+    """``cmoop_fake_quant_act``: the operator alone, in place on ``x`` (a CUDA float32 tensor, or a 4-byte-aligned view of one).
+    ``a`` None: batch mode, and ``record`` (m_b, r, count) advances -> the new (m_b, r, count); else tracked mode under ``a``
+    -> ``record`` unchanged."""
+    import torch
+    rec = ActRangeStruct()
+    if record is not None:
+        rec.m_b, rec.r, rec.count = float(record[0]), float(record[1]), int(record[2])
+    a_in = C.c_float(float(a)) if a is not None else None
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_fake_quant_act(C.c_void_p(x.data_ptr()), C.c_int64(int(x.numel())), C.c_int32(int(bits)),
+                                               C.byref(a_in) if a_in is not None else None, C.byref(rec), C.c_float(float(momentum))))
+    return np.float32(rec.m_b), np.float32(rec.r), int(rec.count)
+
+
+def fake_quant_act_time(x, bits: int, a=None, momentum: float = 0.99, iters: int = 100) -> float:
+    """``cmoop_fake_quant_act_time``: average milliseconds of the call's launches (two in batch mode, one in tracked mode)."""
+    import torch
+    a_in, ms = (C.c_float(float(a)) if a is not None else None), C.c_double()
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_fake_quant_act_time(C.c_void_p(x.data_ptr()), C.c_int64(int(x.numel())), C.c_int32(int(bits)),
+                                                    C.byref(a_in) if a_in is not None else None, C.c_float(float(momentum)),
+                                                    C.c_int32(int(iters)), C.byref(ms)))
+    return float(ms.value)
 
 
 def quant_table(gene, variant: int, classes: int) -> List[Tuple[int, int, int, int, int]]:

@@ -27,10 +27,10 @@ class NetSession:
         _lib.check(_lib.lib().cmoop_net_total_params(self._h, C.byref(n)))
         self.n_params = int(n.value)
         self.T, self.F = int(T), int(F)
-        self.augment = self.loss = self.optim = self.ema = self.opoint = self.quant = self.prune = None
+        self.augment = self.loss = self.optim = self.ema = self.opoint = self.quant = self.prune = self.act_quant = None
         for name, setter in (("augment", self.set_augment), ("loss", self.set_loss), ("optim", self.set_optim),
                              ("ema", self.set_ema), ("operating_point", self.set_operating_point), ("quant", self.set_quant),
-                             ("prune", self.set_prune)):
+                             ("prune", self.set_prune), ("act_quant", self.set_act_quant)):
             if getattr(config, name, None) is not None:
                 try:
                     setter(getattr(config, name))
@@ -224,6 +224,49 @@ class NetSession:
         w, zeros = np.empty(self.n_params, np.float32), np.empty(rows, np.uint32)
         _lib.check(_lib.lib().cmoop_net_get_pruned(self._h, _lib.ptr(w), _lib.ptr(zeros)))
         return w, zeros
+
+    def set_act_quant(self, act_quant) -> None:
+        """Activation fake quantisation (``quant.ActQuantConfig``) of every following train step and inference call of this
+        net.  None or bits 0 turns it off (``self.act_quant`` is then None), and the net is bit for bit one that never had it.
+        On, the forward pass quantises every site (``quant.act_sites``) in place: train steps with the batch's own range, which
+        they also track, inference with the tracked range -- refused until a train step has run or ``set_act_ranges`` loaded
+        some.  ``get_state`` / ``set_state`` do not carry the ranges: ``get_act_ranges`` / ``set_act_ranges`` do."""
+        self._set("cmoop_net_set_actquant", None if act_quant is None else act_quant.check()._struct())
+        self.act_quant = act_quant if act_quant is not None and act_quant.enabled else None
+
+    def _n_sites(self) -> int:
+        n = C.c_int32()                                  # the net's own count: the session cannot disagree with what it wraps
+        _lib.check(_lib.lib().cmoop_net_get_act_ranges(self._h, None, C.c_int32(0), C.byref(n)))
+        return int(n.value)
+
+    def get_act_ranges(self) -> np.ndarray:
+        """The site records, a structured array [sites] of (m_b, r, count, reserved) in site order; raises while the net has
+        none (the option was never on)."""
+        from . import quant as Q
+        out, n = np.zeros(self._n_sites(), Q.ACT_RANGE_DTYPE), C.c_int32()
+        _lib.check(_lib.lib().cmoop_net_get_act_ranges(self._h, _lib.ptr(out), C.c_int32(len(out)), C.byref(n)))
+        assert n.value == len(out)
+        return out
+
+    def set_act_ranges(self, ranges) -> None:
+        """Loads site records as ``get_act_ranges`` gives them; inference is possible once every count is positive."""
+        from . import quant as Q
+        ranges = np.ascontiguousarray(ranges, Q.ACT_RANGE_DTYPE).reshape(-1)
+        _lib.check(_lib.lib().cmoop_net_set_act_ranges(self._h, _lib.ptr(ranges), C.c_int32(len(ranges))))
+
+    def act_dims(self, i: int):
+        """(H, W, C, materialised, has a gradient, number of acts) of act ``i`` of the plan (debug read-out)."""
+        dims = (C.c_int32 * 6)()
+        _lib.check(_lib.lib().cmoop_net_get_act(self._h, C.c_int32(int(i)), C.c_int32(0), dims, None, None))
+        return tuple(int(v) for v in dims)
+
+    def get_act(self, i: int, B: int, grad: bool = False):
+        """Debug read-out: float32 [B, H, W, C] of act ``i`` as the last step or pass left it (``grad``: its gradient)."""
+        H, W, Cn = self.act_dims(i)[:3]
+        out = np.empty((int(B), H, W, Cn), np.float32)
+        _lib.check(_lib.lib().cmoop_net_get_act(self._h, C.c_int32(int(i)), C.c_int32(int(B)), None, None if grad else _lib.ptr(out),
+                                                _lib.ptr(out) if grad else None))
+        return out
 
     def optim_stats(self) -> dict:
         """The last train step's optimiser read-out: dict(sumsq, norm, scale, path) -- the float64 sum of squares of the

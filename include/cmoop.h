@@ -96,11 +96,12 @@ int cmoop_fwd_flops(const int32_t gene[6], int32_t variant, int32_t classes, int
 
 /* compute_objectives_and_constraints' inner loop (nsga_penalty.py:426-427): evaluate n
  * candidates; outputs are host arrays of length n (any may be NULL).
- * THE POPULATION CALL.  The ten cmoop_eval_population* symbols are ONE call, cmoop_eval_population_p, each with fewer
+ * THE POPULATION CALL.  The eleven cmoop_eval_population* symbols are ONE call, cmoop_eval_population_aq, each with fewer
  * of its arguments: next (with ctx and evaluated; NULL: the library's own longest-first queue, evaluated may then be
- * NULL too) and the eight options aug, loss, distill, optim, ema, op, q, pr (cmoop_augment, cmoop_loss, cmoop_distill,
- * cmoop_optim, cmoop_ema, cmoop_opoint, cmoop_quant, cmoop_prune below, checked in that order).  An option that is NULL or disabled
- * gives exactly -- launch for launch, bit for bit -- the call without it, so a caller may always take _p and pass NULL for what is off. */
+ * NULL too) and the nine options aug, loss, distill, optim, ema, op, q, pr, aq (cmoop_augment, cmoop_loss, cmoop_distill,
+ * cmoop_optim, cmoop_ema, cmoop_opoint, cmoop_quant, cmoop_prune, cmoop_actquant below, checked in that order).  An option that is
+ * NULL or disabled gives exactly -- launch for launch, bit for bit -- the call without it, so a caller may always take _aq (or _p,
+ * which is _aq with aq NULL) and pass NULL for what is off. */
 int cmoop_eval_population(const cmoop_config* cfg, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
                           const uint32_t* seeds /* [n] */, int32_t n, double* acc, double* size_mb, double* fpr,
                           int32_t* epochs_run, double* val_loss, double* seconds);
@@ -457,8 +458,9 @@ int cmoop_eval_population_op(const cmoop_config* cfg, const cmoop_augment* aug, 
  *     it is about to read: the average under cmoop_net_use_ema.  A fit therefore validates, early-stops and reads out the quantised
  *     model; restore_best snapshots latent weights and the read-out re-quantises them, which is deterministic, so it is the same
  *     model.  The step is not captured as a graph.
- *   Out of scope: activations stay fp32 (weight-only); BatchNorm folding; TFLite / ONNX writers.  It composes with every
- *     gemm_mode (the bf16 bodies round wq); only fp32 is tested.
+ *   Out of scope: activations stay fp32 under this option (weight-only; cmoop_actquant below is the separate, opt-in activation
+ *     quantiser); BatchNorm folding; TFLite / ONNX writers.  It composes with every gemm_mode (the bf16 bodies round wq); only
+ *     fp32 is tested.
  *   Size: quant_size_bytes = sum over kernel tensors of ceil(elements * bits / 8) + 4 * (total channels) + 4 * (n_params -
  *     kernel elements).  size_mb of the population call stays count_params * 4 / 2^20; the new number is returned next to it.
  * Domain: bits in {0, 2..8}, objective in {0, 1}, reserved 0.  A config is ENABLED iff bits != 0.  objective is read by the host
@@ -564,7 +566,8 @@ int cmoop_prune_weights(const float* w_dev, int64_t n, const int64_t* rows_host 
  * warm-up calls */
 int cmoop_prune_weights_time(const float* w_dev, int64_t n, const int64_t* rows_host, int32_t count, double s, float* out_dev,
                              uint32_t* zeros_dev, int32_t iters, double* avg_ms);
-/* the population call (above) with every argument: the other nine forward here.  pr NULL or disabled: cmoop_eval_population_q's
+/* the population call (above) with every argument but the activation quantiser: forwards to cmoop_eval_population_aq with NULL.
+ * pr NULL or disabled: cmoop_eval_population_q's
  * launches and bytes, and prune (may be NULL) receives zeros; enabled: prune [n][3] receives every candidate's
  * {prune_size_bytes / 2^20, sparsity, zero fraction of the pruned tensors of the scored model} */
 int cmoop_eval_population_p(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
@@ -574,6 +577,76 @@ int cmoop_eval_population_p(const cmoop_config* cfg, const cmoop_augment* aug, c
                             double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated,
                             double* opoint /* [n][4], may be NULL */, double* quant /* [n][2], may be NULL */,
                             double* prune /* [n][3], may be NULL */);
+
+/* ---- activation fake quantisation: train and score full-int8 candidates (opt-in, off by default).  BUILD-DEFINED: the reference
+ * trains and scores an fp32 model and has no counterpart; with no actquant config, or a disabled one, every launch and every bit is
+ * that of a build without it.  No accuracy figure is measured or claimed.
+ * Per-tensor, symmetric, signed fake quantisation of an fp32 tensor, in place.  bits in 2..8, qmax = 2^(bits-1) - 1.  The
+ * arithmetic is cmoop_quant's, applied to ONE channel that spans the whole tensor, with elements x_i and a range a:
+ *     s    = a / (float)qmax, one correctly rounded fp32 division.
+ *     if s > 0 is false (a is zero, a / qmax underflows to zero, or NaN): every code is 0.
+ *     else q_i = clamp(rintf(x_i / s), -qmax, qmax): one fp32 division, round half to even; a NaN quotient is code 0.
+ *     y_i  = (float)q_i * s, one fp32 product.  NaNs are stored in ONE form, the quiet NaN 0x7FC00000.
+ *   Two range modes:
+ *     BATCH mode (train steps): a = m_b, the float whose bits are max_i (bits(x_i) & 0x7FFFFFFF) compared as uint32, over the B
+ *       rows actually in the batch: exact and order-free.  It never clips, so the straight-through gradient needs no upper mask.
+ *     TRACKED mode (every inference pass): a = r, the site's tracked range; the clamp now does real work.
+ *   Tracking, on each train step, count being the number of steps the site has seen: count == 0: r = m_b; otherwise
+ *     r = fl(fl(mu * r) + fl(omu * m_b)) in fp32 with no contraction, mu = (float)momentum and omu = (float)(1.0 - (double)momentum)
+ *     formed on the host; a NaN m_b propagates in the canonical form.  Then count += 1 (saturating).
+ *   Sites of a net: act i of the plan is a site iff i is not the input features, not the logits, is materialised (not a BatchNorm
+ *     output fused into its max-pool) and is the input of at least one convolution (full, depthwise, pointwise, skip projection),
+ *     dense layer or the global average pool: the operand tensors of every MAC layer and of the global pool, numbered in act
+ *     order (cmoop_actquant_sites).  The forward pass quantises a site right after the launch that writes it (for a fused
+ *     BatchNorm + pool: the pool's output); every consumer reads the quantised tensor.  Two launches per site per train step
+ *     (absmax partials; fold + quantise + record), one per site per inference chunk.
+ *   GAPS: the first layer reads the resident feature tensor, which stays untouched; the operands of the residual add + ReLU stay
+ *     fp32.  Symmetric signed ranges cost one bit on ReLU outputs.  Asymmetric or unsigned ranges, per-channel activation scales,
+ *     learned clipping, a quantiser fused into the producers' epilogues, BatchNorm folding and an integer inference engine are out
+ *     of scope.  It composes with the bf16 gemm modes, untested.
+ *   The backward pass is not changed.  Weight gradients are formed with the quantised operands.  The x > 0 masks the dgrad / pool
+ *     / GAP kernels already take from the layer input now read quantised values, so an element that rounds to code 0 passes no
+ *     gradient, exactly as the integer model's ReLU would see it.  Everything else is straight-through.
+ *   Inference with the option on is refused, with a message and before anything is launched, while no train step has run with
+ *     the option on and no ranges were loaded (cmoop_net_set_act_ranges).  The restore_best snapshot of a fit carries the site
+ *     records with the weights: the best-epoch model has the ranges it was validated with.  Under cmoop_net_use_ema the tracked
+ *     ranges are those of the raw-weight trajectory.  Independent of cmoop_quant and cmoop_prune, and composes with both.  The
+ *     step is not captured as a graph while the option is on.
+ * Domain: bits in {0, 2..8}, momentum in [0, 1), reserved 0.  A config is ENABLED iff bits != 0. */
+typedef struct cmoop_actquant {
+    int32_t bits;         /* 0 = off, else 2 .. 8 */
+    float momentum;       /* of the tracked range, in [0, 1) */
+    int32_t reserved[2];  /* 0 */
+} cmoop_actquant;         /* 16 bytes */
+typedef struct cmoop_act_range {
+    float m_b;            /* absmax of the site's tensor at the last train step */
+    float r;              /* the tracked range */
+    int32_t count;        /* train steps the site has seen (saturating) */
+    int32_t reserved;     /* 0 */
+} cmoop_act_range;        /* 16 bytes */
+int cmoop_actquant_default(cmoop_actquant* aq);   /* off: bits 0, momentum 0.99 */
+/* host-only: non-zero + a message naming the offending field (bits, momentum, reserved) when the config is outside the domain */
+int cmoop_actquant_check(const cmoop_actquant* aq);
+/* host-only: the sites of a candidate at a T x F patch in site order, rows [count][4] = {act index, H, W, C}.  cap: rows the
+ * buffer holds (an error when too small); count may be NULL */
+int cmoop_actquant_sites(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int32_t* rows /* [cap][4] */,
+                         int32_t cap, int32_t* count);
+/* the operator alone on the library stream: x_dev [n] (n < 2^31, aligned to 4 bytes) quantised in place at `bits`.  a_in NULL:
+ * batch mode, and record_inout (required) advances as a site's record does under `momentum`.  a_in given: tracked mode with
+ * a = *a_in; record_inout (may be NULL) is left as it is */
+int cmoop_fake_quant_act(float* x_dev, int64_t n, int32_t bits, const float* a_in, cmoop_act_range* record_inout, float momentum);
+/* average milliseconds of that call's launches (two in batch mode, one in tracked mode) over `iters` back-to-back repetitions
+ * between two HIP events on the library stream, after 3 warm-up repetitions */
+int cmoop_fake_quant_act_time(float* x_dev, int64_t n, int32_t bits, const float* a_in, float momentum, int32_t iters, double* avg_ms);
+/* the population call (above) with every argument: the other ten forward here.  aq NULL or disabled: cmoop_eval_population_p's
+ * launches and bytes */
+int cmoop_eval_population_aq(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
+                             const cmoop_optim* optim, const cmoop_ema* ema, const cmoop_opoint* op, const cmoop_quant* q,
+                             const cmoop_prune* pr, const cmoop_actquant* aq, const cmoop_dataset* ds, const int32_t* genes /* [n][6] */,
+                             const uint32_t* seeds /* [n] */, int32_t n, cmoop_next_fn next, void* ctx, double* acc, double* size_mb,
+                             double* fpr, int32_t* epochs_run, double* val_loss, double* seconds, int32_t* evaluated,
+                             double* opoint /* [n][4], may be NULL */, double* quant /* [n][2], may be NULL */,
+                             double* prune /* [n][3], may be NULL */);
 
 /* host-only: does every conv layer of this candidate at `batch` rows per launch (pass max(batch, eval_batch)) stay inside
  * the kernels' 32-bit byte offsets (each activation / kernel tensor below 2^29 elements)?  Non-zero + message if not;
@@ -883,6 +956,22 @@ int cmoop_net_set_prune(cmoop_net* net, const cmoop_prune* p /* NULL = off */);
  * weff_params_host [total params] (every element outside the pruned tensors copied) and zeros_host [count of cmoop_prune_table]
  * uint32, the elements of each tensor that became zero; either may be NULL.  An error while the option is off. */
 int cmoop_net_get_pruned(cmoop_net* net, float* weff_params_host, uint32_t* zeros_host);
+/* Activation fake quantisation (cmoop_actquant above) of every following train step and inference call of this net (NULL or a
+ * disabled config: off, and every launch and bit is that of a net that never had one; the site records are kept).  The per-site
+ * records (count 0) and the partials workspace are allocated on first use.  cmoop_net_get_state / _set_state do not carry the
+ * records: a re-synchronising caller uses the two entry points below as well. */
+int cmoop_net_set_actquant(cmoop_net* net, const cmoop_actquant* aq /* NULL = off */);
+/* the site records in site order: host [cap] receives count = the number of sites of them (an error when cap is smaller; count
+ * may be NULL).  host NULL with count given: the number of sites alone.  An error while no records exist (the option was never
+ * on). */
+int cmoop_net_get_act_ranges(cmoop_net* net, cmoop_act_range* host, int32_t cap, int32_t* count);
+/* loads the site records (count must be the number of sites; every count >= 0, no negative r or m_b).  When every record has
+ * count > 0, inference is possible from here on. */
+int cmoop_net_set_act_ranges(cmoop_net* net, const cmoop_act_range* host, int32_t count);
+/* debug read-out of act index i of the plan: dims (may be NULL) = {H, W, C, 1 if materialised, 1 if it has a gradient buffer,
+ * the number of acts}; data_host / grad_host (either may be NULL; both NULL: dims only) receive the first B rows of the data and
+ * of the gradient as the last step or pass left them.  An error for an act that is never materialised. */
+int cmoop_net_get_act(cmoop_net* net, int32_t i, int32_t B, int32_t dims[6], float* data_host, float* grad_host);
 /* cmoop_net_train_step_targets with a teacher row per batch row, q_dev [B][classes], and the distillation loss at
  * (alpha, temperature), whatever cmoop_net_set_distill says. */
 int cmoop_net_train_step_distill_targets(cmoop_net* net, const float* x_rows_dev, const float* t_dev, const float* w_dev,
