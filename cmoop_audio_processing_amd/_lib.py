@@ -318,6 +318,18 @@ DWCONV_PROTOTYPES = {
     "cmoop_plan_dwconvs": [_V, _I32, _I32, _I32, _V, _I32, _V],
 }
 
+#: prototypes of the integer-inference entry points (include/cmoop.h); pointers travel as void*, None is NULL
+_F32 = C.c_float
+INT8_PROTOTYPES = {
+    "cmoop_conv_fwd_i8": [_V, _V, _F32, _V, _V, _V] + [_I32] * 8,
+    "cmoop_dense_fwd_i8": [_V, _V, _F32, _V, _V, _V] + [_I32] * 4,
+    "cmoop_conv_fwd_i8_time": [_V, _V, _F32, _V, _V, _V] + [_I32] * 9 + [_V],
+    "cmoop_fake_quant_act_codes": [_V, _I64, _I32, _V, _V],
+    "cmoop_int8_ops": [_V, _I32, _I32, _I32, _I32, _V, _I32, _V],
+    "cmoop_net_set_int8": [_V, _I32],
+    "cmoop_net_int8_ops": [_V, _V, _I32, _V],
+}
+
 #: CMOOP_GEMM_* (include/cmoop.h)
 GEMM_DEFAULT, GEMM_FP32, GEMM_BF16X3, GEMM_BF16 = 0, 1, 2, 3
 
@@ -362,7 +374,7 @@ def lib():
         L.cmoop_config_default.restype = None
         for table in (STREAM_PROTOTYPES, AUGMENT_PROTOTYPES, PCEN_PROTOTYPES, ELEM_PROTOTYPES, LOSS_PROTOTYPES, DENSE_PROTOTYPES,
                       DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES, OPOINT_PROTOTYPES, QUANT_PROTOTYPES,
-                      PRUNE_PROTOTYPES, ACTQUANT_PROTOTYPES, RESAMPLE_PROTOTYPES):
+                      PRUNE_PROTOTYPES, ACTQUANT_PROTOTYPES, RESAMPLE_PROTOTYPES, INT8_PROTOTYPES):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         _lib = L

@@ -579,6 +579,78 @@ int cmoop_fake_quant_act_time(float* x_dev, int64_t n, int32_t bits, const float
     });
 }
 
+// ---- integer inference ---------------------------------------------------------------
+int cmoop_fake_quant_act_codes(float* x_dev, int64_t n, int32_t bits, const float* a_in, int8_t* codes_dev) {
+    return guard([&] {
+        CMOOP_REQUIRE(a_in != nullptr, "fake_quant_act_codes: tracked mode only (a_in is required)");
+        CMOOP_REQUIRE(bits >= 2 && bits <= 8, "fake_quant_act_codes: bits must be in [2, 8]");
+        CMOOP_REQUIRE(n >= 0 && n <= ACT_QUANT_MAX_ELEMS, "fake_quant_act_codes: n must stay below 2^31 elements");
+        if (n == 0) return;
+        CMOOP_REQUIRE(x_dev != nullptr && reinterpret_cast<uintptr_t>(x_dev) % 4 == 0, "fake_quant_act_codes: x_dev is NULL or not aligned to 4 bytes");
+        const ActRange rec{0.f, *a_in, 0, 0};
+        hipStream_t s = lib_stream();
+        PoolScope pool(s);
+        ActRange* rec_dev = pool.get<ActRange>(sizeof(ActRange));
+        CMOOP_HIP(hipMemcpyAsync(rec_dev, &rec, sizeof(rec), hipMemcpyHostToDevice, s));
+        CMOOP_HIP(hipStreamSynchronize(s));
+        launch_fake_quant_act(x_dev, n, bits, true, nullptr, rec_dev, 0.f, 0.f, s, codes_dev);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_conv_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
+                      int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t relu) {
+    return guard([&] {
+        hipStream_t s = lib_stream();
+        launch_conv_i8_fwd(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, B, H, W, Cin, Cout, KS, stride, relu, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_dense_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
+                       int32_t M, int32_t N, int32_t K, int32_t relu) {
+    return guard([&] {
+        hipStream_t s = lib_stream();
+        launch_dense_i8_fwd(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, M, N, K, relu, s);
+        CMOOP_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cmoop_conv_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
+                           int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t relu,
+                           int32_t iters, double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "conv_fwd_i8_time: iters >= 1 and avg_ms");
+        hipStream_t s = lib_stream();
+        *avg_ms = time_launches(s, iters, [&] {
+            launch_conv_i8_fwd(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, B, H, W, Cin, Cout, KS, stride, relu, s);
+        });
+    });
+}
+
+// rows [count][16] of cmoop_int8_ops from a plan
+static void int8_ops_abi(const NetPlan& plan, int64_t* rows, int32_t cap, int32_t* count) {
+    const std::vector<Int8Op> ops = int8_ops(plan);
+    CMOOP_REQUIRE(rows && cap >= (int32_t)ops.size(), "int8_ops: the rows buffer is too small");
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const Op& op = plan.ops[ops[i].op];
+        const int64_t v[16] = {ops[i].op, op.kind == OP_DENSE ? 1 : 0, ops[i].in, ops[i].out, ops[i].site, op.H, op.W, op.Cin, op.Cout,
+                               op.KS, op.stride, op.relu, op.w_off, op.b_off, ops[i].scale_off, 0};
+        std::memcpy(rows + 16 * i, v, sizeof(v));
+    }
+    if (count) *count = (int32_t)ops.size();
+}
+
+int cmoop_int8_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap,
+                   int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(gene != nullptr && T >= 1 && F >= 1, "int8_ops: NULL gene or an empty patch");
+        NetConfig cfg;
+        cfg.variant = variant; cfg.classes = classes;
+        int8_ops_abi(plan_net(gene, cfg, T, F), rows, cap, count);
+    });
+}
+
 // ---- quantisation-aware training ---------------------------------------------------
 int cmoop_quant_default(cmoop_quant* q) {
     return guard([&] {
@@ -1627,6 +1699,18 @@ int cmoop_net_set_act_ranges(cmoop_net* h, const cmoop_act_range* host, int32_t 
         CMOOP_REQUIRE(h && h->net, "set_act_ranges: NULL net");
         CMOOP_REQUIRE(host && count == h->net->act_sites(), "set_act_ranges: count must be the number of sites");
         h->net->set_act_ranges(reinterpret_cast<const ActRange*>(host));
+    });
+}
+int cmoop_net_set_int8(cmoop_net* h, int32_t on) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "set_int8: NULL net");
+        h->net->set_int8(on != 0);
+    });
+}
+int cmoop_net_int8_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "int8_ops: NULL net");
+        int8_ops_abi(h->net->plan(), rows, cap, count);
     });
 }
 int cmoop_net_get_act(cmoop_net* h, int32_t i, int32_t B, int32_t dims[6], float* data_host, float* grad_host) {

@@ -565,9 +565,24 @@ inline int act_quant_blocks(int64_t n) {
 }
 // x [n] quantised in place at `bits`.  tracked: a = rec->r, rec is only read, partials unused (may be null).  Else batch mode:
 // a = absmax(x) through partials [act_quant_blocks(n)], and rec becomes {a, count == 0 ? a : (mu r) + (omu a), count + 1}.
-// n == 0: nothing is launched
+// n == 0: nothing is launched.  codes (tracked mode only, may be null): the int8 code of every element, [n], next to x
 void launch_fake_quant_act(float* x, int64_t n, int bits, bool tracked, uint32_t* partials, ActRange* rec, float mu, float omu,
-                           hipStream_t s);
+                           hipStream_t s, int8_t* codes = nullptr);
+
+// ---------------------------------------------------------------------------
+// Integer inference (opt-in, build-defined; include/cmoop.h fixes the arithmetic at "Integer inference"): a conv / dense layer on
+// int8 codes, exact int32 accumulation on v_mfma_i32_16x16x64_i8 and one dequantising epilogue (int8.hip).  Inference only.
+// ---------------------------------------------------------------------------
+// what the kernels take: Cin a multiple of 16, KS 1 / 3 / 5, stride 1 or the 1x1 stride-2 projection, 127^2 K < 2^31
+bool int8_layer_ok(int Cin, int Cout, int KS, int stride);
+// y [B][OH][OW][Cout] fp32 from xq [B][H][W][Cin] and wq [Cout][KS][KS][Cin] int8 (both 16-byte aligned), s_w / bias [Cout].
+// rec non-null: s_x = quant_scale(rec->r, qmax(act_bits)) read on the device (the tracked scale of the input site), else s_x
+void launch_conv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
+                        const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int KS, int stride, int relu,
+                        hipStream_t s);
+// y [M][N] fp32 from xq [M][K] and wq [N][K] int8; K a multiple of 16, any N
+void launch_dense_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
+                         const float* bias, float* y, int M, int N, int K, int relu, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Magnitude pruning in training (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_prune): per kernel tensor

@@ -227,6 +227,11 @@ NetPlan plan_net(const int32_t gene[6], const NetConfig& cfg, int T, int F);
 // plan.n_params.  Pruning rows have k = -1 (pruned at the sparsity of each launch); with skip_small the first convolution and
 // the depthwise kernels have k = 0 (copied)
 QuantTable quant_table(const NetPlan& plan);
+// host-only: the ops that run integer under Net::set_int8 -- every OP_CONV / OP_DENSE whose input is an activation-quantisation
+// site -- in op order.  Throws when such an op is beyond the integer kernels (int8_layer_ok) or its code rows would not be
+// 16-byte aligned (w_off % 16)
+struct Int8Op { int op, in, out, site; int64_t scale_off; };
+std::vector<Int8Op> int8_ops(const NetPlan& plan);
 PruneTable prune_table(const NetPlan& plan, bool skip_small = true);
 
 // The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
@@ -362,6 +367,18 @@ class Net : public GemmHook {
     // and r not negative; a record with count > 0 makes inference possible
     void get_act_ranges(ActRange* host);
     void set_act_ranges(const ActRange* host);
+    // Integer inference (kernels.h; include/cmoop.h fixes the arithmetic).  on: refused, before anything is launched and with the
+    // net unchanged, unless set_quant and set_actquant are both on and the ranges are ready, or when a tracked r or a weight
+    // scale (both read on the host here) is not finite.  First use allocates the weight-code arena, the scale buffer and one int8
+    // buffer per site.  While on, every inference pass stages the weights with codes and scales, the tracked apply kernel writes
+    // each site's codes next to its fp32 tensor, and the ops of int8_ops(plan) take the integer launch in place of the fp32 one
+    // (gemm_mode is ignored by them); every other launch, and every train step, is what it was.  Turning set_quant or
+    // set_actquant off turns the mode off as well.  The finiteness check is made when enabling and by set_act_ranges while the
+    // mode is on, NOT per pass: a train step or set_params that later produces a NaN or Inf range or scale is not caught, and
+    // the integer passes then return NaN logits without a fault, as the fp32 passes do
+    void set_int8(bool on);
+    bool int8_on() const { return int8_on_; }
+    const NetPlan& plan() const { return plan_; }
     // debug read-out: dims = {H, W, C, materialised, has a gradient, number of acts} of act i; data / grad (either may be null)
     // receive the first B rows as the last step or pass left them (grad: B <= cfg.batch)
     void get_act(int i, int B, int32_t dims[6], float* data_host, float* grad_host);
@@ -443,6 +460,7 @@ class Net : public GemmHook {
     // null).  Returns the arena of the last stage that ran, params_ when none did: where forward / backward read kernel tensors
     const float* stage_kernels(double sparsity, float* wp, uint32_t* zeros, float* wq, int8_t* codes, float* scales);
     void refresh_kernels(double sparsity) { kernels_ = stage_kernels(sparsity, wp_, nullptr, wq_, nullptr, nullptr); }
+    bool op_is_int8(size_t oi) const { return oi < op_scale_off_.size() && op_scale_off_[oi] >= 0; }
     ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
 
@@ -483,6 +501,11 @@ class Net : public GemmHook {
     ActRange *act_rec_ = nullptr, *act_rec_snap_ = nullptr;   // [n_sites] records and their snapshot_params copy, first enabled set_actquant
     uint32_t* act_partials_ = nullptr;  // [ACT_QUANT_MAX_BLOCKS] absmax partials of the site being quantised
     bool act_ranges_ready_ = false, act_ranges_ready_snap_ = false;   // host mirror of "every record has count > 0", and of the snapshot's
+    bool int8_on_ = false;              // set_int8: inference passes take the integer launches
+    int8_t* w_codes_ = nullptr;         // [n_params] weight codes (only kernel elements are ever written or read), first set_int8(true)
+    float* w_scales_ = nullptr;         // [qtab_.total_channels]
+    std::vector<int8_t*> site_codes_;   // per site: [Bmax][per_sample] activation codes
+    std::vector<int64_t> op_scale_off_; // per op: first scale of its kernel tensor when it runs integer, else -1
     std::vector<OpointClass> last_op_classes_;   // store_opoint: empty when the last fit ran without the read-out
     double last_op_summary_[4] = {0, 0, 0, 0};
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;

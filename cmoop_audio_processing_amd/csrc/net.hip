@@ -422,6 +422,21 @@ QuantTable quant_table(const NetPlan& plan) {
     return tab;
 }
 
+std::vector<Int8Op> int8_ops(const NetPlan& plan) {
+    std::vector<Int8Op> out;
+    int64_t channels = 0;                              // quant_table's scale_off: the channels of the kernel tensors before this one
+    for (const KernelTensor& t : plan.kernel_tensors()) {
+        const Op& op = plan.ops[t.op];
+        if ((op.kind == OP_CONV || op.kind == OP_DENSE) && plan.acts[op.in].site >= 0) {
+            CMOOP_REQUIRE(int8_layer_ok(op.Cin, op.Cout, op.KS, op.stride), "int8: a layer is beyond the integer kernels (Cin % 16, KS, stride, 127^2 K < 2^31)");
+            CMOOP_REQUIRE(op.w_off % 16 == 0, "int8: a kernel tensor's code rows are not 16-byte aligned (w_off % 16)");
+            out.push_back(Int8Op{t.op, op.in, op.out, plan.acts[op.in].site, channels});
+        }
+        channels += t.channels;
+    }
+    return out;
+}
+
 PruneTable prune_table(const NetPlan& plan, bool skip_small) {
     PruneTable tab;
     for (const KernelTensor& t : plan.kernel_tensors()) {
@@ -834,6 +849,14 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
             break;
         }
         case OP_CONV: {
+            if (!train && int8_on_ && op_is_int8(oi)) {   // integer inference: the site's codes against the staged weight codes
+                const Act& ia = acts_[op.in];
+                launch_conv_i8_fwd(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
+                                   w_scales_ + op_scale_off_[oi], params_ + op.b_off, acts_[op.out].data, B, op.H, op.W, op.Cin,
+                                   op.Cout, op.KS, op.stride, op.relu, stream_);
+                fused_stats_blocks_ = 0;
+                break;
+            }
             GemmEpilogue e;
             e.mode = op.gemm_mode;
             e.bias = params_ + op.b_off;
@@ -847,6 +870,13 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
             launch_dwconv_fwd(acts_[op.in].data, kern + op.w_off, acts_[op.out].data, B, op.H, op.W, op.Cin, op.KS, 0, nullptr, stream_);
             break;
         case OP_DENSE: {
+            if (!train && int8_on_ && op_is_int8(oi)) {
+                const Act& ia = acts_[op.in];
+                launch_dense_i8_fwd(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
+                                    w_scales_ + op_scale_off_[oi], params_ + op.b_off, acts_[op.out].data, B, op.Cout, op.Cin,
+                                    op.relu, stream_);
+                break;
+            }
             const bool drop = train && op.dropout_layer >= 0;
             const DropoutParams dp = dropout_params(cfg_.dropout);
             const uint32_t drop_stream = drop ? DropoutParams::stream(op.dropout_layer) : 0u;
@@ -909,8 +939,9 @@ void Net::quantise_site(int act, int B, bool train) {
     const Act& a = acts_[act];
     const EmaPair m = actquant_rates(actq_cfg_.momentum);
     // train: batch mode over the B rows of this step, and the site's record advances; inference: the tracked range
+    // integer inference: the codes go to the site's int8 buffer as well (the fp32 tensor stays: OP_GAP / OP_DWCONV read it)
     launch_fake_quant_act(a.data, (int64_t)B * (int64_t)a.per_sample(), actq_cfg_.bits, !train, act_partials_, act_rec_ + a.site, m.mf, m.omf,
-                          stream_);
+                          stream_, (!train && int8_on_) ? site_codes_[a.site] : nullptr);
 }
 
 void Net::require_act_ranges() const {
@@ -1348,6 +1379,7 @@ void Net::set_quant(const QuantCfg* quant) {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running; the table's upload is done
     quant_cfg_ = on ? *quant : QuantCfg();
     quant_on_ = on;
+    if (!on) int8_on_ = false;                    // integer inference needs the weight codes
     option_changed(on);
 }
 
@@ -1448,7 +1480,48 @@ void Net::set_actquant(const ActQuantCfg* actq) {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running
     actq_cfg_ = on ? *actq : ActQuantCfg();
     actq_on_ = on;
+    if (!on) int8_on_ = false;                    // integer inference needs the sites' codes
     option_changed(on);
+}
+
+void Net::set_int8(bool on) {
+    if (!on) {
+        CMOOP_HIP(hipStreamSynchronize(stream_));
+        int8_on_ = false;
+        return;
+    }
+    // every refusal comes before the first allocation or launch: a refused net is the net it was
+    CMOOP_REQUIRE(quant_on_, "int8: needs quantised weights -- set_quant with bits in [2, 8] first");
+    CMOOP_REQUIRE(actq_on_, "int8: needs quantised activations -- set_actquant with bits in [2, 8] first");
+    CMOOP_REQUIRE(act_ranges_ready_, "int8: needs tracked ranges -- run a train step with set_actquant on or load them (set_act_ranges) first");
+    const std::vector<Int8Op> iops = int8_ops(plan_);
+    CMOOP_HIP(hipStreamSynchronize(stream_));
+    std::vector<ActRange> rec((size_t)std::max(plan_.n_sites, 1));
+    CMOOP_HIP(hipMemcpy(rec.data(), act_rec_, (size_t)plan_.n_sites * sizeof(ActRange), hipMemcpyDeviceToHost));
+    for (int i = 0; i < plan_.n_sites; ++i)
+        CMOOP_REQUIRE(std::isfinite(rec[i].r), "int8: the tracked range of site " + std::to_string(i) + " is not finite");
+    {   // the scales inference would form now, into pooled buffers.  With pruning on the stage rewrites the net's own pruned
+        // arena at the final sparsity on the way: harmless, every step and every pass restages it before reading it
+        PoolScope pool(stream_);
+        const size_t n = (size_t)n_params_, ch = (size_t)qtab_.total_channels;
+        float* d_wq = pool.get<float>(std::max<size_t>(n, 1) * 4);
+        float* d_scales = pool.get<float>(std::max<size_t>(ch, 1) * 4);
+        stage_kernels(prune_cfg_.sparsity, wp_, nullptr, d_wq, nullptr, d_scales);
+        std::vector<float> sc(ch);
+        CMOOP_HIP(hipMemcpyAsync(sc.data(), d_scales, ch * 4, hipMemcpyDeviceToHost, stream_));
+        CMOOP_HIP(hipStreamSynchronize(stream_));
+        for (size_t i = 0; i < ch; ++i) CMOOP_REQUIRE(std::isfinite(sc[i]), "int8: a weight scale is not finite (channel " + std::to_string(i) + ")");
+    }
+    if (!w_codes_) {
+        w_codes_ = reinterpret_cast<int8_t*>(dalloc(((size_t)n_params_ + 3) / 4 + 4));
+        w_scales_ = dalloc((size_t)qtab_.total_channels);
+        site_codes_.assign((size_t)plan_.n_sites, nullptr);
+        for (const Act& a : acts_)
+            if (a.site >= 0) site_codes_[a.site] = reinterpret_cast<int8_t*>(dalloc(((size_t)Bmax_ * a.per_sample() + 3) / 4 + 4));
+        op_scale_off_.assign(ops_.size(), -1);
+        for (const Int8Op& o : iops) op_scale_off_[o.op] = o.scale_off;
+    }
+    int8_on_ = true;
 }
 
 void Net::get_act_ranges(ActRange* host) {
@@ -1463,6 +1536,9 @@ void Net::set_act_ranges(const ActRange* host) {
     for (int i = 0; i < plan_.n_sites; ++i) {
         CMOOP_REQUIRE(host[i].count >= 0, "set_act_ranges: count must not be negative");
         CMOOP_REQUIRE(!(host[i].r < 0.f) && !(host[i].m_b < 0.f), "set_act_ranges: r and m_b must not be negative");
+        // integer inference is on: what set_int8 refused at enabling is refused here as well (nothing is loaded)
+        CMOOP_REQUIRE(!int8_on_ || std::isfinite(host[i].r), "set_act_ranges: the tracked range of site " + std::to_string(i) +
+                      " is not finite while integer inference is on (set_int8(false) first)");
         ready = ready && host[i].count > 0;
     }
     CMOOP_HIP(hipMemcpyAsync(act_rec_, host, (size_t)plan_.n_sites * sizeof(ActRange), hipMemcpyHostToDevice, stream_));
@@ -1675,7 +1751,9 @@ void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch
 }
 
 template <class Source, class Sink> void Net::inference_pass(int64_t n, Source&& source, Sink&& sink) {
-    refresh_kernels(prune_cfg_.sparsity);   // once per call, on the arena this pass reads
+    // once per call, on the arena this pass reads; integer inference: with the codes and scales its integer launches take
+    if (int8_on_) kernels_ = stage_kernels(prune_cfg_.sparsity, wp_, nullptr, wq_, w_codes_, w_scales_);
+    else refresh_kernels(prune_cfg_.sparsity);
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);
         const std::pair<const float*, BatchRows> in = source(s, B);

@@ -156,9 +156,12 @@ __device__ __forceinline__ void act_range_advance(ActRange* rec, uint32_t abits,
     rec->reserved = 0;
 }
 
-template <bool TRACKED>
+// CODES (tracked mode only, integer inference): the int8 code of every element goes to codes [n] next to the fp32 value, four
+// codes per store where the group's first code is 4-byte aligned.  !CODES is the kernel as it always was
+template <bool TRACKED, bool CODES = false>
 __global__ __launch_bounds__(256) void act_quant_apply_kernel(float* __restrict__ x, int n, const uint32_t* __restrict__ partials,
-                                                              int nparts, ActRange* __restrict__ rec, float qmaxf, float mu, float omu) {
+                                                              int nparts, ActRange* __restrict__ rec, float qmaxf, float mu, float omu,
+                                                              int8_t* __restrict__ codes = nullptr) {
     __shared__ uint32_t red[4];
     uint32_t abits;
     if (TRACKED) {
@@ -175,26 +178,34 @@ __global__ __launch_bounds__(256) void act_quant_apply_kernel(float* __restrict_
     const ActSpan sp = act_span(x, n);
     const int gid = (int)(blockIdx.x * 256u + threadIdx.x), stride = (int)(gridDim.x * 256u);
     f32x4* xv = reinterpret_cast<f32x4*>(x + sp.head);
+    const bool packed = CODES && reinterpret_cast<uintptr_t>(codes + sp.head) % 4 == 0;
     for (int i = gid; i < sp.nv; i += stride) {
         const f32x4 v = xv[i];
-        int q;
+        int q0, q1, q2, q3;
         float y0, y1, y2, y3;
-        quant_element(v.x, s, live, qmaxf, q, y0);
-        quant_element(v.y, s, live, qmaxf, q, y1);
-        quant_element(v.z, s, live, qmaxf, q, y2);
-        quant_element(v.w, s, live, qmaxf, q, y3);
+        quant_element(v.x, s, live, qmaxf, q0, y0);
+        quant_element(v.y, s, live, qmaxf, q1, y1);
+        quant_element(v.z, s, live, qmaxf, q2, y2);
+        quant_element(v.w, s, live, qmaxf, q3, y3);
         const f32x4 y = {y0, y1, y2, y3};
         xv[i] = y;
+        if (CODES) {
+            int8_t* c = codes + sp.head + 4 * i;
+            if (packed) *reinterpret_cast<uint32_t*>(c) = pack_codes(q0, q1, q2, q3);
+            else { c[0] = (int8_t)q0; c[1] = (int8_t)q1; c[2] = (int8_t)q2; c[3] = (int8_t)q3; }
+        }
     }
     if (gid < sp.head) {
         int q; float y;
         quant_element(x[gid], s, live, qmaxf, q, y);
         x[gid] = y;
+        if (CODES) codes[gid] = (int8_t)q;
     }
     if (gid < n - sp.tail0) {
         int q; float y;
         quant_element(x[sp.tail0 + gid], s, live, qmaxf, q, y);
         x[sp.tail0 + gid] = y;
+        if (CODES) codes[sp.tail0 + gid] = (int8_t)q;
     }
 }
 
@@ -209,7 +220,7 @@ void actquant_check(const ActQuantCfg& c) {
 EmaPair actquant_rates(float momentum) { return EmaPair{momentum, (float)(1.0 - (double)momentum)}; }
 
 void launch_fake_quant_act(float* x, int64_t n, int bits, bool tracked, uint32_t* partials, ActRange* rec, float mu, float omu,
-                           hipStream_t s) {
+                           hipStream_t s, int8_t* codes) {
     CMOOP_REQUIRE(bits >= 2 && bits <= 8, "fake_quant_act: bits must be in [2, 8]");
     CMOOP_REQUIRE(n >= 0 && n <= ACT_QUANT_MAX_ELEMS, "fake_quant_act: n must stay below 2^31 elements (ACT_QUANT_MAX_ELEMS: 32-bit index math)");
     if (n == 0) return;
@@ -217,12 +228,17 @@ void launch_fake_quant_act(float* x, int64_t n, int bits, bool tracked, uint32_t
     CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(x) % 4 == 0, "fake_quant_act: x must be aligned to 4 bytes");
     const int blocks = act_quant_blocks(n);
     const float qmaxf = (float)quant_qmax(bits);
-    if (tracked) {
-        hipLaunchKernelGGL(act_quant_apply_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, (int)n, nullptr, 0, rec, qmaxf, mu, omu);
+    CMOOP_REQUIRE(!codes || tracked, "fake_quant_act: codes are written in tracked mode only");
+    if (tracked && codes) {
+        hipLaunchKernelGGL((act_quant_apply_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, (int)n, nullptr, 0, rec, qmaxf,
+                           mu, omu, codes);
+    } else if (tracked) {
+        hipLaunchKernelGGL(act_quant_apply_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, (int)n, nullptr, 0, rec, qmaxf, mu, omu,
+                           nullptr);
     } else {
         hipLaunchKernelGGL(act_absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, (int)n, partials);
         hipLaunchKernelGGL(act_quant_apply_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, x, (int)n, partials, blocks, rec, qmaxf, mu,
-                           omu);
+                           omu, nullptr);
     }
     CMOOP_HIP(hipGetLastError());
 }

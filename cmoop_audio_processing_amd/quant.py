@@ -17,6 +17,10 @@ the statement the kernel is tested against; no accuracy figure is measured or cl
 channel that spans a whole activation tensor, at the operand tensors of every MAC layer and of the global pool.  Train steps
 take the batch's own absmax (never clips) and track it with a momentum; inference takes the tracked range (clips).
 ``fake_quant_act_ref`` / ``act_range_update_ref`` / ``act_sites`` are its numpy statements.
+
+Integer inference (``NetSession.set_int8``; ``include/cmoop.h``, "Integer inference") executes a model trained under both: the
+conv and dense layers whose input is a site multiply int8 codes, accumulate exactly in int32 and dequantise once per output.
+``conv_i8_ref`` / ``dense_i8_ref`` / ``act_codes_ref`` / ``int8_ops`` are its numpy statements.
 """
 from __future__ import annotations
 
@@ -162,6 +166,138 @@ def fake_quant_act_ref(x, bits: int, a=None):
         a = np.asarray([a], np.float32)
     _s, _q, y = _quant_elements(flat, a, bits)
     return a[0], y.reshape(x.shape)
+
+
+def act_codes_ref(x, bits: int, a):
+    """The codes of ``fake_quant_act_ref`` in tracked mode under the range ``a``: int8 in the shape of ``x``, with
+    ``float32(codes) * s == fake_quant_act_ref(x, bits, a)[1]`` bit for bit, ``s = act_scale_ref(a, bits)``."""
+    x = np.ascontiguousarray(x, np.float32)
+    _s, q, _y = _quant_elements(x.reshape(1, -1), np.asarray([a], np.float32), bits)
+    return q.reshape(x.shape)
+
+
+def act_scale_ref(a, bits: int):
+    """``s_x = a / float32(qmax)``: the tracked-mode scale of a site with range ``a`` (a NaN as 0x7FC00000)."""
+    s = np.asarray([a], np.float32)
+    with np.errstate(all="ignore"):
+        s = (s / np.float32(qmax_of(bits))).astype(np.float32)
+    s.view(np.uint32)[np.isnan(s)] = CANONICAL_NAN
+    return s[0]
+
+
+# ---- integer inference (include/cmoop.h fixes the arithmetic at "Integer inference") ------------------------------------
+def i8_epilogue_ref(acc, s_x, s_w, bias, relu):
+    """``fl(fl(float32(acc) * fl(s_x * s_w[c])) + bias[c])``, then ``max(y, 0)``: acc int64 [..., C], one IEEE single operation
+    per line.  The ReLU is the fp32 epilogues' fmaxf(y, 0): a NaN becomes 0 and a zero result is +0.0."""
+    f = np.float32
+    acc = np.asarray(acc, np.int64)
+    if acc.size and int(np.abs(acc).max()) >= 2 ** 31:
+        raise ValueError("an accumulator left int32")
+    with np.errstate(all="ignore"):
+        sc = (f(s_x) * np.asarray(s_w, f)).astype(f)
+        y = (acc.astype(np.int32).astype(f) * sc).astype(f)            # int32 -> float32 rounds to nearest even
+        y = (y + np.asarray(bias, f)).astype(f)
+        if relu:
+            y = np.where(y > 0, y, f(0)).astype(f)
+    return y
+
+
+def conv_i8_acc(qx, qw, KS: int, stride: int) -> np.ndarray:
+    """The exact accumulators of ``conv_i8_ref``, int64 [B, OH, OW, Cout] (of absolute codes: the sum a rounding bound scales)."""
+    qx = np.asarray(qx, np.int8)
+    B, H, W, Cin = qx.shape
+    qw = np.asarray(qw, np.int8).reshape(-1, KS, KS, Cin)
+    Cout = qw.shape[0]
+    OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
+    pt, pl = max((OH - 1) * stride + KS - H, 0) // 2, max((OW - 1) * stride + KS - W, 0) // 2
+    xp = np.zeros((B, max((OH - 1) * stride + KS, pt + H), max((OW - 1) * stride + KS, pl + W), Cin), np.int64)
+    xp[:, pt:pt + H, pl:pl + W] = qx
+    acc = np.zeros((B, OH, OW, Cout), np.int64)
+    for kh in range(KS):
+        for kw in range(KS):
+            win = xp[:, kh:kh + (OH - 1) * stride + 1:stride, kw:kw + (OW - 1) * stride + 1:stride]
+            acc += win.reshape(-1, Cin).dot(qw[:, kh, kw].astype(np.int64).T).reshape(B, OH, OW, Cout)
+    return acc
+
+
+def conv_i8_ref(qx, qw, s_x, s_w, bias, KS: int, stride: int, relu) -> np.ndarray:
+    """The integer conv layer restated: ``qx`` int8 [B, H, W, Cin], ``qw`` int8 [Cout, KS, KS, Cin] (or [Cout, KS*KS*Cin]),
+    ``s_w`` / ``bias`` float32 [Cout] -> float32 [B, ceil(H/stride), ceil(W/stride), Cout].  SAME padding (TF: total // 2 on
+    the top / left) contributes 0; the sum is exact (int64), the epilogue float32."""
+    return i8_epilogue_ref(conv_i8_acc(qx, qw, KS, stride), s_x, s_w, bias, relu)
+
+
+def dense_i8_ref(qx, qw, s_x, s_w, bias, relu) -> np.ndarray:
+    """The integer dense layer restated: ``qx`` int8 [M, K], ``qw`` int8 [N, K] -> float32 [M, N]."""
+    acc = np.asarray(qx, np.int8).astype(np.int64).dot(np.asarray(qw, np.int8).astype(np.int64).T)
+    return i8_epilogue_ref(acc, s_x, s_w, bias, relu)
+
+
+INT8_OP_FIELDS = ("op", "kind", "in_act", "out_act", "site", "H", "W", "Cin", "Cout", "KS", "stride", "relu", "w_off", "b_off",
+                  "scale_off")
+
+
+def int8_ops(hparams, variant, classes: int, T: int, F: int) -> List[Tuple[int, int, int]]:
+    """[(op index, input act, output act)] of the ops that run integer under ``NetSession.set_int8``, the rule restated on
+    ``act_plan``: every conv / dense op whose input is an activation-quantisation site.  The twin of ``cmoop_int8_ops``."""
+    _acts, ops, _logits = act_plan(hparams, variant, classes, T, F)
+    sites = {s[0] for s in act_sites(hparams, variant, classes, T, F)}
+    return [(i, op[1], op[3]) for i, op in enumerate(ops) if op[0] in ("conv", "dense") and op[1] in sites]
+
+
+def _int8_rows(rows, n):
+    return [dict(zip(INT8_OP_FIELDS, (int(v) for v in r))) for r in rows[:n]]
+
+
+def c_int8_ops(gene, variant: int, classes: int, T: int, F: int):
+    """``cmoop_int8_ops``: a list of dicts keyed by ``INT8_OP_FIELDS`` (kind 0: conv, 1: dense)."""
+    g, cap = (C.c_int32 * 6)(*(int(v) for v in gene)), 64
+    rows, n = np.zeros((cap, 16), np.int64), C.c_int32()
+    _lib.check(_lib.lib().cmoop_int8_ops(g, C.c_int32(int(variant)), C.c_int32(int(classes)), C.c_int32(int(T)), C.c_int32(int(F)),
+                                         _lib.ptr(rows), C.c_int32(cap), C.byref(n)))
+    return _int8_rows(rows, n.value)
+
+
+def _dev_ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def conv_fwd_i8(xq, wq, s_x, s_w, bias, y, B, H, W, Cin, Cout, KS, stride, relu) -> None:
+    """``cmoop_conv_fwd_i8``: the lone integer conv layer.  ``xq`` / ``wq`` CUDA int8 (16-byte aligned views), ``s_w`` /
+    ``bias`` / ``y`` CUDA float32."""
+    import torch
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_conv_fwd_i8(_dev_ptr(xq), _dev_ptr(wq), C.c_float(float(s_x)), _dev_ptr(s_w), _dev_ptr(bias), _dev_ptr(y),
+                                            *(C.c_int32(int(v)) for v in (B, H, W, Cin, Cout, KS, stride, relu))))
+
+
+def dense_fwd_i8(xq, wq, s_x, s_w, bias, y, M, N, K, relu) -> None:
+    """``cmoop_dense_fwd_i8``: the lone integer dense layer."""
+    import torch
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_dense_fwd_i8(_dev_ptr(xq), _dev_ptr(wq), C.c_float(float(s_x)), _dev_ptr(s_w), _dev_ptr(bias), _dev_ptr(y),
+                                             *(C.c_int32(int(v)) for v in (M, N, K, relu))))
+
+
+def conv_fwd_i8_time(xq, wq, s_x, s_w, bias, y, B, H, W, Cin, Cout, KS, stride, relu, iters: int = 50) -> float:
+    """``cmoop_conv_fwd_i8_time``: average milliseconds of the launch."""
+    import torch
+    ms = C.c_double()
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_conv_fwd_i8_time(_dev_ptr(xq), _dev_ptr(wq), C.c_float(float(s_x)), _dev_ptr(s_w), _dev_ptr(bias),
+                                                 _dev_ptr(y), *(C.c_int32(int(v)) for v in (B, H, W, Cin, Cout, KS, stride, relu, iters)),
+                                                 C.byref(ms)))
+    return float(ms.value)
+
+
+def fake_quant_act_codes(x, bits: int, a, codes=None) -> None:
+    """``cmoop_fake_quant_act_codes``: tracked mode under ``a`` in place on ``x`` (CUDA float32), the codes into ``codes`` (CUDA
+    int8 of as many elements, or None: the plain tracked launch)."""
+    import torch
+    a_in = C.c_float(float(a))
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_fake_quant_act_codes(C.c_void_p(x.data_ptr()), C.c_int64(int(x.numel())), C.c_int32(int(bits)),
+                                                     C.byref(a_in), _dev_ptr(codes)))
 
 
 def act_momentum_pair(momentum):

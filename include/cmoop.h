@@ -602,8 +602,8 @@ int cmoop_eval_population_p(const cmoop_config* cfg, const cmoop_augment* aug, c
  *     (absmax partials; fold + quantise + record), one per site per inference chunk.
  *   GAPS: the first layer reads the resident feature tensor, which stays untouched; the operands of the residual add + ReLU stay
  *     fp32.  Symmetric signed ranges cost one bit on ReLU outputs.  Asymmetric or unsigned ranges, per-channel activation scales,
- *     learned clipping, a quantiser fused into the producers' epilogues, BatchNorm folding and an integer inference engine are out
- *     of scope.  It composes with the bf16 gemm modes, untested.
+ *     learned clipping, a quantiser fused into the producers' epilogues and BatchNorm folding are out of scope (the conv and dense
+ *     layers can be executed on int8 codes: "Integer inference" below).  It composes with the bf16 gemm modes, untested.
  *   The backward pass is not changed.  Weight gradients are formed with the quantised operands.  The x > 0 masks the dgrad / pool
  *     / GAP kernels already take from the layer input now read quantised values, so an element that rounds to code 0 passes no
  *     gradient, exactly as the integer model's ReLU would see it.  Everything else is straight-through.
@@ -638,6 +638,51 @@ int cmoop_fake_quant_act(float* x_dev, int64_t n, int32_t bits, const float* a_i
 /* average milliseconds of that call's launches (two in batch mode, one in tracked mode) over `iters` back-to-back repetitions
  * between two HIP events on the library stream, after 3 warm-up repetitions */
 int cmoop_fake_quant_act_time(float* x_dev, int64_t n, int32_t bits, const float* a_in, float momentum, int32_t iters, double* avg_ms);
+
+/* ---- Integer inference (opt-in, BUILD-DEFINED; off by default) ---------------------------------------------------------------------
+ * THE arithmetic of an integer layer (quant.py restates it in numpy: conv_i8_ref / dense_i8_ref / act_codes_ref).  A model trained
+ * under cmoop_quant and cmoop_actquant has int8 weight codes qw with one scale s_w[c] per output channel (the value the weight
+ * quantiser stores) and, per site, int8 activation codes qx under the tracked-mode scale s_x = r / (float)qmax_act (the scale the
+ * tracked apply kernel forms from the site's record).  For a conv / dense layer whose input is a site:
+ *     acc[m][c] = sum over (kh, kw, ci) of (int32) qx[pixel(m, kh, kw)][ci] * (int32) qw[c][kh][kw][ci]     exact, in int32;
+ *                 a tap in the SAME padding contributes 0
+ *     y[m][c]   = fl( fl( (float)acc[m][c] * fl(s_x * s_w[c]) ) + bias[c] )                                  then ReLU if the op has it
+ *   (float)acc is the correctly rounded int32 -> fp32 conversion (round to nearest even): accumulators above 2^24 occur and round
+ *   there, which is part of the definition.  Every fl() is ONE correctly rounded fp32 operation, contraction off (no fma), so
+ *   np.float32 arithmetic restates it bit for bit.  |acc| <= 127 * 127 * K must stay below 2^31: it does for every layer of the
+ *   search space (K <= 12800: 512 -> 512, k5), and a launch asserts it from the shape.  The ReLU is the fp32 conv and dense
+ *   epilogues' max(y, 0) (fmaxf): a NaN becomes 0 and a zero result is +0.0.  A scale of 0 (an all-zero channel or site: s > 0
+ *   false) is legal, its codes are 0 and y = bias.
+ * In a net (cmoop_net_set_int8) every OP_CONV and OP_DENSE whose input is an activation-quantisation site runs this way
+ *   (cmoop_int8_ops): stride-1 convs, pointwise halves, the 1x1 stride-2 skip projections and every dense layer.  Everything else is
+ *   launch for launch what it was: the first convolution (its input is no site), depthwise convolutions and the global pool (they
+ *   keep reading the fp32 site tensor, which stays written), BatchNorm, pooling, add + ReLU, and every train step.  gemm_mode is
+ *   ignored by integer ops.  Weights come through the existing weight stage (snapshots, EMA, cmoop_net_use_ema and pruning compose).
+ * Kernels (int8.hip): implicit GEMM on v_mfma_i32_16x16x64_i8, Cin a multiple of 16, KS 1 / 3 / 5 at stride 1 or the 1x1 stride-2
+ *   projection; 16-byte code loads, so code buffers must be 16-byte aligned.  No split-K, no atomics.
+ * OUT OF SCOPE: integer BatchNorm / pool / add / GAP / depthwise, BatchNorm folding, int8 outputs between layers, asymmetric or
+ *   per-channel activation scales, training on integer kernels, the population objectives. */
+/* the lone conv layer on the library stream: y_dev [B][ceil(H/stride)][ceil(W/stride)][Cout] fp32 from xq_dev [B][H][W][Cin] and
+ * wq_dev [Cout][KS][KS][Cin] int8 codes (16-byte aligned), s_w_dev / bias_dev [Cout].  B == 0: success, nothing written */
+int cmoop_conv_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
+                      int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t relu);
+/* the lone dense layer: y_dev [M][N] from xq_dev [M][K] and wq_dev [N][K]; K a multiple of 16, any N.  M == 0: success, nothing written */
+int cmoop_dense_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
+                       int32_t M, int32_t N, int32_t K, int32_t relu);
+/* average milliseconds of cmoop_conv_fwd_i8's launch over `iters` back-to-back repetitions between two HIP events on the library
+ * stream, after 3 warm-up repetitions */
+int cmoop_conv_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
+                           int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t relu,
+                           int32_t iters, double* avg_ms);
+/* cmoop_fake_quant_act in tracked mode (a_in required) with the codes output: codes_dev [n] int8 receives the code of every element
+ * next to the fp32 value in x_dev.  codes_dev NULL: cmoop_fake_quant_act's launch and bytes */
+int cmoop_fake_quant_act_codes(float* x_dev, int64_t n, int32_t bits, const float* a_in, int8_t* codes_dev);
+/* host-only: the ops of a candidate at a T x F patch that run integer under cmoop_net_set_int8, in op order: rows [count][16] =
+ * {op index, kind (0 conv, 1 dense), input act, output act, input site, H, W, Cin, Cout, KS, stride, relu, w_off, b_off (offsets
+ * into the parameter arena), scale_off (first scale of the tensor in cmoop_net_get_quantized's scales), 0}.  An error when cap is
+ * too small, or when such an op is beyond the kernels (Cin % 16, w_off % 16, 127^2 K < 2^31); count may be NULL */
+int cmoop_int8_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows /* [cap][16] */,
+                   int32_t cap, int32_t* count);
 /* the population call (above) with every argument: the other ten forward here.  aq NULL or disabled: cmoop_eval_population_p's
  * launches and bytes */
 int cmoop_eval_population_aq(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
@@ -968,6 +1013,17 @@ int cmoop_net_get_act_ranges(cmoop_net* net, cmoop_act_range* host, int32_t cap,
 /* loads the site records (count must be the number of sites; every count >= 0, no negative r or m_b).  When every record has
  * count > 0, inference is possible from here on. */
 int cmoop_net_set_act_ranges(cmoop_net* net, const cmoop_act_range* host, int32_t count);
+/* Integer inference ("Integer inference" above) of every following inference call of this net; train steps never take it.  on != 0
+ * is refused, with a message, before anything is launched and with the net unchanged, unless cmoop_net_set_quant and
+ * cmoop_net_set_actquant are both on and the ranges are ready; and when a tracked r or a weight scale, read on the host here, is
+ * not finite.  The weight-code arena, the scale buffer and one int8 buffer per site (max(batch, eval_batch) samples) are allocated
+ * on first use.  on == 0: off, and every launch and byte is that of a net that never had it.  Turning cmoop_net_set_quant or
+ * cmoop_net_set_actquant off turns it off as well.  Finiteness is checked HERE and by cmoop_net_set_act_ranges while the mode is
+ * on (a non-finite r is then an error and nothing is loaded), not per pass: a train step or cmoop_net_set_params that later
+ * yields a NaN or Inf range or scale is not caught, and integer passes then return NaN logits without a fault, as fp32 passes do. */
+int cmoop_net_set_int8(cmoop_net* net, int32_t on);
+/* cmoop_int8_ops of this net's plan (host arithmetic; the mode need not be on) */
+int cmoop_net_int8_ops(cmoop_net* net, int64_t* rows /* [cap][16] */, int32_t cap, int32_t* count);
 /* debug read-out of act index i of the plan: dims (may be NULL) = {H, W, C, 1 if materialised, 1 if it has a gradient buffer,
  * the number of acts}; data_host / grad_host (either may be NULL; both NULL: dims only) receive the first B rows of the data and
  * of the gradient as the last step or pass left them.  An error for an act that is never materialised. */
