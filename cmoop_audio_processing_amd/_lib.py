@@ -330,6 +330,11 @@ INT8_PROTOTYPES = {
     "cmoop_net_int8_ops": [_V, _V, _I32, _V],
 }
 
+#: prototype of the train-step launch counters (include/cmoop.h)
+STEP_PROTOTYPES = {
+    "cmoop_step_launch_counts": [_V],
+}
+
 #: CMOOP_GEMM_* (include/cmoop.h)
 GEMM_DEFAULT, GEMM_FP32, GEMM_BF16X3, GEMM_BF16 = 0, 1, 2, 3
 
@@ -374,7 +379,7 @@ def lib():
         L.cmoop_config_default.restype = None
         for table in (STREAM_PROTOTYPES, AUGMENT_PROTOTYPES, PCEN_PROTOTYPES, ELEM_PROTOTYPES, LOSS_PROTOTYPES, DENSE_PROTOTYPES,
                       DWCONV_PROTOTYPES, DISTILL_PROTOTYPES, OPTIM_PROTOTYPES, EMA_PROTOTYPES, OPOINT_PROTOTYPES, QUANT_PROTOTYPES,
-                      PRUNE_PROTOTYPES, ACTQUANT_PROTOTYPES, RESAMPLE_PROTOTYPES, INT8_PROTOTYPES):
+                      PRUNE_PROTOTYPES, ACTQUANT_PROTOTYPES, RESAMPLE_PROTOTYPES, INT8_PROTOTYPES, STEP_PROTOTYPES):
             for name, argtypes in table.items():
                 getattr(L, name).argtypes = argtypes
         _lib = L
@@ -384,6 +389,14 @@ def lib():
 def check(rc: int) -> None:
     if rc != 0:
         raise CmoopError(lib().cmoop_last_error().decode("utf-8", "replace"))
+
+
+def step_launch_counts() -> dict:
+    """Process-wide totals since load of the fit loop's train steps (cmoop_step_launch_counts): launched eagerly, replayed from
+    a captured graph (CMOOP_GRAPH=1), captures made, captures dropped.  Host only."""
+    out = (C.c_int64 * 4)()
+    check(lib().cmoop_step_launch_counts(out))
+    return {"eager": int(out[0]), "replays": int(out[1]), "captures": int(out[2]), "drops": int(out[3])}
 
 
 def default_config() -> Config:

@@ -1776,10 +1776,15 @@ int cmoop_net_set_gather_rows(cmoop_net* h, int64_t n_rows) {
 int cmoop_net_run_epoch(cmoop_net* h, const float* x, const int32_t* y, int64_t n_train, int32_t epoch) {
     return guard([&] {
         CMOOP_REQUIRE(x && y && n_train >= 1, "run_epoch: NULL / empty training split");
-        PoolScope pool(h->net->stream());
-        h->net->run_epoch(x, y, n_train, epoch, pool.get<int32_t>((size_t)n_train * 4));
+        h->net->run_epoch(x, y, n_train, epoch);
         CMOOP_HIP(hipStreamSynchronize(h->net->stream()));
         h->net->drain_profile();
+    });
+}
+int cmoop_step_launch_counts(int64_t out[4]) {
+    return guard([&] {
+        CMOOP_REQUIRE(out, "step_launch_counts: NULL output");
+        step_launch_counts(out);
     });
 }
 int cmoop_net_fit(cmoop_net* h, const cmoop_dataset* ds, int32_t hist_cap, double* val_loss_hist, double* val_acc_hist,

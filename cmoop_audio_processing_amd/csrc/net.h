@@ -248,6 +248,26 @@ struct TrainOptions {
     const ActQuantCfg* actq = nullptr;
 };
 
+// What a captured train step (CMOOP_GRAPH=1, Net::train_step_stateful) froze and a later call can change under it;
+// Net::capture_key fills it and lists why each field is there
+struct StepCaptureKey {
+    const float* X = nullptr;
+    const int32_t* y = nullptr;
+    const int32_t* idx = nullptr;
+    int64_t gather_rows = 0;
+    const float* alpha_tab = nullptr;
+    const float* kd_zt = nullptr;
+    int64_t kd_rows = 0;
+    int env_knobs = 0;
+    bool operator==(const StepCaptureKey& o) const {
+        return X == o.X && y == o.y && idx == o.idx && gather_rows == o.gather_rows && alpha_tab == o.alpha_tab && kd_zt == o.kd_zt &&
+               kd_rows == o.kd_rows && env_knobs == o.env_knobs;
+    }
+};
+// process-wide totals since load of Net::train_step_stateful: {steps launched eagerly, steps replayed from a captured graph,
+// captures made, captures dropped while their net lived}.  Host only: launches nothing, allocates nothing
+void step_launch_counts(int64_t out[4]);
+
 class Net : public GemmHook {
   public:
     const GemmTiming* begin(int cls, double flops) override;
@@ -391,8 +411,9 @@ class Net : public GemmHook {
     // with distillation on, n must be the rows of the teacher table: refused here, before any step is enqueued
     void set_gather_rows(int64_t n);
     // ONE epoch of Model.fit on the production path (device permutation of (seed, epoch) when cfg.shuffle, device
-    // StepState steps, last partial batch kept); idx_scratch: n_train int32 on the device
-    void run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch, int32_t* idx_scratch);
+    // StepState steps, last partial batch kept).  The permutation goes into a buffer of the net, which stays where it is from
+    // epoch to epoch (a captured step keeps reading it) and grows when a longer split comes
+    void run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch);
 
     // fwd + bwd + Adam on rows idx[row0 .. row0+B) (idx may be null -> rows row0..)
     void train_step(const float* X, const int32_t* y, const int32_t* idx, int64_t row0, int B);
@@ -407,6 +428,14 @@ class Net : public GemmHook {
     // The fit loop's form of the same step: the batch position, dropout counter and Adam iteration live in a device
     // StepState (kernels.h), so a full-batch step has no per-step host arguments; with CMOOP_GRAPH=1 it is captured ONCE
     // as a hipGraph and replayed (opt-in: measured no faster than eager launches, see begin_fit).
+    // A capture freezes every host-side argument of the step's launches.  What of that can change while the net lives is in
+    // StepCaptureKey (above; capture_key in net.hip is the complete list): the caller's X / y / idx, the split length, the
+    // step-size table, the teacher table and the per-step environment knobs.  train_step_stateful compares the key before
+    // every replay; a mismatch drops the capture and the same step captures again.  Every option setter and set_state drop
+    // it too (option_changed), and so does a re-entered begin_fit, which also gives the previous tables back to the pool.
+    // Steps that are never captured or replayed: step 0, partial batches, profiled steps, and every step of a net with an
+    // AdamW / clipping optimiser, EMA, weight or activation quantisation or pruning on.  step_launch_counts() says which
+    // of these happened.
     void begin_fit(int64_t total_steps);      // uploads Adam's per-iteration step sizes, sets the device state to (0, step, iterations)
     void begin_epoch();                       // state.row0 = 0
     void train_step_stateful(const float* X, const int32_t* y, const int32_t* idx, int B);
@@ -449,6 +478,9 @@ class Net : public GemmHook {
     void upload_rate_tables();                          // alpha_tab_ (and, on the finish + update path, lr_tab_) from optim_rates; ema_tab_ from ema_rates
     void ensure_kinds();                                // kinds_dev_, uploaded once (set_optim's finish path and set_ema share it)
     void option_changed(bool breaks_graph);             // every setter's tail: the captured step is stale; breaks_graph: and none is captured again
+    void require_step_allowed(bool gather) const;       // the whole-step refusals, before anything is enqueued: step_body's first lines, and in front of every replay
+    StepCaptureKey capture_key(const float* X, const int32_t* y, const int32_t* idx) const;   // what a capture made now would freeze
+    void dfree(void* p);                                // a dalloc'd buffer back to the pool (the caller has drained the stream); null: no-op
     void upload_step_state();                           // enqueues the device StepState at (0, step_, iterations_); no-op without one
     void ensure_target_buffers();                       // t / w / primary, allocated by the first enabled set_loss or set_distill
     void ensure_quant_table();                          // qtab_ from the plan, once (host only)
@@ -538,7 +570,10 @@ class Net : public GemmHook {
     int optim_last_path_ = 0;
     int64_t alpha_tab_n_ = 0, host_row0_ = 0, gather_rows_ = 0;
     hipGraphExec_t graph_exec_ = nullptr;   // the captured full-batch train step
+    StepCaptureKey graph_key_;              // what graph_exec_ froze; compared before every replay
     bool graph_ok_ = true;
+    int32_t* epoch_idx_ = nullptr;          // run_epoch's permutation buffer, grown on demand
+    int64_t epoch_idx_n_ = 0;
     FlipEntry* flip_table_ = nullptr;   // device table of the conv layers whose dgrad needs flip-transposed weights
     int flip_layers_ = 0;
     int64_t flip_max_elems_ = 0;

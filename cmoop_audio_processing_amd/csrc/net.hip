@@ -212,6 +212,10 @@ void pool_free(void* p) { pool(false).put(p); }
 void* pool_alloc_pinned(size_t bytes) { return pool(true).get(bytes); }
 void pool_free_pinned(void* p) { pool(true).put(p); }
 
+// step_launch_counts: what train_step_stateful did, over every net of the process (the population path steps from several threads)
+enum { STEP_COUNT_EAGER = 0, STEP_COUNT_REPLAYS = 1, STEP_COUNT_CAPTURES = 2, STEP_COUNT_DROPS = 3 };
+static std::atomic<int64_t> g_step_counts[4];
+
 float* Net::dalloc(size_t floats) {
     void* p = pool_alloc(std::max<size_t>(floats, 4) * sizeof(float));
     allocs_.push_back(p);
@@ -1065,11 +1069,15 @@ const float* Net::stage_kernels(double sparsity, float* wp, uint32_t* zeros, flo
     return src;
 }
 
-template <class Loss> void Net::step_body(const float* X, const BatchRows& rows, int B, bool gather, Loss&& loss) {
+void Net::require_step_allowed(bool gather) const {
     CMOOP_REQUIRE(params_ == weights_, "train step while inference reads the average: use_average(false) first");
     // before anything is enqueued: a teacher table of another length than the split the step gathers from is refused whole
     CMOOP_REQUIRE(!gather || !distill_on_ || gather_rows_ == 0 || gather_rows_ == kd_rows_, "distill: the teacher table has " +
                   std::to_string(kd_rows_) + " rows, the training split " + std::to_string(gather_rows_));
+}
+
+template <class Loss> void Net::step_body(const float* X, const BatchRows& rows, int B, bool gather, Loss&& loss) {
+    require_step_allowed(gather);
     refresh_kernels(prune_sparsity_at(prune_cfg_, iterations_));   // the step's first launches, on the latent weights of this moment
     batch_in_ = nullptr;
     if (gather) {
@@ -1206,10 +1214,17 @@ void Net::train_step_distill_targets(const float* x_rows, const float* t, const 
 void Net::begin_fit(int64_t total_steps) {
     // total_steps counts from optimizer.iterations == 0; a net that has already trained (session API: state loaded with
     // set_state, or earlier epochs) continues from its own counters
+    if (alpha_tab_ || graph_exec_) {
+        // re-entered (a second fit, or run_epoch past the budget): a kept capture would go on reading the previous, shorter
+        // table.  It is dropped, and once nothing queued reads them the previous tables go back to the pool: a net holds one set
+        CMOOP_HIP(hipStreamSynchronize(stream_));
+        option_changed(false);
+        dfree(alpha_tab_); dfree(lr_tab_); dfree(ema_tab_);
+        alpha_tab_ = nullptr; lr_tab_ = nullptr; ema_tab_ = nullptr;
+        alpha_tab_n_ = 0;
+    }
     if (total_steps < 1 || total_steps > (1ll << 24)) { graph_ok_ = false; st_dev_ = nullptr; return; }   // explicit-argument steps beyond 16 M iterations
     alpha_tab_ = dalloc(total_steps);
-    lr_tab_ = nullptr;
-    ema_tab_ = nullptr;
     alpha_tab_n_ = total_steps;
     if (!st_dev_) st_dev_ = reinterpret_cast<StepState*>(dalloc(8));
     upload_rate_tables();
@@ -1248,7 +1263,50 @@ void Net::upload_rate_tables() {
 
 void Net::option_changed(bool breaks_graph) {
     if (breaks_graph) graph_ok_ = false;          // nothing is promised under CMOOP_GRAPH=1
-    if (graph_exec_) { hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
+    if (graph_exec_) {
+        hipGraphExecDestroy(graph_exec_);
+        graph_exec_ = nullptr;
+        g_step_counts[STEP_COUNT_DROPS].fetch_add(1, std::memory_order_relaxed);
+    }
+    graph_key_ = StepCaptureKey();
+}
+
+void step_launch_counts(int64_t out[4]) {
+    for (int i = 0; i < 4; ++i) out[i] = g_step_counts[i].load(std::memory_order_relaxed);
+}
+
+void Net::dfree(void* p) {
+    if (!p) return;
+    auto it = std::find(allocs_.begin(), allocs_.end(), p);
+    CMOOP_REQUIRE(it != allocs_.end(), "dfree: not a buffer of this net");
+    allocs_.erase(it);
+    pool_free(p);
+}
+
+// THE list of what a captured step depends on beyond the net's own buffers and options.  The net's buffers (arenas, acts,
+// workspaces, st_dev_, the option buffers) are allocated once and live as long as the net; every option a launch reads
+// (augment, loss, distill, optimiser, EMA, quantisation, pruning, the loaded state) is changed only by a setter, and every
+// setter ends in option_changed, which drops the capture.  What is left is what callers hand in per call and what
+// begin_fit / run_epoch replace:
+//   X, y          the resident training tensors: by value in the gather, first-layer, loss and wgrad launches
+//   idx           the epoch's permutation buffer (null: shuffle off): a fit's pooled buffer or run_epoch's own
+//   gather_rows   gather_rows_, the clamp of every gather launch (set_gather_rows does not drop the capture: the key does)
+//   alpha_tab     the step-size table the Adam launch indexes with st->iter; a re-entered begin_fit replaces it
+//   kd_zt/kd_rows the caller's teacher table and its clamp (set_distill drops the capture too)
+//   env_knobs     CMOOP_ADAM_UNFUSED and CMOOP_DENSE_UNFUSED, which choose launches per step and which tests flip
+// A launch argument that can change without passing through here or through option_changed is a bug in this list.
+static int step_env_knobs() {
+    const char* du = std::getenv("CMOOP_DENSE_UNFUSED");
+    return (std::getenv("CMOOP_ADAM_UNFUSED") != nullptr ? 1 : 0) | (du && du[0] == '1' ? 2 : 0);
+}
+StepCaptureKey Net::capture_key(const float* X, const int32_t* y, const int32_t* idx) const {
+    StepCaptureKey k;
+    k.X = X; k.y = y; k.idx = idx;
+    k.gather_rows = gather_rows_;
+    k.alpha_tab = alpha_tab_;
+    k.kd_zt = kd_zt_; k.kd_rows = kd_rows_;
+    k.env_knobs = step_env_knobs();
+    return k;
 }
 
 void Net::upload_step_state() {
@@ -1584,12 +1642,21 @@ void Net::train_step_stateful(const float* X, const int32_t* y, const int32_t* i
     if (!st_dev_) {   // no device state (step budget beyond the table limit): explicit-argument steps
         train_step(X, y, idx, host_row0_, B);
         host_row0_ += B;
+        g_step_counts[STEP_COUNT_EAGER].fetch_add(1, std::memory_order_relaxed);
         return;
     }
     CMOOP_REQUIRE(iterations_ < alpha_tab_n_, "train_step_stateful outside begin_fit's step budget");
     const BatchRows rows{idx, 0, gather_rows_, st_dev_};
     counted_step([&] {
-        if (graph_ok_ && B == cfg_.batch && !profiling_now_ && step_ >= 1) {
+        // EMA (like the other options begin_fit lists) stays out of captures: graph_ok_ is false for good once one was on
+        if (graph_ok_ && !ema_on_ && B == cfg_.batch && !profiling_now_ && step_ >= 1) {
+            // a replay runs none of step_body's host code: what it refuses is refused here, whatever a capture holds
+            require_step_allowed(true);
+            const StepCaptureKey key = capture_key(X, y, idx);
+            if (graph_exec_ && !(key == graph_key_)) {   // the capture froze other arguments than this call's: it is stale
+                CMOOP_HIP(hipStreamSynchronize(stream_));   // its earlier replays have finished before it is destroyed
+                option_changed(false);
+            }
             if (!graph_exec_) {   // capture the step once (thread-local mode: the other candidates' threads keep launching)
                 hipGraph_t graph = nullptr;
                 bool ok = hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal) == hipSuccess;
@@ -1608,15 +1675,20 @@ void Net::train_step_stateful(const float* X, const int32_t* y, const int32_t* i
                 if (!ok) {
                     (void)hipGetLastError();
                     graph_exec_ = nullptr;
-                    graph_ok_ = false;      // fall back to eager steps for this candidate
+                    graph_ok_ = false;      // fall back to eager steps for this candidate (step_launch_counts shows it: no capture, no replay)
+                } else {
+                    graph_key_ = key;
+                    g_step_counts[STEP_COUNT_CAPTURES].fetch_add(1, std::memory_order_relaxed);
                 }
             }
             if (graph_exec_) {
                 CMOOP_HIP(hipGraphLaunch(graph_exec_, stream_));
+                g_step_counts[STEP_COUNT_REPLAYS].fetch_add(1, std::memory_order_relaxed);
                 return;
             }
         }
         gathered_step(X, y, rows, B);
+        g_step_counts[STEP_COUNT_EAGER].fetch_add(1, std::memory_order_relaxed);
     });
 }
 
@@ -1721,7 +1793,7 @@ void Net::loss_buffers(int64_t out[4]) const {
     out[3] = tgt_primary_ ? (int64_t)cfg_.batch : 0;
 }
 
-void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch, int32_t* idx_scratch) {
+void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch) {
     CMOOP_REQUIRE(n_train >= 1 && n_train < (1ll << 31) && epoch >= 0, "run_epoch: bad arguments");
     const int64_t spe = (n_train + cfg_.batch - 1) / cfg_.batch;
     // the device StepState / step-size table of the fit loop, (re)built when this epoch runs past what is there
@@ -1730,16 +1802,24 @@ void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch
     set_gather_rows(n_train);
     const int32_t* idx = nullptr;
     if (cfg_.shuffle) {
-        CMOOP_REQUIRE(idx_scratch != nullptr, "run_epoch: shuffle needs an index buffer");
+        // the permutation lives in a buffer of the net, at the same address every epoch, so a captured step stays valid
+        // across epochs (a pooled buffer per call moves: the pool hands equal-sized blocks out oldest first)
+        if (n_train > epoch_idx_n_) {
+            CMOOP_HIP(hipStreamSynchronize(stream_));   // nothing queued still reads the shorter one
+            dfree(epoch_idx_);
+            epoch_idx_ = nullptr; epoch_idx_n_ = 0;
+            epoch_idx_ = reinterpret_cast<int32_t*>(dalloc((size_t)n_train));
+            epoch_idx_n_ = n_train;
+        }
         if (n_train <= EPOCH_PERMUTATION_DEVICE_MAX) {
-            launch_epoch_permutation(seed_, (uint32_t)epoch, n_train, idx_scratch, stream_);
+            launch_epoch_permutation(seed_, (uint32_t)epoch, n_train, epoch_idx_, stream_);
         } else {
             std::vector<int32_t> h(n_train);
             epoch_permutation(seed_, (uint32_t)epoch, n_train, h.data());
-            CMOOP_HIP(hipMemcpyAsync(idx_scratch, h.data(), n_train * 4, hipMemcpyHostToDevice, stream_));
+            CMOOP_HIP(hipMemcpyAsync(epoch_idx_, h.data(), n_train * 4, hipMemcpyHostToDevice, stream_));
             CMOOP_HIP(hipStreamSynchronize(stream_));
         }
-        idx = idx_scratch;
+        idx = epoch_idx_;
     }
     if (st_dev_) {   // explicit-argument steps (session API) do not advance the device state: start the epoch from the host's counters
         upload_step_state();

@@ -1040,6 +1040,16 @@ int cmoop_net_set_gather_rows(cmoop_net* net, int64_t n_rows);
 /* ONE epoch of Model.fit on the trainer's own path: epoch permutation of (seed, epoch) computed on the device when
  * cfg.shuffle, ceil(n_train / batch) steps driven by the device-resident step state, last partial batch kept. */
 int cmoop_net_run_epoch(cmoop_net* net, const float* x_train_dev, const int32_t* y_train_dev, int64_t n_train, int32_t epoch);
+/* What the fit loop's train steps (cmoop_net_run_epoch, cmoop_net_fit, cmoop_eval_population*) did, as process-wide totals since
+ * the library was loaded: out = {steps launched eagerly, steps replayed from a captured graph, captures made, captures
+ * dropped}.  Without CMOOP_GRAPH=1 in the environment the last three stay 0.  With it, a full-batch step after a net's first is
+ * captured once and replayed; the capture is dropped, and the step captured again, when an option setter or
+ * cmoop_net_set_state ran, when the step budget was rebuilt (a second fit, an epoch past cfg.epochs) or when the training
+ * tensors, the split length or the teacher table differ from the ones it froze.  Partial batches, profiled steps and nets with
+ * an option that forbids capture step eagerly.  A capture that the runtime refuses is not an error: the net steps eagerly, and
+ * only these totals show it.  Host only: launches nothing, allocates nothing; the totals are atomic, a read while other threads
+ * step is a snapshot of each. */
+int cmoop_step_launch_counts(int64_t out[4]);
 /* evaluate_individual's fit + read-outs (nsga_penalty.py:377-392) on THIS net -- the body of cmoop_eval_population's
  * per-candidate work -- with the per-epoch validation history (first hist_cap epochs), the epoch EarlyStopping took its
  * best weights from (-1: none / early_stop off) and the epochs run. */

@@ -24,6 +24,17 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert L.cmoop_abi_version() == 3
 
 
+def test_step_launch_counts_is_declared_bound_and_host_only():
+    """cmoop_step_launch_counts: in the header (so the symbol check above covers it), bound with its prototype, and answering
+    without a device -- four zeros in a process that has trained nothing, NULL refused"""
+    assert "cmoop_step_launch_counts" in _lib.declared_symbols()
+    L = _lib.lib()
+    assert L.cmoop_step_launch_counts.argtypes == [C.c_void_p]
+    assert L.cmoop_step_launch_counts(None) != 0 and b"NULL" in L.cmoop_last_error()
+    assert _lib.step_launch_counts() == {"eager": 0, "replays": 0, "captures": 0, "drops": 0}
+    assert L.cmoop_abi_version() == 3, "functions are added only"
+
+
 def test_makefile_lists_every_hip_source():
     """SRCS of csrc/Makefile is exactly the set of csrc/*.hip: a file left out would link a library that fails to load (an
     undefined launcher), a name without a file would not build."""
