@@ -328,6 +328,13 @@ INT8_PROTOTYPES = {
     "cmoop_int8_ops": [_V, _I32, _I32, _I32, _I32, _V, _I32, _V],
     "cmoop_net_set_int8": [_V, _I32],
     "cmoop_net_int8_ops": [_V, _V, _I32, _V],
+    "cmoop_fake_quant_act_codes_time": [_V, _I64, _I32, _V, _V, _I32, _V],
+    # integer depthwise, the second level
+    "cmoop_dwconv_fwd_i8": [_V, _V, _F32, _V] + [_I32] * 6 + [_V, _V, _V],
+    "cmoop_dwconv_fwd_i8_time": [_V, _V, _F32, _V] + [_I32] * 6 + [_V, _V, _V, _I32, _V],
+    "cmoop_int8_dw_ops": [_V, _I32, _I32, _I32, _I32, _V, _I32, _V],
+    "cmoop_net_set_int8_depthwise": [_V, _I32],
+    "cmoop_net_int8_dw_ops": [_V, _V, _I32, _V],
 }
 
 #: prototype of the train-step launch counters (include/cmoop.h)

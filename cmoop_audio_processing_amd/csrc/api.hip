@@ -598,6 +598,24 @@ int cmoop_fake_quant_act_codes(float* x_dev, int64_t n, int32_t bits, const floa
     });
 }
 
+int cmoop_fake_quant_act_codes_time(float* x_dev, int64_t n, int32_t bits, const float* a_in, int8_t* codes_dev, int32_t iters,
+                                    double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "fake_quant_act_codes_time: iters >= 1 and avg_ms");
+        CMOOP_REQUIRE(a_in != nullptr, "fake_quant_act_codes_time: tracked mode only (a_in is required)");
+        CMOOP_REQUIRE(bits >= 2 && bits <= 8, "fake_quant_act_codes_time: bits must be in [2, 8]");
+        CMOOP_REQUIRE(n >= 1 && n <= ACT_QUANT_MAX_ELEMS, "fake_quant_act_codes_time: n must be in [1, 2^31)");
+        CMOOP_REQUIRE(x_dev != nullptr && reinterpret_cast<uintptr_t>(x_dev) % 4 == 0, "fake_quant_act_codes_time: x_dev is NULL or not aligned to 4 bytes");
+        const ActRange rec{0.f, *a_in, 0, 0};
+        hipStream_t s = lib_stream();
+        PoolScope pool(s);
+        ActRange* rec_dev = pool.get<ActRange>(sizeof(ActRange));
+        CMOOP_HIP(hipMemcpyAsync(rec_dev, &rec, sizeof(rec), hipMemcpyHostToDevice, s));
+        CMOOP_HIP(hipStreamSynchronize(s));
+        *avg_ms = time_launches(s, iters, [&] { launch_fake_quant_act(x_dev, n, bits, true, nullptr, rec_dev, 0.f, 0.f, s, codes_dev); });
+    });
+}
+
 int cmoop_conv_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
                       int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t relu) {
     return guard([&] {
@@ -648,6 +666,64 @@ int cmoop_int8_ops(const int32_t gene[6], int32_t variant, int32_t classes, int3
         NetConfig cfg;
         cfg.variant = variant; cfg.classes = classes;
         int8_ops_abi(plan_net(gene, cfg, T, F), rows, cap, count);
+    });
+}
+
+// the lone integer depthwise layer; avg_ms non-null: timed over `iters` launches
+static void dwconv_fwd_i8_abi(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, int32_t B, int32_t H, int32_t W,
+                              int32_t C, int32_t KS, int32_t out_bits, const float* a_out, float* y_dev, int8_t* codes_dev, int32_t iters,
+                              double* avg_ms) {
+    CMOOP_REQUIRE(a_out || !codes_dev, "dwconv_fwd_i8: codes need an output range (a_out)");
+    CMOOP_REQUIRE(!a_out || (out_bits >= 2 && out_bits <= 8), "dwconv_fwd_i8: output bits must be in [2, 8]");
+    hipStream_t s = lib_stream();
+    PoolScope pool(s);
+    ActRange* rec_dev = nullptr;
+    if (a_out) {
+        const ActRange rec{0.f, *a_out, 0, 0};
+        rec_dev = pool.get<ActRange>(sizeof(ActRange));
+        CMOOP_HIP(hipMemcpyAsync(rec_dev, &rec, sizeof(rec), hipMemcpyHostToDevice, s));
+        CMOOP_HIP(hipStreamSynchronize(s));        // rec is this frame's
+    }
+    auto once = [&] { launch_dwconv_i8_fwd(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, rec_dev, out_bits, y_dev, codes_dev, B, H, W, C, KS, s); };
+    if (avg_ms) *avg_ms = time_launches(s, iters, once);
+    else once();
+    CMOOP_HIP(hipStreamSynchronize(s));
+}
+
+int cmoop_dwconv_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, int32_t B, int32_t H, int32_t W,
+                        int32_t C, int32_t KS, int32_t out_bits, const float* a_out, float* y_dev, int8_t* codes_dev) {
+    return guard([&] { dwconv_fwd_i8_abi(xq_dev, wq_dev, s_x, s_w_dev, B, H, W, C, KS, out_bits, a_out, y_dev, codes_dev, 0, nullptr); });
+}
+
+int cmoop_dwconv_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, int32_t B, int32_t H, int32_t W,
+                             int32_t C, int32_t KS, int32_t out_bits, const float* a_out, float* y_dev, int8_t* codes_dev, int32_t iters,
+                             double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "dwconv_fwd_i8_time: iters >= 1 and avg_ms");
+        dwconv_fwd_i8_abi(xq_dev, wq_dev, s_x, s_w_dev, B, H, W, C, KS, out_bits, a_out, y_dev, codes_dev, iters, avg_ms);
+    });
+}
+
+// rows [count][16] of cmoop_int8_dw_ops from a plan
+static void int8_dw_ops_abi(const NetPlan& plan, int64_t* rows, int32_t cap, int32_t* count) {
+    const std::vector<Int8DwOp> ops = int8_dw_ops(plan);
+    CMOOP_REQUIRE((rows || ops.empty()) && cap >= (int32_t)ops.size(), "int8_dw_ops: the rows buffer is too small");
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const Op& op = plan.ops[ops[i].op];
+        const int64_t v[16] = {ops[i].op, 2, ops[i].in, ops[i].out, ops[i].site, op.H, op.W, op.Cin, op.Cin, op.KS, 1, 0, op.w_off, -1,
+                               ops[i].scale_off, ops[i].out_site};
+        std::memcpy(rows + 16 * i, v, sizeof(v));
+    }
+    if (count) *count = (int32_t)ops.size();
+}
+
+int cmoop_int8_dw_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap,
+                      int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(gene != nullptr && T >= 1 && F >= 1, "int8_dw_ops: NULL gene or an empty patch");
+        NetConfig cfg;
+        cfg.variant = variant; cfg.classes = classes;
+        int8_dw_ops_abi(plan_net(gene, cfg, T, F), rows, cap, count);
     });
 }
 
@@ -1711,6 +1787,18 @@ int cmoop_net_int8_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count)
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "int8_ops: NULL net");
         int8_ops_abi(h->net->plan(), rows, cap, count);
+    });
+}
+int cmoop_net_set_int8_depthwise(cmoop_net* h, int32_t on) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "set_int8_depthwise: NULL net");
+        h->net->set_int8_depthwise(on != 0);
+    });
+}
+int cmoop_net_int8_dw_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "int8_dw_ops: NULL net");
+        int8_dw_ops_abi(h->net->plan(), rows, cap, count);
     });
 }
 int cmoop_net_get_act(cmoop_net* h, int32_t i, int32_t B, int32_t dims[6], float* data_host, float* grad_host) {

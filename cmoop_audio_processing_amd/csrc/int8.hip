@@ -172,7 +172,149 @@ void i8_check_common(const void* xq, const void* wq, const float* s_w, const flo
     CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(y) % 4 == 0, w + ": y must be aligned to 4 bytes");
 }
 
+// ---- integer depthwise (include/cmoop.h, "Integer depthwise") -------------------------------------------------------------------
+// dwconv_fwd_kernel's work split on int8 codes: work item = (sample, run of RH image rows, column), a lane owns 4 channels of
+// one item -- ONE 4-byte load per horizontal tap of an input row, read once and reused by the K output rows it reaches -- and
+// a workgroup is CB4 channel quads x 256 / CB4 items with consecutive columns.  (16 channels per lane, a 16-byte load per tap,
+// would need K K 16 weight registers: 400 at K = 5.)  The codes are converted to fp32 once per load and accumulated with FMAs:
+// every partial sum is an integer below 2^24, so each FMA is exact and the sum is the int32 sum.  The workgroup's weight codes
+// are staged once through LDS with 16-byte loads and converted once per lane.  The epilogue dequantises once and, with a
+// record of the output site, applies the tracked quantiser (quant_math.h) and stores the four codes as one word.
+constexpr int DWI8_MAX_CB4 = 16;                // channel quads per workgroup: 64 bytes of one pixel
+constexpr int DWI8_TARGET_THREADS = 256 * 1024;
+
+struct DwI8Args {
+    const int8_t* xq;           // [B][H][W][C] codes
+    const int8_t* wq;           // [K][K][C] codes
+    const float* s_w;           // [C]
+    const ActRange* rec_in;     // non-null: s_x = quant_scale(rec_in->r, qmax_in)
+    const ActRange* rec_out;    // non-null: the tracked quantiser of the output under rec_out->r; null: y = z
+    float* y;                   // [B][H][W][C]
+    int8_t* codes;              // [B][H][W][C] or null (only with rec_out)
+    float s_x, qmax_in, qmax_out;
+    int H, W, C, RH, runs, items, cb4_log;
+};
+
+__device__ __forceinline__ f32x4 dwi8_unpack(uint32_t v) {   // four signed bytes -> fp32, exact
+    return f32x4{(float)(int8_t)(v & 0xFFu), (float)(int8_t)((v >> 8) & 0xFFu), (float)(int8_t)((v >> 16) & 0xFFu),
+                 (float)(int8_t)(v >> 24)};
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void dwconv_i8_fwd_kernel(const DwI8Args a) {
+    constexpr int P = (K - 1) / 2, TAPS = K * K;
+    __shared__ i32x4 wl[TAPS * DWI8_MAX_CB4 / 4];   // [tap][DWI8_MAX_CB4] words of four codes
+    const int t = threadIdx.x, CB4 = 1 << a.cb4_log;
+    const int cql = t & (CB4 - 1), slot = t >> a.cb4_log;
+    const int c0 = (int)blockIdx.y * CB4 * 4;
+    const int pl = a.cb4_log - 2;                   // log2 of the 16-byte pieces of one tap's row (CB4 >= 4)
+    for (int i = t; i < (TAPS << pl); i += 256) {   // the workgroup's K*K x (CB4*4) weight codes, staged once
+        const int tap = i >> pl, p = i & ((1 << pl) - 1);
+        wl[tap * (DWI8_MAX_CB4 / 4) + p] = *reinterpret_cast<const i32x4*>(a.wq + tap * a.C + c0 + p * 16);
+    }
+    __syncthreads();
+    const int item = (int)blockIdx.x * (256 >> a.cb4_log) + slot;
+    if (item >= a.items) return;
+    const uint32_t* wlw = reinterpret_cast<const uint32_t*>(wl);
+    f32x4 wr[TAPS];
+#pragma unroll
+    for (int i = 0; i < TAPS; ++i) wr[i] = dwi8_unpack(wlw[i * DWI8_MAX_CB4 + cql]);
+    // item -> (sample, run, column): 32-bit divisions, once per item
+    const unsigned q = (unsigned)item / (unsigned)a.W;
+    const unsigned b = q / (unsigned)a.runs, run = q - b * (unsigned)a.runs;
+    const int w = (int)((unsigned)item - q * (unsigned)a.W);
+    const int row_base = (int)b * a.H, h0 = (int)run * a.RH, h1 = min(a.H, h0 + a.RH);
+    const int c = c0 + cql * 4;
+    // scales: one product per channel; the output site's scale as the tracked apply kernel forms it
+    const float s_x = a.rec_in ? quant_scale(__float_as_uint(a.rec_in->r), a.qmax_in) : a.s_x;
+    const f32x4 sw = *reinterpret_cast<const f32x4*>(a.s_w + c);
+    const f32x4 sc = {s_x * sw[0], s_x * sw[1], s_x * sw[2], s_x * sw[3]};
+    const float s_out = a.rec_out ? quant_scale(__float_as_uint(a.rec_out->r), a.qmax_out) : 0.f;
+    const bool live = s_out > 0.f;
+    f32x4 acc[K];   // acc[j]: output row r - P + j, which input row r reaches through vertical tap K - 1 - j
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int r = h0 - P; r < h1 + P; ++r) {
+        f32x4 x[K];
+        const bool rv = r >= 0 && r < a.H;
+        const int base = ((row_base + r) * a.W + (w - P)) * a.C + c;
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx) {
+            const int col = w + kx - P;
+            uint32_t v = 0u;                        // SAME padding: zero codes, never read from memory
+            if (rv && col >= 0 && col < a.W) v = *reinterpret_cast<const uint32_t*>(a.xq + base + kx * a.C);
+            x[kx] = dwi8_unpack(v);
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+#pragma unroll
+            for (int kx = 0; kx < K; ++kx) acc[j] = __builtin_elementwise_fma(x[kx], wr[(K - 1 - j) * K + kx], acc[j]);   // exact
+        const int h = r - P;   // complete: r is its last input row
+        if (h >= h0) {
+            const int o = ((row_base + h) * a.W + w) * a.C + c;
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = acc[0][e] * sc[e];      // z: one product
+            if (a.rec_out) {
+                int qc[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float yq;
+                    quant_element(v[e], s_out, live, a.qmax_out, qc[e], yq);
+                    v[e] = yq;
+                }
+                if (a.codes)
+                    *reinterpret_cast<uint32_t*>(a.codes + o) = ((uint32_t)qc[0] & 0xFFu) | (((uint32_t)qc[1] & 0xFFu) << 8) |
+                                                                (((uint32_t)qc[2] & 0xFFu) << 16) | (((uint32_t)qc[3] & 0xFFu) << 24);
+            }
+            *reinterpret_cast<f32x4*>(a.y + o) = v;
+        }
+#pragma unroll
+        for (int j = 0; j + 1 < K; ++j) acc[j] = acc[j + 1];
+        acc[K - 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
 }  // namespace
+
+bool int8_dw_layer_ok(int C, int KS) { return C >= 16 && C <= 512 && ilog2_exact(C) >= 0 && (KS == 3 || KS == 5); }
+
+void launch_dwconv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec_in, int act_bits, const float* s_w,
+                          const ActRange* rec_out, int out_bits, float* y, int8_t* codes, int B, int H, int W, int C, int KS,
+                          hipStream_t s) {
+    CMOOP_REQUIRE(B >= 0 && H >= 1 && W >= 1, "dwconv_fwd_i8: empty image");
+    CMOOP_REQUIRE(KS == 3 || KS == 5, "dwconv_fwd_i8: KS must be 3 or 5");
+    CMOOP_REQUIRE(C >= 16 && C <= 512 && ilog2_exact(C) >= 0, "dwconv_fwd_i8: channels must be a power of two in 16..512");
+    CMOOP_REQUIRE(!rec_in || (act_bits >= 2 && act_bits <= 8), "dwconv_fwd_i8: activation bits must be in [2, 8]");
+    CMOOP_REQUIRE(!rec_out || (out_bits >= 2 && out_bits <= 8), "dwconv_fwd_i8: output bits must be in [2, 8]");
+    CMOOP_REQUIRE(!codes || rec_out, "dwconv_fwd_i8: codes are written only under an output range");
+    if (B == 0) return;
+    // 32-bit index math: element offsets of the codes, byte offsets of y four times as large
+    CMOOP_REQUIRE((int64_t)B * H * W * C < (1ll << 29), "dwconv_fwd_i8: activation exceeds 2^29 elements (32-bit offsets)");
+    CMOOP_REQUIRE(xq && wq && s_w && y, "dwconv_fwd_i8: NULL buffer");
+    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(xq) % 16 == 0 && reinterpret_cast<uintptr_t>(wq) % 16 == 0,
+                  "dwconv_fwd_i8: code buffers must be aligned to 16 bytes");
+    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(y) % 16 == 0 && reinterpret_cast<uintptr_t>(s_w) % 16 == 0,
+                  "dwconv_fwd_i8: y and s_w must be aligned to 16 bytes");
+    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(codes) % 4 == 0, "dwconv_fwd_i8: the output codes must be aligned to 4 bytes");
+    DwI8Args a;
+    a.xq = xq; a.wq = wq; a.s_w = s_w; a.rec_in = rec_in; a.rec_out = rec_out; a.y = y; a.codes = codes;
+    a.s_x = s_x;
+    a.qmax_in = rec_in ? (float)quant_qmax(act_bits) : 0.f;
+    a.qmax_out = rec_out ? (float)quant_qmax(out_bits) : 0.f;
+    a.H = H; a.W = W; a.C = C;
+    const int C4 = C / 4, CB4 = std::min(C4, DWI8_MAX_CB4);
+    a.cb4_log = ilog2_exact(CB4);
+    // rows per run: shorter runs (more halo rows re-read through the caches) until the launch fills the chip
+    a.RH = std::min(H, 16);
+    while (a.RH > 4 && (int64_t)B * cdiv(H, a.RH) * W * C4 < DWI8_TARGET_THREADS) a.RH = (a.RH + 1) / 2;
+    a.runs = cdiv(H, a.RH);
+    a.items = B * a.runs * W;
+    const dim3 grid((unsigned)cdiv(a.items, 256 / CB4), (unsigned)(C4 / CB4));
+    if (KS == 3) hipLaunchKernelGGL(dwconv_i8_fwd_kernel<3>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(dwconv_i8_fwd_kernel<5>, grid, dim3(256), 0, s, a);
+    CMOOP_HIP(hipGetLastError());
+}
 
 bool int8_layer_ok(int Cin, int Cout, int KS, int stride) {
     return Cin >= 16 && Cin % 16 == 0 && Cout >= 1 && (KS == 1 || KS == 3 || KS == 5) && (stride == 1 || (stride == 2 && KS == 1)) &&

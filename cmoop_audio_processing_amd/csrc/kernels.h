@@ -583,6 +583,15 @@ void launch_conv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const Act
 // y [M][N] fp32 from xq [M][K] and wq [N][K] int8; K a multiple of 16, any N
 void launch_dense_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
                          const float* bias, float* y, int M, int N, int K, int relu, hipStream_t s);
+// Integer depthwise (include/cmoop.h, "Integer depthwise"): what launch_dwconv_i8_fwd accepts
+bool int8_dw_layer_ok(int C, int KS);
+// y [B][H][W][C] fp32 from xq [B][H][W][C] and wq [KS][KS][C] int8 (both 16-byte aligned), s_w [C] (16-byte aligned): SAME,
+// stride 1, no bias, no activation.  rec_in as launch_conv_i8_fwd's rec.  rec_out null: y = z, the dequantised sums; non-null:
+// y is z under the tracked quantiser of that record (out_bits) and codes (may be null; 4-byte aligned) receives its codes.
+// Every element of y (and of codes) of the B rows is written.  B == 0: nothing is launched
+void launch_dwconv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec_in, int act_bits, const float* s_w,
+                          const ActRange* rec_out, int out_bits, float* y, int8_t* codes, int B, int H, int W, int C, int KS,
+                          hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Magnitude pruning in training (opt-in, build-defined; include/cmoop.h fixes the semantics at cmoop_prune): per kernel tensor

@@ -232,6 +232,11 @@ QuantTable quant_table(const NetPlan& plan);
 // 16-byte aligned (w_off % 16)
 struct Int8Op { int op, in, out, site; int64_t scale_off; };
 std::vector<Int8Op> int8_ops(const NetPlan& plan);
+// host-only: the ops that run integer under Net::set_int8_depthwise -- every OP_DWCONV -- in op order; site / out_site are the
+// sites of its input and output.  Throws when one reads or writes an act that is no site, is beyond the kernel
+// (int8_dw_layer_ok), or its code rows (w_off % 16) or scales (scale_off % 4) would not be 16-byte aligned
+struct Int8DwOp { int op, in, out, site, out_site; int64_t scale_off; };
+std::vector<Int8DwOp> int8_dw_ops(const NetPlan& plan);
 PruneTable prune_table(const NetPlan& plan, bool skip_small = true);
 
 // The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
@@ -398,6 +403,13 @@ class Net : public GemmHook {
     // the integer passes then return NaN logits without a fault, as the fp32 passes do
     void set_int8(bool on);
     bool int8_on() const { return int8_on_; }
+    // Integer depthwise, the second level of integer inference (include/cmoop.h, "Integer depthwise").  on: refused unless
+    // set_int8 is on.  While on, every OP_DWCONV of an inference pass is ONE launch that reads the input site's codes and the
+    // staged weight codes and writes the output site's quantised fp32 tensor and its codes: the fp32 depthwise launch and the
+    // site's quantiser launch are not made.  Train steps never take it.  A plan without a depthwise op accepts it and does
+    // nothing.  Turning set_int8, set_quant or set_actquant off turns it off
+    void set_int8_depthwise(bool on);
+    bool int8_depthwise_on() const { return int8_dw_on_; }
     const NetPlan& plan() const { return plan_; }
     // debug read-out: dims = {H, W, C, materialised, has a gradient, number of acts} of act i; data / grad (either may be null)
     // receive the first B rows as the last step or pass left them (grad: B <= cfg.batch)
@@ -538,6 +550,8 @@ class Net : public GemmHook {
     float* w_scales_ = nullptr;         // [qtab_.total_channels]
     std::vector<int8_t*> site_codes_;   // per site: [Bmax][per_sample] activation codes
     std::vector<int64_t> op_scale_off_; // per op: first scale of its kernel tensor when it runs integer, else -1
+    bool int8_dw_on_ = false;           // set_int8_depthwise: inference passes take the integer depthwise launch
+    std::vector<int64_t> dw_scale_off_; // per op: first scale of its kernel tensor when it is a depthwise op, else -1
     std::vector<OpointClass> last_op_classes_;   // store_opoint: empty when the last fit ran without the read-out
     double last_op_summary_[4] = {0, 0, 0, 0};
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;

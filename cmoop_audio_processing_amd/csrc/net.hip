@@ -441,6 +441,24 @@ std::vector<Int8Op> int8_ops(const NetPlan& plan) {
     return out;
 }
 
+std::vector<Int8DwOp> int8_dw_ops(const NetPlan& plan) {
+    std::vector<Int8DwOp> out;
+    int64_t channels = 0;                              // as int8_ops: quant_table's scale_off
+    for (const KernelTensor& t : plan.kernel_tensors()) {
+        const Op& op = plan.ops[t.op];
+        if (op.kind == OP_DWCONV) {
+            const int si = plan.acts[op.in].site, so = plan.acts[op.out].site;
+            CMOOP_REQUIRE(si >= 0 && so >= 0, "int8 depthwise: a depthwise op reads or writes an act that is no activation-quantisation site");
+            CMOOP_REQUIRE(int8_dw_layer_ok(op.Cin, op.KS), "int8 depthwise: a layer is beyond the integer kernel (C a power of two in 16..512, KS 3 or 5)");
+            CMOOP_REQUIRE(op.w_off % 16 == 0, "int8 depthwise: a kernel tensor's code rows are not 16-byte aligned (w_off % 16)");
+            CMOOP_REQUIRE(channels % 4 == 0, "int8 depthwise: a kernel tensor's scales are not 16-byte aligned (scale_off % 4)");
+            out.push_back(Int8DwOp{t.op, op.in, op.out, si, so, channels});
+        }
+        channels += t.channels;
+    }
+    return out;
+}
+
 PruneTable prune_table(const NetPlan& plan, bool skip_small) {
     PruneTable tab;
     for (const KernelTensor& t : plan.kernel_tensors()) {
@@ -871,6 +889,13 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
             break;
         }
         case OP_DWCONV:
+            if (!train && int8_dw_on_) {   // integer depthwise: codes in, the output site's quantised tensor and codes out
+                const Act &ia = acts_[op.in], &oa = acts_[op.out];
+                launch_dwconv_i8_fwd(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
+                                     w_scales_ + dw_scale_off_[oi], act_rec_ + oa.site, actq_cfg_.bits, oa.data, site_codes_[oa.site],
+                                     B, op.H, op.W, op.Cin, op.KS, stream_);
+                continue;                  // the launch applied the site's quantiser
+            }
             launch_dwconv_fwd(acts_[op.in].data, kern + op.w_off, acts_[op.out].data, B, op.H, op.W, op.Cin, op.KS, 0, nullptr, stream_);
             break;
         case OP_DENSE: {
@@ -1437,7 +1462,7 @@ void Net::set_quant(const QuantCfg* quant) {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running; the table's upload is done
     quant_cfg_ = on ? *quant : QuantCfg();
     quant_on_ = on;
-    if (!on) int8_on_ = false;                    // integer inference needs the weight codes
+    if (!on) int8_on_ = int8_dw_on_ = false;      // integer inference needs the weight codes
     option_changed(on);
 }
 
@@ -1538,14 +1563,14 @@ void Net::set_actquant(const ActQuantCfg* actq) {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running
     actq_cfg_ = on ? *actq : ActQuantCfg();
     actq_on_ = on;
-    if (!on) int8_on_ = false;                    // integer inference needs the sites' codes
+    if (!on) int8_on_ = int8_dw_on_ = false;      // integer inference needs the sites' codes
     option_changed(on);
 }
 
 void Net::set_int8(bool on) {
     if (!on) {
         CMOOP_HIP(hipStreamSynchronize(stream_));
-        int8_on_ = false;
+        int8_on_ = int8_dw_on_ = false;
         return;
     }
     // every refusal comes before the first allocation or launch: a refused net is the net it was
@@ -1580,6 +1605,17 @@ void Net::set_int8(bool on) {
         for (const Int8Op& o : iops) op_scale_off_[o.op] = o.scale_off;
     }
     int8_on_ = true;
+}
+
+void Net::set_int8_depthwise(bool on) {
+    if (on) {
+        CMOOP_REQUIRE(int8_on_, "int8 depthwise: needs integer inference -- set_int8 first");
+        const std::vector<Int8DwOp> dops = int8_dw_ops(plan_);   // asserts that every depthwise op reads and writes a site
+        dw_scale_off_.assign(ops_.size(), -1);
+        for (const Int8DwOp& o : dops) dw_scale_off_[o.op] = o.scale_off;
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old level is still running
+    int8_dw_on_ = on;
 }
 
 void Net::get_act_ranges(ActRange* host) {

@@ -20,7 +20,10 @@ take the batch's own absmax (never clips) and track it with a momentum; inferenc
 
 Integer inference (``NetSession.set_int8``; ``include/cmoop.h``, "Integer inference") executes a model trained under both: the
 conv and dense layers whose input is a site multiply int8 codes, accumulate exactly in int32 and dequantise once per output.
-``conv_i8_ref`` / ``dense_i8_ref`` / ``act_codes_ref`` / ``int8_ops`` are its numpy statements.
+``conv_i8_ref`` / ``dense_i8_ref`` / ``act_codes_ref`` / ``int8_ops`` are its numpy statements.  Its opt-in second level
+(``NetSession.set_int8(True, depthwise=True)``; "Integer depthwise") runs the depthwise half of every separable layer on the
+codes as well, in one launch that also applies the quantiser of the site it writes: ``dwconv_i8_acc`` / ``dwconv_i8_ref`` /
+``int8_dw_ops`` state it.
 """
 from __future__ import annotations
 
@@ -290,6 +293,104 @@ def conv_fwd_i8_time(xq, wq, s_x, s_w, bias, y, B, H, W, Cin, Cout, KS, stride, 
     return float(ms.value)
 
 
+# ---- integer depthwise: the second level (include/cmoop.h fixes the arithmetic at "Integer depthwise") ------------------------
+# For a depthwise layer with input-site scale s_x = r_in / float32(qmax_act), weight codes qw[ky][kx][c], channel scales s_w[c]
+# and the tracked range r_out of the site it writes:
+#     acc[b,h,w,c] = sum over (ky, kx) of int32(qx[b,h+ky-p,w+kx-p,c]) * int32(qw[ky][kx][c])     p = (K-1)/2, padding taps give 0
+#     z            = fl(float32(acc) * fl(s_x * s_w[c]))                                            no bias, no activation
+#     q, y         = the tracked-mode code and dequantised value of z under r_out (_quant_elements, unchanged)
+# |acc| <= 25 * 127^2 = 403 225 < 2^24: float32(acc) is exact.  Every fl is one float32 operation.  s > 0 false: codes 0, y = +0.0.
+def _dw_weights(qw, KS, C):
+    qw = np.asarray(qw, np.int8)
+    if KS is None:
+        if qw.ndim != 3 or qw.shape[0] != qw.shape[1]:
+            raise ValueError("depthwise weight codes must be [K, K, C] (or flat with KS given)")
+        KS = qw.shape[0]
+    if int(KS) not in (3, 5):
+        raise ValueError("depthwise kernel size must be 3 or 5")
+    return qw.reshape(int(KS), int(KS), C), int(KS)
+
+
+def dwconv_i8_acc(qx, qw, KS=None) -> np.ndarray:
+    """The exact accumulators of ``dwconv_i8_ref``: ``qx`` int8 [B, H, W, C], ``qw`` int8 [K, K, C] (or flat with ``KS``) ->
+    int64 [B, H, W, C].  SAME padding, stride 1; a padding tap contributes 0."""
+    qx = np.asarray(qx, np.int8)
+    B, H, W, Cn = qx.shape
+    qw, K = _dw_weights(qw, KS, Cn)
+    p = (K - 1) // 2
+    xp = np.zeros((B, H + 2 * p, W + 2 * p, Cn), np.int64)
+    xp[:, p:p + H, p:p + W] = qx
+    acc = np.zeros((B, H, W, Cn), np.int64)
+    for ky in range(K):
+        for kx in range(K):
+            acc += xp[:, ky:ky + H, kx:kx + W] * qw[ky, kx].astype(np.int64)
+    return acc
+
+
+def dwconv_i8_ref(qx, qw, s_x, s_w, KS=None, out_bits=None, a_out=None):
+    """The integer depthwise layer restated.  ``a_out`` None: float32 ``z`` [B, H, W, C], the dequantised sums.  ``a_out``
+    given: ``(y, codes)`` -- ``fake_quant_act_ref(z, out_bits, a_out)[1]`` and ``act_codes_ref(z, out_bits, a_out)``."""
+    f = np.float32
+    acc = dwconv_i8_acc(qx, qw, KS)
+    with np.errstate(all="ignore"):
+        sc = (f(s_x) * np.asarray(s_w, f)).astype(f)
+        z = (acc.astype(np.int32).astype(f) * sc).astype(f)            # |acc| < 2^24: the conversion is exact
+    if a_out is None:
+        return z
+    return fake_quant_act_ref(z, out_bits, a_out)[1], act_codes_ref(z, out_bits, a_out)
+
+
+INT8_DW_OP_FIELDS = INT8_OP_FIELDS + ("out_site",)
+INT8_DW_KIND = 2                    # the kind field of a depthwise row (cmoop_int8_ops uses 0: conv, 1: dense)
+
+
+def int8_dw_ops(hparams, variant, classes: int, T: int, F: int) -> List[Tuple[int, int, int]]:
+    """[(op index, input act, output act)] of the ops that run integer under ``NetSession.set_int8(True, depthwise=True)``:
+    every depthwise op, the rule restated on ``act_plan``.  The twin of ``cmoop_int8_dw_ops``."""
+    _acts, ops, _logits = act_plan(hparams, variant, classes, T, F)
+    return [(i, op[1], op[3]) for i, op in enumerate(ops) if op[0] == "dwconv"]
+
+
+def _int8_dw_rows(rows, n):
+    return [dict(zip(INT8_DW_OP_FIELDS, (int(v) for v in r))) for r in rows[:n]]
+
+
+def c_int8_dw_ops(gene, variant: int, classes: int, T: int, F: int, cap: int = 64):
+    """``cmoop_int8_dw_ops``: a list of dicts keyed by ``INT8_DW_OP_FIELDS`` (kind 2, b_off -1)."""
+    g = (C.c_int32 * 6)(*(int(v) for v in gene))
+    rows, n = np.zeros((max(int(cap), 1), 16), np.int64), C.c_int32()
+    _lib.check(_lib.lib().cmoop_int8_dw_ops(g, C.c_int32(int(variant)), C.c_int32(int(classes)), C.c_int32(int(T)), C.c_int32(int(F)),
+                                            _lib.ptr(rows), C.c_int32(int(cap)), C.byref(n)))
+    return _int8_dw_rows(rows, n.value)
+
+
+def _dwconv_i8_args(xq, wq, s_x, s_w, B, H, W, Cn, KS, out_bits, a_out, y, codes):
+    a = C.c_float(float(a_out)) if a_out is not None else None
+    return a, (_dev_ptr(xq), _dev_ptr(wq), C.c_float(float(s_x)), _dev_ptr(s_w),
+               *(C.c_int32(int(v)) for v in (B, H, W, Cn, KS, out_bits if out_bits is not None else 0)),
+               C.byref(a) if a is not None else None, _dev_ptr(y), _dev_ptr(codes))
+
+
+def dwconv_fwd_i8(xq, wq, s_x, s_w, y, B, H, W, Cn, KS, out_bits=None, a_out=None, codes=None) -> None:
+    """``cmoop_dwconv_fwd_i8``: the lone integer depthwise layer.  ``xq`` [B, H, W, C] / ``wq`` [KS, KS, C] CUDA int8 (16-byte
+    aligned views), ``s_w`` / ``y`` CUDA float32.  ``a_out`` None: ``y = z``; else ``y`` and ``codes`` (CUDA int8 or None)
+    under that range at ``out_bits``."""
+    import torch
+    _a, args = _dwconv_i8_args(xq, wq, s_x, s_w, B, H, W, Cn, KS, out_bits, a_out, y, codes)
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_dwconv_fwd_i8(*args))
+
+
+def dwconv_fwd_i8_time(xq, wq, s_x, s_w, y, B, H, W, Cn, KS, out_bits=None, a_out=None, codes=None, iters: int = 50) -> float:
+    """``cmoop_dwconv_fwd_i8_time``: average milliseconds of the launch."""
+    import torch
+    ms = C.c_double()
+    _a, args = _dwconv_i8_args(xq, wq, s_x, s_w, B, H, W, Cn, KS, out_bits, a_out, y, codes)
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_dwconv_fwd_i8_time(*args, C.c_int32(int(iters)), C.byref(ms)))
+    return float(ms.value)
+
+
 def fake_quant_act_codes(x, bits: int, a, codes=None) -> None:
     """``cmoop_fake_quant_act_codes``: tracked mode under ``a`` in place on ``x`` (CUDA float32), the codes into ``codes`` (CUDA
     int8 of as many elements, or None: the plain tracked launch)."""
@@ -298,6 +399,16 @@ def fake_quant_act_codes(x, bits: int, a, codes=None) -> None:
     torch.cuda.synchronize()
     _lib.check(_lib.lib().cmoop_fake_quant_act_codes(C.c_void_p(x.data_ptr()), C.c_int64(int(x.numel())), C.c_int32(int(bits)),
                                                      C.byref(a_in), _dev_ptr(codes)))
+
+
+def fake_quant_act_codes_time(x, bits: int, a, codes=None, iters: int = 50) -> float:
+    """``cmoop_fake_quant_act_codes_time``: average milliseconds of ``fake_quant_act_codes``' launch."""
+    import torch
+    a_in, ms = C.c_float(float(a)), C.c_double()
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_fake_quant_act_codes_time(C.c_void_p(x.data_ptr()), C.c_int64(int(x.numel())), C.c_int32(int(bits)),
+                                                          C.byref(a_in), _dev_ptr(codes), C.c_int32(int(iters)), C.byref(ms)))
+    return float(ms.value)
 
 
 def act_momentum_pair(momentum):

@@ -602,8 +602,9 @@ int cmoop_eval_population_p(const cmoop_config* cfg, const cmoop_augment* aug, c
  *     (absmax partials; fold + quantise + record), one per site per inference chunk.
  *   GAPS: the first layer reads the resident feature tensor, which stays untouched; the operands of the residual add + ReLU stay
  *     fp32.  Symmetric signed ranges cost one bit on ReLU outputs.  Asymmetric or unsigned ranges, per-channel activation scales,
- *     learned clipping, a quantiser fused into the producers' epilogues and BatchNorm folding are out of scope (the conv and dense
- *     layers can be executed on int8 codes: "Integer inference" below).  It composes with the bf16 gemm modes, untested.
+ *     learned clipping, a quantiser fused into the producers' epilogues (but for the depthwise producer of "Integer depthwise"
+ *     below) and BatchNorm folding are out of scope (the conv and dense layers can be executed on int8 codes: "Integer
+ *     inference" below).  It composes with the bf16 gemm modes, untested.
  *   The backward pass is not changed.  Weight gradients are formed with the quantised operands.  The x > 0 masks the dgrad / pool
  *     / GAP kernels already take from the layer input now read quantised values, so an element that rounds to code 0 passes no
  *     gradient, exactly as the integer model's ReLU would see it.  Everything else is straight-through.
@@ -655,13 +656,15 @@ int cmoop_fake_quant_act_time(float* x_dev, int64_t n, int32_t bits, const float
  *   false) is legal, its codes are 0 and y = bias.
  * In a net (cmoop_net_set_int8) every OP_CONV and OP_DENSE whose input is an activation-quantisation site runs this way
  *   (cmoop_int8_ops): stride-1 convs, pointwise halves, the 1x1 stride-2 skip projections and every dense layer.  Everything else is
- *   launch for launch what it was: the first convolution (its input is no site), depthwise convolutions and the global pool (they
- *   keep reading the fp32 site tensor, which stays written), BatchNorm, pooling, add + ReLU, and every train step.  gemm_mode is
+ *   launch for launch what it was: the first convolution (its input is no site), depthwise convolutions (unless "Integer depthwise"
+ *   below is on as well) and the global pool (they keep reading the fp32 site tensor, which stays written), BatchNorm, pooling,
+ *   add + ReLU, and every train step.  gemm_mode is
  *   ignored by integer ops.  Weights come through the existing weight stage (snapshots, EMA, cmoop_net_use_ema and pruning compose).
  * Kernels (int8.hip): implicit GEMM on v_mfma_i32_16x16x64_i8, Cin a multiple of 16, KS 1 / 3 / 5 at stride 1 or the 1x1 stride-2
  *   projection; 16-byte code loads, so code buffers must be 16-byte aligned.  No split-K, no atomics.
- * OUT OF SCOPE: integer BatchNorm / pool / add / GAP / depthwise, BatchNorm folding, int8 outputs between layers, asymmetric or
- *   per-channel activation scales, training on integer kernels, the population objectives. */
+ * OUT OF SCOPE: integer BatchNorm / pool / add / GAP, BatchNorm folding, int8 outputs between layers (but for "Integer depthwise"
+ *   below, the opt-in second level), asymmetric or per-channel activation scales, training on integer kernels, the population
+ *   objectives. */
 /* the lone conv layer on the library stream: y_dev [B][ceil(H/stride)][ceil(W/stride)][Cout] fp32 from xq_dev [B][H][W][Cin] and
  * wq_dev [Cout][KS][KS][Cin] int8 codes (16-byte aligned), s_w_dev / bias_dev [Cout].  B == 0: success, nothing written */
 int cmoop_conv_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
@@ -677,12 +680,56 @@ int cmoop_conv_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x
 /* cmoop_fake_quant_act in tracked mode (a_in required) with the codes output: codes_dev [n] int8 receives the code of every element
  * next to the fp32 value in x_dev.  codes_dev NULL: cmoop_fake_quant_act's launch and bytes */
 int cmoop_fake_quant_act_codes(float* x_dev, int64_t n, int32_t bits, const float* a_in, int8_t* codes_dev);
+/* average milliseconds of cmoop_fake_quant_act_codes' launch (n >= 1), as cmoop_conv_fwd_i8_time: what a site's quantiser costs an
+ * integer inference pass, and the second launch of the pair "Integer depthwise" below replaces */
+int cmoop_fake_quant_act_codes_time(float* x_dev, int64_t n, int32_t bits, const float* a_in, int8_t* codes_dev, int32_t iters,
+                                    double* avg_ms);
 /* host-only: the ops of a candidate at a T x F patch that run integer under cmoop_net_set_int8, in op order: rows [count][16] =
  * {op index, kind (0 conv, 1 dense), input act, output act, input site, H, W, Cin, Cout, KS, stride, relu, w_off, b_off (offsets
  * into the parameter arena), scale_off (first scale of the tensor in cmoop_net_get_quantized's scales), 0}.  An error when cap is
  * too small, or when such an op is beyond the kernels (Cin % 16, w_off % 16, 127^2 K < 2^31); count may be NULL */
 int cmoop_int8_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows /* [cap][16] */,
                    int32_t cap, int32_t* count);
+/* ---- Integer depthwise: the second level of integer inference (opt-in on top of it, BUILD-DEFINED; off by default) ---------------
+ * THE arithmetic of an integer depthwise layer (quant.py restates it in numpy: dwconv_i8_acc / dwconv_i8_ref).  With the input
+ * site's scale s_x = r_in / (float)qmax_act, the depthwise weight codes qw[ky][kx][c] (the layout of the parameter arena), their
+ * channel scales s_w[c] and the tracked range r_out of the site the layer writes:
+ *     acc[b,h,w,c] = sum over (ky, kx) of (int32) qx[b,h+ky-p,w+kx-p,c] * (int32) qw[ky][kx][c]      p = (K-1)/2; exact; a tap in
+ *                    the SAME padding contributes 0
+ *     z            = fl( (float)acc * fl(s_x * s_w[c]) )                        no bias, no activation (as the fp32 depthwise op)
+ *     q, y         = the tracked-mode code and dequantised value of z under r_out: cmoop_actquant's element arithmetic, unchanged
+ *   |acc| <= 25 * 127^2 = 403 225 < 2^24, so (float)acc is exact and ANY exact way of forming it gives the same bytes: int32
+ *   multiply-adds, or fp32 FMAs on the converted codes (what the kernel does: every partial sum is an integer below 2^24).  Every
+ *   fl() is ONE correctly rounded fp32 operation, contraction off.  A scale with s > 0 false gives codes 0 and y = +0.0.
+ * In a net (cmoop_net_set_int8_depthwise, which needs cmoop_net_set_int8) every OP_DWCONV of an inference pass is ONE launch: it
+ *   reads the input site's codes and the staged weight codes and writes the output site's quantised fp32 tensor AND its codes, so
+ *   the fp32 depthwise launch and the site's quantiser launch are not made.  The fp32 tensor of the site stays written
+ *   (cmoop_net_get_act and every fp32 reader keep working).  Every depthwise op of the search space reads a site and writes a site
+ *   whose only reader is a pointwise op of cmoop_int8_ops (cmoop_int8_dw_ops asserts the former).  Train steps never take it.
+ * Kernel (int8.hip, dwconv_i8_fwd_kernel<K>): NHWC int8 in, C a power of two in 16..512, K 3 / 5; a lane owns four channels
+ *   (4-byte code loads, a 16-byte fp32 store and ONE packed store of four codes), an input row is read once and reused by the K
+ *   output rows it reaches; weight codes [K][K][C] must be 16-byte aligned (w_off % 16 == 0 over the whole search space), as must
+ *   the scales; 32-bit index math below 2^29 elements; no atomics.
+ * OUT OF SCOPE: codes-only sites (the fp32 tensor not written), a fused depthwise + pointwise kernel. */
+/* the lone integer depthwise layer on the library stream: xq_dev [B][H][W][C] and wq_dev [KS][KS][C] int8 codes (16-byte aligned),
+ * s_w_dev [C] (16-byte aligned), y_dev [B][H][W][C] fp32 (16-byte aligned).  a_out (host) NULL: y = z, codes_dev must be NULL;
+ * a_out given: y and codes_dev (may be NULL; 4-byte aligned) are z's dequantised value and code under the range *a_out at
+ * out_bits.  Every element of the B rows of both outputs is written.  B == 0: success, nothing written.  C no power of two in
+ * 16..512, KS not 3 or 5, a misaligned buffer or 2^29 elements and more: an error */
+int cmoop_dwconv_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, int32_t B, int32_t H, int32_t W,
+                        int32_t C, int32_t KS, int32_t out_bits, const float* a_out /* host, may be NULL */, float* y_dev,
+                        int8_t* codes_dev /* may be NULL */);
+/* average milliseconds of cmoop_dwconv_fwd_i8's launch, as cmoop_conv_fwd_i8_time */
+int cmoop_dwconv_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, int32_t B, int32_t H, int32_t W,
+                             int32_t C, int32_t KS, int32_t out_bits, const float* a_out, float* y_dev, int8_t* codes_dev,
+                             int32_t iters, double* avg_ms);
+/* host-only: the depthwise ops of a candidate that run integer under cmoop_net_set_int8_depthwise, in op order: rows [count][16] in
+ * cmoop_int8_ops' layout with kind 2, Cin = Cout = C, stride 1, relu 0, b_off -1 (no bias), and the OUTPUT site in the last
+ * field: {op index, 2, input act, output act, input site, H, W, C, C, KS, 1, 0, w_off, -1, scale_off, output site}.  Empty for
+ * variants A / B.  An error when cap is too small, when a depthwise op reads or writes an act that is no site, or is beyond the
+ * kernel (C, KS, w_off % 16, scale_off % 4); count may be NULL */
+int cmoop_int8_dw_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows /* [cap][16] */,
+                      int32_t cap, int32_t* count);
 /* the population call (above) with every argument: the other ten forward here.  aq NULL or disabled: cmoop_eval_population_p's
  * launches and bytes */
 int cmoop_eval_population_aq(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
@@ -1024,6 +1071,13 @@ int cmoop_net_set_act_ranges(cmoop_net* net, const cmoop_act_range* host, int32_
 int cmoop_net_set_int8(cmoop_net* net, int32_t on);
 /* cmoop_int8_ops of this net's plan (host arithmetic; the mode need not be on) */
 int cmoop_net_int8_ops(cmoop_net* net, int64_t* rows /* [cap][16] */, int32_t cap, int32_t* count);
+/* Integer depthwise ("Integer depthwise" above) of every following inference call of this net; train steps never take it.  on != 0
+ * is refused, with a message and the net unchanged, unless cmoop_net_set_int8 is on; a net without a depthwise op (variants A / B)
+ * accepts it and nothing changes.  on == 0: off, and every launch and byte is that of cmoop_net_set_int8 alone.  Turning
+ * cmoop_net_set_int8, cmoop_net_set_quant or cmoop_net_set_actquant off turns it off as well */
+int cmoop_net_set_int8_depthwise(cmoop_net* net, int32_t on);
+/* cmoop_int8_dw_ops of this net's plan (host arithmetic; the level need not be on) */
+int cmoop_net_int8_dw_ops(cmoop_net* net, int64_t* rows /* [cap][16] */, int32_t cap, int32_t* count);
 /* debug read-out of act index i of the plan: dims (may be NULL) = {H, W, C, 1 if materialised, 1 if it has a gradient buffer,
  * the number of acts}; data_host / grad_host (either may be NULL; both NULL: dims only) receive the first B rows of the data and
  * of the gradient as the last step or pass left them.  An error for an act that is never materialised. */
