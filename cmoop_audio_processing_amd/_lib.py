@@ -335,6 +335,16 @@ INT8_PROTOTYPES = {
     "cmoop_int8_dw_ops": [_V, _I32, _I32, _I32, _I32, _V, _I32, _V],
     "cmoop_net_set_int8_depthwise": [_V, _I32],
     "cmoop_net_int8_dw_ops": [_V, _V, _I32, _V],
+    # the requantising epilogue, the third level
+    "cmoop_conv_fwd_i8_q": [_V, _V, _F32, _V, _V, _V, _V] + [_I32] * 10 + [_V, _V, _V],
+    "cmoop_conv_fwd_i8_q_time": [_V, _V, _F32, _V, _V, _V, _V] + [_I32] * 10 + [_V, _V, _V, _I32, _V],
+    "cmoop_dense_fwd_i8_q": [_V, _V, _F32, _V, _V, _V, _V] + [_I32] * 6 + [_V, _V, _V],
+    "cmoop_dense_fwd_i8_q_time": [_V, _V, _F32, _V, _V, _V, _V] + [_I32] * 6 + [_V, _V, _V, _I32, _V],
+    "cmoop_dense_fwd_i8_time": [_V, _V, _F32, _V, _V, _V] + [_I32] * 5 + [_V],
+    "cmoop_scale_shift_time": [_V, _V, _V, _V, _I64, _I32, _I32, _I32, _V],
+    "cmoop_int8_fused_ops": [_V, _I32, _I32, _I32, _I32, _V, _I32, _V],
+    "cmoop_net_set_int8_fused": [_V, _I32],
+    "cmoop_net_int8_fused_ops": [_V, _V, _I32, _V],
 }
 
 #: prototype of the train-step launch counters (include/cmoop.h)

@@ -646,6 +646,26 @@ int cmoop_conv_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x
     });
 }
 
+int cmoop_dense_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
+                            int32_t M, int32_t N, int32_t K, int32_t relu, int32_t iters, double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "dense_fwd_i8_time: iters >= 1 and avg_ms");
+        hipStream_t s = lib_stream();
+        *avg_ms = time_launches(s, iters, [&] { launch_dense_i8_fwd(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, M, N, K, relu, s); });
+    });
+}
+
+int cmoop_scale_shift_time(const float* x_dev, float* y_dev, const float* scale_dev, const float* shift_dev, int64_t M, int32_t C, int32_t relu,
+                           int32_t iters, double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "scale_shift_time: iters >= 1 and avg_ms");
+        CMOOP_REQUIRE(M >= 1 && C >= 4 && C % 4 == 0, "scale_shift_time: M >= 1 and C a multiple of 4");
+        CMOOP_REQUIRE(x_dev && y_dev && scale_dev && shift_dev, "scale_shift_time: NULL buffer");
+        hipStream_t s = lib_stream();
+        *avg_ms = time_launches(s, iters, [&] { launch_scale_shift(x_dev, y_dev, scale_dev, shift_dev, M, C, relu, s); });
+    });
+}
+
 // rows [count][16] of cmoop_int8_ops from a plan
 static void int8_ops_abi(const NetPlan& plan, int64_t* rows, int32_t cap, int32_t* count) {
     const std::vector<Int8Op> ops = int8_ops(plan);
@@ -666,6 +686,98 @@ int cmoop_int8_ops(const int32_t gene[6], int32_t variant, int32_t classes, int3
         NetConfig cfg;
         cfg.variant = variant; cfg.classes = classes;
         int8_ops_abi(plan_net(gene, cfg, T, F), rows, cap, count);
+    });
+}
+
+// the lone requantising conv (conv: true) / dense layer; avg_ms non-null: timed over `iters` launches.  Dense: B rows, H = N, W = K
+static void fwd_i8_q_abi(bool conv, const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                         const float* bn_scale_dev, const float* bn_shift_dev, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                         int32_t KS, int32_t stride, int32_t relu, int32_t relu_after, int32_t out_bits, const float* a_out, float* y_dev,
+                         int8_t* codes_dev, int32_t iters, double* avg_ms) {
+    const std::string who = conv ? "conv_fwd_i8_q" : "dense_fwd_i8_q";
+    CMOOP_REQUIRE(a_out != nullptr, who + ": the output range (a_out) is required");
+    CMOOP_REQUIRE(out_bits >= 2 && out_bits <= 8, who + ": output bits must be in [2, 8]");
+    hipStream_t s = lib_stream();
+    PoolScope pool(s);
+    const ActRange rec{0.f, *a_out, 0, 0};
+    ActRange* rec_dev = pool.get<ActRange>(sizeof(ActRange));
+    CMOOP_HIP(hipMemcpyAsync(rec_dev, &rec, sizeof(rec), hipMemcpyHostToDevice, s));
+    CMOOP_HIP(hipStreamSynchronize(s));            // rec is this frame's
+    auto once = [&] {
+        if (conv)
+            launch_conv_i8_fwd_q(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, relu_after, rec_dev, out_bits,
+                                 y_dev, codes_dev, B, H, W, Cin, Cout, KS, stride, relu, s);
+        else
+            launch_dense_i8_fwd_q(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, relu_after, rec_dev, out_bits,
+                                  y_dev, codes_dev, B, H, W, relu, s);
+    };
+    if (avg_ms) *avg_ms = time_launches(s, iters, once);
+    else once();
+    CMOOP_HIP(hipStreamSynchronize(s));
+}
+
+int cmoop_conv_fwd_i8_q(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                        const float* bn_scale_dev, const float* bn_shift_dev, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                        int32_t KS, int32_t stride, int32_t relu, int32_t relu_after, int32_t out_bits, const float* a_out, float* y_dev,
+                        int8_t* codes_dev) {
+    return guard([&] {
+        fwd_i8_q_abi(true, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, B, H, W, Cin, Cout, KS, stride, relu, relu_after,
+                     out_bits, a_out, y_dev, codes_dev, 0, nullptr);
+    });
+}
+
+int cmoop_conv_fwd_i8_q_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                             const float* bn_scale_dev, const float* bn_shift_dev, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                             int32_t Cout, int32_t KS, int32_t stride, int32_t relu, int32_t relu_after, int32_t out_bits, const float* a_out,
+                             float* y_dev, int8_t* codes_dev, int32_t iters, double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "conv_fwd_i8_q_time: iters >= 1 and avg_ms");
+        fwd_i8_q_abi(true, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, B, H, W, Cin, Cout, KS, stride, relu, relu_after,
+                     out_bits, a_out, y_dev, codes_dev, iters, avg_ms);
+    });
+}
+
+int cmoop_dense_fwd_i8_q(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                         const float* bn_scale_dev, const float* bn_shift_dev, int32_t M, int32_t N, int32_t K, int32_t relu,
+                         int32_t relu_after, int32_t out_bits, const float* a_out, float* y_dev, int8_t* codes_dev) {
+    return guard([&] {
+        fwd_i8_q_abi(false, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, M, N, K, 0, 0, 1, 1, relu, relu_after, out_bits,
+                     a_out, y_dev, codes_dev, 0, nullptr);
+    });
+}
+
+int cmoop_dense_fwd_i8_q_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                              const float* bn_scale_dev, const float* bn_shift_dev, int32_t M, int32_t N, int32_t K, int32_t relu,
+                              int32_t relu_after, int32_t out_bits, const float* a_out, float* y_dev, int8_t* codes_dev, int32_t iters,
+                              double* avg_ms) {
+    return guard([&] {
+        CMOOP_REQUIRE(avg_ms && iters >= 1, "dense_fwd_i8_q_time: iters >= 1 and avg_ms");
+        fwd_i8_q_abi(false, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, M, N, K, 0, 0, 1, 1, relu, relu_after, out_bits,
+                     a_out, y_dev, codes_dev, iters, avg_ms);
+    });
+}
+
+// rows [count][20] of cmoop_int8_fused_ops from a plan
+static void int8_fused_ops_abi(const NetPlan& plan, int64_t* rows, int32_t cap, int32_t* count) {
+    const std::vector<Int8FusedOp> ops = int8_fused_ops(plan);
+    CMOOP_REQUIRE((rows || ops.empty()) && cap >= (int32_t)ops.size(), "int8_fused_ops: the rows buffer is too small");
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const Int8Op& o = ops[i].i8;
+        const Op& op = plan.ops[o.op];
+        const int64_t v[20] = {o.op, op.kind == OP_DENSE ? 1 : 0, o.in, o.out, o.site, op.H, op.W, op.Cin, op.Cout, op.KS, op.stride, op.relu,
+                               op.w_off, op.b_off, o.scale_off, 0, ops[i].bn, ops[i].relu_after, ops[i].out_site, ops[i].site_act};
+        std::memcpy(rows + 20 * i, v, sizeof(v));
+    }
+    if (count) *count = (int32_t)ops.size();
+}
+
+int cmoop_int8_fused_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap,
+                         int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(gene != nullptr && T >= 1 && F >= 1, "int8_fused_ops: NULL gene or an empty patch");
+        NetConfig cfg;
+        cfg.variant = variant; cfg.classes = classes;
+        int8_fused_ops_abi(plan_net(gene, cfg, T, F), rows, cap, count);
     });
 }
 
@@ -1799,6 +1911,18 @@ int cmoop_net_int8_dw_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* cou
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "int8_dw_ops: NULL net");
         int8_dw_ops_abi(h->net->plan(), rows, cap, count);
+    });
+}
+int cmoop_net_set_int8_fused(cmoop_net* h, int32_t on) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "set_int8_fused: NULL net");
+        h->net->set_int8_fused(on != 0);
+    });
+}
+int cmoop_net_int8_fused_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, "int8_fused_ops: NULL net");
+        int8_fused_ops_abi(h->net->plan(), rows, cap, count);
     });
 }
 int cmoop_net_get_act(cmoop_net* h, int32_t i, int32_t B, int32_t dims[6], float* data_host, float* grad_host) {

@@ -2,6 +2,8 @@
 // model on the i8 matrix cores of gfx950 (v_mfma_i32_16x16x64_i8), exact int32 accumulation of the int8 codes and ONE
 // dequantising epilogue per output:  y = fl(fl((float)acc * fl(s_x * s_w[c])) + bias[c]), then max(y, 0) where the op has a ReLU.
 // Inference only: no split-K, no atomics, no statistics epilogue; 32-bit index math inside the bounds the launchers check.
+// The ..._q kernels are the same tiles with the requantising epilogue ("Integer inference: requantising epilogue"): the eval
+// BatchNorm as one fma, its ReLU, and the tracked quantiser of the site written -- the fp32 quad and one word of four codes.
 //
 // Tiling (the simplest correct one: operands straight from global memory, no LDS).  K is a sequence of 16-byte FRAGMENTS: 16
 // input channels of one (pixel, tap) -- [Cout][kh][kw][Cin] weight rows and NHWC activation pixels hold them contiguously, so a
@@ -33,10 +35,20 @@ struct I8Epi {
     float s_x, qmaxf;
     int relu, vec;          // vec: y is 16-byte aligned and Cout % 4 == 0 -> 16-byte stores
 };
+// the requantising epilogue (include/cmoop.h, "Integer inference: requantising epilogue"): after the epilogue above, the eval
+// BatchNorm affine as ONE fma (what scale_shift_kernel compiles to) with its ReLU, then the tracked quantiser of the site written
+struct I8Req {
+    const float* bn_scale;  // [Cout] or null (then bn_shift is null too): what bn_eval_prepare_kernel left
+    const float* bn_shift;
+    const ActRange* rec_out;   // s_out = quant_scale(rec_out->r, qmax_out), formed as the tracked apply kernel forms it
+    int8_t* codes;          // [M][Cout], 4-byte aligned
+    float qmax_out;
+    int relu_after;
+};
 
-template <bool CONV, int MT, int NT>
+template <bool CONV, int MT, int NT, bool REQ = false>
 __device__ __forceinline__ void i8_tile(const int8_t* __restrict__ xq, const int8_t* __restrict__ wq, float* __restrict__ y,
-                                        const I8Geom g, const I8Epi e) {
+                                        const I8Geom g, const I8Epi e, const I8Req q = I8Req()) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int r16 = lane & 15, kg = lane >> 4;
     const int m_base = ((int)blockIdx.x * 4 + wave) * (16 * MT);
@@ -115,6 +127,8 @@ __device__ __forceinline__ void i8_tile(const int8_t* __restrict__ xq, const int
 
     // epilogue: result element (row = channel 4 kg + r of the block, column = output row r16)
     const float s_x = e.rec ? quant_scale(__float_as_uint(e.rec->r), e.qmaxf) : e.s_x;
+    const float s_out = REQ ? quant_scale(__float_as_uint(q.rec_out->r), q.qmax_out) : 0.f;
+    const bool live = s_out > 0.f;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         const int m = m_base + 16 * i + r16;
@@ -133,7 +147,21 @@ __device__ __forceinline__ void i8_tile(const int8_t* __restrict__ xq, const int
                 v[r] = e.relu ? fmaxf(t, 0.f) : t;
             }
             float* out = y + m * g.Cout + n;
-            if (e.vec) {
+            if (REQ) {   // Cout % 4 == 0 (the launcher's): the quad is whole.  y is the SITE's act; one word of four codes
+                int qc[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float t = v[r];
+                    if (q.bn_scale) {
+                        t = __builtin_fmaf(t, q.bn_scale[n + r], q.bn_shift[n + r]);   // ONE rounding, as scale_shift_kernel
+                        t = q.relu_after ? fmaxf(t, 0.f) : t;
+                    }
+                    quant_element(t, s_out, live, q.qmax_out, qc[r], v[r]);
+                }
+                *reinterpret_cast<f32x4*>(out) = f32x4{v[0], v[1], v[2], v[3]};
+                *reinterpret_cast<uint32_t*>(q.codes + m * g.Cout + n) = ((uint32_t)qc[0] & 0xFFu) | (((uint32_t)qc[1] & 0xFFu) << 8) |
+                                                                         (((uint32_t)qc[2] & 0xFFu) << 16) | (((uint32_t)qc[3] & 0xFFu) << 24);
+            } else if (e.vec) {
                 *reinterpret_cast<f32x4*>(out) = f32x4{v[0], v[1], v[2], v[3]};
             } else {
 #pragma unroll
@@ -154,6 +182,18 @@ template <int MT, int NT>
 __global__ __launch_bounds__(256) void dense_i8_fwd_kernel(const int8_t* __restrict__ xq, const int8_t* __restrict__ wq,
                                                            float* __restrict__ y, const I8Geom g, const I8Epi e) {
     i8_tile<false, MT, NT>(xq, wq, y, g, e);
+}
+
+template <int MT, int NT>
+__global__ __launch_bounds__(256) void conv_i8_fwd_q_kernel(const int8_t* __restrict__ xq, const int8_t* __restrict__ wq,
+                                                            float* __restrict__ y, const I8Geom g, const I8Epi e, const I8Req q) {
+    i8_tile<true, MT, NT, true>(xq, wq, y, g, e, q);
+}
+
+template <int MT, int NT>
+__global__ __launch_bounds__(256) void dense_i8_fwd_q_kernel(const int8_t* __restrict__ xq, const int8_t* __restrict__ wq,
+                                                             float* __restrict__ y, const I8Geom g, const I8Epi e, const I8Req q) {
+    i8_tile<false, MT, NT, true>(xq, wq, y, g, e, q);
 }
 
 constexpr int64_t I8_MAX_ELEMS = ((int64_t)1 << 31) - 1;   // every operand and the output: 32-bit index math
@@ -342,6 +382,63 @@ void launch_conv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const Act
     if (Cout > 32) hipLaunchKernelGGL((conv_i8_fwd_kernel<MT, 4>), dim3(gx, (unsigned)cdiv(Cout, 64)), dim3(256), 0, s, xq, wq, y, g, e);
     else if (Cout > 16) hipLaunchKernelGGL((conv_i8_fwd_kernel<MT, 2>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e);
     else hipLaunchKernelGGL((conv_i8_fwd_kernel<MT, 1>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e);
+    CMOOP_HIP(hipGetLastError());
+}
+
+// the checks the requantising launchers add to i8_check_common, and the I8Req they pass
+static I8Req i8_req_args(const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out, int out_bits, const float* y,
+                  int8_t* codes, int Cout, const char* who) {
+    const std::string w(who);
+    CMOOP_REQUIRE(Cout % 4 == 0, w + ": Cout must be a multiple of 4 (a lane stores four channels as one word of codes)");
+    CMOOP_REQUIRE((bn_scale != nullptr) == (bn_shift != nullptr), w + ": bn_scale and bn_shift come together or not at all");
+    CMOOP_REQUIRE(rec_out != nullptr, w + ": the record of the site written is required");
+    CMOOP_REQUIRE(out_bits >= 2 && out_bits <= 8, w + ": output bits must be in [2, 8]");
+    CMOOP_REQUIRE(codes != nullptr, w + ": NULL codes");
+    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(y) % 16 == 0, w + ": y must be aligned to 16 bytes");
+    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(codes) % 4 == 0, w + ": the output codes must be aligned to 4 bytes");
+    return I8Req{bn_scale, bn_shift, rec_out, codes, (float)quant_qmax(out_bits), relu_after};
+}
+
+void launch_conv_i8_fwd_q(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
+                          const float* bias, const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out,
+                          int out_bits, float* y, int8_t* codes, int B, int H, int W, int Cin, int Cout, int KS, int stride, int relu,
+                          hipStream_t s) {
+    CMOOP_REQUIRE(B >= 0 && H >= 1 && W >= 1, "conv_fwd_i8_q: empty image");
+    CMOOP_REQUIRE(KS == 1 || KS == 3 || KS == 5, "conv_fwd_i8_q: KS must be 1, 3 or 5");
+    CMOOP_REQUIRE(stride == 1 || (stride == 2 && KS == 1), "conv_fwd_i8_q: stride 1, or the 1x1 stride-2 projection");
+    CMOOP_REQUIRE(Cin >= 16 && Cin % 16 == 0, "conv_fwd_i8_q: Cin must be a multiple of 16");
+    CMOOP_REQUIRE(!rec || (act_bits >= 2 && act_bits <= 8), "conv_fwd_i8_q: activation bits must be in [2, 8]");
+    const I8Req q = i8_req_args(bn_scale, bn_shift, relu_after, rec_out, out_bits, y, codes, Cout, "conv_fwd_i8_q");
+    if (B == 0) return;
+    const int64_t OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
+    const int64_t M = (int64_t)B * OH * OW, K = (int64_t)KS * KS * Cin;
+    i8_check_common(xq, wq, s_w, bias, y, (int64_t)B * H * W * Cin, M, K, Cout, "conv_fwd_i8_q");
+    const ConvGeom cg = conv_geometry(B, H, W, Cin, Cout, KS, stride);
+    const I8Geom g{H, W, Cin, cg.OH, cg.OW, Cout, KS, stride, cg.pad_t, cg.pad_l, (int)M, (int)(K / 16), Cin / 16};
+    const I8Epi e{s_w, bias, rec, s_x, rec ? (float)quant_qmax(act_bits) : 0.f, relu, 1};
+    constexpr int MT = 2;                              // launch_conv_i8_fwd's tiles and grid
+    const unsigned gx = (unsigned)cdiv64(M, 64 * MT);
+    if (Cout > 32) hipLaunchKernelGGL((conv_i8_fwd_q_kernel<MT, 4>), dim3(gx, (unsigned)cdiv(Cout, 64)), dim3(256), 0, s, xq, wq, y, g, e, q);
+    else if (Cout > 16) hipLaunchKernelGGL((conv_i8_fwd_q_kernel<MT, 2>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e, q);
+    else hipLaunchKernelGGL((conv_i8_fwd_q_kernel<MT, 1>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e, q);
+    CMOOP_HIP(hipGetLastError());
+}
+
+void launch_dense_i8_fwd_q(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
+                           const float* bias, const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out,
+                           int out_bits, float* y, int8_t* codes, int M, int N, int K, int relu, hipStream_t s) {
+    CMOOP_REQUIRE(M >= 0 && N >= 1, "dense_fwd_i8_q: M >= 0 and N >= 1");
+    CMOOP_REQUIRE(K >= 16 && K % 16 == 0, "dense_fwd_i8_q: K must be a multiple of 16");
+    CMOOP_REQUIRE(!rec || (act_bits >= 2 && act_bits <= 8), "dense_fwd_i8_q: activation bits must be in [2, 8]");
+    const I8Req q = i8_req_args(bn_scale, bn_shift, relu_after, rec_out, out_bits, y, codes, N, "dense_fwd_i8_q");
+    if (M == 0) return;
+    i8_check_common(xq, wq, s_w, bias, y, (int64_t)M * K, M, K, N, "dense_fwd_i8_q");
+    const I8Geom g{1, 1, K, 1, 1, N, 1, 1, 0, 0, M, K / 16, K / 16};
+    const I8Epi e{s_w, bias, rec, s_x, rec ? (float)quant_qmax(act_bits) : 0.f, relu, 1};
+    const unsigned gx = (unsigned)cdiv(M, 64);
+    if (N > 32) hipLaunchKernelGGL((dense_i8_fwd_q_kernel<1, 4>), dim3(gx, (unsigned)cdiv(N, 64)), dim3(256), 0, s, xq, wq, y, g, e, q);
+    else if (N > 16) hipLaunchKernelGGL((dense_i8_fwd_q_kernel<1, 2>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e, q);
+    else hipLaunchKernelGGL((dense_i8_fwd_q_kernel<1, 1>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e, q);
     CMOOP_HIP(hipGetLastError());
 }
 

@@ -583,6 +583,19 @@ void launch_conv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const Act
 // y [M][N] fp32 from xq [M][K] and wq [N][K] int8; K a multiple of 16, any N
 void launch_dense_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
                          const float* bias, float* y, int M, int N, int K, int relu, hipStream_t s);
+// The requantising epilogue (include/cmoop.h, "Integer inference: requantising epilogue"): launch_conv_i8_fwd / launch_dense_i8_fwd
+// with the tail of the op fused in.  bn_scale / bn_shift [Cout] (both null: no BatchNorm; one without the other: an error) are
+// what launch_bn_eval_prepare left: t = fma(t, scale[c], shift[c]), then max(t, 0) under relu_after.  rec_out (required) is the
+// record of the site written: y (16-byte aligned) receives the tracked-mode dequantised values at out_bits and codes (required,
+// 4-byte aligned, [rows][Cout]) their codes.  Cout % 4 == 0.  Every element of both outputs of the B (M) rows is written.
+// B == 0 / M == 0: nothing is launched
+void launch_conv_i8_fwd_q(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
+                          const float* bias, const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out,
+                          int out_bits, float* y, int8_t* codes, int B, int H, int W, int Cin, int Cout, int KS, int stride, int relu,
+                          hipStream_t s);
+void launch_dense_i8_fwd_q(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
+                           const float* bias, const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out,
+                           int out_bits, float* y, int8_t* codes, int M, int N, int K, int relu, hipStream_t s);
 // Integer depthwise (include/cmoop.h, "Integer depthwise"): what launch_dwconv_i8_fwd accepts
 bool int8_dw_layer_ok(int C, int KS);
 // y [B][H][W][C] fp32 from xq [B][H][W][C] and wq [KS][KS][C] int8 (both 16-byte aligned), s_w [C] (16-byte aligned): SAME,

@@ -237,6 +237,12 @@ std::vector<Int8Op> int8_ops(const NetPlan& plan);
 // (int8_dw_layer_ok), or its code rows (w_off % 16) or scales (scale_off % 4) would not be 16-byte aligned
 struct Int8DwOp { int op, in, out, site, out_site; int64_t scale_off; };
 std::vector<Int8DwOp> int8_dw_ops(const NetPlan& plan);
+// host-only: the ops of int8_ops that take the requantising epilogue under Net::set_int8_fused, in op order: the act they feed
+// reaches an activation-quantisation site through per-channel elementwise ops only.  bn < 0 (T0): the op's own output act is the
+// site.  bn >= 0 (T1): that OP_BN (not fused with a pool) is the only reader of the op's output and ITS output act is the site;
+// relu_after is that BN's.  site_act / out_site: the act and the site the launch writes.  Throws when Cout % 4 != 0
+struct Int8FusedOp { Int8Op i8; int bn, relu_after, site_act, out_site; };
+std::vector<Int8FusedOp> int8_fused_ops(const NetPlan& plan);
 PruneTable prune_table(const NetPlan& plan, bool skip_small = true);
 
 // The optional training options of a candidate's fit, each null = off (kernels.h; Net::set_augment / set_loss /
@@ -410,9 +416,19 @@ class Net : public GemmHook {
     // nothing.  Turning set_int8, set_quant or set_actquant off turns it off
     void set_int8_depthwise(bool on);
     bool int8_depthwise_on() const { return int8_dw_on_; }
+    // The requantising epilogue, the third level of integer inference (include/cmoop.h, "Integer inference: requantising
+    // epilogue"), independent of the depthwise level.  on: refused unless set_int8 is on.  While on, every op of int8_fused_ops
+    // is ONE launch in an inference pass: it applies the op's bias / ReLU, the eval BatchNorm that follows it (whose
+    // bn_eval_prepare launch moves ahead of it) and the quantiser of the site, and writes the site's fp32 tensor and codes: the
+    // scale_shift launch and the site's quantiser launch are not made, and the pre-BatchNorm act is not written.  Train steps
+    // never take it.  A plan without such an op accepts it and does nothing.  Turning set_int8, set_quant or set_actquant off
+    // turns it off
+    void set_int8_fused(bool on);
+    bool int8_fused_on() const { return int8_fused_on_; }
     const NetPlan& plan() const { return plan_; }
     // debug read-out: dims = {H, W, C, materialised, has a gradient, number of acts} of act i; data / grad (either may be null)
-    // receive the first B rows as the last step or pass left them (grad: B <= cfg.batch)
+    // receive the first B rows as the last step or pass left them (grad: B <= cfg.batch).  Under set_int8_fused an inference pass
+    // does not write the act between a fused op and its BatchNorm (nothing reads it): it keeps what an earlier pass or step left
     void get_act(int i, int B, int32_t dims[6], float* data_host, float* grad_host);
     // the enabled ones of o through the nine setters above, in that order: augment, loss, distill, optim, ema, opoint, quant, prune, actq.  THE
     // place of "a disabled config is no config": null or disabled is not applied at all, and the net stays one that never had it
@@ -499,6 +515,7 @@ class Net : public GemmHook {
     void ensure_prune_table();                          // ptab_ from the plan and the config's skip_small (host only)
     void require_act_ranges() const;                    // first line of every public inference entry: with set_actquant on, tracked ranges
     void quantise_site(int act, int B, bool train);     // forward's launch(es) for a site the op just wrote
+    const float* fused_bn_prepare(size_t oi);           // set_int8_fused: bn_eval_prepare of the BN fused op oi applies (null: none)
     // THE weight stage, from params_ (the average under use_average).  Prune on: its kernels pruned at `sparsity` into wp (zeros:
     // per-row counts, or null).  Quant on and wq given: the kernels of wp, else of params_, quantised into wq (codes / scales or
     // null).  Returns the arena of the last stage that ran, params_ when none did: where forward / backward read kernel tensors
@@ -552,6 +569,11 @@ class Net : public GemmHook {
     std::vector<int64_t> op_scale_off_; // per op: first scale of its kernel tensor when it runs integer, else -1
     bool int8_dw_on_ = false;           // set_int8_depthwise: inference passes take the integer depthwise launch
     std::vector<int64_t> dw_scale_off_; // per op: first scale of its kernel tensor when it is a depthwise op, else -1
+    bool int8_fused_on_ = false;        // set_int8_fused: inference passes take the requantising launches
+    // per op under set_int8_fused: 0 nothing, 1 a fused conv / dense op, 2 a BatchNorm a fused op has applied; and for the
+    // former its BN op (-1: none) and the act it writes
+    std::vector<uint8_t> fused_role_;
+    std::vector<int> fused_bn_, fused_act_;
     std::vector<OpointClass> last_op_classes_;   // store_opoint: empty when the last fit ran without the read-out
     double last_op_summary_[4] = {0, 0, 0, 0};
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;

@@ -459,6 +459,31 @@ std::vector<Int8DwOp> int8_dw_ops(const NetPlan& plan) {
     return out;
 }
 
+std::vector<Int8FusedOp> int8_fused_ops(const NetPlan& plan) {
+    std::vector<Int8FusedOp> out;
+    for (const Int8Op& o : int8_ops(plan)) {
+        const Op& op = plan.ops[o.op];
+        int bn = -1, site_act = -1;
+        if (plan.acts[op.out].site >= 0) {                       // T0: the op's own output is a site
+            site_act = op.out;
+        } else {                                                 // T1: op -> BatchNorm (no fused pool) -> site
+            int readers = 0, reader = -1;
+            for (int j = 0; j < (int)plan.ops.size(); ++j)
+                if (plan.ops[j].in == op.out || plan.ops[j].in2 == op.out) { ++readers; reader = j; }
+            if (readers == 0 || plan.ops[reader].kind != OP_BN || plan.ops[reader].fuse_pool || plan.acts[plan.ops[reader].out].site < 0)
+                continue;
+            CMOOP_REQUIRE(readers == 1, "int8 fused: the pre-BatchNorm act of a fusible op has another reader");
+            bn = reader;
+            site_act = plan.ops[reader].out;
+        }
+        const int so = plan.acts[site_act].site;
+        CMOOP_REQUIRE(so >= 0, "int8 fused: the act a fusible op writes is no activation-quantisation site");
+        CMOOP_REQUIRE(op.Cout % 4 == 0, "int8 fused: Cout must be a multiple of 4 (a lane stores four codes as one word)");
+        out.push_back(Int8FusedOp{o, bn, bn >= 0 ? plan.ops[bn].relu_after : 0, site_act, so});
+    }
+    return out;
+}
+
 PruneTable prune_table(const NetPlan& plan, bool skip_small) {
     PruneTable tab;
     for (const KernelTensor& t : plan.kernel_tensors()) {
@@ -873,10 +898,19 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
         case OP_CONV: {
             if (!train && int8_on_ && op_is_int8(oi)) {   // integer inference: the site's codes against the staged weight codes
                 const Act& ia = acts_[op.in];
+                fused_stats_blocks_ = 0;
+                if (int8_fused_on_ && fused_role_[oi] == 1) {   // the requantising epilogue: the site's tensor and codes, one launch
+                    const Act& sa = acts_[fused_act_[oi]];
+                    const float* scale = fused_bn_prepare(oi);
+                    launch_conv_i8_fwd_q(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
+                                         w_scales_ + op_scale_off_[oi], params_ + op.b_off, scale, scale ? scale + op.Cout : nullptr,
+                                         scale ? ops_[fused_bn_[oi]].relu_after : 0, act_rec_ + sa.site, actq_cfg_.bits, sa.data,
+                                         site_codes_[sa.site], B, op.H, op.W, op.Cin, op.Cout, op.KS, op.stride, op.relu, stream_);
+                    continue;                                   // the launch applied the site's quantiser
+                }
                 launch_conv_i8_fwd(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
                                    w_scales_ + op_scale_off_[oi], params_ + op.b_off, acts_[op.out].data, B, op.H, op.W, op.Cin,
                                    op.Cout, op.KS, op.stride, op.relu, stream_);
-                fused_stats_blocks_ = 0;
                 break;
             }
             GemmEpilogue e;
@@ -901,6 +935,15 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
         case OP_DENSE: {
             if (!train && int8_on_ && op_is_int8(oi)) {
                 const Act& ia = acts_[op.in];
+                if (int8_fused_on_ && fused_role_[oi] == 1) {
+                    const Act& sa = acts_[fused_act_[oi]];
+                    const float* scale = fused_bn_prepare(oi);
+                    launch_dense_i8_fwd_q(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
+                                          w_scales_ + op_scale_off_[oi], params_ + op.b_off, scale, scale ? scale + op.Cout : nullptr,
+                                          scale ? ops_[fused_bn_[oi]].relu_after : 0, act_rec_ + sa.site, actq_cfg_.bits, sa.data,
+                                          site_codes_[sa.site], B, op.Cout, op.Cin, op.relu, stream_);
+                    continue;
+                }
                 launch_dense_i8_fwd(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
                                     w_scales_ + op_scale_off_[oi], params_ + op.b_off, acts_[op.out].data, B, op.Cout, op.Cin,
                                     op.relu, stream_);
@@ -915,6 +958,7 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
             break;
         }
         case OP_BN: {
+            if (!train && int8_fused_on_ && fused_role_[oi] == 2) continue;   // the producer's requantising epilogue applied it
             const Act& ia = acts_[op.in];
             const int64_t M = (int64_t)B * ia.H * ia.W;
             const int C = op.Cout;
@@ -962,6 +1006,17 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
             if (written >= 0 && acts_[written].site >= 0) quantise_site(written, B, train);
         }
     }
+}
+
+// the eval BatchNorm vectors of the BN a fused op applies, prepared ahead of it: scale (shift follows at + C), or null (T0)
+const float* Net::fused_bn_prepare(size_t oi) {
+    if (fused_bn_[oi] < 0) return nullptr;
+    const Op& bn = ops_[fused_bn_[oi]];
+    const int C = bn.Cout;
+    float *scale = bn.bn_buf + 2 * C, *shift = scale + C;
+    launch_bn_eval_prepare(params_ + bn.gamma_off, params_ + bn.beta_off, params_ + bn.mm_off, params_ + bn.mv_off, scale, shift, C,
+                           (float)cfg_.bn_eps, stream_);
+    return scale;
 }
 
 void Net::quantise_site(int act, int B, bool train) {
@@ -1462,7 +1517,7 @@ void Net::set_quant(const QuantCfg* quant) {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running; the table's upload is done
     quant_cfg_ = on ? *quant : QuantCfg();
     quant_on_ = on;
-    if (!on) int8_on_ = int8_dw_on_ = false;      // integer inference needs the weight codes
+    if (!on) int8_on_ = int8_dw_on_ = int8_fused_on_ = false;      // integer inference needs the weight codes
     option_changed(on);
 }
 
@@ -1563,14 +1618,14 @@ void Net::set_actquant(const ActQuantCfg* actq) {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running
     actq_cfg_ = on ? *actq : ActQuantCfg();
     actq_on_ = on;
-    if (!on) int8_on_ = int8_dw_on_ = false;      // integer inference needs the sites' codes
+    if (!on) int8_on_ = int8_dw_on_ = int8_fused_on_ = false;      // integer inference needs the sites' codes
     option_changed(on);
 }
 
 void Net::set_int8(bool on) {
     if (!on) {
         CMOOP_HIP(hipStreamSynchronize(stream_));
-        int8_on_ = int8_dw_on_ = false;
+        int8_on_ = int8_dw_on_ = int8_fused_on_ = false;
         return;
     }
     // every refusal comes before the first allocation or launch: a refused net is the net it was
@@ -1616,6 +1671,24 @@ void Net::set_int8_depthwise(bool on) {
     }
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old level is still running
     int8_dw_on_ = on;
+}
+
+void Net::set_int8_fused(bool on) {
+    if (on) {
+        CMOOP_REQUIRE(int8_on_, "int8 fused: needs integer inference -- set_int8 first");
+        const std::vector<Int8FusedOp> fops = int8_fused_ops(plan_);   // asserts the sites, Cout % 4 and the lone reader
+        fused_role_.assign(ops_.size(), 0);
+        fused_bn_.assign(ops_.size(), -1);
+        fused_act_.assign(ops_.size(), -1);
+        for (const Int8FusedOp& o : fops) {
+            fused_role_[o.i8.op] = 1;
+            fused_bn_[o.i8.op] = o.bn;
+            fused_act_[o.i8.op] = o.site_act;
+            if (o.bn >= 0) fused_role_[o.bn] = 2;
+        }
+    }
+    CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old level is still running
+    int8_fused_on_ = on;
 }
 
 void Net::get_act_ranges(ActRange* host) {

@@ -269,11 +269,13 @@ class TrainedModel:
                        params=z["params"].copy(), objectives=obj, frontend=fe, mean=mean, scale=scale,
                        thresholds=thresholds, **quant, **prune, **act)
 
-    def _require_int8(self, int8: bool = True, int8_depthwise: bool = False) -> None:
-        """ValueError naming what a model lacks for integer inference, or ``int8_depthwise`` without ``int8`` (host only:
-        before any session opens)."""
+    def _require_int8(self, int8: bool = True, int8_depthwise: bool = False, int8_fused: bool = False) -> None:
+        """ValueError naming what a model lacks for integer inference, or ``int8_depthwise`` / ``int8_fused`` without ``int8``
+        (host only: before any session opens)."""
         if int8_depthwise and not int8:
             raise ValueError("int8_depthwise=True needs int8=True: integer depthwise is a level of integer inference")
+        if int8_fused and not int8:
+            raise ValueError("int8_fused=True needs int8=True: the requantising epilogue is a level of integer inference")
         if not int8:
             return
         missing = [name for name, v in (("quant_codes (train it under EvalConfig.quant)", self.quant_codes),
@@ -281,7 +283,8 @@ class TrainedModel:
         if missing:
             raise ValueError("int8=True needs a full-int8 model; this one carries no " + " and no ".join(missing))
 
-    def session(self, config: Optional[EvalConfig] = None, int8: bool = False, int8_depthwise: bool = False):
+    def session(self, config: Optional[EvalConfig] = None, int8: bool = False, int8_depthwise: bool = False,
+                int8_fused: bool = False):
         """A ``NetSession`` holding these parameters (needs the GPU).  ``config`` supplies ``eval_batch`` and the like;
         its variant and class count must be the model's.  A model that carries ``act_ranges`` gets the activation quantiser
         at ``act_bits`` and ``act_momentum`` with those ranges, whatever ``config.act_quant`` says.  ``int8``: integer
@@ -290,9 +293,10 @@ class TrainedModel:
         scales back from the dequantised ``params`` (the absmax element of a channel is code qmax, and
         ``fl(fl(qmax s) / qmax) == s``).  ``int8_depthwise``: the second level as well (``NetSession.set_int8(True,
         depthwise=True)``): it needs ``int8=True`` (ValueError otherwise, before the session opens), needs nothing more of the
-        model, and has no effect on an A / B model."""
+        model, and has no effect on an A / B model.  ``int8_fused``: the third level (``NetSession.set_int8(True, fused=True)``),
+        under the same terms; its logits are those of the levels it is added to, bit for bit."""
         from .session import NetSession
-        self._require_int8(int8, int8_depthwise)
+        self._require_int8(int8, int8_depthwise, int8_fused)
         if config is None:
             config = EvalConfig(variant=self.variant, classes=self.classes)
         if config.variant != self.variant or int(config.classes) != self.classes:
@@ -308,31 +312,37 @@ class TrainedModel:
             if int8:
                 from .quant import QuantConfig
                 net.set_quant(QuantConfig(bits=self.quant_bits, objective=False))
-                net.set_int8(True, depthwise=bool(int8_depthwise))
+                net.set_int8(True, depthwise=bool(int8_depthwise), fused=bool(int8_fused))
         except Exception:
             net.close()
             raise
         return net
 
-    def logits(self, X, config: Optional[EvalConfig] = None, int8: bool = False, int8_depthwise: bool = False):
+    def logits(self, X, config: Optional[EvalConfig] = None, int8: bool = False, int8_depthwise: bool = False,
+               int8_fused: bool = False):
         """CUDA float32 [n, classes]: this model's logits of the rows X (CUDA float32 [n, T, F]) -- ``session(config)`` and
         ``NetSession.predict_logits``; what ``PopulationEvaluator.set_teacher`` trains candidates against.  ``int8``: the
-        integer-inference logits (``session(config, int8=True)``), ``int8_depthwise``: with its second level."""
-        with self.session(config, int8=int8, int8_depthwise=int8_depthwise) as net:
+        integer-inference logits (``session(config, int8=True)``), ``int8_depthwise``: with its second level, ``int8_fused``: with
+        its third."""
+        with self.session(config, int8=int8, int8_depthwise=int8_depthwise, int8_fused=int8_fused) as net:
             return net.predict_logits(X)
 
-    def int8_report(self, X, y=None, config: Optional[EvalConfig] = None, depthwise: bool = False) -> Dict[str, float]:
+    def int8_report(self, X, y=None, config: Optional[EvalConfig] = None, depthwise: bool = False,
+                    fused: bool = False) -> Dict[str, float]:
         """How far integer inference lies from the fake-quantised fp32 pass on the rows X (CUDA float32 [n, T, F]): one
         session, ``predict_logits`` with the mode off and on -> {"rows", "argmax_agree" (fraction of rows with the same arg
         max), "max_abs_logit_diff", "int8_ops" (how many ops ran integer)}, and with labels ``y`` (CUDA or host ints [n])
         "acc_fakequant" and "acc_int8" as well.  ``depthwise``: the integer side runs with the second level on, and the report
-        gains "int8_dw_ops" (how many depthwise ops ran integer; 0 for an A / B model).  A reported figure, no gate."""
+        gains "int8_dw_ops" (how many depthwise ops ran integer; 0 for an A / B model).  ``fused``: the integer side runs with the
+        third level on, and the report gains "int8_fused_ops" (how many ops took the requantising epilogue).  A reported
+        figure, no gate."""
         import torch
         self._require_int8()
-        with self.session(config, int8=True, int8_depthwise=depthwise) as net:
+        with self.session(config, int8=True, int8_depthwise=depthwise, int8_fused=fused) as net:
             zi = net.predict_logits(X)
             n_ops = len(net.int8_ops())
             n_dw = len(net.int8_dw_ops()) if depthwise else 0
+            n_fused = len(net.int8_fused_ops()) if fused else 0
             net.set_int8(False)
             zf = net.predict_logits(X)
         n = int(zi.shape[0])
@@ -345,6 +355,8 @@ class TrainedModel:
             out["acc_int8"] = float((ai == yt).float().mean().item()) if n else 0.0
         if depthwise:
             out["int8_dw_ops"] = n_dw
+        if fused:
+            out["int8_fused_ops"] = n_fused
         return out
 
 
@@ -355,16 +367,16 @@ class StreamScorer:
     does not: ``log_mel_stream`` has normalised the recording once, windows are plain cuts of it."""
 
     def __init__(self, model: TrainedModel, hop_frames: int, config: Optional[EvalConfig] = None, int8: bool = False,
-                 int8_depthwise: bool = False):
+                 int8_depthwise: bool = False, int8_fused: bool = False):
         if int(hop_frames) < 1:
             raise ValueError("hop_frames must be at least 1")
-        model._require_int8(int8, int8_depthwise)
+        model._require_int8(int8, int8_depthwise, int8_fused)
         self.model, self.hop_frames = model, int(hop_frames)
         self.frontend = model.frontend if model.frontend is not None else FrontendConfig()
         if int(self.frontend.n_mels) != model.F:
             raise ValueError(f"the front end gives {self.frontend.n_mels} mel bands, the model reads F = {model.F}")
-        # int8: the windows are scored by integer inference (int8_depthwise: with its second level)
-        self.net = model.session(config, int8=int8, int8_depthwise=int8_depthwise)
+        # int8: the windows are scored by integer inference (int8_depthwise / int8_fused: with its second / third level)
+        self.net = model.session(config, int8=int8, int8_depthwise=int8_depthwise, int8_fused=int8_fused)
 
     def close(self):
         self.net.close()

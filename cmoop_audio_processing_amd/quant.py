@@ -23,7 +23,10 @@ conv and dense layers whose input is a site multiply int8 codes, accumulate exac
 ``conv_i8_ref`` / ``dense_i8_ref`` / ``act_codes_ref`` / ``int8_ops`` are its numpy statements.  Its opt-in second level
 (``NetSession.set_int8(True, depthwise=True)``; "Integer depthwise") runs the depthwise half of every separable layer on the
 codes as well, in one launch that also applies the quantiser of the site it writes: ``dwconv_i8_acc`` / ``dwconv_i8_ref`` /
-``int8_dw_ops`` state it.
+``int8_dw_ops`` state it.  Its opt-in third level (``NetSession.set_int8(True, fused=True)``; "Integer inference: requantising
+epilogue") gives the conv and dense launches the tail of their op -- the eval BatchNorm as one fma, its ReLU and the quantiser of
+the site written -- so they emit the next layer's codes themselves: ``fma32_ref`` / ``conv_i8_q_ref`` / ``dense_i8_q_ref`` /
+``int8_fused_ops`` state it.
 """
 from __future__ import annotations
 
@@ -290,6 +293,164 @@ def conv_fwd_i8_time(xq, wq, s_x, s_w, bias, y, B, H, W, Cin, Cout, KS, stride, 
     _lib.check(_lib.lib().cmoop_conv_fwd_i8_time(_dev_ptr(xq), _dev_ptr(wq), C.c_float(float(s_x)), _dev_ptr(s_w), _dev_ptr(bias),
                                                  _dev_ptr(y), *(C.c_int32(int(v)) for v in (B, H, W, Cin, Cout, KS, stride, relu, iters)),
                                                  C.byref(ms)))
+    return float(ms.value)
+
+
+# ---- the requantising epilogue: the third level (include/cmoop.h, "Integer inference: requantising epilogue") -----------------
+# For a conv / dense op of int8_ops whose output reaches a site through per-channel elementwise ops only (int8_fused_ops):
+#     t    = i8_epilogue_ref(acc, s_x, s_w, bias, relu)                                       today's epilogue, unchanged
+#     t    = fma32_ref(t, scale[c], shift[c]), then max(t, 0) under relu_after                only with a BatchNorm; ONE rounding
+#     q, y = the tracked-mode code and dequantised value of t under the range of the site written (_quant_elements, unchanged)
+def fma32_ref(a, b, c) -> np.ndarray:
+    """The correctly rounded float32 ``a * b + c`` (ONE rounding), elementwise with broadcasting.  The product of two float32 is
+    exact in float64 (48 bits); ``c`` is added with a TwoSum and the float64 sum is rounded to odd when the error term is
+    non-zero; 53 >= 2 * 24 + 2, so the cast of that sum to float32 is the correctly rounded result."""
+    f8 = np.float64
+    with np.errstate(all="ignore"):
+        p = np.asarray(a, np.float32).astype(f8) * np.asarray(b, np.float32).astype(f8)
+        cc = np.broadcast_to(np.asarray(c, np.float32).astype(f8), p.shape)
+        s = p + cc
+        bb = s - p
+        e = (p - (s - bb)) + (cc - bb)                                   # s + e == p + c exactly (finite operands)
+        fix = np.isfinite(s) & np.isfinite(e) & (e != 0) & ((np.ascontiguousarray(s).view(np.uint64) & np.uint64(1)) == 0)
+        s = np.where(fix, np.nextafter(s, np.where(e > 0, f8(np.inf), f8(-np.inf))), s)
+        return s.astype(np.float32)
+
+
+def i8_requant_ref(t, bn_scale=None, bn_shift=None, relu_after=0, out_bits=None, a_out=None):
+    """The tail of the requantising epilogue on ``t`` float32 [..., C] (what ``i8_epilogue_ref`` returns) -> ``(y, codes)``."""
+    f = np.float32
+    if (bn_scale is None) != (bn_shift is None):
+        raise ValueError("bn_scale and bn_shift come together or not at all")
+    if out_bits is None or a_out is None:
+        raise ValueError("the site written needs out_bits and a_out")
+    t = np.asarray(t, f)
+    if bn_scale is not None:
+        t = fma32_ref(t, np.asarray(bn_scale, f), np.asarray(bn_shift, f))
+        if relu_after:
+            with np.errstate(all="ignore"):
+                t = np.where(t > 0, t, f(0)).astype(f)                  # fmaxf(t, 0): a NaN becomes 0
+    return fake_quant_act_ref(t, out_bits, a_out)[1], act_codes_ref(t, out_bits, a_out)
+
+
+def conv_i8_q_ref(qx, qw, s_x, s_w, bias, KS: int, stride: int, relu, bn_scale=None, bn_shift=None, relu_after=0, out_bits=None,
+                  a_out=None):
+    """The requantising integer conv layer restated: ``conv_i8_ref``'s operands, the eval BatchNorm vectors (both None: no
+    BatchNorm) and the range ``a_out`` of the site written at ``out_bits`` -> ``(y float32, codes int8)``, both
+    [B, OH, OW, Cout]."""
+    t = i8_epilogue_ref(conv_i8_acc(qx, qw, KS, stride), s_x, s_w, bias, relu)
+    return i8_requant_ref(t, bn_scale, bn_shift, relu_after, out_bits, a_out)
+
+
+def dense_i8_q_ref(qx, qw, s_x, s_w, bias, relu, bn_scale=None, bn_shift=None, relu_after=0, out_bits=None, a_out=None):
+    """The requantising integer dense layer restated: ``dense_i8_ref``'s operands and ``conv_i8_q_ref``'s tail -> ``(y, codes)``
+    [M, N]."""
+    return i8_requant_ref(dense_i8_ref(qx, qw, s_x, s_w, bias, relu), bn_scale, bn_shift, relu_after, out_bits, a_out)
+
+
+def dense_fwd_i8_time(xq, wq, s_x, s_w, bias, y, M, N, K, relu, iters: int = 50) -> float:
+    """``cmoop_dense_fwd_i8_time``: average milliseconds of ``dense_fwd_i8``'s launch."""
+    import torch
+    ms = C.c_double()
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_dense_fwd_i8_time(_dev_ptr(xq), _dev_ptr(wq), C.c_float(float(s_x)), _dev_ptr(s_w), _dev_ptr(bias), _dev_ptr(y),
+                                                  *(C.c_int32(int(v)) for v in (M, N, K, relu, iters)), C.byref(ms)))
+    return float(ms.value)
+
+
+def scale_shift_time(x, y, scale, shift, M, Cn, relu, iters: int = 50) -> float:
+    """``cmoop_scale_shift_time``: average milliseconds of the eval BatchNorm's apply launch alone."""
+    import torch
+    ms = C.c_double()
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_scale_shift_time(_dev_ptr(x), _dev_ptr(y), _dev_ptr(scale), _dev_ptr(shift), C.c_int64(int(M)),
+                                                 *(C.c_int32(int(v)) for v in (Cn, relu, iters)), C.byref(ms)))
+    return float(ms.value)
+
+
+INT8_FUSED_OP_FIELDS = INT8_OP_FIELDS + ("zero", "bn_op", "relu_after", "out_site", "site_act")
+
+
+def int8_fused_ops(hparams, variant, classes: int, T: int, F: int) -> List[Tuple[int, int, int, int, int, int]]:
+    """[(op index, input act, output act, BatchNorm op index or -1, relu_after, act written)] of the ops that take the
+    requantising epilogue under ``NetSession.set_int8(True, fused=True)``, the rule restated on ``act_plan``: an op of
+    ``int8_ops`` whose own output act is a site (T0), or whose output is read by one op only, a BatchNorm whose output is
+    materialised (no fused pool) and a site (T1).  Such a BatchNorm is topology A's, which carries the ReLU, so ``relu_after``
+    is 1 exactly on the T1 rows.  The twin of ``cmoop_int8_fused_ops``."""
+    _acts, ops, _logits = act_plan(hparams, variant, classes, T, F)
+    sites = {s[0] for s in act_sites(hparams, variant, classes, T, F)}
+    out = []
+    for i, a_in, a_out in int8_ops(hparams, variant, classes, T, F):
+        if a_out in sites:
+            out.append((i, a_in, a_out, -1, 0, a_out))
+            continue
+        readers = [j for j, op in enumerate(ops) if a_out in (op[1], op[2])]
+        if len(readers) == 1 and ops[readers[0]][0] == "bn" and ops[readers[0]][3] in sites:
+            out.append((i, a_in, a_out, readers[0], 1, ops[readers[0]][3]))
+    return out
+
+
+def _int8_fused_rows(rows, n):
+    return [dict(zip(INT8_FUSED_OP_FIELDS, (int(v) for v in r))) for r in rows[:n]]
+
+
+def c_int8_fused_ops(gene, variant: int, classes: int, T: int, F: int, cap: int = 64):
+    """``cmoop_int8_fused_ops``: a list of dicts keyed by ``INT8_FUSED_OP_FIELDS`` (``bn_op`` -1: the op's own output is the
+    site)."""
+    g = (C.c_int32 * 6)(*(int(v) for v in gene))
+    rows, n = np.zeros((max(int(cap), 1), 20), np.int64), C.c_int32()
+    _lib.check(_lib.lib().cmoop_int8_fused_ops(g, C.c_int32(int(variant)), C.c_int32(int(classes)), C.c_int32(int(T)), C.c_int32(int(F)),
+                                               _lib.ptr(rows), C.c_int32(int(cap)), C.byref(n)))
+    return _int8_fused_rows(rows, n.value)
+
+
+def _i8_q_args(xq, wq, s_x, s_w, bias, bn_scale, bn_shift, ints, a_out, y, codes):
+    a = C.c_float(float(a_out)) if a_out is not None else None
+    return a, (_dev_ptr(xq), _dev_ptr(wq), C.c_float(float(s_x)), _dev_ptr(s_w), _dev_ptr(bias), _dev_ptr(bn_scale), _dev_ptr(bn_shift),
+               *(C.c_int32(int(v)) for v in ints), C.byref(a) if a is not None else None, _dev_ptr(y), _dev_ptr(codes))
+
+
+def conv_fwd_i8_q(xq, wq, s_x, s_w, bias, y, codes, B, H, W, Cin, Cout, KS, stride, relu, out_bits, a_out, bn_scale=None,
+                  bn_shift=None, relu_after=0) -> None:
+    """``cmoop_conv_fwd_i8_q``: the lone requantising conv layer.  ``conv_fwd_i8``'s operands; ``y`` CUDA float32 (16-byte
+    aligned) and ``codes`` CUDA int8 receive the site's dequantised values and codes under ``a_out`` at ``out_bits``;
+    ``bn_scale`` / ``bn_shift`` CUDA float32 [Cout] or both None."""
+    import torch
+    _a, args = _i8_q_args(xq, wq, s_x, s_w, bias, bn_scale, bn_shift, (B, H, W, Cin, Cout, KS, stride, relu, relu_after, out_bits), a_out,
+                          y, codes)
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_conv_fwd_i8_q(*args))
+
+
+def conv_fwd_i8_q_time(xq, wq, s_x, s_w, bias, y, codes, B, H, W, Cin, Cout, KS, stride, relu, out_bits, a_out, bn_scale=None,
+                       bn_shift=None, relu_after=0, iters: int = 50) -> float:
+    """``cmoop_conv_fwd_i8_q_time``: average milliseconds of the launch."""
+    import torch
+    ms = C.c_double()
+    _a, args = _i8_q_args(xq, wq, s_x, s_w, bias, bn_scale, bn_shift, (B, H, W, Cin, Cout, KS, stride, relu, relu_after, out_bits), a_out,
+                          y, codes)
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_conv_fwd_i8_q_time(*args, C.c_int32(int(iters)), C.byref(ms)))
+    return float(ms.value)
+
+
+def dense_fwd_i8_q(xq, wq, s_x, s_w, bias, y, codes, M, N, K, relu, out_bits, a_out, bn_scale=None, bn_shift=None,
+                   relu_after=0) -> None:
+    """``cmoop_dense_fwd_i8_q``: the lone requantising dense layer."""
+    import torch
+    _a, args = _i8_q_args(xq, wq, s_x, s_w, bias, bn_scale, bn_shift, (M, N, K, relu, relu_after, out_bits), a_out, y, codes)
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_dense_fwd_i8_q(*args))
+
+
+def dense_fwd_i8_q_time(xq, wq, s_x, s_w, bias, y, codes, M, N, K, relu, out_bits, a_out, bn_scale=None, bn_shift=None,
+                        relu_after=0, iters: int = 50) -> float:
+    """``cmoop_dense_fwd_i8_q_time``: average milliseconds of the launch."""
+    import torch
+    ms = C.c_double()
+    _a, args = _i8_q_args(xq, wq, s_x, s_w, bias, bn_scale, bn_shift, (M, N, K, relu, relu_after, out_bits), a_out, y, codes)
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cmoop_dense_fwd_i8_q_time(*args, C.c_int32(int(iters)), C.byref(ms)))
     return float(ms.value)
 
 

@@ -30,6 +30,7 @@ class NetSession:
         self.augment = self.loss = self.optim = self.ema = self.opoint = self.quant = self.prune = self.act_quant = None
         self.int8 = False
         self.int8_depthwise = False
+        self.int8_fused = False
         for name, setter in (("augment", self.set_augment), ("loss", self.set_loss), ("optim", self.set_optim),
                              ("ema", self.set_ema), ("operating_point", self.set_operating_point), ("quant", self.set_quant),
                              ("prune", self.set_prune), ("act_quant", self.set_act_quant)):
@@ -195,6 +196,7 @@ class NetSession:
         self.quant = quant if quant is not None and quant.enabled else None
         self.int8 = self.int8 and self.quant is not None       # the net drops integer inference with its weight codes
         self.int8_depthwise = self.int8_depthwise and self.int8
+        self.int8_fused = self.int8_fused and self.int8
 
     def get_quantized(self):
         """(wq_params float32 [n_params]: kernels dequantised, every other element a copy; codes int8 [n_params]: 0 outside
@@ -239,8 +241,9 @@ class NetSession:
         self.act_quant = act_quant if act_quant is not None and act_quant.enabled else None
         self.int8 = self.int8 and self.act_quant is not None   # ... and with its activation codes
         self.int8_depthwise = self.int8_depthwise and self.int8
+        self.int8_fused = self.int8_fused and self.int8
 
-    def set_int8(self, on, depthwise: bool = False) -> None:
+    def set_int8(self, on, depthwise: bool = False, fused: bool = False) -> None:
         """Integer inference (``cmoop_net_set_int8``) of every following ``evaluate`` / ``predict_*`` call: every conv and dense
         op whose input is an activation-quantisation site (``int8_ops``) runs on int8 codes with exact int32 accumulation
         (``quant.conv_i8_ref`` / ``dense_i8_ref``); train steps never do.  Turning it on raises, and leaves the net as it was,
@@ -248,10 +251,19 @@ class NetSession:
         finite.  Off (the default), every launch and byte is that of a net that never had it.  ``depthwise``: the second level
         (``cmoop_net_set_int8_depthwise``; it needs ``on``): every depthwise op (``int8_dw_ops``) is one launch on the codes
         that also applies the quantiser of the site it writes (``quant.dwconv_i8_ref``).  False -- the default -- is
-        ``set_int8(on)`` as it always was; a net without a depthwise op accepts it and nothing changes."""
+        ``set_int8(on)`` as it always was; a net without a depthwise op accepts it and nothing changes.  ``fused``: the third
+        level (``cmoop_net_set_int8_fused``; it needs ``on`` and is independent of ``depthwise``): every op of
+        ``int8_fused_ops`` is one launch that also applies the eval BatchNorm after it and the quantiser of the site it reaches
+        (``quant.conv_i8_q_ref`` / ``dense_i8_q_ref``), with the bytes of the launches it replaces.  False is the default; a
+        net without a fusible op accepts it and nothing changes."""
         if depthwise and not on:
             raise ValueError("depthwise=True needs on=True: integer depthwise is a level of integer inference")
+        if fused and not on:
+            raise ValueError("fused=True needs on=True: the requantising epilogue is a level of integer inference")
         L = _lib.lib()
+        if not on or not fused:
+            _lib.check(L.cmoop_net_set_int8_fused(self._h, C.c_int32(0)))
+            self.int8_fused = False
         if not on or not depthwise:                      # the level goes first: turning integer inference off drops it anyway
             _lib.check(L.cmoop_net_set_int8_depthwise(self._h, C.c_int32(0)))
             self.int8_depthwise = False
@@ -260,6 +272,9 @@ class NetSession:
         if depthwise:
             _lib.check(L.cmoop_net_set_int8_depthwise(self._h, C.c_int32(1)))
             self.int8_depthwise = True
+        if fused:
+            _lib.check(L.cmoop_net_set_int8_fused(self._h, C.c_int32(1)))
+            self.int8_fused = True
 
     def int8_ops(self):
         """``cmoop_net_int8_ops``: the ops that run integer under ``set_int8``, dicts keyed by ``quant.INT8_OP_FIELDS``."""
@@ -277,6 +292,15 @@ class NetSession:
         rows, n = np.zeros((cap, 16), np.int64), C.c_int32()
         _lib.check(_lib.lib().cmoop_net_int8_dw_ops(self._h, _lib.ptr(rows), C.c_int32(cap), C.byref(n)))
         return Q._int8_dw_rows(rows, n.value)
+
+    def int8_fused_ops(self):
+        """``cmoop_net_int8_fused_ops``: the ops that take the requantising epilogue under ``set_int8(True, fused=True)``, dicts
+        keyed by ``quant.INT8_FUSED_OP_FIELDS``."""
+        from . import quant as Q
+        cap = 64
+        rows, n = np.zeros((cap, 20), np.int64), C.c_int32()
+        _lib.check(_lib.lib().cmoop_net_int8_fused_ops(self._h, _lib.ptr(rows), C.c_int32(cap), C.byref(n)))
+        return Q._int8_fused_rows(rows, n.value)
 
     def _n_sites(self) -> int:
         n = C.c_int32()                                  # the net's own count: the session cannot disagree with what it wraps

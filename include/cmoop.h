@@ -603,7 +603,7 @@ int cmoop_eval_population_p(const cmoop_config* cfg, const cmoop_augment* aug, c
  *   GAPS: the first layer reads the resident feature tensor, which stays untouched; the operands of the residual add + ReLU stay
  *     fp32.  Symmetric signed ranges cost one bit on ReLU outputs.  Asymmetric or unsigned ranges, per-channel activation scales,
  *     learned clipping, a quantiser fused into the producers' epilogues (but for the depthwise producer of "Integer depthwise"
- *     below) and BatchNorm folding are out of scope (the conv and dense layers can be executed on int8 codes: "Integer
+ *     and the conv / dense producers of "Integer inference: requantising epilogue" below) and BatchNorm folding are out of scope (the conv and dense layers can be executed on int8 codes: "Integer
  *     inference" below).  It composes with the bf16 gemm modes, untested.
  *   The backward pass is not changed.  Weight gradients are formed with the quantised operands.  The x > 0 masks the dgrad / pool
  *     / GAP kernels already take from the layer input now read quantised values, so an element that rounds to code 0 passes no
@@ -662,8 +662,8 @@ int cmoop_fake_quant_act_time(float* x_dev, int64_t n, int32_t bits, const float
  *   ignored by integer ops.  Weights come through the existing weight stage (snapshots, EMA, cmoop_net_use_ema and pruning compose).
  * Kernels (int8.hip): implicit GEMM on v_mfma_i32_16x16x64_i8, Cin a multiple of 16, KS 1 / 3 / 5 at stride 1 or the 1x1 stride-2
  *   projection; 16-byte code loads, so code buffers must be 16-byte aligned.  No split-K, no atomics.
- * OUT OF SCOPE: integer BatchNorm / pool / add / GAP, BatchNorm folding, int8 outputs between layers (but for "Integer depthwise"
- *   below, the opt-in second level), asymmetric or per-channel activation scales, training on integer kernels, the population
+ * OUT OF SCOPE: integer BatchNorm / pool / add / GAP, BatchNorm folding, int8 outputs between layers (but for the opt-in levels
+ *   below: "Integer depthwise", the second, and "Integer inference: requantising epilogue", the third), asymmetric or per-channel activation scales, training on integer kernels, the population
  *   objectives. */
 /* the lone conv layer on the library stream: y_dev [B][ceil(H/stride)][ceil(W/stride)][Cout] fp32 from xq_dev [B][H][W][Cin] and
  * wq_dev [Cout][KS][KS][Cin] int8 codes (16-byte aligned), s_w_dev / bias_dev [Cout].  B == 0: success, nothing written */
@@ -730,6 +730,70 @@ int cmoop_dwconv_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s
  * kernel (C, KS, w_off % 16, scale_off % 4); count may be NULL */
 int cmoop_int8_dw_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows /* [cap][16] */,
                       int32_t cap, int32_t* count);
+/* ---- Integer inference: requantising epilogue, the third level (opt-in on top of integer inference, independent of "Integer
+ * depthwise"; BUILD-DEFINED; off by default) ------------------------------------------------------------------------------------
+ * THE arithmetic of a conv / dense op of cmoop_int8_ops whose output reaches an activation-quantisation site through per-channel
+ * elementwise ops only (quant.py restates it in numpy: conv_i8_q_ref / dense_i8_q_ref, with fma32_ref).  acc, s_x and s_w[c] as in
+ * "Integer inference"; scale[c] / shift[c] the fp32 vectors the eval BatchNorm prepares (cmoop_bn_eval_fwd's scale_dev / shift_dev);
+ * r_out the tracked range of the site written:
+ *     t = fl( fl( (float)acc * fl(s_x * s_w[c]) ) + bias[c] ) ;  t = fmaxf(t, 0) if the op has a ReLU      ("Integer inference")
+ *     with a BatchNorm only:  t = fma(t, scale[c], shift[c])     ONE rounding ;  t = fmaxf(t, 0) if that BatchNorm has relu_after
+ *     q, y = the tracked-mode code and dequantised value of t under r_out: cmoop_actquant's element arithmetic, unchanged
+ *   The affine is a fused multiply-add because the eval BatchNorm's apply kernel (scale_shift_kernel, compiled at the default
+ *   contraction setting) is one v_fma_f32 per element on gfx950.  The purpose of the definition is EQUALITY OF BYTES with the
+ *   un-fused chain (cmoop_conv_fwd_i8 -> cmoop_bn_eval_fwd -> cmoop_fake_quant_act_codes): where the device's chain disagrees with
+ *   this paragraph, the chain wins.  A scale with s > 0 false gives codes 0 and y = +0.0.
+ * Which ops (cmoop_int8_fused_ops): T0 -- the op's own output act is a site (every hidden dense layer; the first convolution of a
+ *   residual block and the pointwise halves when bn = 0); T1 -- the op's output is read only by an OP_BN that is not fused with a
+ *   pool, and that BatchNorm's output act is a site (res*_conv1 -> bn -> ReLU of topology A, and the same on A_ds' pointwise
+ *   halves).  Tails through a pool or the residual add, the skip projections, the output layer and the first convolution keep
+ *   their launches.
+ * In a net (cmoop_net_set_int8_fused, which needs cmoop_net_set_int8) such an op is ONE launch in an inference pass: for T1 the
+ *   BatchNorm's tiny prepare launch moves ahead of it; the fused launch writes the site's quantised fp32 tensor and its codes; the
+ *   scale_shift launch and the site's quantiser launch are not made.  The act between a T1 op and its BatchNorm is no longer
+ *   written (nothing else reads it: the plan walk asserts this).  Train steps never take it.  It composes with "Integer depthwise".
+ * Kernels (int8.hip, conv_i8_fwd_q_kernel / dense_i8_fwd_q_kernel): the tiles of "Integer inference" with this epilogue: a lane
+ *   holds four consecutive channels of an output row and stores the fp32 quad as one 16-byte store and the four codes as ONE
+ *   32-bit word.  Cout % 4 == 0, y 16-byte and codes 4-byte aligned; the same 32-bit index bounds; no atomics, no LDS.
+ * OUT OF SCOPE: code emission from the pool, add + ReLU, global-pool and first-layer producers; dropping the fp32 tensor of a site
+ *   whose readers are all integer ops; BatchNorm folding into the weights. */
+/* the lone requantising conv layer on the library stream: cmoop_conv_fwd_i8's operands, then bn_scale_dev / bn_shift_dev [Cout]
+ * (both NULL: no BatchNorm; one without the other: an error), relu_after (ignored without a BatchNorm), and the site written:
+ * the range *a_out (host, required) at out_bits in [2, 8]; y_dev [B][OH][OW][Cout] fp32 (16-byte aligned) receives the dequantised
+ * values and codes_dev (required, 4-byte aligned) the codes.  Cout % 4 != 0: an error.  B == 0: success, nothing written */
+int cmoop_conv_fwd_i8_q(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                        const float* bn_scale_dev, const float* bn_shift_dev, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                        int32_t KS, int32_t stride, int32_t relu, int32_t relu_after, int32_t out_bits, const float* a_out /* host */,
+                        float* y_dev, int8_t* codes_dev);
+/* average milliseconds of cmoop_conv_fwd_i8_q's launch, as cmoop_conv_fwd_i8_time */
+int cmoop_conv_fwd_i8_q_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                             const float* bn_scale_dev, const float* bn_shift_dev, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                             int32_t Cout, int32_t KS, int32_t stride, int32_t relu, int32_t relu_after, int32_t out_bits, const float* a_out,
+                             float* y_dev, int8_t* codes_dev, int32_t iters, double* avg_ms);
+/* the lone requantising dense layer: cmoop_dense_fwd_i8's operands and the tail of cmoop_conv_fwd_i8_q; y_dev [M][N], codes_dev
+ * [M][N].  N % 4 != 0: an error.  M == 0: success, nothing written */
+int cmoop_dense_fwd_i8_q(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                         const float* bn_scale_dev, const float* bn_shift_dev, int32_t M, int32_t N, int32_t K, int32_t relu,
+                         int32_t relu_after, int32_t out_bits, const float* a_out /* host */, float* y_dev, int8_t* codes_dev);
+/* average milliseconds of cmoop_dense_fwd_i8_q's launch */
+int cmoop_dense_fwd_i8_q_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                              const float* bn_scale_dev, const float* bn_shift_dev, int32_t M, int32_t N, int32_t K, int32_t relu,
+                              int32_t relu_after, int32_t out_bits, const float* a_out, float* y_dev, int8_t* codes_dev, int32_t iters,
+                              double* avg_ms);
+/* average milliseconds of cmoop_dense_fwd_i8's launch and of the eval BatchNorm's apply launch alone (y = fma(x, scale[c], shift[c]),
+ * then max(y, 0) under relu; x_dev / y_dev [M][C], C % 4 == 0), as cmoop_conv_fwd_i8_time: with cmoop_fake_quant_act_codes_time, the
+ * launches of the chain a requantising launch replaces */
+int cmoop_dense_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev, float* y_dev,
+                            int32_t M, int32_t N, int32_t K, int32_t relu, int32_t iters, double* avg_ms);
+int cmoop_scale_shift_time(const float* x_dev, float* y_dev, const float* scale_dev, const float* shift_dev, int64_t M, int32_t C,
+                           int32_t relu, int32_t iters, double* avg_ms);
+/* host-only: the ops of a candidate that take the requantising epilogue under cmoop_net_set_int8_fused, in op order: rows
+ * [count][20] = the op's cmoop_int8_ops row (16 fields, the last 0), then {the OP_BN's op index (-1: T0), that BatchNorm's
+ * relu_after (0 for T0), the output site, the act written (the site's)}.  Every row's first 16 fields are a row of cmoop_int8_ops.
+ * An error when cap is too small, when Cout % 4 != 0, when the act written is no site, or when the act between a T1 op and its
+ * BatchNorm has another reader; count may be NULL */
+int cmoop_int8_fused_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows /* [cap][20] */,
+                         int32_t cap, int32_t* count);
 /* the population call (above) with every argument: the other ten forward here.  aq NULL or disabled: cmoop_eval_population_p's
  * launches and bytes */
 int cmoop_eval_population_aq(const cmoop_config* cfg, const cmoop_augment* aug, const cmoop_loss* loss, const cmoop_distill* distill,
@@ -1078,6 +1142,15 @@ int cmoop_net_int8_ops(cmoop_net* net, int64_t* rows /* [cap][16] */, int32_t ca
 int cmoop_net_set_int8_depthwise(cmoop_net* net, int32_t on);
 /* cmoop_int8_dw_ops of this net's plan (host arithmetic; the level need not be on) */
 int cmoop_net_int8_dw_ops(cmoop_net* net, int64_t* rows /* [cap][16] */, int32_t cap, int32_t* count);
+/* The requantising epilogue ("Integer inference: requantising epilogue" above) of every following inference call of this net;
+ * train steps never take it.  on != 0 is refused, with a message and the net unchanged, unless cmoop_net_set_int8 is on; a net
+ * without a fusible op accepts it and nothing changes.  on == 0: off, and every launch and byte is that of the levels that stay
+ * on.  Turning cmoop_net_set_int8, cmoop_net_set_quant or cmoop_net_set_actquant off turns it off as well.  While it is on, an
+ * inference pass does not write the act between a fused op and its BatchNorm (cmoop_net_get_act then returns what an earlier
+ * pass or step left there) */
+int cmoop_net_set_int8_fused(cmoop_net* net, int32_t on);
+/* cmoop_int8_fused_ops of this net's plan (host arithmetic; the level need not be on) */
+int cmoop_net_int8_fused_ops(cmoop_net* net, int64_t* rows /* [cap][20] */, int32_t cap, int32_t* count);
 /* debug read-out of act index i of the plan: dims (may be NULL) = {H, W, C, 1 if materialised, 1 if it has a gradient buffer,
  * the number of acts}; data_host / grad_host (either may be NULL; both NULL: dims only) receive the first B rows of the data and
  * of the gradient as the last step or pass left them.  An error for an act that is never materialised. */
