@@ -620,7 +620,7 @@ int cmoop_conv_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, con
                       int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t stride, int32_t relu) {
     return guard([&] {
         hipStream_t s = lib_stream();
-        launch_conv_i8_fwd(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, B, H, W, Cin, Cout, KS, stride, relu, s);
+        launch_i8_fwd(I8Layer{true, B, H, W, Cin, Cout, KS, stride}, xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, relu, nullptr, s);
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
@@ -629,7 +629,7 @@ int cmoop_dense_fwd_i8(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, co
                        int32_t M, int32_t N, int32_t K, int32_t relu) {
     return guard([&] {
         hipStream_t s = lib_stream();
-        launch_dense_i8_fwd(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, M, N, K, relu, s);
+        launch_i8_fwd(I8Layer::dense(M, N, K), xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, relu, nullptr, s);
         CMOOP_HIP(hipStreamSynchronize(s));
     });
 }
@@ -640,9 +640,8 @@ int cmoop_conv_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_x
     return guard([&] {
         CMOOP_REQUIRE(avg_ms && iters >= 1, "conv_fwd_i8_time: iters >= 1 and avg_ms");
         hipStream_t s = lib_stream();
-        *avg_ms = time_launches(s, iters, [&] {
-            launch_conv_i8_fwd(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, B, H, W, Cin, Cout, KS, stride, relu, s);
-        });
+        const I8Layer L{true, B, H, W, Cin, Cout, KS, stride};
+        *avg_ms = time_launches(s, iters, [&] { launch_i8_fwd(L, xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, relu, nullptr, s); });
     });
 }
 
@@ -651,7 +650,8 @@ int cmoop_dense_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s_
     return guard([&] {
         CMOOP_REQUIRE(avg_ms && iters >= 1, "dense_fwd_i8_time: iters >= 1 and avg_ms");
         hipStream_t s = lib_stream();
-        *avg_ms = time_launches(s, iters, [&] { launch_dense_i8_fwd(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, M, N, K, relu, s); });
+        const I8Layer L = I8Layer::dense(M, N, K);
+        *avg_ms = time_launches(s, iters, [&] { launch_i8_fwd(L, xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, relu, nullptr, s); });
     });
 }
 
@@ -666,35 +666,68 @@ int cmoop_scale_shift_time(const float* x_dev, float* y_dev, const float* scale_
     });
 }
 
-// rows [count][16] of cmoop_int8_ops from a plan
-static void int8_ops_abi(const NetPlan& plan, int64_t* rows, int32_t cap, int32_t* count) {
-    const std::vector<Int8Op> ops = int8_ops(plan);
-    CMOOP_REQUIRE(rows && cap >= (int32_t)ops.size(), "int8_ops: the rows buffer is too small");
-    for (size_t i = 0; i < ops.size(); ++i) {
-        const Op& op = plan.ops[ops[i].op];
-        const int64_t v[16] = {ops[i].op, op.kind == OP_DENSE ? 1 : 0, ops[i].in, ops[i].out, ops[i].site, op.H, op.W, op.Cin, op.Cout,
-                               op.KS, op.stride, op.relu, op.w_off, op.b_off, ops[i].scale_off, 0};
-        std::memcpy(rows + 16 * i, v, sizeof(v));
+// The plan rows of one level of integer inference -- 0: cmoop_int8_ops [count][16], 1: cmoop_int8_dw_ops [count][16], 2:
+// cmoop_int8_fused_ops [count][20], a level-0 row and four more columns.  Only level 0 refuses a NULL rows for an empty plan
+static const char* const INT8_PLAN_NAME[3] = {"int8_ops", "int8_dw_ops", "int8_fused_ops"};
+
+static void int8_rows_abi(int level, const NetPlan& plan, int64_t* rows, int32_t cap, int32_t* count) {
+    std::vector<int64_t> v;
+    auto matrix_row = [&](const Int8Op& o) {
+        const Op& op = plan.ops[o.op];
+        v.insert(v.end(), {o.op, op.kind == OP_DENSE ? 1 : 0, o.in, o.out, o.site, op.H, op.W, op.Cin, op.Cout, op.KS, op.stride, op.relu, op.w_off,
+                           op.b_off, o.scale_off, 0});
+    };
+    if (level == 0) {
+        for (const Int8Op& o : int8_ops(plan)) matrix_row(o);
+    } else if (level == 1) {
+        for (const Int8DwOp& o : int8_dw_ops(plan)) {
+            const Op& op = plan.ops[o.op];
+            v.insert(v.end(), {o.op, 2, o.in, o.out, o.site, op.H, op.W, op.Cin, op.Cin, op.KS, 1, 0, op.w_off, -1, o.scale_off, o.out_site});
+        }
+    } else {
+        for (const Int8FusedOp& o : int8_fused_ops(plan)) {
+            matrix_row(o.i8);
+            v.insert(v.end(), {o.bn, o.relu_after, o.out_site, o.site_act});
+        }
     }
-    if (count) *count = (int32_t)ops.size();
+    const int32_t n = (int32_t)(v.size() / (level == 2 ? 20 : 16));
+    CMOOP_REQUIRE((rows || (level != 0 && n == 0)) && cap >= n, std::string(INT8_PLAN_NAME[level]) + ": the rows buffer is too small");
+    if (n) std::memcpy(rows, v.data(), v.size() * sizeof(int64_t));
+    if (count) *count = n;
 }
 
-int cmoop_int8_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap,
-                   int32_t* count) {
+static int int8_plan_abi(int level, const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap,
+                         int32_t* count) {
     return guard([&] {
-        CMOOP_REQUIRE(gene != nullptr && T >= 1 && F >= 1, "int8_ops: NULL gene or an empty patch");
+        CMOOP_REQUIRE(gene != nullptr && T >= 1 && F >= 1, std::string(INT8_PLAN_NAME[level]) + ": NULL gene or an empty patch");
         NetConfig cfg;
         cfg.variant = variant; cfg.classes = classes;
-        int8_ops_abi(plan_net(gene, cfg, T, F), rows, cap, count);
+        int8_rows_abi(level, plan_net(gene, cfg, T, F), rows, cap, count);
     });
 }
 
-// the lone requantising conv (conv: true) / dense layer; avg_ms non-null: timed over `iters` launches.  Dense: B rows, H = N, W = K
-static void fwd_i8_q_abi(bool conv, const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
-                         const float* bn_scale_dev, const float* bn_shift_dev, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
-                         int32_t KS, int32_t stride, int32_t relu, int32_t relu_after, int32_t out_bits, const float* a_out, float* y_dev,
-                         int8_t* codes_dev, int32_t iters, double* avg_ms) {
-    const std::string who = conv ? "conv_fwd_i8_q" : "dense_fwd_i8_q";
+static int int8_net_plan_abi(int level, cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) {
+    return guard([&] {
+        CMOOP_REQUIRE(h && h->net, std::string(INT8_PLAN_NAME[level]) + ": NULL net");
+        int8_rows_abi(level, h->net->plan(), rows, cap, count);
+    });
+}
+
+int cmoop_int8_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap, int32_t* count) {
+    return int8_plan_abi(0, gene, variant, classes, T, F, rows, cap, count);
+}
+int cmoop_int8_dw_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap, int32_t* count) {
+    return int8_plan_abi(1, gene, variant, classes, T, F, rows, cap, count);
+}
+int cmoop_int8_fused_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap, int32_t* count) {
+    return int8_plan_abi(2, gene, variant, classes, T, F, rows, cap, count);
+}
+
+// the lone requantising conv / dense layer L under the range *a_out; avg_ms non-null: timed over `iters` launches
+static void fwd_i8_q_abi(const I8Layer& L, const int8_t* xq_dev, const int8_t* wq_dev, float s_x, const float* s_w_dev, const float* bias_dev,
+                         const float* bn_scale_dev, const float* bn_shift_dev, int32_t relu, int32_t relu_after, int32_t out_bits,
+                         const float* a_out, float* y_dev, int8_t* codes_dev, int32_t iters, double* avg_ms) {
+    const std::string who = L.conv ? "conv_fwd_i8_q" : "dense_fwd_i8_q";
     CMOOP_REQUIRE(a_out != nullptr, who + ": the output range (a_out) is required");
     CMOOP_REQUIRE(out_bits >= 2 && out_bits <= 8, who + ": output bits must be in [2, 8]");
     hipStream_t s = lib_stream();
@@ -703,14 +736,8 @@ static void fwd_i8_q_abi(bool conv, const int8_t* xq_dev, const int8_t* wq_dev, 
     ActRange* rec_dev = pool.get<ActRange>(sizeof(ActRange));
     CMOOP_HIP(hipMemcpyAsync(rec_dev, &rec, sizeof(rec), hipMemcpyHostToDevice, s));
     CMOOP_HIP(hipStreamSynchronize(s));            // rec is this frame's
-    auto once = [&] {
-        if (conv)
-            launch_conv_i8_fwd_q(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, relu_after, rec_dev, out_bits,
-                                 y_dev, codes_dev, B, H, W, Cin, Cout, KS, stride, relu, s);
-        else
-            launch_dense_i8_fwd_q(xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, relu_after, rec_dev, out_bits,
-                                  y_dev, codes_dev, B, H, W, relu, s);
-    };
+    const I8Requant rq{bn_scale_dev, bn_shift_dev, relu_after, rec_dev, out_bits, codes_dev};
+    auto once = [&] { launch_i8_fwd(L, xq_dev, wq_dev, s_x, nullptr, 0, s_w_dev, bias_dev, y_dev, relu, &rq, s); };
     if (avg_ms) *avg_ms = time_launches(s, iters, once);
     else once();
     CMOOP_HIP(hipStreamSynchronize(s));
@@ -721,8 +748,8 @@ int cmoop_conv_fwd_i8_q(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, c
                         int32_t KS, int32_t stride, int32_t relu, int32_t relu_after, int32_t out_bits, const float* a_out, float* y_dev,
                         int8_t* codes_dev) {
     return guard([&] {
-        fwd_i8_q_abi(true, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, B, H, W, Cin, Cout, KS, stride, relu, relu_after,
-                     out_bits, a_out, y_dev, codes_dev, 0, nullptr);
+        fwd_i8_q_abi(I8Layer{true, B, H, W, Cin, Cout, KS, stride}, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, relu,
+                   relu_after, out_bits, a_out, y_dev, codes_dev, 0, nullptr);
     });
 }
 
@@ -732,8 +759,8 @@ int cmoop_conv_fwd_i8_q_time(const int8_t* xq_dev, const int8_t* wq_dev, float s
                              float* y_dev, int8_t* codes_dev, int32_t iters, double* avg_ms) {
     return guard([&] {
         CMOOP_REQUIRE(avg_ms && iters >= 1, "conv_fwd_i8_q_time: iters >= 1 and avg_ms");
-        fwd_i8_q_abi(true, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, B, H, W, Cin, Cout, KS, stride, relu, relu_after,
-                     out_bits, a_out, y_dev, codes_dev, iters, avg_ms);
+        fwd_i8_q_abi(I8Layer{true, B, H, W, Cin, Cout, KS, stride}, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, relu,
+                   relu_after, out_bits, a_out, y_dev, codes_dev, iters, avg_ms);
     });
 }
 
@@ -741,8 +768,8 @@ int cmoop_dense_fwd_i8_q(const int8_t* xq_dev, const int8_t* wq_dev, float s_x, 
                          const float* bn_scale_dev, const float* bn_shift_dev, int32_t M, int32_t N, int32_t K, int32_t relu,
                          int32_t relu_after, int32_t out_bits, const float* a_out, float* y_dev, int8_t* codes_dev) {
     return guard([&] {
-        fwd_i8_q_abi(false, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, M, N, K, 0, 0, 1, 1, relu, relu_after, out_bits,
-                     a_out, y_dev, codes_dev, 0, nullptr);
+        fwd_i8_q_abi(I8Layer::dense(M, N, K), xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, relu, relu_after, out_bits,
+                   a_out, y_dev, codes_dev, 0, nullptr);
     });
 }
 
@@ -752,32 +779,8 @@ int cmoop_dense_fwd_i8_q_time(const int8_t* xq_dev, const int8_t* wq_dev, float 
                               double* avg_ms) {
     return guard([&] {
         CMOOP_REQUIRE(avg_ms && iters >= 1, "dense_fwd_i8_q_time: iters >= 1 and avg_ms");
-        fwd_i8_q_abi(false, xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, M, N, K, 0, 0, 1, 1, relu, relu_after, out_bits,
-                     a_out, y_dev, codes_dev, iters, avg_ms);
-    });
-}
-
-// rows [count][20] of cmoop_int8_fused_ops from a plan
-static void int8_fused_ops_abi(const NetPlan& plan, int64_t* rows, int32_t cap, int32_t* count) {
-    const std::vector<Int8FusedOp> ops = int8_fused_ops(plan);
-    CMOOP_REQUIRE((rows || ops.empty()) && cap >= (int32_t)ops.size(), "int8_fused_ops: the rows buffer is too small");
-    for (size_t i = 0; i < ops.size(); ++i) {
-        const Int8Op& o = ops[i].i8;
-        const Op& op = plan.ops[o.op];
-        const int64_t v[20] = {o.op, op.kind == OP_DENSE ? 1 : 0, o.in, o.out, o.site, op.H, op.W, op.Cin, op.Cout, op.KS, op.stride, op.relu,
-                               op.w_off, op.b_off, o.scale_off, 0, ops[i].bn, ops[i].relu_after, ops[i].out_site, ops[i].site_act};
-        std::memcpy(rows + 20 * i, v, sizeof(v));
-    }
-    if (count) *count = (int32_t)ops.size();
-}
-
-int cmoop_int8_fused_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap,
-                         int32_t* count) {
-    return guard([&] {
-        CMOOP_REQUIRE(gene != nullptr && T >= 1 && F >= 1, "int8_fused_ops: NULL gene or an empty patch");
-        NetConfig cfg;
-        cfg.variant = variant; cfg.classes = classes;
-        int8_fused_ops_abi(plan_net(gene, cfg, T, F), rows, cap, count);
+        fwd_i8_q_abi(I8Layer::dense(M, N, K), xq_dev, wq_dev, s_x, s_w_dev, bias_dev, bn_scale_dev, bn_shift_dev, relu, relu_after, out_bits,
+                   a_out, y_dev, codes_dev, iters, avg_ms);
     });
 }
 
@@ -813,29 +816,6 @@ int cmoop_dwconv_fwd_i8_time(const int8_t* xq_dev, const int8_t* wq_dev, float s
     return guard([&] {
         CMOOP_REQUIRE(avg_ms && iters >= 1, "dwconv_fwd_i8_time: iters >= 1 and avg_ms");
         dwconv_fwd_i8_abi(xq_dev, wq_dev, s_x, s_w_dev, B, H, W, C, KS, out_bits, a_out, y_dev, codes_dev, iters, avg_ms);
-    });
-}
-
-// rows [count][16] of cmoop_int8_dw_ops from a plan
-static void int8_dw_ops_abi(const NetPlan& plan, int64_t* rows, int32_t cap, int32_t* count) {
-    const std::vector<Int8DwOp> ops = int8_dw_ops(plan);
-    CMOOP_REQUIRE((rows || ops.empty()) && cap >= (int32_t)ops.size(), "int8_dw_ops: the rows buffer is too small");
-    for (size_t i = 0; i < ops.size(); ++i) {
-        const Op& op = plan.ops[ops[i].op];
-        const int64_t v[16] = {ops[i].op, 2, ops[i].in, ops[i].out, ops[i].site, op.H, op.W, op.Cin, op.Cin, op.KS, 1, 0, op.w_off, -1,
-                               ops[i].scale_off, ops[i].out_site};
-        std::memcpy(rows + 16 * i, v, sizeof(v));
-    }
-    if (count) *count = (int32_t)ops.size();
-}
-
-int cmoop_int8_dw_ops(const int32_t gene[6], int32_t variant, int32_t classes, int32_t T, int32_t F, int64_t* rows, int32_t cap,
-                      int32_t* count) {
-    return guard([&] {
-        CMOOP_REQUIRE(gene != nullptr && T >= 1 && F >= 1, "int8_dw_ops: NULL gene or an empty patch");
-        NetConfig cfg;
-        cfg.variant = variant; cfg.classes = classes;
-        int8_dw_ops_abi(plan_net(gene, cfg, T, F), rows, cap, count);
     });
 }
 
@@ -1895,36 +1875,21 @@ int cmoop_net_set_int8(cmoop_net* h, int32_t on) {
         h->net->set_int8(on != 0);
     });
 }
-int cmoop_net_int8_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) {
-    return guard([&] {
-        CMOOP_REQUIRE(h && h->net, "int8_ops: NULL net");
-        int8_ops_abi(h->net->plan(), rows, cap, count);
-    });
-}
+int cmoop_net_int8_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) { return int8_net_plan_abi(0, h, rows, cap, count); }
 int cmoop_net_set_int8_depthwise(cmoop_net* h, int32_t on) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "set_int8_depthwise: NULL net");
         h->net->set_int8_depthwise(on != 0);
     });
 }
-int cmoop_net_int8_dw_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) {
-    return guard([&] {
-        CMOOP_REQUIRE(h && h->net, "int8_dw_ops: NULL net");
-        int8_dw_ops_abi(h->net->plan(), rows, cap, count);
-    });
-}
+int cmoop_net_int8_dw_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) { return int8_net_plan_abi(1, h, rows, cap, count); }
 int cmoop_net_set_int8_fused(cmoop_net* h, int32_t on) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "set_int8_fused: NULL net");
         h->net->set_int8_fused(on != 0);
     });
 }
-int cmoop_net_int8_fused_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) {
-    return guard([&] {
-        CMOOP_REQUIRE(h && h->net, "int8_fused_ops: NULL net");
-        int8_fused_ops_abi(h->net->plan(), rows, cap, count);
-    });
-}
+int cmoop_net_int8_fused_ops(cmoop_net* h, int64_t* rows, int32_t cap, int32_t* count) { return int8_net_plan_abi(2, h, rows, cap, count); }
 int cmoop_net_get_act(cmoop_net* h, int32_t i, int32_t B, int32_t dims[6], float* data_host, float* grad_host) {
     return guard([&] {
         CMOOP_REQUIRE(h && h->net, "get_act: NULL net");

@@ -159,8 +159,7 @@ __device__ __forceinline__ void i8_tile(const int8_t* __restrict__ xq, const int
                     quant_element(t, s_out, live, q.qmax_out, qc[r], v[r]);
                 }
                 *reinterpret_cast<f32x4*>(out) = f32x4{v[0], v[1], v[2], v[3]};
-                *reinterpret_cast<uint32_t*>(q.codes + m * g.Cout + n) = ((uint32_t)qc[0] & 0xFFu) | (((uint32_t)qc[1] & 0xFFu) << 8) |
-                                                                         (((uint32_t)qc[2] & 0xFFu) << 16) | (((uint32_t)qc[3] & 0xFFu) << 24);
+                *reinterpret_cast<uint32_t*>(q.codes + m * g.Cout + n) = quant_pack4(qc);
             } else if (e.vec) {
                 *reinterpret_cast<f32x4*>(out) = f32x4{v[0], v[1], v[2], v[3]};
             } else {
@@ -197,20 +196,6 @@ __global__ __launch_bounds__(256) void dense_i8_fwd_q_kernel(const int8_t* __res
 }
 
 constexpr int64_t I8_MAX_ELEMS = ((int64_t)1 << 31) - 1;   // every operand and the output: 32-bit index math
-
-void i8_check_common(const void* xq, const void* wq, const float* s_w, const float* bias, const float* y, int64_t x_elems,
-                     int64_t M, int64_t K, int Cout, const char* who) {
-    const std::string w(who);
-    CMOOP_REQUIRE(K >= 16 && K % 16 == 0, w + ": the reduction must be whole 16-channel fragments");
-    // |acc| <= 127 * 127 * K must stay inside int32 (the largest layer of the search space, 512 -> 512 k5: K = 12800)
-    CMOOP_REQUIRE((int64_t)127 * 127 * K < ((int64_t)1 << 31), w + ": 127^2 K must stay below 2^31 (exact int32 accumulation)");
-    CMOOP_REQUIRE(Cout >= 1 && x_elems <= I8_MAX_ELEMS && M * Cout <= I8_MAX_ELEMS && (int64_t)Cout * K <= I8_MAX_ELEMS,
-                  w + ": operands and output must stay below 2^31 elements (32-bit index math)");
-    CMOOP_REQUIRE(xq && wq && s_w && bias && y, w + ": NULL buffer");
-    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(xq) % 16 == 0 && reinterpret_cast<uintptr_t>(wq) % 16 == 0,
-                  w + ": code buffers must be aligned to 16 bytes");
-    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(y) % 4 == 0, w + ": y must be aligned to 4 bytes");
-}
 
 // ---- integer depthwise (include/cmoop.h, "Integer depthwise") -------------------------------------------------------------------
 // dwconv_fwd_kernel's work split on int8 codes: work item = (sample, run of RH image rows, column), a lane owns 4 channels of
@@ -304,8 +289,7 @@ __global__ __launch_bounds__(256) void dwconv_i8_fwd_kernel(const DwI8Args a) {
                     v[e] = yq;
                 }
                 if (a.codes)
-                    *reinterpret_cast<uint32_t*>(a.codes + o) = ((uint32_t)qc[0] & 0xFFu) | (((uint32_t)qc[1] & 0xFFu) << 8) |
-                                                                (((uint32_t)qc[2] & 0xFFu) << 16) | (((uint32_t)qc[3] & 0xFFu) << 24);
+                    *reinterpret_cast<uint32_t*>(a.codes + o) = quant_pack4(qc);
             }
             *reinterpret_cast<f32x4*>(a.y + o) = v;
         }
@@ -315,16 +299,26 @@ __global__ __launch_bounds__(256) void dwconv_i8_fwd_kernel(const DwI8Args a) {
     }
 }
 
+// THE shape rules of the integer kernels, one predicate per refusal: the launchers' checks and the plan's predicates
+// (int8_layer_ok / int8_dw_layer_ok) are made of these
+bool i8_ks_ok(int KS) { return KS == 1 || KS == 3 || KS == 5; }
+bool i8_stride_ok(int KS, int stride) { return stride == 1 || (stride == 2 && KS == 1); }
+bool i8_cin_ok(int Cin) { return Cin >= 16 && Cin % 16 == 0; }
+// |acc| <= 127 * 127 * K must stay inside int32 (the largest layer of the search space, 512 -> 512 k5: K = 12800)
+bool i8_acc_ok(int64_t K) { return (int64_t)127 * 127 * K < ((int64_t)1 << 31); }
+bool dwi8_ks_ok(int KS) { return KS == 3 || KS == 5; }
+bool dwi8_channels_ok(int C) { return C >= 16 && C <= 512 && ilog2_exact(C) >= 0; }
+
 }  // namespace
 
-bool int8_dw_layer_ok(int C, int KS) { return C >= 16 && C <= 512 && ilog2_exact(C) >= 0 && (KS == 3 || KS == 5); }
+bool int8_dw_layer_ok(int C, int KS) { return dwi8_channels_ok(C) && dwi8_ks_ok(KS); }
 
 void launch_dwconv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec_in, int act_bits, const float* s_w,
                           const ActRange* rec_out, int out_bits, float* y, int8_t* codes, int B, int H, int W, int C, int KS,
                           hipStream_t s) {
     CMOOP_REQUIRE(B >= 0 && H >= 1 && W >= 1, "dwconv_fwd_i8: empty image");
-    CMOOP_REQUIRE(KS == 3 || KS == 5, "dwconv_fwd_i8: KS must be 3 or 5");
-    CMOOP_REQUIRE(C >= 16 && C <= 512 && ilog2_exact(C) >= 0, "dwconv_fwd_i8: channels must be a power of two in 16..512");
+    CMOOP_REQUIRE(dwi8_ks_ok(KS), "dwconv_fwd_i8: KS must be 3 or 5");
+    CMOOP_REQUIRE(dwi8_channels_ok(C), "dwconv_fwd_i8: channels must be a power of two in 16..512");
     CMOOP_REQUIRE(!rec_in || (act_bits >= 2 && act_bits <= 8), "dwconv_fwd_i8: activation bits must be in [2, 8]");
     CMOOP_REQUIRE(!rec_out || (out_bits >= 2 && out_bits <= 8), "dwconv_fwd_i8: output bits must be in [2, 8]");
     CMOOP_REQUIRE(!codes || rec_out, "dwconv_fwd_i8: codes are written only under an output range");
@@ -357,105 +351,64 @@ void launch_dwconv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const A
 }
 
 bool int8_layer_ok(int Cin, int Cout, int KS, int stride) {
-    return Cin >= 16 && Cin % 16 == 0 && Cout >= 1 && (KS == 1 || KS == 3 || KS == 5) && (stride == 1 || (stride == 2 && KS == 1)) &&
-           (int64_t)127 * 127 * KS * KS * Cin < ((int64_t)1 << 31);
+    return i8_cin_ok(Cin) && Cout >= 1 && i8_ks_ok(KS) && i8_stride_ok(KS, stride) && i8_acc_ok((int64_t)KS * KS * Cin);
 }
 
-void launch_conv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
-                        const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int KS, int stride, int relu,
-                        hipStream_t s) {
-    CMOOP_REQUIRE(B >= 0 && H >= 1 && W >= 1, "conv_fwd_i8: empty image");
-    CMOOP_REQUIRE(KS == 1 || KS == 3 || KS == 5, "conv_fwd_i8: KS must be 1, 3 or 5");
-    CMOOP_REQUIRE(stride == 1 || (stride == 2 && KS == 1), "conv_fwd_i8: stride 1, or the 1x1 stride-2 projection");
-    CMOOP_REQUIRE(Cin >= 16 && Cin % 16 == 0, "conv_fwd_i8: Cin must be a multiple of 16");
-    CMOOP_REQUIRE(!rec || (act_bits >= 2 && act_bits <= 8), "conv_fwd_i8: activation bits must be in [2, 8]");
-    if (B == 0) return;
-    const int64_t OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
-    const int64_t M = (int64_t)B * OH * OW, K = (int64_t)KS * KS * Cin;
-    i8_check_common(xq, wq, s_w, bias, y, (int64_t)B * H * W * Cin, M, K, Cout, "conv_fwd_i8");
-    const ConvGeom cg = conv_geometry(B, H, W, Cin, Cout, KS, stride);
-    const I8Geom g{H, W, Cin, cg.OH, cg.OW, Cout, KS, stride, cg.pad_t, cg.pad_l, (int)M, (int)(K / 16), Cin / 16};
+// the four kernel families at one NT; the conv tiles are two row blocks high, the dense tiles one
+template <int NT>
+static void i8_launch_nt(bool conv, dim3 grid, hipStream_t s, const int8_t* xq, const int8_t* wq, float* y, const I8Geom& g, const I8Epi& e,
+                         const I8Req* q) {
+    if (conv && q) hipLaunchKernelGGL((conv_i8_fwd_q_kernel<2, NT>), grid, dim3(256), 0, s, xq, wq, y, g, e, *q);
+    else if (conv) hipLaunchKernelGGL((conv_i8_fwd_kernel<2, NT>), grid, dim3(256), 0, s, xq, wq, y, g, e);
+    else if (q) hipLaunchKernelGGL((dense_i8_fwd_q_kernel<1, NT>), grid, dim3(256), 0, s, xq, wq, y, g, e, *q);
+    else hipLaunchKernelGGL((dense_i8_fwd_kernel<1, NT>), grid, dim3(256), 0, s, xq, wq, y, g, e);
+}
+
+void launch_i8_fwd(const I8Layer& L, const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
+                   const float* bias, float* y, int relu, const I8Requant* rq, hipStream_t s) {
+    const std::string w = std::string(L.conv ? "conv_fwd_i8" : "dense_fwd_i8") + (rq ? "_q" : "");
+    const int Cout = L.Cout;
+    if (L.conv) {
+        CMOOP_REQUIRE(L.B >= 0 && L.H >= 1 && L.W >= 1, w + ": empty image");
+        CMOOP_REQUIRE(i8_ks_ok(L.KS), w + ": KS must be 1, 3 or 5");
+        CMOOP_REQUIRE(i8_stride_ok(L.KS, L.stride), w + ": stride 1, or the 1x1 stride-2 projection");
+        CMOOP_REQUIRE(i8_cin_ok(L.Cin), w + ": Cin must be a multiple of 16");
+    } else {
+        CMOOP_REQUIRE(L.B >= 0 && Cout >= 1, w + ": M >= 0 and N >= 1");
+        CMOOP_REQUIRE(i8_cin_ok(L.Cin), w + ": K must be a multiple of 16");
+    }
+    CMOOP_REQUIRE(!rec || (act_bits >= 2 && act_bits <= 8), w + ": activation bits must be in [2, 8]");
+    I8Req q{};
+    if (rq) {   // the checks the requantising epilogue adds, ahead of the empty-batch return
+        CMOOP_REQUIRE(Cout % 4 == 0, w + ": Cout must be a multiple of 4 (a lane stores four channels as one word of codes)");
+        CMOOP_REQUIRE((rq->bn_scale != nullptr) == (rq->bn_shift != nullptr), w + ": bn_scale and bn_shift come together or not at all");
+        CMOOP_REQUIRE(rq->rec_out != nullptr, w + ": the record of the site written is required");
+        CMOOP_REQUIRE(rq->out_bits >= 2 && rq->out_bits <= 8, w + ": output bits must be in [2, 8]");
+        CMOOP_REQUIRE(rq->codes != nullptr, w + ": NULL codes");
+        CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(y) % 16 == 0, w + ": y must be aligned to 16 bytes");
+        CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(rq->codes) % 4 == 0, w + ": the output codes must be aligned to 4 bytes");
+        q = I8Req{rq->bn_scale, rq->bn_shift, rq->rec_out, rq->codes, (float)quant_qmax(rq->out_bits), rq->relu_after};
+    }
+    if (L.B == 0) return;
+    const int64_t OH = (L.H + L.stride - 1) / L.stride, OW = (L.W + L.stride - 1) / L.stride;
+    const int64_t M = (int64_t)L.B * OH * OW, K = (int64_t)L.KS * L.KS * L.Cin;
+    CMOOP_REQUIRE(K >= 16 && K % 16 == 0, w + ": the reduction must be whole 16-channel fragments");
+    CMOOP_REQUIRE(i8_acc_ok(K), w + ": 127^2 K must stay below 2^31 (exact int32 accumulation)");
+    CMOOP_REQUIRE(Cout >= 1 && (int64_t)L.B * L.H * L.W * L.Cin <= I8_MAX_ELEMS && M * Cout <= I8_MAX_ELEMS && (int64_t)Cout * K <= I8_MAX_ELEMS,
+                  w + ": operands and output must stay below 2^31 elements (32-bit index math)");
+    CMOOP_REQUIRE(xq && wq && s_w && bias && y, w + ": NULL buffer");
+    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(xq) % 16 == 0 && reinterpret_cast<uintptr_t>(wq) % 16 == 0,
+                  w + ": code buffers must be aligned to 16 bytes");
+    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(y) % 4 == 0, w + ": y must be aligned to 4 bytes");
+    const ConvGeom cg = conv_geometry(L.B, L.H, L.W, L.Cin, Cout, L.KS, L.stride);   // dense (1 x 1, KS 1): OH = OW = 1, no padding
+    const I8Geom g{L.H, L.W, L.Cin, cg.OH, cg.OW, Cout, L.KS, L.stride, cg.pad_t, cg.pad_l, (int)M, (int)(K / 16), L.Cin / 16};
     const I8Epi e{s_w, bias, rec, s_x, rec ? (float)quant_qmax(act_bits) : 0.f, relu,
-                  (reinterpret_cast<uintptr_t>(y) % 16 == 0 && Cout % 4 == 0) ? 1 : 0};
-    constexpr int MT = 2;
-    const unsigned gx = (unsigned)cdiv64(M, 64 * MT);
-    if (Cout > 32) hipLaunchKernelGGL((conv_i8_fwd_kernel<MT, 4>), dim3(gx, (unsigned)cdiv(Cout, 64)), dim3(256), 0, s, xq, wq, y, g, e);
-    else if (Cout > 16) hipLaunchKernelGGL((conv_i8_fwd_kernel<MT, 2>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e);
-    else hipLaunchKernelGGL((conv_i8_fwd_kernel<MT, 1>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e);
-    CMOOP_HIP(hipGetLastError());
-}
-
-// the checks the requantising launchers add to i8_check_common, and the I8Req they pass
-static I8Req i8_req_args(const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out, int out_bits, const float* y,
-                  int8_t* codes, int Cout, const char* who) {
-    const std::string w(who);
-    CMOOP_REQUIRE(Cout % 4 == 0, w + ": Cout must be a multiple of 4 (a lane stores four channels as one word of codes)");
-    CMOOP_REQUIRE((bn_scale != nullptr) == (bn_shift != nullptr), w + ": bn_scale and bn_shift come together or not at all");
-    CMOOP_REQUIRE(rec_out != nullptr, w + ": the record of the site written is required");
-    CMOOP_REQUIRE(out_bits >= 2 && out_bits <= 8, w + ": output bits must be in [2, 8]");
-    CMOOP_REQUIRE(codes != nullptr, w + ": NULL codes");
-    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(y) % 16 == 0, w + ": y must be aligned to 16 bytes");
-    CMOOP_REQUIRE(reinterpret_cast<uintptr_t>(codes) % 4 == 0, w + ": the output codes must be aligned to 4 bytes");
-    return I8Req{bn_scale, bn_shift, rec_out, codes, (float)quant_qmax(out_bits), relu_after};
-}
-
-void launch_conv_i8_fwd_q(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
-                          const float* bias, const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out,
-                          int out_bits, float* y, int8_t* codes, int B, int H, int W, int Cin, int Cout, int KS, int stride, int relu,
-                          hipStream_t s) {
-    CMOOP_REQUIRE(B >= 0 && H >= 1 && W >= 1, "conv_fwd_i8_q: empty image");
-    CMOOP_REQUIRE(KS == 1 || KS == 3 || KS == 5, "conv_fwd_i8_q: KS must be 1, 3 or 5");
-    CMOOP_REQUIRE(stride == 1 || (stride == 2 && KS == 1), "conv_fwd_i8_q: stride 1, or the 1x1 stride-2 projection");
-    CMOOP_REQUIRE(Cin >= 16 && Cin % 16 == 0, "conv_fwd_i8_q: Cin must be a multiple of 16");
-    CMOOP_REQUIRE(!rec || (act_bits >= 2 && act_bits <= 8), "conv_fwd_i8_q: activation bits must be in [2, 8]");
-    const I8Req q = i8_req_args(bn_scale, bn_shift, relu_after, rec_out, out_bits, y, codes, Cout, "conv_fwd_i8_q");
-    if (B == 0) return;
-    const int64_t OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
-    const int64_t M = (int64_t)B * OH * OW, K = (int64_t)KS * KS * Cin;
-    i8_check_common(xq, wq, s_w, bias, y, (int64_t)B * H * W * Cin, M, K, Cout, "conv_fwd_i8_q");
-    const ConvGeom cg = conv_geometry(B, H, W, Cin, Cout, KS, stride);
-    const I8Geom g{H, W, Cin, cg.OH, cg.OW, Cout, KS, stride, cg.pad_t, cg.pad_l, (int)M, (int)(K / 16), Cin / 16};
-    const I8Epi e{s_w, bias, rec, s_x, rec ? (float)quant_qmax(act_bits) : 0.f, relu, 1};
-    constexpr int MT = 2;                              // launch_conv_i8_fwd's tiles and grid
-    const unsigned gx = (unsigned)cdiv64(M, 64 * MT);
-    if (Cout > 32) hipLaunchKernelGGL((conv_i8_fwd_q_kernel<MT, 4>), dim3(gx, (unsigned)cdiv(Cout, 64)), dim3(256), 0, s, xq, wq, y, g, e, q);
-    else if (Cout > 16) hipLaunchKernelGGL((conv_i8_fwd_q_kernel<MT, 2>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e, q);
-    else hipLaunchKernelGGL((conv_i8_fwd_q_kernel<MT, 1>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e, q);
-    CMOOP_HIP(hipGetLastError());
-}
-
-void launch_dense_i8_fwd_q(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
-                           const float* bias, const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out,
-                           int out_bits, float* y, int8_t* codes, int M, int N, int K, int relu, hipStream_t s) {
-    CMOOP_REQUIRE(M >= 0 && N >= 1, "dense_fwd_i8_q: M >= 0 and N >= 1");
-    CMOOP_REQUIRE(K >= 16 && K % 16 == 0, "dense_fwd_i8_q: K must be a multiple of 16");
-    CMOOP_REQUIRE(!rec || (act_bits >= 2 && act_bits <= 8), "dense_fwd_i8_q: activation bits must be in [2, 8]");
-    const I8Req q = i8_req_args(bn_scale, bn_shift, relu_after, rec_out, out_bits, y, codes, N, "dense_fwd_i8_q");
-    if (M == 0) return;
-    i8_check_common(xq, wq, s_w, bias, y, (int64_t)M * K, M, K, N, "dense_fwd_i8_q");
-    const I8Geom g{1, 1, K, 1, 1, N, 1, 1, 0, 0, M, K / 16, K / 16};
-    const I8Epi e{s_w, bias, rec, s_x, rec ? (float)quant_qmax(act_bits) : 0.f, relu, 1};
-    const unsigned gx = (unsigned)cdiv(M, 64);
-    if (N > 32) hipLaunchKernelGGL((dense_i8_fwd_q_kernel<1, 4>), dim3(gx, (unsigned)cdiv(N, 64)), dim3(256), 0, s, xq, wq, y, g, e, q);
-    else if (N > 16) hipLaunchKernelGGL((dense_i8_fwd_q_kernel<1, 2>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e, q);
-    else hipLaunchKernelGGL((dense_i8_fwd_q_kernel<1, 1>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e, q);
-    CMOOP_HIP(hipGetLastError());
-}
-
-void launch_dense_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
-                         const float* bias, float* y, int M, int N, int K, int relu, hipStream_t s) {
-    CMOOP_REQUIRE(M >= 0 && N >= 1, "dense_fwd_i8: M >= 0 and N >= 1");
-    CMOOP_REQUIRE(K >= 16 && K % 16 == 0, "dense_fwd_i8: K must be a multiple of 16");
-    CMOOP_REQUIRE(!rec || (act_bits >= 2 && act_bits <= 8), "dense_fwd_i8: activation bits must be in [2, 8]");
-    if (M == 0) return;
-    i8_check_common(xq, wq, s_w, bias, y, (int64_t)M * K, M, K, N, "dense_fwd_i8");
-    const I8Geom g{1, 1, K, 1, 1, N, 1, 1, 0, 0, M, K / 16, K / 16};
-    const I8Epi e{s_w, bias, rec, s_x, rec ? (float)quant_qmax(act_bits) : 0.f, relu,
-                  (reinterpret_cast<uintptr_t>(y) % 16 == 0 && N % 4 == 0) ? 1 : 0};
-    const unsigned gx = (unsigned)cdiv(M, 64);
-    if (N > 32) hipLaunchKernelGGL((dense_i8_fwd_kernel<1, 4>), dim3(gx, (unsigned)cdiv(N, 64)), dim3(256), 0, s, xq, wq, y, g, e);
-    else if (N > 16) hipLaunchKernelGGL((dense_i8_fwd_kernel<1, 2>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e);
-    else hipLaunchKernelGGL((dense_i8_fwd_kernel<1, 1>), dim3(gx, 1u), dim3(256), 0, s, xq, wq, y, g, e);
+                  (rq || (reinterpret_cast<uintptr_t>(y) % 16 == 0 && Cout % 4 == 0)) ? 1 : 0};
+    const unsigned gx = (unsigned)cdiv64(M, L.conv ? 128 : 64);   // four waves of 16 MT rows
+    const I8Req* qp = rq ? &q : nullptr;
+    if (Cout > 32) i8_launch_nt<4>(L.conv, dim3(gx, (unsigned)cdiv(Cout, 64)), s, xq, wq, y, g, e, qp);
+    else if (Cout > 16) i8_launch_nt<2>(L.conv, dim3(gx, 1u), s, xq, wq, y, g, e, qp);
+    else i8_launch_nt<1>(L.conv, dim3(gx, 1u), s, xq, wq, y, g, e, qp);
     CMOOP_HIP(hipGetLastError());
 }
 

@@ -575,31 +575,34 @@ void launch_fake_quant_act(float* x, int64_t n, int bits, bool tracked, uint32_t
 // ---------------------------------------------------------------------------
 // what the kernels take: Cin a multiple of 16, KS 1 / 3 / 5, stride 1 or the 1x1 stride-2 projection, 127^2 K < 2^31
 bool int8_layer_ok(int Cin, int Cout, int KS, int stride);
-// y [B][OH][OW][Cout] fp32 from xq [B][H][W][Cin] and wq [Cout][KS][KS][Cin] int8 (both 16-byte aligned), s_w / bias [Cout].
-// rec non-null: s_x = quant_scale(rec->r, qmax(act_bits)) read on the device (the tracked scale of the input site), else s_x
-void launch_conv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
-                        const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int KS, int stride, int relu,
-                        hipStream_t s);
-// y [M][N] fp32 from xq [M][K] and wq [N][K] int8; K a multiple of 16, any N
-void launch_dense_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
-                         const float* bias, float* y, int M, int N, int K, int relu, hipStream_t s);
-// The requantising epilogue (include/cmoop.h, "Integer inference: requantising epilogue"): launch_conv_i8_fwd / launch_dense_i8_fwd
-// with the tail of the op fused in.  bn_scale / bn_shift [Cout] (both null: no BatchNorm; one without the other: an error) are
-// what launch_bn_eval_prepare left: t = fma(t, scale[c], shift[c]), then max(t, 0) under relu_after.  rec_out (required) is the
-// record of the site written: y (16-byte aligned) receives the tracked-mode dequantised values at out_bits and codes (required,
-// 4-byte aligned, [rows][Cout]) their codes.  Cout % 4 == 0.  Every element of both outputs of the B (M) rows is written.
-// B == 0 / M == 0: nothing is launched
-void launch_conv_i8_fwd_q(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
-                          const float* bias, const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out,
-                          int out_bits, float* y, int8_t* codes, int B, int H, int W, int Cin, int Cout, int KS, int stride, int relu,
-                          hipStream_t s);
-void launch_dense_i8_fwd_q(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
-                           const float* bias, const float* bn_scale, const float* bn_shift, int relu_after, const ActRange* rec_out,
-                           int out_bits, float* y, int8_t* codes, int M, int N, int K, int relu, hipStream_t s);
+// One matrix-core layer.  conv: y [B][OH][OW][Cout] from xq [B][H][W][Cin] and wq [Cout][KS][KS][Cin].  dense: y [M][N] from
+// xq [M][K] and wq [N][K], K a multiple of 16, any N -- the 1 x 1 image of I8Layer::dense
+struct I8Layer {
+    bool conv;
+    int B, H, W, Cin, Cout, KS, stride;
+    static I8Layer dense(int M, int N, int K) { return I8Layer{false, M, 1, 1, K, N, 1, 1}; }
+};
+// The requantising epilogue (include/cmoop.h, "Integer inference: requantising epilogue"): the tail of the op fused into the
+// launch.  bn_scale / bn_shift [Cout] (both null: no BatchNorm; one without the other: an error) are what launch_bn_eval_prepare
+// left: t = fma(t, scale[c], shift[c]), then max(t, 0) under relu_after.  rec_out (required) is the record of the site written:
+// y (then 16-byte aligned) receives the tracked-mode dequantised values at out_bits and codes (required, 4-byte aligned,
+// [rows][Cout]) their codes.  Cout % 4 == 0.  Every element of both outputs of the B rows is written
+struct I8Requant {
+    const float *bn_scale, *bn_shift;
+    int relu_after;
+    const ActRange* rec_out;
+    int out_bits;
+    int8_t* codes;
+};
+// y fp32 from int8 xq and wq (both 16-byte aligned), s_w / bias [Cout].  rec non-null: s_x = quant_scale(rec->r, qmax(act_bits))
+// read on the device (the tracked scale of the input site), else s_x.  rq null: the plain kernels (refusals under conv_fwd_i8 /
+// dense_fwd_i8), else their ..._q twins (conv_fwd_i8_q / dense_fwd_i8_q).  B == 0: nothing is launched
+void launch_i8_fwd(const I8Layer& L, const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec, int act_bits, const float* s_w,
+                   const float* bias, float* y, int relu, const I8Requant* rq, hipStream_t s);
 // Integer depthwise (include/cmoop.h, "Integer depthwise"): what launch_dwconv_i8_fwd accepts
 bool int8_dw_layer_ok(int C, int KS);
 // y [B][H][W][C] fp32 from xq [B][H][W][C] and wq [KS][KS][C] int8 (both 16-byte aligned), s_w [C] (16-byte aligned): SAME,
-// stride 1, no bias, no activation.  rec_in as launch_conv_i8_fwd's rec.  rec_out null: y = z, the dequantised sums; non-null:
+// stride 1, no bias, no activation.  rec_in as launch_i8_fwd's rec.  rec_out null: y = z, the dequantised sums; non-null:
 // y is z under the tracked quantiser of that record (out_bits) and codes (may be null; 4-byte aligned) receives its codes.
 // Every element of y (and of codes) of the B rows is written.  B == 0: nothing is launched
 void launch_dwconv_i8_fwd(const int8_t* xq, const int8_t* wq, float s_x, const ActRange* rec_in, int act_bits, const float* s_w,

@@ -408,14 +408,14 @@ class Net : public GemmHook {
     // mode is on, NOT per pass: a train step or set_params that later produces a NaN or Inf range or scale is not caught, and
     // the integer passes then return NaN logits without a fault, as the fp32 passes do
     void set_int8(bool on);
-    bool int8_on() const { return int8_on_; }
+    bool int8_on() const { return int8_.on; }
     // Integer depthwise, the second level of integer inference (include/cmoop.h, "Integer depthwise").  on: refused unless
     // set_int8 is on.  While on, every OP_DWCONV of an inference pass is ONE launch that reads the input site's codes and the
     // staged weight codes and writes the output site's quantised fp32 tensor and its codes: the fp32 depthwise launch and the
     // site's quantiser launch are not made.  Train steps never take it.  A plan without a depthwise op accepts it and does
     // nothing.  Turning set_int8, set_quant or set_actquant off turns it off
     void set_int8_depthwise(bool on);
-    bool int8_depthwise_on() const { return int8_dw_on_; }
+    bool int8_depthwise_on() const { return int8_.depthwise; }
     // The requantising epilogue, the third level of integer inference (include/cmoop.h, "Integer inference: requantising
     // epilogue"), independent of the depthwise level.  on: refused unless set_int8 is on.  While on, every op of int8_fused_ops
     // is ONE launch in an inference pass: it applies the op's bias / ReLU, the eval BatchNorm that follows it (whose
@@ -424,7 +424,7 @@ class Net : public GemmHook {
     // never take it.  A plan without such an op accepts it and does nothing.  Turning set_int8, set_quant or set_actquant off
     // turns it off
     void set_int8_fused(bool on);
-    bool int8_fused_on() const { return int8_fused_on_; }
+    bool int8_fused_on() const { return int8_.fused; }
     const NetPlan& plan() const { return plan_; }
     // debug read-out: dims = {H, W, C, materialised, has a gradient, number of acts} of act i; data / grad (either may be null)
     // receive the first B rows as the last step or pass left them (grad: B <= cfg.batch).  Under set_int8_fused an inference pass
@@ -515,13 +515,20 @@ class Net : public GemmHook {
     void ensure_prune_table();                          // ptab_ from the plan and the config's skip_small (host only)
     void require_act_ranges() const;                    // first line of every public inference entry: with set_actquant on, tracked ranges
     void quantise_site(int act, int B, bool train);     // forward's launch(es) for a site the op just wrote
-    const float* fused_bn_prepare(size_t oi);           // set_int8_fused: bn_eval_prepare of the BN fused op oi applies (null: none)
+    // the integer work of op oi in an inference pass, by int8_ and int8_tab_: the op's integer launch (a fused op's
+    // bn_eval_prepare ahead of it), or nothing.  What forward still owes the op:
+    enum Int8Done {
+        INT8_NOT_HERE,     // not integer here: run the fp32 launch
+        INT8_WROTE_OUT,    // wrote the op's output: quantise the site as usual
+        INT8_WROTE_SITE    // wrote the site itself (or a fused producer did, for its BatchNorm): skip the quantiser
+    };
+    Int8Done forward_int8(size_t oi, int B);
+    void int8_levels_off() { int8_ = Int8Levels(); }    // set_quant / set_actquant off and set_int8(false): no level outlives them
     // THE weight stage, from params_ (the average under use_average).  Prune on: its kernels pruned at `sparsity` into wp (zeros:
     // per-row counts, or null).  Quant on and wq given: the kernels of wp, else of params_, quantised into wq (codes / scales or
     // null).  Returns the arena of the last stage that ran, params_ when none did: where forward / backward read kernel tensors
     const float* stage_kernels(double sparsity, float* wp, uint32_t* zeros, float* wq, int8_t* codes, float* scales);
     void refresh_kernels(double sparsity) { kernels_ = stage_kernels(sparsity, wp_, nullptr, wq_, nullptr, nullptr); }
-    bool op_is_int8(size_t oi) const { return oi < op_scale_off_.size() && op_scale_off_[oi] >= 0; }
     ConvBuffers buffers_of(const Op& op) const;   // the slices of the arenas an OP_CONV's launches use
     float* dalloc(size_t floats);
 
@@ -562,18 +569,21 @@ class Net : public GemmHook {
     ActRange *act_rec_ = nullptr, *act_rec_snap_ = nullptr;   // [n_sites] records and their snapshot_params copy, first enabled set_actquant
     uint32_t* act_partials_ = nullptr;  // [ACT_QUANT_MAX_BLOCKS] absmax partials of the site being quantised
     bool act_ranges_ready_ = false, act_ranges_ready_snap_ = false;   // host mirror of "every record has count > 0", and of the snapshot's
-    bool int8_on_ = false;              // set_int8: inference passes take the integer launches
+    // the three levels of integer inference: set_int8 (the matrix-core ops), set_int8_depthwise, set_int8_fused
+    struct Int8Levels { bool on = false, depthwise = false, fused = false; } int8_;
     int8_t* w_codes_ = nullptr;         // [n_params] weight codes (only kernel elements are ever written or read), first set_int8(true)
     float* w_scales_ = nullptr;         // [qtab_.total_channels]
     std::vector<int8_t*> site_codes_;   // per site: [Bmax][per_sample] activation codes
-    std::vector<int64_t> op_scale_off_; // per op: first scale of its kernel tensor when it runs integer, else -1
-    bool int8_dw_on_ = false;           // set_int8_depthwise: inference passes take the integer depthwise launch
-    std::vector<int64_t> dw_scale_off_; // per op: first scale of its kernel tensor when it is a depthwise op, else -1
-    bool int8_fused_on_ = false;        // set_int8_fused: inference passes take the requantising launches
-    // per op under set_int8_fused: 0 nothing, 1 a fused conv / dense op, 2 a BatchNorm a fused op has applied; and for the
-    // former its BN op (-1: none) and the act it writes
-    std::vector<uint8_t> fused_role_;
-    std::vector<int> fused_bn_, fused_act_;
+    // per op, what integer inference can make of it; each level fills its part when it is turned on (the first set_int8 the
+    // matrix-core ops) and the level's flag in int8_ says whether a pass uses it: a fused op runs as a matrix-core op and the
+    // BatchNorm it would apply as itself while the fused level is off, a depthwise op in fp32 while the depthwise level is off
+    enum Int8Role : uint8_t { I8_NONE, I8_MATRIX, I8_DEPTHWISE, I8_FUSED, I8_FUSED_BN /* a BatchNorm a fused op applies */ };
+    struct Int8Entry {
+        Int8Role role = I8_NONE;
+        int64_t scale_off = -1;         // first scale of the op's kernel tensor
+        int bn = -1, site_act = -1;     // I8_FUSED: the BatchNorm op it applies (-1: none) and the act (a site) it writes
+    };
+    std::vector<Int8Entry> int8_tab_;
     std::vector<OpointClass> last_op_classes_;   // store_opoint: empty when the last fit ran without the read-out
     double last_op_summary_[4] = {0, 0, 0, 0};
     float *wgrad_ws_ = nullptr, *wd_ws_ = nullptr, *red_ws_ = nullptr, *splitk_ws_ = nullptr;

@@ -884,139 +884,139 @@ void Net::forward(const float* X, const BatchRows& rows, int B, bool train) {
     const float* kern = kernels_;   // what the caller's weight stage left: the source arena, the pruned or the quantised one
     for (size_t oi = 0; oi < ops_.size(); ++oi) {
         const Op& op = ops_[oi];
-        switch (op.kind) {
-        case OP_CONV1: {
-            fused_stats_blocks_ = 0;
-            const float* bin = train ? batch_in_ : nullptr;   // the batch is rows 0 .. B of the buffer step_body's augment / mixup launch wrote
-            BatchRows first = bin ? BatchRows() : rows;
-            if (!train) first.n_rows = 0;
-            launch_conv1_fwd(bin ? bin : X, first, kern + op.w_off, params_ + op.b_off, acts_[op.out].data, B, T_, F_, op.Cout,
-                             op.KS, op.relu, stream_, (train && op.feeds_bn) ? red_ws_ : nullptr,
-                             (train && op.feeds_bn) ? &fused_stats_blocks_ : nullptr);
-            break;
-        }
-        case OP_CONV: {
-            if (!train && int8_on_ && op_is_int8(oi)) {   // integer inference: the site's codes against the staged weight codes
-                const Act& ia = acts_[op.in];
+        const Int8Done i8 = train ? INT8_NOT_HERE : forward_int8(oi, B);   // integer inference made the op's launch(es), or the fp32 ones follow
+        if (i8 == INT8_NOT_HERE) {
+            switch (op.kind) {
+            case OP_CONV1: {
                 fused_stats_blocks_ = 0;
-                if (int8_fused_on_ && fused_role_[oi] == 1) {   // the requantising epilogue: the site's tensor and codes, one launch
-                    const Act& sa = acts_[fused_act_[oi]];
-                    const float* scale = fused_bn_prepare(oi);
-                    launch_conv_i8_fwd_q(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
-                                         w_scales_ + op_scale_off_[oi], params_ + op.b_off, scale, scale ? scale + op.Cout : nullptr,
-                                         scale ? ops_[fused_bn_[oi]].relu_after : 0, act_rec_ + sa.site, actq_cfg_.bits, sa.data,
-                                         site_codes_[sa.site], B, op.H, op.W, op.Cin, op.Cout, op.KS, op.stride, op.relu, stream_);
-                    continue;                                   // the launch applied the site's quantiser
-                }
-                launch_conv_i8_fwd(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
-                                   w_scales_ + op_scale_off_[oi], params_ + op.b_off, acts_[op.out].data, B, op.H, op.W, op.Cin,
-                                   op.Cout, op.KS, op.stride, op.relu, stream_);
+                const float* bin = train ? batch_in_ : nullptr;   // the batch is rows 0 .. B of the buffer step_body's augment / mixup launch wrote
+                BatchRows first = bin ? BatchRows() : rows;
+                if (!train) first.n_rows = 0;
+                launch_conv1_fwd(bin ? bin : X, first, kern + op.w_off, params_ + op.b_off, acts_[op.out].data, B, T_, F_, op.Cout,
+                                 op.KS, op.relu, stream_, (train && op.feeds_bn) ? red_ws_ : nullptr,
+                                 (train && op.feeds_bn) ? &fused_stats_blocks_ : nullptr);
                 break;
             }
-            GemmEpilogue e;
-            e.mode = op.gemm_mode;
-            e.bias = params_ + op.b_off;
-            e.relu = op.relu;
-            // train && feeds_bn: the BatchNorm batch statistics come with the conv (its epilogue, or the reduction after it)
-            fused_stats_blocks_ = op.conv().forward(acts_[op.in].data, kern + op.w_off, acts_[op.out].data, B, e,
-                                                    train && op.feeds_bn, buffers_of(op), stream_, this);
-            break;
-        }
-        case OP_DWCONV:
-            if (!train && int8_dw_on_) {   // integer depthwise: codes in, the output site's quantised tensor and codes out
-                const Act &ia = acts_[op.in], &oa = acts_[op.out];
-                launch_dwconv_i8_fwd(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
-                                     w_scales_ + dw_scale_off_[oi], act_rec_ + oa.site, actq_cfg_.bits, oa.data, site_codes_[oa.site],
-                                     B, op.H, op.W, op.Cin, op.KS, stream_);
-                continue;                  // the launch applied the site's quantiser
-            }
-            launch_dwconv_fwd(acts_[op.in].data, kern + op.w_off, acts_[op.out].data, B, op.H, op.W, op.Cin, op.KS, 0, nullptr, stream_);
-            break;
-        case OP_DENSE: {
-            if (!train && int8_on_ && op_is_int8(oi)) {
-                const Act& ia = acts_[op.in];
-                if (int8_fused_on_ && fused_role_[oi] == 1) {
-                    const Act& sa = acts_[fused_act_[oi]];
-                    const float* scale = fused_bn_prepare(oi);
-                    launch_dense_i8_fwd_q(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
-                                          w_scales_ + op_scale_off_[oi], params_ + op.b_off, scale, scale ? scale + op.Cout : nullptr,
-                                          scale ? ops_[fused_bn_[oi]].relu_after : 0, act_rec_ + sa.site, actq_cfg_.bits, sa.data,
-                                          site_codes_[sa.site], B, op.Cout, op.Cin, op.relu, stream_);
-                    continue;
-                }
-                launch_dense_i8_fwd(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits,
-                                    w_scales_ + op_scale_off_[oi], params_ + op.b_off, acts_[op.out].data, B, op.Cout, op.Cin,
-                                    op.relu, stream_);
+            case OP_CONV: {
+                GemmEpilogue e;
+                e.mode = op.gemm_mode;
+                e.bias = params_ + op.b_off;
+                e.relu = op.relu;
+                // train && feeds_bn: the BatchNorm batch statistics come with the conv (its epilogue, or the reduction after it)
+                fused_stats_blocks_ = op.conv().forward(acts_[op.in].data, kern + op.w_off, acts_[op.out].data, B, e,
+                                                        train && op.feeds_bn, buffers_of(op), stream_, this);
                 break;
             }
-            const bool drop = train && op.dropout_layer >= 0;
-            const DropoutParams dp = dropout_params(cfg_.dropout);
-            const uint32_t drop_stream = drop ? DropoutParams::stream(op.dropout_layer) : 0u;
-            launch_dense_fwd(acts_[op.in].data, kern + op.w_off, params_ + op.b_off, acts_[op.out].data, B, op.Cout, op.Cin,
-                             op.relu, drop ? 1 : 0, drop ? rng_prefix(seed_, drop_stream, (uint32_t)step_) : 0u, dp.thr,
-                             dp.keep_scale, op.gemm_mode, stream_, drop ? rows.st : nullptr, seed_, drop_stream);
-            break;
-        }
-        case OP_BN: {
-            if (!train && int8_fused_on_ && fused_role_[oi] == 2) continue;   // the producer's requantising epilogue applied it
-            const Act& ia = acts_[op.in];
-            const int64_t M = (int64_t)B * ia.H * ia.W;
-            const int C = op.Cout;
-            float *mean = op.bn_buf, *invstd = mean + C, *scale = invstd + C, *shift = scale + C;
-            if (train) {
-                int nb = fused_stats_blocks_;              // partials the producing conv left, if any
-                fused_stats_blocks_ = 0;
-                if (nb == 0) {                             // first conv on the VALU kernel
-                    nb = colreduce_blocks(M, C);
-                    launch_colstats(ia.data, red_ws_, M, C, nb, stream_);
+            case OP_DWCONV:
+                launch_dwconv_fwd(acts_[op.in].data, kern + op.w_off, acts_[op.out].data, B, op.H, op.W, op.Cin, op.KS, 0, nullptr, stream_);
+                break;
+            case OP_DENSE: {
+                const bool drop = train && op.dropout_layer >= 0;
+                const DropoutParams dp = dropout_params(cfg_.dropout);
+                const uint32_t drop_stream = drop ? DropoutParams::stream(op.dropout_layer) : 0u;
+                launch_dense_fwd(acts_[op.in].data, kern + op.w_off, params_ + op.b_off, acts_[op.out].data, B, op.Cout, op.Cin,
+                                 op.relu, drop ? 1 : 0, drop ? rng_prefix(seed_, drop_stream, (uint32_t)step_) : 0u, dp.thr,
+                                 dp.keep_scale, op.gemm_mode, stream_, drop ? rows.st : nullptr, seed_, drop_stream);
+                break;
+            }
+            case OP_BN: {
+                const Act& ia = acts_[op.in];
+                const int64_t M = (int64_t)B * ia.H * ia.W;
+                const int C = op.Cout;
+                float *mean = op.bn_buf, *invstd = mean + C, *scale = invstd + C, *shift = scale + C;
+                if (train) {
+                    int nb = fused_stats_blocks_;              // partials the producing conv left, if any
+                    fused_stats_blocks_ = 0;
+                    if (nb == 0) {                             // first conv on the VALU kernel
+                        nb = colreduce_blocks(M, C);
+                        launch_colstats(ia.data, red_ws_, M, C, nb, stream_);
+                    }
+                    launch_bn_finalize(red_ws_, nb, M, C, params_ + op.gamma_off, params_ + op.beta_off, params_ + op.mm_off,
+                                       params_ + op.mv_off, mean, invstd, scale, shift, (float)cfg_.bn_eps, (float)cfg_.bn_momentum,
+                                       (float)(1.0 - cfg_.bn_momentum), stream_);
+                } else {
+                    launch_bn_eval_prepare(params_ + op.gamma_off, params_ + op.beta_off, params_ + op.mm_off,
+                                           params_ + op.mv_off, scale, shift, C, (float)cfg_.bn_eps, stream_);
                 }
-                launch_bn_finalize(red_ws_, nb, M, C, params_ + op.gamma_off, params_ + op.beta_off, params_ + op.mm_off,
-                                   params_ + op.mv_off, mean, invstd, scale, shift, (float)cfg_.bn_eps, (float)cfg_.bn_momentum,
-                                   (float)(1.0 - cfg_.bn_momentum), stream_);
-            } else {
-                launch_bn_eval_prepare(params_ + op.gamma_off, params_ + op.beta_off, params_ + op.mm_off,
-                                       params_ + op.mv_off, scale, shift, C, (float)cfg_.bn_eps, stream_);
+                if (op.fuse_pool) {
+                    const Op& pool = ops_[oi + 1];
+                    launch_bn_pool_fwd(ia.data, acts_[pool.out].data, pool.arg, scale, shift, B, ia.H, ia.W, C, op.relu_after, stream_);
+                } else {
+                    launch_scale_shift(ia.data, acts_[op.out].data, scale, shift, M, C, op.relu_after, stream_);
+                }
+                break;
             }
-            if (op.fuse_pool) {
-                const Op& pool = ops_[oi + 1];
-                launch_bn_pool_fwd(ia.data, acts_[pool.out].data, pool.arg, scale, shift, B, ia.H, ia.W, C, op.relu_after, stream_);
-            } else {
-                launch_scale_shift(ia.data, acts_[op.out].data, scale, shift, M, C, op.relu_after, stream_);
+            case OP_POOL: {
+                if (op.fused_into_bn) break;
+                const Act& ia = acts_[op.in];
+                launch_maxpool_fwd(ia.data, acts_[op.out].data, op.arg, B, ia.H, ia.W, ia.C, stream_);
+                break;
             }
-            break;
+            case OP_ADDRELU:
+                launch_add_relu(acts_[op.in].data, acts_[op.in2].data, acts_[op.out].data,
+                                (int64_t)B * acts_[op.out].per_sample(), stream_);
+                break;
+            case OP_GAP: {
+                const Act& ia = acts_[op.in];
+                launch_gap_fwd(ia.data, acts_[op.out].data, B, ia.H * ia.W, ia.C, stream_);
+                break;
+            }
+            }
         }
-        case OP_POOL: {
-            if (op.fused_into_bn) break;
-            const Act& ia = acts_[op.in];
-            launch_maxpool_fwd(ia.data, acts_[op.out].data, op.arg, B, ia.H, ia.W, ia.C, stream_);
-            break;
-        }
-        case OP_ADDRELU:
-            launch_add_relu(acts_[op.in].data, acts_[op.in2].data, acts_[op.out].data,
-                            (int64_t)B * acts_[op.out].per_sample(), stream_);
-            break;
-        case OP_GAP: {
-            const Act& ia = acts_[op.in];
-            launch_gap_fwd(ia.data, acts_[op.out].data, B, ia.H * ia.W, ia.C, stream_);
-            break;
-        }
-        }
-        if (actq_on_) {   // the act this op's launches just wrote: a fused BatchNorm + pool writes the pool's output
+        if (actq_on_ && i8 != INT8_WROTE_SITE) {   // the act this op's launches just wrote: a fused BatchNorm + pool writes the pool's output
             const int written = (op.kind == OP_BN && op.fuse_pool) ? ops_[oi + 1].out : (op.kind == OP_POOL && op.fused_into_bn) ? -1 : op.out;
             if (written >= 0 && acts_[written].site >= 0) quantise_site(written, B, train);
         }
     }
 }
 
-// the eval BatchNorm vectors of the BN a fused op applies, prepared ahead of it: scale (shift follows at + C), or null (T0)
-const float* Net::fused_bn_prepare(size_t oi) {
-    if (fused_bn_[oi] < 0) return nullptr;
-    const Op& bn = ops_[fused_bn_[oi]];
-    const int C = bn.Cout;
-    float *scale = bn.bn_buf + 2 * C, *shift = scale + C;
-    launch_bn_eval_prepare(params_ + bn.gamma_off, params_ + bn.beta_off, params_ + bn.mm_off, params_ + bn.mv_off, scale, shift, C,
-                           (float)cfg_.bn_eps, stream_);
-    return scale;
+Net::Int8Done Net::forward_int8(size_t oi, int B) {
+    if (!int8_.on) return INT8_NOT_HERE;
+    const Int8Entry& t = int8_tab_[oi];
+    const Op& op = ops_[oi];
+    switch (t.role) {
+    case I8_NONE:
+        break;
+    case I8_FUSED_BN:      // the producer's requantising epilogue applied it and wrote its site
+        if (int8_.fused) return INT8_WROTE_SITE;
+        break;
+    case I8_DEPTHWISE:     // codes in, the output site's quantised tensor and codes out
+        if (int8_.depthwise) {
+            const Act &ia = acts_[op.in], &oa = acts_[op.out];
+            launch_dwconv_i8_fwd(site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits, w_scales_ + t.scale_off,
+                                 act_rec_ + oa.site, actq_cfg_.bits, oa.data, site_codes_[oa.site], B, op.H, op.W, op.Cin, op.KS, stream_);
+            return INT8_WROTE_SITE;
+        }
+        break;
+    case I8_MATRIX:
+    case I8_FUSED: {       // the input site's codes against the staged weight codes
+        const Act& ia = acts_[op.in];
+        const I8Layer L = op.kind == OP_CONV ? I8Layer{true, B, op.H, op.W, op.Cin, op.Cout, op.KS, op.stride} : I8Layer::dense(B, op.Cout, op.Cin);
+        const bool fused = t.role == I8_FUSED && int8_.fused;
+        if (op.kind == OP_CONV) fused_stats_blocks_ = 0;   // as the fp32 conv launch leaves it in an inference pass
+        I8Requant rq{};
+        float* y = acts_[op.out].data;
+        if (fused) {       // the requantising epilogue: the site's tensor and codes, one launch
+            const Act& sa = acts_[t.site_act];
+            rq.rec_out = act_rec_ + sa.site;
+            rq.out_bits = actq_cfg_.bits;
+            rq.codes = site_codes_[sa.site];
+            y = sa.data;
+            if (t.bn >= 0) {   // the eval BatchNorm vectors of the BN the op applies, prepared ahead of it
+                const Op& bn = ops_[t.bn];
+                const int C = bn.Cout;
+                float *scale = bn.bn_buf + 2 * C, *shift = scale + C;
+                launch_bn_eval_prepare(params_ + bn.gamma_off, params_ + bn.beta_off, params_ + bn.mm_off, params_ + bn.mv_off, scale, shift, C,
+                                       (float)cfg_.bn_eps, stream_);
+                rq.bn_scale = scale; rq.bn_shift = shift; rq.relu_after = bn.relu_after;
+            }
+        }
+        launch_i8_fwd(L, site_codes_[ia.site], w_codes_ + op.w_off, 0.f, act_rec_ + ia.site, actq_cfg_.bits, w_scales_ + t.scale_off,
+                      params_ + op.b_off, y, op.relu, fused ? &rq : nullptr, stream_);
+        return fused ? INT8_WROTE_SITE : INT8_WROTE_OUT;
+    }
+    }
+    return INT8_NOT_HERE;
 }
 
 void Net::quantise_site(int act, int B, bool train) {
@@ -1025,7 +1025,7 @@ void Net::quantise_site(int act, int B, bool train) {
     // train: batch mode over the B rows of this step, and the site's record advances; inference: the tracked range
     // integer inference: the codes go to the site's int8 buffer as well (the fp32 tensor stays: OP_GAP / OP_DWCONV read it)
     launch_fake_quant_act(a.data, (int64_t)B * (int64_t)a.per_sample(), actq_cfg_.bits, !train, act_partials_, act_rec_ + a.site, m.mf, m.omf,
-                          stream_, (!train && int8_on_) ? site_codes_[a.site] : nullptr);
+                          stream_, (!train && int8_.on) ? site_codes_[a.site] : nullptr);
 }
 
 void Net::require_act_ranges() const {
@@ -1517,7 +1517,7 @@ void Net::set_quant(const QuantCfg* quant) {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running; the table's upload is done
     quant_cfg_ = on ? *quant : QuantCfg();
     quant_on_ = on;
-    if (!on) int8_on_ = int8_dw_on_ = int8_fused_on_ = false;      // integer inference needs the weight codes
+    if (!on) int8_levels_off();                   // integer inference needs the weight codes
     option_changed(on);
 }
 
@@ -1618,14 +1618,14 @@ void Net::set_actquant(const ActQuantCfg* actq) {
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old option is still running
     actq_cfg_ = on ? *actq : ActQuantCfg();
     actq_on_ = on;
-    if (!on) int8_on_ = int8_dw_on_ = int8_fused_on_ = false;      // integer inference needs the sites' codes
+    if (!on) int8_levels_off();                   // integer inference needs the sites' codes
     option_changed(on);
 }
 
 void Net::set_int8(bool on) {
     if (!on) {
         CMOOP_HIP(hipStreamSynchronize(stream_));
-        int8_on_ = int8_dw_on_ = int8_fused_on_ = false;
+        int8_levels_off();
         return;
     }
     // every refusal comes before the first allocation or launch: a refused net is the net it was
@@ -1656,39 +1656,33 @@ void Net::set_int8(bool on) {
         site_codes_.assign((size_t)plan_.n_sites, nullptr);
         for (const Act& a : acts_)
             if (a.site >= 0) site_codes_[a.site] = reinterpret_cast<int8_t*>(dalloc(((size_t)Bmax_ * a.per_sample() + 3) / 4 + 4));
-        op_scale_off_.assign(ops_.size(), -1);
-        for (const Int8Op& o : iops) op_scale_off_[o.op] = o.scale_off;
+        int8_tab_.assign(ops_.size(), Int8Entry());
+        for (const Int8Op& o : iops) int8_tab_[o.op] = Int8Entry{I8_MATRIX, o.scale_off, -1, -1};
     }
-    int8_on_ = true;
+    int8_.on = true;
 }
 
 void Net::set_int8_depthwise(bool on) {
     if (on) {
-        CMOOP_REQUIRE(int8_on_, "int8 depthwise: needs integer inference -- set_int8 first");
+        CMOOP_REQUIRE(int8_.on, "int8 depthwise: needs integer inference -- set_int8 first");
         const std::vector<Int8DwOp> dops = int8_dw_ops(plan_);   // asserts that every depthwise op reads and writes a site
-        dw_scale_off_.assign(ops_.size(), -1);
-        for (const Int8DwOp& o : dops) dw_scale_off_[o.op] = o.scale_off;
+        for (const Int8DwOp& o : dops) int8_tab_[o.op] = Int8Entry{I8_DEPTHWISE, o.scale_off, -1, -1};
     }
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old level is still running
-    int8_dw_on_ = on;
+    int8_.depthwise = on;
 }
 
 void Net::set_int8_fused(bool on) {
     if (on) {
-        CMOOP_REQUIRE(int8_on_, "int8 fused: needs integer inference -- set_int8 first");
+        CMOOP_REQUIRE(int8_.on, "int8 fused: needs integer inference -- set_int8 first");
         const std::vector<Int8FusedOp> fops = int8_fused_ops(plan_);   // asserts the sites, Cout % 4 and the lone reader
-        fused_role_.assign(ops_.size(), 0);
-        fused_bn_.assign(ops_.size(), -1);
-        fused_act_.assign(ops_.size(), -1);
-        for (const Int8FusedOp& o : fops) {
-            fused_role_[o.i8.op] = 1;
-            fused_bn_[o.i8.op] = o.bn;
-            fused_act_[o.i8.op] = o.site_act;
-            if (o.bn >= 0) fused_role_[o.bn] = 2;
+        for (const Int8FusedOp& o : fops) {    // a subset of the matrix-core ops: the scale offset is the one set_int8 wrote
+            int8_tab_[o.i8.op] = Int8Entry{I8_FUSED, o.i8.scale_off, o.bn, o.site_act};
+            if (o.bn >= 0) int8_tab_[o.bn].role = I8_FUSED_BN;
         }
     }
     CMOOP_HIP(hipStreamSynchronize(stream_));     // nothing of the old level is still running
-    int8_fused_on_ = on;
+    int8_.fused = on;
 }
 
 void Net::get_act_ranges(ActRange* host) {
@@ -1704,7 +1698,7 @@ void Net::set_act_ranges(const ActRange* host) {
         CMOOP_REQUIRE(host[i].count >= 0, "set_act_ranges: count must not be negative");
         CMOOP_REQUIRE(!(host[i].r < 0.f) && !(host[i].m_b < 0.f), "set_act_ranges: r and m_b must not be negative");
         // integer inference is on: what set_int8 refused at enabling is refused here as well (nothing is loaded)
-        CMOOP_REQUIRE(!int8_on_ || std::isfinite(host[i].r), "set_act_ranges: the tracked range of site " + std::to_string(i) +
+        CMOOP_REQUIRE(!int8_.on || std::isfinite(host[i].r), "set_act_ranges: the tracked range of site " + std::to_string(i) +
                       " is not finite while integer inference is on (set_int8(false) first)");
         ready = ready && host[i].count > 0;
     }
@@ -1941,7 +1935,7 @@ void Net::run_epoch(const float* X, const int32_t* y, int64_t n_train, int epoch
 
 template <class Source, class Sink> void Net::inference_pass(int64_t n, Source&& source, Sink&& sink) {
     // once per call, on the arena this pass reads; integer inference: with the codes and scales its integer launches take
-    if (int8_on_) kernels_ = stage_kernels(prune_cfg_.sparsity, wp_, nullptr, wq_, w_codes_, w_scales_);
+    if (int8_.on) kernels_ = stage_kernels(prune_cfg_.sparsity, wp_, nullptr, wq_, w_codes_, w_scales_);
     else refresh_kernels(prune_cfg_.sparsity);
     for (int64_t s = 0; s < n; s += cfg_.eval_batch) {
         const int B = (int)std::min<int64_t>(cfg_.eval_batch, n - s);

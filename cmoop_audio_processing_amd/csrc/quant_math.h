@@ -29,4 +29,9 @@ __device__ __forceinline__ void quant_element(float w, float s, bool live, float
     wq = x == x ? x : __uint_as_float(QUANT_CANONICAL_NAN);
 }
 
+// four codes as one word, code 0 in the lowest byte: what a lane that owns four consecutive channels stores
+__device__ __forceinline__ uint32_t quant_pack4(const int q[4]) {
+    return ((uint32_t)q[0] & 0xFFu) | (((uint32_t)q[1] & 0xFFu) << 8) | (((uint32_t)q[2] & 0xFFu) << 16) | (((uint32_t)q[3] & 0xFFu) << 24);
+}
+
 }  // namespace cmoop

@@ -27,6 +27,7 @@ import numpy as np
 from . import genes as G
 from .evaluator import EvalConfig
 from .frontend import FrontendConfig, PcenConfig, log_mel_stream
+from .quant import Int8Levels
 from .resample import to_rate
 
 _OBJECTIVE_KEYS = ("acc", "size_mb", "fpr", "epochs_run")
@@ -269,19 +270,18 @@ class TrainedModel:
                        params=z["params"].copy(), objectives=obj, frontend=fe, mean=mean, scale=scale,
                        thresholds=thresholds, **quant, **prune, **act)
 
-    def _require_int8(self, int8: bool = True, int8_depthwise: bool = False, int8_fused: bool = False) -> None:
-        """ValueError naming what a model lacks for integer inference, or ``int8_depthwise`` / ``int8_fused`` without ``int8``
-        (host only: before any session opens)."""
-        if int8_depthwise and not int8:
-            raise ValueError("int8_depthwise=True needs int8=True: integer depthwise is a level of integer inference")
-        if int8_fused and not int8:
-            raise ValueError("int8_fused=True needs int8=True: the requantising epilogue is a level of integer inference")
-        if not int8:
-            return
+    def _require_int8(self, int8: bool = True, int8_depthwise: bool = False, int8_fused: bool = False) -> Int8Levels:
+        """The level keywords of a public entry as one checked record (``_open`` takes it).  ValueError naming what a model
+        lacks for integer inference, or ``int8_depthwise`` / ``int8_fused`` without ``int8`` (host only: before any session
+        opens)."""
+        levels = Int8Levels.of(int8, int8_depthwise, int8_fused, (
+            "int8_depthwise=True needs int8=True: integer depthwise is a level of integer inference",
+            "int8_fused=True needs int8=True: the requantising epilogue is a level of integer inference"))
         missing = [name for name, v in (("quant_codes (train it under EvalConfig.quant)", self.quant_codes),
                                         ("act_ranges (train it under EvalConfig.act_quant)", self.act_ranges)) if v is None]
-        if missing:
+        if levels.on and missing:
             raise ValueError("int8=True needs a full-int8 model; this one carries no " + " and no ".join(missing))
+        return levels
 
     def session(self, config: Optional[EvalConfig] = None, int8: bool = False, int8_depthwise: bool = False,
                 int8_fused: bool = False):
@@ -295,8 +295,11 @@ class TrainedModel:
         depthwise=True)``): it needs ``int8=True`` (ValueError otherwise, before the session opens), needs nothing more of the
         model, and has no effect on an A / B model.  ``int8_fused``: the third level (``NetSession.set_int8(True, fused=True)``),
         under the same terms; its logits are those of the levels it is added to, bit for bit."""
+        return self._open(config, self._require_int8(int8, int8_depthwise, int8_fused))
+
+    def _open(self, config: Optional[EvalConfig], levels: Int8Levels):
+        """``session`` behind the public boundary: ``levels`` is what ``_require_int8`` returned."""
         from .session import NetSession
-        self._require_int8(int8, int8_depthwise, int8_fused)
         if config is None:
             config = EvalConfig(variant=self.variant, classes=self.classes)
         if config.variant != self.variant or int(config.classes) != self.classes:
@@ -309,10 +312,10 @@ class TrainedModel:
                 from .quant import ActQuantConfig
                 net.set_act_quant(ActQuantConfig(bits=self.act_bits, momentum=self.act_momentum))
                 net.set_act_ranges(self.act_ranges)
-            if int8:
+            if levels.on:
                 from .quant import QuantConfig
                 net.set_quant(QuantConfig(bits=self.quant_bits, objective=False))
-                net.set_int8(True, depthwise=bool(int8_depthwise), fused=bool(int8_fused))
+                net.set_int8(True, depthwise=levels.depthwise, fused=levels.fused)
         except Exception:
             net.close()
             raise
@@ -324,7 +327,7 @@ class TrainedModel:
         ``NetSession.predict_logits``; what ``PopulationEvaluator.set_teacher`` trains candidates against.  ``int8``: the
         integer-inference logits (``session(config, int8=True)``), ``int8_depthwise``: with its second level, ``int8_fused``: with
         its third."""
-        with self.session(config, int8=int8, int8_depthwise=int8_depthwise, int8_fused=int8_fused) as net:
+        with self._open(config, self._require_int8(int8, int8_depthwise, int8_fused)) as net:
             return net.predict_logits(X)
 
     def int8_report(self, X, y=None, config: Optional[EvalConfig] = None, depthwise: bool = False,
@@ -337,12 +340,12 @@ class TrainedModel:
         third level on, and the report gains "int8_fused_ops" (how many ops took the requantising epilogue).  A reported
         figure, no gate."""
         import torch
-        self._require_int8()
-        with self.session(config, int8=True, int8_depthwise=depthwise, int8_fused=fused) as net:
+        levels = self._require_int8(True, depthwise, fused)
+        with self._open(config, levels) as net:
             zi = net.predict_logits(X)
             n_ops = len(net.int8_ops())
-            n_dw = len(net.int8_dw_ops()) if depthwise else 0
-            n_fused = len(net.int8_fused_ops()) if fused else 0
+            n_dw = len(net.int8_dw_ops()) if levels.depthwise else 0
+            n_fused = len(net.int8_fused_ops()) if levels.fused else 0
             net.set_int8(False)
             zf = net.predict_logits(X)
         n = int(zi.shape[0])
@@ -370,13 +373,13 @@ class StreamScorer:
                  int8_depthwise: bool = False, int8_fused: bool = False):
         if int(hop_frames) < 1:
             raise ValueError("hop_frames must be at least 1")
-        model._require_int8(int8, int8_depthwise, int8_fused)
+        levels = model._require_int8(int8, int8_depthwise, int8_fused)
         self.model, self.hop_frames = model, int(hop_frames)
         self.frontend = model.frontend if model.frontend is not None else FrontendConfig()
         if int(self.frontend.n_mels) != model.F:
             raise ValueError(f"the front end gives {self.frontend.n_mels} mel bands, the model reads F = {model.F}")
         # int8: the windows are scored by integer inference (int8_depthwise / int8_fused: with its second / third level)
-        self.net = model.session(config, int8=int8, int8_depthwise=int8_depthwise, int8_fused=int8_fused)
+        self.net = model._open(config, levels)
 
     def close(self):
         self.net.close()

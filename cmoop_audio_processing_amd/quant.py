@@ -32,7 +32,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-from typing import List, Tuple
+from typing import List, NamedTuple, Tuple
 
 import numpy as np
 
@@ -251,17 +251,42 @@ def int8_ops(hparams, variant, classes: int, T: int, F: int) -> List[Tuple[int, 
     return [(i, op[1], op[3]) for i, op in enumerate(ops) if op[0] in ("conv", "dense") and op[1] in sites]
 
 
-def _int8_rows(rows, n):
-    return [dict(zip(INT8_OP_FIELDS, (int(v) for v in r))) for r in rows[:n]]
+class Int8Levels(NamedTuple):
+    """The three levels of integer inference as one value: integer inference itself, its depthwise level, its requantising
+    epilogue.  THE place of "a level needs ``on``"."""
+    on: bool = False
+    depthwise: bool = False
+    fused: bool = False
+
+    @classmethod
+    def of(cls, on, depthwise, fused, refusals) -> "Int8Levels":
+        """The checked record.  ``refusals``: the caller's two ValueError texts, in its own keywords -- (depthwise without on,
+        fused without on)."""
+        if depthwise and not on:
+            raise ValueError(refusals[0])
+        if fused and not on:
+            raise ValueError(refusals[1])
+        return cls(bool(on), bool(depthwise), bool(fused))
+
+
+def _plan_rows(fields, rows, n):
+    """The first ``n`` plan rows of any level as dicts keyed by ``fields`` (a row's trailing zero column has no field)."""
+    return [dict(zip(fields, (int(v) for v in r))) for r in rows[:n]]
+
+
+def _c_plan_ops(entry: str, fields, width: int, gene, variant: int, classes: int, T: int, F: int, cap: int):
+    """``cmoop_int8_ops`` / ``cmoop_int8_dw_ops`` / ``cmoop_int8_fused_ops`` by name: the plan rows of a gene (``width`` int64
+    columns each), keyed by ``fields``."""
+    g = (C.c_int32 * 6)(*(int(v) for v in gene))
+    rows, n = np.zeros((max(int(cap), 1), int(width)), np.int64), C.c_int32()
+    _lib.check(getattr(_lib.lib(), entry)(g, C.c_int32(int(variant)), C.c_int32(int(classes)), C.c_int32(int(T)), C.c_int32(int(F)),
+                                          _lib.ptr(rows), C.c_int32(int(cap)), C.byref(n)))
+    return _plan_rows(fields, rows, n.value)
 
 
 def c_int8_ops(gene, variant: int, classes: int, T: int, F: int):
     """``cmoop_int8_ops``: a list of dicts keyed by ``INT8_OP_FIELDS`` (kind 0: conv, 1: dense)."""
-    g, cap = (C.c_int32 * 6)(*(int(v) for v in gene)), 64
-    rows, n = np.zeros((cap, 16), np.int64), C.c_int32()
-    _lib.check(_lib.lib().cmoop_int8_ops(g, C.c_int32(int(variant)), C.c_int32(int(classes)), C.c_int32(int(T)), C.c_int32(int(F)),
-                                         _lib.ptr(rows), C.c_int32(cap), C.byref(n)))
-    return _int8_rows(rows, n.value)
+    return _c_plan_ops("cmoop_int8_ops", INT8_OP_FIELDS, 16, gene, variant, classes, T, F, 64)
 
 
 def _dev_ptr(t):
@@ -390,18 +415,10 @@ def int8_fused_ops(hparams, variant, classes: int, T: int, F: int) -> List[Tuple
     return out
 
 
-def _int8_fused_rows(rows, n):
-    return [dict(zip(INT8_FUSED_OP_FIELDS, (int(v) for v in r))) for r in rows[:n]]
-
-
 def c_int8_fused_ops(gene, variant: int, classes: int, T: int, F: int, cap: int = 64):
     """``cmoop_int8_fused_ops``: a list of dicts keyed by ``INT8_FUSED_OP_FIELDS`` (``bn_op`` -1: the op's own output is the
     site)."""
-    g = (C.c_int32 * 6)(*(int(v) for v in gene))
-    rows, n = np.zeros((max(int(cap), 1), 20), np.int64), C.c_int32()
-    _lib.check(_lib.lib().cmoop_int8_fused_ops(g, C.c_int32(int(variant)), C.c_int32(int(classes)), C.c_int32(int(T)), C.c_int32(int(F)),
-                                               _lib.ptr(rows), C.c_int32(int(cap)), C.byref(n)))
-    return _int8_fused_rows(rows, n.value)
+    return _c_plan_ops("cmoop_int8_fused_ops", INT8_FUSED_OP_FIELDS, 20, gene, variant, classes, T, F, cap)
 
 
 def _i8_q_args(xq, wq, s_x, s_w, bias, bn_scale, bn_shift, ints, a_out, y, codes):
@@ -512,17 +529,9 @@ def int8_dw_ops(hparams, variant, classes: int, T: int, F: int) -> List[Tuple[in
     return [(i, op[1], op[3]) for i, op in enumerate(ops) if op[0] == "dwconv"]
 
 
-def _int8_dw_rows(rows, n):
-    return [dict(zip(INT8_DW_OP_FIELDS, (int(v) for v in r))) for r in rows[:n]]
-
-
 def c_int8_dw_ops(gene, variant: int, classes: int, T: int, F: int, cap: int = 64):
     """``cmoop_int8_dw_ops``: a list of dicts keyed by ``INT8_DW_OP_FIELDS`` (kind 2, b_off -1)."""
-    g = (C.c_int32 * 6)(*(int(v) for v in gene))
-    rows, n = np.zeros((max(int(cap), 1), 16), np.int64), C.c_int32()
-    _lib.check(_lib.lib().cmoop_int8_dw_ops(g, C.c_int32(int(variant)), C.c_int32(int(classes)), C.c_int32(int(T)), C.c_int32(int(F)),
-                                            _lib.ptr(rows), C.c_int32(int(cap)), C.byref(n)))
-    return _int8_dw_rows(rows, n.value)
+    return _c_plan_ops("cmoop_int8_dw_ops", INT8_DW_OP_FIELDS, 16, gene, variant, classes, T, F, cap)
 
 
 def _dwconv_i8_args(xq, wq, s_x, s_w, B, H, W, Cn, KS, out_bits, a_out, y, codes):

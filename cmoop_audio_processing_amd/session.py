@@ -194,9 +194,7 @@ class NetSession:
         plain fit it is post-training quantisation."""
         self._set("cmoop_net_set_quant", None if quant is None else quant.check()._struct())
         self.quant = quant if quant is not None and quant.enabled else None
-        self.int8 = self.int8 and self.quant is not None       # the net drops integer inference with its weight codes
-        self.int8_depthwise = self.int8_depthwise and self.int8
-        self.int8_fused = self.int8_fused and self.int8
+        self._int8_needs(self.quant)                    # the net drops integer inference with its weight codes
 
     def get_quantized(self):
         """(wq_params float32 [n_params]: kernels dequantised, every other element a copy; codes int8 [n_params]: 0 outside
@@ -239,9 +237,16 @@ class NetSession:
         some.  ``get_state`` / ``set_state`` do not carry the ranges: ``get_act_ranges`` / ``set_act_ranges`` do."""
         self._set("cmoop_net_set_actquant", None if act_quant is None else act_quant.check()._struct())
         self.act_quant = act_quant if act_quant is not None and act_quant.enabled else None
-        self.int8 = self.int8 and self.act_quant is not None   # ... and with its activation codes
-        self.int8_depthwise = self.int8_depthwise and self.int8
-        self.int8_fused = self.int8_fused and self.int8
+        self._int8_needs(self.act_quant)                # ... and with its activation codes
+
+    def _int8_needs(self, option) -> None:
+        """Dropping ``quant`` or ``act_quant`` drops every level of integer inference in the net: the mirrors follow."""
+        if option is None:
+            self.int8 = self.int8_depthwise = self.int8_fused = False
+
+    # set_int8's refusals of a level without `on` (quant.Int8Levels.of)
+    _INT8_LEVEL_REFUSALS = ("depthwise=True needs on=True: integer depthwise is a level of integer inference",
+                            "fused=True needs on=True: the requantising epilogue is a level of integer inference")
 
     def set_int8(self, on, depthwise: bool = False, fused: bool = False) -> None:
         """Integer inference (``cmoop_net_set_int8``) of every following ``evaluate`` / ``predict_*`` call: every conv and dense
@@ -256,51 +261,49 @@ class NetSession:
         ``int8_fused_ops`` is one launch that also applies the eval BatchNorm after it and the quantiser of the site it reaches
         (``quant.conv_i8_q_ref`` / ``dense_i8_q_ref``), with the bytes of the launches it replaces.  False is the default; a
         net without a fusible op accepts it and nothing changes."""
-        if depthwise and not on:
-            raise ValueError("depthwise=True needs on=True: integer depthwise is a level of integer inference")
-        if fused and not on:
-            raise ValueError("fused=True needs on=True: the requantising epilogue is a level of integer inference")
+        from .quant import Int8Levels
+        lv = Int8Levels.of(on, depthwise, fused, self._INT8_LEVEL_REFUSALS)
         L = _lib.lib()
-        if not on or not fused:
+        if not lv.fused:
             _lib.check(L.cmoop_net_set_int8_fused(self._h, C.c_int32(0)))
             self.int8_fused = False
-        if not on or not depthwise:                      # the level goes first: turning integer inference off drops it anyway
+        if not lv.depthwise:                             # the level goes first: turning integer inference off drops it anyway
             _lib.check(L.cmoop_net_set_int8_depthwise(self._h, C.c_int32(0)))
             self.int8_depthwise = False
-        _lib.check(L.cmoop_net_set_int8(self._h, C.c_int32(int(bool(on)))))
-        self.int8 = bool(on)
-        if depthwise:
+        _lib.check(L.cmoop_net_set_int8(self._h, C.c_int32(int(lv.on))))
+        self.int8 = lv.on
+        if lv.depthwise:
             _lib.check(L.cmoop_net_set_int8_depthwise(self._h, C.c_int32(1)))
             self.int8_depthwise = True
-        if fused:
+        if lv.fused:
             _lib.check(L.cmoop_net_set_int8_fused(self._h, C.c_int32(1)))
             self.int8_fused = True
 
     def int8_ops(self):
         """``cmoop_net_int8_ops``: the ops that run integer under ``set_int8``, dicts keyed by ``quant.INT8_OP_FIELDS``."""
-        from . import quant as Q
-        cap = 64
-        rows, n = np.zeros((cap, 16), np.int64), C.c_int32()
-        _lib.check(_lib.lib().cmoop_net_int8_ops(self._h, _lib.ptr(rows), C.c_int32(cap), C.byref(n)))
-        return Q._int8_rows(rows, n.value)
+        from .quant import INT8_OP_FIELDS
+        return self._plan_rows("cmoop_net_int8_ops", INT8_OP_FIELDS, 16)
 
     def int8_dw_ops(self):
         """``cmoop_net_int8_dw_ops``: the depthwise ops that run integer under ``set_int8(True, depthwise=True)``, dicts keyed
         by ``quant.INT8_DW_OP_FIELDS``; empty for variants A / B."""
-        from . import quant as Q
-        cap = 64
-        rows, n = np.zeros((cap, 16), np.int64), C.c_int32()
-        _lib.check(_lib.lib().cmoop_net_int8_dw_ops(self._h, _lib.ptr(rows), C.c_int32(cap), C.byref(n)))
-        return Q._int8_dw_rows(rows, n.value)
+        from .quant import INT8_DW_OP_FIELDS
+        return self._plan_rows("cmoop_net_int8_dw_ops", INT8_DW_OP_FIELDS, 16)
 
     def int8_fused_ops(self):
         """``cmoop_net_int8_fused_ops``: the ops that take the requantising epilogue under ``set_int8(True, fused=True)``, dicts
         keyed by ``quant.INT8_FUSED_OP_FIELDS``."""
+        from .quant import INT8_FUSED_OP_FIELDS
+        return self._plan_rows("cmoop_net_int8_fused_ops", INT8_FUSED_OP_FIELDS, 20)
+
+    def _plan_rows(self, entry: str, fields, width: int):
+        """The rows of this net's plan at one level of integer inference (``cmoop_net_int8*_ops`` by name; ``width`` int64
+        columns each), keyed by ``fields``."""
         from . import quant as Q
         cap = 64
-        rows, n = np.zeros((cap, 20), np.int64), C.c_int32()
-        _lib.check(_lib.lib().cmoop_net_int8_fused_ops(self._h, _lib.ptr(rows), C.c_int32(cap), C.byref(n)))
-        return Q._int8_fused_rows(rows, n.value)
+        rows, n = np.zeros((cap, width), np.int64), C.c_int32()
+        _lib.check(getattr(_lib.lib(), entry)(self._h, _lib.ptr(rows), C.c_int32(cap), C.byref(n)))
+        return Q._plan_rows(fields, rows, n.value)
 
     def _n_sites(self) -> int:
         n = C.c_int32()                                  # the net's own count: the session cannot disagree with what it wraps
